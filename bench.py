@@ -18,7 +18,10 @@ At --gpus N the 60 000 images are sharded over N ranks (strong scaling) and the 
 partials are summed by an RCCL all-reduce inside the library; the control plane (unique-id
 broadcast, barriers, max-over-ranks timing) uses torch.distributed.
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md section "Measurement").
+Prints ONE JSON line on rank 0 (see README / DESIGN.md section "Measurement").  A plain run sets up, warms up, times
+--steps bond updates and prints the headline figure; everything else the line can carry (per-kernel and roofline
+figures, the literal-order rate, the centre bonds and the 8(d) workload, the CPU baseline, the second transport at
+--gpus N > 1) is measured with --full.  --dump-outputs DIR writes what the last timed bond update returned as .npy files.
 """
 import argparse
 import json
@@ -255,21 +258,21 @@ def free_port():
 
 def second_transport_leg(transport, port, rank, local_rank, world, timeout_s):
     """This rank's share of the SECOND transport's measurement: the same command as a child process (own rendezvous on `port`, the same
-    RANK / LOCAL_RANK / WORLD_SIZE), --plain.  Returns (json line of the child's rank 0 or None, error text or None).  A child that dies,
-    hangs past `timeout_s` or prints nothing costs an error string, never the parent's line."""
+    RANK / LOCAL_RANK / WORLD_SIZE), --full --plain, no output dump.  Returns (json line of the child's rank 0 or None, error text or None).
+    A child that dies, hangs past `timeout_s` or prints nothing costs an error string, never the parent's line."""
     import subprocess
     argv, skip = [], False
     for a in sys.argv[1:]:
         if skip:
             skip = False
             continue
-        if a in ("--allreduce",):
+        if a in ("--allreduce", "--dump-outputs"):
             skip = True
             continue
-        if a.startswith("--allreduce=") or a in ("--leg", "--plain", "--no-cpu-baseline"):
+        if a.startswith(("--allreduce=", "--dump-outputs=")) or a in ("--leg", "--full", "--plain", "--no-cpu-baseline"):
             continue
         argv.append(a)
-    cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--allreduce", transport, "--leg", "--plain", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--allreduce", transport, "--leg", "--full", "--plain", "--no-cpu-baseline"]
     env = dict(os.environ)
     env.update(RANK=str(rank), LOCAL_RANK=str(local_rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     for k in ("TORCHELASTIC_USE_AGENT_STORE", "TORCHELASTIC_RUN_ID", "TORCHELASTIC_RESTART_COUNT", "TORCHELASTIC_MAX_RESTARTS", "GROUP_RANK", "ROLE_RANK"):
@@ -294,9 +297,30 @@ def n1_reference(N, maxm, NT, dtype):
         except (OSError, ValueError, IndexError):
             continue
         c = d.get("config", {})
-        if d.get("n_gpus") == 1 and d.get("dtype") == dtype and c.get("sites") == N and c.get("maxm") == maxm and c.get("global_images") == NT:
+        if d.get("n_gpus") == 1 and d.get("dtype") == dtype and c.get("sites") == N and c.get("maxm") == maxm and c.get("global_images") == NT \
+                and "gradient_phase_ms" in d:                    # a line of a plain run carries the headline figure only
             return d, "profiles/" + os.path.basename(f)
     return None, None
+
+
+REPORT_FIELDS = ("bond", "half", "c", "mL", "mR", "label_on_B", "origm", "newm", "truncerr", "norm_newB", "diff", "cost", "reg_cost",
+                 "ncorrect", "cost_old", "cost_cg", "reg_cost_cg", "norm_oB")
+DUMP_SAMPLE = 1 << 20                                            # values kept of a site tensor larger than this (fixed, seeded sample)
+
+
+def dump_outputs(d, ts, rep):
+    """what the last timed bond update handed back, as d/<name>.npy in float64: its report (scalars in REPORT_FIELDS order, the
+    per-label costs, the CG trace) and the two site tensors it rewrote, W.A(b) and W.A(b+1) in Fortran order (at most 2 x 8 MB)"""
+    os.makedirs(d, exist_ok=True)
+    b = rep["bond"]
+    arrays = {"report": [float(rep[k]) for k in REPORT_FIELDS], "label_cost": rep["label_cost"],
+              "cg_cost": rep["cg"]["cost"], "cg_rnorm": rep["cg"]["rnorm"], "cg_pAp": rep["cg"]["pAp"], "cg_alpha": rep["cg"]["alpha"],
+              "site_left": ts.get_site(b).ravel(order="F"), "site_right": ts.get_site(b + 1).ravel(order="F")}
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def read_prof(ts):
@@ -338,8 +362,14 @@ def main():
                     "training per label, replicas only) for this label instead of the fixedL sweep")
     ap.add_argument("--no-extras", action="store_true", help="skip the two secondary measurements of the default line: the two Label-on-B centre bonds "
                     "(centre_bond_ms) and the SURVEY.md 8(d) workload (value_8d)")
-    ap.add_argument("--plain", action="store_true", help="main window + breakdown steps only (no literal-order, unfused-forward, centre-bond or 8(d) "
-                    "measurements): what the profiler runs of tools/*.sh use, so that the last bond updates of the run are ordinary ones")
+    ap.add_argument("--full", action="store_true", help="measure everything the line can carry beside the headline figure: HIP-event timing of "
+                    "the matrix-pipe kernels in the timed window, breakdown steps, roofline figures, literal-order rate, unfused forward pass, "
+                    "centre bonds and 8(d) workload, CPU baseline, and at --gpus N > 1 the second transport (default: the headline figure only; "
+                    "--no-cpu-baseline, --cpu-baseline-full, --literal-steps, --no-extras, --plain and --no-second-transport act on these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned (its report and "
+                    "the two site tensors it rewrote) as DIR/<name>.npy, float64")
+    ap.add_argument("--plain", action="store_true", help="with --full: main window + breakdown steps only (no literal-order, unfused-forward, centre-bond "
+                    "or 8(d) measurements): what the profiler runs of tools/*.sh use, so that the last bond updates of the run are ordinary ones")
     ap.add_argument("--env-budget-gb", type=float, default=0.0, help="cap on the environment slabs held in HBM; what does not fit spills to host memory "
                     "(tnml_set_option env_budget_mb; 0: everything resident, the headline configuration)")
     ap.add_argument("--allreduce", default="rccl", choices=["rccl", "oneshot"], help="transport of the library's collectives at --gpus N > 1: RCCL (ncclAllReduce / "
@@ -393,7 +423,7 @@ def main():
             assert [g[0] for g in gathered] == list(range(world))
         # the second transport's leg (a child process per rank with a rendezvous of its own) runs over the same control plane
         second = None
-        if world > 1 and not args.leg and not args.no_second_transport:
+        if world > 1 and args.full and not args.leg and not args.no_second_transport:
             other = "oneshot" if args.allreduce == "rccl" else "rccl"
             port = [free_port() if rank == 0 else None]
             dist.broadcast_object_list(port, src=0)
@@ -489,6 +519,40 @@ def main():
             inflight -= 1
 
     full_sweeps = args.steps >= 2 * (N - 1)
+
+    def headline(elapsed, timed):
+        """the entries every line carries: the headline figure and the workload it was measured on"""
+        m_avg = float(np.mean([0.5 * (r["mL"] + r["mR"]) for r in timed])) if timed else 0.0
+        return {
+            "metric": "two-site bond updates/sec" if not single else "two-site bond updates/sec (per-label variant, label %d)" % args.single_label,
+            "value": args.steps / elapsed,
+            "unit": "bond updates/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / args.steps,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": args.dtype,
+            "data": "synthetic",
+            "parity": "unpinned-oracle (no reference-held vectors exist and ITensor is absent: GPU results are checked against "
+                      "oracle/, a line-cited restatement of fixedL.cc cross-checked by an independent numpy restatement)",
+            "config": {"workload": "fixedL N=%d, maxm=%d, %d images (%s), Npass=%d, lambda=%g, minm=%d, "
+                                   "%s; %s; timed bonds %d..%d (%s, m=%.0f)" % (N, maxm, NT, baseline_config_name(N, maxm, NT, world, args.dtype), npass, lam, minm,
+                                                                               {"f64": "fp64 throughout", "f64_e32": "fp64 MFMA over fp32-stored environments", "f32": "fp32 study mode",
+                                                                                "bf16x3": "fp32 storage, forward feature GEMM on bf16 MFMA with hi + lo operands (study mode)",
+                                                                                "bf16": "fp32 storage, forward feature GEMM on bf16 MFMA (study mode)"}[args.dtype],
+                                                                               "random-init W at m=maxm" if args.workload == "default" else "SURVEY 8(d): after one warm-up sweep from the random-init W",
+                                                                               timed[0]["bond"] if timed else 0,
+                                                                               timed[-1]["bond"] if timed else 0,
+                                                                               "whole sweeps" if full_sweeps else
+                                                                               ("consecutive interior bonds, Label-carrying shiftE on each" if args.workload == "default" else "consecutive interior bonds of the second sweep"),
+                                                                               m_avg),
+                       "global_images": NT, "sites": N, "maxm": maxm, "parallelism": "dp%d (image sharding + %s)" % (world, "RCCL all-reduce" if main_tr == "rccl" or world == 1 else "one-shot all-reduce over IPC-mapped regions"),
+                       "rccl_ranks": comm_ranks},
+        }
+
     if args.workload == "8d":
         for _ in range(2 * (N - 1)):                             # the warm-up sweep of SURVEY.md 8(d): bonds grow to their trained size
             step()
@@ -508,7 +572,7 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # timed region: HIP events only around the roofline kernel (two event records per launch cost host
+    # timed region: with --full, HIP events only around the roofline kernel (two event records per launch cost host
     # time; timing all ~70 launches of a bond update would lower the very throughput being measured)
     # (the split is one event pair per bond update around the whole of svd_split: it costs nothing and, unlike the other classes, its time
     # depends on WHICH bonds are timed -- the rank-adaptive tridiagonalisation forms ~131 reflectors on bonds whose neighbours are still
@@ -516,8 +580,9 @@ def main():
     # (the gradient GEMM and the shift are timed live as well -- roofline_kernels -- where a bond update is GPU-bound; on toy workloads, where
     # it is bound by the host's launch rate, ten more event records per bond update would move the figure being measured)
     live = "fgemm_fwd,fwd_fused,fwd_res,svd" + (",bgemm,grad_quad,fgemm_shift" if (hi - lo) * maxm * maxm >= 1e8 else "")
-    ts.profile(os.environ.get("TNML_BENCH_NOPROF", "0") != "1", only=live)
-    ts.profile_reset()
+    if args.full:
+        ts.profile(os.environ.get("TNML_BENCH_NOPROF", "0") != "1", only=live)
+        ts.profile_reset()
     # no cyclic garbage collection inside the timed region: a generation-2 pass over this process's heap takes ~40 ms -- the time of
     # 30 bond updates of an 8-GPU shard -- and where it lands depends on the allocation count (seen as one 40 ms step in an otherwise
     # flat 1.4 ms series, profiles/r03_gc_pause_in_timed_region.txt)
@@ -525,8 +590,9 @@ def main():
     gc.collect()
     gc.disable()
     sync()
-    coll0 = ts.collective_stats()
-    split0 = ts.split_stats()
+    if args.full:
+        coll0 = ts.collective_stats()
+        split0 = ts.split_stats()
     t0 = time.perf_counter()
     step_marks = []
     for _ in range(args.steps):
@@ -536,13 +602,29 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    coll1 = ts.collective_stats()
-    split1 = ts.split_stats()
     if step_marks and rank == 0:
         print("host time at the end of each timed step (ms):", " ".join("%.2f" % (1e3 * t) for t in step_marks), "| total %.2f" % (1e3 * elapsed), file=sys.stderr)
+    n_timed_end = len(reports)                                   # sync() has drained the pipeline: every timed report is in
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ts, reports[n_timed_end - 1])
+    if not args.full:
+        if world > 1:
+            t = torch.tensor([elapsed], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t[0])
+        if rank == 0:
+            out = headline(elapsed, reports[n_timed_end - args.steps:n_timed_end])
+            out["last_cost_per_image"] = reports[n_timed_end - 1]["cost"] / NT
+            print(json.dumps(out))
+        ts.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    coll1 = ts.collective_stats()
+    split1 = ts.split_stats()
     ts.profile(False)
     prof = read_prof(ts)
-    n_timed_end = len(reports)                                   # sync() has drained the pipeline: every timed report is in
     # untimed extra steps with every kernel class timed: the per-class breakdown.  After whole sweeps the next bonds are the
     # chain start (bond dimensions 2, 4, 8, ...): move on to interior bonds first
     if full_sweeps and N >= 64:
@@ -688,34 +770,8 @@ def main():
         grad_classes = ("fgemm_fwd", "fwd_fused", "labeldot", "p_update", "bgemm", "slab_reduce", "zprime", "allreduce")
         tr_fg, src_fg = pmc_traffic("fwd_fused" if fused else "fgemm_fwd") if args.dtype == "f64" and maxm == 120 and NT == 60000 and world == 1 else (None, None)
         shortcuts_on = os.environ.get("TNML_FAST_CG", "1") != "0" or os.environ.get("TNML_REUSE_P", "1") != "0"
-        out = {
-            "metric": "two-site bond updates/sec" if not single else "two-site bond updates/sec (per-label variant, label %d)" % args.single_label,
-            "value": args.steps / elapsed,
-            "unit": "bond updates/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic",
-            "parity": "unpinned-oracle (no reference-held vectors exist and ITensor is absent: GPU results are checked against "
-                      "oracle/, a line-cited restatement of fixedL.cc cross-checked by an independent numpy restatement)",
-            "config": {"workload": "fixedL N=%d, maxm=%d, %d images (%s), Npass=%d, lambda=%g, minm=%d, "
-                                   "%s; %s; timed bonds %d..%d (%s, m=%.0f)" % (N, maxm, NT, baseline_config_name(N, maxm, NT, world, args.dtype), npass, lam, minm,
-                                                                               {"f64": "fp64 throughout", "f64_e32": "fp64 MFMA over fp32-stored environments", "f32": "fp32 study mode",
-                                                                                "bf16x3": "fp32 storage, forward feature GEMM on bf16 MFMA with hi + lo operands (study mode)",
-                                                                                "bf16": "fp32 storage, forward feature GEMM on bf16 MFMA (study mode)"}[args.dtype],
-                                                                               "random-init W at m=maxm" if args.workload == "default" else "SURVEY 8(d): after one warm-up sweep from the random-init W",
-                                                                               timed[0]["bond"] if timed else 0,
-                                                                               timed[-1]["bond"] if timed else 0,
-                                                                               "whole sweeps" if full_sweeps else
-                                                                               ("consecutive interior bonds, Label-carrying shiftE on each" if args.workload == "default" else "consecutive interior bonds of the second sweep"),
-                                                                               m_avg),
-                       "global_images": NT, "sites": N, "maxm": maxm, "parallelism": "dp%d (image sharding + %s)" % (world, "RCCL all-reduce" if main_tr == "rccl" or world == 1 else "one-shot all-reduce over IPC-mapped regions"),
-                       "rccl_ranks": comm_ranks},
+        out = headline(elapsed, timed)
+        out.update({
             "roofline": {"bound": "mfma", "kernel": FWD_KERNEL[0] if fused else ("k_fgemm64" if args.dtype in ("f64", "f64_e32") else ("k_fgemm" if args.dtype == "f32" else "k_fgemm_bf16")),
                          "achieved": achieved_tf, "peak": peak, "unit": "TFLOP/s",
                          "frac": achieved_tf / peak,
@@ -787,7 +843,7 @@ def main():
                 "mode": ts.allreduce_mode() if hasattr(ts, "allreduce_mode") else "rccl",
                 "note": "sum all-reduces of the packed [scalars | gradient or A p] buffer (merged CG passes, carried after-SVD scalars) and "
                         "broadcasts of rank 0's eigenvalues, per bond update of the timed region; allreduce ms from HIP events on the breakdown steps"},
-        }
+        })
         if world > 1:
             # both transports side by side: this process's own (`value`) now, the other one after its child leg below
             cm = out["collectives"]

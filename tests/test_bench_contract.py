@@ -4,12 +4,16 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
             "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"}
+# what a plain run (no --full) prints: the headline figure and its workload
+HEADLINE = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+            "vs_baseline", "dtype", "data", "parity", "config", "last_cost_per_image"}
 
 
 def _run(*extra):
@@ -23,7 +27,7 @@ def _run(*extra):
 
 @pytest.mark.gpu
 def test_bench_json_line_whole_sweep():
-    d = _run()
+    d = _run("--full")
     assert REQUIRED <= set(d), REQUIRED - set(d)
     assert d["metric"] == "two-site bond updates/sec" and d["unit"] == "bond updates/s"
     assert d["steps"] == 2 * (24 - 1) and d["warmup"] == 2 and d["n_gpus"] == 1       # default: one whole sweep
@@ -52,12 +56,40 @@ def test_bench_json_line_whole_sweep():
 
 @pytest.mark.gpu
 def test_bench_window_and_variants():
-    d = _run("--steps", "4", "--no-cpu-baseline")
+    d = _run("--steps", "4", "--full", "--no-cpu-baseline")
     assert d["steps"] == 4 and "cpu_baseline" not in d
     e = _run("--steps", "4", "--no-cpu-baseline", "--dtype", "f64_e32")
     assert e["dtype"] == "f64_e32"
     s = _run("--steps", "4", "--no-cpu-baseline", "--single-label", "3")
     assert s["value"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run (no --full) prints the headline figure only, over exactly --steps timed bond updates; --dump-outputs DIR writes what
+    the last of them returned (report, per-label costs, CG trace, the two site tensors it rewrote) in float64 -- the same bits in a
+    second run and in a --full run of the same window, whose extra measurements all come after the dump"""
+    fields = ("bond", "half", "c", "mL", "mR", "label_on_B", "origm", "newm", "truncerr", "norm_newB", "diff", "cost", "reg_cost",
+              "ncorrect", "cost_old", "cost_cg", "reg_cost_cg", "norm_oB")                   # report.npy, in this order
+    runs = {k: _run("--steps", "5", "--dump-outputs", str(tmp_path / k), *extra)
+            for k, extra in (("a", ()), ("b", ()), ("full", ("--full", "--no-cpu-baseline")))}
+    d = runs["a"]
+    assert set(d) == HEADLINE, set(d) ^ HEADLINE
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["metric"] == "two-site bond updates/sec" and d["dtype"] == "f64"
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    names = ["cg_alpha.npy", "cg_cost.npy", "cg_pAp.npy", "cg_rnorm.npy", "label_cost.npy", "report.npy", "site_left.npy", "site_right.npy"]
+    for k in runs:
+        assert sorted(os.listdir(tmp_path / k)) == names
+    for n in names:
+        a = np.load(tmp_path / "a" / n)
+        assert a.dtype == np.float64 and np.isfinite(a).all() and (n != "report.npy" or a.size == len(fields))
+        for k in ("b", "full"):
+            np.testing.assert_array_equal(a, np.load(tmp_path / k / n), err_msg="%s of run %s" % (n, k))
+    rep = dict(zip(fields, np.load(tmp_path / "a" / "report.npy")))
+    assert rep["cost"] / 3000 == d["last_cost_per_image"] == runs["full"]["last_cost_per_image"]
+    b = int(rep["bond"])
+    assert "timed bonds %d..%d" % (b - 4, b) in d["config"]["workload"]          # the dump is of the LAST timed bond update
+    assert np.load(tmp_path / "a" / "site_left.npy").size == rep["mL"] * 2 * rep["newm"]
 
 
 def test_bench_refuses_without_a_device():
@@ -73,18 +105,18 @@ def test_bench_gpus_n_without_a_launcher_starts_n_ranks():
     rendezvous on 127.0.0.1, shard bounds, max-over-ranks reduction and ONE JSON line from rank 0 (--dry-run: the control
     plane only, there is no GPU in this test)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--images", "61"],
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--images", "61", "--full"],
                          capture_output=True, text=True, cwd=ROOT, timeout=600, env=env)
     assert run.returncode == 0, (run.stderr + run.stdout)[-2000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, run.stdout[-2000:]
     d = json.loads(lines[0])
     # ... and the SECOND transport's leg of the same invocation (one child process per rank with a rendezvous of its own, here --dry-run too):
-    # `bench.py --gpus N` times its window over RCCL and over the one-shot all-reduce and reports both under `collectives`
+    # `bench.py --gpus N --full` times its window over RCCL and over the one-shot all-reduce and reports both under `collectives`
     assert d == {"dry_run": True, "n_gpus": 2, "max_over_ranks": 2.0, "images_over_ranks": 61, "shard_of_rank0": [0, 30], "allreduce": "rccl", "handles_gathered": None,
                  "second_transport": {"transport": "oneshot", "n_gpus": 2, "handles_gathered": 2}}
     # --allreduce oneshot: the IPC handles of the cross-process one-shot all-reduce travel over the same gloo control plane
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--images", "61", "--allreduce", "oneshot"],
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--images", "61", "--allreduce", "oneshot", "--full"],
                          capture_output=True, text=True, cwd=ROOT, timeout=600, env=env)
     assert run.returncode == 0, (run.stderr + run.stdout)[-2000:]
     d = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][0])
@@ -104,14 +136,14 @@ def test_bench_under_the_launcher_form_the_driver_uses():
 
 @pytest.mark.gpu
 def test_bench_gpus_2_reports_both_transports_in_one_line():
-    """`bench.py --gpus 2` tells the whole multi-GPU story in ONE line: `collectives` carries a block per transport (RCCL and the
+    """`bench.py --gpus 2 --full` tells the whole multi-GPU story in ONE line: `collectives` carries a block per transport (RCCL and the
     cross-process one-shot all-reduce), each with its bond updates/s, ms per all-reduce, gradient-phase and split time; per-rank image
     counts; the communicator size.  On a one-GPU box both ranks share device 0 (--share-device): RCCL refuses two ranks on one device,
     so its block carries that as an error string and `value` comes from the one-shot transport -- the second-leg machinery itself
     (child process per rank, own rendezvous, merge on rank 0) is what test_bench_gpus_n_without_a_launcher_starts_n_ranks covers."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-device", "--sites", "24", "--images", "3000", "--maxm", "12",
-                          "--steps", "6", "--warmup", "2", "--plain", "--no-cpu-baseline"], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
+                          "--steps", "6", "--warmup", "2", "--full", "--plain", "--no-cpu-baseline"], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
     assert run.returncode == 0, (run.stderr + run.stdout)[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, run.stdout[-2000:]
@@ -133,7 +165,7 @@ def test_bench_gpus_8_runs_eight_ranks_over_the_one_shot_transport():
     rate means nothing; that every rank finishes the same bond updates with the same bits is checked inside the library (check_replicas)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-device", "--sites", "24", "--images", "8000", "--maxm", "12",
-                          "--steps", "6", "--warmup", "2", "--plain", "--no-cpu-baseline"], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
+                          "--steps", "6", "--warmup", "2", "--full", "--plain", "--no-cpu-baseline"], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
     assert run.returncode == 0, (run.stderr + run.stdout)[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, run.stdout[-2000:]

@@ -1,9 +1,10 @@
 #!/bin/bash
 # where the waves of each kernel spend their cycles (MI355X_MICROARCH.md "rocprofv3 PMC slots"): SQ wait / issue counters
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 out=$GRAFT_REPO_ROOT/gpurun_out/pmc_stalls
 mkdir -p $out
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $out -o st -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --steps 6 --warmup 2 "$@" > $out/st.log 2>&1
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $out -o st -- python $root/bench.py --full --no-cpu-baseline --steps 6 --warmup 2 "$@" > $out/st.log 2>&1
 python - $out <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/**/st_counter_collection.csv", recursive=True)[0]

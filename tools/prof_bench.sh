@@ -1,10 +1,11 @@
 #!/bin/bash
 # rocprofv3 kernel trace of a short bench run; summary -> gpurun_out/prof_<tag>/  (copy what matters into profiles/)
 tag=${1:-run}; shift
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 out=$GRAFT_REPO_ROOT/gpurun_out/prof_$tag
 mkdir -p $out
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -o trace -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --plain "$@" > $out/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -o trace -- python $root/bench.py --full --no-cpu-baseline --plain "$@" > $out/bench.log 2>&1
 tail -1 $out/bench.log | cut -c1-300
 f=$(find $out -name '*kernel_stats.csv' | head -1)
 python - "$f" <<'PY'
