@@ -328,6 +328,35 @@ int tnml_device_memory(int device, int64_t* free_bytes, int64_t* total_bytes);
 /* largest maxm in [floor_m, wanted] reachable by an N-site MPS whose tnml_estimate_bytes fits budget_bytes (<= 0: no memory bound) */
 int tnml_plan_maxm(const tnml_config* cfg, int wanted, int floor_m, int64_t budget_bytes);
 
+/* ---- the linear classifier (linear.cc) -------------------------------------------------------------------------
+ * Ridge regression per label column by the reference's CG (linear.cc:27-90), K label columns at once over one shared
+ * data set (kernels_linear.hip).  Features v_n = [1, x_n1/4, ..., x_nN/4], x = byte/255. (linear.cc:118-121,133-139,
+ * mllib/mnist.h:495 -- the single normalisation); targets y_nk = +1 if label_n == L_k else -1 (:132).
+ * Vectors cross the ABI as V[k][N+1] (bias first).  Same error convention as tnml_ctx: 0 on success, the message from
+ * tnml_lin_last_error (NULL context: the last tnml_lin_create failure).  The context owns its device memory and stream. */
+#define TNML_LIN_MAX_COLS 16
+typedef struct tnml_lin tnml_lin;
+/* a context for N-pixel images on HIP device `device`; fails without a usable device (no CPU fallback) */
+int tnml_lin_create(tnml_lin** out, int device, int N);
+int tnml_lin_destroy(tnml_lin* ctx);
+const char* tnml_lin_last_error(const tnml_lin* ctx);
+/* the data set (replaces the previous one; the CG must be started again): raw bytes pixels[NT][N] decoded as
+   fl(b/255.)/4 (linear.cc:133-139, readMNIST's vector of train/test images, :111-112), or fp64 feature values
+   features[NT][N] (the x/4 components, for reduced images and tests); labels[NT] */
+int tnml_lin_set_data_u8(tnml_lin* ctx, int NT, const uint8_t* pixels, const int32_t* labels);
+int tnml_lin_set_data_f64(tnml_lin* ctx, int NT, const double* features, const int32_t* labels);
+/* the label column of each of the K (1..TNML_LIN_MAX_COLS) independent regressions: column k is `label = L_k` (:114, :132) */
+int tnml_lin_set_labels(tnml_lin* ctx, int K, const int32_t* labels);
+/* cgrad's preamble (:37-48): W = V[K][N+1], r = sum_n (y_n - W.v_n) v_n / NT - lambda W, p = r */
+int tnml_lin_cg_start(tnml_lin* ctx, const double* V, double lambda);
+/* npass more passes of the same CG (:51-89, no convergence exit); costs[npass][K] receives each pass's
+   C = sum_n e_n^2 / NT + lambda W.W (:76).  Chunked calls continue the recursion: run(10) + run(20) == run(30) bitwise */
+int tnml_lin_cg_run(tnml_lin* ctx, int npass, double* costs);
+/* the current W as V[K][N+1] (:166, writeToFile(Vname,V) at :191) */
+int tnml_lin_get_v(tnml_lin* ctx, double* V);
+/* evaluate (:169-187) V[K][N+1] on the loaded data: ncorrect[k] = #(f y > 0), cnl[k] = sum (f - y)^2 / NT; leaves the CG state alone */
+int tnml_lin_evaluate(tnml_lin* ctx, const double* V, int64_t* ncorrect, double* cnl);
+
 #ifdef __cplusplus
 }
 #endif

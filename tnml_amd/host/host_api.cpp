@@ -8,6 +8,7 @@
 #include "host_mps.h"
 #include "init_w.h"
 #include "input_group.h"
+#include "linear_mps.h"
 #include "mnist_idx.h"
 
 using namespace tnmlh;
@@ -76,6 +77,23 @@ int tnmlh_mps_info(const char* file, int* N, int* c0) {
 int tnmlh_mps_site(const char* file, int j, int* ml, int* mr, int* L, double* data) {
     try { HostMPS W = read_mps(file); const Site& s = W.A.at(j); *ml = s.ml; *mr = s.mr; *L = s.L; if (data) std::memcpy(data, s.a.data(), sizeof(double) * s.a.size()); return 0; }
     catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// the linear driver's embedding (linear.cc:205-236, linear_mps.h): V[n] (bias first) -> MPS file `out` (TNMLW1); overlap(W,W) through *ovl
+int tnmlh_linear_mps(const double* V, int n, double entry_scale, const char* out, double* ovl) {
+    try {
+        HostMPS W = linear_mps(std::vector<double>(V, V + n), entry_scale);
+        write_mps(out, W);
+        if (ovl) *ovl = overlap(W, W);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// V%d files (TNMLV1): size first (V == NULL), then the data
+int tnmlh_vec_read(const char* file, int* n, double* V) {
+    try { std::vector<double> v = read_vec(file); *n = (int)v.size(); if (V) std::memcpy(V, v.data(), sizeof(double) * v.size()); return 0; }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+int tnmlh_vec_write(const char* file, int n, const double* V) {
+    try { write_vec(file, std::vector<double>(V, V + n)); return 0; } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 // write a weight file from a flat list of sites (dims[3*j..] = ml, mr, L; data concatenated)
 int tnmlh_mps_write(const char* file, int N, const int* dims, const double* data) {

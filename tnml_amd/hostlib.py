@@ -32,6 +32,9 @@ def load():
         L.tnmlh_mps_site.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                      C.POINTER(C.c_double)]
         L.tnmlh_mps_write.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        L.tnmlh_linear_mps.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_double, C.c_char_p, C.POINTER(C.c_double)]
+        L.tnmlh_vec_read.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        L.tnmlh_vec_write.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_double)]
         _LIB = L
     return _LIB
 
@@ -128,3 +131,33 @@ def read_sites(path):
     if load().tnmlh_sites_read(path.encode(), N, d) != 0:
         raise _err()
     return N.value, d.value
+
+
+def linear_mps(V, path, entry_scale=1.0):
+    """the linear driver's MPS embedding of V[N+1] (linear.cc:205-236) written to `path`; returns overlap(W,W)"""
+    V = np.ascontiguousarray(V, dtype=np.float64)
+    ovl = C.c_double()
+    if load().tnmlh_linear_mps(V.ctypes.data_as(C.POINTER(C.c_double)), V.shape[0], float(entry_scale), path.encode(), ovl) != 0:
+        raise _err()
+    return ovl.value
+
+
+def read_vec(path):
+    """V%d file (TNMLV1) -> numpy vector"""
+    L = load()
+    n = C.c_int()
+    if L.tnmlh_vec_read(path.encode(), n, None) != 0:
+        raise _err()
+    out = np.empty(n.value)
+    m = C.c_int()
+    if L.tnmlh_vec_read(path.encode(), m, None) != 0 or m.value != n.value:
+        raise RuntimeError(path + " changed while it was read")
+    if L.tnmlh_vec_read(path.encode(), m, out.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise _err()
+    return out
+
+
+def write_vec(path, V):
+    V = np.ascontiguousarray(V, dtype=np.float64)
+    if load().tnmlh_vec_write(path.encode(), V.shape[0], V.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise _err()

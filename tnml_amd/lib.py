@@ -28,6 +28,8 @@ EXPORTS = [
     "tnml_profile_reset", "tnml_synchronize", "tnml_device_bytes", "tnml_svd_stats", "tnml_classify", "tnml_replica_check",
     "tnml_estimate_bytes", "tnml_device_memory", "tnml_plan_maxm", "tnml_set_option", "tnml_comm_init_local", "tnml_comm_init_oneshot", "tnml_collective_mode", "tnml_bond_update_begin", "tnml_bond_update_end", "tnml_replica_repairs", "tnml_pAp", "tnml_collective_stats", "tnml_last_warning",
     "tnml_exact", "tnml_set_option_real", "tnml_pinv", "tnml_env_stats", "tnml_oneshot_export", "tnml_oneshot_connect", "tnml_oneshot_mem_kind", "tnml_split_stats", "tnml_oneshot_region_bytes",
+    "tnml_lin_create", "tnml_lin_destroy", "tnml_lin_last_error", "tnml_lin_set_data_u8", "tnml_lin_set_data_f64", "tnml_lin_set_labels",
+    "tnml_lin_cg_start", "tnml_lin_cg_run", "tnml_lin_get_v", "tnml_lin_evaluate",
 ]
 
 
@@ -135,6 +137,17 @@ def load():
     L.tnml_oneshot_region_bytes.restype = C.c_int64
     L.tnml_device_memory.argtypes = [C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.tnml_plan_maxm.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_int64]
+    L.tnml_lin_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
+    L.tnml_lin_destroy.argtypes = [vp]
+    L.tnml_lin_last_error.restype = C.c_char_p
+    L.tnml_lin_last_error.argtypes = [vp]
+    L.tnml_lin_set_data_u8.argtypes = [vp, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]
+    L.tnml_lin_set_data_f64.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_int32)]
+    L.tnml_lin_set_labels.argtypes = [vp, C.c_int, C.POINTER(C.c_int32)]
+    L.tnml_lin_cg_start.argtypes = [vp, dp, C.c_double]
+    L.tnml_lin_cg_run.argtypes = [vp, C.c_int, dp]
+    L.tnml_lin_get_v.argtypes = [vp, dp]
+    L.tnml_lin_evaluate.argtypes = [vp, dp, C.POINTER(C.c_int64), dp]
     _lib = L
     return L
 
