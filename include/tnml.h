@@ -273,28 +273,30 @@ int tnml_profile_count(tnml_ctx* ctx);
 int tnml_profile_get(tnml_ctx* ctx, int idx, char* name64, int64_t* launches, double* total_ms);
 int tnml_profile_reset(tnml_ctx* ctx);
 int tnml_synchronize(tnml_ctx* ctx);
-/* run-time switches of the algebraic shortcuts and checks (defaults: all 1; the environment variables TNML_FAST_CG,
-   TNML_REUSE_P, TNML_FUSE_Z, TNML_CHECK_REPLICAS set the defaults at tnml_create):
-     "fast_cg"        P <- P + a (p*t.v) instead of re-running the forward GEMM inside cgrad (single.h:290-398 idea)
-     "reuse_p"        the after-SVD quadcost of one bond update provides the first residuals of the next
-     "fuse_z"         the gradient GEMM builds Z = sum_l EL[l] dP[l] itself
-     "merged_cg"      one all-reduce per CG pass instead of two: the image sum of a pass is A p = sum_n (p.v_n) v_n, formed from the
+/* run-time options; a value outside an option's range, or an unknown name, is refused.  Where an environment variable is named it
+   supplies the default at tnml_create (and a bad value there makes tnml_create fail).  Bool options take any value, nonzero = on.
+   The algebraic shortcuts and checks (defaults: all 1):
+     "fast_cg"        (TNML_FAST_CG) P <- P + a (p*t.v) instead of re-running the forward GEMM inside cgrad (single.h:290-398 idea)
+     "reuse_p"        (TNML_REUSE_P) the after-SVD quadcost of one bond update provides the first residuals of the next
+     "fuse_z"         (TNML_FUSE_Z) the gradient GEMM builds Z = sum_l EL[l] dP[l] itself
+     "merged_cg"      (TNML_MERGED_CG) one all-reduce per CG pass instead of two: the image sum of a pass is A p = sum_n (p.v_n) v_n, formed from the
                       pAp pass's own outputs, and travels with sum |p.v_n|^2; the residual follows r <- r - a (A p + lambda p)
                       (the structure of the reference's own fast_cgrad, single.h:347-379); needs fast_cg.  1 (default): on ranks that
                       have a communicator -- where it halves the collectives; a single rank keeps the reference's literal residual
                       (the recurrence moves the 4th step size of an ill-conditioned Label-on-B bond by 1e-3, the cost by 1e-10);
                       2: always; 0: never
-     "defer_tail"     multi-rank: the cost partials of the "after SVD" quadcost and the replica fingerprint ride in the first
+     "defer_tail"     (TNML_DEFER_TAIL) multi-rank: the cost partials of the "after SVD" quadcost and the replica fingerprint ride in the first
                       all-reduce of the NEXT bond update (tnml_bond_update_end issues one small all-reduce when nothing followed);
                       with both on a bond update enters 5 payload all-reduces instead of 9 + 1 (default 1)
-     "check_replicas" multi-rank: fingerprint check of the two site tensors a split rewrote (1, default: folded into the packed
+     "check_replicas" (TNML_CHECK_REPLICAS) multi-rank: fingerprint check of the two site tensors a split rewrote (1, default: folded into the packed
                       sum all-reduce as exact integer pieces, a mismatch is an error when the report is handed out; 2: checked at
                       once inside the bond update, before anything consumes the tensors -- one extra 8-double all-reduce and a
                       host synchronisation -- and on a mismatch rank 0's two tensors are re-broadcast, the sweep continues,
                       tnml_replica_repairs counts; 0: off)
-     "fg64_cfg", "ldot_cfg"  force a tile configuration of the feature GEMM / the label dot that is otherwise chosen by the
-                      image count (2 / 1 = the large-image-count forms bench.py times; parity tests run them at small sizes)
-     "fused_fwd"      the forward pass of a Label-on-environment bond at m = 120 as one persistent kernel (feature GEMM +
+     "fg64_cfg", "ldot_cfg"  (TNML_FG64_CFG, TNML_LDOT_CFG) force a tile configuration of the feature GEMM / the label dot that is
+                      otherwise chosen by the image count (2 / 1 = the large-image-count forms bench.py times; parity tests run them at
+                      small sizes; ldot_cfg 2 = the small-shard form)
+     "fused_fwd"      (TNML_FUSED_FWD) the forward pass of a Label-on-environment bond at m = 120 as one persistent kernel (feature GEMM +
                       label dot of the previous tile, kernels_fused.hip): 1 = from 14 336 images per rank on (default),
                       0 = never, 2 = always (parity tests at small sizes), > 2 = always with that many workgroups at most
      "cg_method"      TNML_MODE_SINGLE only: 0 = conj (single.h:162-288, default), 1 = fast_conj (single.h:290-398: one image sum
@@ -302,6 +304,26 @@ int tnml_synchronize(tnml_ctx* ctx);
                       2 = exact (single.h:117-160, see tnml_exact; "pcut" through tnml_set_option_real)
      "sytrd_exit"     the split's tridiagonalisation stops once the trailing block of the Gram matrix is numerically zero
                       (trace <= 1e-15 trace(G); default 1; 0 = all n-2 Householder steps)
+   Kernel selection (0 never, 1 by shape and image count (default), 2 always):
+     "fwd_res", "shift_res"  (TNML_FWD_RES, TNML_SHIFT_RES) the resident-operand forward pass / Label-carrying shift (kernels_res.hip);
+                      fwd_res 3 = the general form on 120 x 120 bonds too
+     "grad_quad"      (TNML_GRAD_QUAD) the resident-accumulator gradient GEMM (kernels_grad.hip)
+     "grad_pair"      (TNML_GRAD_PAIR) its pair form for bonds up to 64 x 64 (default 1; 0 = the quad form)
+     "bgs_chol"       (TNML_BGS_CHOL) block Gram-Schmidt Cholesky QR of a kept basis of 129-384 columns (default 1; 0 = dpotrf + dtrsm)
+     "spec_split"     (TNML_SPEC_SPLIT) the speculative split without its host synchronisation (default 1)
+     "bf16_grad", "bf16_once"  the bf16 modes: gradient GEMM on the bf16 pipe / operands converted once (default 1 each)
+   Tuning and test knobs (0: the default):
+     "res_pace"       (TNML_RES_PACE) 0-4, pause pattern of the GEMM waves of k_fwd_res
+     "res_grid"       workgroups of the resident-operand kernels
+     "bgemm_wgs", "bgemm_per"  (TNML_BGEMM_WGS, TNML_BGEMM_PER) workgroups the gradient GEMM aims at / images per slab in units of 32
+     "mc_spin_max"    polls before the workgroup cluster of the tridiagonalisation gives up (-1 default; 0 forces the fallback)
+     "debug_fail_split"  k >= 0: the k-th speculative split reports a failed check (-1 off)
+     "debug_nudge_rank"  this rank's copy of a split site tensor is moved by one ulp (-1 off)
+     "svd_print"      (TNML_SVD_PRINT) k >= 0: print the spectrum of the k-th split; -1: the check values of every split (-2 off)
+   Memory and transport:
+     "env_budget_mb"  cap on the environment slabs held on the device, the rest spills to host memory (0: none)
+     "env_async"      the host tier's copies beside the compute stream (default 1)
+     "comm_timeout_s" how long a rank of an in-process or one-shot communicator waits for its peers (>= 1, default 120)
    fast_cg = reuse_p = 0 is the reference's literal evaluation order (fixedL.cc:374-421). */
 int tnml_set_option(tnml_ctx* ctx, const char* name, int value);
 /* real-valued options: "pcut" (PCut of the exact solver inside tnml_bond_update, single.cc:50, default 1E-8);

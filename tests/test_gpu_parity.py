@@ -1337,15 +1337,25 @@ def test_properties_at_the_full_baseline_size():
     assert _relmax(Gs, G) < 1e-11
 
 
-@pytest.mark.parametrize("N,NT,m,dtype", [(20, 300, 8, "f64"), (16, 700, 24, "f64_e32"), (24, 48, 150, "f64")])
-def test_memory_estimate_covers_what_a_sweep_allocates(N, NT, m, dtype):
+def _estimate_cases():
+    # every dtype on every shape, fixedL and the per-label variant (ids of the fixedL cases: N-NT-m-dtype)
+    for N, NT, m in ((20, 300, 8), (16, 700, 24), (24, 48, 150)):
+        for dtype in ("f64", "f64_e32", "f32", "bf16", "bf16x3"):
+            for single in (False, True):
+                yield pytest.param(N, NT, m, dtype, single, id="%d-%d-%d-%s%s" % (N, NT, m, dtype, "-single" if single else ""))
+
+
+@pytest.mark.parametrize("N,NT,m,dtype,single", list(_estimate_cases()))
+def test_memory_estimate_covers_what_a_sweep_allocates(N, NT, m, dtype, single):
     """tnml_estimate_bytes is what the drivers size maxm with (tnml_plan_maxm) before any environment exists; the
     environment slabs are allocated lazily during the first sweep.  An estimate below the real footprint would surface
     as a failed hipMalloc in the middle of a sweep: after a full sweep the context must hold no more than estimated
     (and not absurdly less: the plan would give memory away)."""
     from tnml_amd.fixedl import TrainStates, mldmrg
     pixels, labels, phi, W = make_problem(N, NT, min(m, 8), 3, pixel_boost=200.0)
-    ts = TrainStates(labels, N, m, pixels=pixels, dtype=dtype)
+    if single:
+        W[N // 2 - 1] = W[N // 2 - 1][..., 0] * 3.0                           # plain MPS: no Label index
+    ts = TrainStates(labels, N, m, pixels=pixels, dtype=dtype, single_label=3 if single else None)
     ts.set_mps(W)
     ts.init()
     mldmrg(ts, 1, m, max(2, m // 2), 1e-10, 2, 1e-3, 1e-10)
@@ -1353,6 +1363,68 @@ def test_memory_estimate_covers_what_a_sweep_allocates(N, NT, m, dtype):
     ts.close()
     assert est > 0 and used <= est, (used, est)
     assert used > 0.25 * est, (used, est)
+
+
+# every value tests/ and tools/ give an option (tnml_set_option, or the environment variable of the same name)
+_OPTION_VALUES_IN_USE = {
+    "fast_cg": (0, 1), "reuse_p": (0, 1), "fuse_z": (0, 1), "merged_cg": (0, 1, 2), "defer_tail": (0, 1), "check_replicas": (0, 1, 2),
+    "fused_fwd": (0, 1, 2, 4), "fwd_res": (0, 1, 2, 3), "shift_res": (0, 1, 2), "res_grid": (0, 16, 32), "res_pace": (0, 1, 2, 3, 4),
+    "grad_quad": (0, 1, 2), "grad_pair": (0, 1), "bgemm_wgs": (0, 4, 6, 8, 12, 4096), "bgemm_per": (0, 5, 72), "sytrd_exit": (0, 1),
+    "bgs_chol": (0, 1), "spec_split": (0, 1), "debug_fail_split": (-1, 0, 4, 5, 17), "bf16_grad": (0, 1), "bf16_once": (0, 1),
+    "env_async": (0, 1), "env_budget_mb": (0, 1, 2, 2048), "comm_timeout_s": (20, 30, 60), "cg_method": (0,), "debug_nudge_rank": (-1, 1),
+    "mc_spin_max": (-1, 0), "svd_print": (-2, -1, 0), "fg64_cfg": (0, 2), "ldot_cfg": (0, 1, 2),
+}
+# one value outside the range of every option that has more than two values (and both grad_quad ablations that are gone)
+_OPTION_VALUES_REFUSED = [
+    ("merged_cg", 3), ("check_replicas", 3), ("fused_fwd", -1), ("fwd_res", 4), ("shift_res", 3), ("res_grid", -1), ("res_pace", 5),
+    ("grad_quad", 3), ("grad_quad", 5), ("grad_quad", -1), ("bgemm_wgs", -1), ("bgemm_per", -1), ("debug_fail_split", -2),
+    ("env_budget_mb", -1), ("comm_timeout_s", 0), ("cg_method", 3), ("debug_nudge_rank", -2), ("mc_spin_max", -2), ("svd_print", -3),
+    ("fg64_cfg", 3), ("ldot_cfg", 3),
+]
+
+
+def test_options_are_range_checked():
+    """the option table (tnml_abi.hip): unknown names, removed options and values outside an option's range are refused with a message
+    that names them; every value in use is accepted; a bad environment default makes tnml_create fail"""
+    import subprocess
+    import sys
+    from tnml_amd.fixedl import TnmlError, TrainStates
+    pixels, labels, phi, W = make_problem(8, 60, 4, 3)
+    ts = TrainStates(labels, 8, 4, pixels=pixels)
+    for name in ("no_such_option", "fold_reduce", "small_gemm", "grad_pair_min", "grad_pair_max", "pcut"):
+        with pytest.raises(TnmlError, match="unknown option %s" % name):
+            ts.set_option(name, 1)
+    with pytest.raises(TnmlError, match="unknown option fast_cg"):
+        ts.set_option_real("fast_cg", 1.0)
+    for name, v in _OPTION_VALUES_REFUSED:
+        with pytest.raises(TnmlError, match=r"tnml_set_option: %s = %d, must be" % (name, v)):
+            ts.set_option(name, v)
+    for name in ("pcut", "noise"):
+        with pytest.raises(TnmlError, match=r"%s = -1, must be >= 0" % name):
+            ts.set_option_real(name, -1.0)
+    with pytest.raises(TnmlError, match="cg_method"):
+        ts.set_option("cg_method", 1)                                      # fast_conj: the per-label variant only
+    for name, values in _OPTION_VALUES_IN_USE.items():
+        for v in values:
+            ts.set_option(name, v)
+    ts.set_option("fast_cg", 7)                                            # bool options: any nonzero value is on
+    ts.set_option_real("pcut", 1e-8)
+    ts.set_option_real("noise", 0.0)
+    ts.close()
+    single = TrainStates(labels, 8, 4, pixels=pixels, single_label=3)
+    for v in (0, 1, 2):
+        single.set_option("cg_method", v)
+    single.set_option_real("noise", 1e-5)
+    single.close()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "import numpy as np\n"
+            "from tnml_amd.fixedl import TnmlError, TrainStates\n"
+            "try:\n    TrainStates(np.zeros(60, np.int32), 8, 4, pixels=np.zeros((60, 8), np.uint8))\n"
+            "except TnmlError as e:\n    print('refused:', e)\n") % root
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, TNML_GRAD_QUAD="5"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "refused: tnml_create: TNML_GRAD_QUAD = 5, must be in 0..2" in r.stdout, (r.stdout, r.stderr[-2000:])
 
 
 def test_cg_on_ill_conditioned_bonds_is_at_least_as_close_to_extended_precision_as_the_oracle():

@@ -99,3 +99,42 @@ def test_oneshot_region_bytes_is_what_the_planner_has_to_subtract():
     assert 2 * 8 * cap120 * 8 <= b120 <= 2 * 8 * cap120 * 8 + 65536
     assert 4.4e8 < b300 < 4.8e8                                       # ~460 MB per rank at maxm = 300 with 8 ranks
     assert L.tnml_oneshot_region_bytes(None) == -1
+
+
+def test_estimate_counts_the_bf16_copies():
+    """tnml_estimate_bytes sums the list of buffers tnml_create allocates: the bf16 modes' copy of the Label-free environment
+    ([planes][NTp][ru32(maxm)] bf16, two planes in bf16x3) is part of it (no GPU needed: pure arithmetic)"""
+    from tnml_amd import lib
+    N, NT, m = 784, 60000, 300
+    NTp = NT + (-NT) % 256
+    env_copy = NTp * ((m + 31) // 32 * 32) * 2                        # bf16e_env_elems(300, NTp, 0) x 2 bytes, ~38 MB
+    f32 = lib.estimate_bytes(N, NT, m, "f32")
+    assert lib.estimate_bytes(N, NT, m, "bf16") - f32 >= env_copy
+    assert lib.estimate_bytes(N, NT, m, "bf16x3") - f32 >= 2 * env_copy
+
+
+def _option_table():
+    """(name, environment variable or None) of every row of the option table in tnml_abi.hip"""
+    src = open(os.path.join(ROOT, "tnml_amd", "csrc", "tnml_abi.hip")).read()
+    body = src[src.index("k_options[] = {"):]
+    body = body[:body.index("};")]
+    return re.findall(r'\{"(\w+)",\s*(?:"(\w+)"|nullptr),', body)
+
+
+def test_option_table_is_what_the_docs_name():
+    """include/tnml.h, README.md and the fields of tnml_internal.h name every option of the table and its environment variable"""
+    rows = _option_table()
+    names = [n for n, _ in rows]
+    assert len(names) == len(set(names)) >= 30
+    assert not {"fold_reduce", "small_gemm", "grad_pair_min", "grad_pair_max"} & set(names)
+    hdr = open(os.path.join(ROOT, "include", "tnml.h")).read()
+    hdr = hdr[hdr.index("/* run-time options"):hdr.index("int tnml_set_option_real(")]
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    internal = open(os.path.join(ROOT, "tnml_amd", "csrc", "tnml_internal.h")).read()
+    for name, env in rows:
+        assert '"%s"' % name in hdr, name
+        assert "`%s`" % name in readme or (env and "`%s`" % env in readme), name
+        if env:
+            assert "`%s`" % env in readme and env in internal, env
+    documented = set(re.findall(r"`(TNML_[A-Z0-9_]+)`", readme[readme.index("Environment knobs"):readme.index("Read outside the table")]))
+    assert documented == {env for _, env in rows if env}

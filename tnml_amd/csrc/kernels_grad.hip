@@ -257,7 +257,7 @@ bool grad_quad_applies(const tnml_ctx* c, const Bgemm64Args& a) {
     if (c->grad_quad == 1) {
         if (gq_pair_form(a)) {
             const int mm = a.mI * a.mO;
-            if (!c->grad_pair || a.NTp < 15360 || mm < c->grad_pair_min * c->grad_pair_min || mm > c->grad_pair_max * c->grad_pair_max) return false;
+            if (!c->grad_pair || a.NTp < 15360 || mm < 33 * 33 || mm > 56 * 56) return false;
         } else if (a.NTp < 4096 || a.mI * a.mO < 72 * 72) return false;
     }
     if ((size_t)TNML_NL * a.EL_lstride * sizeof(double) >= ((size_t)1 << 32)) return false;      // 32-bit lane offsets
@@ -269,17 +269,12 @@ static int grad_quad_go(tnml_ctx* c, const GradQuadArgs& K, int grid) {
     const size_t lds = sizeof(double) * GQ_LDS_DOUBLES_N(NR);
     bool& done = NR == 4 ? c->attr_gq : c->attr_gp;
     if (!done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_grad_quad<0, NR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_grad_quad<1, NR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_grad_quad<3, NR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_grad_quad<0, NR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return tnml_fail(c, "grad_quad: cannot reserve %zu bytes of LDS", lds);
         done = true;
     }
     ProfScope ps(c, KC_GRAD_QUAD);
-    // (grad_quad = 3 / 5: the ablations of the record under profiles/ -- compute side alone / the MFMA loop alone; wrong results by construction)
-    if (c->grad_quad == 3)      hipLaunchKernelGGL((k_grad_quad<1, NR>), dim3(grid), dim3(1024), lds, c->stream, K);
-    else if (c->grad_quad == 5) hipLaunchKernelGGL((k_grad_quad<3, NR>), dim3(grid), dim3(1024), lds, c->stream, K);
-    else                        hipLaunchKernelGGL((k_grad_quad<0, NR>), dim3(grid), dim3(1024), lds, c->stream, K);
+    hipLaunchKernelGGL((k_grad_quad<0, NR>), dim3(grid), dim3(1024), lds, c->stream, K);
     return 0;
 }
 

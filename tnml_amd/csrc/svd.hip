@@ -99,9 +99,9 @@ __global__ void k_mc_flag(const unsigned long long* __restrict__ status, double*
 }
 
 // C = op(A) op(B) at the sizes of the split: k_dgemm_small (kernels_sgemm.hip) up to 4e7 multiply-adds, rocBLAS as
-// `strips` column strips beyond (the Label-on-B bonds reduce over 2400: 133 us as one call, 17 us as 8 strips) or with option small_gemm = 0
+// `strips` column strips beyond (the Label-on-B bonds reduce over 2400: 133 us as one call, 17 us as 8 strips)
 int split_gemm(tnml_ctx* c, bool ta, bool tb, int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C, int ldc, int strips, const SmallGemmArgs* chk) {
-    if (c->small_gemm && K <= 1024 && (double)M * N * K <= 4.0e7) {   // (tools/probe/probe_sgemm.hip: 8.7-9.9 us against 19 at 240^3, 17 against 25 at 300 x 300 x 600; loses from ~6e7 on)
+    if (K <= 1024 && (double)M * N * K <= 4.0e7) {   // (tools/probe/probe_sgemm.hip: 8.7-9.9 us against 19 at 240^3, 17 against 25 at 300 x 300 x 600; loses from ~6e7 on)
         SmallGemmArgs g{A, lda, B, ldb, C, ldc, M, N, K, ta ? 1 : 0, tb ? 1 : 0};
         if (chk) { g.chk_src = chk->chk_src; g.chk_host = chk->chk_host; g.chk_bad = chk->chk_bad; }
         return launch_dgemm_small(c, g);
@@ -326,13 +326,8 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
         // the kept basis lands where it is needed: straight in the site tensor when that is its final place
         direct_left = left && !labL && mk <= c->maxm;
         if (direct_left) Q = Sl.a;
-        if (c->small_gemm) {                              // the factor 1.5 I - 0.5 S is formed while the product loads S; d by an atomic max into dv[0]
-            SmallGemmArgs g{Qin, n, c->sS, mk, Q, n, n, mk, mk, 0, 0, 1, dv};
-            TCK(launch_dgemm_small(c, g));
-        } else {
-            TCK(eigh_ns_matrix(c, c->sS, c->sCm, mk, dv));
-            RBCK(c, rocblas_dgemm(c->blas, rocblas_operation_none, rocblas_operation_none, n, mk, mk, &one, Qin, n, c->sCm, mk, &zero, Q, n));
-        }
+        SmallGemmArgs g{Qin, n, c->sS, mk, Q, n, n, mk, mk, 0, 0, 1, dv};     // the factor 1.5 I - 0.5 S is formed while the product loads S; d by an atomic max into dv[0]
+        TCK(launch_dgemm_small(c, g));
     }
     int m = mk;
     bool stock = !tri;                                   // eigenvectors of rho itself in sG (dsyevd)

@@ -3,6 +3,7 @@
 //
 // No CPU fallback lives here: every contraction is a HIP kernel launch on the context's stream.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdlib>
@@ -75,45 +76,86 @@ int tnml_profile_reset(tnml_ctx* c) {
     for (int i = 0; i < KC_COUNT; ++i) { c->prof_launches[i] = 0; c->prof_ms[i] = 0.; }
     return 0;
 }
-int tnml_set_option(tnml_ctx* c, const char* name, int value) {
-    if (!c || !name) return tnml_fail(c, "tnml_set_option: null argument");
-    if (!strcmp(name, "fast_cg")) c->fast_cg = value != 0;
-    else if (!strcmp(name, "reuse_p")) { c->reuse_p = value != 0; c->p_valid = false; }
-    else if (!strcmp(name, "fuse_z")) c->fuse_z = value != 0;
-    else if (!strcmp(name, "merged_cg")) c->merged_cg = value;
-    else if (!strcmp(name, "defer_tail")) { if (c->pend_count) return tnml_fail(c, "defer_tail: a bond update is in flight"); c->defer_tail = value != 0; }
-    else if (!strcmp(name, "check_replicas")) { c->check_replicas = value != 0; c->check_replicas_mode = value; }
-    else if (!strcmp(name, "fused_fwd")) c->fused_fwd = value;
-    else if (!strcmp(name, "fold_reduce")) c->fold_reduce = value != 0;
-    else if (!strcmp(name, "fwd_res")) c->fwd_res = value;
-    else if (!strcmp(name, "shift_res")) c->shift_res = value;
-    else if (!strcmp(name, "res_grid")) c->res_grid = value;
-    else if (!strcmp(name, "res_pace")) c->res_pace = value;
-    else if (!strcmp(name, "bgemm_wgs")) c->bgemm_wgs = value;
-    else if (!strcmp(name, "bgemm_per")) c->bgemm_per = value;
-    else if (!strcmp(name, "sytrd_exit")) c->sytrd_exit = value;
-    else if (!strcmp(name, "bgs_chol")) c->bgs_chol = value != 0;
-    else if (!strcmp(name, "small_gemm")) c->small_gemm = value != 0;
-    else if (!strcmp(name, "spec_split")) c->spec_split = value != 0;
-    else if (!strcmp(name, "debug_fail_split")) { c->debug_fail_split = value; c->spec_splits = 0; }
-    else if (!strcmp(name, "bf16_grad")) c->bf16_grad = value != 0;
-    else if (!strcmp(name, "bf16_once")) c->bf16_once = value != 0;
-    else if (!strcmp(name, "env_async")) c->env_async = value != 0;
-    else if (!strcmp(name, "env_budget_mb")) { if (value < 0) return tnml_fail(c, "env_budget_mb must be >= 0"); c->env_budget_bytes = (long)value << 20; }
-    else if (!strcmp(name, "comm_timeout_s")) { if (value < 1) return tnml_fail(c, "comm_timeout_s must be >= 1"); c->comm_timeout_s = value; local_comm_set_timeout(c, value); }
-    else if (!strcmp(name, "cg_method")) { if (value < 0 || value > 2 || (value >= 1 && !c->single())) return tnml_fail(c, "cg_method: 0 (conj) or, in TNML_MODE_SINGLE, 1 (fast_conj) / 2 (exact)"); c->cg_method = value; }
-    else if (!strcmp(name, "debug_nudge_rank")) c->debug_nudge_rank = value;
-    else if (!strcmp(name, "mc_spin_max")) c->mc_spin_max = value;
-    else if (!strcmp(name, "svd_print")) { c->svd_print = value; c->svd_calls = 0; }
-    else if (!strcmp(name, "grad_quad")) c->grad_quad = value;
-    else if (!strcmp(name, "grad_pair")) c->grad_pair = value;
-    else if (!strcmp(name, "grad_pair_min")) c->grad_pair_min = value;
-    else if (!strcmp(name, "grad_pair_max")) c->grad_pair_max = value;
-    else if (!strcmp(name, "fg64_cfg")) c->opt_fg64_cfg = value;
-    else if (!strcmp(name, "ldot_cfg")) c->opt_ldot_cfg = value;
-    else return tnml_fail(c, "tnml_set_option: unknown option %s", name);
+// ---- context options ------------------------------------------------------------------------
+// One row per option of tnml_set_option / tnml_set_option_real: its name, the environment variable that supplies its default at
+// tnml_create (or none), the field it sets, its kind and the values it accepts.  A bool option takes any value (nonzero: on).
+enum OptKind { OPT_BOOL, OPT_INT, OPT_REAL };
+enum OptHook { HK_NONE, HK_REUSE_P, HK_DEFER_TAIL, HK_CHECK_REPLICAS, HK_ENV_BUDGET, HK_COMM_TIMEOUT, HK_FAIL_SPLIT, HK_SVD_PRINT, HK_CG_METHOD, HK_NOISE };
+struct OptDef {
+    const char* name; const char* env; OptKind kind;
+    int tnml_ctx::* ifield; double tnml_ctx::* rfield;    // the field set (none for env_budget_mb: its hook stores bytes)
+    double lo, hi; OptHook hook;
+};
+static const OptDef k_options[] = {
+    {"fast_cg",          "TNML_FAST_CG",        OPT_BOOL, &tnml_ctx::fast_cg,             nullptr,          0, 1,       HK_NONE},
+    {"reuse_p",          "TNML_REUSE_P",        OPT_BOOL, &tnml_ctx::reuse_p,             nullptr,          0, 1,       HK_REUSE_P},
+    {"fuse_z",           "TNML_FUSE_Z",         OPT_BOOL, &tnml_ctx::fuse_z,              nullptr,          0, 1,       HK_NONE},
+    {"merged_cg",        "TNML_MERGED_CG",      OPT_INT,  &tnml_ctx::merged_cg,           nullptr,          0, 2,       HK_NONE},
+    {"defer_tail",       "TNML_DEFER_TAIL",     OPT_BOOL, &tnml_ctx::defer_tail,          nullptr,          0, 1,       HK_DEFER_TAIL},
+    {"check_replicas",   "TNML_CHECK_REPLICAS", OPT_INT,  &tnml_ctx::check_replicas_mode, nullptr,          0, 2,       HK_CHECK_REPLICAS},
+    {"fused_fwd",        "TNML_FUSED_FWD",      OPT_INT,  &tnml_ctx::fused_fwd,           nullptr,          0, INT_MAX, HK_NONE},   // > 2: always, with that many workgroups at most
+    {"fwd_res",          "TNML_FWD_RES",        OPT_INT,  &tnml_ctx::fwd_res,             nullptr,          0, 3,       HK_NONE},   // 3: the general form on 120 x 120 bonds too
+    {"shift_res",        "TNML_SHIFT_RES",      OPT_INT,  &tnml_ctx::shift_res,           nullptr,          0, 2,       HK_NONE},
+    {"res_grid",         nullptr,               OPT_INT,  &tnml_ctx::res_grid,            nullptr,          0, INT_MAX, HK_NONE},
+    {"res_pace",         "TNML_RES_PACE",       OPT_INT,  &tnml_ctx::res_pace,            nullptr,          0, 4,       HK_NONE},
+    {"grad_quad",        "TNML_GRAD_QUAD",      OPT_INT,  &tnml_ctx::grad_quad,           nullptr,          0, 2,       HK_NONE},
+    {"grad_pair",        "TNML_GRAD_PAIR",      OPT_BOOL, &tnml_ctx::grad_pair,           nullptr,          0, 1,       HK_NONE},
+    {"bgemm_wgs",        "TNML_BGEMM_WGS",      OPT_INT,  &tnml_ctx::bgemm_wgs,           nullptr,          0, INT_MAX, HK_NONE},
+    {"bgemm_per",        "TNML_BGEMM_PER",      OPT_INT,  &tnml_ctx::bgemm_per,           nullptr,          0, 1 << 20, HK_NONE},   // (x 32 images: stays an int)
+    {"sytrd_exit",       nullptr,               OPT_BOOL, &tnml_ctx::sytrd_exit,          nullptr,          0, 1,       HK_NONE},
+    {"bgs_chol",         "TNML_BGS_CHOL",       OPT_BOOL, &tnml_ctx::bgs_chol,            nullptr,          0, 1,       HK_NONE},
+    {"spec_split",       "TNML_SPEC_SPLIT",     OPT_BOOL, &tnml_ctx::spec_split,          nullptr,          0, 1,       HK_NONE},
+    {"debug_fail_split", nullptr,               OPT_INT,  &tnml_ctx::debug_fail_split,    nullptr,         -1, INT_MAX, HK_FAIL_SPLIT},
+    {"bf16_grad",        nullptr,               OPT_BOOL, &tnml_ctx::bf16_grad,           nullptr,          0, 1,       HK_NONE},
+    {"bf16_once",        nullptr,               OPT_BOOL, &tnml_ctx::bf16_once,           nullptr,          0, 1,       HK_NONE},
+    {"env_async",        nullptr,               OPT_BOOL, &tnml_ctx::env_async,           nullptr,          0, 1,       HK_NONE},
+    {"env_budget_mb",    nullptr,               OPT_INT,  nullptr,                        nullptr,          0, INT_MAX, HK_ENV_BUDGET},
+    {"comm_timeout_s",   nullptr,               OPT_INT,  &tnml_ctx::comm_timeout_s,      nullptr,          1, INT_MAX, HK_COMM_TIMEOUT},
+    {"cg_method",        nullptr,               OPT_INT,  &tnml_ctx::cg_method,           nullptr,          0, 2,       HK_CG_METHOD},
+    {"debug_nudge_rank", nullptr,               OPT_INT,  &tnml_ctx::debug_nudge_rank,    nullptr,         -1, INT_MAX, HK_NONE},
+    {"mc_spin_max",      nullptr,               OPT_INT,  &tnml_ctx::mc_spin_max,         nullptr,         -1, INT_MAX, HK_NONE},
+    {"svd_print",        "TNML_SVD_PRINT",      OPT_INT,  &tnml_ctx::svd_print,           nullptr,         -2, INT_MAX, HK_SVD_PRINT},
+    {"fg64_cfg",         "TNML_FG64_CFG",       OPT_INT,  &tnml_ctx::opt_fg64_cfg,        nullptr,          0, 2,       HK_NONE},
+    {"ldot_cfg",         "TNML_LDOT_CFG",       OPT_INT,  &tnml_ctx::opt_ldot_cfg,        nullptr,          0, 2,       HK_NONE},
+    {"pcut",             nullptr,               OPT_REAL, nullptr,                        &tnml_ctx::pcut,  0, HUGE_VAL, HK_NONE},
+    {"noise",            nullptr,               OPT_REAL, nullptr,                        &tnml_ctx::noise, 0, HUGE_VAL, HK_NOISE},
+};
+// checks v against the row, then the option's own refusals and side effects, then sets the field; `who` and `what` name the caller
+// and the option (or the environment variable) in a message
+static int apply_option(tnml_ctx* c, const OptDef& d, double v, const char* who, const char* what) {
+    if (d.kind != OPT_BOOL && !(v >= d.lo && v <= d.hi)) {
+        if (d.hi >= INT_MAX) return tnml_fail(c, "%s: %s = %.15g, must be >= %.15g", who, what, v, d.lo);
+        return tnml_fail(c, "%s: %s = %.15g, must be in %.15g..%.15g", who, what, v, d.lo, d.hi);
+    }
+    switch (d.hook) {
+        case HK_NONE: break;
+        case HK_REUSE_P: c->p_valid = false; break;
+        case HK_DEFER_TAIL: if (c->pend_count) return tnml_fail(c, "defer_tail: a bond update is in flight"); break;
+        case HK_CHECK_REPLICAS: c->check_replicas = v != 0; break;
+        case HK_ENV_BUDGET: c->env_budget_bytes = (long)v << 20; break;
+        case HK_COMM_TIMEOUT: local_comm_set_timeout(c, (int)v); break;
+        case HK_FAIL_SPLIT: c->spec_splits = 0; break;
+        case HK_SVD_PRINT: c->svd_calls = 0; break;
+        case HK_CG_METHOD:
+            if (v >= 1 && !c->single()) return tnml_fail(c, "cg_method: 0 (conj) or, in TNML_MODE_SINGLE, 1 (fast_conj) / 2 (exact)");
+            break;
+        case HK_NOISE:                                                 // single.cc:25,222: the noise of every sweep
+            if (v >= 1e-14 && !c->single()) return tnml_fail(c, "noise: the density-matrix split exists in the per-label variant only (single.h:648-672)");
+            if (v >= 1e-14 && !c->env64()) return tnml_fail(c, "noise: needs fp64 environments (dtype f64)");
+            break;
+    }
+    if (d.ifield) c->*d.ifield = d.kind == OPT_BOOL ? v != 0 : (int)v;
+    if (d.rfield) c->*d.rfield = v;
     return 0;
 }
+static int set_option(tnml_ctx* c, const char* who, const char* name, double v, bool real) {
+    if (!c || !name) return tnml_fail(c, "%s: null argument", who);
+    for (const OptDef& d : k_options)
+        if ((d.kind == OPT_REAL) == real && !strcmp(d.name, name)) return apply_option(c, d, v, who, name);
+    return tnml_fail(c, "%s: unknown option %s", who, name);
+}
+int tnml_set_option(tnml_ctx* c, const char* name, int value) { return set_option(c, "tnml_set_option", name, value, false); }
+int tnml_set_option_real(tnml_ctx* c, const char* name, double value) { return set_option(c, "tnml_set_option_real", name, value, true); }
 int tnml_synchronize(tnml_ctx* c) { HIPCK(c, hipStreamSynchronize(c->stream)); if (c->copy_stream) HIPCK(c, hipStreamSynchronize(c->copy_stream)); return ipc_comm_check(c); }
 int64_t tnml_device_bytes(tnml_ctx* c) { return c->bytes; }
 int64_t tnml_replica_repairs(tnml_ctx* c) { return c->replica_repairs; }
@@ -170,40 +212,83 @@ void tnml_shard_bounds(int64_t NT_total, int nranks, int rank, int64_t* begin, i
     *end = (rank == nranks - 1) ? NT_total : th * (rank + 1);
 }
 
-// ---- allocation helpers ---------------------------------------------------------------------
-template <typename T>
-static int dmalloc(tnml_ctx* c, T** p, size_t n) {
-    if (n == 0) n = 1;
-    hipError_t e = hipMalloc((void**)p, n * sizeof(T));
-    if (e != hipSuccess) return tnml_fail(c, "hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
-    c->bytes += (int64_t)(n * sizeof(T));
+// ---- workspace plan -------------------------------------------------------------------------
+static inline int ru16(int x) { return (x + 15) / 16 * 16; }
+// the dimensions and workspace sizes a configuration implies, and the shape of the site-tensor sets (tnml_create, tnml_estimate_bytes)
+static void ctx_plan(tnml_ctx* c, const tnml_config& cfg) {
+    c->cfg = cfg;
+    c->N = cfg.N; c->NT = cfg.NT_local; c->maxm = cfg.maxm;
+    c->c0 = cfg.mode == TNML_MODE_SINGLE ? -1 : cfg.N / 2;      // fixedL.cc:616; no Label site in the per-label variant
+    c->NTp = (cfg.NT_local + TNML_NTPAD - 1) / TNML_NTPAD * TNML_NTPAD;
+    const size_t NTp = c->NTp, m = c->maxm;
+    const int Kmax = c->bf16() ? (2 * c->maxm + 31) / 32 * 32 : ru16(2 * c->maxm);
+    c->mcap = (size_t)TNML_NL * Kmax * Kmax;
+    c->small_elems = m * NTp;
+    c->big_elems = TNML_NL * m * NTp;
+    c->svd_n = 2 * c->maxm;
+    c->slab_bytes = (size_t)128 * Kmax * Kmax * 4 * (c->f64() ? 2 : 1);
+    c->partial_cap = (int)(NTp / 64);
+    // sM holds (a) the Label-permuted bond matrix of the split, 40 maxm^2, and (b) the 16-padded site matrix of an
+    // environment shift, L * ru16(2 m) * ru16(m) -- at small maxm the padding of (b) dominates
+    c->sM_cap = std::max(40 * m * m, (size_t)TNML_NL * Kmax * ru16(c->maxm));
+    c->ebt_cap = c->bf16() ? bf16e_env_elems(c->maxm, c->NTp, c->bf16() == 2) : 0;   // bf16 copies of the forward pass's operands (kernels_bf16e.hip)
+    c->mbt_cap = c->bf16() ? bf16e_m_elems(c->maxm, c->bf16() == 2) : 0;
+    c->W.resize(c->N + 2);
+    c->env.resize(c->N + 2);
+    // speculative split: spare site tensors (two bond updates in flight replace two sites each; the Label site has its own size class)
+    c->spare_small.assign(4, nullptr);
+    c->spare_big.assign(c->c0 > 0 ? 2 : 0, nullptr);
+}
+// Every device buffer tnml_create allocates, in its order: the slot, its bytes, whether this configuration has it, and whether it is a
+// site tensor (W and the spares trade buffers during speculative splits: tnml_destroy frees those by their own rule)
+struct DevBuf { void** slot; size_t bytes; bool on, site; };
+static std::vector<DevBuf> device_buffers(tnml_ctx* c) {
+    const size_t NTp = c->NTp, m = c->maxm, n = c->svd_n, esz = c->esz(), eesz = c->eesz(), D = sizeof(double);
+    std::vector<DevBuf> v;
+    auto add = [&](auto& p, size_t bytes, bool on = true) { v.push_back({(void**)&p, bytes, on, false}); };
+    add(c->phi, c->N * 2 * NTp * eesz); add(c->label, NTp * sizeof(int)); add(c->ones, NTp * eesz);
+    add(c->U, c->big_elems * esz); add(c->P, TNML_NL * NTp * esz); add(c->dP, TNML_NL * NTp * esz); add(c->Pp, TNML_NL * NTp * esz);
+    add(c->Zp, c->small_elems * esz); add(c->Mf, c->mcap * sizeof(float)); add(c->slab, c->slab_bytes);
+    add(c->partials, c->partial_cap * 12 * D); add(c->partials2, c->partial_cap * 12 * D); add(c->counters, 16 * sizeof(unsigned));
+    add(c->Ppart, 2 * TNML_NL * NTp * D, c->cfg.dtype == TNML_F64 && c->cfg.mode == TNML_MODE_FIXEDL && m >= 33);   // k_fwd_res (input dimensions 33..120)
+    add(c->ebt, c->ebt_cap * sizeof(unsigned short), c->bf16() != 0); add(c->mbt, c->mbt_cap * sizeof(unsigned short), c->bf16() != 0);
+    add(c->vB, c->mcap * D); add(c->vR, c->mcap * D); add(c->vP, c->mcap * D); add(c->arbuf, (c->mcap + TNML_TAILN) * D); add(c->locals, 32 * D);
+    add(c->scal, (SC_N + 4 * TNML_MAX_PASS) * D);      // CG scalars, then the per-pass trace: one copy to the host
+    add(c->vpart, (1024 + 16) * D);     // [256][2] phase-1 partials, then [256][2] for |p|^2 of the next pass, then the summed cost of an output update
+    add(c->tB, c->mcap * D); add(c->tB2, c->mcap * D);
+    add(c->sM, c->sM_cap * D); add(c->sG, n * n * D); add(c->sD, n * D); add(c->sE, 2 * n * D); add(c->sF, (n * m + 2 * TNML_NL * m * m) * D);
+    add(c->sInfo, 4 * sizeof(int)); add(c->fprint, 2 * sizeof(unsigned long long));
+    add(c->sE2, n * D); add(c->sTau, n * D); add(c->sV, n * n * D); add(c->sC, n * n * D);
+    add(c->sW, (n + 8) * D);            // + room for the orthogonality check values behind the eigenvalues
+    add(c->sScr, std::max<size_t>(5 * n * m, TEIG_SCRATCH_DOUBLES) * D); add(c->sS, m * m * D); add(c->sCm, m * m * D); add(c->sQ1, n * m * D); add(c->sDev, 4 * D);
+    add(c->mc_xbuf, eigh_mc_xbuf_bytes(), n > 240);                  // multi-workgroup tridiagonalisation (eigh_mc.hip)
+    for (int j = 1; j <= c->N; ++j) v.push_back({(void**)&c->W[j].a, 2 * m * m * (j == c->c0 ? TNML_NL : 1) * D, true, true});   // the W replica
+    for (auto& p : c->spare_small) v.push_back({(void**)&p, 2 * m * m * D, true, true});
+    for (auto& p : c->spare_big) v.push_back({(void**)&p, 2 * m * m * TNML_NL * D, true, true});
+    return v;
+}
+static int dalloc(tnml_ctx* c, void** p, size_t bytes) {
+    hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) return tnml_fail(c, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    c->bytes += (int64_t)bytes;
     return 0;
 }
-int ctx_alloc_doubles(tnml_ctx* c, double** p, size_t n) { return dmalloc(c, p, n); }
-static inline int ru16(int x) { return (x + 15) / 16 * 16; }
+int ctx_alloc_doubles(tnml_ctx* c, double** p, size_t n) { return dalloc(c, (void**)p, (n ? n : 1) * sizeof(double)); }
 
-// Device memory a context of this configuration will own once a sweep has touched every environment: the workspaces of
-// tnml_create plus the environment slabs (about N/2 Label-carrying + N/2 Label-free environments
-// at any time = 0.55 N slabs of 10*maxm*NTp elements, + the three chain buffers of tnml_classify).
+// Device memory a context of this configuration will own once a sweep has touched every environment: the buffers of tnml_create
+// plus what is allocated on first use.
 int64_t tnml_estimate_bytes(const tnml_config* cfg) {
     if (!cfg || cfg->N < 1 || cfg->NT_local < 1 || cfg->maxm < 1) return -1;
-    const double NTp = (double)((cfg->NT_local + TNML_NTPAD - 1) / TNML_NTPAD * TNML_NTPAD);
-    const bool bf = cfg->dtype == TNML_BF16 || cfg->dtype == TNML_BF16X3;
-    const double m = cfg->maxm, Kmax = bf ? (2 * cfg->maxm + 31) / 32 * 32 : ru16(2 * cfg->maxm), n = 2. * m;   // (as tnml_create pads it)
-    const bool is64 = cfg->dtype == TNML_F64 || cfg->dtype == TNML_F64_E32;
-    const double esz = is64 ? 8 : 4, eesz = cfg->dtype == TNML_F64 ? 8 : 4;
-    const bool single = cfg->mode == TNML_MODE_SINGLE;
-    const double mcap = TNML_NL * Kmax * Kmax;
-    double b = cfg->N * 2. * NTp * eesz + NTp * (4 + eesz);                                  // features, labels, ones
-    b += (TNML_NL * m * NTp + 3. * TNML_NL * NTp + m * NTp) * esz;                          // U, P, dP, Pp, Zp
-    b += mcap * (4 + 6 * 8) + 128. * Kmax * Kmax * 4 * (is64 ? 2 : 1);    // Mf, vB vR vP [tail|G] tB tB2, split-K slabs
-    b += 8. * (std::max(40. * m * m, TNML_NL * Kmax * (double)ru16(cfg->maxm)) + 3. * n * n + 7. * n * m + 2. * TNML_NL * m * m + 2. * m * m);   // split workspaces
-    b += 8. * (cfg->N - 1 + TNML_NL) * 2. * m * m;                                            // W replica
-    b += 8. * (4 + 2 * TNML_NL) * 2. * m * m;                                                 // spare site tensors of the speculative split
-    if (2 * cfg->maxm > 240) b += (double)eigh_mc_xbuf_bytes();                               // exchange buffer of the multi-workgroup tridiagonalisation
-    if (single) b += 8. * (5. * m * NTp + 3. * NTp + 3. * m * m);                             // workspace of the noise split (allocated on first use with noise > 0)
-    const double nslab = single ? (cfg->N / 10. + 2.) : (0.55 * cfg->N + 3.);
-    b += nslab * TNML_NL * m * NTp * eesz;
+    tnml_ctx t;
+    ctx_plan(&t, *cfg);
+    double b = 0.;
+    for (const DevBuf& d : device_buffers(&t)) if (d.on) b += (double)d.bytes;
+    const double m = t.maxm, NTp = t.NTp;
+    // the environment slabs (about N/2 Label-carrying + N/2 Label-free environments at any time = 0.55 N slabs
+    // of 10*maxm*NTp elements, + the three chain buffers of tnml_classify; the per-label variant: N Label-free environments, 10 per slab)
+    const double nslab = t.single() ? (t.N / 10. + 2.) : (0.55 * t.N + 3.);
+    b += nslab * TNML_NL * m * NTp * t.eesz();
+    if (t.single()) b += 8. * (5. * m * NTp + 3. * NTp + 3. * m * m);       // noise_ws: the workspace of the noise split (svd.hip, first use with noise > 0)
     return (int64_t)b;
 }
 int tnml_device_memory(int device, int64_t* free_bytes, int64_t* total_bytes) {
@@ -256,129 +341,38 @@ int tnml_create(tnml_ctx** out, const tnml_config* cfg) {
     if (cfg->device < 0 || cfg->device >= ndev) return tnml_fail(nullptr, "tnml_create: device %d out of range (%d visible)", cfg->device, ndev);
     if (hipSetDevice(cfg->device) != hipSuccess) return tnml_fail(nullptr, "tnml_create: hipSetDevice failed");
     tnml_ctx* c = new tnml_ctx();
-    c->cfg = *cfg;
-    c->N = cfg->N; c->NT = cfg->NT_local; c->maxm = cfg->maxm;
-    c->c0 = cfg->mode == TNML_MODE_SINGLE ? -1 : cfg->N / 2;      // fixedL.cc:616; no Label site in the per-label variant
-    c->NTp = (cfg->NT_local + TNML_NTPAD - 1) / TNML_NTPAD * TNML_NTPAD;
+    ctx_plan(c, *cfg);
     int rc = 0;
     auto bail = [&](int r) { g_create_err = c->err; tnml_destroy(c); return r; };
+    for (const OptDef& d : k_options)                         // the environment's defaults of the options
+        if (const char* e = d.env ? getenv(d.env) : nullptr)
+            if ((rc = apply_option(c, d, atoi(e), "tnml_create", d.env))) return bail(rc);
+    if (const char* e = getenv("TNML_SVD_BACKEND")) c->cfg.svd_backend = atoi(e);
+    if (const char* e = getenv("TNML_SVD_DUMP")) c->svd_dump = e;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(tnml_fail(c, "hipStreamCreate failed"));
-    if (const char* e = getenv("TNML_FUSED_FWD")) c->fused_fwd = atoi(e);
-    if (const char* e = getenv("TNML_FWD_RES")) c->fwd_res = atoi(e);
-    if (const char* e = getenv("TNML_SHIFT_RES")) c->shift_res = atoi(e);
-    if (const char* e = getenv("TNML_RES_PACE")) c->res_pace = atoi(e);
-    if (const char* e = getenv("TNML_BGEMM_WGS")) c->bgemm_wgs = atoi(e);
-    if (const char* e = getenv("TNML_GRAD_QUAD")) c->grad_quad = atoi(e);
-    if (const char* e = getenv("TNML_GRAD_PAIR")) c->grad_pair = atoi(e);
-    if (const char* e = getenv("TNML_GRAD_PAIR_MIN")) c->grad_pair_min = atoi(e);
-    if (const char* e = getenv("TNML_GRAD_PAIR_MAX")) c->grad_pair_max = atoi(e);
-    if (const char* e = getenv("TNML_BGEMM_PER")) c->bgemm_per = atoi(e);
-    if (const char* e = getenv("TNML_BGS_CHOL")) c->bgs_chol = atoi(e) != 0;
-    if (const char* e = getenv("TNML_SMALL_GEMM")) c->small_gemm = atoi(e) != 0;
     if (rocblas_create_handle(&c->blas) != rocblas_status_success) return bail(tnml_fail(c, "rocblas_create_handle failed"));
     rocblas_set_stream(c->blas, c->stream);
     // replicas of W must stay bit-identical over the ranks: no atomics-based split-K inside rocBLAS
     rocblas_set_atomics_mode(c->blas, rocblas_atomics_not_allowed);
-    const size_t NTp = c->NTp;
-    const int Kmax = c->bf16() ? (2 * c->maxm + 31) / 32 * 32 : ru16(2 * c->maxm);
-    c->mcap = (size_t)TNML_NL * Kmax * Kmax;
-    c->small_elems = (size_t)c->maxm * NTp;
-    c->big_elems = (size_t)TNML_NL * c->maxm * NTp;
-    c->svd_n = 2 * c->maxm;
-    c->slab_bytes = (size_t)128 * Kmax * Kmax * 4 * ((cfg->dtype == TNML_F64 || cfg->dtype == TNML_F64_E32) ? 2 : 1);
-    c->partial_cap = (int)(NTp / 64);
-    c->W.resize(c->N + 2);
-    c->env.resize(c->N + 2);
-    if ((rc = dmalloc(c, (char**)&c->phi, (size_t)c->N * 2 * NTp * c->eesz()))) return bail(rc);
-    if ((rc = dmalloc(c, &c->label, NTp))) return bail(rc);
-    if ((rc = dmalloc(c, (char**)&c->ones, NTp * c->eesz()))) return bail(rc);
-    const size_t esz = c->esz();
-    if ((rc = dmalloc(c, (char**)&c->U, c->big_elems * esz))) return bail(rc);
-    if ((rc = dmalloc(c, (char**)&c->P, (size_t)TNML_NL * NTp * esz))) return bail(rc);
-    if ((rc = dmalloc(c, (char**)&c->dP, (size_t)TNML_NL * NTp * esz))) return bail(rc);
-    if ((rc = dmalloc(c, (char**)&c->Pp, (size_t)TNML_NL * NTp * esz))) return bail(rc);
-    if (const char* e = getenv("TNML_FAST_CG")) c->fast_cg = atoi(e) != 0;
-    if (const char* e = getenv("TNML_FUSE_Z")) c->fuse_z = atoi(e) != 0;
-    if (const char* e = getenv("TNML_REUSE_P")) c->reuse_p = atoi(e) != 0;
-    if (const char* e = getenv("TNML_MERGED_CG")) c->merged_cg = atoi(e);
-    if (const char* e = getenv("TNML_DEFER_TAIL")) c->defer_tail = atoi(e) != 0;
-    if (const char* e = getenv("TNML_FG64_CFG")) c->opt_fg64_cfg = atoi(e);
-    if (const char* e = getenv("TNML_LDOT_CFG")) c->opt_ldot_cfg = atoi(e);
-    if ((rc = dmalloc(c, (char**)&c->Zp, c->small_elems * esz))) return bail(rc);
-    if ((rc = dmalloc(c, &c->Mf, c->mcap))) return bail(rc);
-    if ((rc = dmalloc(c, (char**)&c->slab, c->slab_bytes))) return bail(rc);
-    if ((rc = dmalloc(c, &c->partials, (size_t)c->partial_cap * 12))) return bail(rc);
-    if ((rc = dmalloc(c, &c->partials2, (size_t)c->partial_cap * 12))) return bail(rc);
-    if ((rc = dmalloc(c, &c->counters, 16))) return bail(rc);
-    if (hipMemsetAsync(c->counters, 0, 16 * sizeof(unsigned), c->stream) != hipSuccess) return bail(tnml_fail(c, "memset failed"));
-    if (cfg->dtype == TNML_F64 && cfg->mode == TNML_MODE_FIXEDL && c->maxm >= 33 && (rc = dmalloc(c, &c->Ppart, (size_t)2 * TNML_NL * NTp))) return bail(rc);   // k_fwd_res (input dimensions 33..120)
-    if (c->bf16()) {                                    // bf16 copies of the forward pass's operands (kernels_bf16e.hip)
-        c->ebt_cap = bf16e_env_elems(c->maxm, NTp, c->bf16() == 2); c->mbt_cap = bf16e_m_elems(c->maxm, c->bf16() == 2);
-        if ((rc = dmalloc(c, &c->ebt, c->ebt_cap)) || (rc = dmalloc(c, &c->mbt, c->mbt_cap))) return bail(rc);
-    }
-    if ((rc = dmalloc(c, &c->vB, c->mcap))) return bail(rc);
-    if ((rc = dmalloc(c, &c->vR, c->mcap))) return bail(rc);
-    if ((rc = dmalloc(c, &c->vP, c->mcap))) return bail(rc);
-    if ((rc = dmalloc(c, &c->arbuf, c->mcap + TNML_TAILN))) return bail(rc);
+    for (const DevBuf& d : device_buffers(c))
+        if (d.on && (rc = dalloc(c, d.slot, d.bytes))) return bail(rc);
     c->tail = c->arbuf; c->vG = c->arbuf + TNML_TAILN;
-    if ((rc = dmalloc(c, &c->locals, 32))) return bail(rc);
-    if ((rc = dmalloc(c, &c->scal, SC_N + (size_t)4 * TNML_MAX_PASS))) return bail(rc);   // CG scalars, then the per-pass trace: one copy to the host
     c->cgtrace = c->scal + SC_N;
-    if ((rc = dmalloc(c, &c->vpart, 1024 + 16))) return bail(rc);   // [256][2] phase-1 partials, then [256][2] for |p|^2 of the next pass, then the summed cost of an output update
-    if ((rc = dmalloc(c, &c->tB, c->mcap))) return bail(rc);
-    if ((rc = dmalloc(c, &c->tB2, c->mcap))) return bail(rc);
-    // sM holds (a) the Label-permuted bond matrix of the split, 40 maxm^2, and (b) the 16-padded site matrix of an
-    // environment shift, L * ru16(2 m) * ru16(m) -- at small maxm the padding of (b) dominates
-    c->sM_cap = std::max((size_t)40 * c->maxm * c->maxm, (size_t)TNML_NL * Kmax * ru16(c->maxm));
-    if ((rc = dmalloc(c, &c->sM, c->sM_cap))) return bail(rc);
-    if ((rc = dmalloc(c, &c->sG, (size_t)c->svd_n * c->svd_n))) return bail(rc);
-    if ((rc = dmalloc(c, &c->sD, (size_t)c->svd_n))) return bail(rc);
-    if ((rc = dmalloc(c, &c->sE, (size_t)2 * c->svd_n))) return bail(rc);
-    if ((rc = dmalloc(c, &c->sF, (size_t)c->svd_n * c->maxm + (size_t)2 * TNML_NL * c->maxm * c->maxm))) return bail(rc);
-    if ((rc = dmalloc(c, &c->sInfo, 4))) return bail(rc);
-    if ((rc = dmalloc(c, &c->fprint, 2))) return bail(rc);
-    if (const char* e = getenv("TNML_CHECK_REPLICAS")) { c->check_replicas = atoi(e) != 0; c->check_replicas_mode = atoi(e); }
-    if ((rc = dmalloc(c, &c->sE2, (size_t)c->svd_n))) return bail(rc);
-    if ((rc = dmalloc(c, &c->sTau, (size_t)c->svd_n))) return bail(rc);
-    if ((rc = dmalloc(c, &c->sV, (size_t)c->svd_n * c->svd_n))) return bail(rc);
-    if ((rc = dmalloc(c, &c->sC, (size_t)c->svd_n * c->svd_n))) return bail(rc);
-    if ((rc = dmalloc(c, &c->sW, (size_t)c->svd_n + 8))) return bail(rc);           // + room for the orthogonality check values behind the eigenvalues
-    if ((rc = dmalloc(c, &c->sScr, std::max<size_t>((size_t)5 * c->svd_n * c->maxm, TEIG_SCRATCH_DOUBLES)))) return bail(rc);
-    if ((rc = dmalloc(c, &c->sS, (size_t)c->maxm * c->maxm))) return bail(rc);
-    if ((rc = dmalloc(c, &c->sCm, (size_t)c->maxm * c->maxm))) return bail(rc);
-    if ((rc = dmalloc(c, &c->sQ1, (size_t)c->svd_n * c->maxm))) return bail(rc);
-    if ((rc = dmalloc(c, &c->sDev, 4))) return bail(rc);
-    if (c->svd_n > 240) {                               // multi-workgroup tridiagonalisation (eigh_mc.hip)
-        if ((rc = dmalloc(c, (char**)&c->mc_xbuf, eigh_mc_xbuf_bytes()))) return bail(rc);
-        if (hipMemsetAsync(c->mc_xbuf, 0, eigh_mc_xbuf_bytes(), c->stream) != hipSuccess) return bail(tnml_fail(c, "memset failed"));
-    }
-    if (const char* e = getenv("TNML_SVD_BACKEND")) c->cfg.svd_backend = atoi(e);
-    if (const char* e = getenv("TNML_SVD_PRINT")) c->svd_print = atoi(e);
-    if (const char* e = getenv("TNML_SVD_DUMP")) c->svd_dump = e;
     for (int k = 0; k < 2; ++k)
         if (hipEventCreateWithFlags(&c->pend[k].ev, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->pend[k].ev2, hipEventDisableTiming) != hipSuccess)
             return bail(tnml_fail(c, "hipEventCreate failed"));
     if (hipHostMalloc((void**)&c->h_scal, sizeof(double) * (2 * c->svd_n + 64 + SC_N + 4 * TNML_MAX_PASS + 2 * 64)) != hipSuccess) return bail(tnml_fail(c, "hipHostMalloc failed"));
-    for (int j = 1; j <= c->N; ++j) {
-        const size_t cap = (size_t)2 * c->maxm * c->maxm * (j == c->c0 ? TNML_NL : 1);
-        if ((rc = dmalloc(c, &c->W[j].a, cap))) return bail(rc);
-    }
-    // speculative split: pinned mirrors [eigenvalues + 4 check values | CG scalars + trace] per bond update in flight, and spare site
-    // tensors (two bond updates in flight replace two sites each; the Label site has its own size class)
+    // speculative split: pinned mirrors [eigenvalues + 4 check values | CG scalars + trace] per bond update in flight
     c->hrep_stride = (size_t)c->svd_n + 8 + SC_N + (size_t)4 * TNML_MAX_PASS + 512 + 64;      // eigenvalues + checks | scal + trace | norm partial pairs | after-SVD scalars
     if (hipHostMalloc((void**)&c->hrep, sizeof(double) * 2 * c->hrep_stride) != hipSuccess) return bail(tnml_fail(c, "hipHostMalloc failed"));
     if (hipHostMalloc((void**)&c->hcost, sizeof(double) * 2 * (size_t)c->partial_cap * 12) != hipSuccess) return bail(tnml_fail(c, "hipHostMalloc failed"));
     memset(c->hrep, 0, sizeof(double) * 2 * c->hrep_stride);
-    for (int k = 0; k < 4 + (c->c0 > 0 ? 2 : 0); ++k) {
-        double* sp = nullptr;
-        if ((rc = dmalloc(c, &sp, (size_t)2 * c->maxm * c->maxm * (k >= 4 ? TNML_NL : 1)))) return bail(rc);
-        (k >= 4 ? c->spare_big : c->spare_small).push_back(sp);
-    }
-    if (const char* e = getenv("TNML_SPEC_SPLIT")) c->spec_split = atoi(e);
-    if (hipMemsetAsync(c->arbuf, 0, sizeof(double) * (c->mcap + TNML_TAILN), c->stream) != hipSuccess) return bail(tnml_fail(c, "memset failed"));
-    if (hipMemsetAsync(c->locals, 0, sizeof(double) * 32, c->stream) != hipSuccess) return bail(tnml_fail(c, "memset failed"));
-    if (hipMemsetAsync(c->scal, 0, sizeof(double) * SC_N, c->stream) != hipSuccess) return bail(tnml_fail(c, "memset failed"));
-    if ((rc = c->env64() ? launch_fill_f64(c, (double*)c->ones, 1.0, NTp) : launch_fill_f32(c, (float*)c->ones, 1.0f, NTp))) return bail(rc);
+    if (hipMemsetAsync(c->counters, 0, 16 * sizeof(unsigned), c->stream) != hipSuccess ||
+        (c->mc_xbuf && hipMemsetAsync(c->mc_xbuf, 0, eigh_mc_xbuf_bytes(), c->stream) != hipSuccess) ||
+        hipMemsetAsync(c->arbuf, 0, sizeof(double) * (c->mcap + TNML_TAILN), c->stream) != hipSuccess ||
+        hipMemsetAsync(c->locals, 0, sizeof(double) * 32, c->stream) != hipSuccess ||
+        hipMemsetAsync(c->scal, 0, sizeof(double) * SC_N, c->stream) != hipSuccess) return bail(tnml_fail(c, "memset failed"));
+    if ((rc = c->env64() ? launch_fill_f64(c, (double*)c->ones, 1.0, c->NTp) : launch_fill_f32(c, (float*)c->ones, 1.0f, c->NTp))) return bail(rc);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return bail(tnml_fail(c, "sync failed"));
     *out = c;
     return 0;
@@ -395,17 +389,17 @@ int tnml_destroy(tnml_ctx* c) {
     for (auto& p : c->prof_pending) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     for (auto e : c->prof_free) (void)hipEventDestroy(e);
     for (auto& p : c->redo_events) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    void* ptrs[] = {c->phi, c->label, c->ones, c->U, c->P, c->dP, c->Pp, c->Zp, c->Mf, c->slab, c->partials, c->partials2, c->vB, c->vR, c->vP,
-                    c->arbuf, c->locals, c->scal, c->vpart, c->counters, c->Ppart, c->tB, c->tB2, c->sM, c->sG, c->sD, c->sE, c->sF, c->sInfo, c->sE2, c->sTau, c->sV, c->sC, c->sW, c->sScr, c->sS, c->sCm, c->sQ1, c->sDev, c->mc_xbuf, c->fprint, c->noise_ws, c->ebt, c->mbt};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    // (site tensors and spares have changed places during speculative splits: every buffer is in exactly one of the two sets)
+    for (const DevBuf& d : device_buffers(c)) if (!d.site && *d.slot) (void)hipFree(*d.slot);
+    // (site tensors and spares have changed places during speculative splits: every buffer is in exactly one of the two sets,
+    // or held by the undo record of a bond update in flight)
     for (auto& s : c->W) if (s.a) (void)hipFree(s.a);
-    for (size_t k = 0; k < c->spare_small.size(); ++k) (void)hipFree(c->spare_small[k]);
-    for (size_t k = 0; k < c->spare_big.size(); ++k) (void)hipFree(c->spare_big[k]);
+    for (size_t k = 0; k < c->spare_small.size(); ++k) if (c->spare_small[k]) (void)hipFree(c->spare_small[k]);
+    for (size_t k = 0; k < c->spare_big.size(); ++k) if (c->spare_big[k]) (void)hipFree(c->spare_big[k]);
     for (int k = 0; k < 2; ++k) for (int u = 0; u < c->pend[k].nundo; ++u) if (c->pend[k].undo[u].old) (void)hipFree(c->pend[k].undo[u].old);
+    if (c->noise_ws) (void)hipFree(c->noise_ws);          // allocated on first use
+    for (auto& sl : c->slabs) if (sl.base) (void)hipFree(sl.base);
     if (c->hrep) (void)hipHostFree(c->hrep);
     if (c->hcost) (void)hipHostFree(c->hcost);
-    for (auto& sl : c->slabs) if (sl.base) (void)hipFree(sl.base);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     if (c->ev_compute) (void)hipEventDestroy(c->ev_compute);
     for (auto& e : c->env) { if (e.host) { if (e.host_pinned) (void)hipHostFree(e.host); else free(e.host); } if (e.ev) (void)hipEventDestroy(e.ev); }
@@ -1140,7 +1134,7 @@ static int cgrad_device(tnml_ctx* c, int npass, double lambda, double cconv, boo
     const bool merged = c->fast_cg && !fastc && (c->merged_cg >= 2 || (c->merged_cg == 1 && c->multi()));
     // one rank, literal pass order: the per-block partial sums of a pAp pass / an output update are summed by the CG step kernel that
     // consumes them (k_cg_step2: sum |p.v|^2, k_cg_resid2: the cost of the trace) -- seven k_reduce_partials launches less per bond update
-    const bool fold = c->fold_reduce && !c->multi() && !merged && !fastc && c->fast_cg;
+    const bool fold = !c->multi() && !merged && !fastc && c->fast_cg;
     // one rank, fp64: the slab reduction of every gradient GEMM is folded into the CG vector kernel that consumes G, the output update
     // P <- P + a (p*t.v) rides in the CG step kernel, and k_cg_init2's work is split between its neighbours (round 5: eight launches less)
     c->defer_slab = fold && c->f64();
@@ -1465,16 +1459,6 @@ int tnml_exact(tnml_ctx* c, double* B, double lambda, double pcut) {   // single
     c->p_valid = false;
     TCK(exact_device(c, lambda, pcut));
     return download_bond(c, c->vB, B);
-}
-int tnml_set_option_real(tnml_ctx* c, const char* name, double value) {
-    if (!strcmp(name, "pcut")) { if (!(value >= 0.)) return tnml_fail(c, "pcut must be >= 0"); c->pcut = value; return 0; }
-    if (!strcmp(name, "noise")) {                                     // single.cc:25,222: the noise of every sweep
-        if (!(value >= 0.)) return tnml_fail(c, "noise must be >= 0");
-        if (value >= 1e-14 && !c->single()) return tnml_fail(c, "noise: the density-matrix split exists in the per-label variant only (single.h:648-672)");
-        if (value >= 1e-14 && !c->env64()) return tnml_fail(c, "noise: needs fp64 environments (dtype f64)");
-        c->noise = value; return 0;
-    }
-    return tnml_fail(c, "tnml_set_option_real: unknown option %s", name);
 }
 int tnml_cgrad(tnml_ctx* c, double* B, int npass, double lambda, double cconv, tnml_cg_trace* trace) {
     CollScope coll_(c);

@@ -109,12 +109,12 @@ struct tnml_ctx {
     tnml_config cfg;
     int N = 0, NT = 0, NTp = 0, c0 = 0, maxm = 0;
     hipStream_t stream = nullptr;
-    int fused_fwd = 1;               // forward pass as one persistent kernel (kernels_fused.hip): 1 = from 14 336 images per rank on, 0 never, 2 always; env TNML_FUSED_FWD / option "fused_fwd"
+    int fused_fwd = 1;               // forward pass as one persistent kernel (kernels_fused.hip): 1 = from 14 336 images per rank on, 0 never, 2 always, > 2 always with that many workgroups at most; env TNML_FUSED_FWD / option "fused_fwd"
     int cg_method = 0;               // per-label variant: 0 = conj (single.h:162-288), 1 = fast_conj (single.h:290-398), 2 = exact (single.h:117-160); option "cg_method"
     double pcut = 1e-8;              // PCut of the exact solver (single.cc:50); tnml_set_option_real "pcut"
     double noise = 0.;               // per-label variant: sweeps.noise() (single.cc:25,222); >= 1e-14 selects the density-matrix split of single.h:648-672; tnml_set_option_real "noise"
     double* noise_ws = nullptr;      // its workspace, allocated with the first such split
-    int sytrd_exit = 1;              // rank-adaptive exit of the tridiagonalisation of the split's Gram matrix (eigh.hip); option "sytrd_exit", env TNML_SYTRD_TOL=0 disables
+    int sytrd_exit = 1;              // rank-adaptive exit of the tridiagonalisation of the split's Gram matrix (eigh.hip); option "sytrd_exit"
     rocblas_handle blas = nullptr;
     ncclComm_t comm = nullptr;
     struct LocalComm* local = nullptr;   // in-process communicator of ranks sharing one device (local_comm.hip)
@@ -140,13 +140,13 @@ struct tnml_ctx {
     void* P = nullptr;         // [10][NTp]
     void* dP = nullptr;        // [10][NTp]
     void* Pp = nullptr;        // [10][NTp]  p*t.v of the last pAp pass (fast CG)
-    bool fuse_z = true;        // gradient GEMM builds Z from EL and dP itself instead of a k_zprime pass (env TNML_FUSE_Z=0 disables)
-    bool fast_cg = true;       // P <- P + a (p*t.v) instead of re-running the forward GEMM (env TNML_FAST_CG=0 disables)
+    int fuse_z = 1;            // gradient GEMM builds Z from EL and dP itself instead of a k_zprime pass; option "fuse_z", env TNML_FUSE_Z
+    int fast_cg = 1;           // P <- P + a (p*t.v) instead of re-running the forward GEMM; option "fast_cg", env TNML_FAST_CG
     // The per-image outputs P_n = W.Phi(x_n) belong to the network, not to the bond they are evaluated at: the "after SVD"
     // quadcost of one bond update leaves in P/dP exactly what the first gradient evaluation of the next bond update would
     // recompute with its own forward GEMM + label dot.  p_valid marks P/dP as current; anything that changes W, the data or
-    // P itself clears it (env TNML_REUSE_P=0 disables the shortcut).
-    bool reuse_p = true, p_valid = false;
+    // P itself clears it (option "reuse_p", env TNML_REUSE_P: 0 disables the shortcut).
+    int reuse_p = 1; bool p_valid = false;
     long env_budget_bytes = 0;           // option env_budget_mb: cap on the environment slabs held on the device (0: none); beyond it environments spill to host memory
     int env_protect[4] = {0, 0, 0, 0};   // sites whose environments must stay on the device (the operands of the operation in flight)
     long env_spills = 0, env_fetches = 0, env_prefetches = 0;
@@ -158,11 +158,10 @@ struct tnml_ctx {
     const void* ebt_src = nullptr; int ebt_m = 0; unsigned long ebt_epoch = 0, env_epoch = 1;        // what the environment copy was made from; env_epoch advances with every write of an environment
     bool attr_bf16e = false;
     int bf16_grad = 1;                   // option bf16_grad: in the bf16 modes the gradient GEMM runs on the bf16 pipe too (0: the fp32 kernel, as through round 3)
-    int small_gemm = 1;                  // option small_gemm: the split's products on k_dgemm_small (0: rocBLAS, as through round 4)
-    int bgs_chol = 1;                    // option bgs_chol: block Gram-Schmidt Cholesky QR for 128 < kept columns <= 384 (0: rocSOLVER dpotrf + dtrsm)
+    int bgs_chol = 1;                    // option bgs_chol, env TNML_BGS_CHOL: block Gram-Schmidt Cholesky QR for 128 < kept columns <= 384 (0: rocSOLVER dpotrf + dtrsm)
     int coll_depth = 0;                  // >0 inside an entry point that every rank calls in step (tnml_fail then aborts an in-process communicator)
     int comm_timeout_s = 120;            // option comm_timeout_s: how long a rank of an in-process communicator waits for its peers
-    int opt_fg64_cfg = 0, opt_ldot_cfg = 0;   // kernel-instantiation overrides (0: chosen by the image count)
+    int opt_fg64_cfg = 0, opt_ldot_cfg = 0;   // kernel-instantiation overrides (0: chosen by the image count); options "fg64_cfg", "ldot_cfg", env TNML_FG64_CFG, TNML_LDOT_CFG
     void* Zp = nullptr;        // [maxm][NTp]
     float* Mf = nullptr;       // fp32 GEMM operand, M-layout, capacity 10*Kmax*Kmax (env shifts, F32 mode)
     void* slab = nullptr;      // split-K partial slabs
@@ -182,7 +181,6 @@ struct tnml_ctx {
     bool rr_from_part = false;   // |r|^2 of the CG's start is still in k_cg_init1's partial sums (no k_cg_init2 launch)
     int partial_cap = 0;
     int part_n = 0;              // rows of `partials` the last forward pass / output update wrote
-    bool fold_reduce = true;     // one rank: the CG step kernels sum those rows themselves (no k_reduce_partials launch inside a CG pass); option "fold_reduce"
     double *vB = nullptr, *vR = nullptr, *vP = nullptr;   // CG vectors, M-layout fp64
     double* arbuf = nullptr;   // the all-reduce buffer [tail | G]
     double* tail = nullptr;    // = arbuf
@@ -191,7 +189,7 @@ struct tnml_ctx {
     int merged_cg = 1;         // (1: with a communicator, 2: always, 0: never) CG passes with ONE all-reduce each: A p = sum_n (p.v_n) v_n is formed from the pAp pass's outputs before alpha is
                                // known and rides with sum |p.v_n|^2; the residual follows r <- r - alpha (A p + lambda p) (the structure of the
                                // reference's own fast_cgrad, single.h:347-379).  Needs fast_cg.  env TNML_MERGED_CG / option "merged_cg"
-    bool defer_tail = true;    // multi-rank: the after-SVD cost partials and the replica fingerprint ride in the next bond update's first all-reduce
+    int defer_tail = 1;        // multi-rank: the after-SVD cost partials and the replica fingerprint ride in the next bond update's first all-reduce; option "defer_tail", env TNML_DEFER_TAIL
     int carry_slot = -1;       // pending report whose carried slots have not been reduced yet
     long allreduce_calls = 0, bcast_calls = 0;  // collectives entered: sum all-reduces (the payload) and broadcasts (rank 0's eigenvalues), for tests and the bench line
     double* scal = nullptr;    // device scalars [SC_N]
@@ -211,25 +209,25 @@ struct tnml_ctx {
     unsigned mc_epoch = 0;
     int mc_spin_max = -1;      // polls before a waiting thread of k_sytrd_mc gives up (-1: default; option "mc_spin_max", 0 in the fallback test)
     bool attr_sr[32] = {false}, attr_fr[4][32] = {{false}};   // LDS attribute set (per device = per context) for k_shift_res<NKS> / k_fwd_res<.., NKA, GEN, NST>: [2 GEN + (NST == 4)][NKA]
-    int res_pace = 0;                // pacing of the GEMM waves of k_fwd_res (0: default; option "res_pace")
-    int fwd_res = 1;                 // forward pass on k_fwd_res (kernels_res.hip): 1 = from 7 680 images per rank on, 0 never, 2 always; option "fwd_res"
-    int shift_res = 1;               // Label-carrying environment shift on k_shift_res (kernels_res.hip): 1 = from 7 680 images per rank on, 0 never, 2 always; option "shift_res"
-    int res_grid = 0;                // test knob: workgroups of the resident-operand kernels (0: one per CU)
+    int res_pace = 0;                // pacing of the GEMM waves of k_fwd_res (0: default, 1..4 the others; option "res_pace", env TNML_RES_PACE)
+    int fwd_res = 1;                 // forward pass on k_fwd_res (kernels_res.hip): 1 = from 7 680 images per rank on, 0 never, 2 always, 3 the general form on 120 x 120 bonds too; option "fwd_res", env TNML_FWD_RES
+    int shift_res = 1;               // Label-carrying environment shift on k_shift_res (kernels_res.hip): 1 = from 7 680 images per rank on, 0 never, 2 always; option "shift_res", env TNML_SHIFT_RES
+    int res_grid = 0;                // test knob: workgroups of the resident-operand kernels (0: one per CU); option "res_grid"
     int grad_quad = 1;               // gradient GEMM on k_grad_quad (kernels_grad.hip; m = 120, fp64 storage, Label on an environment): 1 = from 4 096 images per rank on, 0 never, 2 always; option "grad_quad", env TNML_GRAD_QUAD
     bool attr_gq = false, attr_gp = false;
-    int grad_pair = 1;               // bonds up to 64 x 64: the pair form of k_grad_quad (128 x 128 tile grid, two workgroups): 1 = for grad_pair_min^2 <= mI mO <= grad_pair_max^2 (and whenever grad_quad = 2 forces the kernel), 0 = never (the quad form when forced)
-    int grad_pair_min = 33, grad_pair_max = 56;      // sqrt(mI mO) range the pair form takes unforced
-    int bgemm_per = 0;               // probe knob (TNML_BGEMM_PER): images per slab of the gradient GEMM, in units of 32 (0: derived from bgemm_wgs)
-    int bgemm_wgs = 0;               // workgroups the gradient GEMM aims at when it cuts the image range into slabs (0: per-shape default; option "bgemm_wgs")
+    int grad_pair = 1;               // bonds up to 64 x 64: the pair form of k_grad_quad (128 x 128 tile grid, two workgroups): 1 = for 33^2 <= mI mO <= 56^2 (and whenever grad_quad = 2 forces the kernel), 0 = never (the quad form when forced); option "grad_pair", env TNML_GRAD_PAIR
+    int bgemm_per = 0;               // probe knob: images per slab of the gradient GEMM, in units of 32 (0: derived from bgemm_wgs); option "bgemm_per", env TNML_BGEMM_PER
+    int bgemm_wgs = 0;               // workgroups the gradient GEMM aims at when it cuts the image range into slabs (0: per-shape default; option "bgemm_wgs", env TNML_BGEMM_WGS)
     unsigned* counters = nullptr;    // [16] device: arrival counters of the "last workgroup reduces" kernels (zero between launches)
     double* Ppart = nullptr;         // [2][10][NTp]: per-half outputs of k_fwd_res
     bool attr_sytrd = false, attr_invit = false, attr_fused = false;   // per-device function attributes set (a process may drive several devices)
     int cu_count = 0;
-    // Speculative split (option spec_split, default on): when the truncation cannot change the outcome (minm >= the columns the split may keep)
+    // Speculative split (option spec_split, env TNML_SPEC_SPLIT, default on): when the truncation cannot change the outcome (minm >= the columns the split may keep)
     // the new bond dimension is known without the eigenvalues, so the split is enqueued WITHOUT its host synchronisation; eigenvalues and
     // check values are mirrored into pinned host memory by the kernels that produce them and read by tnml_bond_update_end.  The new site
     // tensors go to spare buffers; a failed check rolls the sites back and repeats the bond update with the synchronous split.
-    int spec_split = 1; bool force_safe = false; long spec_redos = 0, spec_splits = 0; int debug_fail_split = -1;
+    int spec_split = 1; bool force_safe = false; long spec_redos = 0, spec_splits = 0;
+    int debug_fail_split = -1;      // test hook (option "debug_fail_split" = k >= 0): the k-th speculative split reports a failed check
     long spec_splits_total = 0; double redo_ms = 0.; std::vector<std::pair<hipEvent_t, hipEvent_t>> redo_events;   // tnml_split_stats
     std::vector<double*> spare_small, spare_big;   // spare site-tensor buffers (capacity 2 maxm^2, x 10 for the Label site)
     double* hrep = nullptr;                        // pinned: [2 slots][hrep_stride] = eigenvalues + check values of a speculative split | CG scalars + trace | norm partials | after-SVD scalars
@@ -244,11 +242,11 @@ struct tnml_ctx {
     double last_bnorm = 0.;         // |B| of the last quadcost
     int* sInfo = nullptr;
     unsigned long long* fprint = nullptr;   // [2] device: fingerprint of replicated tensors (and its complement)
-    int check_replicas_mode = 1;            // 1: a mismatch is an error (checked with the deferred tail: no extra collective); 2: checked at once, inside the bond update
+    int check_replicas_mode = 1;            // option "check_replicas", env TNML_CHECK_REPLICAS: 0 off, 1: a mismatch is an error (checked with the deferred tail: no extra collective); 2: checked at once, inside the bond update
                                             //    and before the environment shift; on a mismatch rank 0's two site tensors are re-broadcast and the event is counted
     long replica_repairs = 0;
-    int debug_nudge_rank = -1;              // test hook: this rank's copy of W.A(b) is moved by one ulp after every split
-    bool check_replicas = true;             // multi-rank: compare the fingerprints of W[b], W[b+1] after every bond update (env TNML_CHECK_REPLICAS=0 disables)
+    int debug_nudge_rank = -1;              // test hook (option "debug_nudge_rank"): this rank's copy of W.A(b) is moved by one ulp after every split
+    bool check_replicas = true;             // multi-rank: compare the fingerprints of W[b], W[b+1] after every bond update (check_replicas_mode != 0)
     int svd_n = 0;
 
     BondPlan plan;
@@ -468,7 +466,6 @@ int split_gemm(tnml_ctx* c, bool ta, bool tb, int M, int N, int K, const double*
 // ---- eigh.hip -----------------------------------------------------------------------------
 int eigh_tridiagonalize(tnml_ctx* c, const double* A, int n, double* D, double* E, double* tau, double* V, double psd_tol = 0.);   // tau: n doubles, tau[n-1] = number of reflectors
 int eigh_tridiag_eig(tnml_ctx* c, const double* D, const double* E, int n, double* W, int mk, double* Z, int ldz, double* scratch, double* W_host = nullptr);      // eigh_tri.hip; W_host: pinned mirror of W (may be null)
-int eigh_ns_matrix(tnml_ctx* c, const double* S, double* Cm, int m, double* dev);
 int eigh_chol_rinv(tnml_ctx* c, const double* S, int m, double* Rinv, double* flag, int zero_prev = 0);   // m <= 128; zero_prev: also clears flag[-1]
 #define TNML_CHOL_MAXM 128
 #define TEIG_SCRATCH_DOUBLES 5120        // eigh_tridiag_eig scratch (n <= 1 024)

@@ -30,7 +30,7 @@ def main():
     rng = np.random.default_rng(3)
     B = B + 0.05 * rng.standard_normal(B.shape)
     out = {}
-    modes = (0, 2) + ((3, 5) if os.environ.get("TNML_DEV_ABL") else ())
+    modes = (0, 2)
     if os.environ.get("TNML_DEV_WGS"):
         ts.set_option("bgemm_wgs", int(os.environ["TNML_DEV_WGS"]))      # workgroups the gradient GEMM aims at (slab count)
     for mode in modes:
@@ -50,9 +50,7 @@ def main():
     G0, G1 = out[0][0], out[2][0]
     print("m %d, images %d: max |G_quad - G_bgemm64| / max |G| = %.3e   (repeats bit-identical: bgemm64 %s, quad %s)" % (
         m, NT, np.abs(G1 - G0).max() / np.abs(G0).max(), out[0][1], out[2][1]))
-    for mode, name in ((0, "k_bgemm64"), (2, "k_grad_quad"), (3, "quad, no EL loads"), (5, "quad, no staging")):
-        if mode not in out:
-            continue
+    for mode, name in ((0, "k_bgemm64"), (2, "k_grad_quad")):
         bg, sr = out[mode][2], out[mode][3]
         us = 1e3 * bg[1] / bg[0] if bg and bg[0] else float("nan")
         us_sr = 1e3 * sr[1] / sr[0] if sr and sr[0] else 0.0
