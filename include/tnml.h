@@ -256,6 +256,31 @@ int tnml_bond_update_end(tnml_ctx* ctx, tnml_bond_report* rep);
  *   a test set gets its own context.  Training environments held by the context are not modified. */
 int tnml_classify(tnml_ctx* ctx, double* weights, int32_t* pred, int64_t count[TNML_NL], int64_t nincorrect[TNML_NL]);
 
+/* ---- held-out evaluation during training ----------------------------------------------------------
+ * A held-out set is an ordinary context created for the held-out images (one rank: nranks = 1, its own shard of the set in
+ * a multi-rank run).  Once attached to a training context, every bond update of `train` also moves the two site tensors it
+ * rewrote to `heldout` and -- after the split is final (a speculative split once its deferred check has passed in
+ * tnml_bond_update_end; nothing of a rolled-back split is kept) -- runs on heldout's own stream the forward pass at the new
+ * bond tensor, the cost / #correct reduction and the environment shift that train does at the end of that bond update.
+ * Training reports and W are bit-identical with and without a held-out context.  While attached, calls that would change
+ * heldout's W, environments, data or bond are refused (read-only calls keep working), and so are the calls that would change
+ * train's W or environments outside a bond update; tnml_destroy of either context detaches first. */
+typedef struct {
+    int bond, half;                /* the bond update these values follow; bond = 0: W as it was at attach time */
+    int64_t count;                 /* held-out images of this context (local: no collective is entered) */
+    int64_t ncorrect;              /* decision rule of tnml_classify for the context's mode */
+    double cost;                   /* sum over images and labels of (W_l(x_n) - y_nl)^2; no regulariser */
+    double label_cost[TNML_NL];    /* split per label as tnml_bond_report::label_cost is */
+} tnml_heldout_report;
+/* Refused, with a message naming the mismatch, unless: same device, N, mode, target_label and dtype; heldout's maxm >= train's,
+   heldout has nranks = 1 and image data; no bond update of train in flight; train at a sweep start (environments as
+   tnml_env_init left them, or the last bond update ended a sweep under tnml_sweepnext).  Copies train's W into heldout,
+   builds heldout's environments and computes the bond-0 values. */
+int tnml_heldout_attach(tnml_ctx* train, tnml_ctx* heldout);
+int tnml_heldout_detach(tnml_ctx* train);
+/* the values of the last bond update ended (tnml_bond_update_end), or of attach; waits for them if they are not ready yet */
+int tnml_heldout_read(tnml_ctx* train, tnml_heldout_report* rep);
+
 /* ITensor truncate(): p = sigma^2 descending; returns kept m */
 int tnml_truncate(const double* p, int n, int maxm, int minm, double cutoff, double* truncerr);
 /* ITensor sweepnext (fixedL.cc:478) */

@@ -23,6 +23,13 @@ const char* tnml_last_error(const tnml_ctx* c) { return c ? c->err.c_str() : g_c
 const char* tnml_last_warning(const tnml_ctx* c) { return c ? c->warn.c_str() : ""; }
 // Entry points every rank calls in step (they contain all-reduces) hold one of these: a failure inside aborts an in-process communicator.
 struct CollScope { tnml_ctx* c; explicit CollScope(tnml_ctx* c_) : c(c_) { ++c->coll_depth; } ~CollScope() { --c->coll_depth; } };
+// Held-out evaluation (tnml_heldout_attach): an attached held-out context refuses what would change its W, environments, data or bond
+// (train_too: and a training context with a held-out context refuses what would change its W or environments outside a bond update)
+static int ho_locked(tnml_ctx* c, const char* who, bool train_too = false) {
+    if (c->held) return tnml_fail(c, "%s: the context is attached as a held-out set (tnml_heldout_detach first)", who);
+    if (train_too && c->ho) return tnml_fail(c, "%s: a held-out context is attached to this context (tnml_heldout_detach first)", who);
+    return 0;
+}
 
 // ---- profiling ------------------------------------------------------------------------------
 static hipEvent_t prof_event(tnml_ctx* c) {
@@ -378,14 +385,17 @@ int tnml_create(tnml_ctx** out, const tnml_config* cfg) {
     return 0;
 }
 
+static void heldout_release(tnml_ctx* c);
 int tnml_destroy(tnml_ctx* c) {
     if (!c) return 0;
+    if (c->ho) heldout_release(c);                        // either context of a held-out pair: detach first
+    if (c->held) heldout_release(c->held->train);
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) ncclCommDestroy(c->comm);
     local_comm_release(c);
     ipc_comm_release(c);
-    for (int k = 0; k < 2; ++k) { if (c->pend[k].ev) (void)hipEventDestroy(c->pend[k].ev); if (c->pend[k].ev2) (void)hipEventDestroy(c->pend[k].ev2); }
+    for (int k = 0; k < 2; ++k) { if (c->pend[k].ev) (void)hipEventDestroy(c->pend[k].ev); if (c->pend[k].ev2) (void)hipEventDestroy(c->pend[k].ev2); if (c->pend[k].ev_ho) (void)hipEventDestroy(c->pend[k].ev_ho); }
     for (auto& p : c->prof_pending) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     for (auto e : c->prof_free) (void)hipEventDestroy(e);
     for (auto& p : c->redo_events) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
@@ -526,6 +536,7 @@ static int set_labels(tnml_ctx* c, const int32_t* labels) {
     return 0;
 }
 int tnml_set_data_u8(tnml_ctx* c, const uint8_t* pixels, const int32_t* labels) {
+    TCK(ho_locked(c, "tnml_set_data_u8", true));
     HIPCK(c, hipSetDevice(c->cfg.device));
     TCK(set_labels(c, labels));
     uint8_t* d_pix = nullptr;
@@ -536,10 +547,11 @@ int tnml_set_data_u8(tnml_ctx* c, const uint8_t* pixels, const int32_t* labels) 
     (void)hipStreamSynchronize(c->stream);
     (void)hipFree(d_pix);
     if (rc) return rc;
-    c->data_set = true; c->currb = -1; c->p_valid = false;
+    c->data_set = true; c->currb = -1; c->p_valid = false; c->sweep_start = false;
     return 0;
 }
 int tnml_set_data_phi(tnml_ctx* c, const double* phi, const int32_t* labels) {
+    TCK(ho_locked(c, "tnml_set_data_phi", true));
     HIPCK(c, hipSetDevice(c->cfg.device));
     TCK(set_labels(c, labels));
     // TState::data[(j-1)*d + (n-1)] (fixedL.cc:39-46) -> [N][2][NTp], rounded once to fp32
@@ -555,12 +567,13 @@ int tnml_set_data_phi(tnml_ctx* c, const double* phi, const int32_t* labels) {
             h[((size_t)j * 2 + s) * c->NTp + i] = (float)phi[((size_t)i * c->N + j) * 2 + s];
         HIPCK(c, hipMemcpy(c->phi, h.data(), sizeof(float) * ne, hipMemcpyHostToDevice));
     }
-    c->data_set = true; c->currb = -1; c->p_valid = false;
+    c->data_set = true; c->currb = -1; c->p_valid = false; c->sweep_start = false;
     return 0;
 }
 
 // ---- weight MPS replica -------------------------------------------------------------------------
 int tnml_set_site(tnml_ctx* c, int j, int ml, int mr, int has_label, const double* A) {
+    TCK(ho_locked(c, "tnml_set_site", true));
     if (j < 1 || j > c->N) return tnml_fail(c, "tnml_set_site: site %d out of range", j);
     if (c->single() && has_label) return tnml_fail(c, "tnml_set_site: the per-label variant has no Label index");
     if ((j == c->c0) != (has_label != 0)) return tnml_fail(c, "Label Index not on site %d", c->c0);     // fixedL.cc:734
@@ -569,7 +582,7 @@ int tnml_set_site(tnml_ctx* c, int j, int ml, int mr, int has_label, const doubl
     SiteT& s = c->W[j];
     s.ml = ml; s.mr = mr; s.L = has_label ? TNML_NL : 1; s.set = true;
     HIPCK(c, hipMemcpy(s.a, A, sizeof(double) * (size_t)ml * 2 * mr * s.L, hipMemcpyHostToDevice));
-    c->currb = -1; c->p_valid = false;
+    c->currb = -1; c->p_valid = false; c->sweep_start = false;
     return 0;
 }
 int tnml_site_dims(tnml_ctx* c, int j, int* ml, int* mr, int* has_label) {
@@ -827,23 +840,36 @@ static int shift_site(tnml_ctx* c, int cs, int ps, bool from_left) {
     return shift_core(c, cs, from_left, has_prev ? c->env[ps].ptr : nullptr, Le, c->env[cs].ptr, false, nullptr);
 }
 
-int tnml_env_init(tnml_ctx* c) {       // TrainStates::init, fixedL.cc:122-157
-    CollScope coll_(c);                // every rank calls it in step: a rank that fails here (host tier out of memory) tells its peers at once
+static int set_bond_impl(tnml_ctx* c, int b);
+static int env_init_impl(tnml_ctx* c) {
     HIPCK(c, hipSetDevice(c->cfg.device));
     if (!c->data_set) return tnml_fail(c, "tnml_env_init: training data not set");
     TCK(check_W(c));
     for (int n = c->N; n >= 3; --n) TCK(shift_site(c, n, n == c->N ? 0 : n + 1, false));   // :136-153
     c->currb = -1;
-    return tnml_set_bond(c, 1);                                                            // :156
+    const int rc = set_bond_impl(c, 1);                                                    // :156
+    if (rc) { c->currb = -1; c->plan = BondPlan(); }
+    return rc;
 }
-int tnml_shift_env(tnml_ctx* c, int b, int from_left) {   // TrainStates::shiftE, fixedL.cc:192-233
-    CollScope coll_(c);
+int tnml_env_init(tnml_ctx* c) {       // TrainStates::init, fixedL.cc:122-157
+    CollScope coll_(c);                // every rank calls it in step: a rank that fails here (host tier out of memory) tells its peers at once
+    TCK(ho_locked(c, "tnml_env_init", true));
+    TCK(env_init_impl(c));
+    c->sweep_start = true;
+    return 0;
+}
+static int shift_env_impl(tnml_ctx* c, int b, int from_left) {
     HIPCK(c, hipSetDevice(c->cfg.device));
     if (b < 1 || b > c->N - 1) return tnml_fail(c, "tnml_shift_env: bond %d out of range", b);
     const int cs = from_left ? b : b + 1;              // :196
     const int prevc = from_left ? b - 1 : b + 2;       // :199
-    TCK(shift_site(c, cs, (prevc >= 1 && prevc <= c->N) ? prevc : 0, from_left != 0));
-    return 0;
+    return shift_site(c, cs, (prevc >= 1 && prevc <= c->N) ? prevc : 0, from_left != 0);
+}
+int tnml_shift_env(tnml_ctx* c, int b, int from_left) {   // TrainStates::shiftE, fixedL.cc:192-233
+    CollScope coll_(c);
+    TCK(ho_locked(c, "tnml_shift_env", true));
+    c->sweep_start = false;
+    return shift_env_impl(c, b, from_left);
 }
 int tnml_env_stats(tnml_ctx* c, int64_t* spills, int64_t* fetches, int64_t* slabs_on_device, int64_t* host_bytes) {
     if (spills) *spills = c->env_spills;
@@ -882,6 +908,7 @@ int tnml_get_env(tnml_ctx* c, int j, double* E) {
 // chain buffers borrowed from the environment pools (the training environments are left untouched).
 int tnml_classify(tnml_ctx* c, double* weights, int32_t* pred, int64_t count[TNML_NL], int64_t nincorrect[TNML_NL]) {
     CollScope coll_(c);
+    TCK(ho_locked(c, "tnml_classify"));
     HIPCK(c, hipSetDevice(c->cfg.device));
     if (!c->data_set) return tnml_fail(c, "tnml_classify: image data not set");
     EnvProtect keep(c, c->currb > 0 ? c->currb - 1 : 0, c->currb > 0 ? c->currb + 2 : 0);      // the chain buffers below may evict, but not the operands of the bond that is set
@@ -955,9 +982,9 @@ static PackDesc bond_pack_desc(const BondPlan& p) {
     d.Kp = p.Kp; d.Np = p.Np;
     return d;
 }
-static int set_bond_impl(tnml_ctx* c, int b);
 int tnml_set_bond(tnml_ctx* c, int b) {
     CollScope coll_(c);
+    TCK(ho_locked(c, "tnml_set_bond"));
     const int rc = set_bond_impl(c, b);
     if (rc) { c->currb = -1; c->plan = BondPlan(); }          // no dangling environment pointers after a failed setBond: the next use has to set a bond again
     return rc;
@@ -1324,6 +1351,7 @@ static int download_bond(tnml_ctx* c, const double* Mvec, double* B) {   // M-la
 }
 
 int tnml_forward(tnml_ctx* c, const double* B, double* P) {
+    TCK(ho_locked(c, "tnml_forward"));
     HIPCK(c, hipSetDevice(c->cfg.device));
     c->p_valid = false;
     TCK(upload_bond(c, B));
@@ -1340,6 +1368,7 @@ int tnml_forward(tnml_ctx* c, const double* B, double* P) {
 }
 int tnml_gradient(tnml_ctx* c, const double* B, double* G) {
     CollScope coll_(c);
+    TCK(ho_locked(c, "tnml_gradient"));
     HIPCK(c, hipSetDevice(c->cfg.device));
     c->p_valid = false;
     TCK(upload_bond(c, B));
@@ -1349,6 +1378,7 @@ int tnml_gradient(tnml_ctx* c, const double* B, double* G) {
 // sum_n |p.v_n|^2 + lambda |p|^2 for a direction p (fixedL.cc:394-403), collective
 int tnml_pAp(tnml_ctx* c, const double* p, double lambda, double* pAp) {
     CollScope coll_(c);
+    TCK(ho_locked(c, "tnml_pAp"));
     HIPCK(c, hipSetDevice(c->cfg.device));
     c->p_valid = false;
     TCK(upload_bond(c, p));
@@ -1363,6 +1393,7 @@ int tnml_pAp(tnml_ctx* c, const double* p, double lambda, double* pAp) {
 }
 int tnml_quadcost(tnml_ctx* c, const double* B, double lambda, double* cost, double label_cost[TNML_NL], double* reg_cost, int64_t* ncorrect) {
     CollScope coll_(c);
+    TCK(ho_locked(c, "tnml_quadcost"));
     HIPCK(c, hipSetDevice(c->cfg.device));
     c->p_valid = false;
     TCK(upload_bond(c, B));
@@ -1374,6 +1405,7 @@ int tnml_quadcost(tnml_ctx* c, const double* B, double lambda, double* cost, dou
 // on its r columns, the filtered inverse) runs on the host.  The reference starts from a time-seeded random V and only prints the cost of
 // the result (single.h:596-601): a diagnostic, with the start an argument here.  One rank only.
 int tnml_pinv(tnml_ctx* c, const double* V0, int r, int npass, double lambda, double pcut, double* B, double* ve, int* npass_done, double* Dsv) {
+    TCK(ho_locked(c, "tnml_pinv"));
     HIPCK(c, hipSetDevice(c->cfg.device));
     if (!c->single()) return tnml_fail(c, "tnml_pinv: only the per-label variant (TNML_MODE_SINGLE) has this solver");
     if (c->currb < 1) return tnml_fail(c, "tnml_pinv: setBond has not been called");
@@ -1454,6 +1486,7 @@ int tnml_pinv(tnml_ctx* c, const double* V0, int r, int npass, double lambda, do
 }
 int tnml_exact(tnml_ctx* c, double* B, double lambda, double pcut) {   // single.h:117-160 on the bond chosen by tnml_set_bond
     CollScope coll_(c);
+    TCK(ho_locked(c, "tnml_exact"));
     HIPCK(c, hipSetDevice(c->cfg.device));
     if (c->currb < 1) return tnml_fail(c, "tnml_exact: setBond has not been called");
     c->p_valid = false;
@@ -1462,6 +1495,7 @@ int tnml_exact(tnml_ctx* c, double* B, double lambda, double pcut) {   // single
 }
 int tnml_cgrad(tnml_ctx* c, double* B, int npass, double lambda, double cconv, tnml_cg_trace* trace) {
     CollScope coll_(c);
+    TCK(ho_locked(c, "tnml_cgrad"));
     HIPCK(c, hipSetDevice(c->cfg.device));
     c->p_valid = false;
     TCK(upload_bond(c, B));
@@ -1472,6 +1506,8 @@ int tnml_cgrad(tnml_ctx* c, double* B, int npass, double lambda, double cconv, t
 int tnml_svd_split(tnml_ctx* c, const double* B, int b, int ha, double cutoff, int maxm, int minm,
                    double* truncerr, int* newm, double* sv, int* nsv) {
     CollScope coll_(c);
+    TCK(ho_locked(c, "tnml_svd_split", true));
+    c->sweep_start = false;
     HIPCK(c, hipSetDevice(c->cfg.device));
     if (b < 1 || b > c->N - 1 || (ha != 1 && ha != 2)) return tnml_fail(c, "tnml_svd_split: bad bond/half");
     c->p_valid = false;
@@ -1489,6 +1525,7 @@ int tnml_svd_split(tnml_ctx* c, const double* B, int b, int ha, double cutoff, i
 // because `begin` of the next bond has already passed its own synchronisation point.
 int tnml_bond_update_begin(tnml_ctx* c, int b, int ha, const tnml_sweep_params* sp) {
     CollScope coll_(c);
+    TCK(ho_locked(c, "tnml_bond_update_begin"));
     HIPCK(c, hipSetDevice(c->cfg.device));
     if (ha != 1 && ha != 2) return tnml_fail(c, "tnml_bond_update: half must be 1 or 2");
     if (c->pend_count >= 2) return tnml_fail(c, "tnml_bond_update_begin: two bond updates are in flight, call tnml_bond_update_end first");
@@ -1496,7 +1533,8 @@ int tnml_bond_update_begin(tnml_ctx* c, int b, int ha, const tnml_sweep_params* 
     PendingReport& pr = c->pend[slot];
     tnml_bond_report* rep = &pr.rep;
     memset(rep, 0, sizeof *rep);
-    pr.b = b; pr.ha = ha; pr.sp = *sp; pr.spec = false; pr.nundo = 0;
+    pr.b = b; pr.ha = ha; pr.sp = *sp; pr.spec = false; pr.nundo = 0; pr.ho = false;
+    c->sweep_start = false;
     // what the report needs reaches its pinned block through the kernels that compute it (round 5: four copy kernels per bond update less):
     // the CG scalars and trace (k_cg_step2 / k_cg_resid2 of the fp64 literal or merged CG), the norms of the new bond tensor (partial pairs,
     // summed by tnml_bond_update_end), and -- on one rank -- the after-SVD cost partials (k_reduce_partials)
@@ -1536,6 +1574,8 @@ int tnml_bond_update_begin(tnml_ctx* c, int b, int ha, const tnml_sweep_params* 
     TCK(launch_unpack(c, pd, c->vB, c->tB));
     c->hmir = nullptr;
     if (!pr.trace_mirrored) TCK(cgrad_trace_enqueue(c, slot));        // parsed by tnml_bond_update_end
+    // held-out context: the split takes spare buffers whose former tensors the held-out stream may still be copying (an empty wait in practice)
+    if (c->ho && c->ho->held->copy_recorded) HIPCK(c, hipStreamWaitEvent(c->stream, c->ho->held->ev_copied, 0));
     TCK(svd_split_device(c, c->tB, b, ha, sp->cutoff, sp->maxm, sp->minm, &rep->truncerr, &rep->newm, nullptr, nullptr, slot));   // :519-522 (may run without its host synchronisation: tnml_ctx::spec_split)
     if (c->debug_nudge_rank == c->cfg.rank) TCK(launch_nudge(c, c->W[b].a));
     // replicas: the two site tensors the split just wrote must be bit-identical on every rank.  Their fingerprint goes into the
@@ -1556,6 +1596,10 @@ int tnml_bond_update_begin(tnml_ctx* c, int b, int ha, const tnml_sweep_params* 
             }
             pr.fp = false;                                            // settled
         }
+    }
+    if (c->ho) {                                                      // what the held-out context copies once the split is final (tnml_bond_update_end)
+        pr.ho = true; pr.ho_site[0] = c->W[b]; pr.ho_site[1] = c->W[b + 1];
+        HIPCK(c, hipEventRecord(pr.ev_ho, c->stream));
     }
     TCK(launch_bond_form(c, c->W[b], c->W[b + 1], c->tB2));           // :527
     TCK(launch_pack(c, pd, c->tB2, c->vB, nullptr));
@@ -1580,7 +1624,7 @@ int tnml_bond_update_begin(tnml_ctx* c, int b, int ha, const tnml_sweep_params* 
         TCK(carry_deliver(c));
     }
     HIPCK(c, hipEventRecord(pr.ev, c->stream));
-    TCK(tnml_shift_env(c, b, ha == 1));                               // :540
+    TCK(shift_env_impl(c, b, ha == 1));                               // :540
     pr.lambda_cost = sp->lambda_cost;
     c->pend_count += 1;
     c->p_valid = true;                                                // in stream order: P/dP of the after-SVD quadcost
@@ -1600,6 +1644,7 @@ static void spec_commit(tnml_ctx* c, PendingReport& pr) {
     for (int u = 0; u < pr.nundo; ++u) ((pr.undo[u].j == c->c0) ? c->spare_big : c->spare_small).push_back(pr.undo[u].old);
     pr.nundo = 0; pr.spec = false;
 }
+static int heldout_step(tnml_ctx* c, const PendingReport& pr);
 int tnml_bond_update_end(tnml_ctx* c, tnml_bond_report* rep) {
     CollScope coll_(c);
     if (c->pend_count < 1) return tnml_fail(c, "tnml_bond_update_end: no bond update in flight");
@@ -1673,6 +1718,8 @@ int tnml_bond_update_end(tnml_ctx* c, tnml_bond_report* rep) {
     t[12] = nb2;
     quadcost_parse(c, t, pr.lambda_cost, &pr.rep.cost_after_svd, pr.rep.label_cost, &pr.rep.reg_cost, &pr.rep.ncorrect);
     pr.rep.norm_newB = std::sqrt(nb2); pr.rep.diff_B_newB = std::sqrt(df2);
+    c->sweep_start = pr.b == 1 && pr.ha == 2;                         // (tnml_sweepnext ends a sweep after bond 1 of half 2)
+    if (pr.ho && c->ho && heldout_step(c, pr)) return tnml_fail(c, "held-out context: %s", c->ho->err.c_str());
     if (rep) *rep = pr.rep;
     return 0;
 }
@@ -1680,4 +1727,127 @@ int tnml_bond_update(tnml_ctx* c, int b, int ha, const tnml_sweep_params* sp, tn
     if (c->pend_count != 0) return tnml_fail(c, "tnml_bond_update: a pipelined bond update is still in flight");
     TCK(tnml_bond_update_begin(c, b, ha, sp));
     return tnml_bond_update_end(c, rep);
+}
+
+// ---- held-out evaluation during training ------------------------------------------------------------
+// A held-out context follows the sweep of the training context it is attached to: it keeps its own environments, receives the two site
+// tensors of every bond update once the split is final, and on its OWN stream evaluates the new bond tensor on its images (the forward
+// pass and the cost / #correct reduction of the training context's after-SVD quadcost) and shifts its environments as training does.
+// Its work overlaps the training context's next bond update; the training stream waits for it only before a split, whose spare buffers
+// may still be being copied by the held-out stream.
+static void heldout_release(tnml_ctx* c) {              // c: the training context
+    tnml_ctx* h = c->ho;
+    if (!h) return;
+    HeldOut* s = h->held;
+    (void)hipSetDevice(h->cfg.device);
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipStreamSynchronize(c->stream);              // (a wait of the training stream on ev_copied is settled before the event goes)
+    if (s) {
+        if (s->ev_copied) (void)hipEventDestroy(s->ev_copied);
+        for (auto& e : s->ev_done) if (e) (void)hipEventDestroy(e);
+        if (s->host) (void)hipHostFree(s->host);
+        delete s;
+    }
+    h->held = nullptr; c->ho = nullptr;
+}
+// the forward pass of the held-out images at bond b of the held-out context's W and its reduction -> the next result slot (in stream order)
+static int heldout_eval(tnml_ctx* h, int bond, int half, int b) {
+    HeldOut* s = h->held;
+    if (set_bond_impl(h, b)) { h->currb = -1; h->plan = BondPlan(); return 1; }
+    TCK(launch_bond_form(h, h->W[b], h->W[b + 1], h->tB));
+    TCK(launch_pack(h, bond_pack_desc(h->plan), h->tB, h->vB, nullptr));
+    TCK(forward_pass(h, h->vB, LD_MODE_COST, h->tail, false));         // tail[0..9] cost per label, [10] #correct
+    const int k = s->slot ^ 1;
+    HIPCK(h, hipMemcpyAsync(s->host + 16 * k, h->tail, sizeof(double) * 12, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipEventRecord(s->ev_done[k], h->stream));
+    s->slot = k; s->bond[k] = bond; s->half[k] = half;
+    return 0;
+}
+// the bond update `pr` of the training context c has been verified: its two site tensors go to the held-out context, which evaluates
+// them and shifts its environments (errors land in the held-out context's message)
+static int heldout_step(tnml_ctx* c, const PendingReport& pr) {
+    tnml_ctx* h = c->ho;
+    HeldOut* s = h->held;
+    HIPCK(h, hipStreamWaitEvent(h->stream, pr.ev_ho, 0));
+    for (int u = 0; u < 2; ++u) {
+        const SiteT& src = pr.ho_site[u];
+        SiteT& dst = h->W[pr.b + u];
+        dst.ml = src.ml; dst.mr = src.mr; dst.L = src.L; dst.set = true;
+        HIPCK(h, hipMemcpyAsync(dst.a, src.a, sizeof(double) * (size_t)src.ml * 2 * src.mr * src.L, hipMemcpyDeviceToDevice, h->stream));
+    }
+    HIPCK(h, hipEventRecord(s->ev_copied, h->stream));
+    s->copy_recorded = true;
+    TCK(heldout_eval(h, pr.b, pr.ha, pr.b));
+    return shift_env_impl(h, pr.b, pr.ha == 1);
+}
+int tnml_heldout_attach(tnml_ctx* c, tnml_ctx* h) {
+    if (!c || !h) return tnml_fail(c, "tnml_heldout_attach: null argument");
+    if (c == h) return tnml_fail(c, "tnml_heldout_attach: a context cannot be its own held-out set");
+    if (c->held) return tnml_fail(c, "tnml_heldout_attach: train is itself attached as a held-out set");
+    if (c->ho) return tnml_fail(c, "tnml_heldout_attach: train already has a held-out context");
+    if (h->held) return tnml_fail(c, "tnml_heldout_attach: heldout is already attached to a training context");
+    if (h->ho) return tnml_fail(c, "tnml_heldout_attach: heldout has a held-out context of its own");
+    if (h->cfg.device != c->cfg.device) return tnml_fail(c, "tnml_heldout_attach: device differs (train %d, heldout %d)", c->cfg.device, h->cfg.device);
+    if (h->N != c->N) return tnml_fail(c, "tnml_heldout_attach: N differs (train %d, heldout %d)", c->N, h->N);
+    if (h->cfg.mode != c->cfg.mode) return tnml_fail(c, "tnml_heldout_attach: mode differs (train %d, heldout %d)", c->cfg.mode, h->cfg.mode);
+    if (c->single() && h->cfg.target_label != c->cfg.target_label)
+        return tnml_fail(c, "tnml_heldout_attach: target_label differs (train %d, heldout %d)", c->cfg.target_label, h->cfg.target_label);
+    if (h->cfg.dtype != c->cfg.dtype) return tnml_fail(c, "tnml_heldout_attach: dtype differs (train %d, heldout %d)", c->cfg.dtype, h->cfg.dtype);
+    if (h->maxm < c->maxm) return tnml_fail(c, "tnml_heldout_attach: heldout maxm = %d is smaller than train's maxm = %d", h->maxm, c->maxm);
+    if (h->cfg.nranks != 1) return tnml_fail(c, "tnml_heldout_attach: heldout has nranks = %d; it must be one rank (each rank attaches its own shard)", h->cfg.nranks);
+    if (!h->data_set) return tnml_fail(c, "tnml_heldout_attach: heldout has no image data (tnml_set_data_*)");
+    if (c->pend_count) return tnml_fail(c, "tnml_heldout_attach: a bond update of train is in flight (tnml_bond_update_end first)");
+    if (!c->sweep_start)
+        return tnml_fail(c, "tnml_heldout_attach: train is not at a sweep start (after tnml_env_init, or after the last bond update of a sweep)");
+    TCK(check_W(c));
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    SYNCK(c, c->stream);
+    HeldOut* s = new HeldOut();
+    s->train = c;
+    int rc = 0;
+    if (hipEventCreateWithFlags(&s->ev_copied, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&s->ev_done[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&s->ev_done[1], hipEventDisableTiming) != hipSuccess ||
+        hipHostMalloc((void**)&s->host, sizeof(double) * 32) != hipSuccess) rc = tnml_fail(h, "event / pinned buffer allocation failed");
+    for (int k = 0; k < 2 && !rc; ++k)
+        if (!c->pend[k].ev_ho && hipEventCreateWithFlags(&c->pend[k].ev_ho, hipEventDisableTiming) != hipSuccess) rc = tnml_fail(h, "hipEventCreate failed");
+    h->held = s; c->ho = h;
+    h->p_valid = false;
+    for (int j = 1; j <= c->N && !rc; ++j) {               // train's W replica, device to device
+        const SiteT& src = c->W[j];
+        SiteT& dst = h->W[j];
+        dst.ml = src.ml; dst.mr = src.mr; dst.L = src.L; dst.set = true;
+        if (hipMemcpyAsync(dst.a, src.a, sizeof(double) * (size_t)src.ml * 2 * src.mr * src.L, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
+            rc = tnml_fail(h, "copy of site %d failed", j);
+    }
+    if (!rc) rc = env_init_impl(h);                          // the environments as tnml_env_init builds them
+    if (!rc) rc = heldout_eval(h, 0, 0, 1);                  // bond 0: W as it is now
+    if (!rc) rc = tnml_synchronize(h);
+    if (rc) {
+        std::string msg = h->err;
+        heldout_release(c);
+        return tnml_fail(c, "tnml_heldout_attach: %s", msg.c_str());
+    }
+    return 0;
+}
+int tnml_heldout_detach(tnml_ctx* c) {
+    if (!c) return tnml_fail(c, "tnml_heldout_detach: null argument");
+    heldout_release(c);
+    return 0;
+}
+int tnml_heldout_read(tnml_ctx* c, tnml_heldout_report* rep) {
+    if (!c || !rep) return tnml_fail(c, "tnml_heldout_read: null argument");
+    if (!c->ho) return tnml_fail(c, "tnml_heldout_read: no held-out context is attached");
+    const tnml_ctx* h = c->ho;
+    const HeldOut* s = h->held;
+    const int k = s->slot;
+    HIPCK(c, hipEventSynchronize(s->ev_done[k]));
+    const double* t = s->host + 16 * k;
+    memset(rep, 0, sizeof *rep);
+    rep->bond = s->bond[k]; rep->half = s->half[k];
+    rep->count = h->NT;
+    rep->ncorrect = (int64_t)llround(t[SC_NCORR]);
+    double C = 0.;
+    for (int l = 0; l < TNML_NL; ++l) { rep->label_cost[l] = t[l]; C += t[l]; }
+    rep->cost = C;
+    return 0;
 }

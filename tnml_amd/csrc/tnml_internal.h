@@ -103,6 +103,18 @@ struct PendingReport {
     int b = 0, ha = 0; tnml_sweep_params sp{};
     bool spec = false; int split_n = 0, split_mk = 0; int nundo = 0; SiteUndo undo[2];
     int dn_pairs = 0, cost_rows = 0; bool trace_mirrored = false, carry_direct = false;
+    // a held-out context is attached: the two site tensors the split wrote (buffers and dimensions) and the event behind the split
+    bool ho = false; hipEvent_t ev_ho = nullptr; SiteT ho_site[2];
+};
+// State of an attached held-out context (held by the held-out context; tnml_heldout_attach)
+struct HeldOut {
+    struct tnml_ctx* train = nullptr;
+    hipEvent_t ev_copied = nullptr;    // heldout stream: the last copy of site tensors out of train's buffers has finished
+    bool copy_recorded = false;        // ev_copied has been recorded at least once (train's stream waits on it before a split)
+    hipEvent_t ev_done[2] = {nullptr, nullptr};
+    double* host = nullptr;            // pinned [2][16]: the reduced [label costs | #correct] of the last two evaluations
+    int slot = 0;                      // the slot of the latest evaluation
+    int bond[2] = {0, 0}, half[2] = {0, 0};
 };
 
 struct tnml_ctx {
@@ -254,6 +266,10 @@ struct tnml_ctx {
     PendingReport pend[2];     // bond updates begun and not yet ended (tnml_bond_update_begin / _end)
     int pend_tail = 0, pend_count = 0;
     bool tail_zeroed = false;  // the pack kernel of the running bond update has cleared the scalar tail behind G
+    // held-out evaluation (tnml_heldout_attach): a training context points at its held-out context, a held-out context holds the state
+    tnml_ctx* ho = nullptr;
+    HeldOut* held = nullptr;
+    bool sweep_start = false;  // environments as tnml_env_init left them, or the last bond update ended a sweep: where attach may happen
 
     // profiling
     bool prof = false;

@@ -316,6 +316,24 @@ class TrainStates:
                     label_cost=np.array(rep.label_cost[:]), reg_cost=rep.reg_cost, ncorrect=rep.ncorrect,
                     cg=_trace_dict(rep.cg), cost_old=rep.cost_old, cost_cg=rep.cost_cg, reg_cost_cg=rep.reg_cost_cg, norm_oB=rep.norm_oB)
 
+    # -- held-out evaluation during training
+    def attach_heldout(self, other):
+        """tnml_heldout_attach: `other` (a TrainStates of the held-out images, one rank) follows every bond update of this context;
+        allowed at a sweep start only.  `other` is locked until detach_heldout (or until either context is closed)."""
+        self._ck(self._L.tnml_heldout_attach(self._h, other._h))
+        self._heldout = other                     # (keeps the held-out context alive while attached)
+
+    def detach_heldout(self):
+        self._ck(self._L.tnml_heldout_detach(self._h))
+        self._heldout = None
+
+    def heldout_report(self):
+        """held-out values after the last bond update ended (bond = 0: at attach): bond, half, count, ncorrect, cost
+        (sum over images and labels of (W_l(x_n) - y_nl)^2, un-normalised, no regulariser) and label_cost[10]"""
+        r = _lib.HeldoutReport()
+        self._ck(self._L.tnml_heldout_read(self._h, C.byref(r)))
+        return dict(bond=r.bond, half=r.half, count=r.count, ncorrect=r.ncorrect, cost=r.cost, label_cost=np.array(r.label_cost[:]))
+
     # -- measurement
     def profile(self, on, only=None):
         """HIP-event timing of kernel launches; `only` restricts it to one kernel class"""
@@ -352,10 +370,21 @@ def cgrad(B, ts, npass=4, lam=0.0, cconv=1e-10):
     return ts.cgrad(B, npass, lam, cconv)
 
 
-def mldmrg(ts, nsweep, maxm, minm, cutoff, npass, lam, cconv, max_bonds=0, log=None, report_costs=False, pipelined=False):
+def mldmrg(ts, nsweep, maxm, minm, cutoff, npass, lam, cconv, max_bonds=0, log=None, report_costs=False, pipelined=False, heldout=None):
     """fixedL.cc:451-570 (single.h:523-728 for a per-label TrainStates): the sweep loop; emits the reference's log lines
     through `log` if given.  pipelined: bond k+1 is enqueued before the report of bond k is fetched (same results, no idle
-    GPU between bond updates; the log of a bond appears one bond later)."""
+    GPU between bond updates; the log of a bond appears one bond later).  heldout: a TrainStates of held-out images, attached
+    for the run (ts must be at a sweep start) and detached after it; every record gets a "heldout" entry (heldout_report())."""
+    if heldout is not None:
+        ts.attach_heldout(heldout)
+        try:
+            return _mldmrg(ts, nsweep, maxm, minm, cutoff, npass, lam, cconv, max_bonds, log, report_costs, pipelined, True)
+        finally:
+            ts.detach_heldout()
+    return _mldmrg(ts, nsweep, maxm, minm, cutoff, npass, lam, cconv, max_bonds, log, report_costs, pipelined, False)
+
+
+def _mldmrg(ts, nsweep, maxm, minm, cutoff, npass, lam, cconv, max_bonds, log, report_costs, pipelined, with_heldout):
     NT = float(ts.NT_total)
     reports = []
     if pipelined and not log:
@@ -372,10 +401,14 @@ def mldmrg(ts, nsweep, maxm, minm, cutoff, npass, lam, cconv, max_bonds=0, log=N
             if k > 0:
                 r = ts.bond_update_end()
                 r["sweep"] = sched[k - 1][0]
+                if with_heldout:
+                    r["heldout"] = ts.heldout_report()
                 reports.append(r)
         if sched:
             r = ts.bond_update_end()
             r["sweep"] = sched[-1][0]
+            if with_heldout:
+                r["heldout"] = ts.heldout_report()
             reports.append(r)
         return reports
     for sw in range(1, nsweep + 1):
@@ -387,6 +420,8 @@ def mldmrg(ts, nsweep, maxm, minm, cutoff, npass, lam, cconv, max_bonds=0, log=N
                 return reports
             r = ts.bond_update(b, ha, maxm, minm, cutoff, npass, lam, cconv, report_costs=report_costs or ts.single)
             r["sweep"] = sw
+            if with_heldout:
+                r["heldout"] = ts.heldout_report()
             reports.append(r)
             if log:
                 log("Sweep %d Half %d Bond %d" % (sw, ha, r["c"]))

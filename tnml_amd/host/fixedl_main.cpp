@@ -10,7 +10,8 @@
 // fp32-stored environments, f32 = fp32 MFMA study mode), `imglen` (block-mean down-sampling of the images to
 // imglen x imglen; present in the reference's sample input but never read by fixedL.cc), `feature_scale`
 // (multiplies the second feature component; 1 = the reference's double normalisation), `pipeline`, `bond_log`
-// (a CSV line per bond update: cost, #correct, bond dimensions, truncation error, seconds).
+// (a CSV line per bond update: cost, #correct, bond dimensions, truncation error, seconds), `heldout` (the t10k images, capped at `Ntest`
+// per label, follow the training as a held-out context: one "Held-out:" line per bond update).
 #include <array>
 #include <chrono>
 #include <condition_variable>
@@ -97,6 +98,8 @@ int main(int argc, const char* argv[]) {
         const std::string precision = input.getString("precision", "f64");              // extension: f64 | mixed | f32 | bf16x3 | bf16
         const long imglen = input.getInt("imglen", 0);                                   // extension: 0 = keep the file's size
         const double feature_scale = input.getReal("feature_scale", 1.);                 // extension
+        const bool heldout = input.getYesNo("heldout", false);                          // extension: evaluate the t10k images after every bond update
+        const long Ntest = input.getInt("Ntest", 50000);                                 // extension: per-label cap of the held-out set (as fulltest)
         int dtype = TNML_F64;
         if (precision == "mixed") dtype = TNML_F64_E32; else if (precision == "f32") dtype = TNML_F32;
         else if (precision == "bf16x3") dtype = TNML_BF16X3; else if (precision == "bf16") dtype = TNML_BF16;   // study modes (forward contraction on the bf16 matrix pipe)
@@ -105,6 +108,12 @@ int main(int argc, const char* argv[]) {
 
         Dataset train = read_mnist(datadir, true, Ntrain);                              // :613
         if (imglen > 0) reduce(train, (int)imglen);
+        Dataset test;                                                                   // the held-out set: read before any context exists
+        if (heldout) {
+            test = read_mnist(datadir, false, Ntest);
+            if (imglen > 0) reduce(test, (int)imglen);
+            if (test.npix() != train.npix()) { std::printf("heldout: the t10k images have %d pixels, the training images %d\n", test.npix(), train.npix()); return 1; }
+        }
         std::printf("Training set consists of %d images:\n", train.size());
         for (int l = 0; l < 10; ++l) std::printf("  %d of label %d\n", train.counts[l], l);
         const int N = train.npix();                                                     // :615
@@ -183,6 +192,34 @@ int main(int argc, const char* argv[]) {
             ctx_maxm = std::min(ctx_maxm, tnml_plan_maxm(&pc, ctx_maxm, wm, env_budget_gb > 0. ? (int64_t)0 : (int64_t)(0.97 * (double)freeb)));
         }
         ctx_maxm = std::max(ctx_maxm, wm);
+        const int totNtest = heldout ? test.size() : 0;
+        std::vector<int64_t> tlo(nranks, 0), thi(nranks, 0);
+        for (int r = 0; heldout && r < nranks; ++r) tnml_shard_bounds(totNtest, nranks, r, &tlo[r], &thi[r]);
+        if (heldout && env_budget_gb <= 0.) {
+            // the held-out context keeps all its environments resident beside the training context: both must fit at the planned maxm
+            auto need = [&](int r, int m) {
+                tnml_config pc{}; pc.device = share_device ? device : device + r; pc.rank = r; pc.nranks = nranks; pc.N = N;
+                pc.NT_local = (int)(hi[r] - lo[r]); pc.NT_total = totNtrain; pc.maxm = m; pc.dtype = dtype;
+                tnml_config hc = pc; hc.rank = 0; hc.nranks = 1; hc.NT_local = (int)std::max<int64_t>(thi[r] - tlo[r], 1); hc.NT_total = hc.NT_local;
+                return tnml_estimate_bytes(&pc) + tnml_estimate_bytes(&hc);
+            };
+            for (int r = 0; r < nranks; ++r) {
+                int64_t freeb = 0, totb = 0;
+                if (tnml_device_memory(share_device ? device : device + r, &freeb, &totb) != 0) die(nullptr, "tnml_device_memory");
+                if (share_device) freeb /= nranks;
+                const int64_t budget = (int64_t)(0.97 * (double)freeb);
+                if (need(r, wm) > budget) {
+                    std::printf("heldout = yes: the training and held-out contexts (%lld + %lld images, Ntest = %ld) do not fit on GPU %d even at m = %d; "
+                                "lower Ntest or train without heldout\n", (long long)(hi[r] - lo[r]), (long long)(thi[r] - tlo[r]), Ntest, r, wm);
+                    return 1;
+                }
+                int lo_m = wm, hi_m = ctx_maxm;
+                if (need(r, hi_m) > budget) {
+                    while (hi_m - lo_m > 1) { const int mid = lo_m + (hi_m - lo_m) / 2; if (need(r, mid) <= budget) lo_m = mid; else hi_m = mid; }
+                    ctx_maxm = lo_m;
+                }
+            }
+        }
         if (ctx_maxm < maxm)
             std::printf("maxm=%ld is beyond what %d sites can reach or the GPU can hold for %lld images: bond dimensions are capped at %d\n",
                         maxm, N, (long long)(hi[0] - lo[0]), ctx_maxm);
@@ -190,6 +227,16 @@ int main(int argc, const char* argv[]) {
         std::vector<double> phi_all;
         const bool use_u8 = !train.reduced() && feature_scale == 1.;
         if (!use_u8) phi_all = all_features(train, false, feature_scale);
+        std::vector<double> phi_test;
+        const bool test_u8 = !test.reduced() && feature_scale == 1.;
+        if (heldout && !test_u8) phi_test = all_features(test, false, feature_scale);
+        std::vector<tnml_heldout_report> ho_rep(nranks);
+        // rank 0 prints the sums of the ranks' held-out shards (local values: no collective)
+        auto print_heldout = [&]() {
+            double cost = 0.; long long nc = 0, cnt = 0;
+            for (const auto& h : ho_rep) { cost += h.cost; nc += h.ncorrect; cnt += h.count; }
+            std::printf("Held-out: Percent correct = %.4f%%, # incorrect = %lld/%lld, Cost = %.10f\n", nc * 100. / cnt, cnt - nc, cnt, cost / cnt);
+        };
         unsigned char uid[128] = {0};
         if (nranks > 1 && !share_device && !oneshot && tnml_comm_unique_id(uid) != 0) die(nullptr, "tnml_comm_unique_id");
         std::vector<tnml_ctx*> all_ctx(nranks, nullptr);
@@ -215,6 +262,14 @@ int main(int argc, const char* argv[]) {
                 bar.wait();
             }
             upload(ctx, W);
+            tnml_ctx* hctx = nullptr;                                                       // this rank's shard of the held-out set
+            if (heldout) {
+                tnml_config hc = cfg; hc.rank = 0; hc.nranks = 1; hc.NT_local = (int)(thi[r] - tlo[r]); hc.NT_total = hc.NT_local;
+                if (hc.NT_local < 1) die(nullptr, "heldout: a rank without held-out images (more GPUs than t10k images)");
+                if (tnml_create(&hctx, &hc) != 0) die(nullptr, "tnml_create (heldout)");
+                if (test_u8) CK(hctx, tnml_set_data_u8(hctx, test.pixels.data() + (size_t)tlo[r] * N, test.labels.data() + tlo[r]));
+                else         CK(hctx, tnml_set_data_phi(hctx, phi_test.data() + (size_t)tlo[r] * N * 2, test.labels.data() + tlo[r]));
+            }
             if (nranks > 1) { int cnt = 0; CK(ctx, tnml_replica_check(ctx, &cnt)); if (root) std::printf("%s communicator of %d ranks, W replicas identical\n", oneshot ? "one-shot peer-write" : (share_device ? "in-process" : "RCCL"), cnt); }
             if (root) { std::printf("Projecting training states..."); std::fflush(stdout); }   // :740
             CK(ctx, tnml_env_init(ctx));                                                    // :741
@@ -230,6 +285,12 @@ int main(int argc, const char* argv[]) {
                     std::printf("Before starting DMRG Cost = %.10f\n", C / totNtrain);      // :746
                 }
             }
+            if (heldout) {
+                CK(ctx, tnml_heldout_attach(ctx, hctx));
+                CK(ctx, tnml_heldout_read(ctx, &ho_rep[r]));
+                bar.wait();
+                if (root) print_heldout();
+            }
             if (root && pause_step) { std::printf("PAUSE"); std::fflush(stdout); std::getchar(); }
             bar.wait();
 
@@ -242,7 +303,8 @@ int main(int argc, const char* argv[]) {
             // pause_step, restores the strict order).  Nothing is in flight across a sweep boundary.
             struct InFlight { long sw; int b, ha; double lam; bool on = false; } fl;
             FILE* blog = (root && !bond_log.empty()) ? std::fopen(bond_log.c_str(), "w") : nullptr;
-            if (blog) std::fprintf(blog, "sweep,half,bond,lambda,cg_passes,cost_after_svd,reg_cost,ncorrect,ntrain,orig_m,new_m,trunc_err,seconds\n");
+            if (blog) std::fprintf(blog, "sweep,half,bond,lambda,cg_passes,cost_after_svd,reg_cost,ncorrect,ntrain,orig_m,new_m,trunc_err,seconds%s\n",
+                                   heldout ? ",heldout_cost,heldout_ncorrect,nheldout" : "");
             auto t_last = std::chrono::steady_clock::now();
             auto finish = [&]() {                                                           // report + log + hooks of the bond update in flight
                 if (!fl.on) return;
@@ -250,6 +312,10 @@ int main(int argc, const char* argv[]) {
                 const long sw = fl.sw; const int b = fl.b, ha = fl.ha;
                 tnml_bond_report rep;
                 CK(ctx, tnml_bond_update_end(ctx, &rep));
+                if (heldout) {
+                    CK(ctx, tnml_heldout_read(ctx, &ho_rep[r]));
+                    if (nranks > 1) bar.wait();
+                }
                 if (root) {
                     const tnml_bond_report& r_ = rep;
                     std::printf("Sweep %ld Half %d Bond %d\n", sw, ha, r_.c);           // :490
@@ -274,10 +340,17 @@ int main(int argc, const char* argv[]) {
                     std::printf("Percent correct = %.4f%%, # incorrect = %lld/%d\n", r_.ncorrect * 100. / totNtrain,
                                 (long long)(totNtrain - r_.ncorrect), totNtrain);       // :341-342
                     std::printf("--> After SVD, Cost = %.10f\n", r_.cost_after_svd / totNtrain);   // :533
+                    if (heldout) print_heldout();
                     if (blog) {                                                         // seconds: wall time since the previous report (pipelined: one bond update of GPU time)
                         const auto t_now = std::chrono::steady_clock::now();
-                        std::fprintf(blog, "%ld,%d,%d,%.6e,%d,%.17g,%.17g,%lld,%d,%d,%d,%.6e,%.6f\n", sw, ha, r_.c, fl.lam, r_.cg.npass_done, r_.cost_after_svd / totNtrain,
+                        std::fprintf(blog, "%ld,%d,%d,%.6e,%d,%.17g,%.17g,%lld,%d,%d,%d,%.6e,%.6f", sw, ha, r_.c, fl.lam, r_.cg.npass_done, r_.cost_after_svd / totNtrain,
                                      r_.reg_cost / totNtrain, (long long)r_.ncorrect, totNtrain, r_.origm, r_.newm, r_.truncerr, std::chrono::duration<double>(t_now - t_last).count());
+                        if (heldout) {
+                            double hc = 0.; long long hn = 0;
+                            for (const auto& h : ho_rep) { hc += h.cost; hn += h.ncorrect; }
+                            std::fprintf(blog, ",%.17g,%lld,%d", hc / totNtest, hn, totNtest);
+                        }
+                        std::fprintf(blog, "\n");
                         t_last = t_now;
                     }
                     const int cs = ha == 1 ? b : b + 1, prevc = ha == 1 ? b - 1 : b + 2;    // :196-209
@@ -324,7 +397,8 @@ int main(int argc, const char* argv[]) {
             }
             if (blog) std::fclose(blog);
             if (nranks > 1) { CK(ctx, tnml_replica_check(ctx, nullptr)); bar.wait(); }
-            tnml_destroy(ctx);
+            tnml_destroy(ctx);                                                              // (detaches the held-out context)
+            if (hctx) tnml_destroy(hctx);
         };
         (void)write_wf;
         std::vector<std::thread> workers;

@@ -8,7 +8,8 @@
 // reference (single.h:596-604): the cost of the pseudo-inverse solution is printed, the update itself is cgrad; its random start comes from
 // `seed` here (the reference's is time-seeded).  Extensions (never read by the reference): `seed`, `device`, `precision`, `imglen`,
 // `feature_scale` as in the fixedL driver; `labels`, `ngpu`, `share_device`, `dry_run`: the one-label-per-GPU launcher
-// of BASELINE config 4 (launch_per_label below).
+// of BASELINE config 4 (launch_per_label below); `heldout`, `Ntest`: the t10k images follow the training as a held-out context
+// (one "Held-out:" line per bond update; correct = [f > 1/2] == [label == L], the rule of tnml_classify).
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -155,6 +156,8 @@ int main(int argc, const char* argv[]) {
         const std::string precision = input.getString("precision", "f64");
         const long imglen = input.getInt("imglen", 0);
         const double feature_scale = input.getReal("feature_scale", 1.);
+        const bool heldout = input.getYesNo("heldout", false);
+        const long Ntest = input.getInt("Ntest", 50000);
         int dtype = TNML_F64;
         if (precision == "mixed") dtype = TNML_F64_E32; else if (precision == "f32") dtype = TNML_F32;
         else if (precision != "f64" && precision != "strict") { std::printf("precision must be f64, mixed or f32\n"); return 1; }
@@ -167,6 +170,12 @@ int main(int argc, const char* argv[]) {
         char wname[32]; std::snprintf(wname, sizeof wname, "W%d", L);                  // :53
         Dataset train = read_mnist(datadir, true, Ntrain);                              // :56
         if (imglen > 0) reduce(train, (int)imglen);
+        Dataset test;                                                                   // the held-out set: read before any context exists
+        if (heldout) {
+            test = read_mnist(datadir, false, Ntest);
+            if (imglen > 0) reduce(test, (int)imglen);
+            if (test.npix() != train.npix()) { std::printf("heldout: the t10k images have %d pixels, the training images %d\n", test.npix(), train.npix()); return 1; }
+        }
         const int N = train.npix();
         std::printf("%d sites\n", N);                                                  // :59
         if (file_exists("sites")) { int Ns, ds; read_sites("sites", &Ns, &ds); if (Ns != N || ds != 2) { std::printf("Mismatched sizes\n"); return 1; } }
@@ -225,6 +234,20 @@ int main(int argc, const char* argv[]) {
             int64_t freeb = 0, totb = 0;
             if (tnml_device_memory(device, &freeb, &totb) != 0) die(nullptr, "tnml_device_memory");
             cfg.maxm = std::max(wm, tnml_plan_maxm(&cfg, cfg.maxm, wm, (int64_t)(0.97 * (double)freeb)));
+            if (heldout) {                                                              // the held-out context keeps all its environments resident as well
+                auto need = [&](int m) { tnml_config t = cfg, h = cfg; t.maxm = h.maxm = m; h.NT_local = test.size(); h.NT_total = test.size(); return tnml_estimate_bytes(&t) + tnml_estimate_bytes(&h); };
+                const int64_t budget = (int64_t)(0.97 * (double)freeb);
+                if (need(wm) > budget) {
+                    std::printf("heldout = yes: the training and held-out contexts (%d + %d images, Ntest = %ld) do not fit on the GPU even at m = %d; "
+                                "lower Ntest or train without heldout\n", totNtrain, test.size(), Ntest, wm);
+                    return 1;
+                }
+                int lo_m = wm, hi_m = cfg.maxm;
+                if (need(hi_m) > budget) {
+                    while (hi_m - lo_m > 1) { const int mid = lo_m + (hi_m - lo_m) / 2; if (need(mid) <= budget) lo_m = mid; else hi_m = mid; }
+                    cfg.maxm = lo_m;
+                }
+            }
             if (cfg.maxm < maxm) std::printf("maxm=%ld is beyond what %d sites can reach or the GPU can hold for %d images: bond dimensions are capped at %d\n", maxm, N, totNtrain, cfg.maxm);
         }
         tnml_ctx* ctx = nullptr;
@@ -235,9 +258,26 @@ int main(int argc, const char* argv[]) {
         CK(ctx, tnml_set_data_phi(ctx, phi.data(), labels.data()));
         phi.clear(); phi.shrink_to_fit();
         for (int j = 1; j <= N; ++j) CK(ctx, tnml_set_site(ctx, j, W.A[j].ml, W.A[j].mr, 0, W.A[j].a.data()));
+        tnml_ctx* hctx = nullptr;
+        if (heldout) {
+            tnml_config hc = cfg; hc.NT_local = test.size(); hc.NT_total = test.size();
+            if (tnml_create(&hctx, &hc) != 0) die(nullptr, "tnml_create (heldout)");
+            std::vector<double> hphi((size_t)test.size() * N * 2);
+            for (int k = 0; k < test.size(); ++k) {
+                if (normal) features_normal(test, k, ph); else features_series(test, k, ph, feature_scale);
+                std::copy(ph.begin(), ph.end(), hphi.begin() + (size_t)k * N * 2);
+            }
+            CK(hctx, tnml_set_data_phi(hctx, hphi.data(), test.labels.data()));
+        }
         std::printf("Projecting training states..."); std::fflush(stdout);              // :183
         CK(ctx, tnml_env_init(ctx));                                                    // :184-199
         std::printf("done\n");
+        auto print_heldout = [&]() {
+            tnml_heldout_report h;
+            CK(ctx, tnml_heldout_read(ctx, &h));
+            std::printf("Held-out: Percent correct = %.4f%%, # incorrect = %lld/%lld, Cost = %.10f\n", h.ncorrect * 100. / h.count,
+                        (long long)(h.count - h.ncorrect), (long long)h.count, h.cost / h.count);
+        };
         {
             int mL, mR, lab; CK(ctx, tnml_bond_dims(ctx, 1, &mL, &mR, &lab));
             std::vector<double> B((size_t)mL * 4 * mR);
@@ -246,6 +286,7 @@ int main(int argc, const char* argv[]) {
             CK(ctx, tnml_quadcost(ctx, B.data(), lambda, &C, nullptr, nullptr, nullptr));   // :217
             std::printf("Before DMRG, Cost = %.10f\n", C / Ntrain);                     // :218 (divides by the per-label cap, as the reference)
         }
+        if (heldout) { CK(ctx, tnml_heldout_attach(ctx, hctx)); print_heldout(); }
         const double NT = (double)totNtrain;                                            // single.h:535 Ntrain = ts.size()
         for (long sw = 1; sw <= Nsweep; ++sw) {                                         // single.h:546
             std::printf("Sweep %ld maxm=%ld\n", sw, maxm);                              // :548
@@ -302,6 +343,7 @@ int main(int argc, const char* argv[]) {
                 std::printf("norm(newB) = %.12g\n", r.norm_newB);                       // :681
                 std::printf("--> After SVD, Cost = %.10f (%.10f)\n", r.cost_after_svd / NT, r.cost_after_svd);   // :684
                 if (r.cost_after_svd > 1.1 * r.cost_cg) std::printf("> 10%% larger C after SVD\n");   // :686
+                if (heldout) print_heldout();
                 if (pause_steps) { std::printf("PAUSE"); std::fflush(stdout); std::getchar(); }
                 if (file_exists("WRITE_WF")) {                                          // :712-718
                     std::printf("File WRITE_WF found\n");
@@ -316,7 +358,8 @@ int main(int argc, const char* argv[]) {
         }
         std::printf("Writing %s to disk\n", wname);                                     // single.cc:240
         write_mps(wname, download(ctx, N));
-        tnml_destroy(ctx);
+        tnml_destroy(ctx);                                                              // (detaches the held-out context)
+        if (hctx) tnml_destroy(hctx);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "Error: %s\n", e.what());
         return 1;

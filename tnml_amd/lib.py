@@ -30,6 +30,7 @@ EXPORTS = [
     "tnml_exact", "tnml_set_option_real", "tnml_pinv", "tnml_env_stats", "tnml_oneshot_export", "tnml_oneshot_connect", "tnml_oneshot_mem_kind", "tnml_split_stats", "tnml_oneshot_region_bytes",
     "tnml_lin_create", "tnml_lin_destroy", "tnml_lin_last_error", "tnml_lin_set_data_u8", "tnml_lin_set_data_f64", "tnml_lin_set_labels",
     "tnml_lin_cg_start", "tnml_lin_cg_run", "tnml_lin_get_v", "tnml_lin_evaluate",
+    "tnml_heldout_attach", "tnml_heldout_detach", "tnml_heldout_read",
 ]
 
 
@@ -56,6 +57,11 @@ class BondReport(C.Structure):
                 ("cost_after_svd", C.c_double), ("label_cost", C.c_double * NL), ("reg_cost", C.c_double),
                 ("ncorrect", C.c_int64), ("cg", CgTrace), ("cost_old", C.c_double), ("cost_cg", C.c_double),
                 ("reg_cost_cg", C.c_double), ("norm_oB", C.c_double)]
+
+
+class HeldoutReport(C.Structure):
+    _fields_ = [("bond", C.c_int), ("half", C.c_int), ("count", C.c_int64), ("ncorrect", C.c_int64),
+                ("cost", C.c_double), ("label_cost", C.c_double * NL)]
 
 
 _lib = None
@@ -137,6 +143,9 @@ def load():
     L.tnml_oneshot_region_bytes.restype = C.c_int64
     L.tnml_device_memory.argtypes = [C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.tnml_plan_maxm.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_int64]
+    L.tnml_heldout_attach.argtypes = [vp, vp]
+    L.tnml_heldout_detach.argtypes = [vp]
+    L.tnml_heldout_read.argtypes = [vp, C.POINTER(HeldoutReport)]
     L.tnml_lin_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
     L.tnml_lin_destroy.argtypes = [vp]
     L.tnml_lin_last_error.restype = C.c_char_p

@@ -6,8 +6,9 @@ Same input file, data directory, `sites` / `W` files (the formats of tnml_amd/ho
 lines as the C++ driver (tnml_amd/host/fixedl_main.cpp, which runs one GPU); the training images are sharded over the
 ranks with tnml_shard_bounds and the gradient / cost sums go through the library's RCCL all-reduce
 (BASELINE config 3: "batch sharded across 8xMI355X").  torch.distributed (gloo) is only the control plane: the RCCL
-unique id, the LAMBDA hot reload and barriers.  Rank 0 prints and writes files.  A single process (no launcher)
-works too and is what the tests run.
+unique id, the LAMBDA hot reload, barriers and the sums of the held-out shards (`heldout = yes`: the t10k images, capped at
+`Ntest` per label, follow the training in a held-out context per rank; one "Held-out:" line per bond update).  Rank 0 prints
+and writes files.  A single process (no launcher) works too and is what the tests run.
 """
 import os
 import sys
@@ -54,6 +55,12 @@ def main(argv=None):
     precision = key("precision", "f64")
     imglen = key("imglen", 0, int)
     feature_scale = key("feature_scale", 1.0, float)
+    try:
+        heldout = hostlib.input_yesno(inp, "heldout", False)
+    except RuntimeError as e:
+        say(str(e))
+        return 1
+    Ntest = key("Ntest", 50000, int)
     dtype = {"f64": "f64", "strict": "f64", "mixed": "f64_e32", "f32": "f32"}.get(precision)
     if dtype is None:
         say("precision must be f64, mixed or f32")
@@ -72,6 +79,16 @@ def main(argv=None):
         vals = hostlib.reduce(px, side, imglen)
     else:
         vals = None
+    if heldout:                                                                 # the held-out set: read before any context exists
+        try:
+            tpx, tlab, _ = hostlib.read_mnist(datadir, False, Ntest)
+        except RuntimeError as e:
+            say(str(e))
+            return 1
+        tvals = hostlib.reduce(tpx, int(round(np.sqrt(tpx.shape[1]))), imglen) if imglen > 0 else None
+        if (tvals if tvals is not None else tpx).shape[1] != (vals if vals is not None else px).shape[1]:
+            say("heldout: the t10k images and the training images differ in size")
+            return 1
     N = (vals if vals is not None else px).shape[1]
     c = N // 2
     NT = len(lab)
@@ -112,6 +129,24 @@ def main(argv=None):
     # `maxm` is only an upper bound for the reference (default 5000): size the context by what an N-site MPS can reach
     # and what fits this GPU for this shard, and say so
     ctx_maxm = lib.plan_maxm(N, hi - lo, maxm, floor_m=wm, dtype=dtype, device=local_rank)
+    if heldout:                                                                 # the held-out context keeps all its environments resident beside it
+        import ctypes as C
+        f, t_ = C.c_int64(), C.c_int64()
+        budget = int(0.97 * f.value) if lib.load().tnml_device_memory(local_rank, C.byref(f), C.byref(t_)) == 0 else 0
+        hlo, hhi = lib.shard_bounds(len(tlab), world, rank)
+
+        def need(m):
+            return lib.estimate_bytes(N, hi - lo, m, dtype) + lib.estimate_bytes(N, max(hhi - hlo, 1), m, dtype)
+        if budget > 0 and need(wm) > budget:
+            say("heldout = yes: the training and held-out contexts (%d + %d images, Ntest = %d) do not fit on GPU %d even at m = %d; "
+                "lower Ntest or train without heldout" % (hi - lo, hhi - hlo, Ntest, local_rank, wm))
+            return 1
+        if budget > 0 and need(ctx_maxm) > budget:
+            a, b = wm, ctx_maxm
+            while b - a > 1:
+                mid = (a + b) // 2
+                a, b = (mid, b) if need(mid) <= budget else (a, mid)
+            ctx_maxm = a
     if world > 1:
         t = torch.tensor([ctx_maxm], dtype=torch.int64)
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
@@ -119,12 +154,18 @@ def main(argv=None):
     if ctx_maxm < maxm:
         say("maxm=%d is beyond what %d sites can reach or this GPU can hold for %d images: bond dimensions are capped at %d" % (maxm, N, hi - lo, ctx_maxm))
 
-    if vals is None and feature_scale == 1.0:
-        ts = TrainStates(lab[lo:hi], N, ctx_maxm, pixels=px[lo:hi], device=local_rank, rank=rank, nranks=world, NT_total=NT, dtype=dtype)
-    else:
-        g = (vals if vals is not None else px.astype(np.float64))[lo:hi] / 255.0
+    def states(p, v, lb, **kw):
+        if v is None and feature_scale == 1.0:
+            return TrainStates(lb, N, ctx_maxm, pixels=p, device=local_rank, dtype=dtype, **kw)
+        g = (v if v is not None else p.astype(np.float64)) / 255.0
         phi = np.stack([np.ones_like(g), feature_scale * ((g / 255.0) / 4.0)], axis=-1)
-        ts = TrainStates(lab[lo:hi], N, ctx_maxm, phi=phi, device=local_rank, rank=rank, nranks=world, NT_total=NT, dtype=dtype)
+        return TrainStates(lb, N, ctx_maxm, phi=phi, device=local_rank, dtype=dtype, **kw)
+    ts = states(px[lo:hi], None if vals is None else vals[lo:hi], lab[lo:hi], rank=rank, nranks=world, NT_total=NT)
+    hs = None
+    if heldout:                                                                 # this rank's shard of the held-out set, one rank of its own
+        NH = len(tlab)
+        hlo, hhi = lib.shard_bounds(NH, world, rank)
+        hs = states(tpx[hlo:hhi], None if tvals is None else tvals[hlo:hhi], tlab[hlo:hhi])
     if world > 1:
         uid = [TrainStates.comm_unique_id() if rank == 0 else None]
         dist.broadcast_object_list(uid, src=0)
@@ -136,6 +177,17 @@ def main(argv=None):
     C0, _, _, nc = ts.quadcost(ts.bond_tensor(1), lam)                          # fixedL.cc:745
     say("Percent correct = %.4f%%, # incorrect = %d/%d" % (nc * 100.0 / NT, NT - nc, NT))
     say("Before starting DMRG Cost = %.10f" % (C0 / NT))
+
+    def say_heldout():
+        h = ts.heldout_report()
+        t = torch.tensor([h["cost"], float(h["ncorrect"]), float(h["count"])], dtype=torch.float64)
+        if world > 1:
+            dist.all_reduce(t)                                                  # local sums of the shards (exact in fp64 for the counts)
+        cost, nc, cnt = float(t[0]), int(round(float(t[1]))), int(round(float(t[2])))
+        say("Held-out: Percent correct = %.4f%%, # incorrect = %d/%d, Cost = %.10f" % (nc * 100.0 / cnt, cnt - nc, cnt, cost / cnt))
+    if hs is not None:
+        ts.attach_heldout(hs)
+        say_heldout()
 
     lam_cost = lam                                                              # cargs copy, fixedL.cc:467
     for sw in range(1, Nsweep + 1):
@@ -162,6 +214,8 @@ def main(argv=None):
                 say("  Reg. cost CR = %.10f" % (r["reg_cost"] / NT))
                 say("Percent correct = %.4f%%, # incorrect = %d/%d" % (r["ncorrect"] * 100.0 / NT, NT - r["ncorrect"], NT))
                 say("--> After SVD, Cost = %.10f" % (r["cost"] / NT))
+            if hs is not None:
+                say_heldout()
             # file hooks: rank 0 looks, every rank follows (fixedL.cc:542-559)
             hook = [None, None]
             if rank == 0:
@@ -195,6 +249,8 @@ def main(argv=None):
     if rank == 0:
         hostlib.write_mps("W", Wnow)
     ts.close()
+    if hs is not None:
+        hs.close()
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
