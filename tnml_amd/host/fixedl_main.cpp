@@ -23,19 +23,11 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/tnml.h"
-#include "host_mps.h"
+#include "driver_util.h"
 #include "init_w.h"
 #include "input_group.h"
-#include "mnist_idx.h"
 
 using namespace tnmlh;
-
-static void die(tnml_ctx* c, const char* what) {
-    std::fprintf(stderr, "%s: %s\n", what, tnml_last_error(c));
-    std::exit(1);
-}
-#define CK(c, call) do { if ((call) != 0) die((c), #call); } while (0)
 
 // the ranks of one process meet here (a generation-counting barrier)
 class HostBarrier {
@@ -50,19 +42,6 @@ class HostBarrier {
         else cv.wait(lk, [&] { return gen != g; });
     }
 };
-
-static void upload(tnml_ctx* ctx, const HostMPS& W) {
-    for (int j = 1; j <= W.N; ++j) CK(ctx, tnml_set_site(ctx, j, W.A[j].ml, W.A[j].mr, W.A[j].L == NL, W.A[j].a.data()));
-}
-static HostMPS download(tnml_ctx* ctx, int N) {
-    HostMPS W(N);
-    for (int j = 1; j <= N; ++j) {
-        int ml, mr, hl; CK(ctx, tnml_site_dims(ctx, j, &ml, &mr, &hl));
-        W.A[j] = Site(ml, mr, hl ? NL : 1);
-        CK(ctx, tnml_get_site(ctx, j, W.A[j].a.data()));
-    }
-    return W;
-}
 
 int main(int argc, const char* argv[]) {
     if (argc != 2) { std::printf("Usage: %s inputfile\n", argv[0]); return 0; }       // fixedL.cc:579-583
@@ -100,20 +79,13 @@ int main(int argc, const char* argv[]) {
         const double feature_scale = input.getReal("feature_scale", 1.);                 // extension
         const bool heldout = input.getYesNo("heldout", false);                          // extension: evaluate the t10k images after every bond update
         const long Ntest = input.getInt("Ntest", 50000);                                 // extension: per-label cap of the held-out set (as fulltest)
-        int dtype = TNML_F64;
-        if (precision == "mixed") dtype = TNML_F64_E32; else if (precision == "f32") dtype = TNML_F32;
-        else if (precision == "bf16x3") dtype = TNML_BF16X3; else if (precision == "bf16") dtype = TNML_BF16;   // study modes (forward contraction on the bf16 matrix pipe)
-        else if (precision != "f64" && precision != "strict") { std::printf("precision must be f64, mixed, f32, bf16x3 or bf16\n"); return 1; }
+        int dtype;
+        if (!parse_dtype(precision, true, &dtype)) return 1;
         if (method != "conj") { std::printf("method type \"%s\" not recognized\n", method.c_str()); return 1; }   // :505
 
-        Dataset train = read_mnist(datadir, true, Ntrain);                              // :613
-        if (imglen > 0) reduce(train, (int)imglen);
+        Dataset train = read_images(datadir, true, Ntrain, imglen);                     // :613
         Dataset test;                                                                   // the held-out set: read before any context exists
-        if (heldout) {
-            test = read_mnist(datadir, false, Ntest);
-            if (imglen > 0) reduce(test, (int)imglen);
-            if (test.npix() != train.npix()) { std::printf("heldout: the t10k images have %d pixels, the training images %d\n", test.npix(), train.npix()); return 1; }
-        }
+        if (heldout && !read_heldout(datadir, Ntest, imglen, train, &test)) return 1;
         std::printf("Training set consists of %d images:\n", train.size());
         for (int l = 0; l < 10; ++l) std::printf("  %d of label %d\n", train.counts[l], l);
         const int N = train.npix();                                                     // :615
@@ -161,15 +133,13 @@ int main(int argc, const char* argv[]) {
         }
         std::printf("overlap(W,W) = %.12g\n", overlap(W, W));                           // :729
         for (int j = 1; j <= N; ++j) if ((W.A[j].L == NL) != (j == c)) { std::printf("Label Index not on site %d\n", c); return 1; }   // :734
-        int wm = 1; for (int j = 1; j <= N; ++j) wm = std::max(wm, std::max(W.A[j].ml, W.A[j].mr));
+        const int wm = max_link_dim(W);
 
         // ---- ranks: one host thread per GPU (the reference's `nthread` worker threads become GPUs: paralleldo.h:21-68) ----
         int nranks = (int)ngpu;
         if (nranks <= 0 && share_device) nranks = 1;
         if (nranks <= 0) {                                                              // ngpu = 0: every visible device from `device` on
-            nranks = 0;
-            int64_t f, t;
-            while (tnml_device_memory(device + nranks, &f, &t) == 0) ++nranks;
+            nranks = count_devices(device);
             if (nranks == 0) die(nullptr, "tnml_device_memory");
         }
         if (nranks > totNtrain) nranks = totNtrain;
@@ -179,46 +149,40 @@ int main(int argc, const char* argv[]) {
             std::printf("Thread %d %lld -> %lld (%lld)\n", r, (long long)lo[r], (long long)hi[r], (long long)(hi[r] - lo[r]));   // :94, one GPU per "thread"
         }
         (void)Nthread;
+        const int totNtest = heldout ? test.size() : 0;
+        std::vector<int64_t> tlo(nranks, 0), thi(nranks, 0);
+        for (int r = 0; heldout && r < nranks; ++r) tnml_shard_bounds(totNtest, nranks, r, &tlo[r], &thi[r]);
+        auto rank_config = [&](int r, int m) {                                          // rank r's training context at maxm = m
+            tnml_config c{};
+            c.device = share_device ? device : device + r; c.rank = r; c.nranks = nranks; c.N = N; c.NT_local = (int)(hi[r] - lo[r]); c.NT_total = totNtrain;
+            c.maxm = m; c.dtype = dtype; c.svd_backend = TNML_SVD_SYEVD;
+            return c;
+        };
+        auto heldout_config = [&](int r, int m) {                                       // rank r's shard of the held-out set, a context of its own
+            tnml_config c = rank_config(r, m);                                          // (a rank without held-out images is refused before its create)
+            c.rank = 0; c.nranks = 1; c.NT_local = c.NT_total = (int)std::max<int64_t>(thi[r] - tlo[r], 1);
+            return c;
+        };
+        const int share_ways = share_device ? nranks : 1;
         // `maxm` is only an upper bound for the reference (default 5000): the contexts are sized by what an N-site MPS can
         // reach and what every GPU can hold for its shard
         int ctx_maxm = (int)std::min<long>(maxm, 1 << 20);
         for (int r = 0; r < nranks; ++r) {
-            tnml_config pc{}; pc.device = share_device ? device : device + r; pc.rank = r; pc.nranks = nranks; pc.N = N; pc.NT_local = (int)(hi[r] - lo[r]); pc.NT_total = totNtrain;
-            pc.maxm = ctx_maxm; pc.dtype = dtype;
-            int64_t freeb = 0, totb = 0;
-            if (tnml_device_memory(pc.device, &freeb, &totb) != 0) die(nullptr, "tnml_device_memory");
-            if (share_device) freeb /= nranks;
+            const tnml_config pc = rank_config(r, ctx_maxm);
+            const int64_t budget = device_budget(pc.device, share_ways);
             // (with a host tier the environments need not fit: only what an N-site MPS can reach bounds maxm then)
-            ctx_maxm = std::min(ctx_maxm, tnml_plan_maxm(&pc, ctx_maxm, wm, env_budget_gb > 0. ? (int64_t)0 : (int64_t)(0.97 * (double)freeb)));
+            ctx_maxm = std::min(ctx_maxm, tnml_plan_maxm(&pc, ctx_maxm, wm, env_budget_gb > 0. ? (int64_t)0 : budget));
         }
         ctx_maxm = std::max(ctx_maxm, wm);
-        const int totNtest = heldout ? test.size() : 0;
-        std::vector<int64_t> tlo(nranks, 0), thi(nranks, 0);
-        for (int r = 0; heldout && r < nranks; ++r) tnml_shard_bounds(totNtest, nranks, r, &tlo[r], &thi[r]);
-        if (heldout && env_budget_gb <= 0.) {
-            // the held-out context keeps all its environments resident beside the training context: both must fit at the planned maxm
-            auto need = [&](int r, int m) {
-                tnml_config pc{}; pc.device = share_device ? device : device + r; pc.rank = r; pc.nranks = nranks; pc.N = N;
-                pc.NT_local = (int)(hi[r] - lo[r]); pc.NT_total = totNtrain; pc.maxm = m; pc.dtype = dtype;
-                tnml_config hc = pc; hc.rank = 0; hc.nranks = 1; hc.NT_local = (int)std::max<int64_t>(thi[r] - tlo[r], 1); hc.NT_total = hc.NT_local;
-                return tnml_estimate_bytes(&pc) + tnml_estimate_bytes(&hc);
-            };
-            for (int r = 0; r < nranks; ++r) {
-                int64_t freeb = 0, totb = 0;
-                if (tnml_device_memory(share_device ? device : device + r, &freeb, &totb) != 0) die(nullptr, "tnml_device_memory");
-                if (share_device) freeb /= nranks;
-                const int64_t budget = (int64_t)(0.97 * (double)freeb);
-                if (need(r, wm) > budget) {
-                    std::printf("heldout = yes: the training and held-out contexts (%lld + %lld images, Ntest = %ld) do not fit on GPU %d even at m = %d; "
-                                "lower Ntest or train without heldout\n", (long long)(hi[r] - lo[r]), (long long)(thi[r] - tlo[r]), Ntest, r, wm);
-                    return 1;
-                }
-                int lo_m = wm, hi_m = ctx_maxm;
-                if (need(r, hi_m) > budget) {
-                    while (hi_m - lo_m > 1) { const int mid = lo_m + (hi_m - lo_m) / 2; if (need(r, mid) <= budget) lo_m = mid; else hi_m = mid; }
-                    ctx_maxm = lo_m;
-                }
+        for (int r = 0; heldout && env_budget_gb <= 0. && r < nranks; ++r) {
+            const tnml_config pc = rank_config(r, wm);
+            const int m = fit_maxm_beside(pc, heldout_config(r, wm), wm, ctx_maxm, device_budget(pc.device, share_ways));
+            if (m < 0) {
+                std::printf("heldout = yes: the training and held-out contexts (%lld + %lld images, Ntest = %ld) do not fit on GPU %d even at m = %d; "
+                            "lower Ntest or train without heldout\n", (long long)(hi[r] - lo[r]), (long long)(thi[r] - tlo[r]), Ntest, r, wm);
+                return 1;
             }
+            ctx_maxm = m;
         }
         if (ctx_maxm < maxm)
             std::printf("maxm=%ld is beyond what %d sites can reach or the GPU can hold for %lld images: bond dimensions are capped at %d\n",
@@ -232,23 +196,21 @@ int main(int argc, const char* argv[]) {
         if (heldout && !test_u8) phi_test = all_features(test, false, feature_scale);
         std::vector<tnml_heldout_report> ho_rep(nranks);
         // rank 0 prints the sums of the ranks' held-out shards (local values: no collective)
-        auto print_heldout = [&]() {
-            double cost = 0.; long long nc = 0, cnt = 0;
-            for (const auto& h : ho_rep) { cost += h.cost; nc += h.ncorrect; cnt += h.count; }
-            std::printf("Held-out: Percent correct = %.4f%%, # incorrect = %lld/%lld, Cost = %.10f\n", nc * 100. / cnt, cnt - nc, cnt, cost / cnt);
+        auto heldout_sum = [&]() {
+            tnml_heldout_report s{};
+            for (const auto& h : ho_rep) { s.cost += h.cost; s.ncorrect += h.ncorrect; s.count += h.count; }
+            return s;
         };
+        auto print_heldout = [&]() { const tnml_heldout_report s = heldout_sum(); print_heldout_line(s.cost, s.ncorrect, s.count); };
         unsigned char uid[128] = {0};
         if (nranks > 1 && !share_device && !oneshot && tnml_comm_unique_id(uid) != 0) die(nullptr, "tnml_comm_unique_id");
         std::vector<tnml_ctx*> all_ctx(nranks, nullptr);
 
         HostBarrier bar(nranks);
         double lambda_shared = lambda;
-        bool write_wf = false;
         auto rank_main = [&](int r) {
             const bool root = r == 0;
-            tnml_config cfg{};
-            cfg.device = share_device ? device : device + r; cfg.rank = r; cfg.nranks = nranks; cfg.N = N; cfg.NT_local = (int)(hi[r] - lo[r]); cfg.NT_total = totNtrain;
-            cfg.maxm = ctx_maxm; cfg.dtype = dtype; cfg.svd_backend = TNML_SVD_SYEVD;
+            const tnml_config cfg = rank_config(r, ctx_maxm);
             tnml_ctx* ctx = nullptr;
             if (tnml_create(&ctx, &cfg) != 0) die(nullptr, "tnml_create");
             if (env_budget_gb > 0.) CK(ctx, tnml_set_option(ctx, "env_budget_mb", (int)(env_budget_gb * 1024.)));
@@ -261,11 +223,11 @@ int main(int argc, const char* argv[]) {
                 if (root && (oneshot ? tnml_comm_init_oneshot(all_ctx.data(), nranks) : tnml_comm_init_local(all_ctx.data(), nranks)) != 0) die(nullptr, "in-process communicator");
                 bar.wait();
             }
-            upload(ctx, W);
+            upload_mps(ctx, W);
             tnml_ctx* hctx = nullptr;                                                       // this rank's shard of the held-out set
             if (heldout) {
-                tnml_config hc = cfg; hc.rank = 0; hc.nranks = 1; hc.NT_local = (int)(thi[r] - tlo[r]); hc.NT_total = hc.NT_local;
-                if (hc.NT_local < 1) die(nullptr, "heldout: a rank without held-out images (more GPUs than t10k images)");
+                if (thi[r] == tlo[r]) die(nullptr, "heldout: a rank without held-out images (more GPUs than t10k images)");
+                const tnml_config hc = heldout_config(r, ctx_maxm);
                 if (tnml_create(&hctx, &hc) != 0) die(nullptr, "tnml_create (heldout)");
                 if (test_u8) CK(hctx, tnml_set_data_u8(hctx, test.pixels.data() + (size_t)tlo[r] * N, test.labels.data() + tlo[r]));
                 else         CK(hctx, tnml_set_data_phi(hctx, phi_test.data() + (size_t)tlo[r] * N * 2, test.labels.data() + tlo[r]));
@@ -346,9 +308,8 @@ int main(int argc, const char* argv[]) {
                         std::fprintf(blog, "%ld,%d,%d,%.6e,%d,%.17g,%.17g,%lld,%d,%d,%d,%.6e,%.6f", sw, ha, r_.c, fl.lam, r_.cg.npass_done, r_.cost_after_svd / totNtrain,
                                      r_.reg_cost / totNtrain, (long long)r_.ncorrect, totNtrain, r_.origm, r_.newm, r_.truncerr, std::chrono::duration<double>(t_now - t_last).count());
                         if (heldout) {
-                            double hc = 0.; long long hn = 0;
-                            for (const auto& h : ho_rep) { hc += h.cost; hn += h.ncorrect; }
-                            std::fprintf(blog, ",%.17g,%lld,%d", hc / totNtest, hn, totNtest);
+                            const tnml_heldout_report s = heldout_sum();
+                            std::fprintf(blog, ",%.17g,%lld,%d", s.cost / totNtest, (long long)s.ncorrect, totNtest);
                         }
                         std::fprintf(blog, "\n");
                         t_last = t_now;
@@ -361,7 +322,7 @@ int main(int argc, const char* argv[]) {
                         std::printf("File WRITE_WF found\n");
                         std::remove("WRITE_WF");
                         std::printf("Writing W to disk\n");
-                        write_mps("W", download(ctx, N));                               // (pipelined: the network as the bond update in flight leaves it)
+                        write_mps("W", download_mps(ctx, N));                           // (pipelined: the network as the bond update in flight leaves it)
                     }
                     if (file_exists("LAMBDA")) {                                        // :550-559
                         std::ifstream lf("LAMBDA"); lf >> lambda_shared; lf.close();
@@ -388,19 +349,18 @@ int main(int argc, const char* argv[]) {
                 finish();
                 if (root) {
                     std::printf("Writing W to disk\n");                                     // :565
-                    write_mps("W", download(ctx, N));                                       // :566
+                    write_mps("W", download_mps(ctx, N));                                   // :566
                 }
             }
             if (root) {
                 std::printf("Writing W to disk\n");                                         // :763
-                write_mps("W", download(ctx, N));                                           // :764
+                write_mps("W", download_mps(ctx, N));                                       // :764
             }
             if (blog) std::fclose(blog);
             if (nranks > 1) { CK(ctx, tnml_replica_check(ctx, nullptr)); bar.wait(); }
             tnml_destroy(ctx);                                                              // (detaches the held-out context)
             if (hctx) tnml_destroy(hctx);
         };
-        (void)write_wf;
         std::vector<std::thread> workers;
         for (int r = 1; r < nranks; ++r) workers.emplace_back(rank_main, r);
         rank_main(0);

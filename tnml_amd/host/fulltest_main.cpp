@@ -12,25 +12,16 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tnml.h"
-#include "host_mps.h"
+#include "driver_util.h"
 #include "init_w.h"
 #include "input_group.h"
-#include "mnist_idx.h"
 
 using namespace tnmlh;
-
-static void die(tnml_ctx* c, const char* what) {
-    std::fprintf(stderr, "%s: %s\n", what, tnml_last_error(c));
-    std::exit(1);
-}
-#define CK(c, call) do { if ((call) != 0) die((c), #call); } while (0)
 
 int main(int argc, const char* argv[]) {
     if (argc != 2) { std::printf("Usage: %s inputfile\n", argv[0]); return 0; }       // fulltest.cc:10-14
     try {
         InputGroup input(argv[1], "input");
-        const int d = 2;
         const std::string datadir = input.getString("datadir", "/Users/mstoudenmire/software/tnml/mllib/MNIST");
         const std::string fname = input.getString("fname", "W");
         const std::string feature = input.getString("feature", "series");
@@ -39,17 +30,13 @@ int main(int argc, const char* argv[]) {
         const long Ntest = input.getInt("Ntest", 50000);                               // mllib/mnist.h:452 default NT
         const long imglen = input.getInt("imglen", 0);
         const double feature_scale = input.getReal("feature_scale", 1.);
-        int dtype = TNML_F64;
-        if (precision == "mixed") dtype = TNML_F64_E32; else if (precision == "f32") dtype = TNML_F32;
-        else if (precision != "f64" && precision != "strict") { std::printf("precision must be f64, mixed or f32\n"); return 1; }
+        int dtype;
+        if (!parse_dtype(precision, false, &dtype)) return 1;
 
-        std::printf("Labels:"); for (int l = 0; l < 10; ++l) std::printf(" %d", l); std::printf("\n");   // :28
-        Dataset test = read_mnist(datadir, false, Ntest);                              // :30
-        if (imglen > 0) reduce(test, (int)imglen);
+        std::printf("Labels: 0 1 2 3 4 5 6 7 8 9\n");                                   // :28
+        Dataset test = read_images(datadir, false, Ntest, imglen);                      // :30
         const int N = test.npix();
-        if (!file_exists("sites")) { std::printf("Couldn't find file 'sites'\n"); return 1; }             // :34-41
-        int Ns, ds; read_sites("sites", &Ns, &ds);
-        if (Ns != N || ds != d) { std::printf("Mismatched sizes\n"); return 1; }                         // util.h:68
+        if (!sites_match(N)) return 1;                                                  // :34-41
         bool normal;
         if (feature == "norm" || feature == "normal") normal = true;                   // :45-56
         else if (feature == "series") normal = false;
@@ -65,11 +52,10 @@ int main(int argc, const char* argv[]) {
         for (int j = 1; j <= N; ++j) if (psi.A[j].L == NL) { cent = j; break; }
         if (cent == 0) { std::printf("expected Label index at some site of psi MPS\n"); return 1; }
         if (cent != N / 2) { std::printf("Label Index not on site %d\n", N / 2); return 1; }
-        int wm = 1; for (int j = 1; j <= N; ++j) wm = std::max(wm, std::max(psi.A[j].ml, psi.A[j].mr));
 
         tnml_config cfg{};
         cfg.device = device; cfg.rank = 0; cfg.nranks = 1; cfg.N = N; cfg.NT_local = totNtest; cfg.NT_total = totNtest;
-        cfg.maxm = wm; cfg.dtype = dtype; cfg.svd_backend = TNML_SVD_SYEVD;
+        cfg.maxm = max_link_dim(psi); cfg.dtype = dtype; cfg.svd_backend = TNML_SVD_SYEVD;
         tnml_ctx* ctx = nullptr;
         if (tnml_create(&ctx, &cfg)) die(nullptr, "tnml_create");
         if (!normal && !test.reduced() && feature_scale == 1.) {
@@ -78,24 +64,12 @@ int main(int argc, const char* argv[]) {
             std::vector<double> phi = all_features(test, normal, feature_scale);       // fulltest.cc:57-70
             CK(ctx, tnml_set_data_phi(ctx, phi.data(), test.labels.data()));
         }
-        for (int j = 1; j <= N; ++j) CK(ctx, tnml_set_site(ctx, j, psi.A[j].ml, psi.A[j].mr, psi.A[j].L == NL, psi.A[j].a.data()));
+        upload_mps(ctx, psi);
 
         std::printf("Running full test of %s\n", fname.c_str());                       // :97
         int64_t counts[10], ninc[10];
         CK(ctx, tnml_classify(ctx, nullptr, nullptr, counts, ninc));
-        long nte = 0, tninc = 0;
-        for (int l = 0; l < 10; ++l) { nte += (long)counts[l]; tninc += (long)ninc[l]; }
-        const long tncor = nte - tninc;
-        std::printf("%ld/%ld correct (%.2f%%), %ld/%ld incorrect (%.2f%%)\n",           // util.h:186-187
-                    tncor, nte, tncor * 100. / nte, tninc, nte, tninc * 100. / nte);
-        long tot = 0;
-        for (int l = 0; l < 10; ++l) {                                                 // util.h:189-198
-            const long nt = (long)counts[l]; tot += nt;
-            if (nt == 0) continue;
-            const long ni = (long)ninc[l], nc = nt - ni;
-            std::printf("  Digit %d %ld/%ld correct (%.2f%%), %ld/%ld incorrect (%.2f%%)\n", l, nc, nt, nc * 100. / nt, ni, nt, ni * 100. / nt);
-        }
-        std::printf("Total # test images = %ld\n", tot);                               // util.h:199
+        print_fulltest_table(counts, ninc);                                            // util.h:186-199
         tnml_destroy(ctx);
     } catch (const std::exception& e) {
         std::printf("%s\n", e.what());

@@ -22,19 +22,11 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tnml.h"
-#include "host_mps.h"
+#include "driver_util.h"
 #include "input_group.h"
 #include "linear_mps.h"
-#include "mnist_idx.h"
 
 using namespace tnmlh;
-
-static void die(tnml_lin* c, const char* what) {
-    std::fprintf(stderr, "%s: %s\n", what, tnml_lin_last_error(c));
-    std::exit(1);
-}
-#define CK(c, call) do { if ((call) != 0) die((c), #call); } while (0)
 
 static std::vector<int> parse_labels(const std::string& s) {
     std::vector<int> out;
@@ -105,7 +97,7 @@ int main(int argc, const char* argv[]) {
         std::printf("done\n");
 
         tnml_lin* ctx = nullptr;
-        if (tnml_lin_create(&ctx, device, N) != 0) die(nullptr, "tnml_lin_create");
+        if (tnml_lin_create(&ctx, device, N) != 0) die(ctx, "tnml_lin_create");         // ctx stays NULL: the create's error
         CK(ctx, tnml_lin_set_data_u8(ctx, train.size(), train.pixels.data(), train.labels.data()));
         CK(ctx, tnml_lin_set_labels(ctx, K, labs.data()));
 

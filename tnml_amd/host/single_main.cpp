@@ -22,26 +22,11 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tnml.h"
-#include "host_mps.h"
+#include "driver_util.h"
 #include "init_w.h"
 #include "input_group.h"
-#include "mnist_idx.h"
 
 using namespace tnmlh;
-
-static void die(tnml_ctx* c, const char* what) { std::fprintf(stderr, "%s: %s\n", what, tnml_last_error(c)); std::exit(1); }
-#define CK(c, call) do { if ((call) != 0) die((c), #call); } while (0)
-
-static HostMPS download(tnml_ctx* ctx, int N) {
-    HostMPS W(N);
-    for (int j = 1; j <= N; ++j) {
-        int ml, mr, hl; CK(ctx, tnml_site_dims(ctx, j, &ml, &mr, &hl));
-        W.A[j] = Site(ml, mr, 1);
-        CK(ctx, tnml_get_site(ctx, j, W.A[j].a.data()));
-    }
-    return W;
-}
 
 // BASELINE config 4: "single.cc per-label MPS x10, one label per GPU (embarrassingly parallel, no collectives)".  The reference trains
 // the ten networks as ten runs of `single` with ten input files, each in its own directory L<n> (separate_fulltest.cc:158 reads
@@ -69,7 +54,7 @@ static int launch_per_label(const char* self, const char* inputfile, const Input
     if (share) ngpu = 1;
     if (ngpu <= 0) {
         if (dry) ngpu = 8;
-        else { int64_t f, t; ngpu = 0; while (tnml_device_memory(dev0 + ngpu, &f, &t) == 0) ++ngpu; }
+        else ngpu = count_devices(dev0);
         if (ngpu == 0) { std::fprintf(stderr, "no HIP device: %s\n", tnml_last_error(nullptr)); return 1; }
     }
     char inabs[PATH_MAX], selfabs[PATH_MAX], ddabs[PATH_MAX];
@@ -158,9 +143,8 @@ int main(int argc, const char* argv[]) {
         const double feature_scale = input.getReal("feature_scale", 1.);
         const bool heldout = input.getYesNo("heldout", false);
         const long Ntest = input.getInt("Ntest", 50000);
-        int dtype = TNML_F64;
-        if (precision == "mixed") dtype = TNML_F64_E32; else if (precision == "f32") dtype = TNML_F32;
-        else if (precision != "f64" && precision != "strict") { std::printf("precision must be f64, mixed or f32\n"); return 1; }
+        int dtype;
+        if (!parse_dtype(precision, false, &dtype)) return 1;
         if (L < 0 || L > 9) { std::printf("label must be in 0..9\n"); return 1; }
         if (method != "conj" && method != "fast_conj" && method != "exact" && method != "pinv") { std::printf("method type \"%s\" not recognized\n", method.c_str()); return 1; }   // single.h:611
         const bool fast_conj = method == "fast_conj";                                  // single.h:599
@@ -168,14 +152,9 @@ int main(int argc, const char* argv[]) {
         const bool pinv = method == "pinv";                                            // single.h:596
 
         char wname[32]; std::snprintf(wname, sizeof wname, "W%d", L);                  // :53
-        Dataset train = read_mnist(datadir, true, Ntrain);                              // :56
-        if (imglen > 0) reduce(train, (int)imglen);
+        Dataset train = read_images(datadir, true, Ntrain, imglen);                     // :56
         Dataset test;                                                                   // the held-out set: read before any context exists
-        if (heldout) {
-            test = read_mnist(datadir, false, Ntest);
-            if (imglen > 0) reduce(test, (int)imglen);
-            if (test.npix() != train.npix()) { std::printf("heldout: the t10k images have %d pixels, the training images %d\n", test.npix(), train.npix()); return 1; }
-        }
+        if (heldout && !read_heldout(datadir, Ntest, imglen, train, &test)) return 1;
         const int N = train.npix();
         std::printf("%d sites\n", N);                                                  // :59
         if (file_exists("sites")) { int Ns, ds; read_sites("sites", &Ns, &ds); if (Ns != N || ds != 2) { std::printf("Mismatched sizes\n"); return 1; } }
@@ -224,29 +203,24 @@ int main(int argc, const char* argv[]) {
             if (normal) features_normal(train, order[k], ph); else features_series(train, order[k], ph, feature_scale);
             std::copy(ph.begin(), ph.end(), phi.begin() + (size_t)k * N * 2);
         }
-        int wm = 1; for (int j = 1; j <= N; ++j) wm = std::max(wm, std::max(W.A[j].ml, W.A[j].mr));
+        const int wm = max_link_dim(W);
 
         tnml_config cfg{};
         cfg.device = device; cfg.rank = 0; cfg.nranks = 1; cfg.N = N; cfg.NT_local = totNtrain; cfg.NT_total = totNtrain;
         cfg.maxm = (int)std::min<long>(maxm, 1 << 20); cfg.dtype = dtype; cfg.svd_backend = TNML_SVD_SYEVD;
         cfg.mode = TNML_MODE_SINGLE; cfg.target_label = L;
+        auto heldout_config = [&]() { tnml_config h = cfg; h.NT_local = h.NT_total = test.size(); return h; };
         {   // `maxm` is only an upper bound for the reference: size the context by what N sites can reach and the GPU can hold
-            int64_t freeb = 0, totb = 0;
-            if (tnml_device_memory(device, &freeb, &totb) != 0) die(nullptr, "tnml_device_memory");
-            cfg.maxm = std::max(wm, tnml_plan_maxm(&cfg, cfg.maxm, wm, (int64_t)(0.97 * (double)freeb)));
-            if (heldout) {                                                              // the held-out context keeps all its environments resident as well
-                auto need = [&](int m) { tnml_config t = cfg, h = cfg; t.maxm = h.maxm = m; h.NT_local = test.size(); h.NT_total = test.size(); return tnml_estimate_bytes(&t) + tnml_estimate_bytes(&h); };
-                const int64_t budget = (int64_t)(0.97 * (double)freeb);
-                if (need(wm) > budget) {
+            const int64_t budget = device_budget(device, 1);
+            cfg.maxm = std::max(wm, tnml_plan_maxm(&cfg, cfg.maxm, wm, budget));
+            if (heldout) {
+                const int m = fit_maxm_beside(cfg, heldout_config(), wm, cfg.maxm, budget);
+                if (m < 0) {
                     std::printf("heldout = yes: the training and held-out contexts (%d + %d images, Ntest = %ld) do not fit on the GPU even at m = %d; "
                                 "lower Ntest or train without heldout\n", totNtrain, test.size(), Ntest, wm);
                     return 1;
                 }
-                int lo_m = wm, hi_m = cfg.maxm;
-                if (need(hi_m) > budget) {
-                    while (hi_m - lo_m > 1) { const int mid = lo_m + (hi_m - lo_m) / 2; if (need(mid) <= budget) lo_m = mid; else hi_m = mid; }
-                    cfg.maxm = lo_m;
-                }
+                cfg.maxm = m;
             }
             if (cfg.maxm < maxm) std::printf("maxm=%ld is beyond what %d sites can reach or the GPU can hold for %d images: bond dimensions are capped at %d\n", maxm, N, totNtrain, cfg.maxm);
         }
@@ -257,27 +231,18 @@ int main(int argc, const char* argv[]) {
         if (noise >= 1E-14) CK(ctx, tnml_set_option_real(ctx, "noise", noise));           // sweeps.noise() = noise, single.cc:222
         CK(ctx, tnml_set_data_phi(ctx, phi.data(), labels.data()));
         phi.clear(); phi.shrink_to_fit();
-        for (int j = 1; j <= N; ++j) CK(ctx, tnml_set_site(ctx, j, W.A[j].ml, W.A[j].mr, 0, W.A[j].a.data()));
+        upload_mps(ctx, W);
         tnml_ctx* hctx = nullptr;
         if (heldout) {
-            tnml_config hc = cfg; hc.NT_local = test.size(); hc.NT_total = test.size();
+            const tnml_config hc = heldout_config();
             if (tnml_create(&hctx, &hc) != 0) die(nullptr, "tnml_create (heldout)");
-            std::vector<double> hphi((size_t)test.size() * N * 2);
-            for (int k = 0; k < test.size(); ++k) {
-                if (normal) features_normal(test, k, ph); else features_series(test, k, ph, feature_scale);
-                std::copy(ph.begin(), ph.end(), hphi.begin() + (size_t)k * N * 2);
-            }
+            const std::vector<double> hphi = all_features(test, normal, feature_scale);
             CK(hctx, tnml_set_data_phi(hctx, hphi.data(), test.labels.data()));
         }
         std::printf("Projecting training states..."); std::fflush(stdout);              // :183
         CK(ctx, tnml_env_init(ctx));                                                    // :184-199
         std::printf("done\n");
-        auto print_heldout = [&]() {
-            tnml_heldout_report h;
-            CK(ctx, tnml_heldout_read(ctx, &h));
-            std::printf("Held-out: Percent correct = %.4f%%, # incorrect = %lld/%lld, Cost = %.10f\n", h.ncorrect * 100. / h.count,
-                        (long long)(h.count - h.ncorrect), (long long)h.count, h.cost / h.count);
-        };
+        auto print_heldout = [&]() { tnml_heldout_report h; CK(ctx, tnml_heldout_read(ctx, &h)); print_heldout_line(h.cost, h.ncorrect, h.count); };
         {
             int mL, mR, lab; CK(ctx, tnml_bond_dims(ctx, 1, &mL, &mR, &lab));
             std::vector<double> B((size_t)mL * 4 * mR);
@@ -349,15 +314,15 @@ int main(int argc, const char* argv[]) {
                     std::printf("File WRITE_WF found\n");
                     std::remove("WRITE_WF");
                     std::printf("Writing %s to disk\n", wname);
-                    write_mps(wname, download(ctx, N));
+                    write_mps(wname, download_mps(ctx, N));
                 }
                 std::fflush(stdout);
             }
             std::printf("Writing %s to disk\n", wname);                                 // :722
-            write_mps(wname, download(ctx, N));
+            write_mps(wname, download_mps(ctx, N));
         }
         std::printf("Writing %s to disk\n", wname);                                     // single.cc:240
-        write_mps(wname, download(ctx, N));
+        write_mps(wname, download_mps(ctx, N));
         tnml_destroy(ctx);                                                              // (detaches the held-out context)
         if (hctx) tnml_destroy(hctx);
     } catch (const std::exception& e) {
