@@ -279,3 +279,104 @@ def test_pinv_matches_numpy_and_approaches_the_exact_solver(b, r):
         y = (labels == 1).astype(float)
         if np.linalg.matrix_rank(Phi) == D:
             np.testing.assert_allclose(Bf.reshape(-1, order="F"), np.linalg.solve(Phi.T @ Phi, Phi.T @ y), rtol=1e-5, atol=1e-8)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the ground truth of test_single_at_shape.py, pinned where that module uses it
+UNEQUAL = [1, 2, 4, 7, 13, 24, 31, 17, 8, 4, 2, 1]
+
+
+def unequal_problem(NT=37, seed=5):
+    import tiled_reference as tr
+    N = len(UNEQUAL) - 1
+    labels = synth.synthetic_labels(NT, seed=seed, per_label=None)
+    pixels = synth.synthetic_images(N, labels, seed=seed)
+    phi = pyoracle.features_single(pixels, True).copy()
+    phi[..., 1] *= 300.0
+    return labels, phi, tr.plain_mps_with_dims(UNEQUAL, seed + 6)
+
+
+@pytest.mark.parametrize("ha", [1, 2])
+def test_single_oracle_matches_numpy_where_left_and_right_dimensions_differ(ha):
+    """mL != mR at every interior bond (link dimensions 1, 2, 4, 7, 13, 24, 31, 17, 8, 4, 2, 1), both half sweeps: gradient, four CG passes
+    (conj and fast_conj) and the split with noise 1e-3, C oracle against the einsum restatement at every bond, the two kept in lockstep."""
+    labels, phi, W = unequal_problem()
+    N = len(UNEQUAL) - 1
+    o = pyoracle.SingleOracle(phi, labels, 3, W, nthread=2)
+    n = npr.NpSingle(phi, labels, 3, W)
+    o.init(); n.init()
+    if ha == 2:
+        for b in range(1, N):
+            o.shiftE(b, True); n.shiftE(b, True)
+    for b in (range(1, N) if ha == 1 else range(N - 1, 0, -1)):
+        o.set_bond(b); n.set_bond(b)
+        B0 = o.bond_tensor(b)
+        assert B0.shape == (UNEQUAL[b - 1], 2, 2, UNEQUAL[b + 1])
+        B = B0 * (1.0 + 0.2 * np.cos(1.0 + np.arange(B0.size)).reshape(B0.shape))
+        Go, Gn = o.gradient(B), n.gradient(B)
+        assert np.abs(Go - Gn).max() < 1e-12 * np.abs(Gn).max(), b
+        assert o.quadcost(B, 1e-3)[0] == pytest.approx(n.quadcost(B, 1e-3), rel=1e-12)
+        Bo, to = o.cgrad(B, 4, 1e-3, 1e-10)
+        Bn, tn = n.cgrad(B, 4, 1e-3, 1e-10)
+        np.testing.assert_allclose(to["cost"], tn["cost"], rtol=1e-10)
+        np.testing.assert_allclose(to["alpha"], tn["alpha"], rtol=1e-8)
+        assert np.abs(Bo - Bn).max() < 1e-8 * np.abs(Bn).max(), b
+        Bo, to = o.fast_cgrad(B, 4, 1e-3, 1e-10)
+        Bn, tn = n.fast_cgrad(B, 4, 1e-3, 1e-10)
+        np.testing.assert_allclose(to["alpha"], tn["alpha"], rtol=1e-8)
+        np.testing.assert_allclose(to["rnorm"], tn["rnorm"], rtol=1e-7)
+        keep = max(2, min(B.shape[0], B.shape[3]))
+        mo, teo = o.noise_split(B, b, ha, 1e-3, 1e-12, keep, 1)
+        mn, ten = n.noise_split(B, b, ha, 1e-3, 1e-12, keep, 1)
+        assert mo == mn and teo == pytest.approx(ten, rel=1e-6, abs=1e-14), b
+        Bo, Bn = o.bond_tensor(b), n.bond_tensor(b)
+        assert np.abs(Bo - Bn).max() < 1e-9 * np.abs(Bn).max(), b
+        for j in (b, b + 1):                                       # the original sites again: the walk keeps the prescribed dimensions
+            o.set_site(j, W[j - 1]); n.W[j] = np.array(W[j - 1])
+        o.shiftE(b, ha == 1); n.shiftE(b, ha == 1)
+
+
+def test_per_label_tiled_identities_with_the_oracle_on_both_sides():
+    """The per-label identities of tiled_reference.py with the C oracle on the MATERIALISED set of 420 = 7 x 60 images and on the 60 base
+    images: outputs, gradient, cost, #correct; the CG at lambda / R, cconv / R; the split with noise at noise R, at an interior bond and
+    at a chain end (drho = NT rho) -- so that test_single_at_shape.py's case at 30 720 images measures the kernels, not the harness."""
+    import tiled_reference as tr
+    N, K, NT, m, target, lam, noise = 12, 60, 420, 6, 3, 1e-3, 1e-4
+    tp = tr.tiled_problem(N, K, NT, m, 3, pixel_boost=200.0)
+    tp.W = tr.without_label(tp.W)
+    R = tp.R
+    assert R == 7 and not np.array_equal(tp.idx, np.arange(NT) % K)
+    big = pyoracle.SingleOracle(tp.phi, tp.labels, target, tp.W, nthread=2)
+    base = pyoracle.SingleOracle(tp.phi0, tp.labels0, target, tp.W, nthread=2)
+    big.init(); base.init()
+    at = 1
+    for b in (1, 4, 8):
+        for bb in range(at, b):
+            big.shiftE(bb, True); base.shiftE(bb, True)
+        at = b
+        big.set_bond(b); base.set_bond(b)
+        B0 = big.bond_tensor(b)
+        B = B0 + 0.1 * np.random.default_rng(b).standard_normal(B0.shape)
+        fb = base.forward(B)
+        want = tr.single_tiled(tp, target, fb, base.gradient(B), base.quadcost(B, lam / R)[0])
+        f = big.forward(B)
+        assert tr.relmax(f, want["P"]) < 1e-12, b
+        assert tr.relmax(big.gradient(B), want["G"]) < 1e-11, b
+        assert big.quadcost(B, lam)[0] == pytest.approx(want["cost"], rel=1e-12), b
+        assert tr.single_hits(f, tp.labels, target) == want["ncorrect"], b
+        Bb, tb = big.cgrad(B0, 4, lam, 1e-10)
+        Bs, ts_ = base.cgrad(B0, 4, lam / R, 1e-10 / R)
+        sc = tr.scaled_trace(ts_, R)
+        assert tb["npass_done"] == ts_["npass_done"] == 4
+        np.testing.assert_allclose(tb["cost"], sc["cost"], rtol=1e-9, err_msg=str(b))
+        for k in ("alpha", "rnorm", "pAp"):
+            np.testing.assert_allclose(tb[k], sc[k], rtol=1e-5, err_msg="%s bond %d" % (k, b))
+        assert tr.relmax(Bb, Bs) < 1e-5, b
+        if b in (1, 8):                                            # the split after the CG, the same bond tensor on both sides
+            keep = max(2, min(B0.shape[0], B0.shape[3]) - 1)
+            mb, teb = big.noise_split(Bs, b, 1, noise, 1e-12, keep, 1)
+            ms, tes = base.noise_split(Bs, b, 1, noise * R, 1e-12, keep, 1)
+            assert mb == ms and teb == pytest.approx(tes, rel=1e-6, abs=1e-16), b
+            assert tr.relmax(big.bond_tensor(b), base.bond_tensor(b)) < 1e-8, b
+            big.shiftE(b, True); base.shiftE(b, True)
+            at = b + 1

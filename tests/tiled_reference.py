@@ -31,6 +31,26 @@ def mps_with_dims(dims, seed):
     return W
 
 
+def plain_mps_with_dims(dims, seed):
+    """the same recipe without the Label index: the plain weight MPS of the per-label variant (single.cc)"""
+    rng = np.random.default_rng(seed)
+    W = []
+    for j in range(1, len(dims)):
+        ml, mr = dims[j - 1], dims[j]
+        A = rng.standard_normal((ml, 2, mr)) / np.sqrt(2. * max(ml, mr))
+        A[:, 0] += np.eye(ml, mr)
+        W.append(A)
+    return W
+
+
+def without_label(W):
+    """a Label-carrying weight MPS as a plain one: the first label's slice of site N/2 (scaled back up, as the per-label tests do)"""
+    W = list(W)
+    c0 = len(W) // 2
+    W[c0 - 1] = W[c0 - 1][..., 0] * 3.0
+    return W
+
+
 class TiledProblem:
     """base problem (phi0, labels0, W), the index vector and its counts; the materialised large set on demand"""
 
@@ -150,3 +170,22 @@ def scaled_trace(tr, R):
     """the large set's CG trace from the base set's at lambda/R, cconv/R"""
     return dict(cost=[R * x for x in tr["cost"]], rnorm=[R * x for x in tr["rnorm"]], alpha=[x / R for x in tr["alpha"]],
                 pAp=[float(R) ** 3 * x for x in tr["pAp"]])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The per-label variant (single.cc / single.h: plain weight MPS, one output f_n per image, target y_n = [l_n == target]).  With a uniform
+# repeat count R the large set follows from the base set alone:
+#   f_big[n] = f_base[idx[n]];  G_big = R G_base;  cost_big(lambda) = R cost_base(lambda / R);  #correct_big = R #correct_base;
+#   the CG (conj) on the large set is the base set's at lambda / R, cconv / R: the same B after every pass, traces scaled as scaled_trace does;
+#   the density-matrix split with a noise term is the base set's at noise * R: rho = B B^dag does not depend on the images while
+#   drho = sum_n dr_n dr_n^dag does, so rho + noise drho_big = rho + (noise R) drho_base -- also at the chain ends, where drho = NT rho.
+def single_hits(f, labels, target):
+    """#correct of the per-label variant (single.h:103,193): the decision f > 1/2 against [label == target]"""
+    return int(((np.asarray(f) > 0.5) == (np.asarray(labels) == target)).sum())
+
+
+def single_tiled(tp, target, f_base, G_base, cost_base_at_lam_over_R):
+    """outputs, gradient, cost and #correct of the large set from the base set's (uniform repeat count)"""
+    assert tp.R is not None
+    return dict(P=np.asarray(f_base)[tp.idx], G=tp.R * np.asarray(G_base), cost=tp.R * cost_base_at_lam_over_R,
+                ncorrect=tp.R * single_hits(f_base, tp.labels0, target))

@@ -132,24 +132,25 @@ __global__ void k_noise_weights(const double* __restrict__ T, int NTp, int NT, i
         }
     w[n] = w00; w[NTp + n] = w01; w[2 * (size_t)NTp + n] = w11;      // images beyond NT (padding) weigh nothing
 }
+// (nblk() caps the grid at 2048 workgroups: like every kernel it sizes, these three stride over the grid -- mE * NTp passes 2048 * 256
+// from 4 608 images at mE = 120 on)
 __global__ void k_noise_scale_rows(const double* __restrict__ E, const double* __restrict__ w, double* __restrict__ Es, int mE, int NTp) {
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i >= (size_t)mE * NTp) return;
-    Es[i] = E[i] * w[i % NTp];
+    const size_t total = (size_t)mE * NTp;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) Es[i] = E[i] * w[i % NTp];
 }
 // rho[(e1,s1),(e2,s2)] += noise * blk_{s1 s2}[e1][e2]; row index e + mE s on the left site (ha = 1), s + 2 e on the right site (ha = 2)
 __global__ void k_noise_add(double* __restrict__ rho, int n, const double* __restrict__ blk, int mE, int ha, double noise) {
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i >= (size_t)n * n) return;
-    const int r1 = (int)(i % n), r2 = (int)(i / n);
-    const int e1 = ha == 1 ? r1 % mE : r1 / 2, s1 = ha == 1 ? r1 / mE : r1 % 2;
-    const int e2 = ha == 1 ? r2 % mE : r2 / 2, s2 = ha == 1 ? r2 / mE : r2 % 2;
-    const int k = s1 + s2;                                           // 0: w00, 1: w01 (= w10), 2: w11
-    rho[i] += noise * blk[(size_t)k * mE * mE + e1 + (size_t)mE * e2];
+    const size_t total = (size_t)n * n;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int r1 = (int)(i % n), r2 = (int)(i / n);
+        const int e1 = ha == 1 ? r1 % mE : r1 / 2, s1 = ha == 1 ? r1 / mE : r1 % 2;
+        const int e2 = ha == 1 ? r2 % mE : r2 / 2, s2 = ha == 1 ? r2 / mE : r2 % 2;
+        const int k = s1 + s2;                                       // 0: w00, 1: w01 (= w10), 2: w11
+        rho[i] += noise * blk[(size_t)k * mE * mE + e1 + (size_t)mE * e2];
+    }
 }
 __global__ void k_scale_all(double* __restrict__ x, size_t n, double f) {
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i < n) x[i] *= f;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) x[i] *= f;
 }
 // G (n x n, the Gram matrix over the indices of site c) += noise * drho.  B_it: the bond tensor in ITensor order [a][s][t][be].
 static int noise_add(tnml_ctx* c, const double* B_it, int b, int ha, int mL, int mR, double* G, int n) {
