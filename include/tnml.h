@@ -332,6 +332,8 @@ int tnml_synchronize(tnml_ctx* ctx);
    Kernel selection (0 never, 1 by shape and image count (default), 2 always):
      "fwd_res", "shift_res"  (TNML_FWD_RES, TNML_SHIFT_RES) the resident-operand forward pass / Label-carrying shift (kernels_res.hip);
                       fwd_res 3 = the general form on 120 x 120 bonds too
+     "shift_skip"     (TNML_SHIFT_SKIP) the resident-operand shift walks a tile's images zero features first and leaves out the odd-row
+                      products of 16-image groups whose phi[1] is 0 throughout (default 1; 0 = natural order, every product; same values)
      "grad_quad"      (TNML_GRAD_QUAD) the resident-accumulator gradient GEMM (kernels_grad.hip)
      "grad_pair"      (TNML_GRAD_PAIR) its pair form for bonds up to 64 x 64 (default 1; 0 = the quad form)
      "bgs_chol"       (TNML_BGS_CHOL) block Gram-Schmidt Cholesky QR of a kept basis of 129-384 columns (default 1; 0 = dpotrf + dtrsm)
@@ -360,6 +362,10 @@ int tnml_set_option_real(tnml_ctx* ctx, const char* name, double value);
    that bond update with the synchronous split, and the one begun after it), and the device time of the repeated work in ms (event-timed;
    call after tnml_synchronize for the full sum).  fixedL.cc:519-521 has no counterpart: ITensor's svd is synchronous. */
 int tnml_split_stats(tnml_ctx* ctx, int64_t* spec_splits, int64_t* roll_backs, double* roll_back_ms);
+/* The tile order tables of the resident-operand shift (option "shift_skip"; fp64 storage, TNML_MODE_FIXEDL, maxm >= 33), built when the data
+   are set: for site 1..N the number of 16-image groups (padded image count / 16) and how many of them hold only images with phi[1] == 0
+   once each 64-image tile is walked zero features first -- the groups whose odd-row products are left out. */
+int tnml_shift_skip_stats(tnml_ctx* ctx, int site, int64_t* groups, int64_t* skipped);
 /* health of the in-house eigensolver: number of fallbacks to rocSOLVER so far, number of splits whose kept basis
    held an eigenvalue cluster and was re-orthonormalised by Cholesky QR, and max|Q^T Q - I| of the kept basis
    before the first / second Newton-Schulz polish step of the last split */

@@ -325,10 +325,73 @@ __global__ __launch_bounds__(768) void k_fwd_res(FwdResArgs A) {
 // Other bond dimensions than 120 (trained bonds shrink towards minm = maxm/2, fixedL.cc:593): the input dimension picks the instantiation
 // (NKS = ceil(mI / 4) rounded up to the next one built; rows from mI on are staged from a valid row and meet zero rows of M); with at most four
 // column tiles (mO <= 64) the eight waves take one 32-image half of the tile each, so all of them keep issuing MFMAs.
+// ZS (zero features first; the tables of launch_shift_order are given): phi[1] = 0 exactly wherever a pixel is 0, and then the odd-row product
+// of that image is multiplied by zero in the epilogue.  The products are per image (the reduction runs over the link index), so the 64 images
+// of a tile may be walked in any order: slot j of a tile is image ord[j], the images with phi[1] == 0 first, and the first nz / 16 of the
+// tile's four 16-image groups run WITHOUT their odd-row MFMAs and take E' = phi[0] (E M_even).  Loop shape: ONE k-loop per tile over all four
+// groups -- four even chains and 4 - nz / 16 odd ones, 4..8 accumulator chains per wave (two loops, even then odd, would leave the odd loop with
+// 1..3 chains; a SIMD needs 8 over its two waves, see k_fwd_res); with at most four column tiles a wave runs two groups, 2..4 chains.  Order
+// granularity: single images (8-byte stores scattered inside a row's 512-byte segment of the tile).  A lane's four slots feed its fragment
+// reads, its feature reads and its output addresses; the next tile's slots are fetched at the top of a round, beside its DMA pieces (nz / 16 rides
+// in spare bits of the order bytes: one fetch).  ALL of a tile's outputs are stored at the top of the next round (the k-loop ends with every
+// group at once).  Registers: 239 at NKS = 30, no scratch -- a spilled element of M is reloaded inside the k-loop behind a vmcnt(0).
 // ==========================================================================================================================
 #define SR_TI 64
 
-template <int NKS>
+// NG 16-image groups of a tile in one k-loop, the first NSK of them without odd rows.  sl: the groups' image slots of this lane, one byte each
+template <int NKS, int NG, int NSK>
+static __device__ __forceinline__ void sr_groups(const double* Eb, const double (&me)[NKS], const double (&mo)[NKS], int lane, unsigned sl, double (&ob)[16]) {
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    int g = ln >> 4;
+    const double* ep[NG];
+    f64x4r ce[NG], co[NG];
+    double x0[NG];
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+        ep[j] = Eb + g * SR_TI + ((sl >> (8 * j)) & 63);
+        ce[j] = f64x4r{0., 0., 0., 0.}; co[j] = f64x4r{0., 0., 0., 0.};
+    }
+    // environment fragments one k-step (4..8 MFMAs) ahead of their MFMAs; the group barriers pin the issue order the source states
+#pragma unroll
+    for (int j = 0; j < NG; ++j) x0[j] = ep[j][0];
+    __builtin_amdgcn_sched_group_barrier(0x100, NG, 0);
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+        double xa[NG];
+#pragma unroll
+        for (int j = 0; j < NG; ++j) xa[j] = x0[j];
+        if (ks + 1 < NKS) {
+#pragma unroll
+            for (int j = 0; j < NG; ++j) x0[j] = ep[j][4 * (ks + 1) * SR_TI];
+            __builtin_amdgcn_sched_group_barrier(0x100, NG, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < NG; ++j) {
+            ce[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(me[ks], xa[j], ce[j], 0, 0, 0);
+            if (j >= NSK) co[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(mo[ks], xa[j], co[j], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, 2 * NG - NSK, 0);
+    }
+    // lane (g, i) holds output links y = 16 ct + g + 4 e of the images in its slots
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+        const int im = (sl >> (8 * j)) & 63;
+        const double pI0 = Eb[(4 * NKS) * SR_TI + im];
+        if (j < NSK) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ob[4 * j + e] = pI0 * ce[j][e];                 // (phi[1] == 0: fma(0, co, x) = x)
+        } else {
+            const double pI1 = Eb[(4 * NKS + 1) * SR_TI + im];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ob[4 * j + e] = fma(pI1, co[j][e], pI0 * ce[j][e]);
+        }
+    }
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+template <int NKS, bool ZS>
 __global__ __launch_bounds__(512) void k_shift_res(ShiftResArgs A) {
     constexpr int ROWS = 4 * NKS + 2;                  // 4 NKS environment rows, phi[0], phi[1]
     constexpr int NP = 2 * NKS + 1;                    // DMA pieces of 2 rows per tile (the last one: the two feature rows)
@@ -379,6 +442,62 @@ __global__ __launch_bounds__(512) void k_shift_res(ShiftResArgs A) {
     if (niter > 0) stage(blockIdx.x, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     fr_barrier();
+    if constexpr (ZS) {
+        // the slots 16 grp + i of a tile, one byte per group (bits 0..5: the image; bits 6, 7 of the first two bytes: nz / 16, the same in every
+        // lane); with half-tile dealing the upper waves take groups 2, 3
+        auto slots = [&](int t, int ln) {
+            const uint8_t* o = A.ord + (size_t)(t % tpl) * SR_TI + (ln & 15);
+            return (unsigned)o[0] | (unsigned)o[16] << 8 | (unsigned)o[32] << 16 | (unsigned)o[48] << 24;
+        };
+        // the outputs of a tile go out at the top of the next round: lane (g, i) holds the links y = 16 ct + g + 4 e of the images in its slots
+        auto put = [&](int t, int ln, unsigned psl, const double (&ob)[16]) {
+            const int l = t / tpl, n0 = (t - l * tpl) * SR_TI, g = ln >> 4;
+            double* op = A.out + (size_t)l * A.out_lstride + (size_t)(16 * ct + g) * NTp + n0;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int y = 16 * ct + g + 4 * (q & 3);
+                if (y < A.mO && (q < 8 || !split)) op[(size_t)(4 * (q & 3)) * NTp + ((psl >> (8 * (q >> 2))) & 63)] = ob[q];
+            }
+        };
+        unsigned sl = 0, sln = 0, psl = 0;
+        if (niter > 0) sl = slots(blockIdx.x, lane);
+        double ob[16];                              // outputs of the previous tile (psl: its slots)
+        for (int it = 0; it < niter; ++it) {
+            const int t = blockIdx.x + it * G;
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            if (act && it > 0) put(t - G, ln, psl, ob);
+            if (it + 1 < niter) { stage(t + G, (it + 1) & 1); sln = slots(t + G, ln); }
+            const double* Eb = sr_lds + (it & 1) * ROWS * SR_TI;
+            if (act) {
+                const int s = __builtin_amdgcn_readfirstlane((int)(((sl >> 6) & 3) | ((sl >> 12) & 4)));      // groups 0 .. s - 1: zero features only
+                if (!split) {
+                    switch (s) {
+                        case 0:  sr_groups<NKS, 4, 0>(Eb, me, mo, lane, sl, ob); break;
+                        case 1:  sr_groups<NKS, 4, 1>(Eb, me, mo, lane, sl, ob); break;
+                        case 2:  sr_groups<NKS, 4, 2>(Eb, me, mo, lane, sl, ob); break;
+                        case 3:  sr_groups<NKS, 4, 3>(Eb, me, mo, lane, sl, ob); break;
+                        default: sr_groups<NKS, 4, 4>(Eb, me, mo, lane, sl, ob); break;
+                    }
+                    psl = sl;
+                } else {
+                    const int s2 = w < 4 ? (s < 2 ? s : 2) : (s > 2 ? s - 2 : 0);
+                    psl = w < 4 ? sl : sl >> 16;
+                    switch (s2) {
+                        case 0:  sr_groups<NKS, 2, 0>(Eb, me, mo, lane, psl, ob); break;
+                        case 1:  sr_groups<NKS, 2, 1>(Eb, me, mo, lane, psl, ob); break;
+                        default: sr_groups<NKS, 2, 2>(Eb, me, mo, lane, psl, ob); break;
+                    }
+                }
+            }
+            // the next tile's pieces and slots have landed (the stores still counted are a round old)
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(sln) :: "memory");
+            sl = sln;
+            fr_barrier();
+        }
+        if (act && niter > 0) put(blockIdx.x + (niter - 1) * G, lane, psl, ob);
+        return;
+    }
     double ob[8];                                   // second-half outputs of the previous tile
     double* obp = nullptr;
     for (int it = 0; it < niter; ++it) {
@@ -455,12 +574,14 @@ template <int NKS>
 static int shift_res_go(tnml_ctx* c, const ShiftResArgs& a, int grid) {
     const size_t lds = sizeof(double) * 2 * (4 * NKS + 2) * SR_TI;
     if (!c->attr_sr[NKS]) {                           // (function attributes are per device: remembered per context)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_shift_res<NKS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_shift_res<NKS, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(k_shift_res<NKS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return tnml_fail(c, "shift_res: cannot reserve %zu bytes of LDS", lds);
         c->attr_sr[NKS] = true;
     }
     ProfScope ps(c, KC_FGEMM_SHIFT);
-    hipLaunchKernelGGL(k_shift_res<NKS>, dim3(grid), dim3(512), lds, c->stream, a);
+    if (a.ord && a.nz) hipLaunchKernelGGL((k_shift_res<NKS, true>), dim3(grid), dim3(512), lds, c->stream, a);
+    else               hipLaunchKernelGGL((k_shift_res<NKS, false>), dim3(grid), dim3(512), lds, c->stream, a);
     return 0;
 }
 int launch_shift_res(tnml_ctx* c, const ShiftResArgs& a_in) {
@@ -484,6 +605,34 @@ int launch_shift_res(tnml_ctx* c, const ShiftResArgs& a_in) {
         case 28: TCK((shift_res_go<28>(c, a, grid))); break;
         default: TCK((shift_res_go<30>(c, a, grid))); break;
     }
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+
+// ---- tile order tables of k_shift_res (ZS) ----
+// One wave per (site, 64-image tile): ord = the stable partition of 0..63 with the images whose stored phi[1] equals 0.0 first (padding
+// images are classified by the value stored for them, like real ones), nz = how many those are; the site's counter takes nz / 16, the number
+// of 16-image groups that run without odd rows (integer atomics: the sum does not depend on the order).
+__global__ __launch_bounds__(256) void k_shift_order(const double* __restrict__ phi, int N, int NTp, uint8_t* __restrict__ ord, uint8_t* __restrict__ nz, int* __restrict__ cnt) {
+    const int lane = threadIdx.x & 63, tpl = NTp / SR_TI;
+    const size_t wave = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wave >= (size_t)N * tpl) return;                        // (uniform per wave)
+    const int j = (int)(wave / tpl), ti = (int)(wave - (size_t)j * tpl);
+    const bool z = phi[((size_t)j * 2 + 1) * NTp + (size_t)ti * SR_TI + lane] == 0.0;
+    const unsigned long long mz = __ballot(z), below = ((unsigned long long)1 << lane) - 1;
+    const int nzc = __popcll(mz);
+    const int slot = z ? __popcll(mz & below) : nzc + __popcll(~mz & below);
+    // (bits 6, 7 of the slots of the first two groups carry nz / 16 = 0..4, low two bits then the high one: k_shift_res fetches nothing else)
+    const int sk = nzc >> 4, code = slot < 16 ? (sk & 3) : (slot < 32 ? sk >> 2 : 0);
+    ord[((size_t)j * tpl + ti) * SR_TI + slot] = (uint8_t)(lane | code << 6);
+    if (lane == 0) { nz[(size_t)j * tpl + ti] = (uint8_t)nzc; if (nzc >= 16) atomicAdd(cnt + j, nzc >> 4); }
+}
+int launch_shift_order(tnml_ctx* c, const double* phi, int N, int NTp, uint8_t* ord, uint8_t* nz, int* cnt) {
+    if (NTp % SR_TI) return tnml_fail(c, "shift_order: image count not a multiple of %d", SR_TI);
+    ProfScope ps(c, KC_PACK);
+    HIPCK(c, hipMemsetAsync(cnt, 0, sizeof(int) * N, c->stream));
+    const size_t waves = (size_t)N * (NTp / SR_TI);
+    hipLaunchKernelGGL(k_shift_order, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, c->stream, phi, N, NTp, ord, nz, cnt);
     HIPCK(c, hipGetLastError());
     return 0;
 }

@@ -103,6 +103,7 @@ static const OptDef k_options[] = {
     {"fused_fwd",        "TNML_FUSED_FWD",      OPT_INT,  &tnml_ctx::fused_fwd,           nullptr,          0, INT_MAX, HK_NONE},   // > 2: always, with that many workgroups at most
     {"fwd_res",          "TNML_FWD_RES",        OPT_INT,  &tnml_ctx::fwd_res,             nullptr,          0, 3,       HK_NONE},   // 3: the general form on 120 x 120 bonds too
     {"shift_res",        "TNML_SHIFT_RES",      OPT_INT,  &tnml_ctx::shift_res,           nullptr,          0, 2,       HK_NONE},
+    {"shift_skip",       "TNML_SHIFT_SKIP",     OPT_BOOL, &tnml_ctx::shift_skip,          nullptr,          0, 1,       HK_NONE},
     {"res_grid",         nullptr,               OPT_INT,  &tnml_ctx::res_grid,            nullptr,          0, INT_MAX, HK_NONE},
     {"res_pace",         "TNML_RES_PACE",       OPT_INT,  &tnml_ctx::res_pace,            nullptr,          0, 4,       HK_NONE},
     {"grad_quad",        "TNML_GRAD_QUAD",      OPT_INT,  &tnml_ctx::grad_quad,           nullptr,          0, 2,       HK_NONE},
@@ -258,6 +259,9 @@ static std::vector<DevBuf> device_buffers(tnml_ctx* c) {
     add(c->Zp, c->small_elems * esz); add(c->Mf, c->mcap * sizeof(float)); add(c->slab, c->slab_bytes);
     add(c->partials, c->partial_cap * 12 * D); add(c->partials2, c->partial_cap * 12 * D); add(c->counters, 16 * sizeof(unsigned));
     add(c->Ppart, 2 * TNML_NL * NTp * D, c->cfg.dtype == TNML_F64 && c->cfg.mode == TNML_MODE_FIXEDL && m >= 33);   // k_fwd_res (input dimensions 33..120)
+    // tile order tables of k_shift_res (input dimensions 33..120, fp64-stored environments): one byte per site and image, one per site and 64-image tile
+    const bool zs = c->cfg.dtype == TNML_F64 && c->cfg.mode == TNML_MODE_FIXEDL && m >= 33;
+    add(c->zs_ord, c->N * NTp, zs); add(c->zs_nz, c->N * (NTp / 64), zs); add(c->zs_cnt, c->N * sizeof(int), zs);
     add(c->ebt, c->ebt_cap * sizeof(unsigned short), c->bf16() != 0); add(c->mbt, c->mbt_cap * sizeof(unsigned short), c->bf16() != 0);
     add(c->vB, c->mcap * D); add(c->vR, c->mcap * D); add(c->vP, c->mcap * D); add(c->arbuf, (c->mcap + TNML_TAILN) * D); add(c->locals, 32 * D);
     add(c->scal, (SC_N + 4 * TNML_MAX_PASS) * D);      // CG scalars, then the per-pass trace: one copy to the host
@@ -535,6 +539,23 @@ static int set_labels(tnml_ctx* c, const int32_t* labels) {
     HIPCK(c, hipMemcpy(c->label, lab.data(), sizeof(int) * c->NTp, hipMemcpyHostToDevice));
     return 0;
 }
+// the tile order tables of k_shift_res follow the stored features: rebuilt whenever the data are replaced (contexts that have them)
+static int shift_order_build(tnml_ctx* c) {
+    if (!c->zs_ord) return 0;
+    TCK(launch_shift_order(c, (const double*)c->phi, c->N, c->NTp, c->zs_ord, c->zs_nz, c->zs_cnt));
+    c->zs_groups.assign(c->N, 0);
+    HIPCK(c, hipMemcpyAsync(c->zs_groups.data(), c->zs_cnt, sizeof(int) * c->N, hipMemcpyDeviceToHost, c->stream));
+    SYNCK(c, c->stream);
+    return 0;
+}
+int tnml_shift_skip_stats(tnml_ctx* c, int site, int64_t* groups, int64_t* skipped) {
+    if (!c) return tnml_fail(c, "tnml_shift_skip_stats: null argument");
+    if (site < 1 || site > c->N) return tnml_fail(c, "tnml_shift_skip_stats: site %d out of range", site);
+    if (!c->zs_ord || !c->data_set || c->zs_groups.size() != (size_t)c->N) return tnml_fail(c, "tnml_shift_skip_stats: this context has no tile order tables (fp64 storage, fixedL, maxm >= 33, data set)");
+    if (groups) *groups = (int64_t)(c->NTp / 16);
+    if (skipped) *skipped = c->zs_groups[site - 1];
+    return 0;
+}
 int tnml_set_data_u8(tnml_ctx* c, const uint8_t* pixels, const int32_t* labels) {
     TCK(ho_locked(c, "tnml_set_data_u8", true));
     HIPCK(c, hipSetDevice(c->cfg.device));
@@ -547,6 +568,7 @@ int tnml_set_data_u8(tnml_ctx* c, const uint8_t* pixels, const int32_t* labels) 
     (void)hipStreamSynchronize(c->stream);
     (void)hipFree(d_pix);
     if (rc) return rc;
+    TCK(shift_order_build(c));
     c->data_set = true; c->currb = -1; c->p_valid = false; c->sweep_start = false;
     return 0;
 }
@@ -561,6 +583,7 @@ int tnml_set_data_phi(tnml_ctx* c, const double* phi, const int32_t* labels) {
         for (int i = 0; i < c->NT; ++i) for (int j = 0; j < c->N; ++j) for (int s = 0; s < 2; ++s)
             h[((size_t)j * 2 + s) * c->NTp + i] = phi[((size_t)i * c->N + j) * 2 + s];
         HIPCK(c, hipMemcpy(c->phi, h.data(), sizeof(double) * ne, hipMemcpyHostToDevice));
+        TCK(shift_order_build(c));
     } else {
         std::vector<float> h(ne, 0.f);
         for (int i = 0; i < c->NT; ++i) for (int j = 0; j < c->N; ++j) for (int s = 0; s < 2; ++s)
@@ -809,6 +832,7 @@ static int shift_core(tnml_ctx* c, int cs, bool from_left, const void* src, int 
             (c->shift_res >= 2 || c->NTp >= 7680) &&
             (size_t)TNML_NL * m_in * c->NTp * sizeof(double) < ((size_t)1 << 32)) {      // (32-bit lane offsets: beyond ~447 000 images per rank the generic kernel takes over)
             ShiftResArgs sa{(const double*)src, (size_t)m_in * c->NTp, (const double*)phi_site(c, cs), c->sM, (double*)dst, (size_t)m_out * c->NTp, m_out, c->NTp, Lout, m_in, d.Kp, d.Np};
+            if (c->shift_skip && c->zs_ord) { sa.ord = c->zs_ord + (size_t)(cs - 1) * c->NTp; sa.nz = c->zs_nz + (size_t)(cs - 1) * (c->NTp / 64); }
             return launch_shift_res(c, sa);
         }
         return launch_fgemm64(c, f);

@@ -224,6 +224,9 @@ struct tnml_ctx {
     int res_pace = 0;                // pacing of the GEMM waves of k_fwd_res (0: default, 1..4 the others; option "res_pace", env TNML_RES_PACE)
     int fwd_res = 1;                 // forward pass on k_fwd_res (kernels_res.hip): 1 = from 7 680 images per rank on, 0 never, 2 always, 3 the general form on 120 x 120 bonds too; option "fwd_res", env TNML_FWD_RES
     int shift_res = 1;               // Label-carrying environment shift on k_shift_res (kernels_res.hip): 1 = from 7 680 images per rank on, 0 never, 2 always; option "shift_res", env TNML_SHIFT_RES
+    int shift_skip = 1;              // k_shift_res walks a tile's images zero features first and leaves out the odd-row products of 16-image groups whose phi[1] is 0 throughout (tables zs_ord / zs_nz, built when the data are set); 0: natural order, every product; option "shift_skip", env TNML_SHIFT_SKIP
+    uint8_t* zs_ord = nullptr; uint8_t* zs_nz = nullptr; int* zs_cnt = nullptr;   // [N][NTp / 64][64], [N][NTp / 64], [N]: launch_shift_order (fp64-stored fixedL contexts with maxm >= 33)
+    std::vector<int> zs_groups;      // host copy of zs_cnt (tnml_shift_skip_stats)
     int res_grid = 0;                // test knob: workgroups of the resident-operand kernels (0: one per CU); option "res_grid"
     int grad_quad = 1;               // gradient GEMM on k_grad_quad (kernels_grad.hip; m = 120, fp64 storage, Label on an environment): 1 = from 4 096 images per rank on, 0 never, 2 always; option "grad_quad", env TNML_GRAD_QUAD
     bool attr_gq = false, attr_gp = false;
@@ -427,9 +430,14 @@ struct ShiftResArgs {
     int NTp, L;
     int mI, Kp, Np;                                   // input bond dimension (33..120) and the packed extents: Kp = ru16(2 mI), Np = ru16(mO) <= 128
     int ntiles = 0;                                   // set by the launcher: L * NTp / 64
+    const uint8_t* ord = nullptr;                     // tile order of the absorbed site [NTp / 64][64] (launch_shift_order; spare bits: nz / 16) and the zero
+    const uint8_t* nz = nullptr;                      // counts [NTp / 64] (the record; the kernel reads ord alone); null: natural image order, every product computed
 };
 bool shift_res_applies(int mI, int mO);
 int launch_shift_res(tnml_ctx* c, const ShiftResArgs& a);
+// tile order tables of every site from the stored features phi [N][2][NTp] (fp64): ord [N][NTp / 64][64], nz [N][NTp / 64], and per site the
+// number of 16-image groups whose images all have phi[1] == 0 -> cnt [N] (device)
+int launch_shift_order(tnml_ctx* c, const double* phi, int N, int NTp, uint8_t* ord, uint8_t* nz, int* cnt);
 
 // ---- kernels_small.hip --------------------------------------------------------------------
 struct PackDesc {       // M[l][2x+s][TO==2 ? 2y+t : y] <-> T[off + x*sx + s*ss + y*sy + t*st + l*sl]

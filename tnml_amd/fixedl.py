@@ -160,6 +160,13 @@ class TrainStates:
         self._ck(self._L.tnml_split_stats(self._h, C.byref(a), C.byref(b), C.byref(ms)))
         return dict(speculative_splits=a.value, roll_backs=b.value, roll_back_ms=ms.value)
 
+    def shift_skip_stats(self, j):
+        """site j (1..N): (16-image groups, groups of zero features only once each 64-image tile is walked zero features first) --
+        the share of odd-row products the resident-operand shift leaves out (tnml_shift_skip_stats)"""
+        a, b = C.c_int64(), C.c_int64()
+        self._ck(self._L.tnml_shift_skip_stats(self._h, int(j), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def device_bytes(self):
         return self._L.tnml_device_bytes(self._h)
 
