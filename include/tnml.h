@@ -187,6 +187,35 @@ int tnml_set_site(tnml_ctx* ctx, int j, int ml, int mr, int has_label, const dou
 int tnml_site_dims(tnml_ctx* ctx, int j, int* ml, int* mr, int* has_label);
 int tnml_get_site(tnml_ctx* ctx, int j, double* A);
 
+/* ---- MPS algebra on the device: the sum of weight MPS behind the W0..W9 start (fixedL.cc:682-701,729) ----------
+ * sum(ipsis,{"Cutoff",1E-10}) is a direct sum of the parts (block-diagonal links; the Label index, a physical index, is shared)
+ * followed by orthogonalize(args).  A context used only for this needs no image data (NT_local = 1, no tnml_set_data_* call).
+ *
+ * tnml_mps_place: one block of the direct sum.  The first placement on site j (since W was last set, split, compressed or used by tnml_env_init /
+ * tnml_mps_overlap, or with other outer dimensions) shapes the site as an ML x 2 x MR tensor (x 10 on the Label site c0) and zeroes it on the device; every
+ * placement then ADDS the ml x 2 x mr block A (ITensor layout, no Label index) at link offsets (row0, col0), into label slot `label` on
+ * site c0 (in.Aref(c) *= setElt(Lval(n)), fixedL.cc:693) and with label = -1 on every other site.  The block travels at its own size;
+ * the zero-padded site never crosses the bus.  Refused as tnml_set_site is (range, maxm, edge dimensions, held-out lock), and when the
+ * block leaves the site, when a label slot is named off c0 (or none on c0), or while a bond update is in flight. */
+int tnml_mps_place(tnml_ctx* ctx, int j, int ML, int MR, int row0, int col0, int ml, int mr, int label, const double* A);
+typedef struct {
+    int maxm_before, maxm_after;   /* largest bond dimension before / after */
+    int nbonds;                    /* N - 1: entries written to newm / truncerr */
+    double truncerr_sum;           /* sum over the bonds of the relative truncation errors of the second pass */
+    int64_t fallbacks;             /* eigensolver fallbacks to rocSOLVER taken inside this call (tnml_svd_stats counts them too) */
+    int* newm;                     /* in: caller's array of N - 1 ints or NULL; [b-1] = new dimension of bond b */
+    double* truncerr;              /* in: caller's array of N - 1 doubles or NULL; [b-1] = relative truncation error of bond b */
+} tnml_compress_report;
+/* orthogonalize(args) behind sum(psis,args): a right-to-left pass brings sites 2..N into right-orthonormal form without discarding weight
+ * (every bond drops to its rank bound min(rows, columns) at most), a left-to-right pass truncates each bond with
+ * tnml_truncate(p, n, maxm, 1, cutoff); the orthogonality centre ends on site N.  maxm <= 0: no Maxm (the context's maxm bounds it).
+ * Device resident: per bond the product A_b A_{b+1} and the split of tnml_svd_split; only eigenvalues and check values reach the host.
+ * One rank only: refused with a communicator, with a bond update in flight, or with a held-out context attached.  Afterwards
+ * environments, bond plan and cached outputs are invalid: call tnml_env_init before anything that uses them.  report may be NULL. */
+int tnml_mps_compress(tnml_ctx* ctx, double cutoff, int maxm, tnml_compress_report* report);
+/* overlap(W,W) (fixedL.cc:729) by the O(m^3) transfer chain E <- sum_{s,l} A_{s,l}^T E A_{s,l} on the context's stream */
+int tnml_mps_overlap(tnml_ctx* ctx, double* ovl);
+
 /* ---- TrainStates::init / setBond / shiftE  (fixedL.cc:122-157, :159-190, :192-233) ------- */
 int tnml_env_init(tnml_ctx* ctx);
 int tnml_set_bond(tnml_ctx* ctx, int b);               /* selects env buffers; t.v is never formed */

@@ -63,6 +63,7 @@ struct SiteT {
     double* a = nullptr;    // ITensor layout [ml][2][mr]([10]), capacity fixed at create
     int ml = 0, mr = 0, L = 1;
     bool set = false;
+    bool placed = false;    // shaped by tnml_mps_place and not rewritten since: further placements add to it
 };
 
 // scalar slots of the device-side CG state (doubles)
@@ -486,6 +487,12 @@ int launch_dgemm_small(tnml_ctx* c, const SmallGemmArgs& a);
 int launch_split_check_mirror(tnml_ctx* c, const double* src, double* host, double* bad);
 // C = op(A) op(B) at the sizes of the split: the in-house kernel up to 4e7 multiply-adds, rocBLAS (as `strips` column strips) beyond
 int split_gemm(tnml_ctx* c, bool ta, bool tb, int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C, int ldc, int strips, const SmallGemmArgs* chk = nullptr);   // chk: its chk_* fields ride along (or get a launch of their own)
+
+// ---- kernels_mps.hip: MPS algebra (tnml_mps_place, tnml_mps_overlap) ----
+// dst[ML][2][MR]([10]) += block src[ml][2][mr] at link offsets (row0, col0) of label slot `slot` (0 on a Label-free site)
+int launch_mps_place(tnml_ctx* c, const double* src, int ml, int mr, double* dst, int ML, int MR, int row0, int col0, int slot);
+// one step of the transfer chain: Eout[mr][mr] = sum_{k < 2 ml, l < L} A[k][r][l] T[k][r'][l] with T = E A (both [2 ml][mr][L], first index fastest)
+int launch_mps_transfer(tnml_ctx* c, const double* A, const double* T, int K, int mr, int L, double* Eout);
 
 // ---- eigh.hip -----------------------------------------------------------------------------
 int eigh_tridiagonalize(tnml_ctx* c, const double* A, int n, double* D, double* E, double* tau, double* V, double psd_tol = 0.);   // tau: n doubles, tau[n-1] = number of reflectors

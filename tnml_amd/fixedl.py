@@ -25,8 +25,9 @@ class TrainStates:
     """Training set + environments + W replica of one rank (TrainStates + MPS W of fixedL.cc)."""
 
     def __init__(self, labels, N, maxm, pixels=None, phi=None, device=0, rank=0, nranks=1, NT_total=None, dtype="f64",
-                 single_label=None, svd_backend=0):
-        """single_label = L selects the per-label variant (single.cc): plain weight MPS, target y_n = [l_n == L];
+                 single_label=None, svd_backend=0, no_data=False):
+        """no_data: a context for the MPS algebra alone (place / set_sum / compress / overlap): `labels` only sizes it (one entry will do);
+        single_label = L selects the per-label variant (single.cc): plain weight MPS, target y_n = [l_n == L];
         svd_backend = 1: the split on stock rocsolver_dsyevd (TNML_SVD_ROCSOLVER) instead of the in-house eigensolver"""
         self._L = _lib.load()
         self._h = C.c_void_p()
@@ -56,7 +57,7 @@ class TrainStates:
             ph = np.ascontiguousarray(phi, dtype=np.float64)
             assert ph.shape == (self.NT, self.N, 2)
             self._ck(self._L.tnml_set_data_phi(self._h, _lib.dptr(ph), labels.ctypes.data_as(C.POINTER(C.c_int32))))
-        else:
+        elif not no_data:
             raise ValueError("need pixels or phi")
 
     # -- plumbing
@@ -205,6 +206,47 @@ class TrainStates:
 
     def get_mps(self):
         return [self.get_site(j) for j in range(1, self.N + 1)]
+
+    # -- MPS algebra: the W0..W9 start (fixedL.cc:682-701,729)
+    def place(self, j, ML, MR, row0, col0, A, label=-1):
+        """tnml_mps_place: add the block A[ml,2,mr] at link offsets (row0, col0) of site j, shaped ML x 2 x MR (x 10 on site c0, where
+        `label` names the slot) and zeroed by its first placement"""
+        A = np.asarray(A, dtype=np.float64)
+        assert A.ndim == 3 and A.shape[1] == 2, A.shape
+        self._ck(self._L.tnml_mps_place(self._h, int(j), int(ML), int(MR), int(row0), int(col0), A.shape[0], A.shape[2], int(label), _lib.dptr(_lib.flat(A))))
+
+    def set_sum(self, parts, labels=None):
+        """the direct sum of `parts` (lists of Label-free site tensors A_j[l,2,r]) as this context's W, part k in label slot labels[k]
+        on site c0 (default k): in.Aref(c) *= setElt(Lval(n)) and the block structure of sum(ipsis), fixedL.cc:693-697, before its truncation"""
+        labels = list(range(len(parts))) if labels is None else list(labels)
+        assert len(labels) == len(parts) and all(len(p) == self.N for p in parts)
+        for j in range(1, self.N + 1):
+            ML = 1 if j == 1 else sum(p[j - 1].shape[0] for p in parts)
+            MR = 1 if j == self.N else sum(p[j - 1].shape[2] for p in parts)
+            r0 = c0 = 0
+            for p, lab in zip(parts, labels):
+                A = p[j - 1]
+                self.place(j, ML, MR, 0 if j == 1 else r0, 0 if j == self.N else c0, A, lab if j == self.c0 else -1)
+                r0 += A.shape[0]
+                c0 += A.shape[2]
+
+    def compress(self, cutoff, maxm=0):
+        """tnml_mps_compress (orthogonalize(args) behind sum(psis,args)); maxm = 0: no Maxm.  Call init() before using the environments again."""
+        nb = self.N - 1
+        newm = np.zeros(nb, dtype=np.int32)
+        te = np.zeros(nb)
+        rep = _lib.CompressReport()
+        rep.newm = newm.ctypes.data_as(C.POINTER(C.c_int))
+        rep.truncerr = _lib.dptr(te)
+        self._ck(self._L.tnml_mps_compress(self._h, float(cutoff), int(maxm or 0), C.byref(rep)))
+        return dict(maxm_before=rep.maxm_before, maxm_after=rep.maxm_after, truncerr_sum=rep.truncerr_sum, fallbacks=rep.fallbacks,
+                    newm=[int(x) for x in newm], truncerr=te)
+
+    def overlap(self):
+        """overlap(W,W) on the device (tnml_mps_overlap)"""
+        out = C.c_double()
+        self._ck(self._L.tnml_mps_overlap(self._h, C.byref(out)))
+        return out.value
 
     # -- TrainStates
     def init(self):

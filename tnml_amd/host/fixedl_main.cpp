@@ -11,7 +11,9 @@
 // imglen x imglen; present in the reference's sample input but never read by fixedL.cc), `feature_scale`
 // (multiplies the second feature component; 1 = the reference's double normalisation), `pipeline`, `bond_log`
 // (a CSV line per bond update: cost, #correct, bond dimensions, truncation error, seconds), `heldout` (the t10k images, capped at `Ntest`
-// per label, follow the training as a held-out context: one "Held-out:" line per bond update).
+// per label, follow the training as a held-out context: one "Held-out:" line per bond update), `mps_device` (auto | yes | no: the W0..W9 sum and
+// overlap(W,W) on the GPU -- tnml_mps_place / tnml_mps_compress / tnml_mps_overlap -- instead of the host's scalar SVD; auto = from a bond of
+// MPS_DEVICE_AUTO_BOND + 1 on), `sum_maxm` (a Maxm for that sum; the reference passes none).
 #include <array>
 #include <chrono>
 #include <condition_variable>
@@ -28,6 +30,28 @@
 #include "input_group.h"
 
 using namespace tnmlh;
+
+// mps_device = auto: the device path from this bond dimension (exclusive) on -- for the sum, the bond of the direct sum of the parts; for the
+// overlap line, W's largest bond.  Both committed driver tests of the host path sit at or below it (parts of bond 2 and 4), and the host path
+// is usable only there: its one-sided Jacobi SVD costs 0.16 s per bulk site at a sum bond of 120, its overlap is O(m^4) per site.
+static const int MPS_DEVICE_AUTO_BOND = 40;
+
+// a one-rank context without image data for the MPS algebra of the start (sum, overlap): sized by `m`, checked against the device's free memory
+static tnml_ctx* algebra_context(int device, int N, int m, const char* what) {
+    tnml_config cfg{};
+    cfg.device = device; cfg.rank = 0; cfg.nranks = 1; cfg.N = N; cfg.NT_local = 1; cfg.NT_total = 1; cfg.maxm = m; cfg.dtype = TNML_F64; cfg.svd_backend = TNML_SVD_SYEVD;
+    const int64_t need = tnml_estimate_bytes(&cfg);
+    int64_t freeb = 0, totb = 0;
+    if (tnml_device_memory(device, &freeb, &totb) != 0) die(nullptr, "tnml_device_memory");
+    if (need < 0 || need > freeb) {
+        std::printf("%s on the GPU: a context of %d sites at bond dimension %d needs %lld bytes, device %d has %lld free (mps_device = no keeps it on the host)\n",
+                    what, N, m, (long long)need, device, (long long)freeb);
+        std::exit(1);
+    }
+    tnml_ctx* ctx = nullptr;
+    if (tnml_create(&ctx, &cfg) != 0) die(nullptr, "tnml_create (MPS algebra)");
+    return ctx;
+}
 
 // the ranks of one process meet here (a generation-counting barrier)
 class HostBarrier {
@@ -79,6 +103,10 @@ int main(int argc, const char* argv[]) {
         const double feature_scale = input.getReal("feature_scale", 1.);                 // extension
         const bool heldout = input.getYesNo("heldout", false);                          // extension: evaluate the t10k images after every bond update
         const long Ntest = input.getInt("Ntest", 50000);                                 // extension: per-label cap of the held-out set (as fulltest)
+        const std::string mps_device = input.getString("mps_device", "auto");            // extension: auto | yes | no -- the W0..W9 sum and overlap(W,W) on the GPU
+        if (mps_device != "auto" && mps_device != "yes" && mps_device != "no") { std::printf("mps_device must be auto, yes or no\n"); return 1; }
+        const long sum_maxm = input.getInt("sum_maxm", 0);                               // extension: Maxm of the W0..W9 sum (0: none, as the reference)
+        auto on_device = [&](int bond) { return mps_device == "yes" || (mps_device == "auto" && bond > MPS_DEVICE_AUTO_BOND); };
         int dtype;
         if (!parse_dtype(precision, true, &dtype)) return 1;
         if (method != "conj") { std::printf("method type \"%s\" not recognized\n", method.c_str()); return 1; }   // :505
@@ -106,6 +134,7 @@ int main(int argc, const char* argv[]) {
         }
 
         HostMPS W;
+        double ovl_device = 0.; bool have_ovl = false;                                  // overlap(W,W) when the device has already computed it
         if (file_exists("W")) {                                                         // :671-681
             std::printf("Reading W from disk\n");
             W = read_mps("W");
@@ -119,11 +148,39 @@ int main(int argc, const char* argv[]) {
                 if (in.N != N) { std::printf("%s has %d sites, data has %d\n", fn, in.N, N); return 1; }
                 for (int j = 1; j <= N; ++j) if (in.A[j].L != 1) { std::printf("%s already carries a Label index\n", fn); return 1; }
                 in.c0 = c;
-                attach_label(in, n, 1.0);                                               // :693 in.Aref(c) *= setElt(Lval(n))
                 ipsis.push_back(std::move(in));
             }
             std::printf("Summing all %d label states together\n", (int)ipsis.size());  // :696
-            W = sum_truncated(ipsis, 1E-10, 1 << 30);                                   // :697 sum(ipsis,{"Cutoff",1E-10})
+            int sb = 1;                                                                 // largest bond of the direct sum: the sum of the parts' bonds
+            for (int j = 1; j < N; ++j) { int t = 0; for (const HostMPS& p : ipsis) t += p.A[j].mr; sb = std::max(sb, t); }
+            if (on_device(sb)) {
+                // the direct sum is placed block by block into a context sized for it (in.Aref(c) *= setElt(Lval(n)) is the label slot of the
+                // block on site c), compressed once on the device (:697 sum(ipsis,{"Cutoff",1E-10})) and downloaded; the context is gone
+                // before the training contexts are planned
+                tnml_ctx* actx = algebra_context(device, N, sb, "Summing W0..W9");
+                for (int j = 1; j <= N; ++j) {
+                    int ML = 0, MR = 0;
+                    for (const HostMPS& p : ipsis) { ML += p.A[j].ml; MR += p.A[j].mr; }
+                    if (j == 1) ML = 1;
+                    if (j == N) MR = 1;
+                    int r0 = 0, c0 = 0;
+                    for (int n = 0; n < 10; ++n) {
+                        const Site& a = ipsis[n].A[j];
+                        CK(actx, tnml_mps_place(actx, j, ML, MR, j == 1 ? 0 : r0, j == N ? 0 : c0, a.ml, a.mr, j == c ? n : -1, a.a.data()));
+                        r0 += a.ml; c0 += a.mr;
+                    }
+                }
+                tnml_compress_report cr{};
+                CK(actx, tnml_mps_compress(actx, 1E-10, (int)sum_maxm, &cr));
+                std::printf("Compressed on the GPU: largest bond %d -> %d, discarded weight %.2E\n", cr.maxm_before, cr.maxm_after, cr.truncerr_sum);
+                W = download_mps(actx, N);
+                CK(actx, tnml_mps_overlap(actx, &ovl_device));
+                have_ovl = true;
+                tnml_destroy(actx);
+            } else {
+                for (int n = 0; n < 10; ++n) attach_label(ipsis[n], n, 1.0);            // :693 in.Aref(c) *= setElt(Lval(n))
+                W = sum_truncated(ipsis, 1E-10, sum_maxm > 0 ? (int)sum_maxm : 1 << 30);   // :697 sum(ipsis,{"Cutoff",1E-10})
+            }
             std::printf("Done making initial W\n");
             write_mps("W", W);                                                          // :700
         } else {
@@ -131,9 +188,16 @@ int main(int argc, const char* argv[]) {
             std::printf("Done making initial W\n");
             write_mps("W", W);                                                          // :727
         }
-        std::printf("overlap(W,W) = %.12g\n", overlap(W, W));                           // :729
         for (int j = 1; j <= N; ++j) if ((W.A[j].L == NL) != (j == c)) { std::printf("Label Index not on site %d\n", c); return 1; }   // :734
         const int wm = max_link_dim(W);
+        if (!have_ovl && on_device(wm)) {                                               // the O(m^3) transfer chain on the GPU instead of the host's O(m^4) contraction
+            tnml_ctx* actx = algebra_context(device, N, wm, "overlap(W,W)");
+            upload_mps(actx, W);
+            CK(actx, tnml_mps_overlap(actx, &ovl_device));
+            have_ovl = true;
+            tnml_destroy(actx);
+        }
+        std::printf("overlap(W,W) = %.12g\n", have_ovl ? ovl_device : overlap(W, W));  // :729
 
         // ---- ranks: one host thread per GPU (the reference's `nthread` worker threads become GPUs: paralleldo.h:21-68) ----
         int nranks = (int)ngpu;

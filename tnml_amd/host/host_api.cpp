@@ -67,6 +67,47 @@ int tnmlh_build_initial_single(const char* datadir, long nt_per_label, int label
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
+// sum(ipsis,{"Cutoff",cutoff[,"Maxm",maxm]}) of K Label-free weight files (fixedL.cc:682-697): file k gets the Label index on site N/2 in slot k
+// (K <= 10), then one_shot = 0: sum_truncated (a compress after every addition, what the fixedL driver's host path does); one_shot = 1: the direct
+// sum of all K parts, then one compress.  maxm <= 0: no Maxm.  Result -> file `out`; *maxdim its largest bond (nullable)
+int tnmlh_mps_sum(const char* const* files, int K, double cutoff, int maxm, int one_shot, const char* out, int* maxdim) {
+    try {
+        if (K < 1 || K > NL) throw std::runtime_error("tnmlh_mps_sum: 1..10 parts");
+        const int mx = maxm <= 0 ? (1 << 30) : maxm;
+        std::vector<HostMPS> ipsis;
+        for (int k = 0; k < K; ++k) {
+            HostMPS in = read_mps(files[k]);
+            for (int j = 1; j <= in.N; ++j) if (in.A[j].L != 1) throw std::runtime_error(std::string(files[k]) + " already carries a Label index");
+            in.c0 = in.N / 2;
+            attach_label(in, k, 1.0);
+            ipsis.push_back(std::move(in));
+        }
+        HostMPS W;
+        if (!one_shot) W = sum_truncated(ipsis, cutoff, mx);
+        else { W = ipsis[0]; for (int k = 1; k < K; ++k) W = add(W, ipsis[k]); compress(W, cutoff, mx); }
+        write_mps(out, W);
+        if (maxdim) { int md = 1; for (int j = 1; j <= W.N; ++j) md = std::max(md, std::max(W.A[j].ml, W.A[j].mr)); *maxdim = md; }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// overlap(W,W) of a weight file by the host contraction the fixedL driver prints at its start (fixedL.cc:729); sites <= 0: the whole chain,
+// else the first `sites` sites only (the open right link traced) -- a timing handle for tools/time_mps_compress.py
+int tnmlh_mps_overlap(const char* file, int sites, double* ovl) {
+    try {
+        HostMPS W = read_mps(file);
+        if (sites > 0 && sites < W.N) {
+            HostMPS H(sites); H.c0 = W.c0;
+            for (int j = 1; j <= sites; ++j) H.A[j] = W.A[j];
+            // close the chain: fold the right link of the last kept site into its site index by keeping only link 0 (timing only)
+            Site& l = H.A[sites]; Site t(l.ml, 1, l.L);
+            for (int lab = 0; lab < l.L; ++lab) for (int sg = 0; sg < 2; ++sg) for (int a = 0; a < l.ml; ++a) t.at(a, sg, 0, lab) = l.at(a, sg, 0, lab);
+            l = t;
+            W = H;
+        }
+        *ovl = overlap(W, W);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
 // `sites` file (SiteSet(N,d), fixedL.cc:619-631)
 int tnmlh_sites_write(const char* file, int N, int d) { try { write_sites(file, N, d); return 0; } catch (const std::exception& e) { g_err = e.what(); return -1; } }
 int tnmlh_sites_read(const char* file, int* N, int* d) { try { read_sites(file, N, d); return 0; } catch (const std::exception& e) { g_err = e.what(); return -1; } }

@@ -35,6 +35,8 @@ def load():
         L.tnmlh_linear_mps.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_double, C.c_char_p, C.POINTER(C.c_double)]
         L.tnmlh_vec_read.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         L.tnmlh_vec_write.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_double)]
+        L.tnmlh_mps_sum.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int)]
+        L.tnmlh_mps_overlap.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_double)]
         _LIB = L
     return _LIB
 
@@ -96,6 +98,25 @@ def write_mps(path, W):
     if load().tnmlh_mps_write(path.encode(), len(W), dims.ctypes.data_as(C.POINTER(C.c_int)),
                               data.ctypes.data_as(C.POINTER(C.c_double))) != 0:
         raise _err()
+
+
+def mps_sum(files, out, cutoff=1e-10, maxm=0, one_shot=False):
+    """sum(ipsis,{"Cutoff",cutoff[,"Maxm",maxm]}) of the Label-free weight files (file k -> label slot k on site N/2) written to `out`:
+    one_shot = False adds part by part with a compress after every addition (the fixedL driver's host path), True adds all parts and
+    compresses once.  Returns the largest bond of the result."""
+    arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
+    md = C.c_int()
+    if load().tnmlh_mps_sum(arr, len(files), float(cutoff), int(maxm or 0), int(bool(one_shot)), out.encode(), md) != 0:
+        raise _err()
+    return md.value
+
+
+def mps_overlap(path, sites=0):
+    """overlap(W,W) of a weight file by the host contraction (fixedL.cc:729); sites > 0: the first `sites` sites only (a timing handle)"""
+    out = C.c_double()
+    if load().tnmlh_mps_overlap(path.encode(), int(sites), out) != 0:
+        raise _err()
+    return out.value
 
 
 def build_initial_w(datadir, nt_per_label, ninitial, seed, out, imglen=0, feature_scale=1.0):

@@ -31,6 +31,7 @@ EXPORTS = [
     "tnml_lin_create", "tnml_lin_destroy", "tnml_lin_last_error", "tnml_lin_set_data_u8", "tnml_lin_set_data_f64", "tnml_lin_set_labels",
     "tnml_lin_cg_start", "tnml_lin_cg_run", "tnml_lin_get_v", "tnml_lin_evaluate",
     "tnml_heldout_attach", "tnml_heldout_detach", "tnml_heldout_read",
+    "tnml_mps_place", "tnml_mps_compress", "tnml_mps_overlap",
 ]
 
 
@@ -62,6 +63,11 @@ class BondReport(C.Structure):
 class HeldoutReport(C.Structure):
     _fields_ = [("bond", C.c_int), ("half", C.c_int), ("count", C.c_int64), ("ncorrect", C.c_int64),
                 ("cost", C.c_double), ("label_cost", C.c_double * NL)]
+
+
+class CompressReport(C.Structure):
+    _fields_ = [("maxm_before", C.c_int), ("maxm_after", C.c_int), ("nbonds", C.c_int), ("truncerr_sum", C.c_double),
+                ("fallbacks", C.c_int64), ("newm", C.POINTER(C.c_int)), ("truncerr", C.POINTER(C.c_double))]
 
 
 _lib = None
@@ -147,6 +153,9 @@ def load():
     L.tnml_heldout_attach.argtypes = [vp, vp]
     L.tnml_heldout_detach.argtypes = [vp]
     L.tnml_heldout_read.argtypes = [vp, C.POINTER(HeldoutReport)]
+    L.tnml_mps_place.argtypes = [vp] + [C.c_int] * 8 + [dp]
+    L.tnml_mps_compress.argtypes = [vp, C.c_double, C.c_int, C.POINTER(CompressReport)]
+    L.tnml_mps_overlap.argtypes = [vp, dp]
     L.tnml_lin_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
     L.tnml_lin_destroy.argtypes = [vp]
     L.tnml_lin_last_error.restype = C.c_char_p
