@@ -367,6 +367,12 @@ int tnml_synchronize(tnml_ctx* ctx);
      "grad_pair"      (TNML_GRAD_PAIR) its pair form for bonds up to 64 x 64 (default 1; 0 = the quad form)
      "bgs_chol"       (TNML_BGS_CHOL) block Gram-Schmidt Cholesky QR of a kept basis of 129-384 columns (default 1; 0 = dpotrf + dtrsm)
      "spec_split"     (TNML_SPEC_SPLIT) the speculative split without its host synchronisation (default 1)
+     "spec_predict"   (TNML_SPEC_PREDICT) truncating splits (minm < the columns the split may keep) take the speculative form too, on a
+                      PREDICTED column count: the count the bond kept at its last two finished visits when both agree at the same matrix
+                      side (otherwise the synchronous split).  A kernel applies the truncation rule to the eigenvalues on the device and
+                      tnml_bond_update_end rolls a wrong guess back like a failed check, repeating with the synchronous split: every
+                      number is that of a run without the option.  tnml_set_site clears the history of the two bonds of its site;
+                      tnml_svd_split and tnml_mps_compress neither read nor write it (default 0; tnml_spec_predict_stats)
      "bf16_grad", "bf16_once"  the bf16 modes: gradient GEMM on the bf16 pipe / operands converted once (default 1 each)
    Tuning and test knobs (0: the default):
      "res_pace"       (TNML_RES_PACE) 0-4, pause pattern of the GEMM waves of k_fwd_res
@@ -374,6 +380,9 @@ int tnml_synchronize(tnml_ctx* ctx);
      "bgemm_wgs", "bgemm_per"  (TNML_BGEMM_WGS, TNML_BGEMM_PER) workgroups the gradient GEMM aims at / images per slab in units of 32
      "mc_spin_max"    polls before the workgroup cluster of the tridiagonalisation gives up (-1 default; 0 forces the fallback)
      "debug_fail_split"  k >= 0: the k-th speculative split reports a failed check (-1 off)
+     "debug_mispredict"  k >= 0: the guess of the k-th predicted split of the context is moved by one column (down while that leaves one,
+                      up otherwise) before anything is enqueued -- a host-side change, no kernel carries a switch (-1 off).  EVERY rank of
+                      a communicator must set the same value: ranks that keep different column counts enter collectives of different sizes
      "debug_nudge_rank"  this rank's copy of a split site tensor is moved by one ulp (-1 off)
      "svd_print"      (TNML_SVD_PRINT) k >= 0: print the spectrum of the k-th split; -1: the check values of every split (-2 off)
    Memory and transport:
@@ -391,6 +400,16 @@ int tnml_set_option_real(tnml_ctx* ctx, const char* name, double value);
    that bond update with the synchronous split, and the one begun after it), and the device time of the repeated work in ms (event-timed;
    call after tnml_synchronize for the full sum).  fixedL.cc:519-521 has no counterpart: ITensor's svd is synchronous. */
 int tnml_split_stats(tnml_ctx* ctx, int64_t* spec_splits, int64_t* roll_backs, double* roll_back_ms);
+/* Predicted splits (option "spec_predict"): how many splits ran the speculative form on a predicted column count, how many of them
+   tnml_bond_update_end rolled back because the truncation rule kept another count, and the device time in ms of the work repeated for
+   those (event-timed; call after tnml_synchronize for the full sum).  Predicted splits also count in tnml_split_stats' spec_splits,
+   mispredictions in its roll_backs and roll_back_ms -- but never in tnml_svd_stats' fallbacks: the eigensolver did not fail. */
+int tnml_spec_predict_stats(tnml_ctx* ctx, int64_t* predicted, int64_t* mispredicted, double* redo_ms);
+/* TEST ENTRY: the device-side truncation rule of the predicted split (k_truncate_verdict) on a spectrum given by the host.
+   evals_ascending[n] are eigenvalues as the eigensolver leaves them (ascending; values that are not > 0, NaN included, count as 0).
+   *m = the count tnml_truncate keeps for (maxm, minm, cutoff) on the same values read largest first, *wrong = (*m != m_pred).
+   Synchronises the stream; not for use while a bond update is in flight. */
+int tnml_truncate_device(tnml_ctx* ctx, const double* evals_ascending, int n, int maxm, int minm, double cutoff, int m_pred, int* m, int* wrong);
 /* The tile order tables of the resident-operand shift (option "shift_skip"; fp64 storage, TNML_MODE_FIXEDL, maxm >= 33), built when the data
    are set: for site 1..N the number of 16-image groups (padded image count / 16) and how many of them hold only images with phi[1] == 0
    once each 64-image tile is walked zero features first -- the groups whose odd-row products are left out. */

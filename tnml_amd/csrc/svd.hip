@@ -98,6 +98,39 @@ __global__ void k_mc_flag(const unsigned long long* __restrict__ status, double*
     if (threadIdx.x == 0) out[0] = status[0] != 0ull ? 1. : 0.;
 }
 
+// The truncation rule on the device (option spec_predict): tnml_truncate (tnml_abi.hip) on the ascending eigenvalues, read largest first with
+// !(lam > 0) -> 0 as the host prepares its copy -- the same operations in the same order (the discarded weight grows from the small end, the
+// scale is summed in index order, no fused multiply-add), so the kept count is the host's bit for bit.  At most 240 values: one lane of
+// one wave does it.  out[0] = kept count, out[1] = [count != m_pred] (the verdict on a predicted split; pinned host memory inside a bond
+// update), bad[0] = the verdict once more for the carried slot that is summed over the ranks.
+__global__ void k_truncate_verdict(const double* __restrict__ ev, int origm, int maxm, int minm, double cutoff, int m_pred,
+                                   double* __restrict__ out, double* __restrict__ bad) {
+#pragma clang fp contract(off)
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    auto P = [&](int j) { const double lam = ev[origm - 1 - j]; return lam > 0. ? lam : 0.; };
+    int m = origm;
+    if (origm > 1) {
+        int n = origm - 1;
+        double te = 0.;
+        while (n >= maxm) { te += P(n); --n; }
+        double scale = 0.;
+        for (int j = 0; j < origm; ++j) scale += P(j);
+        if (scale == 0.) scale = 1.;
+        while (n >= 0 && te + P(n) < cutoff * scale && n >= minm) { te += P(n); --n; }
+        if (n < 0) n = 0;
+        m = n + 1;
+    }
+    const double wrong = m != m_pred ? 1. : 0.;
+    out[0] = (double)m; out[1] = wrong;
+    if (bad) bad[0] = wrong;
+}
+int launch_truncate_verdict(tnml_ctx* c, const double* ev, int n, int maxm, int minm, double cutoff, int m_pred, double* host_m, double* bad) {
+    if (n < 1 || !ev || !host_m) return tnml_fail(c, "truncate_verdict: bad argument");
+    hipLaunchKernelGGL(k_truncate_verdict, dim3(1), dim3(64), 0, c->stream, ev, n, maxm, minm, cutoff, m_pred, host_m, bad);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+
 // C = op(A) op(B) at the sizes of the split: k_dgemm_small (kernels_sgemm.hip) up to 4e7 multiply-adds, rocBLAS as
 // `strips` column strips beyond (the Label-on-B bonds reduce over 2400: 133 us as one call, 17 us as 8 strips)
 int split_gemm(tnml_ctx* c, bool ta, bool tb, int M, int N, int K, const double* A, int lda, const double* B, int ldb, double* C, int ldc, int strips, const SmallGemmArgs* chk) {
@@ -232,7 +265,20 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
     // decision can wait for tnml_bond_update_end.  No eigenvalue broadcast, no copy, no stream synchronisation: eigenvalues and check
     // values reach the host through pinned mirrors written by the kernels themselves, the two site tensors go to spare buffers, and a
     // failed check rolls the bond update back (tnml_abi.hip).  One-workgroup sizes only (the cluster's give-up flag is a collective decision).
-    bool spec = spec_slot >= 0 && c->spec_split && !c->force_safe && own_eig && !mc && minm >= mk && !sv_host && c->hrep != nullptr;
+    const bool spec_form = spec_slot >= 0 && c->spec_split && !c->force_safe && own_eig && !mc && !sv_host && c->hrep != nullptr;
+    bool spec = spec_form && minm >= mk;
+    // Predicted form (option spec_predict): a truncating split whose bond kept the same count at the same matrix side on its last two finished
+    // visits runs the speculative form on that count; k_truncate_verdict judges the guess in stream order and tnml_bond_update_end rolls a
+    // wrong one back.  All mk candidate columns are back-transformed and polished as ever, the first m_pred are kept.
+    int m_pred = 0;
+    if (spec_form && !spec && c->spec_predict && b >= 1 && b < (int)c->bond_hist.size()) {
+        const tnml_ctx::BondHist& hs = c->bond_hist[b];
+        if (hs.n[0] == n && hs.n[1] == n && hs.m[0] == hs.m[1] && hs.m[0] >= 1) {
+            m_pred = std::min(std::max(hs.m[0], std::min(minm, mk)), mk);
+            spec = true;
+        }
+    }
+    const bool pred = m_pred > 0;
     double* hmir = spec ? c->hrep + (size_t)spec_slot * c->hrep_stride : nullptr;     // [n eigenvalues | 4 check values]
     if (spec_slot >= 0) {
         // inside a bond update in flight the two new site tensors ALWAYS go to spare buffers (whichever form the split takes): a later
@@ -250,8 +296,14 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
                 S.a = pool.back(); pool.pop_back();
             }
         } else spec = false;
-        if (spec) { pr.spec = true; pr.split_n = n; pr.split_mk = mk; c->spec_splits += 1; c->spec_splits_total += 1; }
+        pr.split_n = n; pr.pred = false;
+        if (spec) { pr.spec = true; pr.split_mk = mk; c->spec_splits += 1; c->spec_splits_total += 1; }
         else hmir = nullptr;
+        if (spec && pred) {
+            // test hook (option debug_mispredict): the guess of the k-th predicted split moves by one -- down while that leaves a column, up otherwise
+            if (c->debug_mispredict >= 0 && c->pred_splits == c->debug_mispredict) { if (m_pred > 1) m_pred -= 1; else if (m_pred < mk) m_pred += 1; }
+            pr.pred = true; pr.m_pred = m_pred; c->pred_splits += 1; c->pred_splits_total += 1;
+        }
     }
     if (tri) {
         // sG is a Gram matrix: rank-adaptive exit once the trailing block weighs less than the error G = B^T B carries anyway -- ~4 eps of
@@ -262,6 +314,8 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
         TCK(eigh_tridiagonalize(c, c->sG, n, c->sD, c->sE2, c->sTau, c->sV, c->sytrd_exit ? exit_tol : 0.));
         if (own_eig) { TCK(eigh_tridiag_eig(c, c->sD, c->sE2, n, c->sW, mk, c->sC, n, c->sScr, hmir)); evals = c->sW; }
         else RBCK(c, rocsolver_dstedc(c->blas, rocblas_evect_tridiagonal, n, c->sD, c->sE2, c->sC, n, c->sInfo));
+        // the verdict on a predicted count (own_eig holds): the true count behind the four check values and their flag, the carried word beside the check's
+        if (spec && pred) { TCK(launch_truncate_verdict(c, evals, n, maxm, minm, cutoff, m_pred, hmir + n + 5, c->tail + TNML_PREDSLOT)); }
     } else {
         RBCK(c, rocsolver_dsyevd(c->blas, rocblas_evect_original, rocblas_fill_upper, n, c->sG, n, c->sD, c->sE, c->sInfo));
     }
@@ -336,7 +390,8 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
     SmallGemmArgs chk{};                                   // the check-value side job of the speculative form (rides in the factor product below)
     const SmallGemmArgs* chkp = nullptr;
     if (spec) {
-        // m = mk; the eigenvalues are on their way to hmir[0..n) (k_teig_vectors), the check values follow with the factor product
+        if (pred) m = m_pred;
+        // m = mk (or the predicted count); the eigenvalues are on their way to hmir[0..n) (k_teig_vectors), the check values follow with the factor product
         chk.chk_src = dv; chk.chk_host = hmir + n; chk.chk_bad = c->tail + TNML_SPECSLOT;
         // test hook (option debug_fail_split): the k-th speculative split reports a failed check -- by spoiling the check VALUE in stream
         // order before the product that mirrors it, so that no product kernel carries a test switch

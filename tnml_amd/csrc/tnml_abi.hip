@@ -87,7 +87,7 @@ int tnml_profile_reset(tnml_ctx* c) {
 // One row per option of tnml_set_option / tnml_set_option_real: its name, the environment variable that supplies its default at
 // tnml_create (or none), the field it sets, its kind and the values it accepts.  A bool option takes any value (nonzero: on).
 enum OptKind { OPT_BOOL, OPT_INT, OPT_REAL };
-enum OptHook { HK_NONE, HK_REUSE_P, HK_DEFER_TAIL, HK_CHECK_REPLICAS, HK_ENV_BUDGET, HK_COMM_TIMEOUT, HK_FAIL_SPLIT, HK_SVD_PRINT, HK_CG_METHOD, HK_NOISE };
+enum OptHook { HK_NONE, HK_REUSE_P, HK_DEFER_TAIL, HK_CHECK_REPLICAS, HK_ENV_BUDGET, HK_COMM_TIMEOUT, HK_FAIL_SPLIT, HK_MISPREDICT, HK_SVD_PRINT, HK_CG_METHOD, HK_NOISE };
 struct OptDef {
     const char* name; const char* env; OptKind kind;
     int tnml_ctx::* ifield; double tnml_ctx::* rfield;    // the field set (none for env_budget_mb: its hook stores bytes)
@@ -114,6 +114,8 @@ static const OptDef k_options[] = {
     {"bgs_chol",         "TNML_BGS_CHOL",       OPT_BOOL, &tnml_ctx::bgs_chol,            nullptr,          0, 1,       HK_NONE},
     {"spec_split",       "TNML_SPEC_SPLIT",     OPT_BOOL, &tnml_ctx::spec_split,          nullptr,          0, 1,       HK_NONE},
     {"debug_fail_split", nullptr,               OPT_INT,  &tnml_ctx::debug_fail_split,    nullptr,         -1, INT_MAX, HK_FAIL_SPLIT},
+    {"spec_predict",     "TNML_SPEC_PREDICT",   OPT_BOOL, &tnml_ctx::spec_predict,        nullptr,          0, 1,       HK_NONE},
+    {"debug_mispredict", nullptr,               OPT_INT,  &tnml_ctx::debug_mispredict,    nullptr,         -1, INT_MAX, HK_MISPREDICT},
     {"bf16_grad",        nullptr,               OPT_BOOL, &tnml_ctx::bf16_grad,           nullptr,          0, 1,       HK_NONE},
     {"bf16_once",        nullptr,               OPT_BOOL, &tnml_ctx::bf16_once,           nullptr,          0, 1,       HK_NONE},
     {"env_async",        nullptr,               OPT_BOOL, &tnml_ctx::env_async,           nullptr,          0, 1,       HK_NONE},
@@ -143,6 +145,7 @@ static int apply_option(tnml_ctx* c, const OptDef& d, double v, const char* who,
         case HK_ENV_BUDGET: c->env_budget_bytes = (long)v << 20; break;
         case HK_COMM_TIMEOUT: local_comm_set_timeout(c, (int)v); break;
         case HK_FAIL_SPLIT: c->spec_splits = 0; break;
+        case HK_MISPREDICT: c->pred_splits = 0; break;
         case HK_SVD_PRINT: c->svd_calls = 0; break;
         case HK_CG_METHOD:
             if (v >= 1 && !c->single()) return tnml_fail(c, "cg_method: 0 (conj) or, in TNML_MODE_SINGLE, 1 (fast_conj) / 2 (exact)");
@@ -167,19 +170,50 @@ int tnml_set_option_real(tnml_ctx* c, const char* name, double value) { return s
 int tnml_synchronize(tnml_ctx* c) { HIPCK(c, hipStreamSynchronize(c->stream)); if (c->copy_stream) HIPCK(c, hipStreamSynchronize(c->copy_stream)); return ipc_comm_check(c); }
 int64_t tnml_device_bytes(tnml_ctx* c) { return c->bytes; }
 int64_t tnml_replica_repairs(tnml_ctx* c) { return c->replica_repairs; }
-int tnml_split_stats(tnml_ctx* c, int64_t* spec_splits, int64_t* roll_backs, double* roll_back_ms) {
-    // resolves the event pairs of the roll-backs that have finished (call after tnml_synchronize for the full sum)
-    for (size_t k = 0; k < c->redo_events.size();) {
+// resolves the event pairs of the roll-backs that have finished (call after tnml_synchronize for the full sum)
+static void resolve_redo_events(std::vector<std::pair<hipEvent_t, hipEvent_t>>& ev, double* sum_ms) {
+    for (size_t k = 0; k < ev.size();) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c->redo_events[k].first, c->redo_events[k].second) == hipSuccess) {
-            c->redo_ms += ms;
-            (void)hipEventDestroy(c->redo_events[k].first); (void)hipEventDestroy(c->redo_events[k].second);
-            c->redo_events.erase(c->redo_events.begin() + k);
+        if (hipEventElapsedTime(&ms, ev[k].first, ev[k].second) == hipSuccess) {
+            *sum_ms += ms;
+            (void)hipEventDestroy(ev[k].first); (void)hipEventDestroy(ev[k].second);
+            ev.erase(ev.begin() + k);
         } else { (void)hipGetLastError(); ++k; }
     }
+}
+int tnml_spec_predict_stats(tnml_ctx* c, int64_t* predicted, int64_t* mispredicted, double* redo_ms) {
+    if (!c) return tnml_fail(c, "tnml_spec_predict_stats: null argument");
+    resolve_redo_events(c->pred_redo_events, &c->pred_redo_ms);
+    if (predicted) *predicted = c->pred_splits_total;
+    if (mispredicted) *mispredicted = c->mispredicted;
+    if (redo_ms) *redo_ms = c->pred_redo_ms;
+    return 0;
+}
+int tnml_truncate_device(tnml_ctx* c, const double* evals_ascending, int n, int maxm, int minm, double cutoff, int m_pred, int* m, int* wrong) {
+    if (!c || !evals_ascending || !m || !wrong) return tnml_fail(c, "tnml_truncate_device: null argument");
+    if (n < 1 || n > (1 << 20)) return tnml_fail(c, "tnml_truncate_device: n = %d, must be in 1..%d", n, 1 << 20);
+    if (c->pend_count > 0) return tnml_fail(c, "tnml_truncate_device: a bond update is in flight (tnml_bond_update_end first)");
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    double* d = nullptr;                                                // a test entry: its own buffer, [n eigenvalues | count | verdict | carried word]
+    HIPCK(c, hipMalloc((void**)&d, sizeof(double) * ((size_t)n + 3)));
+    double out[3] = {-1., -1., -1.};
+    int rc = 0;
+    if (hipMemcpyAsync(d, evals_ascending, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_truncate_device: copy to the device failed");
+    if (!rc) rc = launch_truncate_verdict(c, d, n, maxm, minm, cutoff, m_pred, d + n, d + n + 2);
+    if (!rc && hipMemcpyAsync(out, d + n, sizeof out, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_truncate_device: copy from the device failed");
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_truncate_device: the kernel failed");
+    (void)hipFree(d);
+    if (rc) return rc;
+    if (out[1] != out[2]) return tnml_fail(c, "tnml_truncate_device: the mirrored verdict %g differs from the carried word %g", out[1], out[2]);
+    *m = (int)out[0]; *wrong = out[1] != 0. ? 1 : 0;
+    return 0;
+}
+int tnml_split_stats(tnml_ctx* c, int64_t* spec_splits, int64_t* roll_backs, double* roll_back_ms) {
+    resolve_redo_events(c->redo_events, &c->redo_ms);
+    resolve_redo_events(c->pred_redo_events, &c->pred_redo_ms);       // mispredictions are roll-backs too (tnml_spec_predict_stats reports them apart)
     if (spec_splits) *spec_splits = c->spec_splits_total;
     if (roll_backs) *roll_backs = c->spec_redos;
-    if (roll_back_ms) *roll_back_ms = c->redo_ms;
+    if (roll_back_ms) *roll_back_ms = c->redo_ms + c->pred_redo_ms;
     return 0;
 }
 int tnml_svd_stats(tnml_ctx* c, int64_t* fallbacks, int64_t* cluster_repairs, double* d0, double* d1) {
@@ -243,6 +277,7 @@ static void ctx_plan(tnml_ctx* c, const tnml_config& cfg) {
     c->mbt_cap = c->bf16() ? bf16e_m_elems(c->maxm, c->bf16() == 2) : 0;
     c->W.resize(c->N + 2);
     c->env.resize(c->N + 2);
+    c->bond_hist.assign(c->N + 1, tnml_ctx::BondHist());
     // speculative split: spare site tensors (two bond updates in flight replace two sites each; the Label site has its own size class)
     c->spare_small.assign(4, nullptr);
     c->spare_big.assign(c->c0 > 0 ? 2 : 0, nullptr);
@@ -403,6 +438,7 @@ int tnml_destroy(tnml_ctx* c) {
     for (auto& p : c->prof_pending) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     for (auto e : c->prof_free) (void)hipEventDestroy(e);
     for (auto& p : c->redo_events) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+    for (auto& p : c->pred_redo_events) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (const DevBuf& d : device_buffers(c)) if (!d.site && *d.slot) (void)hipFree(*d.slot);
     // (site tensors and spares have changed places during speculative splits: every buffer is in exactly one of the two sets,
     // or held by the undo record of a bond update in flight)
@@ -411,6 +447,7 @@ int tnml_destroy(tnml_ctx* c) {
     for (size_t k = 0; k < c->spare_big.size(); ++k) if (c->spare_big[k]) (void)hipFree(c->spare_big[k]);
     for (int k = 0; k < 2; ++k) for (int u = 0; u < c->pend[k].nundo; ++u) if (c->pend[k].undo[u].old) (void)hipFree(c->pend[k].undo[u].old);
     if (c->noise_ws) (void)hipFree(c->noise_ws);          // allocated on first use
+    if (c->psave) (void)hipFree(c->psave);                // (option spec_predict)
     for (auto& sl : c->slabs) if (sl.base) (void)hipFree(sl.base);
     if (c->hrep) (void)hipHostFree(c->hrep);
     if (c->hcost) (void)hipHostFree(c->hcost);
@@ -606,6 +643,7 @@ int tnml_set_site(tnml_ctx* c, int j, int ml, int mr, int has_label, const doubl
     s.ml = ml; s.mr = mr; s.L = has_label ? TNML_NL : 1; s.set = true; s.placed = false;
     HIPCK(c, hipMemcpy(s.a, A, sizeof(double) * (size_t)ml * 2 * mr * s.L, hipMemcpyHostToDevice));
     c->currb = -1; c->p_valid = false; c->sweep_start = false;
+    for (int b = j - 1; b <= j; ++b) if (b >= 1 && b < (int)c->bond_hist.size()) c->bond_hist[b] = tnml_ctx::BondHist();   // the bonds of this site start over (option spec_predict)
     return 0;
 }
 int tnml_site_dims(tnml_ctx* c, int j, int* ml, int* mr, int* has_label) {
@@ -1653,7 +1691,7 @@ int tnml_bond_update_begin(tnml_ctx* c, int b, int ha, const tnml_sweep_params* 
     PendingReport& pr = c->pend[slot];
     tnml_bond_report* rep = &pr.rep;
     memset(rep, 0, sizeof *rep);
-    pr.b = b; pr.ha = ha; pr.sp = *sp; pr.spec = false; pr.nundo = 0; pr.ho = false;
+    pr.b = b; pr.ha = ha; pr.sp = *sp; pr.spec = false; pr.pred = false; pr.split_n = 0; pr.nundo = 0; pr.ho = false;
     c->sweep_start = false;
     // what the report needs reaches its pinned block through the kernels that compute it (round 5: four copy kernels per bond update less):
     // the CG scalars and trace (k_cg_step2 / k_cg_resid2 of the fp64 literal or merged CG), the norms of the new bond tensor (partial pairs,
@@ -1675,6 +1713,17 @@ int tnml_bond_update_begin(tnml_ctx* c, int b, int ha, const tnml_sweep_params* 
     const PackDesc pd = bond_pack_desc(p);
     TCK(launch_bond_form(c, c->W[b], c->W[b + 1], c->tB));            // :494
     bool outputs_current = c->reuse_p && c->p_valid;                  // left by the previous bond update's quadcost
+    // option spec_predict: a misprediction must repeat this bond update bit for bit as a run without the option computes it -- and that run
+    // reuses P / dP here instead of a forward pass of its own (another summation order).  Keep them: two device-to-device copies per bond update.
+    pr.p_saved = false;
+    if (c->spec_predict && outputs_current && !c->force_safe) {
+        const size_t pb = (size_t)TNML_NL * c->NTp * c->esz();
+        if (!c->psave) TCK(ctx_alloc_doubles(c, &c->psave, (size_t)4 * TNML_NL * c->NTp));
+        char* sv = (char*)c->psave + (size_t)slot * 2 * TNML_NL * c->NTp * sizeof(double);
+        HIPCK(c, hipMemcpyAsync(sv, c->P, pb, hipMemcpyDeviceToDevice, c->stream));
+        HIPCK(c, hipMemcpyAsync(sv + pb, c->dP, pb, hipMemcpyDeviceToDevice, c->stream));
+        pr.p_saved = true;
+    }
     c->p_valid = false;
     // with carried outputs no label dot rewrites the [cost | ncorrect | pAp] head of the tail before the first all-reduce: the
     // pack kernel clears it on the way
@@ -1784,7 +1833,24 @@ int tnml_bond_update_end(tnml_ctx* c, tnml_bond_report* rep) {
         // the deferred check of the speculative split: its verdict came with the carried slots (summed over the ranks: every rank sees the same number)
         const double* hm = c->hrep + (size_t)slot * c->hrep_stride;
         const int n = pr.split_n;
-        if ((c->multi() ? hq[TNML_SPECSLOT] : hm[n + 4]) != 0.) {    // (one rank: straight from the mirror of the check values)
+        const bool check_failed = (c->multi() ? hq[TNML_SPECSLOT] : hm[n + 4]) != 0.;   // (one rank: straight from the mirror of the check values)
+        // a predicted split (option spec_predict): k_truncate_verdict has left the count the truncation rule keeps behind the check values and its
+        // verdict in a carried word of its own.  The host applies the rule to the mirrored eigenvalues as it does for every speculative split;
+        // its count must be the kernel's.  A wrong guess takes the roll-back below -- the repeat is the synchronous split, so nothing differs
+        // from a run without the option -- but is no fallback of the eigensolver.
+        bool wrong_count = false;
+        if (pr.pred) {
+            std::vector<double> p(n);
+            for (int g = 0; g < n; ++g) { double lam = hm[n - 1 - g]; if (!(lam > 0.)) lam = 0.; p[g] = lam; }
+            const int mx = pr.sp.maxm < c->maxm ? pr.sp.maxm : c->maxm;
+            const int m_host = tnml_truncate(p.data(), n, mx, pr.sp.minm < mx ? pr.sp.minm : mx, pr.sp.cutoff, nullptr);
+            if ((double)m_host != hm[n + 5])
+                return tnml_fail(c, "bond %d: the truncation rule keeps %d columns on the host and %g on the device", pr.rep.bond, m_host, hm[n + 5]);
+            wrong_count = (c->multi() ? hq[TNML_PREDSLOT] : hm[n + 6]) != 0.;           // (summed over the ranks: every rank rolls back together)
+            if (!wrong_count && m_host != pr.m_pred) return tnml_fail(c, "bond %d: the verdict passed a predicted split of %d columns, the truncation rule says %d", pr.rep.bond, pr.m_pred, m_host);
+        }
+        const bool mispredicted = wrong_count && !check_failed;
+        if (check_failed || wrong_count) {
             // dependent vectors even after re-orthonormalisation (or the test hook): everything this bond update and the one begun after
             // it wrote is dropped -- site tensors back from their spare buffers -- and both run again, this one with the synchronous split
             // and its rocSOLVER fallback.  Rare (a few per sweep), so the repeat may cost what it costs.
@@ -1798,7 +1864,15 @@ int tnml_bond_update_end(tnml_ctx* c, tnml_bond_report* rep) {
             spec_rollback(c, pr);
             c->pend_count = 0; c->carry_slot = -1; c->p_valid = false; c->currb = -1;
             HIPCK(c, hipMemsetAsync(c->tail + TNML_CARRY, 0, sizeof(double) * TNML_CARRYN, c->stream));
-            c->spec_redos += 1; c->svd_fallbacks += 1;
+            if (pr.p_saved && c->psave) {                             // (option spec_predict) the outputs the first run of this bond update reused
+                const size_t pb = (size_t)TNML_NL * c->NTp * c->esz();
+                const char* sv = (const char*)c->psave + (size_t)slot * 2 * TNML_NL * c->NTp * sizeof(double);
+                HIPCK(c, hipMemcpyAsync(c->P, sv, pb, hipMemcpyDeviceToDevice, c->stream));
+                HIPCK(c, hipMemcpyAsync(c->dP, sv + pb, pb, hipMemcpyDeviceToDevice, c->stream));
+                c->p_valid = true; pr.p_saved = false;
+            }
+            c->spec_redos += 1;
+            if (mispredicted) c->mispredicted += 1; else c->svd_fallbacks += 1;
             // what a roll-back costs = the device time of the work enqueued again (tnml_split_stats reports count and sum)
             hipEvent_t re0 = nullptr, re1 = nullptr;
             if (hipEventCreate(&re0) == hipSuccess && hipEventCreate(&re1) == hipSuccess) (void)hipEventRecord(re0, c->stream);
@@ -1807,7 +1881,7 @@ int tnml_bond_update_end(tnml_ctx* c, tnml_bond_report* rep) {
             c->force_safe = false;
             if (rc) return rc;
             if (had_next) TCK(tnml_bond_update_begin(c, b1, ha1, &sp1));
-            if (re0 && re1) { (void)hipEventRecord(re1, c->stream); c->redo_events.push_back({re0, re1}); }
+            if (re0 && re1) { (void)hipEventRecord(re1, c->stream); (mispredicted ? c->pred_redo_events : c->redo_events).push_back({re0, re1}); }
             return tnml_bond_update_end(c, rep);
         }
         spec_commit(c, pr);
@@ -1840,6 +1914,10 @@ int tnml_bond_update_end(tnml_ctx* c, tnml_bond_report* rep) {
     pr.rep.norm_newB = std::sqrt(nb2); pr.rep.diff_B_newB = std::sqrt(df2);
     c->sweep_start = pr.b == 1 && pr.ha == 2;                         // (tnml_sweepnext ends a sweep after bond 1 of half 2)
     if (pr.ho && c->ho && heldout_step(c, pr)) return tnml_fail(c, "held-out context: %s", c->ho->err.c_str());
+    if (pr.split_n > 0 && pr.b >= 1 && pr.b < (int)c->bond_hist.size()) {   // the history the prediction reads: what this call reports, after any roll-back
+        tnml_ctx::BondHist& hs = c->bond_hist[pr.b];
+        hs.n[1] = hs.n[0]; hs.m[1] = hs.m[0]; hs.n[0] = pr.split_n; hs.m[0] = pr.rep.newm;
+    }
     if (rep) *rep = pr.rep;
     return 0;
 }

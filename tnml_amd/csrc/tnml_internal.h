@@ -82,6 +82,7 @@ enum { SC_COST0 = 0, /* ..9 */ SC_NCORR = 10, SC_PP = 11, SC_RR = 12, /* 13: sec
 #define TNML_FPSLOT 32     /* first fingerprint slot (8 doubles) */
 #define TNML_CARRYN 24     /* carried doubles: slots 16..39 */
 #define TNML_SPECSLOT 28   /* carried: 1 when the deferred check of a speculative split failed (summed over the ranks: every rank rolls back together) */
+#define TNML_PREDSLOT 29   /* carried: 1 when a predicted split kept another column count than the truncation rule (k_truncate_verdict; a word of its own, so the two verdicts stay apart in the sum over the ranks) */
 
 struct BondPlan {
     int b = -1;
@@ -103,6 +104,8 @@ struct PendingReport {
     // and, when the deferred orthogonality check fails, to roll the bond update back and run it again with the synchronous split
     int b = 0, ha = 0; tnml_sweep_params sp{};
     bool spec = false; int split_n = 0, split_mk = 0; int nundo = 0; SiteUndo undo[2];
+    bool p_saved = false;                  // option spec_predict: the outputs P / dP this bond update found (left by its predecessor) are kept in tnml_ctx::psave
+    bool pred = false; int m_pred = 0;     // the speculative split ran on a PREDICTED column count (option spec_predict): k_truncate_verdict has judged it
     int dn_pairs = 0, cost_rows = 0; bool trace_mirrored = false, carry_direct = false;
     // a held-out context is attached: the two site tensors the split wrote (buffers and dimensions) and the event behind the split
     bool ho = false; hipEvent_t ev_ho = nullptr; SiteT ho_site[2];
@@ -245,6 +248,16 @@ struct tnml_ctx {
     int spec_split = 1; bool force_safe = false; long spec_redos = 0, spec_splits = 0;
     int debug_fail_split = -1;      // test hook (option "debug_fail_split" = k >= 0): the k-th speculative split reports a failed check
     long spec_splits_total = 0; double redo_ms = 0.; std::vector<std::pair<hipEvent_t, hipEvent_t>> redo_events;   // tnml_split_stats
+    // Predicted split (option spec_predict, env TNML_SPEC_PREDICT, default off): a truncating split (minm < the columns it may keep) takes the speculative
+    // form on the column count the bond kept at its last two finished visits; k_truncate_verdict applies the truncation rule to the
+    // eigenvalues on the device, and a wrong guess is rolled back like a failed check and repeated with the synchronous split.
+    int spec_predict = 0;
+    int debug_mispredict = -1;      // test hook (option "debug_mispredict" = k >= 0): the guess of the k-th predicted split is moved by one (host side only)
+    long pred_splits = 0, pred_splits_total = 0, mispredicted = 0; double pred_redo_ms = 0.;   // tnml_spec_predict_stats
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pred_redo_events;
+    struct BondHist { int n[2] = {0, 0}, m[2] = {0, 0}; };   // matrix side and kept columns of the last two finished splits of a bond ([0]: the latest; n = 0: none)
+    std::vector<BondHist> bond_hist;               // 1..N-1
+    double* psave = nullptr;                       // [2 slots][P | dP], allocated with the first bond update of spec_predict: a rolled-back bond update starts again from the very outputs its first run reused
     std::vector<double*> spare_small, spare_big;   // spare site-tensor buffers (capacity 2 maxm^2, x 10 for the Label site)
     double* hrep = nullptr;                        // pinned: [2 slots][hrep_stride] = eigenvalues + check values of a speculative split | CG scalars + trace | norm partials | after-SVD scalars
     double* hmir = nullptr;                        // != nullptr while a bond update is being enqueued: the [scal | trace] mirror of its slot (the CG step kernels write it)
@@ -531,6 +544,9 @@ int ctx_alloc_doubles(tnml_ctx* c, double** p, size_t n);       // device memory
 // ---- svd.hip ------------------------------------------------------------------------------
 int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cutoff, int maxm, int minm,
                      double* truncerr, int* newm, double* sv_host, int* nsv, int spec_slot = -1);   // spec_slot >= 0: may run without its host synchronisation (see tnml_ctx::spec_split)
+// tnml_truncate on the ascending eigenvalues `ev` (device), one lane: the kept count to host_m[0], [m != m_pred] to host_m[1] (both as doubles;
+// pinned or device memory) and, when given, to bad[0]
+int launch_truncate_verdict(tnml_ctx* c, const double* ev, int n, int maxm, int minm, double cutoff, int m_pred, double* host_m, double* bad);
 
 // ---- wave64 DPP helpers (device) ----
 // quad-lane exchange of a double through DPP (lanes 4q..4q+3 hold the 4 column strips of one block)

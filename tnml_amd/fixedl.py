@@ -161,6 +161,20 @@ class TrainStates:
         self._ck(self._L.tnml_split_stats(self._h, C.byref(a), C.byref(b), C.byref(ms)))
         return dict(speculative_splits=a.value, roll_backs=b.value, roll_back_ms=ms.value)
 
+    def spec_predict_stats(self):
+        """option spec_predict: splits that ran on a predicted column count, how many of them tnml_bond_update_end rolled back because
+        the truncation rule kept another count, device ms of the work repeated for those (tnml_spec_predict_stats)"""
+        a, b, ms = C.c_int64(), C.c_int64(), C.c_double()
+        self._ck(self._L.tnml_spec_predict_stats(self._h, C.byref(a), C.byref(b), C.byref(ms)))
+        return dict(predicted=a.value, mispredicted=b.value, redo_ms=ms.value)
+
+    def truncate_device(self, evals_ascending, maxm, minm, cutoff, m_pred):
+        """test entry (tnml_truncate_device): the device-side truncation rule on a host spectrum -> (kept count, count != m_pred)"""
+        ev = np.ascontiguousarray(evals_ascending, dtype=np.float64)
+        m, wrong = C.c_int(), C.c_int()
+        self._ck(self._L.tnml_truncate_device(self._h, _lib.dptr(ev), len(ev), int(maxm), int(minm), float(cutoff), int(m_pred), C.byref(m), C.byref(wrong)))
+        return m.value, wrong.value
+
     def shift_skip_stats(self, j):
         """site j (1..N): (16-image groups, groups of zero features only once each 64-image tile is walked zero features first) --
         the share of odd-row products the resident-operand shift leaves out (tnml_shift_skip_stats)"""

@@ -97,6 +97,7 @@ int main(int argc, const char* argv[]) {
         if (!oneshot && allreduce_kind != "rccl") die(nullptr, "allreduce must be rccl or oneshot");
         const std::string bond_log = input.getString("bond_log", "");                      // extension: a CSV line per bond update (machine-readable log for parity and bond updates/s)
         const double env_budget_gb = input.getReal("env_budget_gb", 0.);                    // extension: cap on the environments held in HBM, the rest lives in host memory (the reference's Nbatch / proj_images spill); 0 = all resident
+        const bool spec_predict = input.getYesNo("spec_predict", false);                // extension: truncating splits run without their host synchronisation on a predicted bond dimension (option spec_predict)
         const bool pipeline = input.getYesNo("pipeline", true);                         // extension: enqueue bond k+1 before fetching the report of bond k (see the sweep loop)
         const std::string precision = input.getString("precision", "f64");              // extension: f64 | mixed | f32 | bf16x3 | bf16
         const long imglen = input.getInt("imglen", 0);                                   // extension: 0 = keep the file's size
@@ -278,6 +279,7 @@ int main(int argc, const char* argv[]) {
             tnml_ctx* ctx = nullptr;
             if (tnml_create(&ctx, &cfg) != 0) die(nullptr, "tnml_create");
             if (env_budget_gb > 0.) CK(ctx, tnml_set_option(ctx, "env_budget_mb", (int)(env_budget_gb * 1024.)));
+            if (spec_predict) CK(ctx, tnml_set_option(ctx, "spec_predict", 1));
             if (use_u8) CK(ctx, tnml_set_data_u8(ctx, train.pixels.data() + (size_t)lo[r] * N, train.labels.data() + lo[r]));   // TState ctor, :644-653
             else        CK(ctx, tnml_set_data_phi(ctx, phi_all.data() + (size_t)lo[r] * N * 2, train.labels.data() + lo[r]));
             if (nranks > 1 && !share_device && !oneshot) CK(ctx, tnml_comm_init(ctx, uid));    // RCCL over xGMI, one rank per GPU
@@ -411,6 +413,11 @@ int main(int argc, const char* argv[]) {
                     if (!pipeline || pause_step) finish();
                 }
                 finish();
+                if (root && spec_predict) {
+                    int64_t np = 0, nm = 0; double ms = 0.;
+                    CK(ctx, tnml_spec_predict_stats(ctx, &np, &nm, &ms));
+                    std::printf("Predicted splits: %lld, mispredicted %lld (%.3f ms repeated)\n", (long long)np, (long long)nm, ms);
+                }
                 if (root) {
                     std::printf("Writing W to disk\n");                                     // :565
                     write_mps("W", download_mps(ctx, N));                                   // :566

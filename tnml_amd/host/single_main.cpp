@@ -143,6 +143,7 @@ int main(int argc, const char* argv[]) {
         const double feature_scale = input.getReal("feature_scale", 1.);
         const bool heldout = input.getYesNo("heldout", false);
         const long Ntest = input.getInt("Ntest", 50000);
+        const bool spec_predict = input.getYesNo("spec_predict", false);                 // extension: truncating splits run without their host synchronisation on a predicted bond dimension (option spec_predict)
         int dtype;
         if (!parse_dtype(precision, false, &dtype)) return 1;
         if (L < 0 || L > 9) { std::printf("label must be in 0..9\n"); return 1; }
@@ -228,6 +229,7 @@ int main(int argc, const char* argv[]) {
         if (tnml_create(&ctx, &cfg) != 0) die(nullptr, "tnml_create");
         if (fast_conj) CK(ctx, tnml_set_option(ctx, "cg_method", 1));
         if (exact) { CK(ctx, tnml_set_option(ctx, "cg_method", 2)); CK(ctx, tnml_set_option_real(ctx, "pcut", pcut)); }
+        if (spec_predict) CK(ctx, tnml_set_option(ctx, "spec_predict", 1));
         if (noise >= 1E-14) CK(ctx, tnml_set_option_real(ctx, "noise", noise));           // sweeps.noise() = noise, single.cc:222
         CK(ctx, tnml_set_data_phi(ctx, phi.data(), labels.data()));
         phi.clear(); phi.shrink_to_fit();
@@ -317,6 +319,11 @@ int main(int argc, const char* argv[]) {
                     write_mps(wname, download_mps(ctx, N));
                 }
                 std::fflush(stdout);
+            }
+            if (spec_predict) {
+                int64_t np = 0, nm = 0; double ms = 0.;
+                CK(ctx, tnml_spec_predict_stats(ctx, &np, &nm, &ms));
+                std::printf("Predicted splits: %lld, mispredicted %lld (%.3f ms repeated)\n", (long long)np, (long long)nm, ms);
             }
             std::printf("Writing %s to disk\n", wname);                                 // :722
             write_mps(wname, download_mps(ctx, N));

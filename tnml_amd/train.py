@@ -57,6 +57,7 @@ def main(argv=None):
     feature_scale = key("feature_scale", 1.0, float)
     try:
         heldout = hostlib.input_yesno(inp, "heldout", False)
+        spec_predict = hostlib.input_yesno(inp, "spec_predict", False)
     except RuntimeError as e:
         say(str(e))
         return 1
@@ -170,6 +171,8 @@ def main(argv=None):
         uid = [TrainStates.comm_unique_id() if rank == 0 else None]
         dist.broadcast_object_list(uid, src=0)
         ts.comm_init(uid[0])
+    if spec_predict:                                                            # truncating splits on a predicted bond dimension (option spec_predict)
+        ts.set_option("spec_predict", 1)
     ts.set_mps(W)
     say("Projecting training states...")
     ts.init()                                                                   # fixedL.cc:741
@@ -240,6 +243,9 @@ def main(argv=None):
                 lam = hook[1]
                 say("new lambda = %g" % lam)
             b, ha = lib.sweepnext(b, ha, N)
+        if spec_predict:
+            st = ts.spec_predict_stats()
+            say("Predicted splits: %d, mispredicted %d (%.3f ms repeated)" % (st["predicted"], st["mispredicted"], st["redo_ms"]))
         say("Writing W to disk")                                                # fixedL.cc:565
         Wnow = ts.get_mps()
         if rank == 0:
