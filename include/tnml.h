@@ -34,6 +34,7 @@ extern "C" {
 
 #define TNML_NL 10           /* label dimension, fixedL.cc:15 */
 #define TNML_MAX_PASS 64
+#define TNML_PREDICT_CHUNK_DEFAULT 8192   /* option "predict_chunk": images per chunk of tnml_predict_u8 / tnml_predict_phi */
 
 typedef struct tnml_ctx tnml_ctx;
 
@@ -285,6 +286,26 @@ int tnml_bond_update_end(tnml_ctx* ctx, tnml_bond_report* rep);
  *   a test set gets its own context.  Training environments held by the context are not modified. */
 int tnml_classify(tnml_ctx* ctx, double* weights, int32_t* pred, int64_t count[TNML_NL], int64_t nincorrect[TNML_NL]);
 
+/* ---- inference on images the context does not hold (util.h:19-40 toverlap + argmax, util.h:42-57) ------------
+ * The same contraction and decision rule as tnml_classify (first maximum of |W_l|; f > 1/2 in the per-label variant), for n images
+ * handed to the call instead of the ones given to tnml_set_data_*: weights[n][nl] (nl = 10, or 1 in TNML_MODE_SINGLE) and pred[n],
+ * either may be NULL.  tnml_predict_u8 applies the feature map of tnml_set_data_u8 to raw bytes, tnml_predict_phi takes features.
+ * Any context whose W is complete works, also one created without image data (NT_local = 1, no tnml_set_data_* call).  The host loop
+ * cuts n into chunks of option "predict_chunk" images; a chunk is staged, contracted by ONE launch of the chain kernel
+ * (kernels_chain.hip: a workgroup carries a tile of 64, 32 or 16 images through all N sites with the chain vectors in LDS; fp64 MFMA
+ * on the fp64 master W whatever cfg.dtype is; an image's result does not depend on n, on the chunk or on the tile it lands in) and
+ * copied back.  Reads W only: training data, environments, the bond plan and the cached outputs stay as they are, no collective is
+ * entered, and the call is allowed on a training context while a held-out context is attached to it.  Refused on a context that is
+ * itself attached as a held-out set (the training context's bond updates rewrite its W; tnml_classify refuses it too), while a bond update is in flight, and when W has a
+ * bond dimension above 512 (use tnml_classify on a context that holds the images).  n = 0 succeeds and does nothing.
+ * Workspace: allocated by the first call (tnml_estimate_bytes does not count it), independent of n, counted by tnml_device_bytes,
+ * freed by tnml_destroy (re-made when predict_chunk changes).  With C = predict_chunk rounded up to 64 and M = min(maxm, 512) rounded
+ * up to 16:   16 N + 8 nl C + 4 C + 8 M C   bytes (site table, results, parked chain vectors)
+ *           + 2 N C                         bytes from the first tnml_predict_u8 on (bytes as given and site-first)
+ *           + 32 N C                        bytes from the first tnml_predict_phi on (features as given and site-first). */
+int tnml_predict_u8(tnml_ctx* ctx, int64_t n, const uint8_t* pixels /*[n][N]*/, double* weights /*[n][nl] or NULL*/, int32_t* pred /*[n] or NULL*/);
+int tnml_predict_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/, double* weights, int32_t* pred);
+
 /* ---- held-out evaluation during training ----------------------------------------------------------
  * A held-out set is an ordinary context created for the held-out images (one rank: nranks = 1, its own shard of the set in
  * a multi-rank run).  Once attached to a training context, every bond update of `train` also moves the two site tensors it
@@ -385,7 +406,10 @@ int tnml_synchronize(tnml_ctx* ctx);
                       a communicator must set the same value: ranks that keep different column counts enter collectives of different sizes
      "debug_nudge_rank"  this rank's copy of a split site tensor is moved by one ulp (-1 off)
      "svd_print"      (TNML_SVD_PRINT) k >= 0: print the spectrum of the k-th split; -1: the check values of every split (-2 off)
+     "predict_tile"   images per workgroup of the chain kernel of tnml_predict_*: 16, 32 or 64, capped by what the LDS holds at W's largest bond
+                      dimension (64 up to 128, 32 up to 256, 16 up to 512); 0: that cap, halved while workgroups are fewer than compute units
    Memory and transport:
+     "predict_chunk"  images per trip of the host loop of tnml_predict_* = per launch of the chain kernel (1..2^20, default 8192); sizes its workspace
      "env_budget_mb"  cap on the environment slabs held on the device, the rest spills to host memory (0: none)
      "env_async"      the host tier's copies beside the compute stream (default 1)
      "comm_timeout_s" how long a rank of an in-process or one-shot communicator waits for its peers (>= 1, default 120)

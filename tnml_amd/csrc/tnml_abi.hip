@@ -87,7 +87,7 @@ int tnml_profile_reset(tnml_ctx* c) {
 // One row per option of tnml_set_option / tnml_set_option_real: its name, the environment variable that supplies its default at
 // tnml_create (or none), the field it sets, its kind and the values it accepts.  A bool option takes any value (nonzero: on).
 enum OptKind { OPT_BOOL, OPT_INT, OPT_REAL };
-enum OptHook { HK_NONE, HK_REUSE_P, HK_DEFER_TAIL, HK_CHECK_REPLICAS, HK_ENV_BUDGET, HK_COMM_TIMEOUT, HK_FAIL_SPLIT, HK_MISPREDICT, HK_SVD_PRINT, HK_CG_METHOD, HK_NOISE };
+enum OptHook { HK_NONE, HK_REUSE_P, HK_DEFER_TAIL, HK_CHECK_REPLICAS, HK_ENV_BUDGET, HK_COMM_TIMEOUT, HK_FAIL_SPLIT, HK_MISPREDICT, HK_SVD_PRINT, HK_CG_METHOD, HK_NOISE, HK_PREDICT_TILE };
 struct OptDef {
     const char* name; const char* env; OptKind kind;
     int tnml_ctx::* ifield; double tnml_ctx::* rfield;    // the field set (none for env_budget_mb: its hook stores bytes)
@@ -125,6 +125,8 @@ static const OptDef k_options[] = {
     {"debug_nudge_rank", nullptr,               OPT_INT,  &tnml_ctx::debug_nudge_rank,    nullptr,         -1, INT_MAX, HK_NONE},
     {"mc_spin_max",      nullptr,               OPT_INT,  &tnml_ctx::mc_spin_max,         nullptr,         -1, INT_MAX, HK_NONE},
     {"svd_print",        "TNML_SVD_PRINT",      OPT_INT,  &tnml_ctx::svd_print,           nullptr,         -2, INT_MAX, HK_SVD_PRINT},
+    {"predict_chunk",    nullptr,               OPT_INT,  &tnml_ctx::predict_chunk,       nullptr,          1, 1 << 20, HK_NONE},
+    {"predict_tile",     nullptr,               OPT_INT,  &tnml_ctx::predict_tile,        nullptr,          0, 64,      HK_PREDICT_TILE},
     {"fg64_cfg",         "TNML_FG64_CFG",       OPT_INT,  &tnml_ctx::opt_fg64_cfg,        nullptr,          0, 2,       HK_NONE},
     {"ldot_cfg",         "TNML_LDOT_CFG",       OPT_INT,  &tnml_ctx::opt_ldot_cfg,        nullptr,          0, 2,       HK_NONE},
     {"pcut",             nullptr,               OPT_REAL, nullptr,                        &tnml_ctx::pcut,  0, HUGE_VAL, HK_NONE},
@@ -149,6 +151,9 @@ static int apply_option(tnml_ctx* c, const OptDef& d, double v, const char* who,
         case HK_SVD_PRINT: c->svd_calls = 0; break;
         case HK_CG_METHOD:
             if (v >= 1 && !c->single()) return tnml_fail(c, "cg_method: 0 (conj) or, in TNML_MODE_SINGLE, 1 (fast_conj) / 2 (exact)");
+            break;
+        case HK_PREDICT_TILE:
+            if (v != 0 && v != 16 && v != 32 && v != 64) return tnml_fail(c, "%s: %s = %.15g, must be 0, 16, 32 or 64", who, what, v);
             break;
         case HK_NOISE:                                                 // single.cc:25,222: the noise of every sweep
             if (v >= 1e-14 && !c->single()) return tnml_fail(c, "noise: the density-matrix split exists in the per-label variant only (single.h:648-672)");
@@ -425,6 +430,7 @@ int tnml_create(tnml_ctx** out, const tnml_config* cfg) {
 }
 
 static void heldout_release(tnml_ctx* c);
+static void predict_release(tnml_ctx* c);
 int tnml_destroy(tnml_ctx* c) {
     if (!c) return 0;
     if (c->ho) heldout_release(c);                        // either context of a held-out pair: detach first
@@ -448,6 +454,7 @@ int tnml_destroy(tnml_ctx* c) {
     for (int k = 0; k < 2; ++k) for (int u = 0; u < c->pend[k].nundo; ++u) if (c->pend[k].undo[u].old) (void)hipFree(c->pend[k].undo[u].old);
     if (c->noise_ws) (void)hipFree(c->noise_ws);          // allocated on first use
     if (c->psave) (void)hipFree(c->psave);                // (option spec_predict)
+    predict_release(c);                                   // the workspace of tnml_predict_* (first call)
     for (auto& sl : c->slabs) if (sl.base) (void)hipFree(sl.base);
     if (c->hrep) (void)hipHostFree(c->hrep);
     if (c->hcost) (void)hipHostFree(c->hcost);
@@ -1032,6 +1039,86 @@ int tnml_classify(tnml_ctx* c, double* weights, int32_t* pred, int64_t count[TNM
         if (nincorrect && wrong) nincorrect[lab[i]] += 1;
     }
     return 0;
+}
+
+// ---- streamed inference: images the context does not hold (util.h:19-40 toverlap + argmax, util.h:42-57) ----------
+// The host loop cuts the n images into chunks of option predict_chunk; a chunk is staged (copy + one transposing pre-kernel), contracted by
+// ONE k_chain launch (kernels_chain.hip) and copied back.  Reads W only: no training data, environment, bond plan, P or p_valid is touched,
+// no collective is entered.  The workspace is allocated by the first call (see tnml.h for its size) and lives until tnml_destroy.
+static void predict_release(tnml_ctx* c) {
+    void** slots[] = {(void**)&c->pk_tab, (void**)&c->pk_w, (void**)&c->pk_pred, (void**)&c->pk_park, (void**)&c->pk_raw8, (void**)&c->pk_x8, (void**)&c->pk_rawphi, (void**)&c->pk_xphi};
+    for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    c->bytes -= c->pk_bytes;
+    c->pk_bytes = 0; c->pk_cap = 0; c->pk_park_elems = 0;
+}
+static int predict_alloc(tnml_ctx* c, void** p, size_t bytes) {
+    TCK(dalloc(c, p, bytes));
+    c->pk_bytes += (int64_t)bytes;
+    return 0;
+}
+static int predict_workspace(tnml_ctx* c, bool bytes_form) {
+    const int cap = (c->predict_chunk + 63) / 64 * 64;
+    if (c->pk_cap != cap) {                               // first call, or option predict_chunk has changed since
+        if (c->pk_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); predict_release(c); }
+        const size_t mc = (size_t)(std::min(c->maxm, TNML_CHAIN_MAXM) + 15) / 16 * 16;
+        int rc = predict_alloc(c, (void**)&c->pk_tab, (size_t)c->N * sizeof(ChainSite));
+        if (!rc) rc = predict_alloc(c, (void**)&c->pk_w, (size_t)cap * c->nl() * sizeof(double));
+        if (!rc) rc = predict_alloc(c, (void**)&c->pk_pred, (size_t)cap * sizeof(int));
+        if (!rc) rc = predict_alloc(c, (void**)&c->pk_park, (size_t)cap * mc * sizeof(double));
+        if (rc) { predict_release(c); return rc; }
+        c->pk_park_elems = (size_t)cap * mc;
+        c->pk_cap = cap;
+    }
+    int rc = 0;
+    if (bytes_form && !c->pk_x8) { rc = predict_alloc(c, (void**)&c->pk_raw8, (size_t)cap * c->N); if (!rc) rc = predict_alloc(c, (void**)&c->pk_x8, (size_t)cap * c->N); }
+    if (!bytes_form && !c->pk_xphi) { rc = predict_alloc(c, (void**)&c->pk_rawphi, (size_t)2 * cap * c->N * sizeof(double)); if (!rc) rc = predict_alloc(c, (void**)&c->pk_xphi, (size_t)2 * cap * c->N * sizeof(double)); }
+    if (rc) predict_release(c);
+    return rc;
+}
+static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, double* weights, int32_t* pred) {
+    if (!c) return tnml_fail(c, "%s: null argument", who);
+    if (n < 0) return tnml_fail(c, "%s: n = %lld, must be >= 0", who, (long long)n);
+    if (c->pend_count > 0) return tnml_fail(c, "%s: a bond update is in flight (tnml_bond_update_end first)", who);
+    TCK(ho_locked(c, who));                                     // attached as a held-out set: its W is rewritten from the training context's stream, as tnml_classify refuses it
+    TCK(check_W(c));
+    int maxbond = 1;
+    for (int j = 1; j <= c->N; ++j) maxbond = std::max(maxbond, std::max(c->W[j].ml, c->W[j].mr));
+    if (maxbond > TNML_CHAIN_MAXM)
+        return tnml_fail(c, "%s: W has a bond of dimension %d, the chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, maxbond, TNML_CHAIN_MAXM);
+    if (n == 0) return 0;
+    if (!pixels && !phi) return tnml_fail(c, "%s: null argument", who);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const bool bytes_form = pixels != nullptr;
+    TCK(predict_workspace(c, bytes_form));
+    const int cs = c->single() ? 1 : c->c0, nl = c->nl();       // the centre tnml_classify takes
+    std::vector<ChainSite> tab(c->N);
+    for (int j = 1; j <= c->N; ++j) tab[j - 1] = ChainSite{c->W[j].a, c->W[j].ml, c->W[j].mr};
+    HIPCK(c, hipMemcpyAsync(c->pk_tab, tab.data(), sizeof(ChainSite) * c->N, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));                  // (tab leaves scope with this call)
+    const size_t per_img = (size_t)c->N * (bytes_form ? 1 : 2 * sizeof(double));
+    for (int64_t off = 0; off < n; off += c->predict_chunk) {
+        const int cnt = (int)std::min<int64_t>(c->predict_chunk, n - off);
+        if (bytes_form) HIPCK(c, hipMemcpyAsync(c->pk_raw8, pixels + (size_t)off * c->N, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+        else            HIPCK(c, hipMemcpyAsync(c->pk_rawphi, phi + (size_t)off * c->N * 2, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+        TCK(launch_chain_stage(c, bytes_form ? c->pk_raw8 : nullptr, bytes_form ? nullptr : c->pk_rawphi, c->N, cnt, c->pk_cap, c->pk_x8, c->pk_xphi));
+        ChainArgs a;
+        a.sites = c->pk_tab; a.N = c->N; a.cs = cs; a.nl = nl; a.single = c->single() ? 1 : 0;
+        a.xT = bytes_form ? c->pk_x8 : nullptr; a.phiT = bytes_form ? nullptr : c->pk_xphi;
+        a.ld = c->pk_cap; a.cnt = cnt; a.wout = c->pk_w; a.pred = c->pk_pred;
+        TCK(launch_chain(c, a, maxbond, chain_tile(c, maxbond, cnt), c->pk_park, c->pk_park_elems));
+        if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->pk_w, sizeof(double) * (size_t)cnt * nl, hipMemcpyDeviceToHost, c->stream));
+        if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->pk_pred, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+        SYNCK(c, c->stream);                                    // the staging buffers are reused by the next chunk
+    }
+    return 0;
+}
+int tnml_predict_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, double* weights, int32_t* pred) {
+    if (n > 0 && !pixels) return tnml_fail(c, "tnml_predict_u8: null argument");
+    return predict_impl(c, "tnml_predict_u8", n, pixels, nullptr, weights, pred);
+}
+int tnml_predict_phi(tnml_ctx* c, int64_t n, const double* phi, double* weights, int32_t* pred) {
+    if (n > 0 && !phi) return tnml_fail(c, "tnml_predict_phi: null argument");
+    return predict_impl(c, "tnml_predict_phi", n, nullptr, phi, weights, pred);
 }
 
 // ---- bond plan (TrainStates::setBond, fixedL.cc:159-190: pointer selection only) ---------------

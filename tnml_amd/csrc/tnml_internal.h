@@ -20,6 +20,7 @@
 #include <rocsolver/rocsolver.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -32,11 +33,11 @@
 
 enum KClass {
     KC_FGEMM_FWD = 0, KC_FGEMM_SHIFT, KC_LABELDOT, KC_ZPRIME, KC_BGEMM, KC_SLABRED, KC_PACK, KC_VEC,
-    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_COUNT
+    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_COUNT
 };
 static const char* const kclass_names[KC_COUNT] = {
     "fgemm_fwd", "fgemm_shift", "labeldot", "zprime", "bgemm", "slab_reduce", "pack", "cg_vec",
-    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad"};
+    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain"};
 
 struct EnvSlot {
     void* ptr = nullptr;    // [L][m][NTp], fp32 or fp64 elements (tnml_ctx::env64); null while the environment is spilled to the host
@@ -288,6 +289,18 @@ struct tnml_ctx {
     HeldOut* held = nullptr;
     bool sweep_start = false;  // environments as tnml_env_init left them, or the last bond update ended a sweep: where attach may happen
 
+    // streamed inference (tnml_predict_u8 / tnml_predict_phi, kernels_chain.hip): images the context does not hold, predict_chunk at a time
+    int predict_chunk = TNML_PREDICT_CHUNK_DEFAULT;        // option "predict_chunk": images staged, launched (one k_chain launch) and copied back per trip of the host loop
+    int predict_tile = 0;            // test knob (option "predict_tile"): images per workgroup of k_chain, 16 / 32 / 64 (capped by the LDS budget); 0: by bond dimension and image count
+    bool attr_chain = false;
+    // its workspace, allocated by the first predict call (counted in `bytes`, freed by tnml_destroy); pk_cap = predict_chunk rounded up to 64 when it was sized
+    int pk_cap = 0; int64_t pk_bytes = 0;
+    struct ChainSite* pk_tab = nullptr;   // [N] per-site table (ml, mr, address)
+    double* pk_w = nullptr; int* pk_pred = nullptr;   // [pk_cap][nl], [pk_cap]: results of a chunk
+    double* pk_park = nullptr; size_t pk_park_elems = 0;   // [pk_cap / T][ru16(m)][T]: the parked right-chain vectors of the workgroups (when three tiles do not fit the LDS)
+    uint8_t *pk_raw8 = nullptr, *pk_x8 = nullptr;     // bytes of a chunk as given [pk_cap][N] and site-first [N][pk_cap] (first tnml_predict_u8)
+    double *pk_rawphi = nullptr, *pk_xphi = nullptr;  // features of a chunk as given [pk_cap][N][2] and site-first [N][2][pk_cap] (first tnml_predict_phi)
+
     // profiling
     bool prof = false;
     unsigned prof_mask = 0xffffffffu;   // kernel classes that are timed while prof is on
@@ -506,6 +519,23 @@ int split_gemm(tnml_ctx* c, bool ta, bool tb, int M, int N, int K, const double*
 int launch_mps_place(tnml_ctx* c, const double* src, int ml, int mr, double* dst, int ML, int MR, int row0, int col0, int slot);
 // one step of the transfer chain: Eout[mr][mr] = sum_{k < 2 ml, l < L} A[k][r][l] T[k][r'][l] with T = E A (both [2 ml][mr][L], first index fastest)
 int launch_mps_transfer(tnml_ctx* c, const double* A, const double* T, int K, int mr, int L, double* Eout);
+
+// ---- kernels_chain.hip: streamed inference, the whole chain of toverlap for a tile of images in one launch ----
+#define TNML_CHAIN_MAXM 512        /* largest bond dimension k_chain serves */
+#define TNML_CHAIN_LDS 163840      /* LDS of a workgroup: 160 KiB */
+struct ChainSite { const double* a; int ml, mr; };   // site tensor where it lives (SiteT::a, ITensor layout) and its bond dimensions
+struct ChainArgs {
+    const ChainSite* sites;            // [N] device
+    int N, cs, nl, single;             // cs: the centre site (N/2, or 1 in the per-label variant); nl: label extent; single: pred = [f > 1/2]
+    const uint8_t* xT;                 // bytes, site-first [N][ld] -- or
+    const double* phiT;                // features, site-first [N][2][ld]
+    int ld, cnt;                       // row length of the staged images, images of this chunk
+    double* wout; int* pred;           // [cnt][nl], [cnt]
+    int mcap = 0; double* park = nullptr;   // set by launch_chain
+};
+int launch_chain_stage(tnml_ctx* c, const uint8_t* pix, const double* phi, int N, int cnt, int ld, uint8_t* xT, double* phiT);   // exactly one of pix [cnt][N] / phi [cnt][N][2]
+int chain_tile(tnml_ctx* c, int maxbond, int cnt);
+int launch_chain(tnml_ctx* c, ChainArgs a, int maxbond, int T, double* park_ws, size_t park_elems);
 
 // ---- eigh.hip -----------------------------------------------------------------------------
 int eigh_tridiagonalize(tnml_ctx* c, const double* A, int n, double* D, double* E, double* tau, double* V, double psd_tol = 0.);   // tau: n doubles, tau[n-1] = number of reflectors

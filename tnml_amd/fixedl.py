@@ -200,6 +200,27 @@ class TrainStates:
                                        cnt.ctypes.data_as(C.POINTER(C.c_int64)), ninc.ctypes.data_as(C.POINTER(C.c_int64))))
         return w, pred, cnt, ninc
 
+    def predict(self, pixels=None, phi=None):
+        """streamed inference on images this context does not hold (tnml_predict_u8 / tnml_predict_phi): pixels[n, N] bytes or
+        phi[n, N, 2] features -> (weights[n, nl], pred[n]); pred is argmax_l |W_l| (per-label variant: [f > 1/2]).  Reads W only."""
+        if (pixels is None) == (phi is None):
+            raise ValueError("need exactly one of pixels or phi")
+        if pixels is not None:
+            x = np.ascontiguousarray(pixels, dtype=np.uint8)
+            assert x.ndim == 2 and x.shape[1] == self.N, x.shape
+        else:
+            x = np.ascontiguousarray(phi, dtype=np.float64)
+            assert x.ndim == 3 and x.shape[1:] == (self.N, 2), x.shape
+        n = int(x.shape[0])
+        w = np.zeros((n, self.nl))
+        pred = np.zeros(n, dtype=np.int32)
+        pp = pred.ctypes.data_as(C.POINTER(C.c_int32))
+        if pixels is not None:
+            self._ck(self._L.tnml_predict_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(w), pp))
+        else:
+            self._ck(self._L.tnml_predict_phi(self._h, n, _lib.dptr(x), _lib.dptr(w), pp))
+        return w, pred
+
     # -- W
     def set_mps(self, W):
         for j, A in enumerate(W, start=1):

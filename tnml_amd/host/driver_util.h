@@ -100,6 +100,12 @@ inline void print_heldout_line(double cost_sum, long long ncorrect, long long co
     std::printf("Held-out: Percent correct = %.4f%%, # incorrect = %lld/%lld, Cost = %.10f\n", ncorrect * 100. / count,
                 count - ncorrect, count, cost_sum / count);
 }
+// the key `predict_chunk` of the evaluators: > 0 sets the context option of that name; returns the chunk size in effect
+inline int predict_chunk_option(tnml_ctx* ctx, long requested) {
+    if (requested <= 0) return TNML_PREDICT_CHUNK_DEFAULT;
+    CK(ctx, tnml_set_option(ctx, "predict_chunk", (int)requested));
+    return (int)requested;
+}
 // fullTest's result table (util.h:186-199) from the images and the misclassified images per label
 inline void print_fulltest_table(const int64_t counts[10], const int64_t nincorrect[10]) {
     long nte = 0, tninc = 0;

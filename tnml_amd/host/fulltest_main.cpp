@@ -5,7 +5,9 @@
 // `datadir`, and the result table of fullTest (util.h:186-199).  The per-image contraction toverlap
 // (util.h:19-40) is one tnml_classify call on the device.  Extensions: `device`, `precision`
 // (f64 | mixed | f32), `Ntest` (per-label cap; the reference takes the whole test set), `imglen` and
-// `feature_scale` as in the fixedL driver (they must match the values W was trained with).
+// `feature_scale` as in the fixedL driver (they must match the values W was trained with); `predict` (yes | no,
+// default no): a data-less context sized by W alone, the test set streamed through tnml_predict_u8 / tnml_predict_phi
+// in chunks of `predict_chunk` images (0: the library's default) and counted on the host.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -30,6 +32,8 @@ int main(int argc, const char* argv[]) {
         const long Ntest = input.getInt("Ntest", 50000);                               // mllib/mnist.h:452 default NT
         const long imglen = input.getInt("imglen", 0);
         const double feature_scale = input.getReal("feature_scale", 1.);
+        const bool predict = input.getYesNo("predict", false);
+        const long predict_chunk = input.getInt("predict_chunk", 0);
         int dtype;
         if (!parse_dtype(precision, false, &dtype)) return 1;
 
@@ -54,21 +58,31 @@ int main(int argc, const char* argv[]) {
         if (cent != N / 2) { std::printf("Label Index not on site %d\n", N / 2); return 1; }
 
         tnml_config cfg{};
-        cfg.device = device; cfg.rank = 0; cfg.nranks = 1; cfg.N = N; cfg.NT_local = totNtest; cfg.NT_total = totNtest;
+        cfg.device = device; cfg.rank = 0; cfg.nranks = 1; cfg.N = N; cfg.NT_local = predict ? 1 : totNtest; cfg.NT_total = cfg.NT_local;
         cfg.maxm = max_link_dim(psi); cfg.dtype = dtype; cfg.svd_backend = TNML_SVD_SYEVD;
         tnml_ctx* ctx = nullptr;
         if (tnml_create(&ctx, &cfg)) die(nullptr, "tnml_create");
-        if (!normal && !test.reduced() && feature_scale == 1.) {
-            CK(ctx, tnml_set_data_u8(ctx, test.pixels.data(), test.labels.data()));    // phi = [1, x/4], x = (byte/255)/255
-        } else {
-            std::vector<double> phi = all_features(test, normal, feature_scale);       // fulltest.cc:57-70
-            CK(ctx, tnml_set_data_phi(ctx, phi.data(), test.labels.data()));
+        const bool bytes_in = !normal && !test.reduced() && feature_scale == 1.;        // phi = [1, x/4], x = (byte/255)/255
+        std::vector<double> phi;
+        if (!bytes_in) phi = all_features(test, normal, feature_scale);                // fulltest.cc:57-70
+        if (!predict) {
+            if (bytes_in) CK(ctx, tnml_set_data_u8(ctx, test.pixels.data(), test.labels.data()));
+            else CK(ctx, tnml_set_data_phi(ctx, phi.data(), test.labels.data()));
         }
         upload_mps(ctx, psi);
 
         std::printf("Running full test of %s\n", fname.c_str());                       // :97
-        int64_t counts[10], ninc[10];
-        CK(ctx, tnml_classify(ctx, nullptr, nullptr, counts, ninc));
+        int64_t counts[10] = {0}, ninc[10] = {0};
+        if (!predict) {
+            CK(ctx, tnml_classify(ctx, nullptr, nullptr, counts, ninc));
+        } else {
+            const int chunk = predict_chunk_option(ctx, predict_chunk);
+            std::printf("Device path: streamed chain kernel (%s), %d images per chunk\n", bytes_in ? "tnml_predict_u8" : "tnml_predict_phi", chunk);
+            std::vector<int32_t> pred(totNtest);
+            if (bytes_in) CK(ctx, tnml_predict_u8(ctx, totNtest, test.pixels.data(), nullptr, pred.data()));
+            else CK(ctx, tnml_predict_phi(ctx, totNtest, phi.data(), nullptr, pred.data()));
+            for (int i = 0; i < totNtest; ++i) { const int l = test.labels[i]; counts[l]++; if (pred[i] != l) ++ninc[l]; }
+        }
         print_fulltest_table(counts, ninc);                                            // util.h:186-199
         tnml_destroy(ctx);
     } catch (const std::exception& e) {

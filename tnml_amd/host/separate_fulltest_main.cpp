@@ -5,7 +5,9 @@
 // the file `sites`, the ten weight files `L<n>/W<n>`, the t10k idx files, the "normal" feature map (hard-coded in the
 // reference, :104-118), and the printed tables: per image the ten overlaps o_n = <W_n|x>, prediction
 // argmax_n |o_n| (first maximum), costs[n] += (n == l) ? (o_n - 1)^2 : o_n^2.  Extensions: `feature` (normal | series),
-// `device`, `precision`, `Ntest`, `imglen` honoured as block-mean down-sampling, `feature_scale`.
+// `device`, `precision`, `Ntest`, `imglen` honoured as block-mean down-sampling, `feature_scale`; `predict` (yes | no,
+// default no): a data-less context sized by the ten W alone, the test set streamed through tnml_predict_phi in chunks of
+// `predict_chunk` images (0: the library's default).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -30,6 +32,8 @@ int main(int argc, const char* argv[]) {
         const std::string precision = input.getString("precision", "f64");
         const long Ntest = input.getInt("Ntest", 50000);
         const double feature_scale = input.getReal("feature_scale", 1.);
+        const bool predict = input.getYesNo("predict", false);
+        const long predict_chunk = input.getInt("predict_chunk", 0);
         int dtype;
         if (!parse_dtype(precision, false, &dtype)) return 1;
         bool normal;
@@ -56,19 +60,22 @@ int main(int argc, const char* argv[]) {
             wm = std::max(wm, max_link_dim(Ws[n]));
         }
         tnml_config cfg{};
-        cfg.device = device; cfg.rank = 0; cfg.nranks = 1; cfg.N = N; cfg.NT_local = totNtest; cfg.NT_total = totNtest;
+        cfg.device = device; cfg.rank = 0; cfg.nranks = 1; cfg.N = N; cfg.NT_local = predict ? 1 : totNtest; cfg.NT_total = cfg.NT_local;
         cfg.maxm = wm; cfg.dtype = dtype; cfg.svd_backend = TNML_SVD_SYEVD; cfg.mode = TNML_MODE_SINGLE; cfg.target_label = 0;
         tnml_ctx* ctx = nullptr;
         if (tnml_create(&ctx, &cfg)) die(nullptr, "tnml_create");
-        {
-            std::vector<double> phi = all_features(test, normal, feature_scale);
+        std::vector<double> phi = all_features(test, normal, feature_scale);
+        if (!predict) {
             CK(ctx, tnml_set_data_phi(ctx, phi.data(), test.labels.data()));
+            std::vector<double>().swap(phi);
         }
         std::printf("Running full test\n");                                            // :165
+        if (predict) std::printf("Device path: streamed chain kernel (tnml_predict_phi), %d images per chunk\n", predict_chunk_option(ctx, predict_chunk));
         std::vector<std::vector<double>> o(NLW, std::vector<double>(totNtest));        // o[n][image] = overlap(Ws[n], testimg), :38
         for (int n = 0; n < NLW; ++n) {
             upload_mps(ctx, Ws[n]);
-            CK(ctx, tnml_classify(ctx, o[n].data(), nullptr, nullptr, nullptr));
+            if (predict) CK(ctx, tnml_predict_phi(ctx, totNtest, phi.data(), o[n].data(), nullptr));
+            else CK(ctx, tnml_classify(ctx, o[n].data(), nullptr, nullptr, nullptr));
         }
         int64_t counts[10] = {0}, ninc[10] = {0};
         double costs[10] = {0};

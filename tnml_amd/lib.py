@@ -33,6 +33,7 @@ EXPORTS = [
     "tnml_lin_cg_start", "tnml_lin_cg_run", "tnml_lin_get_v", "tnml_lin_evaluate",
     "tnml_heldout_attach", "tnml_heldout_detach", "tnml_heldout_read",
     "tnml_mps_place", "tnml_mps_compress", "tnml_mps_overlap",
+    "tnml_predict_u8", "tnml_predict_phi",
 ]
 
 
@@ -129,6 +130,8 @@ def load():
     L.tnml_device_bytes.argtypes = [vp]
     L.tnml_classify.argtypes = [vp, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.tnml_device_bytes.restype = C.c_int64
+    L.tnml_predict_u8.argtypes = [vp, C.c_int64, C.POINTER(C.c_uint8), dp, C.POINTER(C.c_int32)]
+    L.tnml_predict_phi.argtypes = [vp, C.c_int64, dp, dp, C.POINTER(C.c_int32)]
     L.tnml_replica_check.argtypes = [vp, ip]
     L.tnml_replica_repairs.argtypes = [vp]
     L.tnml_replica_repairs.restype = C.c_int64
