@@ -178,10 +178,36 @@ int64_t tnml_replica_repairs(tnml_ctx* ctx);           /* re-broadcasts so far i
 int tnml_collective_stats(tnml_ctx* ctx, int64_t* allreduces, int64_t* broadcasts);
 
 /* ---- training set: TState ctor fixedL.cc:28-47 + feature map :637-642 -------------------- */
-/* raw bytes [NT_local][N] with the reference's feature map phi = [1, byte/(255*255*4)] */
+/* raw bytes [NT_local][N] with the reference's feature map phi = [1, byte/(255*255*4)]; under an input map (below)
+   [NT_local][src_rows*src_cols] bytes with the map's block sums and table */
 int tnml_set_data_u8(tnml_ctx* ctx, const uint8_t* pixels, const int32_t* labels);
 /* arbitrary d=2 local features phi[NT_local][N][2] (TState::data layout) */
 int tnml_set_data_phi(tnml_ctx* ctx, const double* phi, const int32_t* labels);
+
+/* ---- input map: raw bytes -> local features for any feature map and any block-sum reduction ------------------------
+ * Every d=2 feature map of a byte image is a table: a site's features depend on its pixel value only, and after a block x block
+ * mean that value is code / block^2 with `code` the integer sum of the block's bytes (0 .. 255 block^2).  While a map is set,
+ * tnml_set_data_u8 and tnml_predict_u8 read src_rows*src_cols bytes per image (not N), the device sums the blocks, looks the two
+ * features of every site up in `table` and transposes to its site-first layouts; a table filled with the host's own feature
+ * expression (tnmlh_feature_table) gives bit for bit the features of the fp64 path (tnml_set_data_phi / tnml_predict_phi).
+ * fp32-storage contexts round table[code][s] once to float for the stored features, as tnml_set_data_phi rounds phi; the chain
+ * kernel of tnml_predict_u8 always reads the fp64 table.
+ * The map is consulted only when bytes arrive: features stored by an earlier tnml_set_data_* call stay as they are, whatever map
+ * is set or removed afterwards.  Without a map every call does, bit for bit, what it did before this entry point existed.
+ * Refused (the message names the field; the previous map stays in force) when block is outside 1..8, ncodes is not
+ * 255 block^2 + 1, out_rows*out_cols is not cfg.N, a block leaves the source image (row0 / col0 negative, or
+ * row0 + block out_rows > src_rows, col0 + block out_cols > src_cols), table is NULL or holds a value that is not finite, the
+ * context is attached as a held-out set, or a bond update is in flight. */
+typedef struct {
+    int src_rows, src_cols;     /* raw image handed to tnml_set_data_u8 / tnml_predict_u8: [src_rows][src_cols] bytes, row-major */
+    int block;                  /* 1..8: a site is the SUM of a block x block square of bytes */
+    int row0, col0;             /* top-left corner of the first block (reduce(): side % bsize) */
+    int out_rows, out_cols;     /* sites in row-major order of the reduced image; out_rows*out_cols == cfg.N */
+    int ncodes;                 /* must be 255*block*block + 1 */
+    const double* table;        /* [ncodes][2]: the two local features of a site whose block sum is `code`; copied by the call */
+} tnml_input_map;
+int tnml_set_input_map(tnml_ctx* ctx, const tnml_input_map* map);   /* NULL: back to the built-in map */
+int tnml_get_input_map(tnml_ctx* ctx, tnml_input_map* out);         /* geometry only (table = NULL); block = 0 when none is set */
 
 /* ---- weight MPS replica (W.A(j) / W.Aref(j)) ------------------------------------------- */
 int tnml_set_site(tnml_ctx* ctx, int j, int ml, int mr, int has_label, const double* A);
@@ -289,7 +315,8 @@ int tnml_classify(tnml_ctx* ctx, double* weights, int32_t* pred, int64_t count[T
 /* ---- inference on images the context does not hold (util.h:19-40 toverlap + argmax, util.h:42-57) ------------
  * The same contraction and decision rule as tnml_classify (first maximum of |W_l|; f > 1/2 in the per-label variant), for n images
  * handed to the call instead of the ones given to tnml_set_data_*: weights[n][nl] (nl = 10, or 1 in TNML_MODE_SINGLE) and pred[n],
- * either may be NULL.  tnml_predict_u8 applies the feature map of tnml_set_data_u8 to raw bytes, tnml_predict_phi takes features.
+ * either may be NULL.  tnml_predict_u8 applies the feature map of tnml_set_data_u8 to raw bytes (the input map when one is set: pixels is
+ * then [n][src_rows*src_cols]), tnml_predict_phi takes features.
  * Any context whose W is complete works, also one created without image data (NT_local = 1, no tnml_set_data_* call).  The host loop
  * cuts n into chunks of option "predict_chunk" images; a chunk is staged, contracted by ONE launch of the chain kernel
  * (kernels_chain.hip: a workgroup carries a tile of 64, 32 or 16 images through all N sites with the chain vectors in LDS; fp64 MFMA
@@ -302,6 +329,9 @@ int tnml_classify(tnml_ctx* ctx, double* weights, int32_t* pred, int64_t count[T
  * freed by tnml_destroy (re-made when predict_chunk changes).  With C = predict_chunk rounded up to 64 and M = min(maxm, 512) rounded
  * up to 16:   16 N + 8 nl C + 4 C + 8 M C   bytes (site table, results, parked chain vectors)
  *           + 2 N C                         bytes from the first tnml_predict_u8 on (bytes as given and site-first)
+ *           + S C + 2 N C + 16 ncodes       bytes instead, from the first tnml_predict_u8 under an input map on (S = src_rows src_cols
+ *                                           bytes as given, 16-bit block sums site-first, the fp64 table); released by every
+ *                                           tnml_set_input_map call and re-made by the next tnml_predict_u8 under a map
  *           + 32 N C                        bytes from the first tnml_predict_phi on (features as given and site-first). */
 int tnml_predict_u8(tnml_ctx* ctx, int64_t n, const uint8_t* pixels /*[n][N]*/, double* weights /*[n][nl] or NULL*/, int32_t* pred /*[n] or NULL*/);
 int tnml_predict_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/, double* weights, int32_t* pred);

@@ -38,14 +38,21 @@ static __device__ __forceinline__ int chain_idx(int k, int n) {
 }
 
 // features of site j (1-indexed) for the NCT columns of this lane: image tile0 + 16 ct + (lane & 15); images beyond cnt get (0, 0)
-template <int NCT>
+// SRC 0: bytes through the built-in expression (g.xT) or fp64 features (g.phiT), chosen at run time as before the input map existed;
+// SRC 1: the input map -- one 2-byte block sum and one dependent 16-byte table row per site and column (g.codeT, g.table; the table
+// is at most 261 KB and stays in L2).  The source is a template parameter so that the SRC 0 instantiations carry nothing of it.
+template <int NCT, int SRC>
 static __device__ __forceinline__ void chain_features(const ChainArgs& g, int j, int img0, double (&p0)[NCT], double (&p1)[NCT]) {
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
         const int n = img0 + 16 * ct;
         double f0 = 0., f1 = 0.;
         if (n < g.cnt) {
-            if (g.xT) {                         // the expression of k_features_u8<double> (kernels_stream.hip)
+            if (SRC == 1) {
+                const unsigned code = g.codeT[(size_t)(j - 1) * g.ld + n];
+                const chain_d2 f = *(const chain_d2*)(g.table + (size_t)2 * code);
+                f0 = f.x; f1 = f.y;
+            } else if (g.xT) {                         // the expression of k_features_u8<double> (kernels_stream.hip)
                 const double gq = (double)g.xT[(size_t)(j - 1) * g.ld + n] / 255.;
                 f0 = 1.;
                 f1 = (gq / 255.) / 4.;
@@ -117,7 +124,7 @@ static __device__ __forceinline__ void chain_step(const double* __restrict__ A, 
     }
 }
 
-template <int NCT>
+template <int NCT, int SRC>
 __global__ __launch_bounds__(CHAIN_THREADS) void k_chain(const ChainArgs g) {
     constexpr int T = 16 * NCT;
     extern __shared__ __attribute__((aligned(16))) double ch_lds[];
@@ -132,13 +139,13 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_chain(const ChainArgs g) {
 
     double p0[NCT], p1[NCT], q0[NCT], q1[NCT];
     const int img0 = tile0 + (lane & 15);
-    chain_features<NCT>(g, site_at(0), img0, p0, p1);
+    chain_features<NCT, SRC>(g, site_at(0), img0, p0, p1);
     if (tid < T) { buf[0][chain_idx<NCT>(0, tid)] = 1.; if (nright == 0) park[chain_idx<NCT>(0, tid)] = 1.; }
     __syncthreads();
     int cur = 0;
     for (int t = 0; t < N - 1; ++t) {
         const int j = site_at(t);
-        chain_features<NCT>(g, site_at(t + 1), img0, q0, q1);           // the next site's features, loaded ahead of the barrier
+        chain_features<NCT, SRC>(g, site_at(t + 1), img0, q0, q1);           // the next site's features, loaded ahead of the barrier
         const ChainSite st = g.sites[j - 1];
         if (t < nright) {
             const bool last = t == nright - 1;
@@ -188,6 +195,82 @@ __global__ void k_chain_stage_phi(const double* __restrict__ phi, int N, int cnt
     }
 }
 
+// Input map: raw bytes [cnt][S] -> block sums, site-first codes[N][ld] with the image index fastest -- the LDS-tiled transpose of the byte
+// path with the block sum folded in.  A workgroup takes 64 images x a group of output rows x a chunk of output columns: it copies the
+// source-row pieces under them into LDS with consecutive threads on consecutive bytes of an image's rows (byte loads: with S odd no
+// image after the first is dword-aligned; full-width rows of one image follow each other in memory, so a group of rows is one run),
+// sums the block x block squares in integers, and writes codes with consecutive lanes on consecutive images (128-byte rows of 16-bit
+// values).  The LDS pitch of an image is an odd number of dwords, so the 64 lanes of the summing phase fall on 64 different banks.
+// Source pixels outside every block are never read.
+#define STAGE_IMGS 64
+#define STAGE_THREADS 256
+#define STAGE_IMG_BYTES 512        /* LDS bytes per image a workgroup aims at: 64 block^2 at block = 8, one output site */
+struct StageLaunch { int ncc, nry, pitch; };
+// output columns and rows per workgroup and the LDS pitch (bytes) of an image
+static StageLaunch stage_shape(const StageGeom& g) {
+    StageLaunch s;
+    const int b2 = g.block * g.block;
+    s.ncc = std::max(1, std::min(g.out_cols, STAGE_IMG_BYTES / b2));
+    s.nry = std::max(1, std::min(g.out_rows, STAGE_IMG_BYTES / (b2 * s.ncc)));
+    int dw = (b2 * s.ncc * s.nry + 3) / 4;
+    if (!(dw & 1)) dw += 1;
+    s.pitch = 4 * dw;
+    return s;
+}
+__global__ __launch_bounds__(STAGE_THREADS) void k_stage_codes(const uint8_t* __restrict__ raw, const StageGeom g, int ncc, int nry, int pitch, int cnt, int ld, uint16_t* __restrict__ codes) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t st_lds[];
+    const int tid = threadIdx.x;
+    const int n0 = blockIdx.x * STAGE_IMGS, oy0 = blockIdx.y * nry, oc0 = blockIdx.z * ncc;
+    const int ncol = min(ncc, g.out_cols - oc0), nrow = min(nry, g.out_rows - oy0), nimg = min(STAGE_IMGS, cnt - n0);
+    const int wc = g.block * ncol, per_img = g.block * nrow * wc;       // bytes of one source-row piece, of all block * nrow pieces of an image (<= pitch)
+    const size_t src0 = (size_t)(g.row0 + g.block * oy0) * g.src_cols + g.col0 + g.block * oc0;
+    for (int i = tid; i < nimg * per_img; i += STAGE_THREADS) {
+        const int img = i / per_img, rem = i - img * per_img, r = rem / wc, x = rem - r * wc;
+        st_lds[img * pitch + rem] = raw[(size_t)(n0 + img) * g.S + src0 + (size_t)r * g.src_cols + x];
+    }
+    __syncthreads();
+    for (int i = tid; i < nrow * ncol * STAGE_IMGS; i += STAGE_THREADS) {
+        const int img = i & (STAGE_IMGS - 1), q = i / STAGE_IMGS, oyl = q / ncol, oc = q - oyl * ncol;
+        if (img >= nimg) continue;
+        const uint8_t* p = st_lds + img * pitch + oyl * g.block * wc + oc * g.block;
+        unsigned sum = 0;
+        for (int r = 0; r < g.block; ++r) for (int dx = 0; dx < g.block; ++dx) sum += p[r * wc + dx];
+        codes[(size_t)((oy0 + oyl) * g.out_cols + oc0 + oc) * ld + n0 + img] = (uint16_t)sum;     // <= 255 * 64
+    }
+}
+int launch_stage_codes(tnml_ctx* c, const uint8_t* raw, const StageGeom& g, int cnt, int ld, uint16_t* codes) {
+    if (cnt < 1 || cnt > ld) return tnml_fail(c, "input map staging: %d images in rows of %d", cnt, ld);
+    if (g.block < 1 || g.block > 8 || g.row0 < 0 || g.col0 < 0 || g.out_rows < 1 || g.out_cols < 1 || g.src_cols < g.col0 + (int64_t)g.block * g.out_cols ||
+        (int64_t)g.S < (g.row0 + (int64_t)g.block * g.out_rows) * g.src_cols)
+        return tnml_fail(c, "input map staging: a block leaves the source image");
+    const StageLaunch s = stage_shape(g);
+    const dim3 grid((cnt + STAGE_IMGS - 1) / STAGE_IMGS, (g.out_rows + s.nry - 1) / s.nry, (g.out_cols + s.ncc - 1) / s.ncc);
+    if (grid.y > 65535 || grid.z > 65535) return tnml_fail(c, "input map staging: %d x %d sites are too many", g.out_rows, g.out_cols);
+    hipLaunchKernelGGL(k_stage_codes, grid, dim3(STAGE_THREADS), (size_t)STAGE_IMGS * s.pitch, c->stream, raw, g, s.ncc, s.nry, s.pitch, cnt, ld, codes);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+// block sums -> stored features (tnml_set_data_u8 under a map): one thread per (site, image), reads and writes along the image index
+template <typename TE>
+__global__ void k_codes_phi(const uint16_t* __restrict__ codes, const TE* __restrict__ tab, int N, int NT, int NTp, TE* __restrict__ phi) {
+    const size_t total = (size_t)N * NTp;
+    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const size_t j = idx / NTp; const int n = (int)(idx - j * NTp);
+        TE f0 = 0, f1 = 0;
+        if (n < NT) { const unsigned code = codes[idx]; f0 = tab[2 * code]; f1 = tab[2 * code + 1]; }
+        phi[(j * 2 + 0) * NTp + n] = f0;
+        phi[(j * 2 + 1) * NTp + n] = f1;
+    }
+}
+int launch_codes_phi(tnml_ctx* c, const uint16_t* codes, const void* tab, int N, int NT, int NTp, void* phi) {
+    const size_t total = (size_t)N * NTp;
+    const int grid = (int)std::min<size_t>((total + 255) / 256, 4096);
+    if (c->env64()) hipLaunchKernelGGL(k_codes_phi<double>, dim3(grid), dim3(256), 0, c->stream, codes, (const double*)tab, N, NT, NTp, (double*)phi);
+    else            hipLaunchKernelGGL(k_codes_phi<float>, dim3(grid), dim3(256), 0, c->stream, codes, (const float*)tab, N, NT, NTp, (float*)phi);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+
 int launch_chain_stage(tnml_ctx* c, const uint8_t* pix, const double* phi, int N, int cnt, int ld, uint8_t* xT, double* phiT) {
     ProfScope ps(c, KC_PACK);
     const size_t total = (size_t)N * cnt * (pix ? 1 : 2);
@@ -220,18 +303,27 @@ int launch_chain(tnml_ctx* c, ChainArgs a, int maxbond, int T, double* park_ws, 
     if (!park_lds && (size_t)grid * a.mcap * T > park_elems) return tnml_fail(c, "chain kernel: scratch of %zu doubles too small for %d tiles of %d x %d", park_elems, grid, a.mcap, T);
     a.park = park_lds ? nullptr : park_ws;
     const size_t lds = (park_lds ? 3 : 2) * tile;
-    if (!c->attr_chain) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain<1>), hipFuncAttributeMaxDynamicSharedMemorySize, TNML_CHAIN_LDS) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain<2>), hipFuncAttributeMaxDynamicSharedMemorySize, TNML_CHAIN_LDS) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain<4>), hipFuncAttributeMaxDynamicSharedMemorySize, TNML_CHAIN_LDS) != hipSuccess)
-            return tnml_fail(c, "chain kernel: hipFuncSetAttribute failed");
-        c->attr_chain = true;
+    const bool codes = a.codeT != nullptr;
+    if (codes ? !c->attr_chain_codes : !c->attr_chain) {
+        const void* f[3];
+        if (codes) { f[0] = reinterpret_cast<const void*>(k_chain<1, 1>); f[1] = reinterpret_cast<const void*>(k_chain<2, 1>); f[2] = reinterpret_cast<const void*>(k_chain<4, 1>); }
+        else       { f[0] = reinterpret_cast<const void*>(k_chain<1, 0>); f[1] = reinterpret_cast<const void*>(k_chain<2, 0>); f[2] = reinterpret_cast<const void*>(k_chain<4, 0>); }
+        for (const void* fn : f)
+            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, TNML_CHAIN_LDS) != hipSuccess) return tnml_fail(c, "chain kernel: hipFuncSetAttribute failed");
+        (codes ? c->attr_chain_codes : c->attr_chain) = true;
     }
+    if (codes && !a.table) return tnml_fail(c, "chain kernel: block sums without a table");
     ProfScope ps(c, KC_CHAIN);
-    if (T == 64)      hipLaunchKernelGGL(k_chain<4>, dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
-    else if (T == 32) hipLaunchKernelGGL(k_chain<2>, dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
-    else if (T == 16) hipLaunchKernelGGL(k_chain<1>, dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
-    else return tnml_fail(c, "chain kernel: tile width %d", T);
+    if (T != 64 && T != 32 && T != 16) return tnml_fail(c, "chain kernel: tile width %d", T);
+    if (codes) {
+        if (T == 64)      hipLaunchKernelGGL((k_chain<4, 1>), dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
+        else if (T == 32) hipLaunchKernelGGL((k_chain<2, 1>), dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
+        else              hipLaunchKernelGGL((k_chain<1, 1>), dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
+    } else {
+        if (T == 64)      hipLaunchKernelGGL((k_chain<4, 0>), dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
+        else if (T == 32) hipLaunchKernelGGL((k_chain<2, 0>), dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
+        else              hipLaunchKernelGGL((k_chain<1, 0>), dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
+    }
     HIPCK(c, hipGetLastError());
     return 0;
 }

@@ -600,10 +600,86 @@ int tnml_shift_skip_stats(tnml_ctx* c, int site, int64_t* groups, int64_t* skipp
     if (skipped) *skipped = c->zs_groups[site - 1];
     return 0;
 }
+// ---- input map (tnml.h): geometry + table; consulted by tnml_set_data_u8 / tnml_predict_u8 when bytes arrive -------------------------
+static StageGeom stage_geom(const tnml_ctx* c) {
+    const tnml_input_map& m = c->im;
+    return StageGeom{m.src_rows * m.src_cols, m.src_cols, m.block, m.row0, m.col0, m.out_rows, m.out_cols};
+}
+// the workspace of tnml_predict_u8 under a map follows the map: released here, re-made by the next such call
+static void predict_release_map(tnml_ctx* c) {
+    void** slots[] = {(void**)&c->pk_mraw, (void**)&c->pk_codes, (void**)&c->pk_mtab};
+    for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    c->bytes -= c->pk_map_bytes; c->pk_bytes -= c->pk_map_bytes;
+    c->pk_map_bytes = 0;
+}
+int tnml_set_input_map(tnml_ctx* c, const tnml_input_map* m) {
+    if (!c) return tnml_fail(c, "tnml_set_input_map: null argument");
+    TCK(ho_locked(c, "tnml_set_input_map"));
+    if (c->pend_count > 0) return tnml_fail(c, "tnml_set_input_map: a bond update is in flight (tnml_bond_update_end first)");
+    if (m) {
+        if (m->block < 1 || m->block > 8) return tnml_fail(c, "tnml_set_input_map: block = %d, must be 1..8", m->block);
+        if (m->ncodes != 255 * m->block * m->block + 1) return tnml_fail(c, "tnml_set_input_map: ncodes = %d, must be 255 block^2 + 1 = %d", m->ncodes, 255 * m->block * m->block + 1);
+        if (m->src_rows < 1 || m->src_cols < 1 || (int64_t)m->src_rows * m->src_cols > (int64_t)1 << 30)
+            return tnml_fail(c, "tnml_set_input_map: src_rows x src_cols = %d x %d, must be at least 1 x 1 and at most 2^30 bytes", m->src_rows, m->src_cols);
+        if (m->out_rows < 1 || m->out_cols < 1 || (int64_t)m->out_rows * m->out_cols != c->N)
+            return tnml_fail(c, "tnml_set_input_map: out_rows * out_cols = %d * %d, must be N = %d", m->out_rows, m->out_cols, c->N);
+        if (m->row0 < 0 || m->row0 + (int64_t)m->block * m->out_rows > m->src_rows)
+            return tnml_fail(c, "tnml_set_input_map: row0 = %d: blocks of %d rows from there leave the %d source rows", m->row0, m->block, m->src_rows);
+        if (m->col0 < 0 || m->col0 + (int64_t)m->block * m->out_cols > m->src_cols)
+            return tnml_fail(c, "tnml_set_input_map: col0 = %d: blocks of %d columns from there leave the %d source columns", m->col0, m->block, m->src_cols);
+        if (!m->table) return tnml_fail(c, "tnml_set_input_map: table is NULL");
+        for (int k = 0; k < 2 * m->ncodes; ++k)
+            if (!std::isfinite(m->table[k])) return tnml_fail(c, "tnml_set_input_map: table[%d][%d] is not finite", k / 2, k % 2);
+    }
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if (c->pk_map_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); predict_release_map(c); }
+    if (!m) { c->im_set = false; c->im = tnml_input_map{}; c->im_table.clear(); return 0; }
+    c->im_table.assign(m->table, m->table + (size_t)2 * m->ncodes);
+    c->im = *m; c->im.table = nullptr;
+    c->im_set = true;
+    return 0;
+}
+int tnml_get_input_map(tnml_ctx* c, tnml_input_map* out) {
+    if (!c || !out) return tnml_fail(c, "tnml_get_input_map: null argument");
+    *out = c->im_set ? c->im : tnml_input_map{};
+    out->table = nullptr;
+    return 0;
+}
+// tnml_set_data_u8 under a map (k_features_codes): raw -> block sums (k_stage_codes with ld = NTp) -> phi [N][2][NTp] through the table in the
+// context's storage type; the three temporaries are freed before the call returns
+static int features_codes(tnml_ctx* c, const uint8_t* pixels) {
+    const StageGeom g = stage_geom(c);
+    const size_t nraw = (size_t)c->NT * g.S, ncode = (size_t)c->N * c->NTp * sizeof(uint16_t), ntab = c->im_table.size();
+    std::vector<float> tab32;
+    if (!c->env64()) { tab32.resize(ntab); for (size_t k = 0; k < ntab; ++k) tab32[k] = (float)c->im_table[k]; }   // rounded once, as tnml_set_data_phi rounds phi
+    const size_t tabb = ntab * (c->env64() ? sizeof(double) : sizeof(float));
+    uint8_t* d_raw = nullptr; uint16_t* d_codes = nullptr; void* d_tab = nullptr;
+    int rc = 0;
+    auto hip = [&](hipError_t e, const char* what) { if (!rc && e != hipSuccess) rc = tnml_fail(c, "tnml_set_data_u8: %s failed: %s", what, hipGetErrorString(e)); };
+    hip(hipMalloc((void**)&d_raw, nraw), "hipMalloc of the raw bytes");
+    if (!rc) hip(hipMalloc((void**)&d_codes, ncode), "hipMalloc of the block sums");
+    if (!rc) hip(hipMalloc(&d_tab, tabb), "hipMalloc of the table");
+    if (!rc) hip(hipMemcpyAsync(d_raw, pixels, nraw, hipMemcpyHostToDevice, c->stream), "copy of the raw bytes");
+    if (!rc) hip(hipMemcpyAsync(d_tab, c->env64() ? (const void*)c->im_table.data() : (const void*)tab32.data(), tabb, hipMemcpyHostToDevice, c->stream), "copy of the table");
+    if (!rc) {
+        ProfScope ps(c, KC_PACK);
+        rc = launch_stage_codes(c, d_raw, g, c->NT, c->NTp, d_codes);
+        if (!rc) rc = launch_codes_phi(c, d_codes, d_tab, c->N, c->NT, c->NTp, c->phi);
+    }
+    hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+    (void)hipFree(d_raw); (void)hipFree(d_codes); (void)hipFree(d_tab);
+    return rc;
+}
 int tnml_set_data_u8(tnml_ctx* c, const uint8_t* pixels, const int32_t* labels) {
     TCK(ho_locked(c, "tnml_set_data_u8", true));
     HIPCK(c, hipSetDevice(c->cfg.device));
     TCK(set_labels(c, labels));
+    if (c->im_set) {
+        TCK(features_codes(c, pixels));
+        TCK(shift_order_build(c));
+        c->data_set = true; c->currb = -1; c->p_valid = false; c->sweep_start = false;
+        return 0;
+    }
     uint8_t* d_pix = nullptr;
     const size_t nb = (size_t)c->NT * c->N;
     HIPCK(c, hipMalloc((void**)&d_pix, nb));
@@ -1048,6 +1124,7 @@ int tnml_classify(tnml_ctx* c, double* weights, int32_t* pred, int64_t count[TNM
 static void predict_release(tnml_ctx* c) {
     void** slots[] = {(void**)&c->pk_tab, (void**)&c->pk_w, (void**)&c->pk_pred, (void**)&c->pk_park, (void**)&c->pk_raw8, (void**)&c->pk_x8, (void**)&c->pk_rawphi, (void**)&c->pk_xphi};
     for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    predict_release_map(c);
     c->bytes -= c->pk_bytes;
     c->pk_bytes = 0; c->pk_cap = 0; c->pk_park_elems = 0;
 }
@@ -1070,6 +1147,19 @@ static int predict_workspace(tnml_ctx* c, bool bytes_form) {
         c->pk_cap = cap;
     }
     int rc = 0;
+    if (bytes_form && c->im_set) {                        // S C + 2 N C + 16 ncodes: bytes as given, block sums site-first, the fp64 table
+        if (c->pk_codes) return 0;
+        const size_t S = (size_t)c->im.src_rows * c->im.src_cols, tabb = c->im_table.size() * sizeof(double);
+        const int64_t before = c->pk_bytes;
+        rc = predict_alloc(c, (void**)&c->pk_mraw, S * cap);
+        if (!rc) rc = predict_alloc(c, (void**)&c->pk_codes, (size_t)cap * c->N * sizeof(uint16_t));
+        if (!rc) rc = predict_alloc(c, (void**)&c->pk_mtab, tabb);
+        c->pk_map_bytes = c->pk_bytes - before;
+        if (!rc && hipMemcpyAsync(c->pk_mtab, c->im_table.data(), tabb, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict_u8: copy of the input map's table failed");
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict_u8: hipStreamSynchronize failed");
+        if (rc) predict_release(c);
+        return rc;
+    }
     if (bytes_form && !c->pk_x8) { rc = predict_alloc(c, (void**)&c->pk_raw8, (size_t)cap * c->N); if (!rc) rc = predict_alloc(c, (void**)&c->pk_x8, (size_t)cap * c->N); }
     if (!bytes_form && !c->pk_xphi) { rc = predict_alloc(c, (void**)&c->pk_rawphi, (size_t)2 * cap * c->N * sizeof(double)); if (!rc) rc = predict_alloc(c, (void**)&c->pk_xphi, (size_t)2 * cap * c->N * sizeof(double)); }
     if (rc) predict_release(c);
@@ -1095,9 +1185,24 @@ static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* 
     for (int j = 1; j <= c->N; ++j) tab[j - 1] = ChainSite{c->W[j].a, c->W[j].ml, c->W[j].mr};
     HIPCK(c, hipMemcpyAsync(c->pk_tab, tab.data(), sizeof(ChainSite) * c->N, hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (tab leaves scope with this call)
-    const size_t per_img = (size_t)c->N * (bytes_form ? 1 : 2 * sizeof(double));
+    const bool mapped = bytes_form && c->im_set;                // the input map: S bytes per image -> block sums -> table look-ups inside the chain kernel
+    const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
+    const size_t per_img = mapped ? (size_t)sg.S : (size_t)c->N * (bytes_form ? 1 : 2 * sizeof(double));
     for (int64_t off = 0; off < n; off += c->predict_chunk) {
         const int cnt = (int)std::min<int64_t>(c->predict_chunk, n - off);
+        if (mapped) {
+            HIPCK(c, hipMemcpyAsync(c->pk_mraw, pixels + (size_t)off * per_img, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+            { ProfScope ps(c, KC_PACK); TCK(launch_stage_codes(c, c->pk_mraw, sg, cnt, c->pk_cap, c->pk_codes)); }
+            ChainArgs a;
+            a.sites = c->pk_tab; a.N = c->N; a.cs = cs; a.nl = nl; a.single = c->single() ? 1 : 0;
+            a.xT = nullptr; a.phiT = nullptr; a.codeT = c->pk_codes; a.table = c->pk_mtab;
+            a.ld = c->pk_cap; a.cnt = cnt; a.wout = c->pk_w; a.pred = c->pk_pred;
+            TCK(launch_chain(c, a, maxbond, chain_tile(c, maxbond, cnt), c->pk_park, c->pk_park_elems));
+            if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->pk_w, sizeof(double) * (size_t)cnt * nl, hipMemcpyDeviceToHost, c->stream));
+            if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->pk_pred, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+            SYNCK(c, c->stream);
+            continue;
+        }
         if (bytes_form) HIPCK(c, hipMemcpyAsync(c->pk_raw8, pixels + (size_t)off * c->N, per_img * cnt, hipMemcpyHostToDevice, c->stream));
         else            HIPCK(c, hipMemcpyAsync(c->pk_rawphi, phi + (size_t)off * c->N * 2, per_img * cnt, hipMemcpyHostToDevice, c->stream));
         TCK(launch_chain_stage(c, bytes_form ? c->pk_raw8 : nullptr, bytes_form ? nullptr : c->pk_rawphi, c->N, cnt, c->pk_cap, c->pk_x8, c->pk_xphi));

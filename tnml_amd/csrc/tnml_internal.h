@@ -292,7 +292,7 @@ struct tnml_ctx {
     // streamed inference (tnml_predict_u8 / tnml_predict_phi, kernels_chain.hip): images the context does not hold, predict_chunk at a time
     int predict_chunk = TNML_PREDICT_CHUNK_DEFAULT;        // option "predict_chunk": images staged, launched (one k_chain launch) and copied back per trip of the host loop
     int predict_tile = 0;            // test knob (option "predict_tile"): images per workgroup of k_chain, 16 / 32 / 64 (capped by the LDS budget); 0: by bond dimension and image count
-    bool attr_chain = false;
+    bool attr_chain = false, attr_chain_codes = false;
     // its workspace, allocated by the first predict call (counted in `bytes`, freed by tnml_destroy); pk_cap = predict_chunk rounded up to 64 when it was sized
     int pk_cap = 0; int64_t pk_bytes = 0;
     struct ChainSite* pk_tab = nullptr;   // [N] per-site table (ml, mr, address)
@@ -300,6 +300,15 @@ struct tnml_ctx {
     double* pk_park = nullptr; size_t pk_park_elems = 0;   // [pk_cap / T][ru16(m)][T]: the parked right-chain vectors of the workgroups (when three tiles do not fit the LDS)
     uint8_t *pk_raw8 = nullptr, *pk_x8 = nullptr;     // bytes of a chunk as given [pk_cap][N] and site-first [N][pk_cap] (first tnml_predict_u8)
     double *pk_rawphi = nullptr, *pk_xphi = nullptr;  // features of a chunk as given [pk_cap][N][2] and site-first [N][2][pk_cap] (first tnml_predict_phi)
+    // input map (tnml_set_input_map): geometry + host copy of the fp64 table; consulted by tnml_set_data_u8 / tnml_predict_u8 only
+    bool im_set = false;
+    tnml_input_map im = {};          // geometry (table = nullptr)
+    std::vector<double> im_table;    // [ncodes][2]
+    // workspace of tnml_predict_u8 under a map (first such call; released by every tnml_set_input_map call)
+    uint8_t* pk_mraw = nullptr;      // bytes of a chunk as given [pk_cap][S]
+    uint16_t* pk_codes = nullptr;    // block sums, site-first [N][pk_cap]
+    double* pk_mtab = nullptr;       // the fp64 table [ncodes][2]
+    int64_t pk_map_bytes = 0;
 
     // profiling
     bool prof = false;
@@ -532,7 +541,15 @@ struct ChainArgs {
     int ld, cnt;                       // row length of the staged images, images of this chunk
     double* wout; int* pred;           // [cnt][nl], [cnt]
     int mcap = 0; double* park = nullptr;   // set by launch_chain
+    const uint16_t* codeT = nullptr;   // third source (input map): block sums, site-first [N][ld], with
+    const double* table = nullptr;     // the features [ncodes][2] of every block sum; both set -> the k_chain instantiations of this source
 };
+// geometry of an input map as the staging kernel takes it (validated by tnml_set_input_map: every block lies inside the source image)
+struct StageGeom { int S, src_cols, block, row0, col0, out_rows, out_cols; };
+// raw bytes [cnt][S] -> block sums site-first codes[N][ld], images fastest (k_stage_codes); images >= cnt are not written.  No ProfScope of its own.
+int launch_stage_codes(tnml_ctx* c, const uint8_t* raw, const StageGeom& g, int cnt, int ld, uint16_t* codes);
+// block sums codes[N][NTp] -> stored features phi[N][2][NTp] in the context's storage type through tab ([ncodes][2] of that type); padding images get (0, 0)
+int launch_codes_phi(tnml_ctx* c, const uint16_t* codes, const void* tab, int N, int NT, int NTp, void* phi);
 int launch_chain_stage(tnml_ctx* c, const uint8_t* pix, const double* phi, int N, int cnt, int ld, uint8_t* xT, double* phiT);   // exactly one of pix [cnt][N] / phi [cnt][N][2]
 int chain_tile(tnml_ctx* c, int maxbond, int cnt);
 int launch_chain(tnml_ctx* c, ChainArgs a, int maxbond, int T, double* park_ws, size_t park_elems);

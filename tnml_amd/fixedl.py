@@ -25,8 +25,10 @@ class TrainStates:
     """Training set + environments + W replica of one rank (TrainStates + MPS W of fixedL.cc)."""
 
     def __init__(self, labels, N, maxm, pixels=None, phi=None, device=0, rank=0, nranks=1, NT_total=None, dtype="f64",
-                 single_label=None, svd_backend=0, no_data=False):
-        """no_data: a context for the MPS algebra alone (place / set_sum / compress / overlap): `labels` only sizes it (one entry will do);
+                 single_label=None, svd_backend=0, no_data=False, input_map=None):
+        """input_map: an InputMap (tnml_amd/input_map.py), set before the data: `pixels` is then [NT, input_map.S] raw bytes and the
+        device does block sums, table look-up and transpose (tnml_set_input_map);
+        no_data: a context for the MPS algebra alone (place / set_sum / compress / overlap): `labels` only sizes it (one entry will do);
         single_label = L selects the per-label variant (single.cc): plain weight MPS, target y_n = [l_n == L];
         svd_backend = 1: the split on stock rocsolver_dsyevd (TNML_SVD_ROCSOLVER) instead of the in-house eigensolver"""
         self._L = _lib.load()
@@ -48,9 +50,13 @@ class TrainStates:
         if rc != 0:
             self._h = C.c_void_p()
             raise TnmlError(self._L.tnml_last_error(None).decode())
+        self._bytes_per_image = self.N
+        if input_map is not None:
+            self.set_input_map(input_map)
         if pixels is not None:
             px = np.ascontiguousarray(pixels, dtype=np.uint8)
-            assert px.shape == (self.NT, self.N)
+            if px.shape != (self.NT, self._bytes_per_image):
+                raise ValueError("pixels must have shape %s, got %s" % ((self.NT, self._bytes_per_image), px.shape))
             self._ck(self._L.tnml_set_data_u8(self._h, px.ctypes.data_as(C.POINTER(C.c_uint8)),
                                               labels.ctypes.data_as(C.POINTER(C.c_int32))))
         elif phi is not None:
@@ -200,14 +206,36 @@ class TrainStates:
                                        cnt.ctypes.data_as(C.POINTER(C.c_int64)), ninc.ctypes.data_as(C.POINTER(C.c_int64))))
         return w, pred, cnt, ninc
 
+    def set_input_map(self, m):
+        """tnml_set_input_map: from now on set-data and predict calls that take bytes read m.S bytes per image and look the features of
+        every block sum up in m.table; None: back to the built-in map.  Stored features are not touched."""
+        if m is None:
+            self._ck(self._L.tnml_set_input_map(self._h, None))
+            self._bytes_per_image = self.N
+            return
+        table = np.ascontiguousarray(m.table, dtype=np.float64)
+        st = _lib.InputMapStruct(m.src_rows, m.src_cols, m.block, m.row0, m.col0, m.out_rows, m.out_cols, int(table.shape[0]), _lib.dptr(table))
+        self._ck(self._L.tnml_set_input_map(self._h, C.byref(st)))
+        self._bytes_per_image = int(m.src_rows) * int(m.src_cols)
+
+    def input_map(self):
+        """tnml_get_input_map: the geometry of the map in force as a dict, or None without a map"""
+        st = _lib.InputMapStruct()
+        self._ck(self._L.tnml_get_input_map(self._h, C.byref(st)))
+        if st.block == 0:
+            return None
+        return {k: getattr(st, k) for k in ("src_rows", "src_cols", "block", "row0", "col0", "out_rows", "out_cols", "ncodes")}
+
     def predict(self, pixels=None, phi=None):
-        """streamed inference on images this context does not hold (tnml_predict_u8 / tnml_predict_phi): pixels[n, N] bytes or
-        phi[n, N, 2] features -> (weights[n, nl], pred[n]); pred is argmax_l |W_l| (per-label variant: [f > 1/2]).  Reads W only."""
+        """streamed inference on images this context does not hold (tnml_predict_u8 / tnml_predict_phi): pixels[n, N] bytes
+        (under an input map: [n, S] raw bytes) or phi[n, N, 2] features -> (weights[n, nl], pred[n]); pred is argmax_l |W_l|
+        (per-label variant: [f > 1/2]).  Reads W only."""
         if (pixels is None) == (phi is None):
             raise ValueError("need exactly one of pixels or phi")
         if pixels is not None:
             x = np.ascontiguousarray(pixels, dtype=np.uint8)
-            assert x.ndim == 2 and x.shape[1] == self.N, x.shape
+            if x.ndim != 2 or x.shape[1] != self._bytes_per_image:
+                raise ValueError("pixels must have shape [n, %d], got %s" % (self._bytes_per_image, x.shape))
         else:
             x = np.ascontiguousarray(phi, dtype=np.float64)
             assert x.ndim == 3 and x.shape[1:] == (self.N, 2), x.shape

@@ -11,6 +11,7 @@
 
 #include "../../include/tnml.h"
 #include "host_mps.h"
+#include "init_w.h"
 #include "mnist_idx.h"
 
 namespace tnmlh {
@@ -53,18 +54,52 @@ inline bool parse_dtype(const std::string& precision, bool allow_bf16, int* dtyp
     return true;
 }
 
-// read_mnist, then block-mean down-sampling to imglen x imglen when imglen > 0
-inline Dataset read_images(const std::string& datadir, bool train, long cap, long imglen) {
+// read_mnist, then block-mean down-sampling to imglen x imglen when imglen > 0; raw (nullable) receives the images as the file has them
+inline Dataset read_images(const std::string& datadir, bool train, long cap, long imglen, Dataset* raw = nullptr) {
     Dataset d = read_mnist(datadir, train, cap);
+    if (raw) *raw = d;
     if (imglen > 0) reduce(d, (int)imglen);
     return d;
 }
 // the t10k images as the held-out set of a training run, read as its training images were; false after printing a mismatch
-inline bool read_heldout(const std::string& datadir, long Ntest, long imglen, const Dataset& train, Dataset* test) {
-    *test = read_images(datadir, false, Ntest, imglen);
+inline bool read_heldout(const std::string& datadir, long Ntest, long imglen, const Dataset& train, Dataset* test, Dataset* raw = nullptr) {
+    *test = read_images(datadir, false, Ntest, imglen, raw);
     if (test->npix() == train.npix()) return true;
     std::printf("heldout: the t10k images have %d pixels, the training images %d\n", test->npix(), train.npix());
     return false;
+}
+// The key `input_map` (yes | no, default no) of the drivers: the images go to the device as the bytes of the idx file and the device does
+// reduce(), the feature map and the transpose (tnml_set_input_map).  The map of a driver's `feature` / `feature_scale` / `imglen` for raw
+// images `raw`: reduce()'s geometry (bsize = side / imglen, blocks from side % bsize) and its refusals in its own words; imglen <= 0
+// keeps the image, of any shape, with block 1.
+struct DriverInputMap {
+    tnml_input_map geo{};
+    std::vector<double> table;
+    std::string feature;
+    void print() const {
+        std::printf("Input map: %d x %d bytes -> %d x %d sites (%d x %d block sums from (%d, %d)), feature = %s, %d codes\n", geo.src_rows, geo.src_cols,
+                    geo.out_rows, geo.out_cols, geo.block, geo.block, geo.row0, geo.col0, feature.c_str(), geo.ncodes);
+    }
+    void set(tnml_ctx* ctx) {
+        tnml_input_map m = geo; m.table = table.data();
+        if (tnml_set_input_map(ctx, &m) != 0) die(ctx, "tnml_set_input_map");
+    }
+};
+inline DriverInputMap make_input_map(const Dataset& raw, long imglen, bool normal, double feature_scale) {
+    DriverInputMap im;
+    tnml_input_map& g = im.geo;
+    g.src_rows = raw.rows; g.src_cols = raw.cols; g.block = 1; g.row0 = g.col0 = 0; g.out_rows = raw.rows; g.out_cols = raw.cols;
+    if (imglen > 0) {
+        if (raw.rows != raw.cols) throw std::runtime_error("reduce: image is not square");
+        if (imglen > raw.rows) throw std::runtime_error("reduce: imglen must be between 1 and the image side");
+        if (imglen < raw.rows) { g.block = raw.rows / (int)imglen; g.row0 = g.col0 = raw.rows % g.block; g.out_rows = g.out_cols = (int)imglen; }
+    }
+    if (g.block > 8) throw std::runtime_error("input_map: imglen gives blocks of more than 8 x 8 pixels");
+    g.ncodes = 255 * g.block * g.block + 1;
+    im.table.resize((size_t)2 * g.ncodes);
+    feature_table(normal, feature_scale, g.block, im.table.data());
+    im.feature = normal ? "normal" : "series";
+    return im;
 }
 // the test drivers need a `sites` file of N sites of dimension 2 (fulltest.cc:34-41, util.h:68); false after printing why not
 inline bool sites_match(int N) {

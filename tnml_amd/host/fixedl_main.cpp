@@ -13,7 +13,8 @@
 // (a CSV line per bond update: cost, #correct, bond dimensions, truncation error, seconds), `heldout` (the t10k images, capped at `Ntest`
 // per label, follow the training as a held-out context: one "Held-out:" line per bond update), `mps_device` (auto | yes | no: the W0..W9 sum and
 // overlap(W,W) on the GPU -- tnml_mps_place / tnml_mps_compress / tnml_mps_overlap -- instead of the host's scalar SVD; auto = from a bond of
-// MPS_DEVICE_AUTO_BOND + 1 on), `sum_maxm` (a Maxm for that sum; the reference passes none).
+// MPS_DEVICE_AUTO_BOND + 1 on), `sum_maxm` (a Maxm for that sum; the reference passes none), `input_map` (yes | no, default no: the images reach
+// the device as the bytes of the idx file and the device does reduce(), the feature map and the transpose -- tnml_set_input_map; same log, same W).
 #include <array>
 #include <chrono>
 #include <condition_variable>
@@ -103,6 +104,7 @@ int main(int argc, const char* argv[]) {
         const long imglen = input.getInt("imglen", 0);                                   // extension: 0 = keep the file's size
         const double feature_scale = input.getReal("feature_scale", 1.);                 // extension
         const bool heldout = input.getYesNo("heldout", false);                          // extension: evaluate the t10k images after every bond update
+        const bool input_map = input.getYesNo("input_map", false);                      // extension: the images reach the device as the bytes of the idx file; the device reduces, maps and transposes (tnml_set_input_map)
         const long Ntest = input.getInt("Ntest", 50000);                                 // extension: per-label cap of the held-out set (as fulltest)
         const std::string mps_device = input.getString("mps_device", "auto");            // extension: auto | yes | no -- the W0..W9 sum and overlap(W,W) on the GPU
         if (mps_device != "auto" && mps_device != "yes" && mps_device != "no") { std::printf("mps_device must be auto, yes or no\n"); return 1; }
@@ -112,9 +114,10 @@ int main(int argc, const char* argv[]) {
         if (!parse_dtype(precision, true, &dtype)) return 1;
         if (method != "conj") { std::printf("method type \"%s\" not recognized\n", method.c_str()); return 1; }   // :505
 
-        Dataset train = read_images(datadir, true, Ntrain, imglen);                     // :613
+        Dataset train_raw, test_raw;                                                    // input_map = yes: the bytes of the idx files (the initial W is still built from the reduced copy)
+        Dataset train = read_images(datadir, true, Ntrain, imglen, input_map ? &train_raw : nullptr);   // :613
         Dataset test;                                                                   // the held-out set: read before any context exists
-        if (heldout && !read_heldout(datadir, Ntest, imglen, train, &test)) return 1;
+        if (heldout && !read_heldout(datadir, Ntest, imglen, train, &test, input_map ? &test_raw : nullptr)) return 1;
         std::printf("Training set consists of %d images:\n", train.size());
         for (int l = 0; l < 10; ++l) std::printf("  %d of label %d\n", train.counts[l], l);
         const int N = train.npix();                                                     // :615
@@ -254,10 +257,19 @@ int main(int argc, const char* argv[]) {
                         maxm, N, (long long)(hi[0] - lo[0]), ctx_maxm);
 
         std::vector<double> phi_all;
-        const bool use_u8 = !train.reduced() && feature_scale == 1.;
+        DriverInputMap im, im_test;
+        if (input_map) {
+            im = make_input_map(train_raw, imglen, false, feature_scale);
+            if (heldout) im_test = make_input_map(test_raw, imglen, false, feature_scale);
+            im.print();
+        }
+        const size_t S = input_map ? (size_t)train_raw.npix() : (size_t)N, St = input_map && heldout ? (size_t)test_raw.npix() : (size_t)N;   // bytes per image as handed over
+        const uint8_t* train_bytes = input_map ? train_raw.pixels.data() : train.pixels.data();
+        const uint8_t* test_bytes = input_map ? test_raw.pixels.data() : test.pixels.data();
+        const bool use_u8 = input_map || (!train.reduced() && feature_scale == 1.);
         if (!use_u8) phi_all = all_features(train, false, feature_scale);
         std::vector<double> phi_test;
-        const bool test_u8 = !test.reduced() && feature_scale == 1.;
+        const bool test_u8 = input_map || (!test.reduced() && feature_scale == 1.);
         if (heldout && !test_u8) phi_test = all_features(test, false, feature_scale);
         std::vector<tnml_heldout_report> ho_rep(nranks);
         // rank 0 prints the sums of the ranks' held-out shards (local values: no collective)
@@ -280,7 +292,8 @@ int main(int argc, const char* argv[]) {
             if (tnml_create(&ctx, &cfg) != 0) die(nullptr, "tnml_create");
             if (env_budget_gb > 0.) CK(ctx, tnml_set_option(ctx, "env_budget_mb", (int)(env_budget_gb * 1024.)));
             if (spec_predict) CK(ctx, tnml_set_option(ctx, "spec_predict", 1));
-            if (use_u8) CK(ctx, tnml_set_data_u8(ctx, train.pixels.data() + (size_t)lo[r] * N, train.labels.data() + lo[r]));   // TState ctor, :644-653
+            if (input_map) im.set(ctx);
+            if (use_u8) CK(ctx, tnml_set_data_u8(ctx, train_bytes + (size_t)lo[r] * S, train.labels.data() + lo[r]));   // TState ctor, :644-653
             else        CK(ctx, tnml_set_data_phi(ctx, phi_all.data() + (size_t)lo[r] * N * 2, train.labels.data() + lo[r]));
             if (nranks > 1 && !share_device && !oneshot) CK(ctx, tnml_comm_init(ctx, uid));    // RCCL over xGMI, one rank per GPU
             if (nranks > 1 && (share_device || oneshot)) {                                  // in-process communicators: staging buffer on one GPU, or one-shot peer writes
@@ -295,7 +308,8 @@ int main(int argc, const char* argv[]) {
                 if (thi[r] == tlo[r]) die(nullptr, "heldout: a rank without held-out images (more GPUs than t10k images)");
                 const tnml_config hc = heldout_config(r, ctx_maxm);
                 if (tnml_create(&hctx, &hc) != 0) die(nullptr, "tnml_create (heldout)");
-                if (test_u8) CK(hctx, tnml_set_data_u8(hctx, test.pixels.data() + (size_t)tlo[r] * N, test.labels.data() + tlo[r]));
+                if (input_map) im_test.set(hctx);
+                if (test_u8) CK(hctx, tnml_set_data_u8(hctx, test_bytes + (size_t)tlo[r] * St, test.labels.data() + tlo[r]));
                 else         CK(hctx, tnml_set_data_phi(hctx, phi_test.data() + (size_t)tlo[r] * N * 2, test.labels.data() + tlo[r]));
             }
             if (nranks > 1) { int cnt = 0; CK(ctx, tnml_replica_check(ctx, &cnt)); if (root) std::printf("%s communicator of %d ranks, W replicas identical\n", oneshot ? "one-shot peer-write" : (share_device ? "in-process" : "RCCL"), cnt); }

@@ -7,7 +7,8 @@
 // (f64 | mixed | f32), `Ntest` (per-label cap; the reference takes the whole test set), `imglen` and
 // `feature_scale` as in the fixedL driver (they must match the values W was trained with); `predict` (yes | no,
 // default no): a data-less context sized by W alone, the test set streamed through tnml_predict_u8 / tnml_predict_phi
-// in chunks of `predict_chunk` images (0: the library's default) and counted on the host.
+// in chunks of `predict_chunk` images (0: the library's default) and counted on the host; `input_map` (yes | no, default no): the
+// images reach the device as the bytes of the idx file, the device does reduce(), the feature map and the transpose (tnml_set_input_map).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -34,11 +35,13 @@ int main(int argc, const char* argv[]) {
         const double feature_scale = input.getReal("feature_scale", 1.);
         const bool predict = input.getYesNo("predict", false);
         const long predict_chunk = input.getInt("predict_chunk", 0);
+        const bool input_map = input.getYesNo("input_map", false);
         int dtype;
         if (!parse_dtype(precision, false, &dtype)) return 1;
 
         std::printf("Labels: 0 1 2 3 4 5 6 7 8 9\n");                                   // :28
-        Dataset test = read_images(datadir, false, Ntest, imglen);                      // :30
+        Dataset raw;                                                                    // input_map = yes: the bytes of the idx file
+        Dataset test = read_images(datadir, false, Ntest, imglen, input_map ? &raw : nullptr);   // :30
         const int N = test.npix();
         if (!sites_match(N)) return 1;                                                  // :34-41
         bool normal;
@@ -62,11 +65,13 @@ int main(int argc, const char* argv[]) {
         cfg.maxm = max_link_dim(psi); cfg.dtype = dtype; cfg.svd_backend = TNML_SVD_SYEVD;
         tnml_ctx* ctx = nullptr;
         if (tnml_create(&ctx, &cfg)) die(nullptr, "tnml_create");
-        const bool bytes_in = !normal && !test.reduced() && feature_scale == 1.;        // phi = [1, x/4], x = (byte/255)/255
+        const bool bytes_in = input_map || (!normal && !test.reduced() && feature_scale == 1.);   // the input map, or the built-in phi = [1, x/4], x = (byte/255)/255
+        if (input_map) { DriverInputMap im = make_input_map(raw, imglen, normal, feature_scale); im.print(); im.set(ctx); }
+        const uint8_t* bytes = input_map ? raw.pixels.data() : test.pixels.data();
         std::vector<double> phi;
         if (!bytes_in) phi = all_features(test, normal, feature_scale);                // fulltest.cc:57-70
         if (!predict) {
-            if (bytes_in) CK(ctx, tnml_set_data_u8(ctx, test.pixels.data(), test.labels.data()));
+            if (bytes_in) CK(ctx, tnml_set_data_u8(ctx, bytes, test.labels.data()));
             else CK(ctx, tnml_set_data_phi(ctx, phi.data(), test.labels.data()));
         }
         upload_mps(ctx, psi);
@@ -79,7 +84,7 @@ int main(int argc, const char* argv[]) {
             const int chunk = predict_chunk_option(ctx, predict_chunk);
             std::printf("Device path: streamed chain kernel (%s), %d images per chunk\n", bytes_in ? "tnml_predict_u8" : "tnml_predict_phi", chunk);
             std::vector<int32_t> pred(totNtest);
-            if (bytes_in) CK(ctx, tnml_predict_u8(ctx, totNtest, test.pixels.data(), nullptr, pred.data()));
+            if (bytes_in) CK(ctx, tnml_predict_u8(ctx, totNtest, bytes, nullptr, pred.data()));
             else CK(ctx, tnml_predict_phi(ctx, totNtest, phi.data(), nullptr, pred.data()));
             for (int i = 0; i < totNtest; ++i) { const int l = test.labels[i]; counts[l]++; if (pred[i] != l) ++ninc[l]; }
         }

@@ -43,6 +43,26 @@ int tnmlh_reduce(const unsigned char* pixels, int n, int side, int newlen, doubl
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
+// table[255 block^2 + 1][2] of an input map (tnml_set_input_map): the features of every block sum under `normal` / `scale` (init_w.h feature_table)
+int tnmlh_feature_table(int normal, double scale, int block, double* table) {
+    try { feature_table(normal != 0, scale, block, table); return 0; } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// the drivers' host feature path on n images of npix bytes: reduce() to imglen x imglen when imglen > 0 (square images), then init_w.h
+// all_features; out[n][sites][2], the layout of tnml_set_data_phi
+int tnmlh_features(const unsigned char* pixels, int n, int npix, int imglen, int normal, double scale, double* out) {
+    try {
+        Dataset d; d.rows = 1; d.cols = npix; d.pixels.assign(pixels, pixels + (size_t)n * npix); d.labels.assign(n, 0);
+        if (imglen > 0) {
+            int side = 0; while (side * side < npix) ++side;
+            if (side * side != npix) throw std::runtime_error("reduce: image is not square");
+            d.rows = d.cols = side;
+            reduce(d, imglen);
+        }
+        const std::vector<double> phi = all_features(d, normal != 0, scale);
+        std::memcpy(out, phi.data(), sizeof(double) * phi.size());
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
 // initial W from a dataset directory -> file `out` (TNMLW1); returns overlap(W,W) through *ovl
 int tnmlh_build_initial_w(const char* datadir, long nt_per_label, int ninitial, unsigned long long seed, const char* out, double* ovl, int* maxdim,
                           int imglen, double feature_scale) {

@@ -12,18 +12,31 @@
 
 namespace tnmlh {
 
-// phi(g,n) = pow((g/255.)/4., n-1) with g = byte/255. (mllib/mnist.h:495, fixedL.cc:637-642); `scale` multiplies the
-// second component (1 = the reference's double normalisation, 255 = the README's [1, x/4] -- SURVEY.md 9-Q1)
+// The two local features of a site whose pixel value is `value` (byte units; a block mean after reduce()).
+//   series: phi(g,n) = pow((g/255.)/4., n-1) with g = value/255. (mllib/mnist.h:495, fixedL.cc:637-642); `scale` multiplies the
+//           second component (1 = the reference's double normalisation, 255 = the README's [1, x/4] -- SURVEY.md 9-Q1)
+//   normal: fulltest.cc:57-66 with the same double normalisation, x = g/255 (scale is not used)
+// The one place these expressions live: the per-image feature functions and the table of an input map (feature_table) both call it.
+inline void feature_of_value(double value, bool normal, double scale, double out[2]) {
+    if (normal) { const double x = (value / 255.) / 255.; out[0] = std::cos(M_PI / 2. * x); out[1] = std::sin(M_PI / 2. * x); }
+    else { const double g = value / 255.; out[0] = 1.; out[1] = scale * ((g / 255.) / 4.); }
+}
 inline void features_series(const Dataset& d, int img, std::vector<double>& phi, double scale = 1.) {
     const int N = d.npix();
     phi.resize((size_t)N * 2);
-    for (int j = 0; j < N; ++j) { const double g = d.value(img, j) / 255.; phi[2 * j] = 1.; phi[2 * j + 1] = scale * ((g / 255.) / 4.); }
+    for (int j = 0; j < N; ++j) feature_of_value(d.value(img, j), false, scale, &phi[2 * j]);
 }
-// fulltest.cc:57-66 "normal" map with the same double normalisation: x = g/255
 inline void features_normal(const Dataset& d, int img, std::vector<double>& phi) {
     const int N = d.npix();
     phi.resize((size_t)N * 2);
-    for (int j = 0; j < N; ++j) { const double x = (d.value(img, j) / 255.) / 255.; phi[2 * j] = std::cos(M_PI / 2. * x); phi[2 * j + 1] = std::sin(M_PI / 2. * x); }
+    for (int j = 0; j < N; ++j) feature_of_value(d.value(img, j), true, 1., &phi[2 * j]);
+}
+// table[code][2] of a tnml_input_map for block x block sums: the features of the block mean code / block^2 -- the double that reduce()
+// (integer sum, one division) followed by the feature functions above produces; 255 block^2 + 1 rows
+inline void feature_table(bool normal, double scale, int block, double* table) {
+    if (block < 1 || block > 8) throw std::runtime_error("feature_table: block must be between 1 and 8");
+    const int ncodes = 255 * block * block + 1;
+    for (int code = 0; code < ncodes; ++code) feature_of_value(code / (double)(block * block), normal, scale, table + 2 * code);
 }
 // all images: [n][N][2], the layout of tnml_set_data_phi
 inline std::vector<double> all_features(const Dataset& d, bool normal, double scale) {

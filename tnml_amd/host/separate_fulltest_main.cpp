@@ -7,7 +7,8 @@
 // argmax_n |o_n| (first maximum), costs[n] += (n == l) ? (o_n - 1)^2 : o_n^2.  Extensions: `feature` (normal | series),
 // `device`, `precision`, `Ntest`, `imglen` honoured as block-mean down-sampling, `feature_scale`; `predict` (yes | no,
 // default no): a data-less context sized by the ten W alone, the test set streamed through tnml_predict_phi in chunks of
-// `predict_chunk` images (0: the library's default).
+// `predict_chunk` images (0: the library's default); `input_map` (yes | no, default no): the bytes of the idx file through
+// tnml_set_input_map and tnml_set_data_u8 / tnml_predict_u8 instead of host features.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -34,6 +35,7 @@ int main(int argc, const char* argv[]) {
         const double feature_scale = input.getReal("feature_scale", 1.);
         const bool predict = input.getYesNo("predict", false);
         const long predict_chunk = input.getInt("predict_chunk", 0);
+        const bool input_map = input.getYesNo("input_map", false);
         int dtype;
         if (!parse_dtype(precision, false, &dtype)) return 1;
         bool normal;
@@ -43,7 +45,10 @@ int main(int argc, const char* argv[]) {
         std::printf("Labels: 0 1 2 3 4 5 6 7 8 9\n");                                   // :108
 
         Dataset test = read_mnist(datadir, false, Ntest);                              // :124
-        if (imglen > 0 && imglen < test.rows) reduce(test, (int)imglen);
+        Dataset raw;                                                                    // input_map = yes: the bytes of the idx file
+        if (input_map) raw = test;
+        const bool reducing = imglen > 0 && imglen < test.rows;
+        if (reducing) reduce(test, (int)imglen);
         const int N = test.npix();
         if (!sites_match(N)) return 1;                                                  // :128-135
         std::printf("Converting test set to MPS\n");                                   // :137
@@ -64,17 +69,21 @@ int main(int argc, const char* argv[]) {
         cfg.maxm = wm; cfg.dtype = dtype; cfg.svd_backend = TNML_SVD_SYEVD; cfg.mode = TNML_MODE_SINGLE; cfg.target_label = 0;
         tnml_ctx* ctx = nullptr;
         if (tnml_create(&ctx, &cfg)) die(nullptr, "tnml_create");
-        std::vector<double> phi = all_features(test, normal, feature_scale);
+        std::vector<double> phi;
+        if (input_map) { DriverInputMap im = make_input_map(raw, reducing ? imglen : 0, normal, feature_scale); im.print(); im.set(ctx); }
+        else phi = all_features(test, normal, feature_scale);
         if (!predict) {
-            CK(ctx, tnml_set_data_phi(ctx, phi.data(), test.labels.data()));
+            if (input_map) CK(ctx, tnml_set_data_u8(ctx, raw.pixels.data(), test.labels.data()));
+            else CK(ctx, tnml_set_data_phi(ctx, phi.data(), test.labels.data()));
             std::vector<double>().swap(phi);
         }
         std::printf("Running full test\n");                                            // :165
-        if (predict) std::printf("Device path: streamed chain kernel (tnml_predict_phi), %d images per chunk\n", predict_chunk_option(ctx, predict_chunk));
+        if (predict) std::printf("Device path: streamed chain kernel (%s), %d images per chunk\n", input_map ? "tnml_predict_u8" : "tnml_predict_phi", predict_chunk_option(ctx, predict_chunk));
         std::vector<std::vector<double>> o(NLW, std::vector<double>(totNtest));        // o[n][image] = overlap(Ws[n], testimg), :38
         for (int n = 0; n < NLW; ++n) {
             upload_mps(ctx, Ws[n]);
-            if (predict) CK(ctx, tnml_predict_phi(ctx, totNtest, phi.data(), o[n].data(), nullptr));
+            if (predict && input_map) CK(ctx, tnml_predict_u8(ctx, totNtest, raw.pixels.data(), o[n].data(), nullptr));
+            else if (predict) CK(ctx, tnml_predict_phi(ctx, totNtest, phi.data(), o[n].data(), nullptr));
             else CK(ctx, tnml_classify(ctx, o[n].data(), nullptr, nullptr, nullptr));
         }
         int64_t counts[10] = {0}, ninc[10] = {0};

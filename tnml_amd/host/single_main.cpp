@@ -9,7 +9,8 @@
 // `seed` here (the reference's is time-seeded).  Extensions (never read by the reference): `seed`, `device`, `precision`, `imglen`,
 // `feature_scale` as in the fixedL driver; `labels`, `ngpu`, `share_device`, `dry_run`: the one-label-per-GPU launcher
 // of BASELINE config 4 (launch_per_label below); `heldout`, `Ntest`: the t10k images follow the training as a held-out context
-// (one "Held-out:" line per bond update; correct = [f > 1/2] == [label == L], the rule of tnml_classify).
+// (one "Held-out:" line per bond update; correct = [f > 1/2] == [label == L], the rule of tnml_classify); `input_map` (yes | no, default no):
+// the images reach the device as the bytes of the idx file (tnml_set_input_map), same log and same W<label>.
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -143,6 +144,7 @@ int main(int argc, const char* argv[]) {
         const double feature_scale = input.getReal("feature_scale", 1.);
         const bool heldout = input.getYesNo("heldout", false);
         const long Ntest = input.getInt("Ntest", 50000);
+        const bool input_map = input.getYesNo("input_map", false);                       // extension: the images reach the device as the bytes of the idx file (tnml_set_input_map)
         const bool spec_predict = input.getYesNo("spec_predict", false);                 // extension: truncating splits run without their host synchronisation on a predicted bond dimension (option spec_predict)
         int dtype;
         if (!parse_dtype(precision, false, &dtype)) return 1;
@@ -153,9 +155,10 @@ int main(int argc, const char* argv[]) {
         const bool pinv = method == "pinv";                                            // single.h:596
 
         char wname[32]; std::snprintf(wname, sizeof wname, "W%d", L);                  // :53
-        Dataset train = read_images(datadir, true, Ntrain, imglen);                     // :56
+        Dataset train_raw, test_raw;                                                    // input_map = yes: the bytes of the idx files (the initial W is still built from the reduced copy)
+        Dataset train = read_images(datadir, true, Ntrain, imglen, input_map ? &train_raw : nullptr);   // :56
         Dataset test;                                                                   // the held-out set: read before any context exists
-        if (heldout && !read_heldout(datadir, Ntest, imglen, train, &test)) return 1;
+        if (heldout && !read_heldout(datadir, Ntest, imglen, train, &test, input_map ? &test_raw : nullptr)) return 1;
         const int N = train.npix();
         std::printf("%d sites\n", N);                                                  // :59
         if (file_exists("sites")) { int Ns, ds; read_sites("sites", &Ns, &ds); if (Ns != N || ds != 2) { std::printf("Mismatched sizes\n"); return 1; } }
@@ -198,9 +201,18 @@ int main(int argc, const char* argv[]) {
             }
         }
         std::vector<int32_t> labels(totNtrain);
-        std::vector<double> phi((size_t)totNtrain * N * 2), ph;
+        std::vector<double> phi, ph;
+        std::vector<uint8_t> bytes;                                                     // input_map = yes: the raw images in ts order
+        DriverInputMap im;
+        if (input_map) {
+            im = make_input_map(train_raw, imglen, normal, feature_scale);
+            const size_t S = (size_t)train_raw.npix();
+            bytes.resize((size_t)totNtrain * S);
+            for (int k = 0; k < totNtrain; ++k) std::copy(train_raw.pixels.begin() + (size_t)order[k] * S, train_raw.pixels.begin() + (size_t)(order[k] + 1) * S, bytes.begin() + (size_t)k * S);
+        } else phi.resize((size_t)totNtrain * N * 2);
         for (int k = 0; k < totNtrain; ++k) {
             labels[k] = train.labels[order[k]];
+            if (input_map) continue;
             if (normal) features_normal(train, order[k], ph); else features_series(train, order[k], ph, feature_scale);
             std::copy(ph.begin(), ph.end(), phi.begin() + (size_t)k * N * 2);
         }
@@ -231,15 +243,19 @@ int main(int argc, const char* argv[]) {
         if (exact) { CK(ctx, tnml_set_option(ctx, "cg_method", 2)); CK(ctx, tnml_set_option_real(ctx, "pcut", pcut)); }
         if (spec_predict) CK(ctx, tnml_set_option(ctx, "spec_predict", 1));
         if (noise >= 1E-14) CK(ctx, tnml_set_option_real(ctx, "noise", noise));           // sweeps.noise() = noise, single.cc:222
-        CK(ctx, tnml_set_data_phi(ctx, phi.data(), labels.data()));
-        phi.clear(); phi.shrink_to_fit();
+        if (input_map) { im.print(); im.set(ctx); CK(ctx, tnml_set_data_u8(ctx, bytes.data(), labels.data())); }
+        else CK(ctx, tnml_set_data_phi(ctx, phi.data(), labels.data()));
+        phi.clear(); phi.shrink_to_fit(); bytes.clear(); bytes.shrink_to_fit();
         upload_mps(ctx, W);
         tnml_ctx* hctx = nullptr;
         if (heldout) {
             const tnml_config hc = heldout_config();
             if (tnml_create(&hctx, &hc) != 0) die(nullptr, "tnml_create (heldout)");
-            const std::vector<double> hphi = all_features(test, normal, feature_scale);
-            CK(hctx, tnml_set_data_phi(hctx, hphi.data(), test.labels.data()));
+            if (input_map) { make_input_map(test_raw, imglen, normal, feature_scale).set(hctx); CK(hctx, tnml_set_data_u8(hctx, test_raw.pixels.data(), test.labels.data())); }
+            else {
+                const std::vector<double> hphi = all_features(test, normal, feature_scale);
+                CK(hctx, tnml_set_data_phi(hctx, hphi.data(), test.labels.data()));
+            }
         }
         std::printf("Projecting training states..."); std::fflush(stdout);              // :183
         CK(ctx, tnml_env_init(ctx));                                                    // :184-199

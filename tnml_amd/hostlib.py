@@ -37,6 +37,8 @@ def load():
         L.tnmlh_vec_write.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_double)]
         L.tnmlh_mps_sum.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_double, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int)]
         L.tnmlh_mps_overlap.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_double)]
+        L.tnmlh_feature_table.argtypes = [C.c_int, C.c_double, C.c_int, C.POINTER(C.c_double)]
+        L.tnmlh_features.argtypes = [C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double)]
         _LIB = L
     return _LIB
 
@@ -132,6 +134,33 @@ def reduce(pixels, side, newlen):
     n = pixels.shape[0]
     out = np.zeros((n, newlen * newlen))
     if load().tnmlh_reduce(pixels.ctypes.data_as(C.POINTER(C.c_ubyte)), n, side, newlen, out.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise _err()
+    return out
+
+
+def features(pixels, feature="series", scale=1.0, imglen=0):
+    """the drivers' host feature path on [n, npix] uint8 images (reduce() to imglen x imglen when imglen > 0, then all_features):
+    phi[n, sites, 2] as tnml_set_data_phi takes it"""
+    if feature not in ("series", "normal"):
+        raise ValueError("feature must be 'series' or 'normal'")
+    pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
+    n, npix = pixels.shape
+    out = np.empty((n, imglen * imglen if imglen > 0 else npix, 2))
+    if load().tnmlh_features(pixels.ctypes.data_as(C.POINTER(C.c_ubyte)), n, npix, int(imglen), int(feature == "normal"), float(scale),
+                             out.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise _err()
+    return out
+
+
+def feature_table(feature="series", scale=1.0, block=1):
+    """table[255 block^2 + 1, 2] of an input map: the two local features of every block sum `code`, i.e. of the block mean
+    code / block^2, by the drivers' own feature expressions (feature = "series" | "normal"; scale is the drivers' feature_scale)"""
+    if feature not in ("series", "normal"):
+        raise ValueError("feature must be 'series' or 'normal'")
+    if not 1 <= int(block) <= 8:
+        raise ValueError("block must be between 1 and 8")
+    out = np.zeros((255 * int(block) ** 2 + 1, 2))
+    if load().tnmlh_feature_table(int(feature == "normal"), float(scale), int(block), out.ctypes.data_as(C.POINTER(C.c_double))) != 0:
         raise _err()
     return out
 

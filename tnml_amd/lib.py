@@ -34,6 +34,7 @@ EXPORTS = [
     "tnml_heldout_attach", "tnml_heldout_detach", "tnml_heldout_read",
     "tnml_mps_place", "tnml_mps_compress", "tnml_mps_overlap",
     "tnml_predict_u8", "tnml_predict_phi",
+    "tnml_set_input_map", "tnml_get_input_map",
 ]
 
 
@@ -70,6 +71,11 @@ class HeldoutReport(C.Structure):
 class CompressReport(C.Structure):
     _fields_ = [("maxm_before", C.c_int), ("maxm_after", C.c_int), ("nbonds", C.c_int), ("truncerr_sum", C.c_double),
                 ("fallbacks", C.c_int64), ("newm", C.POINTER(C.c_int)), ("truncerr", C.POINTER(C.c_double))]
+
+
+class InputMapStruct(C.Structure):
+    _fields_ = [("src_rows", C.c_int), ("src_cols", C.c_int), ("block", C.c_int), ("row0", C.c_int), ("col0", C.c_int),
+                ("out_rows", C.c_int), ("out_cols", C.c_int), ("ncodes", C.c_int), ("table", C.POINTER(C.c_double))]
 
 
 _lib = None
@@ -132,6 +138,8 @@ def load():
     L.tnml_device_bytes.restype = C.c_int64
     L.tnml_predict_u8.argtypes = [vp, C.c_int64, C.POINTER(C.c_uint8), dp, C.POINTER(C.c_int32)]
     L.tnml_predict_phi.argtypes = [vp, C.c_int64, dp, dp, C.POINTER(C.c_int32)]
+    L.tnml_set_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
+    L.tnml_get_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_replica_check.argtypes = [vp, ip]
     L.tnml_replica_repairs.argtypes = [vp]
     L.tnml_replica_repairs.restype = C.c_int64

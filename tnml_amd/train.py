@@ -8,7 +8,8 @@ ranks with tnml_shard_bounds and the gradient / cost sums go through the library
 (BASELINE config 3: "batch sharded across 8xMI355X").  torch.distributed (gloo) is only the control plane: the RCCL
 unique id, the LAMBDA hot reload, barriers and the sums of the held-out shards (`heldout = yes`: the t10k images, capped at
 `Ntest` per label, follow the training in a held-out context per rank; one "Held-out:" line per bond update).  Rank 0 prints
-and writes files.  A single process (no launcher) works too and is what the tests run.
+and writes files.  A single process (no launcher) works too and is what the tests run.  `input_map = yes` (default no) hands the
+bytes of the idx file to the device, which reduces, maps and transposes them (tnml_set_input_map): same log, same W.
 """
 import os
 import sys
@@ -58,6 +59,7 @@ def main(argv=None):
     try:
         heldout = hostlib.input_yesno(inp, "heldout", False)
         spec_predict = hostlib.input_yesno(inp, "spec_predict", False)
+        use_map = hostlib.input_yesno(inp, "input_map", False)                  # the images reach the device as the bytes of the idx file (tnml_set_input_map)
     except RuntimeError as e:
         say(str(e))
         return 1
@@ -155,7 +157,22 @@ def main(argv=None):
     if ctx_maxm < maxm:
         say("maxm=%d is beyond what %d sites can reach or this GPU can hold for %d images: bond dimensions are capped at %d" % (maxm, N, hi - lo, ctx_maxm))
 
+    imap = None
+    if use_map:                                                                 # reduce(), the feature map and the transpose on the device
+        from .input_map import InputMap
+        side = int(round(np.sqrt(px.shape[1])))
+        try:
+            if side * side != px.shape[1]:
+                raise ValueError("reduce: image is not square")
+            imap = InputMap.from_imglen(side, imglen if imglen > 0 else side, "series", feature_scale)
+        except ValueError as e:
+            say(str(e))
+            return 1
+        say(imap.describe())
+
     def states(p, v, lb, **kw):
+        if imap is not None:
+            return TrainStates(lb, N, ctx_maxm, pixels=p, input_map=imap, device=local_rank, dtype=dtype, **kw)
         if v is None and feature_scale == 1.0:
             return TrainStates(lb, N, ctx_maxm, pixels=p, device=local_rank, dtype=dtype, **kw)
         g = (v if v is not None else p.astype(np.float64)) / 255.0
