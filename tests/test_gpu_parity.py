@@ -1384,7 +1384,7 @@ _OPTION_VALUES_REFUSED = [
 
 
 def test_options_are_range_checked():
-    """the option table (tnml_abi.hip): unknown names, removed options and values outside an option's range are refused with a message
+    """the option table (tnml_core.hip): unknown names, removed options and values outside an option's range are refused with a message
     that names them; every value in use is accepted; a bad environment default makes tnml_create fail"""
     import subprocess
     import sys

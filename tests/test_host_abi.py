@@ -114,8 +114,8 @@ def test_estimate_counts_the_bf16_copies():
 
 
 def _option_table():
-    """(name, environment variable or None) of every row of the option table in tnml_abi.hip"""
-    src = open(os.path.join(ROOT, "tnml_amd", "csrc", "tnml_abi.hip")).read()
+    """(name, environment variable or None) of every row of the option table in tnml_core.hip"""
+    src = open(os.path.join(ROOT, "tnml_amd", "csrc", "tnml_core.hip")).read()
     body = src[src.index("k_options[] = {"):]
     body = body[:body.index("};")]
     return re.findall(r'\{"(\w+)",\s*(?:"(\w+)"|nullptr),', body)

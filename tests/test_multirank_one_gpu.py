@@ -1,5 +1,5 @@
 """The library's multi-rank path (image shards, packed [G | cost | ncorrect | pAp] all-reduce, collective truncation
-decision, replica fingerprints -- tnml_abi.hip: grad_eval / cgrad_device / quadcost_launch / tnml_bond_update, svd.hip)
+decision, replica fingerprints -- tnml_bond.hip: grad_eval / cgrad_device / quadcost_launch, tnml_update.hip: tnml_bond_update, tnml_comm.hip, svd.hip)
 with MORE THAN ONE RANK on the one GPU a test box has: every rank gets its own context and host thread, the ranks are
 joined by the in-process communicator (tnml_comm_init_local; RCCL itself refuses two ranks on one device and is covered
 by test_rccl_path_with_a_one_rank_communicator).  Replaces paralleldo.h:21-68 + the stdx::accumulate reductions
@@ -98,7 +98,7 @@ def test_roll_back_of_a_speculative_split_on_several_ranks(nranks, oneshot, defe
     (slot TNML_SPECSLOT, summed over the ranks), so that every rank rolls back together.  With the test hook debug_fail_split the first,
     an interior and the last speculative split of a pipelined sweep report a failed check on EVERY rank, and -- the case the sum is
     there for -- on rank 1 ALONE: all ranks must repeat the bond update (and the one begun after it) with the synchronous split and
-    its collectives, end with bit-identical site tensors, and follow the undisturbed run (tnml_abi.hip: tnml_bond_update_end)."""
+    its collectives, end with bit-identical site tensors, and follow the undisturbed run (tnml_update.hip: tnml_bond_update_end)."""
     from tnml_amd.fixedl import mldmrg
     N, NT, m = 12, 151, 6
     pixels, labels, phi, W = make_problem(N, NT, m, 5, pixel_boost=200.0)
@@ -253,7 +253,7 @@ def test_a_pipelined_bond_update_enters_five_payload_allreduces():
     # amplifies any rounding difference -- the oracle with 1 and with 8 threads does the same), close after
     np.testing.assert_allclose(new[0]["cost"][:4], old[0]["cost"][:4], rtol=1e-9)
     # bonds 5 and 6 carry the Label index on B: there the merged recurrence and the literal order differ in the later step sizes at 1e-3
-    # and in the cost at ~1e-9 (tnml_abi.hip, cgrad_device; 1.7e-9 at bond 6 with the round-5 split kernels, 0.9e-9 with round 4's)
+    # and in the cost at ~1e-9 (tnml_bond.hip, cgrad_device; 1.7e-9 at bond 6 with the round-5 split kernels, 0.9e-9 with round 4's)
     np.testing.assert_allclose(new[0]["cost"][:8], old[0]["cost"][:8], rtol=1e-8)
     np.testing.assert_allclose(new[0]["cost"], old[0]["cost"], rtol=1e-3)
     for a, b in zip(new[0]["cg"][:8], old[0]["cg"][:8]):                          # the per-pass costs the reference prints (:429)

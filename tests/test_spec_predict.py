@@ -1,4 +1,4 @@
-"""Predicted splits (option spec_predict; svd.hip: k_truncate_verdict, tnml_abi.hip: tnml_bond_update_end).  A truncating split
+"""Predicted splits (option spec_predict; svd.hip: k_truncate_verdict, tnml_update.hip: tnml_bond_update_end).  A truncating split
 (minm < the columns it may keep) takes the speculative form -- no host synchronisation inside tnml_bond_update_begin -- on the column
 count its bond kept at its last two finished visits; a kernel applies the truncation rule to the eigenvalues on the device and a
 wrong guess is rolled back and repeated with the synchronous split.  Whatever is predicted, every number must be the one a run

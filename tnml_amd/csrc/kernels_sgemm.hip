@@ -12,7 +12,7 @@
 // stores into the column-major C): first operand a[j][k] = op(B)[k][j], second b[k][i] = op(A)[i][k], acc[e] = C[i0 + (lane & 15)][j0 + (lane >> 4) + 4 e].
 // The four k of one MFMA are k = 16 kb + 4 (lane >> 4) + u, u = the MFMA's number inside the block of 16: a lane's four k are
 // consecutive in memory (transposed operands read 32 contiguous bytes per block), and a sum over k does not care about its order.
-#include "tnml_internal.h"
+#include "tnml_host.h"   // the check words HC_* of the pinned report block
 
 typedef double f64x4s __attribute__((ext_vector_type(4)));
 
@@ -106,9 +106,9 @@ __global__ __launch_bounds__(64 * KS) void k_dgemm_small(SmallGemmArgs P) {
     if (P.chk_src && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
         // (launched after the polish step: the check values are final) -> pinned host mirror; bad = the test svd_split_device applies
         const double d0 = P.chk_src[0], d1 = P.chk_src[1];
-        P.chk_host[0] = d0; P.chk_host[1] = d1; P.chk_host[2] = P.chk_src[2]; P.chk_host[3] = P.chk_src[3];
+        P.chk_host[HC_DEV0] = d0; P.chk_host[HC_CHOLFAIL] = d1; P.chk_host[HC_CHOLQR] = P.chk_src[2]; P.chk_host[HC_DEV_IN] = P.chk_src[3];
         const double bad = (!(d0 < 1e-6) || d1 != 0.) ? 1. : 0.;
-        P.chk_host[4] = bad;
+        P.chk_host[HC_BAD] = bad;
         if (P.chk_bad) P.chk_bad[0] = bad;
     }
     if (BMODE == 1 && blockIdx.x == 0) {
@@ -145,9 +145,9 @@ int launch_dgemm_small(tnml_ctx* c, const SmallGemmArgs& a) {
 __global__ void k_split_check_mirror(const double* __restrict__ src, double* __restrict__ host, double* __restrict__ bad) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         const double d0 = src[0], d1 = src[1];
-        host[0] = d0; host[1] = d1; host[2] = src[2]; host[3] = src[3];
+        host[HC_DEV0] = d0; host[HC_CHOLFAIL] = d1; host[HC_CHOLQR] = src[2]; host[HC_DEV_IN] = src[3];
         const double b = (!(d0 < 1e-6) || d1 != 0.) ? 1. : 0.;
-        host[4] = b;
+        host[HC_BAD] = b;
         if (bad) bad[0] = b;
     }
 }

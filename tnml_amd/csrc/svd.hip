@@ -17,7 +17,7 @@
 #include <utility>
 #include <vector>
 
-#include "tnml_internal.h"
+#include "tnml_host.h"
 
 static inline int nblk(size_t n) { size_t b = (n + 255) / 256; return (int)(b > 2048 ? 2048 : (b ? b : 1)); }
 
@@ -98,7 +98,7 @@ __global__ void k_mc_flag(const unsigned long long* __restrict__ status, double*
     if (threadIdx.x == 0) out[0] = status[0] != 0ull ? 1. : 0.;
 }
 
-// The truncation rule on the device (option spec_predict): tnml_truncate (tnml_abi.hip) on the ascending eigenvalues, read largest first with
+// The truncation rule on the device (option spec_predict): tnml_truncate (tnml_core.hip) on the ascending eigenvalues, read largest first with
 // !(lam > 0) -> 0 as the host prepares its copy -- the same operations in the same order (the discarded weight grows from the small end, the
 // scale is summed in index order, no fused multiply-add), so the kept count is the host's bit for bit.  At most 240 values: one lane of
 // one wave does it.  out[0] = kept count, out[1] = [count != m_pred] (the verdict on a predicted split; pinned host memory inside a bond
@@ -264,7 +264,7 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
     // the spectrum (tnml_truncate stops at its minm test), so nothing the host would read decides anything but the FALLBACK -- and that
     // decision can wait for tnml_bond_update_end.  No eigenvalue broadcast, no copy, no stream synchronisation: eigenvalues and check
     // values reach the host through pinned mirrors written by the kernels themselves, the two site tensors go to spare buffers, and a
-    // failed check rolls the bond update back (tnml_abi.hip).  One-workgroup sizes only (the cluster's give-up flag is a collective decision).
+    // failed check rolls the bond update back (tnml_update.hip).  One-workgroup sizes only (the cluster's give-up flag is a collective decision).
     const bool spec_form = spec_slot >= 0 && c->spec_split && !c->force_safe && own_eig && !mc && !sv_host && c->hrep != nullptr;
     bool spec = spec_form && minm >= mk;
     // Predicted form (option spec_predict): a truncating split whose bond kept the same count at the same matrix side on its last two finished
@@ -279,7 +279,7 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
         }
     }
     const bool pred = m_pred > 0;
-    double* hmir = spec ? c->hrep + (size_t)spec_slot * c->hrep_stride : nullptr;     // [n eigenvalues | 4 check values]
+    double* hmir = spec ? hrep_eig(c, spec_slot) : nullptr;     // the pinned mirror of this split: [n eigenvalues | check words HC_*] (tnml_host.h)
     if (spec_slot >= 0) {
         // inside a bond update in flight the two new site tensors ALWAYS go to spare buffers (whichever form the split takes): a later
         // roll-back -- of this bond update, or of the one before it whose check is still pending -- can then restore both sites
@@ -314,8 +314,8 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
         TCK(eigh_tridiagonalize(c, c->sG, n, c->sD, c->sE2, c->sTau, c->sV, c->sytrd_exit ? exit_tol : 0.));
         if (own_eig) { TCK(eigh_tridiag_eig(c, c->sD, c->sE2, n, c->sW, mk, c->sC, n, c->sScr, hmir)); evals = c->sW; }
         else RBCK(c, rocsolver_dstedc(c->blas, rocblas_evect_tridiagonal, n, c->sD, c->sE2, c->sC, n, c->sInfo));
-        // the verdict on a predicted count (own_eig holds): the true count behind the four check values and their flag, the carried word beside the check's
-        if (spec && pred) { TCK(launch_truncate_verdict(c, evals, n, maxm, minm, cutoff, m_pred, hmir + n + 5, c->tail + TNML_PREDSLOT)); }
+        // the verdict on a predicted count (own_eig holds): the true count and its verdict behind the check values and their flag (HC_MKEPT, HC_WRONG), the carried word beside the check's
+        if (spec && pred) { TCK(launch_truncate_verdict(c, evals, n, maxm, minm, cutoff, m_pred, hrep_check(c, spec_slot, n) + HC_MKEPT, c->tail + TNML_PREDSLOT)); }
     } else {
         RBCK(c, rocsolver_dsyevd(c->blas, rocblas_evect_original, rocblas_fill_upper, n, c->sG, n, c->sD, c->sE, c->sInfo));
     }
@@ -323,7 +323,7 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
     bool direct_left = false;
     double* Lf = c->sF + (size_t)c->svd_n * c->maxm;     // left factor when a permutation is still needed
     double* Q0 = c->sQ1;
-    double* hd = c->h_scal + 2 * c->svd_n + 32;
+    double* hd = hscal_kept(c);
     double* dv = own_eig ? c->sW + n : c->sDev;           // [0] max|Q^T Q - I| into the polish step, [1] Cholesky failed, [2] a factorisation was needed
     if (own_eig) {
         // Z (already "largest first") -> U = H_0 H_1 ... Z for all mk candidate columns, queued BEFORE the eigenvalues go to
@@ -386,13 +386,13 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
     }
     int m = mk;
     bool stock = !tri;                                   // eigenvectors of rho itself in sG (dsyevd)
-    double* h = c->h_scal;          // pinned, capacity >= 2*svd_n + 64
+    double* h = hscal_eig(c);       // pinned: [n eigenvalues | HC_SYNC_N check words], the cluster's flag at n + HC_RESERVED
     SmallGemmArgs chk{};                                   // the check-value side job of the speculative form (rides in the factor product below)
     const SmallGemmArgs* chkp = nullptr;
     if (spec) {
         if (pred) m = m_pred;
         // m = mk (or the predicted count); the eigenvalues are on their way to hmir[0..n) (k_teig_vectors), the check values follow with the factor product
-        chk.chk_src = dv; chk.chk_host = hmir + n; chk.chk_bad = c->tail + TNML_SPECSLOT;
+        chk.chk_src = dv; chk.chk_host = hrep_check(c, spec_slot, n); chk.chk_bad = c->tail + TNML_SPECSLOT;
         // test hook (option debug_fail_split): the k-th speculative split reports a failed check -- by spoiling the check VALUE in stream
         // order before the product that mirrors it, so that no product kernel carries a test switch
         if (c->debug_fail_split >= 0 && c->spec_splits - 1 == c->debug_fail_split) TCK(launch_fill_f64(c, dv + 1, 1.0, 1));
@@ -404,7 +404,7 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
     // eigenvalues -> host: the truncation decision (ITensor truncate()) fixes the new bond dimension.  With more than
     // one rank the decision is made collective: every rank decides on rank 0's eigenvalues (and rank 0's orthogonality
     // check), so that a last-bit difference between replicas can never produce different bond dimensions.
-    const int nev = own_eig ? n + 4 : n;                 // the check values ride behind the eigenvalues: one broadcast, one copy
+    const int nev = own_eig ? n + HC_SYNC_N : n;                 // the check values ride behind the eigenvalues: one broadcast, one copy
     TCK(bcast_rank0(c, const_cast<double*>(evals), nev));
     // The workgroup cluster of ANY rank may have given up (a workgroup that never got a CU): the fallback below contains
     // collectives, so every rank has to take it together -- the status words are summed over the ranks (one 8-byte all-reduce,
@@ -415,7 +415,7 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
         TCK(allreduce_sum(c, mcflag, 1));
     }
     HIPCK(c, hipMemcpyAsync(h, evals, sizeof(double) * nev, hipMemcpyDeviceToHost, st));
-    double* h_mc = h + n + 8;
+    double* h_mc = h + n + HC_RESERVED;
     *h_mc = 0.;
     if (mc) HIPCK(c, hipMemcpyAsync(h_mc, mcflag, 8, hipMemcpyDeviceToHost, st));
     SYNCK(c, st);
@@ -433,7 +433,7 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
         HIPCK(c, hipMemcpyAsync(h, evals, sizeof(double) * n, hipMemcpyDeviceToHost, st));
         SYNCK(c, st);
     }
-    if (own_eig) { hd[0] = h[n]; hd[1] = h[n + 1]; hd[2] = h[n + 2]; }
+    if (own_eig) { hd[HC_DEV0] = h[n + HC_DEV0]; hd[HC_CHOLFAIL] = h[n + HC_CHOLFAIL]; hd[HC_CHOLQR] = h[n + HC_CHOLQR]; }
     if (c->svd_print >= 0) {                                                   // debugging aid (option svd_print = k): the spectrum of the k-th split of this context
         if (c->svd_calls++ == c->svd_print) { fprintf(stderr, "svd_spectrum n=%d:", n); for (int g = 0; g < n; ++g) fprintf(stderr, " %.3e", h[n - 1 - g]); fprintf(stderr, "\n"); }
     }
@@ -454,11 +454,11 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
         if (c->svd_print == -1) {                                                  // debugging aid (option svd_print = -1): the check values of every split
             double nref = -1.;
             (void)hipMemcpy(&nref, c->sTau + (n - 1), sizeof(double), hipMemcpyDeviceToHost);
-            fprintf(stderr, "svd_check n=%d mk=%d dev=%.2e cholfail=%g factored=%g dev_in=%.2e reflectors=%g\n", n, mk, hd[0], hd[1], hd[2], h[n + 3], nref);
+            fprintf(stderr, "svd_check n=%d mk=%d dev=%.2e cholfail=%g factored=%g dev_in=%.2e reflectors=%g\n", n, mk, hd[HC_DEV0], hd[HC_CHOLFAIL], hd[HC_CHOLQR], h[n + HC_DEV_IN], nref);
         }
-        c->svd_last_dev0 = hd[0]; c->svd_last_dev1 = 0.75 * hd[0] * hd[0];      // Newton-Schulz: error -> 3/4 error^2
-        const bool ok = hd[0] < 1e-6 && hd[1] == 0.;                             // the polish step leaves 3/4 d^2 < 1e-12
-        if (hd[2] != 0.) c->svd_cholqr += 1;
+        c->svd_last_dev0 = hd[HC_DEV0]; c->svd_last_dev1 = 0.75 * hd[HC_DEV0] * hd[HC_DEV0];      // Newton-Schulz: error -> 3/4 error^2
+        const bool ok = hd[HC_DEV0] < 1e-6 && hd[HC_CHOLFAIL] == 0.;                             // the polish step leaves 3/4 d^2 < 1e-12
+        if (hd[HC_CHOLQR] != 0.) c->svd_cholqr += 1;
         if (!ok && !c->svd_dump.empty()) {                                       // debugging aid (TNML_SVD_DUMP at tnml_create): the offending tridiagonal problem
             const char* dump = c->svd_dump.c_str();
             int& dumped = c->svd_dumped;

@@ -1,0 +1,177 @@
+// tnml_data.hip -- what a context is given: labels and features (as features, as bytes, as bytes through an input map), the tile
+// order tables that follow the features, and the replica of the weight MPS.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "tnml_host.h"
+
+// ---- training set -----------------------------------------------------------------------------
+static int set_labels(tnml_ctx* c, const int32_t* labels) {
+    std::vector<int> lab(c->NTp, -1);
+    for (int i = 0; i < c->NT; ++i) {
+        if (labels[i] < 0 || labels[i] >= TNML_NL) return tnml_fail(c, "label %d of image %d out of range", labels[i], i);
+        lab[i] = labels[i];
+    }
+    HIPCK(c, hipMemcpy(c->label, lab.data(), sizeof(int) * c->NTp, hipMemcpyHostToDevice));
+    return 0;
+}
+// the tile order tables of k_shift_res follow the stored features: rebuilt whenever the data are replaced (contexts that have them)
+static int shift_order_build(tnml_ctx* c) {
+    if (!c->zs_ord) return 0;
+    TCK(launch_shift_order(c, (const double*)c->phi, c->N, c->NTp, c->zs_ord, c->zs_nz, c->zs_cnt));
+    c->zs_groups.assign(c->N, 0);
+    HIPCK(c, hipMemcpyAsync(c->zs_groups.data(), c->zs_cnt, sizeof(int) * c->N, hipMemcpyDeviceToHost, c->stream));
+    SYNCK(c, c->stream);
+    return 0;
+}
+int tnml_shift_skip_stats(tnml_ctx* c, int site, int64_t* groups, int64_t* skipped) {
+    if (!c) return tnml_fail(c, "tnml_shift_skip_stats: null argument");
+    if (site < 1 || site > c->N) return tnml_fail(c, "tnml_shift_skip_stats: site %d out of range", site);
+    if (!c->zs_ord || !c->data_set || c->zs_groups.size() != (size_t)c->N) return tnml_fail(c, "tnml_shift_skip_stats: this context has no tile order tables (fp64 storage, fixedL, maxm >= 33, data set)");
+    if (groups) *groups = (int64_t)(c->NTp / 16);
+    if (skipped) *skipped = c->zs_groups[site - 1];
+    return 0;
+}
+// ---- input map (tnml.h): geometry + table; consulted by tnml_set_data_u8 / tnml_predict_u8 when bytes arrive -------------------------
+StageGeom stage_geom(const tnml_ctx* c) {
+    const tnml_input_map& m = c->im;
+    return StageGeom{m.src_rows * m.src_cols, m.src_cols, m.block, m.row0, m.col0, m.out_rows, m.out_cols};
+}
+int tnml_set_input_map(tnml_ctx* c, const tnml_input_map* m) {
+    if (!c) return tnml_fail(c, "tnml_set_input_map: null argument");
+    TCK(ho_locked(c, "tnml_set_input_map"));
+    if (c->pend_count > 0) return tnml_fail(c, "tnml_set_input_map: a bond update is in flight (tnml_bond_update_end first)");
+    if (m) {
+        if (m->block < 1 || m->block > 8) return tnml_fail(c, "tnml_set_input_map: block = %d, must be 1..8", m->block);
+        if (m->ncodes != 255 * m->block * m->block + 1) return tnml_fail(c, "tnml_set_input_map: ncodes = %d, must be 255 block^2 + 1 = %d", m->ncodes, 255 * m->block * m->block + 1);
+        if (m->src_rows < 1 || m->src_cols < 1 || (int64_t)m->src_rows * m->src_cols > (int64_t)1 << 30)
+            return tnml_fail(c, "tnml_set_input_map: src_rows x src_cols = %d x %d, must be at least 1 x 1 and at most 2^30 bytes", m->src_rows, m->src_cols);
+        if (m->out_rows < 1 || m->out_cols < 1 || (int64_t)m->out_rows * m->out_cols != c->N)
+            return tnml_fail(c, "tnml_set_input_map: out_rows * out_cols = %d * %d, must be N = %d", m->out_rows, m->out_cols, c->N);
+        if (m->row0 < 0 || m->row0 + (int64_t)m->block * m->out_rows > m->src_rows)
+            return tnml_fail(c, "tnml_set_input_map: row0 = %d: blocks of %d rows from there leave the %d source rows", m->row0, m->block, m->src_rows);
+        if (m->col0 < 0 || m->col0 + (int64_t)m->block * m->out_cols > m->src_cols)
+            return tnml_fail(c, "tnml_set_input_map: col0 = %d: blocks of %d columns from there leave the %d source columns", m->col0, m->block, m->src_cols);
+        if (!m->table) return tnml_fail(c, "tnml_set_input_map: table is NULL");
+        for (int k = 0; k < 2 * m->ncodes; ++k)
+            if (!std::isfinite(m->table[k])) return tnml_fail(c, "tnml_set_input_map: table[%d][%d] is not finite", k / 2, k % 2);
+    }
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if (c->pk_map_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); predict_release_map(c); }
+    if (!m) { c->im_set = false; c->im = tnml_input_map{}; c->im_table.clear(); return 0; }
+    c->im_table.assign(m->table, m->table + (size_t)2 * m->ncodes);
+    c->im = *m; c->im.table = nullptr;
+    c->im_set = true;
+    return 0;
+}
+int tnml_get_input_map(tnml_ctx* c, tnml_input_map* out) {
+    if (!c || !out) return tnml_fail(c, "tnml_get_input_map: null argument");
+    *out = c->im_set ? c->im : tnml_input_map{};
+    out->table = nullptr;
+    return 0;
+}
+// tnml_set_data_u8 under a map (k_features_codes): raw -> block sums (k_stage_codes with ld = NTp) -> phi [N][2][NTp] through the table in the
+// context's storage type; the three temporaries are freed before the call returns
+static int features_codes(tnml_ctx* c, const uint8_t* pixels) {
+    const StageGeom g = stage_geom(c);
+    const size_t nraw = (size_t)c->NT * g.S, ncode = (size_t)c->N * c->NTp * sizeof(uint16_t), ntab = c->im_table.size();
+    std::vector<float> tab32;
+    if (!c->env64()) { tab32.resize(ntab); for (size_t k = 0; k < ntab; ++k) tab32[k] = (float)c->im_table[k]; }   // rounded once, as tnml_set_data_phi rounds phi
+    const size_t tabb = ntab * (c->env64() ? sizeof(double) : sizeof(float));
+    uint8_t* d_raw = nullptr; uint16_t* d_codes = nullptr; void* d_tab = nullptr;
+    int rc = 0;
+    auto hip = [&](hipError_t e, const char* what) { if (!rc && e != hipSuccess) rc = tnml_fail(c, "tnml_set_data_u8: %s failed: %s", what, hipGetErrorString(e)); };
+    hip(hipMalloc((void**)&d_raw, nraw), "hipMalloc of the raw bytes");
+    if (!rc) hip(hipMalloc((void**)&d_codes, ncode), "hipMalloc of the block sums");
+    if (!rc) hip(hipMalloc(&d_tab, tabb), "hipMalloc of the table");
+    if (!rc) hip(hipMemcpyAsync(d_raw, pixels, nraw, hipMemcpyHostToDevice, c->stream), "copy of the raw bytes");
+    if (!rc) hip(hipMemcpyAsync(d_tab, c->env64() ? (const void*)c->im_table.data() : (const void*)tab32.data(), tabb, hipMemcpyHostToDevice, c->stream), "copy of the table");
+    if (!rc) {
+        ProfScope ps(c, KC_PACK);
+        rc = launch_stage_codes(c, d_raw, g, c->NT, c->NTp, d_codes);
+        if (!rc) rc = launch_codes_phi(c, d_codes, d_tab, c->N, c->NT, c->NTp, c->phi);
+    }
+    hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+    (void)hipFree(d_raw); (void)hipFree(d_codes); (void)hipFree(d_tab);
+    return rc;
+}
+int tnml_set_data_u8(tnml_ctx* c, const uint8_t* pixels, const int32_t* labels) {
+    TCK(ho_locked(c, "tnml_set_data_u8", true));
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    TCK(set_labels(c, labels));
+    if (c->im_set) {
+        TCK(features_codes(c, pixels));
+        TCK(shift_order_build(c));
+        c->data_set = true; c->currb = -1; c->p_valid = false; c->sweep_start = false;
+        return 0;
+    }
+    uint8_t* d_pix = nullptr;
+    const size_t nb = (size_t)c->NT * c->N;
+    HIPCK(c, hipMalloc((void**)&d_pix, nb));
+    HIPCK(c, hipMemcpy(d_pix, pixels, nb, hipMemcpyHostToDevice));
+    int rc = launch_features_u8(c, d_pix, c->N, c->NT, c->NTp, c->phi);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(d_pix);
+    if (rc) return rc;
+    TCK(shift_order_build(c));
+    c->data_set = true; c->currb = -1; c->p_valid = false; c->sweep_start = false;
+    return 0;
+}
+int tnml_set_data_phi(tnml_ctx* c, const double* phi, const int32_t* labels) {
+    TCK(ho_locked(c, "tnml_set_data_phi", true));
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    TCK(set_labels(c, labels));
+    // TState::data[(j-1)*d + (n-1)] (fixedL.cc:39-46) -> [N][2][NTp], rounded once to fp32
+    const size_t ne = (size_t)c->N * 2 * c->NTp;
+    if (c->env64()) {
+        std::vector<double> h(ne, 0.);
+        for (int i = 0; i < c->NT; ++i) for (int j = 0; j < c->N; ++j) for (int s = 0; s < 2; ++s)
+            h[((size_t)j * 2 + s) * c->NTp + i] = phi[((size_t)i * c->N + j) * 2 + s];
+        HIPCK(c, hipMemcpy(c->phi, h.data(), sizeof(double) * ne, hipMemcpyHostToDevice));
+        TCK(shift_order_build(c));
+    } else {
+        std::vector<float> h(ne, 0.f);
+        for (int i = 0; i < c->NT; ++i) for (int j = 0; j < c->N; ++j) for (int s = 0; s < 2; ++s)
+            h[((size_t)j * 2 + s) * c->NTp + i] = (float)phi[((size_t)i * c->N + j) * 2 + s];
+        HIPCK(c, hipMemcpy(c->phi, h.data(), sizeof(float) * ne, hipMemcpyHostToDevice));
+    }
+    c->data_set = true; c->currb = -1; c->p_valid = false; c->sweep_start = false;
+    return 0;
+}
+
+// ---- weight MPS replica -------------------------------------------------------------------------
+int tnml_set_site(tnml_ctx* c, int j, int ml, int mr, int has_label, const double* A) {
+    TCK(ho_locked(c, "tnml_set_site", true));
+    if (j < 1 || j > c->N) return tnml_fail(c, "tnml_set_site: site %d out of range", j);
+    if (c->single() && has_label) return tnml_fail(c, "tnml_set_site: the per-label variant has no Label index");
+    if ((j == c->c0) != (has_label != 0)) return tnml_fail(c, "Label Index not on site %d", c->c0);     // fixedL.cc:734
+    if (ml < 1 || mr < 1 || ml > c->maxm || mr > c->maxm) return tnml_fail(c, "tnml_set_site: bond dimension outside 1..maxm");
+    if ((j == 1 && ml != 1) || (j == c->N && mr != 1)) return tnml_fail(c, "tnml_set_site: edge sites must have outer dimension 1");
+    SiteT& s = c->W[j];
+    s.ml = ml; s.mr = mr; s.L = has_label ? TNML_NL : 1; s.set = true; s.placed = false;
+    HIPCK(c, hipMemcpy(s.a, A, sizeof(double) * (size_t)ml * 2 * mr * s.L, hipMemcpyHostToDevice));
+    c->currb = -1; c->p_valid = false; c->sweep_start = false;
+    for (int b = j - 1; b <= j; ++b) if (b >= 1 && b < (int)c->bond_hist.size()) c->bond_hist[b] = tnml_ctx::BondHist();   // the bonds of this site start over (option spec_predict)
+    return 0;
+}
+int tnml_site_dims(tnml_ctx* c, int j, int* ml, int* mr, int* has_label) {
+    if (j < 1 || j > c->N || !c->W[j].set) return tnml_fail(c, "tnml_site_dims: site %d not set", j);
+    *ml = c->W[j].ml; *mr = c->W[j].mr; *has_label = c->W[j].L == TNML_NL;
+    return 0;
+}
+int tnml_get_site(tnml_ctx* c, int j, double* A) {
+    if (j < 1 || j > c->N || !c->W[j].set) return tnml_fail(c, "tnml_get_site: site %d not set", j);
+    const SiteT& s = c->W[j];
+    SYNCK(c, c->stream);
+    HIPCK(c, hipMemcpy(A, s.a, sizeof(double) * (size_t)s.ml * 2 * s.mr * s.L, hipMemcpyDeviceToHost));
+    return 0;
+}
+int check_W(tnml_ctx* c) {
+    for (int j = 1; j <= c->N; ++j) {
+        if (!c->W[j].set) return tnml_fail(c, "W: site %d not set", j);
+        if (j > 1 && c->W[j].ml != c->W[j - 1].mr) return tnml_fail(c, "W: bond dimension mismatch between sites %d and %d", j - 1, j);
+    }
+    return 0;
+}

@@ -1,0 +1,191 @@
+// tnml_infer.hip -- inference: tnml_classify on the images a context holds, tnml_predict_* on images it does not.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "tnml_host.h"
+
+// ---- inference: toverlap / fullTest (util.h:19-40,123-200) ------------------------------------------
+// W_n[l] = (prod_{j<c} phi_j*A_j) * (phi_c*A_c) * (prod_{j>c} phi_j*A_j) for every local image, with rolling
+// chain buffers borrowed from the environment pools (the training environments are left untouched).
+int tnml_classify(tnml_ctx* c, double* weights, int32_t* pred, int64_t count[TNML_NL], int64_t nincorrect[TNML_NL]) {
+    CollScope coll_(c);
+    TCK(ho_locked(c, "tnml_classify"));
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if (!c->data_set) return tnml_fail(c, "tnml_classify: image data not set");
+    EnvProtect keep(c, c->currb > 0 ? c->currb - 1 : 0, c->currb > 0 ? c->currb + 2 : 0);      // the chain buffers below may evict, but not the operands of the bond that is set
+    c->p_valid = false;
+    TCK(check_W(c));
+    EnvSlot buf[3];
+    int rc = 0;
+    for (int k = 0; k < 3 && !rc; ++k) rc = slot_acquire(c, buf[k], c->maxm, 1);
+    auto give_back = [&]() { for (auto& b : buf) slot_release(c, b); };
+    if (rc) { give_back(); return rc; }
+    const int cs = c->single() ? 1 : c->c0;                // per-label variant: site 1 plays the centre, no left chain
+    // right chain N -> c+1 (util.h:25-29), ping-pong between buf[0] and buf[1]
+    const void* R = nullptr; int cur = 0;
+    for (int j = c->N; j > cs && !rc; --j) { rc = shift_core(c, j, false, R, 1, buf[cur].ptr, false, nullptr); R = buf[cur].ptr; cur ^= 1; }
+    // left chain 1 -> c-1 (util.h:32-37), ping-pong between buf[2] and the free one of the pair above
+    const void* Lc = nullptr; void* lbuf[2] = {buf[2].ptr, buf[cur].ptr}; int lcur = 0;
+    for (int j = 1; j < cs && !rc; ++j) { rc = shift_core(c, j, true, Lc, 1, lbuf[lcur], false, nullptr); Lc = lbuf[lcur]; lcur ^= 1; }
+    // centre site: T[l][r][n] = sum_{a,s} L[a][n] phi_c[s][n] A_c[a,s,r,l], then W_n[l] = sum_r T[l][r][n] R[r][n]
+    if (!rc) rc = shift_core(c, cs, true, Lc, 1, c->U, true, nullptr);
+    double* tail = c->tail;
+    if (!rc) {
+        LdotArgs a;
+        a.A = c->U; a.A_lstride = (size_t)c->W[cs].mr * c->NTp; a.Bv = R; a.a_is_env = 0;
+        a.mq = c->W[cs].mr; a.NTp = c->NTp; a.label = c->label; a.nl = c->nl(); a.target = c->target();
+        a.P = c->P; a.dP = nullptr; a.mode = LD_MODE_COST;
+        rc = launch_labeldot(c, a, tail);
+    }
+    give_back();
+    if (rc) return rc;
+    std::vector<char> h((size_t)TNML_NL * c->NTp * c->esz());
+    std::vector<int> lab(c->NTp);
+    SYNCK(c, c->stream);
+    HIPCK(c, hipMemcpy(h.data(), c->P, h.size(), hipMemcpyDeviceToHost));
+    HIPCK(c, hipMemcpy(lab.data(), c->label, sizeof(int) * c->NTp, hipMemcpyDeviceToHost));
+    HIPCK(c, hipMemsetAsync(tail, 0, sizeof(double) * TNML_NSCAL_AR, c->stream));
+    if (count) for (int l = 0; l < TNML_NL; ++l) count[l] = 0;
+    if (nincorrect) for (int l = 0; l < TNML_NL; ++l) nincorrect[l] = 0;
+    const int nl = c->nl();
+    for (int i = 0; i < c->NT; ++i) {
+        double w[TNML_NL];
+        for (int l = 0; l < nl; ++l) {
+            const size_t k = (size_t)l * c->NTp + i;
+            w[l] = c->f64() ? ((const double*)h.data())[k] : (double)((const float*)h.data())[k];
+            if (weights) weights[(size_t)i * nl + l] = w[l];
+        }
+        bool wrong;
+        if (c->single()) {                                         // decision function f(x): pred = [f > 1/2]
+            const int pl = w[0] > 0.5 ? 1 : 0;
+            if (pred) pred[i] = pl;
+            wrong = pl != (lab[i] == c->target() ? 1 : 0);
+        } else {
+            int pl = 0; double best = std::fabs(w[0]);             // argmax of |W_l|, first maximum (util.h:42-57,160-163)
+            for (int l = 1; l < TNML_NL; ++l) if (std::fabs(w[l]) > best) { best = std::fabs(w[l]); pl = l; }
+            if (pred) pred[i] = pl;
+            wrong = pl != lab[i];
+        }
+        if (count) count[lab[i]] += 1;
+        if (nincorrect && wrong) nincorrect[lab[i]] += 1;
+    }
+    return 0;
+}
+
+// ---- streamed inference: images the context does not hold (util.h:19-40 toverlap + argmax, util.h:42-57) ----------
+// The host loop cuts the n images into chunks of option predict_chunk; a chunk is staged (copy + one transposing pre-kernel), contracted by
+// ONE k_chain launch (kernels_chain.hip) and copied back.  Reads W only: no training data, environment, bond plan, P or p_valid is touched,
+// no collective is entered.  The workspace is allocated by the first call (see tnml.h for its size) and lives until tnml_destroy.
+// the workspace of tnml_predict_u8 under a map follows the map: released here, re-made by the next such call
+void predict_release_map(tnml_ctx* c) {
+    void** slots[] = {(void**)&c->pk_mraw, (void**)&c->pk_codes, (void**)&c->pk_mtab};
+    for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    c->bytes -= c->pk_map_bytes; c->pk_bytes -= c->pk_map_bytes;
+    c->pk_map_bytes = 0;
+}
+void predict_release(tnml_ctx* c) {
+    void** slots[] = {(void**)&c->pk_tab, (void**)&c->pk_w, (void**)&c->pk_pred, (void**)&c->pk_park, (void**)&c->pk_raw8, (void**)&c->pk_x8, (void**)&c->pk_rawphi, (void**)&c->pk_xphi};
+    for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    predict_release_map(c);
+    c->bytes -= c->pk_bytes;
+    c->pk_bytes = 0; c->pk_cap = 0; c->pk_park_elems = 0;
+}
+static int predict_alloc(tnml_ctx* c, void** p, size_t bytes) {
+    TCK(dalloc(c, p, bytes));
+    c->pk_bytes += (int64_t)bytes;
+    return 0;
+}
+static int predict_workspace(tnml_ctx* c, bool bytes_form) {
+    const int cap = (c->predict_chunk + 63) / 64 * 64;
+    if (c->pk_cap != cap) {                               // first call, or option predict_chunk has changed since
+        if (c->pk_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); predict_release(c); }
+        const size_t mc = (size_t)(std::min(c->maxm, TNML_CHAIN_MAXM) + 15) / 16 * 16;
+        int rc = predict_alloc(c, (void**)&c->pk_tab, (size_t)c->N * sizeof(ChainSite));
+        if (!rc) rc = predict_alloc(c, (void**)&c->pk_w, (size_t)cap * c->nl() * sizeof(double));
+        if (!rc) rc = predict_alloc(c, (void**)&c->pk_pred, (size_t)cap * sizeof(int));
+        if (!rc) rc = predict_alloc(c, (void**)&c->pk_park, (size_t)cap * mc * sizeof(double));
+        if (rc) { predict_release(c); return rc; }
+        c->pk_park_elems = (size_t)cap * mc;
+        c->pk_cap = cap;
+    }
+    int rc = 0;
+    if (bytes_form && c->im_set) {                        // S C + 2 N C + 16 ncodes: bytes as given, block sums site-first, the fp64 table
+        if (c->pk_codes) return 0;
+        const size_t S = (size_t)c->im.src_rows * c->im.src_cols, tabb = c->im_table.size() * sizeof(double);
+        const int64_t before = c->pk_bytes;
+        rc = predict_alloc(c, (void**)&c->pk_mraw, S * cap);
+        if (!rc) rc = predict_alloc(c, (void**)&c->pk_codes, (size_t)cap * c->N * sizeof(uint16_t));
+        if (!rc) rc = predict_alloc(c, (void**)&c->pk_mtab, tabb);
+        c->pk_map_bytes = c->pk_bytes - before;
+        if (!rc && hipMemcpyAsync(c->pk_mtab, c->im_table.data(), tabb, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict_u8: copy of the input map's table failed");
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict_u8: hipStreamSynchronize failed");
+        if (rc) predict_release(c);
+        return rc;
+    }
+    if (bytes_form && !c->pk_x8) { rc = predict_alloc(c, (void**)&c->pk_raw8, (size_t)cap * c->N); if (!rc) rc = predict_alloc(c, (void**)&c->pk_x8, (size_t)cap * c->N); }
+    if (!bytes_form && !c->pk_xphi) { rc = predict_alloc(c, (void**)&c->pk_rawphi, (size_t)2 * cap * c->N * sizeof(double)); if (!rc) rc = predict_alloc(c, (void**)&c->pk_xphi, (size_t)2 * cap * c->N * sizeof(double)); }
+    if (rc) predict_release(c);
+    return rc;
+}
+static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, double* weights, int32_t* pred) {
+    if (!c) return tnml_fail(c, "%s: null argument", who);
+    if (n < 0) return tnml_fail(c, "%s: n = %lld, must be >= 0", who, (long long)n);
+    if (c->pend_count > 0) return tnml_fail(c, "%s: a bond update is in flight (tnml_bond_update_end first)", who);
+    TCK(ho_locked(c, who));                                     // attached as a held-out set: its W is rewritten from the training context's stream, as tnml_classify refuses it
+    TCK(check_W(c));
+    int maxbond = 1;
+    for (int j = 1; j <= c->N; ++j) maxbond = std::max(maxbond, std::max(c->W[j].ml, c->W[j].mr));
+    if (maxbond > TNML_CHAIN_MAXM)
+        return tnml_fail(c, "%s: W has a bond of dimension %d, the chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, maxbond, TNML_CHAIN_MAXM);
+    if (n == 0) return 0;
+    if (!pixels && !phi) return tnml_fail(c, "%s: null argument", who);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const bool bytes_form = pixels != nullptr;
+    TCK(predict_workspace(c, bytes_form));
+    const int cs = c->single() ? 1 : c->c0, nl = c->nl();       // the centre tnml_classify takes
+    std::vector<ChainSite> tab(c->N);
+    for (int j = 1; j <= c->N; ++j) tab[j - 1] = ChainSite{c->W[j].a, c->W[j].ml, c->W[j].mr};
+    HIPCK(c, hipMemcpyAsync(c->pk_tab, tab.data(), sizeof(ChainSite) * c->N, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));                  // (tab leaves scope with this call)
+    const bool mapped = bytes_form && c->im_set;                // the input map: S bytes per image -> block sums -> table look-ups inside the chain kernel
+    const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
+    const size_t per_img = mapped ? (size_t)sg.S : (size_t)c->N * (bytes_form ? 1 : 2 * sizeof(double));
+    for (int64_t off = 0; off < n; off += c->predict_chunk) {
+        const int cnt = (int)std::min<int64_t>(c->predict_chunk, n - off);
+        if (mapped) {
+            HIPCK(c, hipMemcpyAsync(c->pk_mraw, pixels + (size_t)off * per_img, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+            { ProfScope ps(c, KC_PACK); TCK(launch_stage_codes(c, c->pk_mraw, sg, cnt, c->pk_cap, c->pk_codes)); }
+            ChainArgs a;
+            a.sites = c->pk_tab; a.N = c->N; a.cs = cs; a.nl = nl; a.single = c->single() ? 1 : 0;
+            a.xT = nullptr; a.phiT = nullptr; a.codeT = c->pk_codes; a.table = c->pk_mtab;
+            a.ld = c->pk_cap; a.cnt = cnt; a.wout = c->pk_w; a.pred = c->pk_pred;
+            TCK(launch_chain(c, a, maxbond, chain_tile(c, maxbond, cnt), c->pk_park, c->pk_park_elems));
+            if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->pk_w, sizeof(double) * (size_t)cnt * nl, hipMemcpyDeviceToHost, c->stream));
+            if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->pk_pred, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+            SYNCK(c, c->stream);
+            continue;
+        }
+        if (bytes_form) HIPCK(c, hipMemcpyAsync(c->pk_raw8, pixels + (size_t)off * c->N, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+        else            HIPCK(c, hipMemcpyAsync(c->pk_rawphi, phi + (size_t)off * c->N * 2, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+        TCK(launch_chain_stage(c, bytes_form ? c->pk_raw8 : nullptr, bytes_form ? nullptr : c->pk_rawphi, c->N, cnt, c->pk_cap, c->pk_x8, c->pk_xphi));
+        ChainArgs a;
+        a.sites = c->pk_tab; a.N = c->N; a.cs = cs; a.nl = nl; a.single = c->single() ? 1 : 0;
+        a.xT = bytes_form ? c->pk_x8 : nullptr; a.phiT = bytes_form ? nullptr : c->pk_xphi;
+        a.ld = c->pk_cap; a.cnt = cnt; a.wout = c->pk_w; a.pred = c->pk_pred;
+        TCK(launch_chain(c, a, maxbond, chain_tile(c, maxbond, cnt), c->pk_park, c->pk_park_elems));
+        if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->pk_w, sizeof(double) * (size_t)cnt * nl, hipMemcpyDeviceToHost, c->stream));
+        if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->pk_pred, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+        SYNCK(c, c->stream);                                    // the staging buffers are reused by the next chunk
+    }
+    return 0;
+}
+int tnml_predict_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, double* weights, int32_t* pred) {
+    if (n > 0 && !pixels) return tnml_fail(c, "tnml_predict_u8: null argument");
+    return predict_impl(c, "tnml_predict_u8", n, pixels, nullptr, weights, pred);
+}
+int tnml_predict_phi(tnml_ctx* c, int64_t n, const double* phi, double* weights, int32_t* pred) {
+    if (n > 0 && !phi) return tnml_fail(c, "tnml_predict_phi: null argument");
+    return predict_impl(c, "tnml_predict_phi", n, nullptr, phi, weights, pred);
+}

@@ -214,7 +214,7 @@ struct tnml_ctx {
     double* vpart = nullptr;   // per-workgroup partial sums of the CG vector kernels [256][2]
     int cg_pass = 0;           // CG pass being issued (selects the parity slot of the convergence flag)
     int rr_slot = 0;           // which of scal[SC_RR], scal[SC_RR+1] holds the current |r|^2
-    double* h_scal = nullptr;  // pinned host mirror
+    double* h_scal = nullptr;  // pinned host mirror of the synchronous paths (the layout: tnml_host.h)
     double *tB = nullptr, *tB2 = nullptr;   // bond tensors in ITensor layout (fp64)
     size_t mcap = 0;           // capacity (elements) of M-layout vectors / bond tensors
     // svd workspaces (fp64)
@@ -260,7 +260,7 @@ struct tnml_ctx {
     std::vector<BondHist> bond_hist;               // 1..N-1
     double* psave = nullptr;                       // [2 slots][P | dP], allocated with the first bond update of spec_predict: a rolled-back bond update starts again from the very outputs its first run reused
     std::vector<double*> spare_small, spare_big;   // spare site-tensor buffers (capacity 2 maxm^2, x 10 for the Label site)
-    double* hrep = nullptr;                        // pinned: [2 slots][hrep_stride] = eigenvalues + check values of a speculative split | CG scalars + trace | norm partials | after-SVD scalars
+    double* hrep = nullptr;                        // pinned: [2 slots][hrep_stride] = eigenvalues + check words of a speculative split | CG scalars + trace | norm partials | carried block (the layout: tnml_host.h)
     double* hmir = nullptr;                        // != nullptr while a bond update is being enqueued: the [scal | trace] mirror of its slot (the CG step kernels write it)
     double* hcost = nullptr;                       // pinned: [2 slots][partial_cap][12]: one rank, the per-block partial sums of the after-SVD quadcost go there (the host adds them)
     int last_dn_pairs = 0;                         // partial pairs the last launch_diffnorm_host wrote
@@ -515,7 +515,7 @@ struct SmallGemmArgs {
     const double* A; int lda; const double* B; int ldb; double* C; int ldc;     // column-major; C = op(A) op(B), M x N, reduction length K
     int M, N, K; int ta, tb;
     int bmode = 0; double* dev = nullptr;      // bmode 1: op(B) = 1.5 I - 0.5 B (B symmetric, K == N), dev[0] = max |B - I| (atomic max: zero it first)
-    // a side job of tile (0, 0) (speculative split): the four check values of the split to their pinned host mirror, and bad[0] = 1 when they fail
+    // a side job of tile (0, 0) (speculative split): the check words HC_DEV0..HC_BAD of the split (tnml_host.h) to their pinned host mirror, and bad[0] = 1 when they fail
     const double* chk_src = nullptr; double* chk_host = nullptr; double* chk_bad = nullptr;
 };
 int launch_dgemm_small(tnml_ctx* c, const SmallGemmArgs& a);
