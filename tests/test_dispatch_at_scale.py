@@ -11,7 +11,8 @@ uniform repeat count R the base problem at lambda/R, cconv/R).  test_tiled_ident
 the CPU with the C oracle on both sides -- the GPU tests below then measure the kernels, not the harness.  The tolerances are the fp64
 figures of test_gpu_parity.py (TOL) and of the forced-kernel tests; the reference's own scatter under the identity is four orders below them.
 
-f32, bf16 and bf16x3 at scale are NOT covered: their gradient sums accumulate in fp32 and no measured bound exists at 60 000 images; only
+f32, bf16 and bf16x3 at scale are NOT covered: their gradient sums accumulate in fp32 and no measured bound exists at 60 000 images (at up to
+700 images tests/rp_model.py models their rounding and test_rp_model_gpu.py holds every kernel of theirs inside its derived bound); only
 f64_e32 (fp32 storage, fp64 accumulation: its rounding does not depend on the image count) gets a case at scale."""
 import os
 
