@@ -34,6 +34,7 @@ extern "C" {
 
 #define TNML_NL 10           /* label dimension, fixedL.cc:15 */
 #define TNML_MAX_PASS 64
+enum { TNML_PREDICT_F64 = 0, TNML_PREDICT_F32 = 1 };   /* option "predict_dtype": arithmetic of tnml_predict_u8 / tnml_predict_phi */
 #define TNML_PREDICT_CHUNK_DEFAULT 8192   /* option "predict_chunk": images per chunk of tnml_predict_u8 / tnml_predict_phi */
 
 typedef struct tnml_ctx tnml_ctx;
@@ -332,7 +333,21 @@ int tnml_classify(tnml_ctx* ctx, double* weights, int32_t* pred, int64_t count[T
  *           + S C + 2 N C + 16 ncodes       bytes instead, from the first tnml_predict_u8 under an input map on (S = src_rows src_cols
  *                                           bytes as given, 16-bit block sums site-first, the fp64 table); released by every
  *                                           tnml_set_input_map call and re-made by the next tnml_predict_u8 under a map
- *           + 32 N C                        bytes from the first tnml_predict_phi on (features as given and site-first). */
+ *           + 32 N C                        bytes from the first tnml_predict_phi on (features as given and site-first).
+ * Option "predict_dtype" = TNML_PREDICT_F32 selects the fp32 chain kernel (kernels_chain32.hip; v_mfma_f32_16x16x4_f32, tiles of 64
+ * images up to bond 256, 32 up to 512, 16 up to 1 024) for the calls that follow; TNML_PREDICT_F64 (the default) is the path above, bit
+ * for bit.  Under fp32 W is rounded to fp32 once per call, the features are formed in fp64 as above and rounded once, every product
+ * and sum is IEEE fp32 in a fixed order (the kernel's header states it; per image independent of n, chunk and tile), weights receives
+ * the fp32 results widened, and pred follows the same rule on the fp32 values (|w| first maximum; w > 0.5f).  Bond dimensions up to
+ * 1 024 are served (above: refused as above, tnml_classify); 513..1 024 stay refused under fp64.  A weight that is not finite -- the
+ * chain has left the fp32 range -- fails the call with a message that names predict_dtype (use fp64); the context stays usable.
+ * Workspace of fp32, allocated by the first fp32 call on top of the above, independent of n, counted and freed the same way:
+ *             16 N + 4 + 4 E                bytes (site table of the fp32 copy of W, range flag, the copy: E = the sum over the sites of
+ *                                           2 ml mr (x nl on the Label site), each rounded up to 4; grown when W has grown)
+ *           + 8 ncodes                      bytes from the first fp32 tnml_predict_u8 under an input map on (the table in fp32; released
+ *                                           with the map's workspace)
+ *           + 16 N C + 8 N C                bytes from the first fp32 tnml_predict_phi on, in place of the 32 N C above (features as
+ *                                           given, and site-first in fp32; the 16 N C are shared with the fp64 path). */
 int tnml_predict_u8(tnml_ctx* ctx, int64_t n, const uint8_t* pixels /*[n][N]*/, double* weights /*[n][nl] or NULL*/, int32_t* pred /*[n] or NULL*/);
 int tnml_predict_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/, double* weights, int32_t* pred);
 
@@ -437,7 +452,9 @@ int tnml_synchronize(tnml_ctx* ctx);
      "debug_nudge_rank"  this rank's copy of a split site tensor is moved by one ulp (-1 off)
      "svd_print"      (TNML_SVD_PRINT) k >= 0: print the spectrum of the k-th split; -1: the check values of every split (-2 off)
      "predict_tile"   images per workgroup of the chain kernel of tnml_predict_*: 16, 32 or 64, capped by what the LDS holds at W's largest bond
-                      dimension (64 up to 128, 32 up to 256, 16 up to 512); 0: that cap, halved while workgroups are fewer than compute units
+                      dimension (64 up to 128, 32 up to 256, 16 up to 512; under predict_dtype = 1: 64 up to 256, 32 up to 512, 16 up to 1 024); 0: that cap, halved while workgroups are fewer than compute units
+     "predict_dtype"  arithmetic of tnml_predict_*: 0 (TNML_PREDICT_F64, default) fp64 MFMA on the fp64 master W, bonds up to 512;
+                      1 (TNML_PREDICT_F32) the fp32 chain kernel on an fp32 copy of W made per call, bonds up to 1 024; any other value is refused
    Memory and transport:
      "predict_chunk"  images per trip of the host loop of tnml_predict_* = per launch of the chain kernel (1..2^20, default 8192); sizes its workspace
      "env_budget_mb"  cap on the environment slabs held on the device, the rest spills to host memory (0: none)

@@ -118,6 +118,7 @@ static const OptDef k_options[] = {
     {"svd_print",        "TNML_SVD_PRINT",      OPT_INT,  &tnml_ctx::svd_print,           nullptr,         -2, INT_MAX, HK_SVD_PRINT},
     {"predict_chunk",    nullptr,               OPT_INT,  &tnml_ctx::predict_chunk,       nullptr,          1, 1 << 20, HK_NONE},
     {"predict_tile",     nullptr,               OPT_INT,  &tnml_ctx::predict_tile,        nullptr,          0, 64,      HK_PREDICT_TILE},
+    {"predict_dtype",    nullptr,               OPT_INT,  &tnml_ctx::predict_dtype,       nullptr,          0, 1,       HK_NONE},   // TNML_PREDICT_F64 / TNML_PREDICT_F32
     {"fg64_cfg",         "TNML_FG64_CFG",       OPT_INT,  &tnml_ctx::opt_fg64_cfg,        nullptr,          0, 2,       HK_NONE},
     {"ldot_cfg",         "TNML_LDOT_CFG",       OPT_INT,  &tnml_ctx::opt_ldot_cfg,        nullptr,          0, 2,       HK_NONE},
     {"pcut",             nullptr,               OPT_REAL, nullptr,                        &tnml_ctx::pcut,  0, HUGE_VAL, HK_NONE},

@@ -82,12 +82,18 @@ int tnml_classify(tnml_ctx* c, double* weights, int32_t* pred, int64_t count[TNM
 void predict_release_map(tnml_ctx* c) {
     void** slots[] = {(void**)&c->pk_mraw, (void**)&c->pk_codes, (void**)&c->pk_mtab};
     for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    if (c->pk_mtab32) {                                   // (the fp32 copy of the table: 8 ncodes bytes)
+        (void)hipFree(c->pk_mtab32); c->pk_mtab32 = nullptr;
+        c->pk_map_bytes += c->pk_mtab32_bytes; c->pk_mtab32_bytes = 0;
+    }
     c->bytes -= c->pk_map_bytes; c->pk_bytes -= c->pk_map_bytes;
     c->pk_map_bytes = 0;
 }
 void predict_release(tnml_ctx* c) {
-    void** slots[] = {(void**)&c->pk_tab, (void**)&c->pk_w, (void**)&c->pk_pred, (void**)&c->pk_park, (void**)&c->pk_raw8, (void**)&c->pk_x8, (void**)&c->pk_rawphi, (void**)&c->pk_xphi};
+    void** slots[] = {(void**)&c->pk_tab, (void**)&c->pk_w, (void**)&c->pk_pred, (void**)&c->pk_park, (void**)&c->pk_raw8, (void**)&c->pk_x8, (void**)&c->pk_rawphi, (void**)&c->pk_xphi,
+                      (void**)&c->pk_w32, (void**)&c->pk_tab32, (void**)&c->pk_flag, (void**)&c->pk_xphi32};
     for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    c->pk_w32_cap = 0;
     predict_release_map(c);
     c->bytes -= c->pk_bytes;
     c->pk_bytes = 0; c->pk_cap = 0; c->pk_park_elems = 0;
@@ -97,7 +103,7 @@ static int predict_alloc(tnml_ctx* c, void** p, size_t bytes) {
     c->pk_bytes += (int64_t)bytes;
     return 0;
 }
-static int predict_workspace(tnml_ctx* c, bool bytes_form) {
+static int predict_workspace(tnml_ctx* c, bool bytes_form, bool f32) {
     const int cap = (c->predict_chunk + 63) / 64 * 64;
     if (c->pk_cap != cap) {                               // first call, or option predict_chunk has changed since
         if (c->pk_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); predict_release(c); }
@@ -125,9 +131,52 @@ static int predict_workspace(tnml_ctx* c, bool bytes_form) {
         return rc;
     }
     if (bytes_form && !c->pk_x8) { rc = predict_alloc(c, (void**)&c->pk_raw8, (size_t)cap * c->N); if (!rc) rc = predict_alloc(c, (void**)&c->pk_x8, (size_t)cap * c->N); }
-    if (!bytes_form && !c->pk_xphi) { rc = predict_alloc(c, (void**)&c->pk_rawphi, (size_t)2 * cap * c->N * sizeof(double)); if (!rc) rc = predict_alloc(c, (void**)&c->pk_xphi, (size_t)2 * cap * c->N * sizeof(double)); }
+    if (!bytes_form && !c->pk_rawphi) rc = predict_alloc(c, (void**)&c->pk_rawphi, (size_t)2 * cap * c->N * sizeof(double));
+    if (!bytes_form && !f32 && !rc && !c->pk_xphi) rc = predict_alloc(c, (void**)&c->pk_xphi, (size_t)2 * cap * c->N * sizeof(double));
+    if (!bytes_form && f32 && !rc && !c->pk_xphi32) rc = predict_alloc(c, (void**)&c->pk_xphi32, (size_t)2 * cap * c->N * sizeof(float));
     if (rc) predict_release(c);
     return rc;
+}
+// The fp32 side of the workspace (first call under predict_dtype = 1): the site table of the fp32 copy of W, the range flag, the copy itself
+// (grown when W has grown) and, under an input map, the table rounded to fp32.  Then the copy is made: W may have changed since the last call.
+static int predict_workspace32(tnml_ctx* c, bool mapped, const std::vector<ChainSite>& tab) {
+    int rc = 0;
+    if (!c->pk_tab32) rc = predict_alloc(c, (void**)&c->pk_tab32, (size_t)c->N * sizeof(ChainSite32));
+    if (!rc && !c->pk_flag) {
+        rc = predict_alloc(c, (void**)&c->pk_flag, sizeof(int));
+        if (!rc && hipMemsetAsync(c->pk_flag, 0, sizeof(int), c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict: memset failed");
+    }
+    std::vector<size_t> off(c->N);
+    size_t total = 0, largest = 0;
+    for (int j = 1; j <= c->N; ++j) {
+        const size_t e = (size_t)2 * tab[j - 1].ml * tab[j - 1].mr * (j == c->c0 ? c->nl() : 1);
+        off[j - 1] = total; total += (e + 3) / 4 * 4; largest = std::max(largest, e);
+    }
+    if (!rc && total > c->pk_w32_cap) {
+        if (c->pk_w32) {
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return tnml_fail(c, "tnml_predict: hipStreamSynchronize failed");
+            (void)hipFree(c->pk_w32); c->pk_w32 = nullptr;
+            c->bytes -= (int64_t)(c->pk_w32_cap * sizeof(float)); c->pk_bytes -= (int64_t)(c->pk_w32_cap * sizeof(float)); c->pk_w32_cap = 0;
+        }
+        rc = predict_alloc(c, (void**)&c->pk_w32, total * sizeof(float));
+        if (!rc) c->pk_w32_cap = total;
+    }
+    if (!rc && mapped && !c->pk_mtab32) {
+        std::vector<float> t32(c->im_table.size());
+        for (size_t k = 0; k < t32.size(); ++k) t32[k] = (float)c->im_table[k];
+        const int64_t before = c->pk_bytes;
+        rc = predict_alloc(c, (void**)&c->pk_mtab32, t32.size() * sizeof(float));
+        if (!rc) c->pk_mtab32_bytes = c->pk_bytes - before;
+        if (!rc && hipMemcpyAsync(c->pk_mtab32, t32.data(), t32.size() * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict_u8: copy of the input map's table failed");
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict_u8: hipStreamSynchronize failed");
+    }
+    if (rc) { predict_release(c); return rc; }
+    std::vector<ChainSite32> t32(c->N);
+    for (int j = 1; j <= c->N; ++j) t32[j - 1] = ChainSite32{c->pk_w32 + off[j - 1], tab[j - 1].ml, tab[j - 1].mr};
+    HIPCK(c, hipMemcpyAsync(c->pk_tab32, t32.data(), sizeof(ChainSite32) * c->N, hipMemcpyHostToDevice, c->stream));
+    TCK(launch_chain_pack32(c, c->pk_tab, c->pk_tab32, c->N, c->c0, c->nl(), largest));
+    HIPCK(c, hipStreamSynchronize(c->stream));                  // (t32 leaves scope with this call)
+    return 0;
 }
 static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, double* weights, int32_t* pred) {
     if (!c) return tnml_fail(c, "%s: null argument", who);
@@ -137,23 +186,58 @@ static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* 
     TCK(check_W(c));
     int maxbond = 1;
     for (int j = 1; j <= c->N; ++j) maxbond = std::max(maxbond, std::max(c->W[j].ml, c->W[j].mr));
-    if (maxbond > TNML_CHAIN_MAXM)
+    const bool f32 = c->predict_dtype == TNML_PREDICT_F32;
+    if (f32 && maxbond > TNML_CHAIN32_MAXM)
+        return tnml_fail(c, "%s: W has a bond of dimension %d, the fp32 chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, maxbond, TNML_CHAIN32_MAXM);
+    if (!f32 && maxbond > TNML_CHAIN_MAXM)
         return tnml_fail(c, "%s: W has a bond of dimension %d, the chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, maxbond, TNML_CHAIN_MAXM);
     if (n == 0) return 0;
     if (!pixels && !phi) return tnml_fail(c, "%s: null argument", who);
     HIPCK(c, hipSetDevice(c->cfg.device));
     const bool bytes_form = pixels != nullptr;
-    TCK(predict_workspace(c, bytes_form));
+    TCK(predict_workspace(c, bytes_form, f32));
     const int cs = c->single() ? 1 : c->c0, nl = c->nl();       // the centre tnml_classify takes
     std::vector<ChainSite> tab(c->N);
     for (int j = 1; j <= c->N; ++j) tab[j - 1] = ChainSite{c->W[j].a, c->W[j].ml, c->W[j].mr};
     HIPCK(c, hipMemcpyAsync(c->pk_tab, tab.data(), sizeof(ChainSite) * c->N, hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (tab leaves scope with this call)
+    if (f32) TCK(predict_workspace32(c, bytes_form && c->im_set, tab));
     const bool mapped = bytes_form && c->im_set;                // the input map: S bytes per image -> block sums -> table look-ups inside the chain kernel
     const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
     const size_t per_img = mapped ? (size_t)sg.S : (size_t)c->N * (bytes_form ? 1 : 2 * sizeof(double));
     for (int64_t off = 0; off < n; off += c->predict_chunk) {
         const int cnt = (int)std::min<int64_t>(c->predict_chunk, n - off);
+        if (f32) {                                              // predict_dtype = 1: the same staging, features rounded to fp32, k_chain32 on the fp32 copy of W
+            ChainArgs32 a;
+            a.sites = c->pk_tab32; a.N = c->N; a.cs = cs; a.nl = nl; a.single = c->single() ? 1 : 0;
+            a.xT = nullptr; a.phiT = nullptr; a.ld = c->pk_cap; a.cnt = cnt; a.wout = c->pk_w; a.pred = c->pk_pred; a.flag = c->pk_flag;
+            if (mapped) {
+                HIPCK(c, hipMemcpyAsync(c->pk_mraw, pixels + (size_t)off * per_img, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+                { ProfScope ps(c, KC_PACK); TCK(launch_stage_codes(c, c->pk_mraw, sg, cnt, c->pk_cap, c->pk_codes)); }
+                a.codeT = c->pk_codes; a.table = c->pk_mtab32;
+            } else if (bytes_form) {
+                HIPCK(c, hipMemcpyAsync(c->pk_raw8, pixels + (size_t)off * c->N, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+                TCK(launch_chain_stage(c, c->pk_raw8, nullptr, c->N, cnt, c->pk_cap, c->pk_x8, nullptr));
+                a.xT = c->pk_x8;
+            } else {
+                HIPCK(c, hipMemcpyAsync(c->pk_rawphi, phi + (size_t)off * c->N * 2, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+                TCK(launch_chain32_stage_phi(c, c->pk_rawphi, c->N, cnt, c->pk_cap, c->pk_xphi32));
+                a.phiT = c->pk_xphi32;
+            }
+            // the scratch of the parked vectors is the fp64 path's: cap x ru16(min(maxm, 512)) doubles hold cap x ru16(min(maxm, 1024)) floats
+            TCK(launch_chain32(c, a, maxbond, chain32_tile(c, maxbond, cnt), (float*)c->pk_park, 2 * c->pk_park_elems));
+            int flag = 0;
+            if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->pk_w, sizeof(double) * (size_t)cnt * nl, hipMemcpyDeviceToHost, c->stream));
+            if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->pk_pred, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+            HIPCK(c, hipMemcpyAsync(&flag, c->pk_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            SYNCK(c, c->stream);
+            if (flag) {
+                HIPCK(c, hipMemsetAsync(c->pk_flag, 0, sizeof(int), c->stream));
+                HIPCK(c, hipStreamSynchronize(c->stream));
+                return tnml_fail(c, "%s: predict_dtype = 1 (fp32): a weight of images %lld..%lld is not finite, the chain has left the fp32 range: use fp64 (predict_dtype = 0)", who, (long long)off, (long long)off + cnt - 1);
+            }
+            continue;
+        }
         if (mapped) {
             HIPCK(c, hipMemcpyAsync(c->pk_mraw, pixels + (size_t)off * per_img, per_img * cnt, hipMemcpyHostToDevice, c->stream));
             { ProfScope ps(c, KC_PACK); TCK(launch_stage_codes(c, c->pk_mraw, sg, cnt, c->pk_cap, c->pk_codes)); }

@@ -293,6 +293,17 @@ struct tnml_ctx {
     int predict_chunk = TNML_PREDICT_CHUNK_DEFAULT;        // option "predict_chunk": images staged, launched (one k_chain launch) and copied back per trip of the host loop
     int predict_tile = 0;            // test knob (option "predict_tile"): images per workgroup of k_chain, 16 / 32 / 64 (capped by the LDS budget); 0: by bond dimension and image count
     bool attr_chain = false, attr_chain_codes = false;
+    // option "predict_dtype": 0 the fp64 chain kernel (kernels_chain.hip), 1 the fp32 one (kernels_chain32.hip).  Its workspace, allocated by the
+    // first fp32 call (counted in `bytes` and pk_bytes, freed with the rest): the fp32 copy of W, re-made by every call and grown when W has grown,
+    // its site table, the range flag, and what the staging of the input form needs
+    int predict_dtype = 0;
+    bool attr_chain32 = false, attr_chain32_codes = false;
+    float* pk_w32 = nullptr; size_t pk_w32_cap = 0;   // [pk_w32_cap] floats: every site tensor, each starting at a multiple of 4 floats
+    struct ChainSite32* pk_tab32 = nullptr;            // [N] per-site table of the copy
+    int* pk_flag = nullptr;                            // raised by k_chain32 when a weight is not finite
+    float* pk_xphi32 = nullptr;                        // features of a chunk site-first [N][2][pk_cap], rounded to fp32 (first fp32 tnml_predict_phi)
+    int64_t pk_mtab32_bytes = 0;
+    float* pk_mtab32 = nullptr;                        // the input map's table rounded to fp32 [ncodes][2] (first fp32 tnml_predict_u8 under a map)
     // its workspace, allocated by the first predict call (counted in `bytes`, freed by tnml_destroy); pk_cap = predict_chunk rounded up to 64 when it was sized
     int pk_cap = 0; int64_t pk_bytes = 0;
     struct ChainSite* pk_tab = nullptr;   // [N] per-site table (ml, mr, address)
@@ -553,6 +564,28 @@ int launch_codes_phi(tnml_ctx* c, const uint16_t* codes, const void* tab, int N,
 int launch_chain_stage(tnml_ctx* c, const uint8_t* pix, const double* phi, int N, int cnt, int ld, uint8_t* xT, double* phiT);   // exactly one of pix [cnt][N] / phi [cnt][N][2]
 int chain_tile(tnml_ctx* c, int maxbond, int cnt);
 int launch_chain(tnml_ctx* c, ChainArgs a, int maxbond, int T, double* park_ws, size_t park_elems);
+
+// ---- kernels_chain32.hip: the chain kernel in fp32 (option predict_dtype = 1) ----
+#define TNML_CHAIN32_MAXM 1024     /* largest bond dimension k_chain32 serves */
+struct ChainSite32 { const float* a; int ml, mr; };  // a site tensor of the fp32 copy of W (layout of SiteT::a)
+struct ChainArgs32 {
+    const ChainSite32* sites;          // [N] device
+    int N, cs, nl, single;             // as ChainArgs
+    const uint8_t* xT;                 // bytes, site-first [N][ld] -- or
+    const float* phiT;                 // features rounded to fp32, site-first [N][2][ld]
+    int ld, cnt;
+    double* wout; int* pred;           // [cnt][nl] (the fp32 weights widened), [cnt]
+    int mcap = 0; float* park = nullptr;    // set by launch_chain32
+    const uint16_t* codeT = nullptr;   // input map: block sums, site-first [N][ld], with
+    const float* table = nullptr;      // the features [ncodes][2] rounded to fp32
+    int* flag = nullptr;               // |= 1 when a weight is Inf or NaN
+};
+int launch_chain32_stage_phi(tnml_ctx* c, const double* phi, int N, int cnt, int ld, float* phiT);   // features [cnt][N][2] -> fp32 [N][2][ld]; class pack
+// dst[j].a = fl32(src[j].a) for the N sites (tables on the device); lsite: the Label site (1-indexed, <= 0: none) carries nl times the elements;
+// largest: the element count of the largest site (sizes the grid); class pack
+int launch_chain_pack32(tnml_ctx* c, const ChainSite* src, const ChainSite32* dst, int N, int lsite, int nl, size_t largest);
+int chain32_tile(tnml_ctx* c, int maxbond, int cnt);
+int launch_chain32(tnml_ctx* c, ChainArgs32 a, int maxbond, int T, float* park_ws, size_t park_elems);
 
 // ---- eigh.hip -----------------------------------------------------------------------------
 int eigh_tridiagonalize(tnml_ctx* c, const double* A, int n, double* D, double* E, double* tau, double* V, double psd_tol = 0.);   // tau: n doubles, tau[n-1] = number of reflectors

@@ -226,12 +226,17 @@ class TrainStates:
             return None
         return {k: getattr(st, k) for k in ("src_rows", "src_cols", "block", "row0", "col0", "out_rows", "out_cols", "ncodes")}
 
-    def predict(self, pixels=None, phi=None):
+    def predict(self, pixels=None, phi=None, dtype=None):
         """streamed inference on images this context does not hold (tnml_predict_u8 / tnml_predict_phi): pixels[n, N] bytes
         (under an input map: [n, S] raw bytes) or phi[n, N, 2] features -> (weights[n, nl], pred[n]); pred is argmax_l |W_l|
-        (per-label variant: [f > 1/2]).  Reads W only."""
+        (per-label variant: [f > 1/2]).  Reads W only.  dtype "f64" / "f32" sets option predict_dtype for this call and the ones
+        after it (None: leave it): "f32" runs the fp32 chain kernel, weights are its fp32 results widened."""
         if (pixels is None) == (phi is None):
             raise ValueError("need exactly one of pixels or phi")
+        if dtype is not None:
+            if dtype not in _lib.PREDICT_DTYPES:
+                raise ValueError("dtype must be one of %s, got %r" % (sorted(_lib.PREDICT_DTYPES), dtype))
+            self.set_option("predict_dtype", _lib.PREDICT_DTYPES[dtype])
         if pixels is not None:
             x = np.ascontiguousarray(pixels, dtype=np.uint8)
             if x.ndim != 2 or x.shape[1] != self._bytes_per_image:

@@ -141,6 +141,17 @@ inline int predict_chunk_option(tnml_ctx* ctx, long requested) {
     CK(ctx, tnml_set_option(ctx, "predict_chunk", (int)requested));
     return (int)requested;
 }
+// the key `predict_dtype` of the evaluators (f64 | f32, default f64): under predict = yes sets the context option of that name and returns
+// whether the fp32 chain kernel is selected; under predict = no the key has no effect, and f32 is said to be ignored
+inline bool predict_dtype_option(tnml_ctx* ctx, bool predict, const std::string& value) {
+    if (!predict) {
+        if (value == "f32") std::printf("predict_dtype = f32 is ignored: it applies to predict = yes only\n");
+        return false;
+    }
+    if (value != "f64" && value != "f32") { std::printf("predict_dtype=%s not recognized (f64 | f32)\n", value.c_str()); std::exit(1); }
+    CK(ctx, tnml_set_option(ctx, "predict_dtype", value == "f32" ? TNML_PREDICT_F32 : TNML_PREDICT_F64));
+    return value == "f32";
+}
 // fullTest's result table (util.h:186-199) from the images and the misclassified images per label
 inline void print_fulltest_table(const int64_t counts[10], const int64_t nincorrect[10]) {
     long nte = 0, tninc = 0;

@@ -7,7 +7,8 @@
 // (f64 | mixed | f32), `Ntest` (per-label cap; the reference takes the whole test set), `imglen` and
 // `feature_scale` as in the fixedL driver (they must match the values W was trained with); `predict` (yes | no,
 // default no): a data-less context sized by W alone, the test set streamed through tnml_predict_u8 / tnml_predict_phi
-// in chunks of `predict_chunk` images (0: the library's default) and counted on the host; `input_map` (yes | no, default no): the
+// in chunks of `predict_chunk` images (0: the library's default) and counted on the host, `predict_dtype` (f64 | f32, default f64)
+// choosing the chain kernel's arithmetic; `input_map` (yes | no, default no): the
 // images reach the device as the bytes of the idx file, the device does reduce(), the feature map and the transpose (tnml_set_input_map).
 #include <cmath>
 #include <cstdio>
@@ -35,6 +36,7 @@ int main(int argc, const char* argv[]) {
         const double feature_scale = input.getReal("feature_scale", 1.);
         const bool predict = input.getYesNo("predict", false);
         const long predict_chunk = input.getInt("predict_chunk", 0);
+        const std::string predict_dtype = input.getString("predict_dtype", "f64");
         const bool input_map = input.getYesNo("input_map", false);
         int dtype;
         if (!parse_dtype(precision, false, &dtype)) return 1;
@@ -75,6 +77,7 @@ int main(int argc, const char* argv[]) {
             else CK(ctx, tnml_set_data_phi(ctx, phi.data(), test.labels.data()));
         }
         upload_mps(ctx, psi);
+        const bool p32 = predict_dtype_option(ctx, predict, predict_dtype);
 
         std::printf("Running full test of %s\n", fname.c_str());                       // :97
         int64_t counts[10] = {0}, ninc[10] = {0};
@@ -82,7 +85,7 @@ int main(int argc, const char* argv[]) {
             CK(ctx, tnml_classify(ctx, nullptr, nullptr, counts, ninc));
         } else {
             const int chunk = predict_chunk_option(ctx, predict_chunk);
-            std::printf("Device path: streamed chain kernel (%s), %d images per chunk\n", bytes_in ? "tnml_predict_u8" : "tnml_predict_phi", chunk);
+            std::printf("Device path: streamed chain kernel (%s%s), %d images per chunk\n", bytes_in ? "tnml_predict_u8" : "tnml_predict_phi", p32 ? ", fp32" : "", chunk);
             std::vector<int32_t> pred(totNtest);
             if (bytes_in) CK(ctx, tnml_predict_u8(ctx, totNtest, bytes, nullptr, pred.data()));
             else CK(ctx, tnml_predict_phi(ctx, totNtest, phi.data(), nullptr, pred.data()));

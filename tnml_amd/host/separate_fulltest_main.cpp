@@ -7,7 +7,7 @@
 // argmax_n |o_n| (first maximum), costs[n] += (n == l) ? (o_n - 1)^2 : o_n^2.  Extensions: `feature` (normal | series),
 // `device`, `precision`, `Ntest`, `imglen` honoured as block-mean down-sampling, `feature_scale`; `predict` (yes | no,
 // default no): a data-less context sized by the ten W alone, the test set streamed through tnml_predict_phi in chunks of
-// `predict_chunk` images (0: the library's default); `input_map` (yes | no, default no): the bytes of the idx file through
+// `predict_chunk` images (0: the library's default), `predict_dtype` (f64 | f32, default f64) choosing the chain kernel's arithmetic; `input_map` (yes | no, default no): the bytes of the idx file through
 // tnml_set_input_map and tnml_set_data_u8 / tnml_predict_u8 instead of host features.
 #include <cmath>
 #include <cstdio>
@@ -35,6 +35,7 @@ int main(int argc, const char* argv[]) {
         const double feature_scale = input.getReal("feature_scale", 1.);
         const bool predict = input.getYesNo("predict", false);
         const long predict_chunk = input.getInt("predict_chunk", 0);
+        const std::string predict_dtype = input.getString("predict_dtype", "f64");
         const bool input_map = input.getYesNo("input_map", false);
         int dtype;
         if (!parse_dtype(precision, false, &dtype)) return 1;
@@ -78,7 +79,8 @@ int main(int argc, const char* argv[]) {
             std::vector<double>().swap(phi);
         }
         std::printf("Running full test\n");                                            // :165
-        if (predict) std::printf("Device path: streamed chain kernel (%s), %d images per chunk\n", input_map ? "tnml_predict_u8" : "tnml_predict_phi", predict_chunk_option(ctx, predict_chunk));
+        const bool p32 = predict_dtype_option(ctx, predict, predict_dtype);
+        if (predict) std::printf("Device path: streamed chain kernel (%s%s), %d images per chunk\n", input_map ? "tnml_predict_u8" : "tnml_predict_phi", p32 ? ", fp32" : "", predict_chunk_option(ctx, predict_chunk));
         std::vector<std::vector<double>> o(NLW, std::vector<double>(totNtest));        // o[n][image] = overlap(Ws[n], testimg), :38
         for (int n = 0; n < NLW; ++n) {
             upload_mps(ctx, Ws[n]);

@@ -15,6 +15,7 @@ import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 NL = 10
 MAX_PASS = 64
 DTYPES = {"f32": 0, "f64_e32": 1, "f64": 2, "bf16": 3, "bf16x3": 4}    # TNML_F32 / TNML_F64_E32 / TNML_F64 / TNML_BF16 / TNML_BF16X3 (include/tnml.h)
+PREDICT_DTYPES = {"f64": 0, "f32": 1}    # TNML_PREDICT_F64 / TNML_PREDICT_F32: option predict_dtype
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtnml.so")
 
