@@ -334,7 +334,7 @@ int tnml_classify(tnml_ctx* ctx, double* weights, int32_t* pred, int64_t count[T
  *                                           bytes as given, 16-bit block sums site-first, the fp64 table); released by every
  *                                           tnml_set_input_map call and re-made by the next tnml_predict_u8 under a map
  *           + 32 N C                        bytes from the first tnml_predict_phi on (features as given and site-first).
- * Option "predict_dtype" = TNML_PREDICT_F32 selects the fp32 chain kernel (kernels_chain32.hip; v_mfma_f32_16x16x4_f32, tiles of 64
+ * Option "predict_dtype" = TNML_PREDICT_F32 selects the fp32 chain kernel (k_chain<float>, kernels_chain.hip; v_mfma_f32_16x16x4_f32, tiles of 64
  * images up to bond 256, 32 up to 512, 16 up to 1 024) for the calls that follow; TNML_PREDICT_F64 (the default) is the path above, bit
  * for bit.  Under fp32 W is rounded to fp32 once per call, the features are formed in fp64 as above and rounded once, every product
  * and sum is IEEE fp32 in a fixed order (the kernel's header states it; per image independent of n, chunk and tile), weights receives

@@ -1,4 +1,4 @@
-"""A bit-exact numpy model of the fp32 chain kernel (kernels_chain32.hip, option predict_dtype = 1): operands rounded where the kernel
+"""A bit-exact numpy model of the fp32 chain kernel (k_chain<float> in kernels_chain.hip, option predict_dtype = 1): operands rounded where the kernel
 rounds them, every sum one fp32 fma chain in the kernel's order.
 
   1. A32 = fl32(A), phi32 = fl32(phi) with phi as the fp64 path forms it;

@@ -1,4 +1,4 @@
-"""Streamed inference in fp32 (option predict_dtype = 1, kernels_chain32.hip) against the bit-exact model of its arithmetic
+"""Streamed inference in fp32 (option predict_dtype = 1, k_chain<float> in kernels_chain.hip) against the bit-exact model of its arithmetic
 (chain32_model.py, proved on the host by test_chain32_model_host.py): np.array_equal on the weights and on pred, never a tolerance.
 Contexts are data-less unless the test is about a training context."""
 import os

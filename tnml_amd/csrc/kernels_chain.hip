@@ -24,38 +24,105 @@
 // __syncthreads() per site.  The finished right-chain vector R waits for the centre site in a third tile when three fit the 160 KiB,
 // otherwise in the workgroup's own slice of a global scratch (written once, read once by the same workgroup).  For T >= 32 the column
 // index of odd rows is XORed with 16: the two k rows a half-wave reads with one ds_read_b64 then fall on different banks.
+//
+// Element type.  Everything below is written once over the element type E: double (option predict_dtype = 0, v_mfma_f64_16x16x4_f64 on
+// W where it lives) and float (predict_dtype = 1, v_mfma_f32_16x16x4_f32 on the fp32 copy k_chain_pack32 makes of W once per call: fl32
+// of every element, in the layout SiteT::a has, all sites packed into one workspace).  What differs between the two -- the MFMA and its
+// C/D map, the LDS swizzle, the non-finite flag, the tile thresholds -- is in ChainT<E>, each with its reasoning.  In fp32 the features
+// are formed in fp64 by the expressions of the fp64 path and rounded once: the byte expression here in the kernel, the given phi by the
+// staging kernel, the input map's table by the host.
+//
+// Arithmetic of the fp32 kernel (IEEE fp32, fixed order; per image independent of n, chunk, tile width and tile position):
+//   * the B operand of every product is fl32(phi32_s * v): one v_mul_f32, never fused (the file is compiled with -ffp-contract=off);
+//   * the contraction index kk runs over the memory order of the site tensor as above (right chain kk = s + 2 r, left chain and centre
+//     kk = a + ml s) in blocks of 16; lane (row = lane & 15, q = lane >> 4) holds kk = base + 4 q + i, i = 0..3, and MFMA step i
+//     multiplies element i.  The MFMA is a k-ordered fmaf chain, so every output element is ONE chain from 0:
+//         for base = 0, 16, ..: for i = 0..3: for q = 0..3:  acc = fmaf(a[kk], b[kk], acc),  kk = base + 4 q + i
+//     kk >= K inside the last block contribute fmaf(0, 0, acc);
+//   * centre, per label: one such step, then w = fmaf(T[r], R[r], w) for r = 0 .. mr-1 ascending, one image per thread; the output is
+//     (double)w; pred = first maximum of |w| over the labels (per-label variant: [w > 0.5f]), decided on the fp32 values.
+//   tests/chain32_model.py restates this order; tests/test_predict_f32_gpu.py holds the kernel to it bit for bit.
+// A weight that is not finite (the chain has left the fp32 range) raises g.flag with a vector atomic; the host fails the call.
+//
+// Latency (fp32).  The MFMA issues every 32 cycles per SIMD and has 40 cycles of dependent latency.  At T = 16 a wave has one
+// accumulator, so alone it would issue every 40 cycles; the workgroup's 8 waves sit two to a SIMD and two dependent chains ask for 64
+// issue cycles per 40, so the pipe, not the latency, is the limit whenever a site has 8 or more row tiles.  No second row tile is
+// interleaved.
 #include "tnml_internal.h"
-
-typedef double chain_d4 __attribute__((ext_vector_type(4)));
-typedef double chain_d2 __attribute__((ext_vector_type(2)));
 
 #define CHAIN_THREADS 512
 #define CHAIN_WAVES 8
 
-template <int NCT>
-static __device__ __forceinline__ int chain_idx(int k, int n) {
-    return k * (16 * NCT) + (NCT > 1 ? (n ^ ((k & 1) << 4)) : n);
-}
+// what differs between the element types, and nothing else
+template <typename E> struct ChainT;
+template <> struct ChainT<double> {
+    typedef double v4 __attribute__((ext_vector_type(4)));
+    typedef double v2 __attribute__((ext_vector_type(2)));
+    // two tiles of ru16(maxbond) x T doubles <= 128 KiB: T = 64 up to bond T64, 32 up to T32, 16 up to MAXM
+    static constexpr int T64 = 128, T32 = 256, MAXM = TNML_CHAIN_MAXM;
+    static constexpr const char* what = "";             // in front of "chain kernel: ..." in every message
+    static constexpr const char* elems = "doubles";
+    // LDS swizzle: see the header (for T >= 32 the column index of odd rows is XORed with 16)
+    template <int NCT>
+    static __device__ __forceinline__ int idx(int k, int n) {
+        return k * (16 * NCT) + (NCT > 1 ? (n ^ ((k & 1) << 4)) : n);
+    }
+    // C/D map of the fp64 MFMA: column = lane & 15, row = (lane >> 4) + 4 reg
+    static __device__ __forceinline__ int row(int rt, int q, int r) { return rt * 16 + q + 4 * r; }
+    static __device__ __forceinline__ v4 mfma(double a, double b, v4 acc) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0); }
+    static __device__ __forceinline__ double fma(double a, double b, double c) { return ::fma(a, b, c); }
+    static __device__ __forceinline__ double abs(double w) { return fabs(w); }
+    static __device__ __forceinline__ bool bad(double) { return false; }
+};
+template <> struct ChainT<float> {
+    typedef float v4 __attribute__((ext_vector_type(4)));
+    typedef float v2 __attribute__((ext_vector_type(2)));
+    // two tiles of ru16(maxbond) x T floats <= 128 KiB: T = 64 up to bond 256, 32 up to 512, 16 up to 1 024
+    static constexpr int T64 = 256, T32 = 512, MAXM = TNML_CHAIN32_MAXM;
+    static constexpr const char* what = "fp32 ";
+    static constexpr const char* elems = "floats";
+    // LDS swizzle.  ds_read_b32 / ds_write_b32 serve a wave in two groups of 32 lanes over 32 banks, so the two k rows (q = 0, 1 and
+    // q = 2, 3) of a group, 16 floats each, must fall on different halves of the banks.  Those rows are 2 apart in the right chain
+    // (row = base / 2 + 2 q + (i >> 1): the lower one has row mod 4 in {0, 1}) and 4 apart in the left chain, the centre and the C/D store
+    // (row = 16 rt + 4 q + reg).  g(k) = bit 1 of k xor bit 2 of k differs across both kinds of pair; it is put into address bit 4 (in floats):
+    //   T >= 32: column ^ (g(k) << 4), the row pitch being a multiple of 32 floats;
+    //   T = 16:  the rows of every aligned group of 8 are permuted, row bits (b2 b1 b0) -> (b2, b0, b1 ^ b2), so that bit 0 of the stored
+    //            row -- address bit 4 -- is g(k).
+    // (a left-chain block that straddles kk = ml pairs rows 4 - ml apart: at most one block per site keeps a 2-way conflict.)
+    template <int NCT>
+    static __device__ __forceinline__ int idx(int k, int n) {
+        const int g = ((k >> 1) ^ (k >> 2)) & 1;
+        if (NCT > 1) return k * (16 * NCT) + (n ^ (g << 4));
+        return ((k & ~3) | ((k & 1) << 1) | g) * 16 + n;
+    }
+    // C/D map of the f32 MFMA: column = lane & 15, row = 4 (lane >> 4) + reg -- not the fp64 form's (lane >> 4) + 4 reg
+    static __device__ __forceinline__ int row(int rt, int q, int r) { return rt * 16 + 4 * q + r; }
+    static __device__ __forceinline__ v4 mfma(float a, float b, v4 acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
+    static __device__ __forceinline__ float fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+    static __device__ __forceinline__ float abs(float w) { return __builtin_fabsf(w); }
+    static __device__ __forceinline__ bool bad(float wa) { return !(wa <= 3.402823466e+38f); }      // Inf or NaN
+};
 
 // features of site j (1-indexed) for the NCT columns of this lane: image tile0 + 16 ct + (lane & 15); images beyond cnt get (0, 0)
-// SRC 0: bytes through the built-in expression (g.xT) or fp64 features (g.phiT), chosen at run time as before the input map existed;
-// SRC 1: the input map -- one 2-byte block sum and one dependent 16-byte table row per site and column (g.codeT, g.table; the table
+// SRC 0: bytes through the built-in expression (g.xT) or staged features (g.phiT), chosen at run time as before the input map existed;
+// SRC 1: the input map -- one 2-byte block sum and one dependent table row per site and column (g.codeT, g.table; the table
 // is at most 261 KB and stays in L2).  The source is a template parameter so that the SRC 0 instantiations carry nothing of it.
-template <int NCT, int SRC>
-static __device__ __forceinline__ void chain_features(const ChainArgs& g, int j, int img0, double (&p0)[NCT], double (&p1)[NCT]) {
+template <typename E, int NCT, int SRC>
+static __device__ __forceinline__ void chain_features(const ChainArgs<E>& g, int j, int img0, E (&p0)[NCT], E (&p1)[NCT]) {
+    typedef typename ChainT<E>::v2 v2;
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
         const int n = img0 + 16 * ct;
-        double f0 = 0., f1 = 0.;
+        E f0 = 0, f1 = 0;
         if (n < g.cnt) {
             if (SRC == 1) {
                 const unsigned code = g.codeT[(size_t)(j - 1) * g.ld + n];
-                const chain_d2 f = *(const chain_d2*)(g.table + (size_t)2 * code);
+                const v2 f = *(const v2*)(g.table + (size_t)2 * code);
                 f0 = f.x; f1 = f.y;
-            } else if (g.xT) {                         // the expression of k_features_u8<double> (kernels_stream.hip)
+            } else if (g.xT) {                         // the expression of k_features_u8<double> (kernels_stream.hip), formed in fp64, rounded once
                 const double gq = (double)g.xT[(size_t)(j - 1) * g.ld + n] / 255.;
-                f0 = 1.;
-                f1 = (gq / 255.) / 4.;
+                f0 = 1;
+                f1 = (E)((gq / 255.) / 4.);
             } else {
                 f0 = g.phiT[((size_t)(j - 1) * 2 + 0) * g.ld + n];
                 f1 = g.phiT[((size_t)(j - 1) * 2 + 1) * g.ld + n];
@@ -66,14 +133,15 @@ static __device__ __forceinline__ void chain_features(const ChainArgs& g, int j,
 }
 
 // the four values kk = base + 4 q + i of output row `orow` (see the header); masked outside the tensor
-template <bool LEFT>
-static __device__ __forceinline__ void chain_load_a(const double* __restrict__ A, int ml, int M, int K, int orow, int kk0, double (&a)[4]) {
-    a[0] = a[1] = a[2] = a[3] = 0.;
+template <typename E, bool LEFT>
+static __device__ __forceinline__ void chain_load_a(const E* __restrict__ A, int ml, int M, int K, int orow, int kk0, E (&a)[4]) {
+    typedef typename ChainT<E>::v2 v2;
+    a[0] = a[1] = a[2] = a[3] = 0;
     if (orow >= M) return;
-    if (LEFT) {                                 // K = 2 ml is even and kk0 a multiple of 4: pairs are inside or outside together, 16-byte aligned
-        const double* p = A + (size_t)2 * ml * orow + kk0;
-        if (kk0 < K)     { const chain_d2 v = *(const chain_d2*)p;       a[0] = v.x; a[1] = v.y; }
-        if (kk0 + 2 < K) { const chain_d2 v = *(const chain_d2*)(p + 2); a[2] = v.x; a[3] = v.y; }
+    if (LEFT) {                                 // K = 2 ml is even and kk0 a multiple of 4: pairs are inside or outside together, aligned to the pair
+        const E* p = A + (size_t)2 * ml * orow + kk0;
+        if (kk0 < K)     { const v2 v = *(const v2*)p;       a[0] = v.x; a[1] = v.y; }
+        if (kk0 + 2 < K) { const v2 v = *(const v2*)(p + 2); a[2] = v.x; a[3] = v.y; }
     } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) if (kk0 + i < K) a[i] = A[(size_t)ml * (kk0 + i) + orow];
@@ -81,21 +149,22 @@ static __device__ __forceinline__ void chain_load_a(const double* __restrict__ A
 }
 
 // one site: vout[M][T] = (site matrix) x (phi . vin); vin is an LDS tile, vout an LDS tile or the parked vector
-template <int NCT, bool LEFT>
-static __device__ __forceinline__ void chain_step(const double* __restrict__ A, int ml, int mr, const double* vin, double* vout,
-                                                  const double (&p0)[NCT], const double (&p1)[NCT], int wave, int lane) {
+template <typename E, int NCT, bool LEFT>
+static __device__ __forceinline__ void chain_step(const E* __restrict__ A, int ml, int mr, const E* vin, E* vout,
+                                                  const E (&p0)[NCT], const E (&p1)[NCT], int wave, int lane) {
+    typedef ChainT<E> Tr;
     const int c16 = lane & 15, q = lane >> 4;
     const int K = LEFT ? 2 * ml : 2 * mr, M = LEFT ? mr : ml;
     const int nrt = (M + 15) >> 4;
     for (int rt = wave; rt < nrt; rt += CHAIN_WAVES) {
         const int orow = rt * 16 + c16;         // the A fragment's row of this lane
-        chain_d4 acc[NCT];
+        typename Tr::v4 acc[NCT];
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) acc[ct] = chain_d4{0., 0., 0., 0.};
-        double a[4], an[4] = {0., 0., 0., 0.};
-        chain_load_a<LEFT>(A, ml, M, K, orow, 4 * q, a);
+        for (int ct = 0; ct < NCT; ++ct) acc[ct] = typename Tr::v4{0, 0, 0, 0};
+        E a[4], an[4] = {0, 0, 0, 0};
+        chain_load_a<E, LEFT>(A, ml, M, K, orow, 4 * q, a);
         for (int base = 0; base < K; base += 16) {
-            if (base + 16 < K) chain_load_a<LEFT>(A, ml, M, K, orow, base + 16 + 4 * q, an);     // the next block's values, in flight during this block's MFMAs
+            if (base + 16 < K) chain_load_a<E, LEFT>(A, ml, M, K, orow, base + 16 + 4 * q, an);  // the next block's values, in flight during this block's MFMAs
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int kk = base + 4 * q + i;
@@ -105,55 +174,56 @@ static __device__ __forceinline__ void chain_step(const double* __restrict__ A, 
                 else      { s = kk & 1; vr = kk >> 1; }
 #pragma unroll
                 for (int ct = 0; ct < NCT; ++ct) {
-                    double b = 0.;
-                    if (kok) b = (s ? p1[ct] : p0[ct]) * vin[chain_idx<NCT>(vr, 16 * ct + c16)];
-                    acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b, acc[ct], 0, 0, 0);
+                    E b = 0;
+                    if (kok) b = (s ? p1[ct] : p0[ct]) * vin[Tr::template idx<NCT>(vr, 16 * ct + c16)];
+                    acc[ct] = Tr::mfma(a[i], b, acc[ct]);
                 }
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) a[i] = an[i];
         }
-        // C/D map of the fp64 MFMA: column = lane & 15, row = (lane >> 4) + 4 reg
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int row = rt * 16 + q + 4 * r;
-                if (row < M) vout[chain_idx<NCT>(row, 16 * ct + c16)] = acc[ct][r];
+                const int row = Tr::row(rt, q, r);
+                if (row < M) vout[Tr::template idx<NCT>(row, 16 * ct + c16)] = acc[ct][r];
             }
     }
 }
 
-template <int NCT, int SRC>
-__global__ __launch_bounds__(CHAIN_THREADS) void k_chain(const ChainArgs g) {
+template <typename E, int NCT, int SRC>
+__global__ __launch_bounds__(CHAIN_THREADS) void k_chain(const ChainArgs<E> g) {
+    typedef ChainT<E> Tr;
     constexpr int T = 16 * NCT;
-    extern __shared__ __attribute__((aligned(16))) double ch_lds[];
+    extern __shared__ __attribute__((aligned(16))) unsigned char ch_lds_raw[];
+    E* const ch_lds = reinterpret_cast<E*>(ch_lds_raw);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tile0 = blockIdx.x * T;
     const size_t tile_elems = (size_t)g.mcap * T;
-    double* buf[2] = {ch_lds, ch_lds + tile_elems};
-    double* park = g.park ? g.park + (size_t)blockIdx.x * tile_elems : ch_lds + 2 * tile_elems;
+    E* buf[2] = {ch_lds, ch_lds + tile_elems};
+    E* park = g.park ? g.park + (size_t)blockIdx.x * tile_elems : ch_lds + 2 * tile_elems;
     const int N = g.N, cs = g.cs, nright = N - cs;
     // walk order: N .. cs+1 (right chain), 1 .. cs-1 (left chain), cs (centre)
     auto site_at = [&](int t) { return t < nright ? N - t : (t < N - 1 ? t - nright + 1 : cs); };
 
-    double p0[NCT], p1[NCT], q0[NCT], q1[NCT];
+    E p0[NCT], p1[NCT], q0[NCT], q1[NCT];
     const int img0 = tile0 + (lane & 15);
-    chain_features<NCT, SRC>(g, site_at(0), img0, p0, p1);
-    if (tid < T) { buf[0][chain_idx<NCT>(0, tid)] = 1.; if (nright == 0) park[chain_idx<NCT>(0, tid)] = 1.; }
+    chain_features<E, NCT, SRC>(g, site_at(0), img0, p0, p1);
+    if (tid < T) { buf[0][Tr::template idx<NCT>(0, tid)] = 1; if (nright == 0) park[Tr::template idx<NCT>(0, tid)] = 1; }
     __syncthreads();
     int cur = 0;
     for (int t = 0; t < N - 1; ++t) {
         const int j = site_at(t);
-        chain_features<NCT, SRC>(g, site_at(t + 1), img0, q0, q1);           // the next site's features, loaded ahead of the barrier
-        const ChainSite st = g.sites[j - 1];
+        chain_features<E, NCT, SRC>(g, site_at(t + 1), img0, q0, q1);        // the next site's features, loaded ahead of the barrier
+        const ChainSite<E> st = g.sites[j - 1];
         if (t < nright) {
             const bool last = t == nright - 1;
-            chain_step<NCT, false>(st.a, st.ml, st.mr, buf[cur], last ? park : buf[cur ^ 1], p0, p1, wave, lane);
-            if (last) { if (tid < T) buf[cur ^ 1][chain_idx<NCT>(0, tid)] = 1.; }       // the left chain starts from 1
+            chain_step<E, NCT, false>(st.a, st.ml, st.mr, buf[cur], last ? park : buf[cur ^ 1], p0, p1, wave, lane);
+            if (last) { if (tid < T) buf[cur ^ 1][Tr::template idx<NCT>(0, tid)] = 1; }        // the left chain starts from 1
             cur ^= 1;
         } else {
-            chain_step<NCT, true>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
+            chain_step<E, NCT, true>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
             cur ^= 1;
         }
 #pragma unroll
@@ -161,25 +231,28 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_chain(const ChainArgs g) {
         __syncthreads();
     }
     // centre site: per label one left-chain step into the free tile, then the dot with R over r = 0 .. mr-1 in order, one image per thread
-    const ChainSite sc = g.sites[cs - 1];
+    const ChainSite<E> sc = g.sites[cs - 1];
     const int img = tile0 + tid;
-    double best = 0., w0 = 0.; int arg = 0;
+    E best = 0, w0 = 0; int arg = 0; bool bad = false;
     for (int l = 0; l < g.nl; ++l) {
-        chain_step<NCT, true>(sc.a + (size_t)l * sc.ml * 2 * sc.mr, sc.ml, sc.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
+        chain_step<E, NCT, true>(sc.a + (size_t)l * sc.ml * 2 * sc.mr, sc.ml, sc.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
         __syncthreads();
         if (tid < T && img < g.cnt) {
-            double w = 0.;
-            for (int r = 0; r < sc.mr; ++r) w = fma(buf[cur ^ 1][chain_idx<NCT>(r, tid)], park[chain_idx<NCT>(r, tid)], w);
-            g.wout[(size_t)img * g.nl + l] = w;
-            const double wa = fabs(w);
+            E w = 0;
+            for (int r = 0; r < sc.mr; ++r) w = Tr::fma(buf[cur ^ 1][Tr::template idx<NCT>(r, tid)], park[Tr::template idx<NCT>(r, tid)], w);
+            g.wout[(size_t)img * g.nl + l] = (double)w;
+            const E wa = Tr::abs(w);
+            if (Tr::bad(wa)) bad = true;
             if (l == 0) { best = wa; w0 = w; } else if (wa > best) { best = wa; arg = l; }      // first maximum of |W_l| (util.h:42-57)
         }
         __syncthreads();
     }
-    if (tid < T && img < g.cnt) g.pred[img] = g.single ? (w0 > 0.5 ? 1 : 0) : arg;
+    if (tid < T && img < g.cnt) {
+        g.pred[img] = g.single ? (w0 > (E)0.5 ? 1 : 0) : arg;
+        if (bad) atomicOr(g.flag, 1);
+    }
 }
-
-// images-first input -> the chunk-local site-first images the chain kernel reads: bytes [cnt][N] -> [N][ld], features [cnt][N][2] -> [N][2][ld]
+// images-first input -> the chunk-local site-first images the chain kernel reads: bytes [cnt][N] -> [N][ld], features [cnt][N][2] doubles -> [N][2][ld] of E, rounded once
 __global__ void k_chain_stage_u8(const uint8_t* __restrict__ pix, int N, int cnt, int ld, uint8_t* __restrict__ xT) {
     const size_t total = (size_t)N * cnt;
     for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
@@ -187,11 +260,12 @@ __global__ void k_chain_stage_u8(const uint8_t* __restrict__ pix, int N, int cnt
         xT[(size_t)j * ld + n] = pix[(size_t)n * N + j];
     }
 }
-__global__ void k_chain_stage_phi(const double* __restrict__ phi, int N, int cnt, int ld, double* __restrict__ phiT) {
+template <typename E>
+__global__ void k_chain_stage_phi(const double* __restrict__ phi, int N, int cnt, int ld, E* __restrict__ phiT) {
     const size_t total = (size_t)N * 2 * cnt;
     for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int js = (int)(idx / cnt), n = (int)(idx % cnt);          // js = 2 (j - 1) + s
-        phiT[(size_t)js * ld + n] = phi[(size_t)n * 2 * N + js];
+        phiT[(size_t)js * ld + n] = (E)phi[(size_t)n * 2 * N + js];
     }
 }
 
@@ -271,59 +345,82 @@ int launch_codes_phi(tnml_ctx* c, const uint16_t* codes, const void* tab, int N,
     return 0;
 }
 
-int launch_chain_stage(tnml_ctx* c, const uint8_t* pix, const double* phi, int N, int cnt, int ld, uint8_t* xT, double* phiT) {
+template <typename E>
+int launch_chain_stage(tnml_ctx* c, const uint8_t* pix, const double* phi, int N, int cnt, int ld, uint8_t* xT, E* phiT) {
     ProfScope ps(c, KC_PACK);
     const size_t total = (size_t)N * cnt * (pix ? 1 : 2);
     const int grid = (int)std::min<size_t>((total + 255) / 256, 4096);
     if (pix) hipLaunchKernelGGL(k_chain_stage_u8, dim3(grid), dim3(256), 0, c->stream, pix, N, cnt, ld, xT);
-    else     hipLaunchKernelGGL(k_chain_stage_phi, dim3(grid), dim3(256), 0, c->stream, phi, N, cnt, ld, phiT);
+    else     hipLaunchKernelGGL(k_chain_stage_phi<E>, dim3(grid), dim3(256), 0, c->stream, phi, N, cnt, ld, phiT);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+template int launch_chain_stage<double>(tnml_ctx*, const uint8_t*, const double*, int, int, int, uint8_t*, double*);
+template int launch_chain_stage<float>(tnml_ctx*, const uint8_t*, const double*, int, int, int, uint8_t*, float*);
+
+// W -> its fp32 copy: blockIdx.y is the site, src[site] the fp64 tensor where it lives, dst[site] its place in the packed workspace;
+// the Label site `lsite` (1-indexed; none: <= 0) carries nl times the elements
+__global__ void k_chain_pack32(const ChainSite<double>* __restrict__ src, const ChainSite<float>* __restrict__ dst, int lsite, int nl) {
+    const ChainSite<double> s = src[blockIdx.y];
+    float* d = const_cast<float*>(dst[blockIdx.y].a);
+    const size_t total = (size_t)2 * s.ml * s.mr * ((int)blockIdx.y + 1 == lsite ? nl : 1);
+    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) d[idx] = (float)s.a[idx];
+}
+int launch_chain_pack32(tnml_ctx* c, const ChainSite<double>* src, const ChainSite<float>* dst, int N, int lsite, int nl, size_t largest) {
+    if (N < 1 || N > 65535) return tnml_fail(c, "fp32 copy of W: %d sites", N);
+    ProfScope ps(c, KC_PACK);
+    const int gx = (int)std::max<size_t>(1, std::min<size_t>((largest + 255) / 256, 64));
+    hipLaunchKernelGGL(k_chain_pack32, dim3(gx, N), dim3(256), 0, c->stream, src, dst, lsite, nl);
     HIPCK(c, hipGetLastError());
     return 0;
 }
 
-// tile width for a chunk of cnt images at largest bond dimension maxbond (<= TNML_CHAIN_MAXM): the widest the LDS budget allows
-// (two tiles of ru16(maxbond) x T doubles <= 128 KiB), halved while that leaves compute units without a workgroup
+// tile width for a chunk of cnt images at largest bond dimension maxbond (<= ChainT<E>::MAXM): the widest the LDS budget allows
+// (two tiles of ru16(maxbond) x T elements <= 128 KiB), halved while that leaves compute units without a workgroup
+template <typename E>
 int chain_tile(tnml_ctx* c, int maxbond, int cnt) {
-    int T = maxbond <= 128 ? 64 : (maxbond <= 256 ? 32 : 16);
+    int T = maxbond <= ChainT<E>::T64 ? 64 : (maxbond <= ChainT<E>::T32 ? 32 : 16);
     if (c->predict_tile) return std::min(T, c->predict_tile);
     if (!c->cu_count) { hipDeviceProp_t pr; c->cu_count = hipGetDeviceProperties(&pr, c->cfg.device) == hipSuccess ? pr.multiProcessorCount : 256; }
     while (T > 16 && (cnt + T - 1) / T < c->cu_count) T /= 2;
     return T;
 }
+template int chain_tile<double>(tnml_ctx*, int, int);
+template int chain_tile<float>(tnml_ctx*, int, int);
 
-// a.mcap, a.park (null: R parked in LDS) and the grid follow from T; park_ws is the context's scratch of park_elems doubles
-int launch_chain(tnml_ctx* c, ChainArgs a, int maxbond, int T, double* park_ws, size_t park_elems) {
-    if (maxbond < 1 || maxbond > TNML_CHAIN_MAXM) return tnml_fail(c, "chain kernel: bond dimension %d outside 1..%d", maxbond, TNML_CHAIN_MAXM);
-    if (a.cnt < 1 || a.cnt > a.ld) return tnml_fail(c, "chain kernel: %d images in a chunk of %d", a.cnt, a.ld);
+// a.mcap, a.park (null: R parked in LDS) and the grid follow from T; park_ws is the context's scratch of park_elems elements
+template <typename E>
+int launch_chain(tnml_ctx* c, ChainArgs<E> a, int maxbond, int T, E* park_ws, size_t park_elems) {
+    typedef ChainT<E> Tr;
+    constexpr bool f32 = sizeof(E) == sizeof(float);
+    if (maxbond < 1 || maxbond > Tr::MAXM) return tnml_fail(c, "%schain kernel: bond dimension %d outside 1..%d", Tr::what, maxbond, Tr::MAXM);
+    if (a.cnt < 1 || a.cnt > a.ld) return tnml_fail(c, "%schain kernel: %d images in a chunk of %d", Tr::what, a.cnt, a.ld);
+    if (T != 64 && T != 32 && T != 16) return tnml_fail(c, "%schain kernel: tile width %d", Tr::what, T);
+    if (f32 && !a.flag) return tnml_fail(c, "%schain kernel: no range flag", Tr::what);
     a.mcap = (maxbond + 15) / 16 * 16;
-    const size_t tile = (size_t)a.mcap * T * sizeof(double);
+    const size_t tile = (size_t)a.mcap * T * sizeof(E);
     const int grid = (a.cnt + T - 1) / T;
     const bool park_lds = 3 * tile <= TNML_CHAIN_LDS;
-    if (2 * tile > TNML_CHAIN_LDS) return tnml_fail(c, "chain kernel: two tiles of %d x %d do not fit the LDS", a.mcap, T);
-    if (!park_lds && (size_t)grid * a.mcap * T > park_elems) return tnml_fail(c, "chain kernel: scratch of %zu doubles too small for %d tiles of %d x %d", park_elems, grid, a.mcap, T);
+    if (2 * tile > TNML_CHAIN_LDS) return tnml_fail(c, "%schain kernel: two tiles of %d x %d do not fit the LDS", Tr::what, a.mcap, T);
+    if (!park_lds && (size_t)grid * a.mcap * T > park_elems)
+        return tnml_fail(c, "%schain kernel: scratch of %zu %s too small for %d tiles of %d x %d", Tr::what, park_elems, Tr::elems, grid, a.mcap, T);
     a.park = park_lds ? nullptr : park_ws;
     const size_t lds = (park_lds ? 3 : 2) * tile;
     const bool codes = a.codeT != nullptr;
-    if (codes ? !c->attr_chain_codes : !c->attr_chain) {
-        const void* f[3];
-        if (codes) { f[0] = reinterpret_cast<const void*>(k_chain<1, 1>); f[1] = reinterpret_cast<const void*>(k_chain<2, 1>); f[2] = reinterpret_cast<const void*>(k_chain<4, 1>); }
-        else       { f[0] = reinterpret_cast<const void*>(k_chain<1, 0>); f[1] = reinterpret_cast<const void*>(k_chain<2, 0>); f[2] = reinterpret_cast<const void*>(k_chain<4, 0>); }
-        for (const void* fn : f)
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, TNML_CHAIN_LDS) != hipSuccess) return tnml_fail(c, "chain kernel: hipFuncSetAttribute failed");
-        (codes ? c->attr_chain_codes : c->attr_chain) = true;
+    if (codes && !a.table) return tnml_fail(c, "%schain kernel: block sums without a table", Tr::what);
+    typedef void (*kern_t)(const ChainArgs<E>);
+    static const kern_t kern[2][3] = {{k_chain<E, 1, 0>, k_chain<E, 2, 0>, k_chain<E, 4, 0>}, {k_chain<E, 1, 1>, k_chain<E, 2, 1>, k_chain<E, 4, 1>}};   // [SRC][T / 32]
+    bool& attr = c->attr_chain[f32][codes];
+    if (!attr) {
+        for (kern_t fn : kern[codes])
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, TNML_CHAIN_LDS) != hipSuccess)
+                return tnml_fail(c, "%schain kernel: hipFuncSetAttribute failed", Tr::what);
+        attr = true;
     }
-    if (codes && !a.table) return tnml_fail(c, "chain kernel: block sums without a table");
     ProfScope ps(c, KC_CHAIN);
-    if (T != 64 && T != 32 && T != 16) return tnml_fail(c, "chain kernel: tile width %d", T);
-    if (codes) {
-        if (T == 64)      hipLaunchKernelGGL((k_chain<4, 1>), dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
-        else if (T == 32) hipLaunchKernelGGL((k_chain<2, 1>), dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
-        else              hipLaunchKernelGGL((k_chain<1, 1>), dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
-    } else {
-        if (T == 64)      hipLaunchKernelGGL((k_chain<4, 0>), dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
-        else if (T == 32) hipLaunchKernelGGL((k_chain<2, 0>), dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
-        else              hipLaunchKernelGGL((k_chain<1, 0>), dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
-    }
+    hipLaunchKernelGGL(kern[codes][T / 32], dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
     HIPCK(c, hipGetLastError());
     return 0;
 }
+template int launch_chain<double>(tnml_ctx*, ChainArgs<double>, int, int, double*, size_t);
+template int launch_chain<float>(tnml_ctx*, ChainArgs<float>, int, int, float*, size_t);

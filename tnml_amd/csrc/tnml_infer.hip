@@ -108,7 +108,7 @@ static int predict_workspace(tnml_ctx* c, bool bytes_form, bool f32) {
     if (c->pk_cap != cap) {                               // first call, or option predict_chunk has changed since
         if (c->pk_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); predict_release(c); }
         const size_t mc = (size_t)(std::min(c->maxm, TNML_CHAIN_MAXM) + 15) / 16 * 16;
-        int rc = predict_alloc(c, (void**)&c->pk_tab, (size_t)c->N * sizeof(ChainSite));
+        int rc = predict_alloc(c, (void**)&c->pk_tab, (size_t)c->N * sizeof(ChainSite<double>));
         if (!rc) rc = predict_alloc(c, (void**)&c->pk_w, (size_t)cap * c->nl() * sizeof(double));
         if (!rc) rc = predict_alloc(c, (void**)&c->pk_pred, (size_t)cap * sizeof(int));
         if (!rc) rc = predict_alloc(c, (void**)&c->pk_park, (size_t)cap * mc * sizeof(double));
@@ -139,9 +139,9 @@ static int predict_workspace(tnml_ctx* c, bool bytes_form, bool f32) {
 }
 // The fp32 side of the workspace (first call under predict_dtype = 1): the site table of the fp32 copy of W, the range flag, the copy itself
 // (grown when W has grown) and, under an input map, the table rounded to fp32.  Then the copy is made: W may have changed since the last call.
-static int predict_workspace32(tnml_ctx* c, bool mapped, const std::vector<ChainSite>& tab) {
+static int predict_workspace32(tnml_ctx* c, bool mapped, const std::vector<ChainSite<double>>& tab) {
     int rc = 0;
-    if (!c->pk_tab32) rc = predict_alloc(c, (void**)&c->pk_tab32, (size_t)c->N * sizeof(ChainSite32));
+    if (!c->pk_tab32) rc = predict_alloc(c, (void**)&c->pk_tab32, (size_t)c->N * sizeof(ChainSite<float>));
     if (!rc && !c->pk_flag) {
         rc = predict_alloc(c, (void**)&c->pk_flag, sizeof(int));
         if (!rc && hipMemsetAsync(c->pk_flag, 0, sizeof(int), c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict: memset failed");
@@ -171,11 +171,59 @@ static int predict_workspace32(tnml_ctx* c, bool mapped, const std::vector<Chain
         if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict_u8: hipStreamSynchronize failed");
     }
     if (rc) { predict_release(c); return rc; }
-    std::vector<ChainSite32> t32(c->N);
-    for (int j = 1; j <= c->N; ++j) t32[j - 1] = ChainSite32{c->pk_w32 + off[j - 1], tab[j - 1].ml, tab[j - 1].mr};
-    HIPCK(c, hipMemcpyAsync(c->pk_tab32, t32.data(), sizeof(ChainSite32) * c->N, hipMemcpyHostToDevice, c->stream));
+    std::vector<ChainSite<float>> t32(c->N);
+    for (int j = 1; j <= c->N; ++j) t32[j - 1] = ChainSite<float>{c->pk_w32 + off[j - 1], tab[j - 1].ml, tab[j - 1].mr};
+    HIPCK(c, hipMemcpyAsync(c->pk_tab32, t32.data(), sizeof(ChainSite<float>) * c->N, hipMemcpyHostToDevice, c->stream));
     TCK(launch_chain_pack32(c, c->pk_tab, c->pk_tab32, c->N, c->c0, c->nl(), largest));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (t32 leaves scope with this call)
+    return 0;
+}
+// the chunk loop of predict_impl in the element type E of option predict_dtype: per chunk stage (map, bytes or phi), ONE chain launch, copy back
+template <typename E>
+static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, double* weights, int32_t* pred, int maxbond) {
+    constexpr bool f32 = sizeof(E) == sizeof(float);
+    const bool bytes_form = pixels != nullptr;
+    const bool mapped = bytes_form && c->im_set;                // the input map: S bytes per image -> block sums -> table look-ups inside the chain kernel
+    const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
+    const size_t per_img = mapped ? (size_t)sg.S : (size_t)c->N * (bytes_form ? 1 : 2 * sizeof(double));
+    const int nl = c->nl();
+    ChainArgs<E> a;
+    a.N = c->N; a.cs = c->single() ? 1 : c->c0; a.nl = nl; a.single = c->single() ? 1 : 0;       // the centre tnml_classify takes
+    a.ld = c->pk_cap; a.wout = c->pk_w; a.pred = c->pk_pred;
+    E *xphi, *park; const E* table; size_t park_elems = c->pk_park_elems;
+    if constexpr (f32) {
+        // fp32: the copy of W, the features and the table rounded to fp32; the scratch of the parked vectors is the fp64 path's:
+        // cap x ru16(min(maxm, 512)) doubles hold cap x ru16(min(maxm, 1024)) floats
+        a.sites = c->pk_tab32; a.flag = c->pk_flag; table = c->pk_mtab32; xphi = c->pk_xphi32; park = (float*)c->pk_park; park_elems *= 2;
+    } else {
+        a.sites = c->pk_tab; table = c->pk_mtab; xphi = c->pk_xphi; park = c->pk_park;
+    }
+    a.xT = nullptr; a.phiT = nullptr;
+    if (mapped) { a.codeT = c->pk_codes; a.table = table; }
+    else if (bytes_form) a.xT = c->pk_x8;
+    else a.phiT = xphi;
+    for (int64_t off = 0; off < n; off += c->predict_chunk) {
+        a.cnt = (int)std::min<int64_t>(c->predict_chunk, n - off);
+        if (mapped) {
+            HIPCK(c, hipMemcpyAsync(c->pk_mraw, pixels + (size_t)off * per_img, per_img * a.cnt, hipMemcpyHostToDevice, c->stream));
+            { ProfScope ps(c, KC_PACK); TCK(launch_stage_codes(c, c->pk_mraw, sg, a.cnt, c->pk_cap, c->pk_codes)); }
+        } else {
+            if (bytes_form) HIPCK(c, hipMemcpyAsync(c->pk_raw8, pixels + (size_t)off * c->N, per_img * a.cnt, hipMemcpyHostToDevice, c->stream));
+            else            HIPCK(c, hipMemcpyAsync(c->pk_rawphi, phi + (size_t)off * c->N * 2, per_img * a.cnt, hipMemcpyHostToDevice, c->stream));
+            TCK(launch_chain_stage<E>(c, bytes_form ? c->pk_raw8 : nullptr, bytes_form ? nullptr : c->pk_rawphi, c->N, a.cnt, c->pk_cap, c->pk_x8, xphi));
+        }
+        TCK(launch_chain<E>(c, a, maxbond, chain_tile<E>(c, maxbond, a.cnt), park, park_elems));
+        int flag = 0;
+        if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->pk_w, sizeof(double) * (size_t)a.cnt * nl, hipMemcpyDeviceToHost, c->stream));
+        if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->pk_pred, sizeof(int32_t) * (size_t)a.cnt, hipMemcpyDeviceToHost, c->stream));
+        if (f32) HIPCK(c, hipMemcpyAsync(&flag, c->pk_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        SYNCK(c, c->stream);                                    // the staging buffers are reused by the next chunk
+        if (flag) {
+            HIPCK(c, hipMemsetAsync(c->pk_flag, 0, sizeof(int), c->stream));
+            HIPCK(c, hipStreamSynchronize(c->stream));
+            return tnml_fail(c, "%s: predict_dtype = 1 (fp32): a weight of images %lld..%lld is not finite, the chain has left the fp32 range: use fp64 (predict_dtype = 0)", who, (long long)off, (long long)off + a.cnt - 1);
+        }
+    }
     return 0;
 }
 static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, double* weights, int32_t* pred) {
@@ -196,74 +244,12 @@ static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* 
     HIPCK(c, hipSetDevice(c->cfg.device));
     const bool bytes_form = pixels != nullptr;
     TCK(predict_workspace(c, bytes_form, f32));
-    const int cs = c->single() ? 1 : c->c0, nl = c->nl();       // the centre tnml_classify takes
-    std::vector<ChainSite> tab(c->N);
-    for (int j = 1; j <= c->N; ++j) tab[j - 1] = ChainSite{c->W[j].a, c->W[j].ml, c->W[j].mr};
-    HIPCK(c, hipMemcpyAsync(c->pk_tab, tab.data(), sizeof(ChainSite) * c->N, hipMemcpyHostToDevice, c->stream));
+    std::vector<ChainSite<double>> tab(c->N);
+    for (int j = 1; j <= c->N; ++j) tab[j - 1] = ChainSite<double>{c->W[j].a, c->W[j].ml, c->W[j].mr};
+    HIPCK(c, hipMemcpyAsync(c->pk_tab, tab.data(), sizeof(ChainSite<double>) * c->N, hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (tab leaves scope with this call)
     if (f32) TCK(predict_workspace32(c, bytes_form && c->im_set, tab));
-    const bool mapped = bytes_form && c->im_set;                // the input map: S bytes per image -> block sums -> table look-ups inside the chain kernel
-    const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
-    const size_t per_img = mapped ? (size_t)sg.S : (size_t)c->N * (bytes_form ? 1 : 2 * sizeof(double));
-    for (int64_t off = 0; off < n; off += c->predict_chunk) {
-        const int cnt = (int)std::min<int64_t>(c->predict_chunk, n - off);
-        if (f32) {                                              // predict_dtype = 1: the same staging, features rounded to fp32, k_chain32 on the fp32 copy of W
-            ChainArgs32 a;
-            a.sites = c->pk_tab32; a.N = c->N; a.cs = cs; a.nl = nl; a.single = c->single() ? 1 : 0;
-            a.xT = nullptr; a.phiT = nullptr; a.ld = c->pk_cap; a.cnt = cnt; a.wout = c->pk_w; a.pred = c->pk_pred; a.flag = c->pk_flag;
-            if (mapped) {
-                HIPCK(c, hipMemcpyAsync(c->pk_mraw, pixels + (size_t)off * per_img, per_img * cnt, hipMemcpyHostToDevice, c->stream));
-                { ProfScope ps(c, KC_PACK); TCK(launch_stage_codes(c, c->pk_mraw, sg, cnt, c->pk_cap, c->pk_codes)); }
-                a.codeT = c->pk_codes; a.table = c->pk_mtab32;
-            } else if (bytes_form) {
-                HIPCK(c, hipMemcpyAsync(c->pk_raw8, pixels + (size_t)off * c->N, per_img * cnt, hipMemcpyHostToDevice, c->stream));
-                TCK(launch_chain_stage(c, c->pk_raw8, nullptr, c->N, cnt, c->pk_cap, c->pk_x8, nullptr));
-                a.xT = c->pk_x8;
-            } else {
-                HIPCK(c, hipMemcpyAsync(c->pk_rawphi, phi + (size_t)off * c->N * 2, per_img * cnt, hipMemcpyHostToDevice, c->stream));
-                TCK(launch_chain32_stage_phi(c, c->pk_rawphi, c->N, cnt, c->pk_cap, c->pk_xphi32));
-                a.phiT = c->pk_xphi32;
-            }
-            // the scratch of the parked vectors is the fp64 path's: cap x ru16(min(maxm, 512)) doubles hold cap x ru16(min(maxm, 1024)) floats
-            TCK(launch_chain32(c, a, maxbond, chain32_tile(c, maxbond, cnt), (float*)c->pk_park, 2 * c->pk_park_elems));
-            int flag = 0;
-            if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->pk_w, sizeof(double) * (size_t)cnt * nl, hipMemcpyDeviceToHost, c->stream));
-            if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->pk_pred, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
-            HIPCK(c, hipMemcpyAsync(&flag, c->pk_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            SYNCK(c, c->stream);
-            if (flag) {
-                HIPCK(c, hipMemsetAsync(c->pk_flag, 0, sizeof(int), c->stream));
-                HIPCK(c, hipStreamSynchronize(c->stream));
-                return tnml_fail(c, "%s: predict_dtype = 1 (fp32): a weight of images %lld..%lld is not finite, the chain has left the fp32 range: use fp64 (predict_dtype = 0)", who, (long long)off, (long long)off + cnt - 1);
-            }
-            continue;
-        }
-        if (mapped) {
-            HIPCK(c, hipMemcpyAsync(c->pk_mraw, pixels + (size_t)off * per_img, per_img * cnt, hipMemcpyHostToDevice, c->stream));
-            { ProfScope ps(c, KC_PACK); TCK(launch_stage_codes(c, c->pk_mraw, sg, cnt, c->pk_cap, c->pk_codes)); }
-            ChainArgs a;
-            a.sites = c->pk_tab; a.N = c->N; a.cs = cs; a.nl = nl; a.single = c->single() ? 1 : 0;
-            a.xT = nullptr; a.phiT = nullptr; a.codeT = c->pk_codes; a.table = c->pk_mtab;
-            a.ld = c->pk_cap; a.cnt = cnt; a.wout = c->pk_w; a.pred = c->pk_pred;
-            TCK(launch_chain(c, a, maxbond, chain_tile(c, maxbond, cnt), c->pk_park, c->pk_park_elems));
-            if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->pk_w, sizeof(double) * (size_t)cnt * nl, hipMemcpyDeviceToHost, c->stream));
-            if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->pk_pred, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
-            SYNCK(c, c->stream);
-            continue;
-        }
-        if (bytes_form) HIPCK(c, hipMemcpyAsync(c->pk_raw8, pixels + (size_t)off * c->N, per_img * cnt, hipMemcpyHostToDevice, c->stream));
-        else            HIPCK(c, hipMemcpyAsync(c->pk_rawphi, phi + (size_t)off * c->N * 2, per_img * cnt, hipMemcpyHostToDevice, c->stream));
-        TCK(launch_chain_stage(c, bytes_form ? c->pk_raw8 : nullptr, bytes_form ? nullptr : c->pk_rawphi, c->N, cnt, c->pk_cap, c->pk_x8, c->pk_xphi));
-        ChainArgs a;
-        a.sites = c->pk_tab; a.N = c->N; a.cs = cs; a.nl = nl; a.single = c->single() ? 1 : 0;
-        a.xT = bytes_form ? c->pk_x8 : nullptr; a.phiT = bytes_form ? nullptr : c->pk_xphi;
-        a.ld = c->pk_cap; a.cnt = cnt; a.wout = c->pk_w; a.pred = c->pk_pred;
-        TCK(launch_chain(c, a, maxbond, chain_tile(c, maxbond, cnt), c->pk_park, c->pk_park_elems));
-        if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->pk_w, sizeof(double) * (size_t)cnt * nl, hipMemcpyDeviceToHost, c->stream));
-        if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->pk_pred, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
-        SYNCK(c, c->stream);                                    // the staging buffers are reused by the next chunk
-    }
-    return 0;
+    return f32 ? predict_chunks<float>(c, who, n, pixels, phi, weights, pred, maxbond) : predict_chunks<double>(c, who, n, pixels, phi, weights, pred, maxbond);
 }
 int tnml_predict_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, double* weights, int32_t* pred) {
     if (n > 0 && !pixels) return tnml_fail(c, "tnml_predict_u8: null argument");

@@ -122,6 +122,8 @@ struct HeldOut {
     int bond[2] = {0, 0}, half[2] = {0, 0};
 };
 
+template <typename E> struct ChainSite;      // kernels_chain.hip, below
+
 struct tnml_ctx {
     tnml_config cfg;
     int N = 0, NT = 0, NTp = 0, c0 = 0, maxm = 0;
@@ -292,21 +294,20 @@ struct tnml_ctx {
     // streamed inference (tnml_predict_u8 / tnml_predict_phi, kernels_chain.hip): images the context does not hold, predict_chunk at a time
     int predict_chunk = TNML_PREDICT_CHUNK_DEFAULT;        // option "predict_chunk": images staged, launched (one k_chain launch) and copied back per trip of the host loop
     int predict_tile = 0;            // test knob (option "predict_tile"): images per workgroup of k_chain, 16 / 32 / 64 (capped by the LDS budget); 0: by bond dimension and image count
-    bool attr_chain = false, attr_chain_codes = false;
-    // option "predict_dtype": 0 the fp64 chain kernel (kernels_chain.hip), 1 the fp32 one (kernels_chain32.hip).  Its workspace, allocated by the
+    bool attr_chain[2][2] = {};      // [fp32][input map]: the LDS attribute of those k_chain instantiations is set
+    // option "predict_dtype": 0 k_chain<double>, 1 k_chain<float> (both kernels_chain.hip).  The fp32 workspace, allocated by the
     // first fp32 call (counted in `bytes` and pk_bytes, freed with the rest): the fp32 copy of W, re-made by every call and grown when W has grown,
     // its site table, the range flag, and what the staging of the input form needs
     int predict_dtype = 0;
-    bool attr_chain32 = false, attr_chain32_codes = false;
     float* pk_w32 = nullptr; size_t pk_w32_cap = 0;   // [pk_w32_cap] floats: every site tensor, each starting at a multiple of 4 floats
-    struct ChainSite32* pk_tab32 = nullptr;            // [N] per-site table of the copy
-    int* pk_flag = nullptr;                            // raised by k_chain32 when a weight is not finite
+    ChainSite<float>* pk_tab32 = nullptr;              // [N] per-site table of the copy
+    int* pk_flag = nullptr;                            // raised by k_chain<float> when a weight is not finite
     float* pk_xphi32 = nullptr;                        // features of a chunk site-first [N][2][pk_cap], rounded to fp32 (first fp32 tnml_predict_phi)
     int64_t pk_mtab32_bytes = 0;
     float* pk_mtab32 = nullptr;                        // the input map's table rounded to fp32 [ncodes][2] (first fp32 tnml_predict_u8 under a map)
     // its workspace, allocated by the first predict call (counted in `bytes`, freed by tnml_destroy); pk_cap = predict_chunk rounded up to 64 when it was sized
     int pk_cap = 0; int64_t pk_bytes = 0;
-    struct ChainSite* pk_tab = nullptr;   // [N] per-site table (ml, mr, address)
+    ChainSite<double>* pk_tab = nullptr;  // [N] per-site table (ml, mr, address)
     double* pk_w = nullptr; int* pk_pred = nullptr;   // [pk_cap][nl], [pk_cap]: results of a chunk
     double* pk_park = nullptr; size_t pk_park_elems = 0;   // [pk_cap / T][ru16(m)][T]: the parked right-chain vectors of the workgroups (when three tiles do not fit the LDS)
     uint8_t *pk_raw8 = nullptr, *pk_x8 = nullptr;     // bytes of a chunk as given [pk_cap][N] and site-first [N][pk_cap] (first tnml_predict_u8)
@@ -541,19 +542,23 @@ int launch_mps_place(tnml_ctx* c, const double* src, int ml, int mr, double* dst
 int launch_mps_transfer(tnml_ctx* c, const double* A, const double* T, int K, int mr, int L, double* Eout);
 
 // ---- kernels_chain.hip: streamed inference, the whole chain of toverlap for a tile of images in one launch ----
-#define TNML_CHAIN_MAXM 512        /* largest bond dimension k_chain serves */
+// One kernel template over the element type E: double (option predict_dtype = 0) on W where it lives, float (predict_dtype = 1) on the
+// fp32 copy of W that k_chain_pack32 makes once per call.
+#define TNML_CHAIN_MAXM 512        /* largest bond dimension k_chain<double> serves */
+#define TNML_CHAIN32_MAXM 1024     /* largest bond dimension k_chain<float> serves */
 #define TNML_CHAIN_LDS 163840      /* LDS of a workgroup: 160 KiB */
-struct ChainSite { const double* a; int ml, mr; };   // site tensor where it lives (SiteT::a, ITensor layout) and its bond dimensions
-struct ChainArgs {
-    const ChainSite* sites;            // [N] device
+template <typename E> struct ChainSite { const E* a; int ml, mr; };   // site tensor (SiteT::a or its fp32 copy, ITensor layout) and its bond dimensions
+template <typename E> struct ChainArgs {
+    const ChainSite<E>* sites;         // [N] device
     int N, cs, nl, single;             // cs: the centre site (N/2, or 1 in the per-label variant); nl: label extent; single: pred = [f > 1/2]
     const uint8_t* xT;                 // bytes, site-first [N][ld] -- or
-    const double* phiT;                // features, site-first [N][2][ld]
+    const E* phiT;                     // features (fp32: rounded once), site-first [N][2][ld]
     int ld, cnt;                       // row length of the staged images, images of this chunk
-    double* wout; int* pred;           // [cnt][nl], [cnt]
-    int mcap = 0; double* park = nullptr;   // set by launch_chain
+    double* wout; int* pred;           // [cnt][nl] (the fp32 weights widened), [cnt]
+    int mcap = 0; E* park = nullptr;   // set by launch_chain
     const uint16_t* codeT = nullptr;   // third source (input map): block sums, site-first [N][ld], with
-    const double* table = nullptr;     // the features [ncodes][2] of every block sum; both set -> the k_chain instantiations of this source
+    const E* table = nullptr;          // the features [ncodes][2] of every block sum (fp32: rounded once); both set -> the k_chain instantiations of this source
+    int* flag = nullptr;               // fp32: |= 1 when a weight is Inf or NaN; fp64: not used
 };
 // geometry of an input map as the staging kernel takes it (validated by tnml_set_input_map: every block lies inside the source image)
 struct StageGeom { int S, src_cols, block, row0, col0, out_rows, out_cols; };
@@ -561,31 +566,13 @@ struct StageGeom { int S, src_cols, block, row0, col0, out_rows, out_cols; };
 int launch_stage_codes(tnml_ctx* c, const uint8_t* raw, const StageGeom& g, int cnt, int ld, uint16_t* codes);
 // block sums codes[N][NTp] -> stored features phi[N][2][NTp] in the context's storage type through tab ([ncodes][2] of that type); padding images get (0, 0)
 int launch_codes_phi(tnml_ctx* c, const uint16_t* codes, const void* tab, int N, int NT, int NTp, void* phi);
-int launch_chain_stage(tnml_ctx* c, const uint8_t* pix, const double* phi, int N, int cnt, int ld, uint8_t* xT, double* phiT);   // exactly one of pix [cnt][N] / phi [cnt][N][2]
-int chain_tile(tnml_ctx* c, int maxbond, int cnt);
-int launch_chain(tnml_ctx* c, ChainArgs a, int maxbond, int T, double* park_ws, size_t park_elems);
-
-// ---- kernels_chain32.hip: the chain kernel in fp32 (option predict_dtype = 1) ----
-#define TNML_CHAIN32_MAXM 1024     /* largest bond dimension k_chain32 serves */
-struct ChainSite32 { const float* a; int ml, mr; };  // a site tensor of the fp32 copy of W (layout of SiteT::a)
-struct ChainArgs32 {
-    const ChainSite32* sites;          // [N] device
-    int N, cs, nl, single;             // as ChainArgs
-    const uint8_t* xT;                 // bytes, site-first [N][ld] -- or
-    const float* phiT;                 // features rounded to fp32, site-first [N][2][ld]
-    int ld, cnt;
-    double* wout; int* pred;           // [cnt][nl] (the fp32 weights widened), [cnt]
-    int mcap = 0; float* park = nullptr;    // set by launch_chain32
-    const uint16_t* codeT = nullptr;   // input map: block sums, site-first [N][ld], with
-    const float* table = nullptr;      // the features [ncodes][2] rounded to fp32
-    int* flag = nullptr;               // |= 1 when a weight is Inf or NaN
-};
-int launch_chain32_stage_phi(tnml_ctx* c, const double* phi, int N, int cnt, int ld, float* phiT);   // features [cnt][N][2] -> fp32 [N][2][ld]; class pack
+// exactly one of pix [cnt][N] -> xT [N][ld] / phi [cnt][N][2] -> phiT [N][2][ld], rounded once to E; class pack
+template <typename E> int launch_chain_stage(tnml_ctx* c, const uint8_t* pix, const double* phi, int N, int cnt, int ld, uint8_t* xT, E* phiT);
 // dst[j].a = fl32(src[j].a) for the N sites (tables on the device); lsite: the Label site (1-indexed, <= 0: none) carries nl times the elements;
 // largest: the element count of the largest site (sizes the grid); class pack
-int launch_chain_pack32(tnml_ctx* c, const ChainSite* src, const ChainSite32* dst, int N, int lsite, int nl, size_t largest);
-int chain32_tile(tnml_ctx* c, int maxbond, int cnt);
-int launch_chain32(tnml_ctx* c, ChainArgs32 a, int maxbond, int T, float* park_ws, size_t park_elems);
+int launch_chain_pack32(tnml_ctx* c, const ChainSite<double>* src, const ChainSite<float>* dst, int N, int lsite, int nl, size_t largest);
+template <typename E> int chain_tile(tnml_ctx* c, int maxbond, int cnt);
+template <typename E> int launch_chain(tnml_ctx* c, ChainArgs<E> a, int maxbond, int T, E* park_ws, size_t park_elems);
 
 // ---- eigh.hip -----------------------------------------------------------------------------
 int eigh_tridiagonalize(tnml_ctx* c, const double* A, int n, double* D, double* E, double* tau, double* V, double psd_tol = 0.);   // tau: n doubles, tau[n-1] = number of reflectors
