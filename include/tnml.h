@@ -351,6 +351,39 @@ int tnml_classify(tnml_ctx* ctx, double* weights, int32_t* pred, int64_t count[T
 int tnml_predict_u8(tnml_ctx* ctx, int64_t n, const uint8_t* pixels /*[n][N]*/, double* weights /*[n][nl] or NULL*/, int32_t* pred /*[n] or NULL*/);
 int tnml_predict_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/, double* weights, int32_t* pred);
 
+/* ---- streamed evaluation: tnml_predict_* on labelled images, with the numbers of a held-out report -------------
+ * The path of tnml_predict_u8 / tnml_predict_phi, unchanged: the same contraction, input forms (the input map is honoured), chunking
+ * ("predict_chunk"), tile choice and "predict_dtype", the same chain kernel on the same staging buffers, the same refusals in the same
+ * words.  weights and pred, when asked for, are bit for bit those of tnml_predict_* on the same images and options; when both are
+ * NULL nothing per-image is copied back, only the report crosses the bus.  After the chain launch of a chunk one launch of
+ * k_eval_tally (kernels_eval.hip) adds the chunk's tallies into a device accumulator block, which is read once at the end of the call.
+ * Targets: y_nl = [l == label_n]; in TNML_MODE_SINGLE y_n = [label_n == target_label], label_cost bucketed by the true label.  Under
+ * predict_dtype = 1 the cost is formed in fp64 from the widened fp32 weights and pred follows the fp32 rule.
+ * label_cost[l] collects the images of true label l in both modes, as tnml_heldout_report and tnml_bond_report do.
+ * The cost has a fixed summation order (one workgroup; thread t sums its images t, t + 256, ... in ascending order, label by label; a
+ * fixed tree over the threads; chunks in chunk order; cost = label_cost[0] + ... + label_cost[9] in index order): the report is bit-identical on
+ * repeats and independent of predict_tile, its integers are independent of predict_chunk, the last bits of the costs may depend on
+ * predict_chunk.
+ * Read-only like tnml_predict_*: reads W, enters no collective, allowed on a training context, also while a held-out context is attached
+ * to it.  Also refused: labels or rep NULL when n > 0, a label outside 0..9 (the message names the image).  A refused call leaves *rep
+ * untouched; n = 0 succeeds with a zeroed report.
+ * Workspace: that of tnml_predict_* for the input form, plus -- from the first tnml_evaluate_* call on, counted by tnml_device_bytes and
+ * freed with the predict workspace (re-made with it when predict_chunk changes) --
+ *             4 C + 1040                    bytes (the labels of a chunk; the accumulator block: label_cost, count, nincorrect, confusion). */
+typedef struct {
+    int64_t n;                               /* images evaluated */
+    int64_t ncorrect;                        /* decision rule of tnml_classify for the context's mode */
+    double  cost;                            /* sum over images and labels of (W_l(x_n) - y_nl)^2; un-normalised, no regulariser */
+    double  label_cost[TNML_NL];             /* as tnml_heldout_report::label_cost in both modes */
+    int64_t count[TNML_NL];                  /* images of true label l            (tnml_classify) */
+    int64_t nincorrect[TNML_NL];             /* of those, wrongly predicted        (tnml_classify) */
+    int64_t confusion[TNML_NL][TNML_NL];     /* [true label][pred]; TNML_MODE_SINGLE: pred is 0 or 1, columns 2..9 stay 0 */
+} tnml_eval_report;
+int tnml_evaluate_u8 (tnml_ctx* ctx, int64_t n, const uint8_t* pixels, const int32_t* labels,
+                      tnml_eval_report* rep, double* weights /*[n][nl] or NULL*/, int32_t* pred /*[n] or NULL*/);
+int tnml_evaluate_phi(tnml_ctx* ctx, int64_t n, const double* phi, const int32_t* labels,
+                      tnml_eval_report* rep, double* weights, int32_t* pred);
+
 /* ---- held-out evaluation during training ----------------------------------------------------------
  * A held-out set is an ordinary context created for the held-out images (one rank: nranks = 1, its own shard of the set in
  * a multi-rank run).  Once attached to a training context, every bond update of `train` also moves the two site tensors it

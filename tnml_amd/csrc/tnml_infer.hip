@@ -91,7 +91,7 @@ void predict_release_map(tnml_ctx* c) {
 }
 void predict_release(tnml_ctx* c) {
     void** slots[] = {(void**)&c->pk_tab, (void**)&c->pk_w, (void**)&c->pk_pred, (void**)&c->pk_park, (void**)&c->pk_raw8, (void**)&c->pk_x8, (void**)&c->pk_rawphi, (void**)&c->pk_xphi,
-                      (void**)&c->pk_w32, (void**)&c->pk_tab32, (void**)&c->pk_flag, (void**)&c->pk_xphi32};
+                      (void**)&c->pk_w32, (void**)&c->pk_tab32, (void**)&c->pk_flag, (void**)&c->pk_xphi32, (void**)&c->pk_lab, (void**)&c->pk_acc};
     for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
     c->pk_w32_cap = 0;
     predict_release_map(c);
@@ -178,9 +178,18 @@ static int predict_workspace32(tnml_ctx* c, bool mapped, const std::vector<Chain
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (t32 leaves scope with this call)
     return 0;
 }
-// the chunk loop of predict_impl in the element type E of option predict_dtype: per chunk stage (map, bytes or phi), ONE chain launch, copy back
+// tnml_evaluate_*: the labels of a chunk and the accumulator block of a call, 4 C + sizeof(EvalAcc) bytes on top of the predict workspace (first such call)
+static int evaluate_workspace(tnml_ctx* c) {
+    int rc = 0;
+    if (!c->pk_lab) rc = predict_alloc(c, (void**)&c->pk_lab, (size_t)c->pk_cap * sizeof(int));
+    if (!rc && !c->pk_acc) rc = predict_alloc(c, (void**)&c->pk_acc, sizeof(EvalAcc));
+    if (rc) predict_release(c);
+    return rc;
+}
+// the chunk loop of predict_impl in the element type E of option predict_dtype: per chunk stage (map, bytes or phi), ONE chain launch, copy back;
+// labels (tnml_evaluate_*): the chunk's labels are staged with its images and ONE k_eval_tally launch behind the chain adds its tallies to pk_acc
 template <typename E>
-static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, double* weights, int32_t* pred, int maxbond) {
+static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, double* weights, int32_t* pred, int maxbond) {
     constexpr bool f32 = sizeof(E) == sizeof(float);
     const bool bytes_form = pixels != nullptr;
     const bool mapped = bytes_form && c->im_set;                // the input map: S bytes per image -> block sums -> table look-ups inside the chain kernel
@@ -212,7 +221,9 @@ static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t
             else            HIPCK(c, hipMemcpyAsync(c->pk_rawphi, phi + (size_t)off * c->N * 2, per_img * a.cnt, hipMemcpyHostToDevice, c->stream));
             TCK(launch_chain_stage<E>(c, bytes_form ? c->pk_raw8 : nullptr, bytes_form ? nullptr : c->pk_rawphi, c->N, a.cnt, c->pk_cap, c->pk_x8, xphi));
         }
+        if (labels) HIPCK(c, hipMemcpyAsync(c->pk_lab, labels + off, sizeof(int32_t) * (size_t)a.cnt, hipMemcpyHostToDevice, c->stream));
         TCK(launch_chain<E>(c, a, maxbond, chain_tile<E>(c, maxbond, a.cnt), park, park_elems));
+        if (labels) TCK(launch_eval_tally(c, c->pk_w, c->pk_pred, c->pk_lab, a.cnt, nl, a.single, c->target(), c->pk_acc));
         int flag = 0;
         if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->pk_w, sizeof(double) * (size_t)a.cnt * nl, hipMemcpyDeviceToHost, c->stream));
         if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->pk_pred, sizeof(int32_t) * (size_t)a.cnt, hipMemcpyDeviceToHost, c->stream));
@@ -226,7 +237,9 @@ static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t
     }
     return 0;
 }
-static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, double* weights, int32_t* pred) {
+// rep: the call is tnml_evaluate_* (labels are then required when n > 0); *rep is written once, after everything has succeeded
+static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, double* weights, int32_t* pred,
+                        bool evaluate = false, const int32_t* labels = nullptr, tnml_eval_report* rep = nullptr) {
     if (!c) return tnml_fail(c, "%s: null argument", who);
     if (n < 0) return tnml_fail(c, "%s: n = %lld, must be >= 0", who, (long long)n);
     if (c->pend_count > 0) return tnml_fail(c, "%s: a bond update is in flight (tnml_bond_update_end first)", who);
@@ -239,17 +252,42 @@ static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* 
         return tnml_fail(c, "%s: W has a bond of dimension %d, the fp32 chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, maxbond, TNML_CHAIN32_MAXM);
     if (!f32 && maxbond > TNML_CHAIN_MAXM)
         return tnml_fail(c, "%s: W has a bond of dimension %d, the chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, maxbond, TNML_CHAIN_MAXM);
-    if (n == 0) return 0;
+    if (n == 0) { if (rep) memset(rep, 0, sizeof(*rep)); return 0; }
     if (!pixels && !phi) return tnml_fail(c, "%s: null argument", who);
+    if (evaluate) {
+        if (!labels || !rep) return tnml_fail(c, "%s: null argument (labels and rep are required)", who);
+        for (int64_t i = 0; i < n; ++i)
+            if (labels[i] < 0 || labels[i] >= TNML_NL) return tnml_fail(c, "%s: label %d of image %lld out of range", who, labels[i], (long long)i);
+    }
     HIPCK(c, hipSetDevice(c->cfg.device));
     const bool bytes_form = pixels != nullptr;
     TCK(predict_workspace(c, bytes_form, f32));
+    if (evaluate) {
+        TCK(evaluate_workspace(c));
+        HIPCK(c, hipMemsetAsync(c->pk_acc, 0, sizeof(EvalAcc), c->stream));
+    }
     std::vector<ChainSite<double>> tab(c->N);
     for (int j = 1; j <= c->N; ++j) tab[j - 1] = ChainSite<double>{c->W[j].a, c->W[j].ml, c->W[j].mr};
     HIPCK(c, hipMemcpyAsync(c->pk_tab, tab.data(), sizeof(ChainSite<double>) * c->N, hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (tab leaves scope with this call)
     if (f32) TCK(predict_workspace32(c, bytes_form && c->im_set, tab));
-    return f32 ? predict_chunks<float>(c, who, n, pixels, phi, weights, pred, maxbond) : predict_chunks<double>(c, who, n, pixels, phi, weights, pred, maxbond);
+    TCK(f32 ? predict_chunks<float>(c, who, n, pixels, phi, labels, weights, pred, maxbond) : predict_chunks<double>(c, who, n, pixels, phi, labels, weights, pred, maxbond));
+    if (!evaluate) return 0;
+    EvalAcc h;                                                  // the one copy of the tallies: every chunk has been added (the loop ends on a synchronisation)
+    HIPCK(c, hipMemcpyAsync(&h, c->pk_acc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    SYNCK(c, c->stream);
+    tnml_eval_report r;
+    memset(&r, 0, sizeof(r));
+    r.n = n;
+    int64_t wrong = 0;
+    for (int l = 0; l < TNML_NL; ++l) {
+        r.label_cost[l] = h.label_cost[l]; r.cost += h.label_cost[l];
+        r.count[l] = h.count[l]; r.nincorrect[l] = h.nincorrect[l]; wrong += h.nincorrect[l];
+        for (int p = 0; p < TNML_NL; ++p) r.confusion[l][p] = h.confusion[l][p];
+    }
+    r.ncorrect = n - wrong;
+    *rep = r;
+    return 0;
 }
 int tnml_predict_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, double* weights, int32_t* pred) {
     if (n > 0 && !pixels) return tnml_fail(c, "tnml_predict_u8: null argument");
@@ -258,4 +296,12 @@ int tnml_predict_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, double* weigh
 int tnml_predict_phi(tnml_ctx* c, int64_t n, const double* phi, double* weights, int32_t* pred) {
     if (n > 0 && !phi) return tnml_fail(c, "tnml_predict_phi: null argument");
     return predict_impl(c, "tnml_predict_phi", n, nullptr, phi, weights, pred);
+}
+int tnml_evaluate_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const int32_t* labels, tnml_eval_report* rep, double* weights, int32_t* pred) {
+    if (n > 0 && !pixels) return tnml_fail(c, "tnml_evaluate_u8: null argument");
+    return predict_impl(c, "tnml_evaluate_u8", n, pixels, nullptr, weights, pred, true, labels, rep);
+}
+int tnml_evaluate_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* labels, tnml_eval_report* rep, double* weights, int32_t* pred) {
+    if (n > 0 && !phi) return tnml_fail(c, "tnml_evaluate_phi: null argument");
+    return predict_impl(c, "tnml_evaluate_phi", n, nullptr, phi, weights, pred, true, labels, rep);
 }

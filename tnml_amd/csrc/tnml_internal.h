@@ -33,11 +33,17 @@
 
 enum KClass {
     KC_FGEMM_FWD = 0, KC_FGEMM_SHIFT, KC_LABELDOT, KC_ZPRIME, KC_BGEMM, KC_SLABRED, KC_PACK, KC_VEC,
-    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_COUNT
+    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_EVAL_TALLY, KC_COUNT
 };
 static const char* const kclass_names[KC_COUNT] = {
     "fgemm_fwd", "fgemm_shift", "labeldot", "zprime", "bgemm", "slab_reduce", "pack", "cg_vec",
-    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain"};
+    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain", "eval_tally"};
+
+// device accumulator block of tnml_evaluate_*: the part of tnml_eval_report that k_eval_tally (kernels_eval.hip) adds up
+struct EvalAcc {
+    double label_cost[TNML_NL];
+    long long count[TNML_NL], nincorrect[TNML_NL], confusion[TNML_NL][TNML_NL];
+};
 
 struct EnvSlot {
     void* ptr = nullptr;    // [L][m][NTp], fp32 or fp64 elements (tnml_ctx::env64); null while the environment is spilled to the host
@@ -312,6 +318,9 @@ struct tnml_ctx {
     double* pk_park = nullptr; size_t pk_park_elems = 0;   // [pk_cap / T][ru16(m)][T]: the parked right-chain vectors of the workgroups (when three tiles do not fit the LDS)
     uint8_t *pk_raw8 = nullptr, *pk_x8 = nullptr;     // bytes of a chunk as given [pk_cap][N] and site-first [N][pk_cap] (first tnml_predict_u8)
     double *pk_rawphi = nullptr, *pk_xphi = nullptr;  // features of a chunk as given [pk_cap][N][2] and site-first [N][2][pk_cap] (first tnml_predict_phi)
+    // streamed evaluation (tnml_evaluate_u8 / tnml_evaluate_phi, kernels_eval.hip): allocated by the first such call, counted in `bytes` and pk_bytes, freed with the rest
+    int* pk_lab = nullptr;           // [pk_cap] labels of a chunk
+    EvalAcc* pk_acc = nullptr;       // the tallies of the call in progress (k_eval_tally adds a chunk, the host reads them once at the end)
     // input map (tnml_set_input_map): geometry + host copy of the fp64 table; consulted by tnml_set_data_u8 / tnml_predict_u8 only
     bool im_set = false;
     tnml_input_map im = {};          // geometry (table = nullptr)
@@ -573,6 +582,12 @@ template <typename E> int launch_chain_stage(tnml_ctx* c, const uint8_t* pix, co
 int launch_chain_pack32(tnml_ctx* c, const ChainSite<double>* src, const ChainSite<float>* dst, int N, int lsite, int nl, size_t largest);
 template <typename E> int chain_tile(tnml_ctx* c, int maxbond, int cnt);
 template <typename E> int launch_chain(tnml_ctx* c, ChainArgs<E> a, int maxbond, int T, E* park_ws, size_t park_elems);
+
+
+// ---- kernels_eval.hip: the tallies of streamed evaluation over the results of a chunk ----
+// w [cnt][nl], pred [cnt] (what k_chain left in pk_w / pk_pred), lab [cnt] in 0..9 (the host has checked them) -> acc += the chunk's
+// label_cost, count, nincorrect, confusion; one workgroup, fixed summation order (the kernel's header states it); class eval_tally
+int launch_eval_tally(tnml_ctx* c, const double* w, const int* pred, const int* lab, int cnt, int nl, int single, int target, EvalAcc* acc);
 
 // ---- eigh.hip -----------------------------------------------------------------------------
 int eigh_tridiagonalize(tnml_ctx* c, const double* A, int n, double* D, double* E, double* tau, double* V, double psd_tol = 0.);   // tau: n doubles, tau[n-1] = number of reflectors

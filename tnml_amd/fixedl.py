@@ -21,6 +21,26 @@ class TnmlError(RuntimeError):
     pass
 
 
+class EvalReport:
+    """tnml_eval_report as numpy values: n, ncorrect, cost, label_cost[10], count[10], nincorrect[10], confusion[10, 10] ([true][pred])"""
+    FIELDS = ("n", "ncorrect", "cost", "label_cost", "count", "nincorrect", "confusion")
+
+    def __init__(self, r):
+        self.n, self.ncorrect, self.cost = int(r.n), int(r.ncorrect), float(r.cost)
+        self.label_cost = np.array(r.label_cost[:], dtype=np.float64)
+        self.count = np.array(r.count[:], dtype=np.int64)
+        self.nincorrect = np.array(r.nincorrect[:], dtype=np.int64)
+        self.confusion = np.array([row[:] for row in r.confusion], dtype=np.int64)
+
+    def __eq__(self, other):
+        return isinstance(other, EvalReport) and all(np.array_equal(getattr(self, f), getattr(other, f)) for f in self.FIELDS)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "EvalReport(n=%d, ncorrect=%d, cost=%r)" % (self.n, self.ncorrect, self.cost)
+
+
 class TrainStates:
     """Training set + environments + W replica of one rank (TrainStates + MPS W of fixedL.cc)."""
 
@@ -231,6 +251,19 @@ class TrainStates:
         (under an input map: [n, S] raw bytes) or phi[n, N, 2] features -> (weights[n, nl], pred[n]); pred is argmax_l |W_l|
         (per-label variant: [f > 1/2]).  Reads W only.  dtype "f64" / "f32" sets option predict_dtype for this call and the ones
         after it (None: leave it): "f32" runs the fp32 chain kernel, weights are its fp32 results widened."""
+        x = self._streamed_input(pixels, phi, dtype)
+        n = int(x.shape[0])
+        w = np.zeros((n, self.nl))
+        pred = np.zeros(n, dtype=np.int32)
+        pp = pred.ctypes.data_as(C.POINTER(C.c_int32))
+        if pixels is not None:
+            self._ck(self._L.tnml_predict_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(w), pp))
+        else:
+            self._ck(self._L.tnml_predict_phi(self._h, n, _lib.dptr(x), _lib.dptr(w), pp))
+        return w, pred
+
+    def _streamed_input(self, pixels, phi, dtype):
+        """the images of predict / evaluate as the C call takes them; dtype (when given) becomes option predict_dtype"""
         if (pixels is None) == (phi is None):
             raise ValueError("need exactly one of pixels or phi")
         if dtype is not None:
@@ -244,15 +277,31 @@ class TrainStates:
         else:
             x = np.ascontiguousarray(phi, dtype=np.float64)
             assert x.ndim == 3 and x.shape[1:] == (self.N, 2), x.shape
+        return x
+
+    def evaluate(self, labels, pixels=None, phi=None, dtype=None, want_weights=False):
+        """streamed evaluation of labelled images this context does not hold (tnml_evaluate_u8 / tnml_evaluate_phi): the path of
+        predict() plus one tally launch per chunk.  Returns an EvalReport (fields as tnml_eval_report: n, ncorrect, cost,
+        label_cost[10], count[10], nincorrect[10], confusion[10, 10]); with want_weights (report, (weights[n, nl], pred[n])), both
+        bit for bit those of predict().  Without it only the report leaves the device.  Reads W only."""
+        x = self._streamed_input(pixels, phi, dtype)
         n = int(x.shape[0])
-        w = np.zeros((n, self.nl))
-        pred = np.zeros(n, dtype=np.int32)
-        pp = pred.ctypes.data_as(C.POINTER(C.c_int32))
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (n,):
+            raise ValueError("labels must have shape [%d], got %s" % (n, lab.shape))
+        w = pred = wp = pp = None
+        if want_weights:
+            w = np.zeros((n, self.nl))
+            pred = np.zeros(n, dtype=np.int32)
+            wp, pp = _lib.dptr(w), pred.ctypes.data_as(C.POINTER(C.c_int32))
+        r = _lib.EvalReport()
+        lp = lab.ctypes.data_as(C.POINTER(C.c_int32))
         if pixels is not None:
-            self._ck(self._L.tnml_predict_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(w), pp))
+            self._ck(self._L.tnml_evaluate_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), lp, C.byref(r), wp, pp))
         else:
-            self._ck(self._L.tnml_predict_phi(self._h, n, _lib.dptr(x), _lib.dptr(w), pp))
-        return w, pred
+            self._ck(self._L.tnml_evaluate_phi(self._h, n, _lib.dptr(x), lp, C.byref(r), wp, pp))
+        rep = EvalReport(r)
+        return (rep, (w, pred)) if want_weights else rep
 
     # -- W
     def set_mps(self, W):

@@ -11,7 +11,9 @@
 // imglen x imglen; present in the reference's sample input but never read by fixedL.cc), `feature_scale`
 // (multiplies the second feature component; 1 = the reference's double normalisation), `pipeline`, `bond_log`
 // (a CSV line per bond update: cost, #correct, bond dimensions, truncation error, seconds), `heldout` (the t10k images, capped at `Ntest`
-// per label, follow the training as a held-out context: one "Held-out:" line per bond update), `mps_device` (auto | yes | no: the W0..W9 sum and
+// per label, follow the training as a held-out context: one "Held-out:" line per bond update; heldout = stream: no second context and no
+// lower maxm for it -- the images are evaluated on the training context by tnml_evaluate_* before the first sweep, after every sweep and,
+// with `heldout_every` = k, after every k-th bond update of a sweep), `mps_device` (auto | yes | no: the W0..W9 sum and
 // overlap(W,W) on the GPU -- tnml_mps_place / tnml_mps_compress / tnml_mps_overlap -- instead of the host's scalar SVD; auto = from a bond of
 // MPS_DEVICE_AUTO_BOND + 1 on), `sum_maxm` (a Maxm for that sum; the reference passes none), `input_map` (yes | no, default no: the images reach
 // the device as the bytes of the idx file and the device does reduce(), the feature map and the transpose -- tnml_set_input_map; same log, same W).
@@ -103,7 +105,10 @@ int main(int argc, const char* argv[]) {
         const std::string precision = input.getString("precision", "f64");              // extension: f64 | mixed | f32 | bf16x3 | bf16
         const long imglen = input.getInt("imglen", 0);                                   // extension: 0 = keep the file's size
         const double feature_scale = input.getReal("feature_scale", 1.);                 // extension
-        const bool heldout = input.getYesNo("heldout", false);                          // extension: evaluate the t10k images after every bond update
+        const bool stream = input.getString("heldout", "no") == "stream";               // extension: heldout = stream -- the t10k images are evaluated on the training context itself (tnml_evaluate_*), no second context
+        const bool heldout = !stream && input.getYesNo("heldout", false);               // extension: evaluate the t10k images after every bond update
+        const long heldout_every = input.getInt("heldout_every", 0);                     // extension (heldout = stream): also evaluate after every k-th bond update of a sweep; 0: sweep ends only
+        if (heldout_every < 0) { std::printf("heldout_every must be >= 0\n"); return 1; }
         const bool input_map = input.getYesNo("input_map", false);                      // extension: the images reach the device as the bytes of the idx file; the device reduces, maps and transposes (tnml_set_input_map)
         const long Ntest = input.getInt("Ntest", 50000);                                 // extension: per-label cap of the held-out set (as fulltest)
         const std::string mps_device = input.getString("mps_device", "auto");            // extension: auto | yes | no -- the W0..W9 sum and overlap(W,W) on the GPU
@@ -117,7 +122,8 @@ int main(int argc, const char* argv[]) {
         Dataset train_raw, test_raw;                                                    // input_map = yes: the bytes of the idx files (the initial W is still built from the reduced copy)
         Dataset train = read_images(datadir, true, Ntrain, imglen, input_map ? &train_raw : nullptr);   // :613
         Dataset test;                                                                   // the held-out set: read before any context exists
-        if (heldout && !read_heldout(datadir, Ntest, imglen, train, &test, input_map ? &test_raw : nullptr)) return 1;
+        if ((heldout || stream) && !read_heldout(datadir, Ntest, imglen, train, &test, input_map ? &test_raw : nullptr)) return 1;
+        if (stream && input_map && test_raw.npix() != train_raw.npix()) { std::printf("heldout = stream: the t10k files have %d bytes per image, the training files %d\n", test_raw.npix(), train_raw.npix()); return 1; }
         std::printf("Training set consists of %d images:\n", train.size());
         for (int l = 0; l < 10; ++l) std::printf("  %d of label %d\n", train.counts[l], l);
         const int N = train.npix();                                                     // :615
@@ -217,9 +223,9 @@ int main(int argc, const char* argv[]) {
             std::printf("Thread %d %lld -> %lld (%lld)\n", r, (long long)lo[r], (long long)hi[r], (long long)(hi[r] - lo[r]));   // :94, one GPU per "thread"
         }
         (void)Nthread;
-        const int totNtest = heldout ? test.size() : 0;
+        const int totNtest = heldout || stream ? test.size() : 0;
         std::vector<int64_t> tlo(nranks, 0), thi(nranks, 0);
-        for (int r = 0; heldout && r < nranks; ++r) tnml_shard_bounds(totNtest, nranks, r, &tlo[r], &thi[r]);
+        for (int r = 0; (heldout || stream) && r < nranks; ++r) tnml_shard_bounds(totNtest, nranks, r, &tlo[r], &thi[r]);
         auto rank_config = [&](int r, int m) {                                          // rank r's training context at maxm = m
             tnml_config c{};
             c.device = share_device ? device : device + r; c.rank = r; c.nranks = nranks; c.N = N; c.NT_local = (int)(hi[r] - lo[r]); c.NT_total = totNtrain;
@@ -263,14 +269,20 @@ int main(int argc, const char* argv[]) {
             if (heldout) im_test = make_input_map(test_raw, imglen, false, feature_scale);
             im.print();
         }
-        const size_t S = input_map ? (size_t)train_raw.npix() : (size_t)N, St = input_map && heldout ? (size_t)test_raw.npix() : (size_t)N;   // bytes per image as handed over
+        const size_t S = input_map ? (size_t)train_raw.npix() : (size_t)N, St = input_map && (heldout || stream) ? (size_t)test_raw.npix() : (size_t)N;   // bytes per image as handed over
         const uint8_t* train_bytes = input_map ? train_raw.pixels.data() : train.pixels.data();
         const uint8_t* test_bytes = input_map ? test_raw.pixels.data() : test.pixels.data();
         const bool use_u8 = input_map || (!train.reduced() && feature_scale == 1.);
         if (!use_u8) phi_all = all_features(train, false, feature_scale);
         std::vector<double> phi_test;
         const bool test_u8 = input_map || (!test.reduced() && feature_scale == 1.);
-        if (heldout && !test_u8) phi_test = all_features(test, false, feature_scale);
+        if ((heldout || stream) && !test_u8) phi_test = all_features(test, false, feature_scale);
+        if (stream) {                                                                   // planned as a run with heldout = no: the evaluation needs no context of its own
+            std::printf("Held-out: streamed evaluation of %d images on the training context (%s), before the first sweep and after every sweep", totNtest,
+                        test_u8 ? "tnml_evaluate_u8" : "tnml_evaluate_phi");
+            if (heldout_every > 0) std::printf(" and every %ld bond updates", heldout_every);
+            std::printf("\n");
+        }
         std::vector<tnml_heldout_report> ho_rep(nranks);
         // rank 0 prints the sums of the ranks' held-out shards (local values: no collective)
         auto heldout_sum = [&]() {
@@ -313,6 +325,19 @@ int main(int argc, const char* argv[]) {
                 else         CK(hctx, tnml_set_data_phi(hctx, phi_test.data() + (size_t)tlo[r] * N * 2, test.labels.data() + tlo[r]));
             }
             if (nranks > 1) { int cnt = 0; CK(ctx, tnml_replica_check(ctx, &cnt)); if (root) std::printf("%s communicator of %d ranks, W replicas identical\n", oneshot ? "one-shot peer-write" : (share_device ? "in-process" : "RCCL"), cnt); }
+            // heldout = stream: this rank's shard of the held-out set through the chain kernel on its own training context (reads W only;
+            // nothing of a bond update may be in flight); rank 0 sums the ranks' values in rank order, as under heldout = yes
+            auto stream_eval = [&]() {
+                tnml_eval_report e;
+                const int64_t cnt = thi[r] - tlo[r];
+                if (test_u8) CK(ctx, tnml_evaluate_u8(ctx, cnt, test_bytes + (size_t)tlo[r] * St, test.labels.data() + tlo[r], &e, nullptr, nullptr));
+                else         CK(ctx, tnml_evaluate_phi(ctx, cnt, phi_test.data() + (size_t)tlo[r] * N * 2, test.labels.data() + tlo[r], &e, nullptr, nullptr));
+                ho_rep[r] = tnml_heldout_report{};
+                ho_rep[r].cost = e.cost; ho_rep[r].ncorrect = e.ncorrect; ho_rep[r].count = e.n;
+                if (nranks > 1) bar.wait();
+            };
+            const int bonds_per_sweep = 2 * (N - 1);
+            auto eval_after = [&](int idx) { return stream && (idx == bonds_per_sweep || (heldout_every > 0 && idx % heldout_every == 0)); };   // idx: 1-based bond update of the sweep
             if (root) { std::printf("Projecting training states..."); std::fflush(stdout); }   // :740
             CK(ctx, tnml_env_init(ctx));                                                    // :741
             if (root) { std::printf("done\n"); std::printf("Calling quadcost...\n"); }     // :744
@@ -333,6 +358,10 @@ int main(int argc, const char* argv[]) {
                 bar.wait();
                 if (root) print_heldout();
             }
+            if (stream) {
+                stream_eval();
+                if (root) print_heldout();
+            }
             if (root && pause_step) { std::printf("PAUSE"); std::fflush(stdout); std::getchar(); }
             bar.wait();
 
@@ -343,10 +372,10 @@ int main(int argc, const char* argv[]) {
             // bond's cost partials ride in this bond's first all-reduce.  The log lines of a bond therefore appear while the next one
             // runs, and the WRITE_WF / LAMBDA hooks act one bond later than in the reference (input key `pipeline = no`, or
             // pause_step, restores the strict order).  Nothing is in flight across a sweep boundary.
-            struct InFlight { long sw; int b, ha; double lam; bool on = false; } fl;
+            struct InFlight { long sw; int b, ha; double lam; bool on = false; int idx = 0; } fl;
             FILE* blog = (root && !bond_log.empty()) ? std::fopen(bond_log.c_str(), "w") : nullptr;
             if (blog) std::fprintf(blog, "sweep,half,bond,lambda,cg_passes,cost_after_svd,reg_cost,ncorrect,ntrain,orig_m,new_m,trunc_err,seconds%s\n",
-                                   heldout ? ",heldout_cost,heldout_ncorrect,nheldout" : "");
+                                   heldout || stream ? ",heldout_cost,heldout_ncorrect,nheldout" : "");
             auto t_last = std::chrono::steady_clock::now();
             auto finish = [&]() {                                                           // report + log + hooks of the bond update in flight
                 if (!fl.on) return;
@@ -358,6 +387,8 @@ int main(int argc, const char* argv[]) {
                     CK(ctx, tnml_heldout_read(ctx, &ho_rep[r]));
                     if (nranks > 1) bar.wait();
                 }
+                const bool evaluated = eval_after(fl.idx);                              // (the loop below has left nothing in flight behind such a bond update)
+                if (evaluated) stream_eval();
                 if (root) {
                     const tnml_bond_report& r_ = rep;
                     std::printf("Sweep %ld Half %d Bond %d\n", sw, ha, r_.c);           // :490
@@ -382,15 +413,15 @@ int main(int argc, const char* argv[]) {
                     std::printf("Percent correct = %.4f%%, # incorrect = %lld/%d\n", r_.ncorrect * 100. / totNtrain,
                                 (long long)(totNtrain - r_.ncorrect), totNtrain);       // :341-342
                     std::printf("--> After SVD, Cost = %.10f\n", r_.cost_after_svd / totNtrain);   // :533
-                    if (heldout) print_heldout();
+                    if (heldout || evaluated) print_heldout();
                     if (blog) {                                                         // seconds: wall time since the previous report (pipelined: one bond update of GPU time)
                         const auto t_now = std::chrono::steady_clock::now();
                         std::fprintf(blog, "%ld,%d,%d,%.6e,%d,%.17g,%.17g,%lld,%d,%d,%d,%.6e,%.6f", sw, ha, r_.c, fl.lam, r_.cg.npass_done, r_.cost_after_svd / totNtrain,
                                      r_.reg_cost / totNtrain, (long long)r_.ncorrect, totNtrain, r_.origm, r_.newm, r_.truncerr, std::chrono::duration<double>(t_now - t_last).count());
-                        if (heldout) {
+                        if (heldout || evaluated) {
                             const tnml_heldout_report s = heldout_sum();
                             std::fprintf(blog, ",%.17g,%lld,%d", s.cost / totNtest, (long long)s.ncorrect, totNtest);
-                        }
+                        } else if (stream) std::fprintf(blog, ",,,");
                         std::fprintf(blog, "\n");
                         t_last = t_now;
                     }
@@ -418,13 +449,14 @@ int main(int argc, const char* argv[]) {
             };
             for (long sw = 1; sw <= Nsweep; ++sw) {                                         // mldmrg, :470
                 if (root) std::printf("\nSweep %ld maxm=%ld minm=%ld\n", sw, maxm, minm);  // :472
+                int idx = 0;
                 for (int b = 1, ha = 1; ha <= 2; tnml_sweepnext(&b, &ha, N)) {              // :478
                     tnml_sweep_params sp{(int)std::min<long>(maxm, cfg.maxm), (int)std::min<long>(minm, cfg.maxm), cutoff, (int)Npass, lam, lambda_cost, cconv, 0};
-                    const InFlight next{sw, b, ha, lam, true};
+                    const InFlight next{sw, b, ha, lam, true, ++idx};
                     CK(ctx, tnml_bond_update_begin(ctx, b, ha, &sp));
                     finish();                                                               // the previous bond update (none at the start of a sweep)
                     fl = next;
-                    if (!pipeline || pause_step) finish();
+                    if (!pipeline || pause_step || eval_after(idx)) finish();               // (an evaluation follows this bond update: it is ended first)
                 }
                 finish();
                 if (root && spec_predict) {

@@ -9,7 +9,8 @@
 // `seed` here (the reference's is time-seeded).  Extensions (never read by the reference): `seed`, `device`, `precision`, `imglen`,
 // `feature_scale` as in the fixedL driver; `labels`, `ngpu`, `share_device`, `dry_run`: the one-label-per-GPU launcher
 // of BASELINE config 4 (launch_per_label below); `heldout`, `Ntest`: the t10k images follow the training as a held-out context
-// (one "Held-out:" line per bond update; correct = [f > 1/2] == [label == L], the rule of tnml_classify); `input_map` (yes | no, default no):
+// (one "Held-out:" line per bond update; correct = [f > 1/2] == [label == L], the rule of tnml_classify; heldout = stream: no second
+// context, tnml_evaluate_* on the training context before the first sweep, after every sweep and every `heldout_every`-th bond update); `input_map` (yes | no, default no):
 // the images reach the device as the bytes of the idx file (tnml_set_input_map), same log and same W<label>.
 #include <sys/stat.h>
 #include <sys/wait.h>
@@ -142,7 +143,10 @@ int main(int argc, const char* argv[]) {
         const std::string precision = input.getString("precision", "f64");
         const long imglen = input.getInt("imglen", 0);
         const double feature_scale = input.getReal("feature_scale", 1.);
-        const bool heldout = input.getYesNo("heldout", false);
+        const bool stream = input.getString("heldout", "no") == "stream";               // heldout = stream: the t10k images are evaluated on the training context itself (tnml_evaluate_*), no second context
+        const bool heldout = !stream && input.getYesNo("heldout", false);
+        const long heldout_every = input.getInt("heldout_every", 0);                     // heldout = stream: also evaluate after every k-th bond update of a sweep; 0: sweep ends only
+        if (heldout_every < 0) { std::printf("heldout_every must be >= 0\n"); return 1; }
         const long Ntest = input.getInt("Ntest", 50000);
         const bool input_map = input.getYesNo("input_map", false);                       // extension: the images reach the device as the bytes of the idx file (tnml_set_input_map)
         const bool spec_predict = input.getYesNo("spec_predict", false);                 // extension: truncating splits run without their host synchronisation on a predicted bond dimension (option spec_predict)
@@ -158,7 +162,8 @@ int main(int argc, const char* argv[]) {
         Dataset train_raw, test_raw;                                                    // input_map = yes: the bytes of the idx files (the initial W is still built from the reduced copy)
         Dataset train = read_images(datadir, true, Ntrain, imglen, input_map ? &train_raw : nullptr);   // :56
         Dataset test;                                                                   // the held-out set: read before any context exists
-        if (heldout && !read_heldout(datadir, Ntest, imglen, train, &test, input_map ? &test_raw : nullptr)) return 1;
+        if ((heldout || stream) && !read_heldout(datadir, Ntest, imglen, train, &test, input_map ? &test_raw : nullptr)) return 1;
+        if (stream && input_map && test_raw.npix() != train_raw.npix()) { std::printf("heldout = stream: the t10k files have %d bytes per image, the training files %d\n", test_raw.npix(), train_raw.npix()); return 1; }
         const int N = train.npix();
         std::printf("%d sites\n", N);                                                  // :59
         if (file_exists("sites")) { int Ns, ds; read_sites("sites", &Ns, &ds); if (Ns != N || ds != 2) { std::printf("Mismatched sizes\n"); return 1; } }
@@ -261,6 +266,21 @@ int main(int argc, const char* argv[]) {
         CK(ctx, tnml_env_init(ctx));                                                    // :184-199
         std::printf("done\n");
         auto print_heldout = [&]() { tnml_heldout_report h; CK(ctx, tnml_heldout_read(ctx, &h)); print_heldout_line(h.cost, h.ncorrect, h.count); };
+        // heldout = stream: the held-out images through the chain kernel on the training context (reads W only; tnml_bond_update leaves nothing in flight)
+        std::vector<double> sphi;
+        if (stream) {
+            if (!input_map) sphi = all_features(test, normal, feature_scale);
+            std::printf("Held-out: streamed evaluation of %d images on the training context (%s), before the first sweep and after every sweep", test.size(),
+                        input_map ? "tnml_evaluate_u8" : "tnml_evaluate_phi");
+            if (heldout_every > 0) std::printf(" and every %ld bond updates", heldout_every);
+            std::printf("\n");
+        }
+        auto stream_eval = [&]() {
+            tnml_eval_report e;
+            if (input_map) CK(ctx, tnml_evaluate_u8(ctx, test.size(), test_raw.pixels.data(), test.labels.data(), &e, nullptr, nullptr));
+            else           CK(ctx, tnml_evaluate_phi(ctx, test.size(), sphi.data(), test.labels.data(), &e, nullptr, nullptr));
+            print_heldout_line(e.cost, e.ncorrect, e.n);
+        };
         {
             int mL, mR, lab; CK(ctx, tnml_bond_dims(ctx, 1, &mL, &mR, &lab));
             std::vector<double> B((size_t)mL * 4 * mR);
@@ -270,9 +290,12 @@ int main(int argc, const char* argv[]) {
             std::printf("Before DMRG, Cost = %.10f\n", C / Ntrain);                     // :218 (divides by the per-label cap, as the reference)
         }
         if (heldout) { CK(ctx, tnml_heldout_attach(ctx, hctx)); print_heldout(); }
+        if (stream) stream_eval();
+        const int bonds_per_sweep = 2 * (N - 1);
         const double NT = (double)totNtrain;                                            // single.h:535 Ntrain = ts.size()
         for (long sw = 1; sw <= Nsweep; ++sw) {                                         // single.h:546
             std::printf("Sweep %ld maxm=%ld\n", sw, maxm);                              // :548
+            int idx = 0;                                                                // bond updates of this sweep so far
             for (int b = 1, ha = 1; ha <= 2; tnml_sweepnext(&b, &ha, N)) {              // :554
                 tnml_sweep_params sp{(int)std::min<long>(maxm, cfg.maxm), (int)std::min<long>(minm, cfg.maxm), cutoff, (int)Npass, lambda, lambda, cconv, 1};
                 tnml_bond_report r;
@@ -327,6 +350,8 @@ int main(int argc, const char* argv[]) {
                 std::printf("--> After SVD, Cost = %.10f (%.10f)\n", r.cost_after_svd / NT, r.cost_after_svd);   // :684
                 if (r.cost_after_svd > 1.1 * r.cost_cg) std::printf("> 10%% larger C after SVD\n");   // :686
                 if (heldout) print_heldout();
+                ++idx;
+                if (stream && (idx == bonds_per_sweep || (heldout_every > 0 && idx % heldout_every == 0))) stream_eval();
                 if (pause_steps) { std::printf("PAUSE"); std::fflush(stdout); std::getchar(); }
                 if (file_exists("WRITE_WF")) {                                          // :712-718
                     std::printf("File WRITE_WF found\n");

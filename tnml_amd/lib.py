@@ -34,7 +34,7 @@ EXPORTS = [
     "tnml_lin_cg_start", "tnml_lin_cg_run", "tnml_lin_get_v", "tnml_lin_evaluate",
     "tnml_heldout_attach", "tnml_heldout_detach", "tnml_heldout_read",
     "tnml_mps_place", "tnml_mps_compress", "tnml_mps_overlap",
-    "tnml_predict_u8", "tnml_predict_phi",
+    "tnml_predict_u8", "tnml_predict_phi", "tnml_evaluate_u8", "tnml_evaluate_phi",
     "tnml_set_input_map", "tnml_get_input_map",
 ]
 
@@ -67,6 +67,11 @@ class BondReport(C.Structure):
 class HeldoutReport(C.Structure):
     _fields_ = [("bond", C.c_int), ("half", C.c_int), ("count", C.c_int64), ("ncorrect", C.c_int64),
                 ("cost", C.c_double), ("label_cost", C.c_double * NL)]
+
+
+class EvalReport(C.Structure):
+    _fields_ = [("n", C.c_int64), ("ncorrect", C.c_int64), ("cost", C.c_double), ("label_cost", C.c_double * NL),
+                ("count", C.c_int64 * NL), ("nincorrect", C.c_int64 * NL), ("confusion", (C.c_int64 * NL) * NL)]
 
 
 class CompressReport(C.Structure):
@@ -139,6 +144,8 @@ def load():
     L.tnml_device_bytes.restype = C.c_int64
     L.tnml_predict_u8.argtypes = [vp, C.c_int64, C.POINTER(C.c_uint8), dp, C.POINTER(C.c_int32)]
     L.tnml_predict_phi.argtypes = [vp, C.c_int64, dp, dp, C.POINTER(C.c_int32)]
+    L.tnml_evaluate_u8.argtypes = [vp, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(EvalReport), dp, C.POINTER(C.c_int32)]
+    L.tnml_evaluate_phi.argtypes = [vp, C.c_int64, dp, C.POINTER(C.c_int32), C.POINTER(EvalReport), dp, C.POINTER(C.c_int32)]
     L.tnml_set_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_get_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_replica_check.argtypes = [vp, ip]

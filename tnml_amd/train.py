@@ -7,7 +7,9 @@ lines as the C++ driver (tnml_amd/host/fixedl_main.cpp, which runs one GPU); the
 ranks with tnml_shard_bounds and the gradient / cost sums go through the library's RCCL all-reduce
 (BASELINE config 3: "batch sharded across 8xMI355X").  torch.distributed (gloo) is only the control plane: the RCCL
 unique id, the LAMBDA hot reload, barriers and the sums of the held-out shards (`heldout = yes`: the t10k images, capped at
-`Ntest` per label, follow the training in a held-out context per rank; one "Held-out:" line per bond update).  Rank 0 prints
+`Ntest` per label, follow the training in a held-out context per rank; one "Held-out:" line per bond update; `heldout = stream`: no second
+context, every rank evaluates its shard on its training context -- TrainStates.evaluate -- before the first sweep, after every
+sweep and after every `heldout_every`-th bond update).  Rank 0 prints
 and writes files.  A single process (no launcher) works too and is what the tests run.  `input_map = yes` (default no) hands the
 bytes of the idx file to the device, which reduces, maps and transposes them (tnml_set_input_map): same log, same W.
 """
@@ -56,8 +58,13 @@ def main(argv=None):
     precision = key("precision", "f64")
     imglen = key("imglen", 0, int)
     feature_scale = key("feature_scale", 1.0, float)
+    stream = (hostlib.input_get(inp, "heldout") or "").strip() == "stream"     # heldout = stream: evaluated on the training context itself (TrainStates.evaluate), no second context
+    heldout_every = key("heldout_every", 0, int)                               # heldout = stream: also after every k-th bond update of a sweep; 0: sweep ends only
+    if heldout_every < 0:
+        say("heldout_every must be >= 0")
+        return 1
     try:
-        heldout = hostlib.input_yesno(inp, "heldout", False)
+        heldout = False if stream else hostlib.input_yesno(inp, "heldout", False)
         spec_predict = hostlib.input_yesno(inp, "spec_predict", False)
         use_map = hostlib.input_yesno(inp, "input_map", False)                  # the images reach the device as the bytes of the idx file (tnml_set_input_map)
     except RuntimeError as e:
@@ -82,7 +89,7 @@ def main(argv=None):
         vals = hostlib.reduce(px, side, imglen)
     else:
         vals = None
-    if heldout:                                                                 # the held-out set: read before any context exists
+    if heldout or stream:                                                       # the held-out set: read before any context exists
         try:
             tpx, tlab, _ = hostlib.read_mnist(datadir, False, Ntest)
         except RuntimeError as e:
@@ -190,6 +197,16 @@ def main(argv=None):
         ts.comm_init(uid[0])
     if spec_predict:                                                            # truncating splits on a predicted bond dimension (option spec_predict)
         ts.set_option("spec_predict", 1)
+    if stream:                                                                  # this rank's shard of the held-out set, as evaluate() takes it
+        hlo, hhi = lib.shard_bounds(len(tlab), world, rank)
+        if imap is not None or (tvals is None and feature_scale == 1.0):
+            held_images = dict(pixels=tpx[hlo:hhi])
+        else:
+            g = (tvals[hlo:hhi] if tvals is not None else tpx[hlo:hhi].astype(np.float64)) / 255.0
+            held_images = dict(phi=np.stack([np.ones_like(g), feature_scale * ((g / 255.0) / 4.0)], axis=-1))
+        say("Held-out: streamed evaluation of %d images on the training context (%s), before the first sweep and after every sweep%s"
+            % (len(tlab), "tnml_evaluate_u8" if "pixels" in held_images else "tnml_evaluate_phi",
+               " and every %d bond updates" % heldout_every if heldout_every > 0 else ""))
     ts.set_mps(W)
     say("Projecting training states...")
     ts.init()                                                                   # fixedL.cc:741
@@ -199,7 +216,11 @@ def main(argv=None):
     say("Before starting DMRG Cost = %.10f" % (C0 / NT))
 
     def say_heldout():
-        h = ts.heldout_report()
+        if stream:                                                              # (bond_update has left nothing in flight)
+            e = ts.evaluate(tlab[hlo:hhi], **held_images)
+            h = dict(cost=e.cost, ncorrect=e.ncorrect, count=e.n)
+        else:
+            h = ts.heldout_report()
         t = torch.tensor([h["cost"], float(h["ncorrect"]), float(h["count"])], dtype=torch.float64)
         if world > 1:
             dist.all_reduce(t)                                                  # local sums of the shards (exact in fp64 for the counts)
@@ -208,12 +229,16 @@ def main(argv=None):
     if hs is not None:
         ts.attach_heldout(hs)
         say_heldout()
+    if stream:
+        say_heldout()
+    bonds_per_sweep = 2 * (N - 1)
 
     lam_cost = lam                                                              # cargs copy, fixedL.cc:467
     for sw in range(1, Nsweep + 1):
         say("\nSweep %d maxm=%d minm=%d" % (sw, maxm, minm))
-        b, ha = 1, 1
+        b, ha, idx = 1, 1, 0
         while ha <= 2:
+            idx += 1
             r = ts.bond_update(b, ha, min(maxm, ctx_maxm), minm, cutoff, Npass, lam, cconv, lam_cost=lam_cost)
             if rank == 0:
                 say("Sweep %d Half %d Bond %d" % (sw, ha, r["c"]))
@@ -234,7 +259,7 @@ def main(argv=None):
                 say("  Reg. cost CR = %.10f" % (r["reg_cost"] / NT))
                 say("Percent correct = %.4f%%, # incorrect = %d/%d" % (r["ncorrect"] * 100.0 / NT, NT - r["ncorrect"], NT))
                 say("--> After SVD, Cost = %.10f" % (r["cost"] / NT))
-            if hs is not None:
+            if hs is not None or (stream and (idx == bonds_per_sweep or (heldout_every > 0 and idx % heldout_every == 0))):
                 say_heldout()
             # file hooks: rank 0 looks, every rank follows (fixedL.cc:542-559)
             hook = [None, None]

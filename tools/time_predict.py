@@ -2,11 +2,14 @@
 data-less context, for n = 256, 10 000 and 60 000 images.
 
     python tools/time_predict.py [--n 256,10000,60000] [--repeats 3] [--chunk C] [--timeout 300] [--out profiles/predict_time.txt]
-                                 [--dtype f64,f32] [--big N,m,n]
+                                 [--dtype f64,f32] [--big N,m,n] [--evaluate]
 
 --dtype f64,f32 adds a predict leg under option predict_dtype = 1 (the fp32 chain kernel) to the alternation, prints its chain time next
 to the fp64 one, and ends with `--repeats` legs at a bond dimension the fp64 path refuses (--big, default N = 196, m = 600, n = 2048;
 fp32 only; "" leaves them out); the default output is then profiles/predict_time_f32.txt.
+
+--evaluate times tnml_evaluate_u8 (labels in, only the report back) against tnml_predict_u8 on the same images instead: the two
+alternated, no classify legs; the default image count is then 10 000 and the default output profiles/evaluate_time.txt.
 
 Every leg runs in a child process of its own under `timeout`; a child that fails or hangs ends the tool (nothing more is started on
 the GPU).  Per image count: one warm-up leg of each path (discarded), then the two paths alternated, `--repeats` legs each.  A leg
@@ -44,10 +47,12 @@ def child(path, n, chunk=0, N=N, M=M):
     ts.synchronize()
     t_ctx = time.perf_counter() - t0
     ts.set_mps(W)
-    if chunk and path == "predict":
+    if chunk and path in ("predict", "evaluate"):
         ts.set_option("predict_chunk", chunk)
 
     def call():
+        if path == "evaluate":                    # only the report comes back: (report, None) in the place of (weights, pred)
+            return ts.evaluate(labels, pixels=pixels), None
         return ts.classify()[:2] if path == "classify" else ts.predict(pixels=pixels)
     if path == "predict_f32":
         ts.set_option("predict_dtype", 1)
@@ -63,8 +68,13 @@ def child(path, n, chunk=0, N=N, M=M):
     prof = {k: v for k, v in ts.profile_read().items() if v[0]}
     ts.profile(False)
     out = dict(path=path, n=n, seconds_call=dt, images_per_s=n / dt, seconds_context=t_ctx, device_bytes=ts.device_bytes(),
-               launches={k: v[0] for k, v in prof.items()}, kernel_ms={k: v[1] for k, v in prof.items()},
-               checksum=float(np.abs(w).sum()), pred_hist=np.bincount(pred, minlength=10).tolist())
+               launches={k: v[0] for k, v in prof.items()}, kernel_ms={k: v[1] for k, v in prof.items()})
+    if path == "evaluate":
+        out.update(ncorrect=w.ncorrect, cost=w.cost, pred_hist=w.confusion.sum(axis=0).tolist())
+    else:
+        out.update(checksum=float(np.abs(w).sum()), pred_hist=np.bincount(pred, minlength=10).tolist())
+        if path == "predict":                     # what an evaluation of these images has to report
+            out.update(ncorrect=int((pred == labels).sum()), cost=float(((w - np.eye(10)[labels]) ** 2).sum()))
     if path == "predict_f32" and M <= 512:        # the fp64 chain kernel on the same context: where do the two disagree
         w64, p64 = ts.predict(pixels=pixels, dtype="f64")
         top = np.sort(np.abs(w64), axis=1)
@@ -78,7 +88,8 @@ def child(path, n, chunk=0, N=N, M=M):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--n", default="256,10000,60000")
+    ap.add_argument("--n", default="")
+    ap.add_argument("--evaluate", action="store_true", help="tnml_evaluate_u8 against tnml_predict_u8, alternated (default --n 10000)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--timeout", type=int, default=300)
     ap.add_argument("--out", default="")
@@ -95,8 +106,11 @@ def main():
     if dtypes not in (["f64"], ["f64", "f32"]):
         ap.error("--dtype must be f64 or f64,f32")
     f32 = "f32" in dtypes
-    a.out = a.out or os.path.join(ROOT, "profiles", "predict_time_f32.txt" if f32 else "predict_time.txt")
-    paths = ("classify", "predict", "predict_f32") if f32 else ("classify", "predict")
+    if a.evaluate and f32:
+        ap.error("--evaluate takes --dtype f64")
+    a.n = a.n or ("10000" if a.evaluate else "256,10000,60000")
+    a.out = a.out or os.path.join(ROOT, "profiles", "evaluate_time.txt" if a.evaluate else "predict_time_f32.txt" if f32 else "predict_time.txt")
+    paths = ("predict", "evaluate") if a.evaluate else ("classify", "predict", "predict_f32") if f32 else ("classify", "predict")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     open(a.out, "w").close()
 
@@ -116,8 +130,8 @@ def main():
 
     def spread(v):
         return "%.4f s (min %.4f, max %.4f)" % (sorted(v)[len(v) // 2], min(v), max(v))
-    say("inference from bytes, N = %d, m = %d, %s; per leg one untimed call, one timed call; median (min, max) of %d legs%s"
-        % (N, M, "fp64 and fp32 (option predict_dtype)" if f32 else "fp64", a.repeats, "; predict_chunk = %d" % a.chunk if a.chunk else ""))
+    say("%s from bytes, N = %d, m = %d, %s; per leg one untimed call, one timed call; median (min, max) of %d legs%s"
+        % ("tnml_evaluate_u8 against tnml_predict_u8" if a.evaluate else "inference", N, M, "fp64 and fp32 (option predict_dtype)" if f32 else "fp64", a.repeats, "; predict_chunk = %d" % a.chunk if a.chunk else ""))
     rc = 0
     results = []
     for n in (int(x) for x in a.n.split(",")):
@@ -136,6 +150,21 @@ def main():
                 break
         if rc:
             break
+        if a.evaluate:
+            p, e = res["predict"], res["evaluate"]
+            tp, te = [r["seconds_call"] for r in p], [r["seconds_call"] for r in e]
+            say("n = %d" % n)
+            say("  tnml_predict_u8  call %s = %.0f images/s; launches %s; device bytes %d"
+                % (spread(tp), n / sorted(tp)[len(tp) // 2], json.dumps(p[0]["launches"], sort_keys=True), p[0]["device_bytes"]))
+            say("  tnml_evaluate_u8 call %s = %.0f images/s; launches %s; device bytes %d"
+                % (spread(te), n / sorted(te)[len(te) // 2], json.dumps(e[0]["launches"], sort_keys=True), e[0]["device_bytes"]))
+            say("  chain kernel %.3f ms under predict, %.3f ms under evaluate; tally kernel (class eval_tally) %.3f ms per call"
+                % (p[0]["kernel_ms"].get("chain", 0.), e[0]["kernel_ms"].get("chain", 0.), e[0]["kernel_ms"].get("eval_tally", 0.)))
+            med_p, med_e = sorted(tp)[len(tp) // 2], sorted(te)[len(te) // 2]
+            say("  evaluate / predict (call alone) = %.3f; evaluate's median is %s predict's own min-max; ncorrect evaluate %d, from predict's output %d; cost %.12e, from predict's output %.12e"
+                % (med_e / med_p, "inside" if min(tp) <= med_e <= max(tp) else "below" if med_e < min(tp) else "above", e[0]["ncorrect"], p[0]["ncorrect"], e[0]["cost"], p[0]["cost"]))
+            results.append(dict(n=n, predict=p, evaluate=e))
+            continue
         c, p = res["classify"], res["predict"]
         tc, tp, tx = [r["seconds_call"] for r in c], [r["seconds_call"] for r in p], [r["seconds_context"] for r in c]
         say("n = %d" % n)
