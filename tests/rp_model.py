@@ -7,7 +7,7 @@ accumulation, and `bound` is a worst-case figure for that.
 
 Where the kernels round
   all modes      features are stored in fp32; the bond tensor / site tensor is rounded fp64 -> fp32 once (k_cvt, k_pack, k_m_bf16t)
-  staged paths   X[n][2a + s] = fl32(E[n][a] * phi[n][s]) is formed in fp32 (k_fgemm, k_fgemm_bf16, k_bgemm, k_bgemm_bf16); in the bf16
+  staged paths   X[n][2a + s] = fl32(E[n][a] * phi[n][s]) is formed in fp32 (k_fgemm and k_bgemm on either matrix pipe); in the bf16
                  modes X and every element of M are then rounded to bf16, round to nearest even by the bit formula of f2bf
   converted once k_fgemm_bf16e rounds the RAW environment to bf16 (k_env_bf16t) and the bond matrix to bf16 (k_m_bf16t); both site
                  features are applied to the fp32 accumulators: T = sum_t phiO_t sum_s phiI_s acc[s][t]
@@ -69,9 +69,9 @@ def _ru(x, k):
 
 
 def bgemm_cut(mode, mI, mO, L, NTp, maxm):
-    """the slab cut of the gradient GEMM, restated from launch_bgemm / bgemm_go: tile class, slab count, images per slab, images of the
+    """the slab cut of the gradient GEMM, restated from launch_bgemm: tile class, slab count, images per slab, images of the
     last slab.  `mode` is the context's dtype (the bf16 modes pad the reduction dimension to 32), maxm the context's.
-    The library does not report its cut, so this is a copy that has to be kept in step with bgemm_go BY HAND (tile classes, the 1024-tile
+    The library does not report its cut, so this is a copy that has to be kept in step with launch_bgemm BY HAND (tile classes, the 1024-tile
     target, the slab workspace of 128 Kmax^2 floats): after a change of the cut there, the bound's `per` and the shapes that reach a short
     last slab / one chunk per slab have to be worked out again here and in test_rp_model_gpu.py."""
     bf = mode != "f32"
@@ -176,7 +176,7 @@ class Model:
     # -- the three launch sequences
     def forward_model(self, mode, path, kind, EI, phiI, B, phiO, EX):
         """P [NT, L] of TrainStates.forward (L = 10; 1 for a 4-index B with kind 2, the per-label variant) and its bound.
-        path "staged": k_fgemm / k_fgemm_bf16; "once": k_fgemm_bf16e (bf16 modes, Label on an environment)."""
+        path "staged": k_fgemm on the mode's matrix pipe; "once": k_fgemm_bf16e (bf16 modes, Label on an environment)."""
         EI, phiI, phiO, EX = self.f32(EI), self.f32(phiI), self.f32(phiO), self.f32(EX)
         M = self.f32(self.m_layout(kind, B))
         L, mI, mO = M.shape[0], M.shape[1], M.shape[3]
@@ -212,7 +212,7 @@ class Model:
 
     def gradient_model(self, mode, kind, EI, phiI, phiO, EX, P, labels, per, Bndim, target=None, bf16_grad=True):
         """G in the shape of B (TrainStates.gradient) and its bound.  P: what the device's forward pass returned for the same B
-        ([NT, L]); per: images per slab (bgemm_cut); target: the per-label variant's label; bf16_grad False: the fp32 kernel (k_bgemm)
+        ([NT, L]); per: images per slab (bgemm_cut); target: the per-label variant's label; bf16_grad False: k_bgemm on the fp32 pipe
         in a bf16 mode."""
         EI, phiI, phiO, EX = self.f32(EI), self.f32(phiI), self.f32(phiO), self.f32(EX)
         P = np.asarray(P, dtype=np.float64).reshape(EI.shape[0], -1)

@@ -1636,7 +1636,7 @@ def test_bond_dimension_above_120_splits_on_the_workgroup_cluster(m, NT):
 
 @pytest.mark.parametrize("dtype,gate_on,gate_off", [("bf16x3", 2e-4, 2e-5), ("bf16", 5e-2, 5e-3)])
 def test_gradient_gemm_on_the_bf16_pipe(dtype, gate_on, gate_off):
-    """dP*dag(t.v) (fixedL.cc:379,418) in the bf16 study modes (BASELINE config 5: bf16 MFMA bond contraction): k_bgemm_bf16 rounds both
+    """dP*dag(t.v) (fixedL.cc:379,418) in the bf16 study modes (BASELINE config 5: bf16 MFMA bond contraction): k_bgemm on the bf16 pipe rounds both
     operands of the gradient GEMM to bf16 (plain: 8 mantissa bits; hi + lo: ~16) and accumulates in fp32; with option bf16_grad = 0
     the fp32 kernel of round 3 runs instead.  All three bond kinds; the gates are the operand precision (a wrong fragment layout gives
     O(1)); the residuals dP that weight the sum come from the mode's own forward pass, so the fp32 kernel's result carries that error too."""

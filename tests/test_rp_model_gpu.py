@@ -76,7 +76,7 @@ class Chain:
         path = "once" if (once == 1 and kind != 2) else "staged"
         P = ts.forward(B).reshape(self.NT, -1)
         Pm, bound = rp.forward_model(self.dtype, path, kind, EI, phiI, B, phiO, EX)
-        kernel = "k_fgemm_bf16e" if path == "once" else ("k_fgemm" if self.dtype == "f32" else "k_fgemm_bf16")
+        kernel = "k_fgemm_bf16e" if path == "once" else ("k_fgemm/f32" if self.dtype == "f32" else "k_fgemm/bf16")
         self.report("forward", kernel, b, kind, EI.shape[1], EX.shape[1], _ratio(P, Pm, bound))
         return P, kind, (EI, phiI, phiO, EX)
 
@@ -103,7 +103,7 @@ class Chain:
                 G = ts.gradient(B)                              # its weights: the forward pass of the same B with the options as they stand (P above)
                 Gm, bound = rp.gradient_model(self.dtype, kind, EI, phiI, phiO, EX, P, self.labels, cut["per"], B.ndim,
                                               target=self.single, bf16_grad=grad != 0)
-                self.report("gradient", "k_bgemm_bf16" if grad == 1 else "k_bgemm", b, kind, mI, mO, _ratio(G, Gm, bound),
+                self.report("gradient", "k_bgemm/bf16" if grad == 1 else "k_bgemm/f32", b, kind, mI, mO, _ratio(G, Gm, bound),
                             " tile %d slabs %d x %d" % (cut["tile"], cut["nsplit"], cut["per"]))
             if bf:
                 ts.set_option("bf16_grad", 1)
@@ -117,7 +117,7 @@ class Chain:
         E = ts.env(b)
         Em, bound = rp.shift_model(self.dtype, prev, self.phi[:, b - 1], self.W[b - 1], True)
         lab = "on the environment" if prev is not None and prev.ndim == 3 else ("on the site" if E.ndim == 3 else "nowhere")
-        self.report("shift", "k_fgemm", b, 0, self.dims[b - 1], self.dims[b], _ratio(E, Em, bound), " Label " + lab)
+        self.report("shift", "k_fgemm/f32", b, 0, self.dims[b - 1], self.dims[b], _ratio(E, Em, bound), " Label " + lab)
         self.at = b + 1
 
     def shift_from_right(self, b):
@@ -128,7 +128,7 @@ class Chain:
         E = ts.env(b + 1)
         Em, bound = rp.shift_model(self.dtype, prev, self.phi[:, b], self.W[b], False)
         lab = "on the environment" if prev is not None and prev.ndim == 3 else ("on the site" if E.ndim == 3 else "nowhere")
-        self.report("shift<-", "k_fgemm", b, 0, self.dims[b + 1], self.dims[b], _ratio(E, Em, bound), " Label " + lab)
+        self.report("shift<-", "k_fgemm/f32", b, 0, self.dims[b + 1], self.dims[b], _ratio(E, Em, bound), " Label " + lab)
 
     def walk(self, bonds, gradient=True):
         """visit the bonds in `bonds` (a dict bond -> expected (mI, mO), or an iterable) from the left; every shift on the way is checked"""
@@ -150,8 +150,8 @@ class Chain:
 
 @pytest.mark.parametrize("dtype", rp.MODES)
 def test_forward_tile_classes_and_reduction_padding(dtype):
-    """every bond of [1, 2, 16, 17, 33, 64, 65, 120, 40, 2, 1] at 40 images: Np <= 32, <= 64, > 64 and == 240 of k_fgemm, <= 64 and > 64 of
-    k_fgemm_bf16, a reduction that fills its last 32-chunk (mI = 16) and one that leaves 30 padded rows (17), KH / QP of k_fgemm_bf16e exact
+    """every bond of [1, 2, 16, 17, 33, 64, 65, 120, 40, 2, 1] at 40 images: Np <= 32, <= 64, > 64 and == 240 of k_fgemm on the fp32 pipe, <= 64 and > 64
+    on the bf16 pipe, a reduction that fills its last 32-chunk (mI = 16) and one that leaves 30 padded rows (17), KH / QP of k_fgemm_bf16e exact
     (32 / 64) and one past (33, 65), the extent-1 edge bonds; Label on the right environment, on B, on the left environment"""
     with Chain(rp.FORWARD_DIMS, 40, dtype, "forward") as c:
         seen = c.walk(range(1, c.N))

@@ -58,7 +58,7 @@ def test_rounding_helpers_equal_torch_bit_for_bit():
 
 
 def test_slab_cut_of_the_issue_shapes():
-    """bgemm_cut restates bgemm_go: m = 150 with the Label on B at 700 (768 padded) images is five slabs of 160, the last of 128; a
+    """bgemm_cut restates launch_bgemm: m = 150 with the Label on B at 700 (768 padded) images is five slabs of 160, the last of 128; a
     small bond at 40 images is one 32-image chunk per slab"""
     for mode in rp.MODES:
         c = rp.bgemm_cut(mode, 150, 150, NL, 768, 150)

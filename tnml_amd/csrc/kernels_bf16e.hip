@@ -1,6 +1,6 @@
 // kernels_bf16e.hip -- the bf16 study modes (TNML_BF16 / TNML_BF16X3; BASELINE config 5's "bf16 MFMA bond contraction") with their operands
 // CONVERTED ONCE (round 6).  Through round 5 both bf16 GEMMs rounded fp32 -> bf16 while staging, on every launch and once per column block
-// of the grid: conversion kernels with MFMAs attached (k_fgemm_bf16: 66 us for the 5.5 GF of an m = 300 forward pass on a 2.5 PF pipe).
+// of the grid: conversion kernels with MFMAs attached (k_fgemm of kernels_gemm32.hip on the bf16 pipe: 66 us for the 5.5 GF of an m = 300 forward pass on a 2.5 PF pipe).
 //
 // The forward pass B*t.v (fixedL.cc:318,377,399,416), Label index on an environment:
 //     T[n][q] = sum_t phiO[t][n] sum_s phiI[s][n] ( E[n][:] . M[2a + s][2q + t] )
@@ -17,14 +17,16 @@
 //                 (lo hi + hi lo + hi hi: ~16 mantissa bits); both features in the epilogue.
 // Rounding: bf16(E) * phi in fp32 instead of bf16(E * phi) -- the same 8 (16) mantissa bits on the same operand.
 #include "tnml_internal.h"
+#include "bf16_dev.h"
 
-typedef short bf16x8e __attribute__((ext_vector_type(8)));
-typedef float f32x4e __attribute__((ext_vector_type(4)));
-static __device__ __forceinline__ unsigned short e_f2bf(float x) {
-    const unsigned u = __float_as_uint(x);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+// 8 consecutive reduction indices, hi plane at dst and -- split -- lo plane at dst + plane
+static __device__ __forceinline__ void store8(unsigned short* dst, size_t plane, int split, const float (&v)[8]) {
+    unsigned short h[8], l[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { h[i] = f2bf(v[i]); l[i] = bf_lo(v[i], h[i]); }
+    *reinterpret_cast<uint4*>(dst) = make_uint4(bf_pack(h[0], h[1]), bf_pack(h[2], h[3]), bf_pack(h[4], h[5]), bf_pack(h[6], h[7]));
+    if (split) *reinterpret_cast<uint4*>(dst + plane) = make_uint4(bf_pack(l[0], l[1]), bf_pack(l[2], l[3]), bf_pack(l[4], l[5]), bf_pack(l[6], l[7]));
 }
-static __device__ __forceinline__ float e_bf2f(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
 
 // E fp32 [mI][NTp] -> out[plane][n][KH]; grid (NTp / 64, KH / 32), 256 lanes
 __global__ __launch_bounds__(256) void k_env_bf16t(const float* __restrict__ E, int mI, int NTp, int KH, unsigned short* __restrict__ out, int split) {
@@ -36,17 +38,10 @@ __global__ __launch_bounds__(256) void k_env_bf16t(const float* __restrict__ E, 
     }
     __syncthreads();
     const int n = tid >> 2, g = tid & 3;
-    unsigned short h[8], l[8];
+    float v[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float v = tile[8 * g + i][n];
-        h[i] = e_f2bf(v);
-        l[i] = e_f2bf(v - e_bf2f(h[i]));
-    }
-    unsigned short* dst = out + (size_t)(n0 + n) * KH + a0 + 8 * g;
-    *reinterpret_cast<uint4*>(dst) = make_uint4((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16), (unsigned)h[4] | ((unsigned)h[5] << 16), (unsigned)h[6] | ((unsigned)h[7] << 16));
-    if (split)
-        *reinterpret_cast<uint4*>(dst + (size_t)NTp * KH) = make_uint4((unsigned)l[0] | ((unsigned)l[1] << 16), (unsigned)l[2] | ((unsigned)l[3] << 16), (unsigned)l[4] | ((unsigned)l[5] << 16), (unsigned)l[6] | ((unsigned)l[7] << 16));
+    for (int i = 0; i < 8; ++i) v[i] = tile[8 * g + i][n];
+    store8(out + (size_t)(n0 + n) * KH + a0 + 8 * g, (size_t)NTp * KH, split, v);
 }
 
 // M fp64 M-layout [Kp][Np] (row 2a + s, column 2q + t) -> out[plane][s][t][q][KH]; one lane per (s, t, q, 8 consecutive a), q fastest
@@ -57,18 +52,13 @@ __global__ __launch_bounds__(256) void k_m_bf16t(const double* __restrict__ M, i
     const int q = idx % QP, rest = idx / QP;
     const int a8 = rest % ng, st = rest / ng;
     const int s = st >> 1, t = st & 1;
-    unsigned short h[8], l[8];
+    float v[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int row = 2 * (8 * a8 + i) + s, col = 2 * q + t;
-        const float v = (q < mO && row < Kp && col < Np) ? (float)M[(size_t)row * Np + col] : 0.f;
-        h[i] = e_f2bf(v);
-        l[i] = e_f2bf(v - e_bf2f(h[i]));
+        v[i] = (q < mO && row < Kp && col < Np) ? (float)M[(size_t)row * Np + col] : 0.f;
     }
-    unsigned short* dst = out + ((size_t)st * QP + q) * KH + 8 * a8;
-    *reinterpret_cast<uint4*>(dst) = make_uint4((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16), (unsigned)h[4] | ((unsigned)h[5] << 16), (unsigned)h[6] | ((unsigned)h[7] << 16));
-    if (split)
-        *reinterpret_cast<uint4*>(dst + (size_t)4 * QP * KH) = make_uint4((unsigned)l[0] | ((unsigned)l[1] << 16), (unsigned)l[2] | ((unsigned)l[3] << 16), (unsigned)l[4] | ((unsigned)l[5] << 16), (unsigned)l[6] | ((unsigned)l[7] << 16));
+    store8(out + ((size_t)st * QP + q) * KH + 8 * a8, (size_t)4 * QP * KH, split, v);
 }
 
 struct FgemmBf16eArgs {
@@ -111,7 +101,7 @@ __global__ __launch_bounds__(256, 2) void k_fgemm_bf16e(FgemmBf16eArgs A) {     
                          : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
         }
     };
-    f32x4e acc[4][2][2][2];                             // [image tile r][q tile c][s][t]
+    f32x4 acc[4][2][2][2];                             // [image tile r][q tile c][s][t]
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -119,7 +109,7 @@ __global__ __launch_bounds__(256, 2) void k_fgemm_bf16e(FgemmBf16eArgs A) {     
 #pragma unroll
             for (int s = 0; s < 2; ++s)
 #pragma unroll
-                for (int t = 0; t < 2; ++t) acc[r][c][s][t] = f32x4e{0.f, 0.f, 0.f, 0.f};
+                for (int t = 0; t < 2; ++t) acc[r][c][s][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int nchunk = KH >> 5;
     stage(0, 0);
     e_barrier();
@@ -127,11 +117,11 @@ __global__ __launch_bounds__(256, 2) void k_fgemm_bf16e(FgemmBf16eArgs A) {     
         const int cur = k & 1;
         if (k + 1 < nchunk) stage(32 * (k + 1), cur ^ 1);
         const unsigned char* base = e_lds + (size_t)cur * NBLK * 1024 + lane * 16;
-        bf16x8e ah[4], al[SPLIT ? 4 : 1];
+        bf16x8 ah[4], al[SPLIT ? 4 : 1];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            ah[r] = *reinterpret_cast<const bf16x8e*>(base + (4 * wr + r) * 1024);
-            if (SPLIT) al[r] = *reinterpret_cast<const bf16x8e*>(base + (24 + 4 * wr + r) * 1024);
+            ah[r] = *reinterpret_cast<const bf16x8*>(base + (4 * wr + r) * 1024);
+            if (SPLIT) al[r] = *reinterpret_cast<const bf16x8*>(base + (24 + 4 * wr + r) * 1024);
         }
 #pragma unroll
         for (int s = 0; s < 2; ++s)
@@ -140,9 +130,9 @@ __global__ __launch_bounds__(256, 2) void k_fgemm_bf16e(FgemmBf16eArgs A) {     
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     const int blk = 8 + (2 * s + t) * 4 + 2 * wc + c;
-                    const bf16x8e bh = *reinterpret_cast<const bf16x8e*>(base + blk * 1024);
-                    bf16x8e bl = bh;
-                    if (SPLIT) bl = *reinterpret_cast<const bf16x8e*>(base + (24 + blk) * 1024);
+                    const bf16x8 bh = *reinterpret_cast<const bf16x8*>(base + blk * 1024);
+                    bf16x8 bl = bh;
+                    if (SPLIT) bl = *reinterpret_cast<const bf16x8*>(base + (24 + blk) * 1024);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if (SPLIT) {                                   // small terms first

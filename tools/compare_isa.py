@@ -7,7 +7,9 @@
 A kernel is matched by its demangled name without the parameter list; --rename rewrites the old names first (in the order given) when
 the refactor renamed kernels.  The instruction stream of a kernel is its lines between the symbol's label and .Lfunc_end with comments
 and directives stripped and label numbers erased.  Prints one row per kernel: instructions old / new, identical or differs, VGPR /
-SGPR / private segment from the kernel's metadata.  Exit status 1 when a kernel of one side has no partner.
+SGPR / private segment / static LDS bytes from the kernel's metadata, waves per SIMD by registers old / new
+(min(8, floor(512 / (ceil(VGPR / 8) * 8)))) and `ok` when the new kernel has no private segment, the old one's LDS size and no fewer
+waves.  Exit status 1 when a kernel of one side has no partner.
 """
 import argparse
 import re
@@ -21,7 +23,7 @@ def demangle(names):
 
 
 def kernels(path):
-    """{mangled name: {"ins": [instruction lines], "vgpr": .., "sgpr": .., "priv": ..}} for the kernels (.amdhsa_kernel) of one file"""
+    """{mangled name: {"ins": [instruction lines], "vgpr": .., "sgpr": .., "priv": .., "lds": ..}} for the kernels (.amdhsa_kernel) of one file"""
     lines = open(path).read().split("\n")
     names = [l.split()[1] for l in lines if l.strip().startswith(".amdhsa_kernel ")]
     res = {}
@@ -35,7 +37,9 @@ def kernels(path):
             if not l or (l.startswith(".") and not l.endswith(":")):
                 continue
             ins.append(re.sub(r"\.L([A-Za-z_]+)\d+(_\d+)?", r".L\1", l))
-        res[name] = {"ins": ins}
+        desc = lines.index("\t.amdhsa_kernel " + name)          # the kernel descriptor: static LDS size
+        lds = re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", "\n".join(lines[desc:desc + 8]))
+        res[name] = {"ins": ins, "lds": int(lds.group(1))}
     meta = "\n".join(lines[lines.index("amdhsa.kernels:"):]) if "amdhsa.kernels:" in lines else ""
     for entry in re.split(r"\n\s*- ", meta):
         n = re.search(r"\.name:\s*(\S+)", entry)
@@ -68,14 +72,20 @@ def main():
     ap.add_argument("--rename", nargs=2, action="append", default=[], metavar=("REGEX", "REPL"))
     a = ap.parse_args()
     old, new = load(a.old, a.rename), load(a.new)
-    print("%-44s %8s %8s  %-9s  %-22s %-22s" % ("kernel (new name)", "ins old", "ins new", "stream", "VGPR/SGPR/private old", "VGPR/SGPR/private new"))
+    print("%-44s %8s %8s  %-9s  %-22s %-22s %-5s %s" % ("kernel (new name)", "ins old", "ins new", "stream", "VGPR/SGPR/priv/LDS old", "VGPR/SGPR/priv/LDS new", "waves", "resources"))
+    waves = lambda k: min(8, 512 // (-(-k["vgpr"] // 8) * 8))
+    kept = 0
     for name in sorted(set(old) | set(new)):
         o, n = old.get(name), new.get(name)
         if o is None or n is None:
             print("%-44s %s" % (name, "only in --new" if o is None else "only in --old"))
             continue
-        res = lambda k: "%d/%d/%d" % (k.get("vgpr", -1), k.get("sgpr", -1), k.get("priv", -1))
-        print("%-44s %8d %8d  %-9s  %-22s %-22s" % (name, len(o["ins"]), len(n["ins"]), "identical" if o["ins"] == n["ins"] else "differs", res(o), res(n)))
+        res = lambda k: "%d/%d/%d/%d" % (k.get("vgpr", -1), k.get("sgpr", -1), k.get("priv", -1), k.get("lds", -1))
+        ok = n["priv"] == 0 and n["lds"] == o["lds"] and waves(n) >= waves(o)
+        kept += ok
+        print("%-44s %8d %8d  %-9s  %-22s %-22s %-5s %s" % (name, len(o["ins"]), len(n["ins"]), "identical" if o["ins"] == n["ins"] else "differs", res(o), res(n),
+                                                          "%d/%d" % (waves(o), waves(n)), "ok" if ok else "WORSE"))
+    print("%d kernels, resources kept by %d" % (len(set(old) & set(new)), kept))
     return 1 if set(old) != set(new) else 0
 
 
