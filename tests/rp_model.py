@@ -16,12 +16,15 @@ Where the kernels round
                  k_zprime_t over the ten labels, in order; Label on B: z = fl32(EX * dP); then Y = fl32(z * phiO) -- all reproduced
                  bit for bit (an fp32 fma is emulated as fl32 of the fp64 sum of the exact product: a double rounding once in ~2^29)
   slab sum       fp64 (k_slab_reduce)
+  cost, pAp      the scalar epilogue of the fp32 label dot: d = fl32(target - P), val = fma(d, d, val) (pAp: fma(P, P, val)) over the labels
+                 in fp32, then fp64 sums over the images -- exact functions of the P the device returns (cost_model, pap_model), held to
+                 NT 2^-52 relative plus one fp32 ulp of one image; #correct exactly
   shift          k_fgemm without phiO in every one of these modes: fp32 operands on the fp32 matrix pipe
 
 The bound: the same contraction with every rounded operand replaced by its absolute value, times
     (n_mfma + 4) u_mfma + n_valu u_32
 n_mfma: products on the longest accumulation chain of the GEMM (the real reduction length, times three with hi + lo operands; for the
-gradient the real images of one slab); n_valu: the fp32 operations behind it (epilogue: 2 staged, 4 converted once; label dot: mO fma
+gradient the real images of one slab, or `chain`: the images of one slab whose product is not zero); n_valu: the fp32 operations behind it (epilogue: 2 staged, 4 converted once; label dot: mO fma
 plus at most 15 adds across the waves).  u_32 = 2^-24: the VALU and v_mfma_f32_16x16x4_f32, a k-ordered fmaf chain with one rounding per
 product.  u_mfma = 2^-23 inside v_mfma_f32_16x16x32_bf16, whose internal summation is not documented: the extra bit covers an adder that
 truncates.  A derived worst case, not a fitted tolerance.
@@ -29,6 +32,8 @@ truncates.  A derived worst case, not a fitted tolerance.
 Array conventions (those of oracle/pyoracle.py and tnml_amd/fixedl.py): B[a, s, t, r(, L)], A_j[a, s, r(, L)], environments [n, m(, L)],
 features of one site [n, 2].  `kind`: 0 Label on the right environment, 1 on the left one, 2 on B (with label extent 1: the per-label
 variant).  (EI, phiI) is the Label-free input side of the bond plan, (EX, phiO) the other one: see `plan`."""
+import math
+
 import numpy as np
 
 NL = 10
@@ -131,6 +136,22 @@ class Model:
     def epilogue_phi(self, phiO):
         return phiO
 
+    def images(self, NT):
+        """the images the gradient sums, as indices into its arguments (a defect repeats or leaves out some)"""
+        return np.arange(self.nimg(NT))
+
+    def cost_images(self, NT):
+        """the images the scalar epilogue of the label dot sums"""
+        return np.arange(NT)
+
+    def bucket(self, labels):
+        """the per-label cost an image is summed into"""
+        return labels
+
+    def argmax(self, a):
+        """k_labeldot: best = a[0]; a[l] > best moves it -- the first maximum"""
+        return np.argmax(a, axis=1)
+
     # -- pieces
     def planes(self, mode, x):
         if mode == "f32":
@@ -173,6 +194,46 @@ class Model:
             z = self.f32(EX[:, :, l] * dP[:, None, l] + z)
         return z
 
+    # -- the scalar epilogue of the fp32 label dot: exact functions of the P the device returns
+    def _sq_chain(self, D):
+        """val = fma(D[l], D[l], val), l in order, in fp32 (the emulation of zprime)"""
+        val = np.zeros(D.shape[0])
+        for l in range(D.shape[1]):
+            val = self.f32(D[:, l] * D[:, l] + val)
+        return val
+
+    def cost_model(self, P, labels, target=None):
+        """LD_MODE_COST of k_labeldot<.., float, float, float> from a device P ([NT, L], fp32 values): d = fl32(tgt - P_l),
+        val = fl32(d d + val) over l in order, the per-label cost the fp64 sum (math.fsum) of val over the images of that label;
+        #correct by the first maximum of |P_l| (strict >), in the per-label variant (P_0 > 0.5) == (label == target).
+        Returns dict(label_cost [10], cost (without the regulariser), ncorrect, gate [10], cost_gate): |device - model| <= gate with
+        gate = NT 2^-52 model + 2^-23 max_n val_n -- fp64 summation in another order, and one fp32 ulp of one image for the rare
+        double rounding of the emulated fma."""
+        labels = np.asarray(labels)
+        P = self.f32(np.asarray(P, dtype=np.float64).reshape(labels.shape[0], -1))
+        NT = P.shape[0]
+        if target is None:
+            tgt = (labels[:, None] == np.arange(NL)[None, :]).astype(np.float64)
+            cor = self.argmax(np.abs(P)) == labels
+        else:
+            tgt = (labels == target).astype(np.float64)[:, None]
+            cor = (P[:, 0] > 0.5) == (labels == target)
+        val = self._sq_chain(self.f32(tgt - P))
+        idx = self.cost_images(NT)
+        val, cor, bucket = val[idx], cor[idx], np.asarray(self.bucket(labels))[idx]
+        lc = np.array([math.fsum(val[bucket == l]) for l in range(NL)])
+        cost = math.fsum(val)
+        ulp = 2.0 ** -23 * (val.max() if val.size else 0.)
+        return dict(label_cost=lc, cost=cost, ncorrect=int(cor.sum()), gate=NT * 2.0 ** -52 * lc + ulp, cost_gate=NT * 2.0 ** -52 * cost + ulp)
+
+    def pap_model(self, P):
+        """LD_MODE_PAP: val = fl32(P_l P_l + val) over l in order, then the fp64 sum over the images; (sum_n |p v_n|^2, its gate)"""
+        P = np.asarray(P, dtype=np.float64)
+        P = self.f32(P.reshape(P.shape[0], -1))
+        val = self._sq_chain(P)[self.cost_images(P.shape[0])]
+        s = math.fsum(val)
+        return s, P.shape[0] * 2.0 ** -52 * s + 2.0 ** -23 * (val.max() if val.size else 0.)
+
     # -- the three launch sequences
     def forward_model(self, mode, path, kind, EI, phiI, B, phiO, EX):
         """P [NT, L] of TrainStates.forward (L = 10; 1 for a 4-index B with kind 2, the per-label variant) and its bound.
@@ -210,10 +271,11 @@ class Model:
         u_mfma = U32 if mode == "f32" else UBF
         return P, ((n_mfma + 4) * u_mfma + (n_epi + mO + 15) * U32) * Pa
 
-    def gradient_model(self, mode, kind, EI, phiI, phiO, EX, P, labels, per, Bndim, target=None, bf16_grad=True):
+    def gradient_model(self, mode, kind, EI, phiI, phiO, EX, P, labels, per, Bndim, target=None, bf16_grad=True, chain=None):
         """G in the shape of B (TrainStates.gradient) and its bound.  P: what the device's forward pass returned for the same B
         ([NT, L]); per: images per slab (bgemm_cut); target: the per-label variant's label; bf16_grad False: k_bgemm on the fp32 pipe
-        in a bf16 mode."""
+        in a bf16 mode; chain: the length of the longest fp32 accumulation chain where it is shorter than min(per, NT) -- the largest
+        number of images of ONE slab whose product is not zero (adding an exact zero does not round, so the bound stays a worst case)."""
         EI, phiI, phiO, EX = self.f32(EI), self.f32(phiI), self.f32(phiO), self.f32(EX)
         P = np.asarray(P, dtype=np.float64).reshape(EI.shape[0], -1)
         labels = np.asarray(labels)
@@ -230,13 +292,17 @@ class Model:
         else:
             Y = self.f32(self.zprime(EX, dP)[:, :, None] * phiO[:, None, :])[:, None]       # [n, 1, q, t]
         L, mO = Y.shape[1], Y.shape[2]
-        n = self.nimg(NT)
+        idx = self.images(NT)
+        X, Y = X[idx], Y[idx].reshape(len(idx), L * 2 * mO)
+        live = np.any(X != 0, axis=1) & np.any(Y != 0, axis=1)
+        if not live.all():                                  # an image whose X or Y is zero adds exact zeros: left out, so that the sum over
+            X, Y = X[live], Y[live]                         # a set equals the sum over its live images bit for bit, whatever the BLAS does
         gm = mode if bf16_grad else "f32"
-        G, Ga, nt = self.dot(gm, X[:n].T, Y[:n].reshape(n, L * 2 * mO))
+        G, Ga, nt = self.dot(gm, X.T, Y)
         G = G.reshape(mI, 2, L, mO, 2).transpose(2, 0, 1, 3, 4)
         Ga = Ga.reshape(mI, 2, L, mO, 2).transpose(2, 0, 1, 3, 4)
         u_mfma = U32 if gm == "f32" else UBF
-        bound = (min(per, NT) * nt + 4) * u_mfma * Ga
+        bound = ((min(per, NT) if chain is None else chain) * nt + 4) * u_mfma * Ga
         return self.from_m_layout(kind, G, Bndim), self.from_m_layout(kind, bound, Bndim)
 
     def shift_model(self, mode, Eprev, phi, A, from_left):
@@ -285,6 +351,8 @@ _M = Model()
 forward_model = _M.forward_model
 gradient_model = _M.gradient_model
 shift_model = _M.shift_model
+cost_model = _M.cost_model
+pap_model = _M.pap_model
 
 
 # ---- the shapes of the gate (test_rp_model_host.py plants its defects at them, test_rp_model_gpu.py runs them) ---------------------
@@ -299,6 +367,28 @@ RAGGED_DIMS, RAGGED_NTS, RAGGED_BONDS = [1, 2, 61, 61, 61, 61, 2, 2, 2, 2, 1], (
 SINGLE_DIMS, SINGLE_NT = [1, 2, 17, 65, 40, 2, 1], 40
 STALE = dict(N=24, NT=300, m=24, bond=6, far=21)                   # the copy-cache case: a 24 x 24 bond, Label on the right environment
 NTPAD = 256
+# at real image counts, per kernel: one short chain with maxm = 40.  Bond 2: 2 x 40 and 3: 16 x 16, Label on the right environment; 4: 40 x 40 and
+# 5: 16 x 16, Label on B; 6: 17 x 40, 7: 2 x 16 and 8: 2 x 17, Label on the left environment.  Gradient tile classes: 80 (bond 4 in f32), 64 (bond 4
+# in the bf16 modes, bond 6), 32 (bonds 3, 5); the label dot has more than one row per wave of its sixteen-wave form from mO = 17 on
+SCALE_DIMS = [1, 2, 16, 40, 16, 40, 16, 17, 2, 2, 1]
+SCALE_LDOT_NT = 300                                                 # both fp32 label-dot forms, forced
+SCALE_THRESHOLD = {24320: 2, 24576: 1}                              # image count -> the form (ldot_cfg) the default dispatch takes: 190 / 192 blocks of 128
+SCALE_THRESHOLD_BONDS = {4: (40, 40), 6: (17, 40)}
+SCALE_NTS = (24576, 25000)                                          # the gradient with long slabs
+SCALE_GRAD_BONDS = {4: (40, 40), 5: (16, 16), 6: (17, 40)}
+
+
+def probe_set(cut, NT):
+    """the images that keep their features in the sparse gradient cases: the first and the last real image of every slab of `cut`
+    (bgemm_cut), the first image of one interior chunk of every slab, the last real image; and the largest number of them in one slab"""
+    per = cut["per"]
+    S = {NT - 1}
+    for k in range(cut["nsplit"]):
+        lo, hi = k * per, min((k + 1) * per, NT) - 1
+        if lo < NT:
+            S.update((lo, hi, lo + 32 * ((hi - lo + 1) // 64)))
+    S = np.array(sorted(S))
+    return S, int(np.bincount(S // per).max())
 
 
 def bonds_of(dims, single=False):

@@ -11,9 +11,13 @@ uniform repeat count R the base problem at lambda/R, cconv/R).  test_tiled_ident
 the CPU with the C oracle on both sides -- the GPU tests below then measure the kernels, not the harness.  The tolerances are the fp64
 figures of test_gpu_parity.py (TOL) and of the forced-kernel tests; the reference's own scatter under the identity is four orders below them.
 
-f32, bf16 and bf16x3 at scale are NOT covered: their gradient sums accumulate in fp32 and no measured bound exists at 60 000 images (at up to
-700 images tests/rp_model.py models their rounding and test_rp_model_gpu.py holds every kernel of theirs inside its derived bound); only
-f64_e32 (fp32 storage, fp64 accumulation: its rounding does not depend on the image count) gets a case at scale."""
+f32, bf16 and bf16x3 are covered PER KERNEL up to 25 000 images, not here: tests/rp_model.py models their rounding and test_rp_model_gpu.py
+holds every kernel of theirs inside its derived bound -- at up to 700 images every tile class, and at 24 320 / 24 576 / 25 000 images the
+default dispatch of the label dot on either side of its threshold (the streaming form k_labeldot<8, 2, NLT, float, float, float> included),
+cost / per-label costs / #correct / pAp as exact functions of the device's own outputs, and the gradient GEMM at its real slab cuts (12 slabs
+of 2 048 images, a short last slab, 79 slabs) on sparse probes and on dense data.  Still open in these modes at scale: the CG and whole bond
+updates, whose fp32 accumulation over the passes has no model, and image counts above 25 000 (the slab grows to 5 024 images at 60 000).  Only
+f64_e32 (fp32 storage, fp64 accumulation: its rounding does not depend on the image count) gets a case at scale in this file."""
 import os
 
 import numpy as np

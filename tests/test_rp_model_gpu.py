@@ -8,7 +8,15 @@ returned), so every comparison isolates one launch sequence.  test_rp_model_host
 after (truncation instead of rounding, a dropped cross term, a dropped reduction index or image chunk, a stale bf16 copy, a swapped
 epilogue index) lie at least 10 bounds away at every shape used here.
 
-Every check prints a line `rp_ratio ...` with the largest |device - model| / bound (profiles/rp_model_ratios.txt is that list)."""
+Every check prints a line `rp_ratio ...` with the largest |device - model| / bound (profiles/rp_model_ratios.txt is that list).
+
+The last part runs the same gate PER KERNEL at real image counts (up to 25 000) on one short chain with maxm = 40 (rp.SCALE_DIMS): both forms
+of the fp32 label dot, forced at 300 images and by the default dispatch on either side of its threshold of 192 blocks, with the scalar epilogue
+(cost, per-label costs, #correct, pAp) held to rp.cost_model / rp.pap_model on the device's own P -- lines `rp_gate ...`, |device - model| / gate;
+and the gradient GEMM at the slab cuts of 24 576 and 25 000 images, sparse (every image outside a probe set is zero, so that the chain of the
+bound is the probes of one slab and a lost or doubled chunk is thousands of bounds away) and dense (the bound with the full slab length)."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -31,15 +39,27 @@ def _ratio(dev, model, bound):
     return float(r.max())
 
 
+@functools.lru_cache(maxsize=None)
+def _problem(N, NT):
+    """(labels, features) of make_problem(N, NT, seed 5), made once per image count and left unchanged"""
+    _, labels, phi, _ = make_problem(N, NT, 2, 5, pixel_boost=200.0)
+    labels.flags.writeable = phi.flags.writeable = False
+    return labels, phi
+
+
 class Chain:
     """a TrainStates context on a chain with prescribed link dimensions, and what the model needs beside the device's environments"""
 
-    def __init__(self, dims, NT, dtype, case, single=None, options=()):
+    def __init__(self, dims, NT, dtype, case, single=None, options=(), keep=None):
+        """keep: the images that keep their features (every other image gets all-zero features at every site)"""
         from tnml_amd.fixedl import TrainStates
         self.dims, self.N, self.NT, self.dtype, self.case, self.single = dims, len(dims) - 1, NT, dtype, case, single
         self.NTp = -(-NT // rp.NTPAD) * rp.NTPAD
         if single is None:
-            _, self.labels, phi, _ = make_problem(self.N, NT, 2, 5, pixel_boost=200.0)
+            self.labels, phi = _problem(self.N, NT)
+            if keep is not None:
+                full, phi = phi, np.zeros_like(phi)
+                phi[keep] = full[keep]
             self.W = _mps_with_dims(dims, 11)
         else:
             from oracle import pyoracle
@@ -64,21 +84,53 @@ class Chain:
         assert r <= 1.0, "%s %s %s (%s) at bond %d (kind %d, %d x %d, %d images%s): |device - model| = %.3f x bound" % (
             self.case, self.dtype, what, kernel, b, kind, mI, mO, self.NT, extra, r)
 
-    def forward_check(self, b, B, once):
-        """forward at the bond that is set, with option bf16_once = once (None: not a bf16 mode); returns the device's P"""
+    def operands(self, b, B):
+        """(kind, (EI, phiI, phiO, EX)) of bond b from the device's own environments"""
         ts = self.ts
         EL = ts.env(b - 1) if b > 1 else self.one
         ER = ts.env(b + 2) if b + 2 <= self.N else self.one
         kind = rp.kind_of(B, EL, ER)
-        EI, phiI, phiO, EX = rp.plan(kind, EL, self.phi[:, b - 1], ER, self.phi[:, b])
+        return kind, rp.plan(kind, EL, self.phi[:, b - 1], ER, self.phi[:, b])
+
+    def goto(self, b):
+        """to bond b by shifts from the left (unchecked: the shift kernels have their cases above); returns a perturbed bond tensor"""
+        for bb in range(self.at, b):
+            self.ts.shiftE(bb, True)
+        self.at = b
+        self.ts.setBond(b)
+        B = self.ts.bond_tensor(b)
+        return B + 0.1 * np.abs(B).max() * self.rng.standard_normal(B.shape)
+
+    def forward_check(self, b, B, once, extra="", ops=None):
+        """forward at the bond that is set, with option bf16_once = once (None: not a bf16 mode); returns the device's P"""
+        ts = self.ts
+        kind, (EI, phiI, phiO, EX) = ops if ops is not None else self.operands(b, B)
         if once is not None:
             ts.set_option("bf16_once", once)
         path = "once" if (once == 1 and kind != 2) else "staged"
         P = ts.forward(B).reshape(self.NT, -1)
         Pm, bound = rp.forward_model(self.dtype, path, kind, EI, phiI, B, phiO, EX)
         kernel = "k_fgemm_bf16e" if path == "once" else ("k_fgemm/f32" if self.dtype == "f32" else "k_fgemm/bf16")
-        self.report("forward", kernel, b, kind, EI.shape[1], EX.shape[1], _ratio(P, Pm, bound))
+        self.report("forward", kernel, b, kind, EI.shape[1], EX.shape[1], _ratio(P, Pm, bound), extra)
         return P, kind, (EI, phiI, phiO, EX)
+
+    def epilogue_check(self, b, B, P, extra=""):
+        """the scalar epilogue of the label dot: quadcost(B) against rp.cost_model on P = forward(B) as the device returned it, and pAp(p)
+        against rp.pap_model on forward(p).  #correct exactly, the regulariser and lambda |p|^2 (fp64) to 1e-12, every cost inside its gate"""
+        ts, lam = self.ts, 1e-3
+        C, lc, cr, nc = ts.quadcost(B, lam)
+        cm = rp.cost_model(P, self.labels, self.single)
+        assert cr == pytest.approx(lam * float(np.sum(B * B)), rel=1e-12)
+        rl = float((np.abs(lc - cm["label_cost"]) / cm["gate"]).max())
+        rc = abs(C - (cm["cost"] + cr)) / (cm["cost_gate"] + 1e-12 * cr)
+        p = np.abs(B).max() * self.rng.standard_normal(B.shape)
+        s, gate = rp.pap_model(ts.forward(p))
+        reg = lam * float(np.sum(p * p))
+        rp_ = abs(ts.pAp(p, lam) - (s + reg)) / (gate + 1e-12 * reg)
+        print("rp_gate  %-9s %-6s bond %2d NT %5d%s  #correct %d (model %d)  cost %.2g per-label %.2g pAp %.2g" %
+              (self.case, self.dtype, b, self.NT, extra, nc, cm["ncorrect"], rc, rl, rp_))
+        assert nc == cm["ncorrect"], "%s %s bond %d%s: #correct %d, from the device's own P %d" % (self.case, self.dtype, b, extra, nc, cm["ncorrect"])
+        assert max(rc, rl, rp_) <= 1.0, "%s %s bond %d%s: cost %.3g, per-label cost %.3g, pAp %.3g x gate" % (self.case, self.dtype, b, extra, rc, rl, rp_)
 
     def check(self, b, expect=None, gradient=True):
         """forward (both settings of bf16_once) and gradient (both settings of bf16_grad) at bond b against the model"""
@@ -282,3 +334,121 @@ def test_bf16_copy_of_the_environment_follows_shifts_and_the_host_tier(dtype):
     assert tight[3] >= 1, "the input environment of bond %d was not on the host in between: this case no longer tests the copy cache under the host tier" % b
     for x, y in zip(free[:3], tight[:3]):
         assert np.array_equal(x, y)
+
+
+# ---- at real image counts, per kernel (rp.SCALE_DIMS: maxm = 40) ---------------------------------------------------------------------
+def _both_forms(c, b, B, once, ops):
+    """forward under ldot_cfg = 1 (k_labeldot<8, 2>: 128-image blocks, non-temporal loads) and 2 (<16, 1>: 64-image blocks), each against the
+    model and each twice with the same bits; {form: P}"""
+    out = {}
+    for form in (1, 2):
+        c.ts.set_option("ldot_cfg", form)
+        out[form] = c.forward_check(b, B, once, " ldot %d" % form, ops)[0]
+        assert np.array_equal(out[form], c.ts.forward(B).reshape(c.NT, -1)), "bond %d, label-dot form %d: forward twice, different bits" % (b, form)
+    return out
+
+
+@pytest.mark.parametrize("dtype,single", [(d, None) for d in rp.MODES] + [("f32", 3), ("bf16", 3)], ids=lambda v: "per-label" if v == 3 else (v or "ten-labels"))
+def test_both_forms_of_the_fp32_label_dot_and_their_scalar_epilogue(dtype, single):
+    """300 images, every bond of rp.SCALE_DIMS, ldot_cfg = 1 and 2 (NLT = 10; NLT = 1 in the per-label variant): P inside the bound of
+    forward_model, cost / per-label costs / #correct / pAp from the device's own P inside the gates of cost_model and pap_model.  The two forms
+    sum the label dot in different orders wherever a wave of either holds more than one row: their P must differ in some bit at every
+    bond with mO >= 17, or this case no longer tells them apart."""
+    bf = dtype in BF
+    with Chain(rp.SCALE_DIMS, rp.SCALE_LDOT_NT, dtype, "ldot", single=single) as c:
+        for b in range(1, c.N):
+            B = c.goto(b)
+            ops = c.operands(b, B)
+            for once in ((0, 1) if bf and ops[0] != 2 else (0,) if bf else (None,)):
+                P = _both_forms(c, b, B, once, ops)
+                for form in (1, 2):
+                    c.ts.set_option("ldot_cfg", form)
+                    c.epilogue_check(b, B, P[form], " ldot %d" % form)
+                if ops[1][3].shape[1] >= 17:
+                    assert not np.array_equal(P[1], P[2]), "bond %d (mO = %d): the 128-image and the 64-image form of the label dot return the same bits: " \
+                        "this case no longer tells them apart" % (b, ops[1][3].shape[1])
+            c.ts.set_option("ldot_cfg", 0)
+
+
+@pytest.mark.parametrize("NT", sorted(rp.SCALE_THRESHOLD))
+@pytest.mark.parametrize("dtype", rp.MODES)
+def test_default_label_dot_dispatch_on_either_side_of_its_threshold(dtype, NT):
+    """24 320 images (190 blocks of 128: the 64-image form) and 24 576 (192: the streaming form k_labeldot<8, 2, 10, float, float, float>), no
+    kernel-selection option set, at the 40 x 40 bond with the Label on B and the 17 x 40 bond with the Label on the left environment.  P is dense
+    and every image is held to forward_model's per-image bound; cost, per-label costs, #correct and pAp to cost_model / pap_model on that P.
+    The form is recognised by its bits: P under ldot_cfg = 0 equals P under the form the threshold predicts and differs from the other."""
+    bf = dtype in BF
+    want = rp.SCALE_THRESHOLD[NT]
+    with Chain(rp.SCALE_DIMS, NT, dtype, "dispatch") as c:
+        assert c.NTp == NT
+        for b, expect in rp.SCALE_THRESHOLD_BONDS.items():
+            B = c.goto(b)
+            ops = c.operands(b, B)
+            assert (ops[1][0].shape[1], ops[1][3].shape[1]) == expect
+            for once in ((0, 1) if bf and ops[0] != 2 else (0,) if bf else (None,)):
+                P = c.forward_check(b, B, once, " default", ops)[0]
+                c.epilogue_check(b, B, P, " default")
+            forced = {}
+            for form in (1, 2):
+                c.ts.set_option("ldot_cfg", form)
+                forced[form] = c.ts.forward(B).reshape(NT, -1)
+            c.ts.set_option("ldot_cfg", 0)
+            assert np.array_equal(P, forced[want]), "bond %d at %d images: the default label dot is not form %d" % (b, NT, want)
+            assert not np.array_equal(P, forced[3 - want]), "bond %d at %d images: both forms return the same bits" % (b, NT)
+
+
+def _grad_options(bf):
+    return (1, 0) if bf else (None,)
+
+
+@pytest.mark.parametrize("NT", rp.SCALE_NTS)
+@pytest.mark.parametrize("dtype", rp.MODES)
+def test_gradient_with_long_slabs_on_sparse_probes(dtype, NT):
+    """24 576 and 25 000 images: 12 slabs of 2 048 / 2 112 images (f32, 40 x 40 with the Label on B; the last of 1 856 at 25 000), 79 slabs of
+    320 with a last one of 128 (16 x 16 at 25 000), hundreds of 32-image chunks per workgroup.  Every image outside rp.probe_set of the bond's
+    cut has all-zero features: its environments and outputs are zero on the device (asserted) and it adds exact zeros to G, so the model is
+    gradient_model on the probes alone (test_rp_model_host.py: the same bits) and the chain of its bound is the probes of one slab --
+    a chunk lost, summed twice, or a lost slab lies thousands of bounds away.  Both settings of bf16_grad in the bf16 modes."""
+    bf = dtype in BF
+    cuts = {}
+    for b, (mI, mO) in rp.SCALE_GRAD_BONDS.items():
+        kind, L = {bb: (k, LL) for bb, k, _, _, LL in rp.bonds_of(rp.SCALE_DIMS)}[b]
+        cut = cuts[b] = rp.bgemm_cut(dtype, mI, mO, L, -(-NT // rp.NTPAD) * rp.NTPAD, max(rp.SCALE_DIMS))
+        S, chain = rp.probe_set(cut, NT)
+        rest = np.setdiff1d(np.arange(NT), S)
+        with Chain(rp.SCALE_DIMS, NT, dtype, "sparse", keep=S) as c:
+            B = c.goto(b)
+            k, (EI, phiI, phiO, EX) = c.operands(b, B)
+            assert k == kind and (EI.shape[1], EX.shape[1]) == (mI, mO)
+            if bf:
+                c.ts.set_option("bf16_once", 0)
+            P = c.ts.forward(B).reshape(NT, -1)
+            assert not EI[rest].any() and not EX[rest].any() and not P[rest].any(), "bond %d: an image without features has a non-zero environment or output" % b
+            assert EI[S].any(axis=1).all() and EX[S].reshape(len(S), -1).any(axis=1).all() and P[S].any(axis=1).all()
+            for grad in _grad_options(bf):
+                if grad is not None:
+                    c.ts.set_option("bf16_grad", grad)
+                G = c.ts.gradient(B)
+                Gm, bound = rp.gradient_model(dtype, kind, EI[S], phiI[S], phiO[S], EX[S], P[S], c.labels[S], cut["per"], B.ndim, bf16_grad=grad != 0, chain=chain)
+                c.report("gradient", "k_bgemm/bf16" if grad == 1 else "k_bgemm/f32", b, kind, mI, mO, _ratio(G, Gm, bound),
+                         " tile %d slabs %d x %d last %d probes %d chain %d" % (cut["tile"], cut["nsplit"], cut["per"], cut["last"], len(S), chain))
+    if dtype == "f32":                                                  # the cuts this case is about
+        assert cuts[4]["per"] >= 2048 and cuts[4]["tile"] == 80
+        if NT == 25000:
+            assert 0 < cuts[4]["last"] < cuts[4]["per"] and cuts[5]["nsplit"] >= 79 and cuts[5]["last"] < cuts[5]["per"]
+    else:
+        assert cuts[4]["per"] >= 1664 and cuts[4]["last"] < cuts[4]["per"] and cuts[4]["tile"] == 64
+    assert cuts[5]["tile"] == 32 and cuts[6]["tile"] == 64
+
+
+@pytest.mark.parametrize("dtype", rp.MODES)
+def test_gradient_with_long_slabs_dense(dtype):
+    """the same bonds at 24 576 images with ordinary features against gradient_model with the full slab length (up to 2 048 images summed
+    in fp32 by one workgroup): the derived bound, ratio <= 1 -- the measured figure of these modes at a real image count.  On an MI355X
+    the largest ratio at per = 2 048 is quoted in DESIGN.md (tolerance study) from profiles/rp_model_ratios.txt."""
+    with Chain(rp.SCALE_DIMS, rp.SCALE_NTS[0], dtype, "dense") as c:
+        for b, expect in rp.SCALE_GRAD_BONDS.items():
+            c.goto(b)
+            kind, cut = c.check(b, expect)
+            if b == 4:
+                assert kind == 2 and cut["per"] >= (2048 if dtype == "f32" else 1664), cut

@@ -4,7 +4,11 @@
 2. with the rounding helpers replaced by the identity the three models equal the fp64 oracle to 1e-12: their index maps are the oracle's;
 3. the gate has teeth: at every shape test_rp_model_gpu.py runs, each planted defect moves the model's result by at least 10 x bound
    somewhere.  The inputs of part 3 are made for that: positive operands (non-cancelling sums) whose bf16 rounding error has one sign
-   (x = c (1 +- 3 * 2^-11) with c a bf16 number), because a worst-case bound grows with n and a sum of random-sign errors with sqrt(n)."""
+   (x = c (1 +- 3 * 2^-11) with c a bf16 number), because a worst-case bound grows with n and a sum of random-sign errors with sqrt(n);
+4. the scalar epilogue of the fp32 label dot (cost_model, pap_model; with exact operands they equal the oracle's quadcost in part 2): a dropped
+   image, an image under the wrong label, a padded image that counts and the last maximum on a tie each miss the gate;
+5. the gradient at the slab cuts of 24 576 / 25 000 images on sparse probes: the whole set and its probes give the same bits, and a lost or
+   doubled chunk and a lost slab are thousands of the short-chain bounds away."""
 import numpy as np
 import pytest
 
@@ -69,6 +73,17 @@ def test_slab_cut_of_the_issue_shapes():
     assert rp.bgemm_cut("f32", 80, 40, 1, 256, 120)["tile"] == 80 and rp.bgemm_cut("bf16", 80, 40, 1, 256, 120)["tile"] == 80
     assert rp.bgemm_cut("f32", 120, 120, NL, 256, 120)["tile"] == 80 and rp.bgemm_cut("bf16x3", 120, 120, NL, 256, 120)["tile"] == 64
     assert rp.bgemm_cut("f32", 33, 17, 1, 256, 33)["tile"] == 64 and rp.bgemm_cut("f32", 9, 5, 1, 256, 80)["tile"] == 32
+    # at real image counts with maxm = 40 (test_rp_model_gpu.py, the long-slab cases): (tile, slabs, images per slab, images of the last slab)
+    for (mode, NTp, m), want in {("f32", 24576, 40): (80, 12, 2048, 2048), ("f32", 25088, 40): (80, 12, 2112, 1856), ("f32", 25088, 16): (32, 79, 320, 128),
+                                 ("bf16", 24576, 40): (64, 15, 1664, 1280), ("bf16x3", 24576, 40): (64, 15, 1664, 1280)}.items():
+        c = rp.bgemm_cut(mode, m, m, NL, NTp, 40)
+        assert (c["tile"], c["nsplit"], c["per"], c["last"]) == want, (mode, NTp, m, c)
+    dims = {b: (mI, mO) for b, _, mI, mO, _ in rp.bonds_of(rp.SCALE_DIMS)}
+    kinds = {b: kind for b, kind, _, _, _ in rp.bonds_of(rp.SCALE_DIMS)}
+    assert max(rp.SCALE_DIMS) == 40 and all(dims[b] == v for b, v in {**rp.SCALE_GRAD_BONDS, **rp.SCALE_THRESHOLD_BONDS}.items())
+    assert (kinds[3], kinds[4], kinds[5], kinds[6]) == (0, 2, 2, 1)
+    assert all(NT % rp.NTPAD == 0 for NT in rp.SCALE_THRESHOLD)                                   # labeldot_streaming: NTp / 128 >= 192
+    assert {NT: (1 if NT // 128 >= 192 else 2) for NT in rp.SCALE_THRESHOLD} == rp.SCALE_THRESHOLD and sorted(NT // 128 for NT in rp.SCALE_THRESHOLD) == [190, 192]
 
 
 # ---- 2. exact operands equal the oracle -------------------------------------------------------------
@@ -103,13 +118,24 @@ def _exact_walk(o, phi, labels, N, single, target, capsys):
             eP1 = _relmax(P1, Po)
         G, _ = ex.gradient_model("f32", kind, EI, phiI, phiO, EX, Po, labels, 32, B.ndim, target=target)
         eG = _relmax(G, o.gradient(B))
+        lam = 1e-3                                                     # the scalar epilogue: cost_model / pap_model on the oracle's own outputs
+        cm, q = ex.cost_model(Po, labels, target), o.quadcost(B, lam)
+        reg = lam * float(np.sum(B * B))
+        eC = abs(cm["cost"] + reg - q[0]) / q[0]
+        assert (q[1] if single else q[2]) == pytest.approx(reg, rel=1e-12)
+        if not single:
+            assert cm["ncorrect"] == q[3], b
+            eC = max(eC, _relmax(cm["label_cost"], q[1]))
+        p = rng.standard_normal(B.shape)
+        Pp = o.forward(p)
+        eC = max(eC, abs(ex.pap_model(Pp)[0] / float(np.sum(Pp * Pp)) - 1.0))
         o.shiftE(b, True)
         E, _ = ex.shift_model("f32", o.env(b - 1) if b > 1 else None, phi[:, b - 1], o.get_site(b), True)
         eE = _relmax(E, o.env(b))
         with capsys.disabled():
-            print("\n  exact-operand model vs oracle%s, bond %d (kind %d, %s): P %.1e (converted-once path %.1e)  G %.1e  shifted E %.1e"
-                  % (" (per-label)" if single else "", b, kind, "x".join(map(str, B.shape)), eP, eP1, eG, eE), end="")
-        worst = max(worst, eP, eP1, eG, eE)
+            print("\n  exact-operand model vs oracle%s, bond %d (kind %d, %s): P %.1e (converted-once path %.1e)  G %.1e  shifted E %.1e  cost, pAp %.1e"
+                  % (" (per-label)" if single else "", b, kind, "x".join(map(str, B.shape)), eP, eP1, eG, eE, eC), end="")
+        worst = max(worst, eP, eP1, eG, eE, eC)
     return worst
 
 
@@ -276,3 +302,135 @@ def test_a_dropped_reduction_index_in_the_shift_is_at_least_ten_bounds_away(m_in
     with capsys.disabled():
         print("\n  shift %d -> %d (Label %s): last reduction index dropped %.3g x bound" % (m_in, m_out, ("nowhere", "on the site", "on the environment")[lab], f), end="")
     assert f >= 10.
+
+
+# ---- 4. the scalar epilogue of the fp32 label dot -----------------------------------------------------
+class DropOneImage(rp.Model):
+    def __init__(self, n):
+        self.n = n
+
+    def cost_images(self, NT):
+        return np.delete(np.arange(NT), self.n)
+
+
+class WrongBucket(rp.Model):
+    def __init__(self, n):
+        self.n = n
+
+    def bucket(self, labels):
+        out = np.array(labels)
+        out[self.n] = (out[self.n] + 1) % NL
+        return out
+
+
+class LastMaximum(rp.Model):
+    def argmax(self, a):
+        return a.shape[1] - 1 - np.argmax(a[:, ::-1], axis=1)
+
+
+def _cost_miss(bad, good):
+    """(largest |defect - model| / gate over the cost and the per-label costs, difference of #correct)"""
+    r = abs(bad["cost"] - good["cost"]) / good["cost_gate"]
+    r = max(r, float((np.abs(bad["label_cost"] - good["label_cost"]) / good["gate"]).max()))
+    return r, bad["ncorrect"] - good["ncorrect"]
+
+
+@pytest.mark.parametrize("target", [None, 3], ids=["ten-labels", "per-label"])
+@pytest.mark.parametrize("NT", [rp.SCALE_LDOT_NT] + sorted(rp.SCALE_THRESHOLD))
+def test_every_planted_defect_of_the_cost_epilogue_misses_its_gate_ten_times(NT, target, capsys):
+    """cost_model / pap_model at the image counts of the GPU cases, on outputs of the size the kernels produce: one image dropped, one image
+    summed under the wrong label, a padded image that counts (as label 0 with outputs 0: one unit of cost for the ten labels, a 'correct'
+    image in the per-label variant), the LAST maximum on a planted tie of |P|.  The cost defects move a gated figure by at least 10 gates;
+    the two that move #correct move it by one, and its gate is equality."""
+    rng = np.random.default_rng(NT)
+    L = NL if target is None else 1
+    labels = rng.integers(0, NL, NT)
+    P = rp.to_f32(0.3 * rng.standard_normal((NT, L)) + (labels[:, None] == (np.arange(L)[None, :] if target is None else target)))
+    n = NT // 3
+    if target is None:                                               # the tie: the image's own label and a later one share the largest |P|
+        a = int(labels[n]) if labels[n] < NL - 1 else 0
+        labels[n] = a
+        P[n] = rp.to_f32(0.1 * rng.uniform(-1, 1, L))
+        P[n, a], P[n, NL - 1] = 0.75, -0.75
+    good = rp.cost_model(P, labels, target)
+    res = {"one image dropped": _cost_miss(DropOneImage(n).cost_model(P, labels, target), good),
+           "one image under the wrong label": _cost_miss(WrongBucket(n).cost_model(P, labels, target), good),
+           "a padded image counted": _cost_miss(rp.cost_model(np.vstack([P, np.zeros((1, L))]), np.append(labels, 0), target), good)}
+    assert res["one image dropped"][0] >= 10. and res["one image under the wrong label"][0] >= 10.
+    assert res["a padded image counted"][1] == 1 and (target is not None or res["a padded image counted"][0] >= 10.)
+    if target is None:
+        res["the last maximum on a tie"] = _cost_miss(LastMaximum().cost_model(P, labels, target), good)
+        assert res["the last maximum on a tie"] == (0., -1)
+    s, gate = rp.pap_model(P)
+    res["pAp: one image dropped"] = (abs(DropOneImage(n).pap_model(P)[0] - s) / gate, 0)
+    assert res["pAp: one image dropped"][0] >= 10.
+    assert gate < 1e-6 * s and np.all(good["gate"] < 1e-6 * good["label_cost"])              # the gates themselves: far below the f32 tolerances
+    with capsys.disabled():
+        print("\n  %5d images, %s: " % (NT, "ten labels" if target is None else "per-label") +
+              "; ".join("%s %.3g gates, #correct %+d" % ((k,) + v) for k, v in res.items()), end="")
+
+
+# ---- 5. the gradient with long slabs: sparse probes ----------------------------------------------------
+class Images(rp.Model):
+    """the gradient over the images `idx` (indices into the WHOLE set; repeats allowed) of arguments that hold the rows `rows` of it"""
+
+    def __init__(self, idx, rows):
+        self.idx, self.rows = np.asarray(idx), np.asarray(rows)
+
+    def images(self, NT):
+        i = self.idx[np.isin(self.idx, self.rows)]                   # every other image is zero and adds nothing
+        return np.searchsorted(self.rows, i)
+
+
+def _sparse_cases():
+    """(name, mode, NT, bond, kind, mI, mO, L) of the sparse GPU cases"""
+    out = []
+    for NT in rp.SCALE_NTS:
+        for b, kind, mI, mO, L in rp.bonds_of(rp.SCALE_DIMS):
+            if b in rp.SCALE_GRAD_BONDS:
+                out += [("%s-%d-b%d" % (mode, NT, b), mode, NT, b, kind, mI, mO, L) for mode in rp.MODES]
+    return out
+
+
+@pytest.mark.parametrize("name,mode,NT,b,kind,mI,mO,L", _sparse_cases(), ids=[c[0] for c in _sparse_cases()])
+def test_sparse_probes_identity_and_planted_slab_defects(name, mode, NT, b, kind, mI, mO, L, capsys):
+    """A set in which every image outside the probe set S (rp.probe_set of the bond's slab cut) has all-zero environments: gradient_model
+    on the whole set equals gradient_model on the rows of S BIT FOR BIT (bonds 4 and 5: kind 2, bond 6: kind 1; kind 0 with the roles of
+    bond 6 exchanged), and the bound with the chain length of S is the whole-set bound times (chain nt + 4) / (per nt + 4).  Planted at
+    that layout, each of these is at least 10 of the short bounds away: a 32-image chunk that holds a probe dropped, a slab boundary
+    moved by one chunk (the first chunk of the next slab summed twice / not at all), the last slab dropped."""
+    NTp = -(-NT // rp.NTPAD) * rp.NTPAD
+    cut = rp.bgemm_cut(mode, mI, mO, L, NTp, max(rp.SCALE_DIMS))
+    S, chain = rp.probe_set(cut, NT)
+    per, ns = cut["per"], cut["nsplit"]
+    last = (NT - 1) // per                                           # the last slab that holds a real image
+    assert chain <= 4 and len(S) >= 2 * (last + 1) and {0, NT - 1, per - 1, per, last * per} <= set(S)
+    lines = []
+    for kd in ((kind,) if kind == 2 else (0, 1)):
+        d = _teeth_inputs(kd, mI, mO, L, len(S), +1 if mode == "bf16x3" else -1, 11)
+        whole = {k: np.zeros((NT,) + d[k].shape[1:]) for k in ("EI", "EX", "P")}
+        for k in whole:
+            whole[k][S] = d[k]
+        labels = np.random.default_rng(5).integers(0, NL, NT)
+        phiI, phiO = (np.stack([np.ones(NT), np.linspace(0.3, 1.0, NT)], axis=1) for _ in range(2))
+        args = lambda rows: (mode, kd, whole["EI"][rows], phiI[rows], phiO[rows], whole["EX"][rows], whole["P"][rows], labels[rows], per, d["B"].ndim)
+        Gw, bw = rp.gradient_model(*args(slice(None)))
+        Gs, bs = rp.gradient_model(*args(S), chain=chain)
+        assert np.array_equal(Gw, Gs), "the whole set and its probes differ"
+        nt = 3 if mode == "bf16x3" else 1
+        np.testing.assert_allclose(bs * (per * nt + 4), bw * (chain * nt + 4), rtol=1e-14)
+        chunk = lambda c: np.arange(32 * c, min(32 * c + 32, NT))
+        k = ns // 2                                                  # the slab boundary k per: its first chunk holds the probe k per
+        keep = np.arange(NT)
+        res = {"the chunk of probe %d dropped" % S[len(S) // 2]: np.setdiff1d(keep, chunk(S[len(S) // 2] // 32)),
+               "boundary %d one chunk late: a chunk twice" % k: np.concatenate([keep, chunk(k * per // 32)]),
+               "boundary %d one chunk late: a chunk not at all" % k: np.setdiff1d(keep, chunk(k * per // 32)),
+               "the last slab dropped": keep[keep < last * per]}
+        for what, idx in res.items():
+            f = _factor(Images(idx, S).gradient_model(*args(S), chain=chain)[0], Gs, bs)
+            assert f >= 10., "%s kind %d: '%s' moves the model by only %.3g x bound" % (name, kd, what, f)
+            res[what] = f
+        lines.append("  %-16s kind %d %2d slabs x %4d (last %4d), %3d probes, chain %d, bound %.0f x tighter: " % (name, kd, ns, per, cut["last"], len(S), chain, (per * nt + 4) / (chain * nt + 4))
+                     + "; ".join("%s %.3g" % kv for kv in res.items()))
+    with capsys.disabled():
+        print("\n" + "\n".join(lines), end="")
