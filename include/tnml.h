@@ -384,6 +384,41 @@ int tnml_evaluate_u8 (tnml_ctx* ctx, int64_t n, const uint8_t* pixels, const int
 int tnml_evaluate_phi(tnml_ctx* ctx, int64_t n, const double* phi, const int32_t* labels,
                       tnml_eval_report* rep, double* weights, int32_t* pred);
 
+/* ---- streamed site responses: every site's effect on an image's output ---------------------------------------
+ * The output of the network is linear in every site's feature vector.  For image n and label l = which[n]
+ *     resp[n][j][s] = the contraction of W with label index l and the features of image n on every site but j, site j getting e_s,
+ * so that  W_l(x_n with site j's feature replaced by psi) = psi_0 resp[n][j][0] + psi_1 resp[n][j][1]  exactly, for any psi; with
+ * psi = phi(x_nj) that is W_l(x_n) itself, at every site.  Saliency and occlusion maps, pixel gradients (resp . dphi/dx) and
+ * single-pixel checks are host arithmetic on this array.
+ * Inputs as tnml_predict_*: bytes through the built-in expression or the input map in force (pixels is then [n][src_rows*src_cols]),
+ * or features; any context with a complete W, data-less ones included.  which[n] in 0..nl-1 names the label (a value outside is
+ * refused, the message names the image); NULL: the image's own prediction (first maximum of |W_l|).  In TNML_MODE_SINGLE there is one
+ * output (nl = 1, site 1 plays the centre) and which must be NULL or all zero.  weights and pred, either may be NULL, are bit for bit
+ * those of tnml_predict_* under predict_dtype = 0 on the same images.
+ * The host loop cuts n into chunks of option "response_chunk" images (default 1 024); a chunk is staged as tnml_predict_* stages it,
+ * ONE launch of k_response (kernels_response.hip) walks the chain inward, keeping every chain vector on a tape in device memory, and
+ * outward from the Label site, and the result is copied back: about two chain passes instead of the 2 N contractions per image that
+ * 2 N tnml_predict_phi calls on modified images take.  fp64 only: under predict_dtype = 1 the call is refused with a message that
+ * names predict_dtype.  resp is summed in a fixed order (the kernel's header states it), without atomics: an image's values do not
+ * depend on n, on the chunk, on the tile width ("predict_tile" is honoured) or on the tile it lands in, and repeats are bit-identical.
+ * Reads W only and enters no collective, like tnml_predict_*, and is refused as tnml_predict_* is, in the same words: on a context
+ * attached as a held-out set, while a bond update is in flight, when W is incomplete and when W has a bond dimension above 512.
+ * n = 0 succeeds and does nothing.  Chains of N = 2 and N = 3 sites do not reach these calls: tnml_create refuses N < 4 with a
+ * message (N = 4, with one site left of the Label site, is the shortest chain served).
+ * Workspace: its own (the predict workspace keeps its bytes), allocated by the first call, counted by tnml_device_bytes, re-made when
+ * response_chunk changes, released by tnml_set_input_map and freed by tnml_destroy.  With C = response_chunk rounded up to 64 and
+ * B = 32 + the sum over the N - 1 inner bonds of W as it is now of ru16(bond) + ru16(ml) + ru16(mr) of the Label site (site 1 in
+ * TNML_MODE_SINGLE):
+ *             16 N + 8 nl C + 8 C + 4 (N + 4) + 32 N C    bytes (site table, weights, pred and which, tape regions, the result as the
+ *                                                         kernel leaves it [N][2][C] and as the caller gets it [C][N][2])
+ *           + 8 B C                                       bytes of tape (grown when W has grown; 0.8 GB at N = 784, m = 120, C = 1 024)
+ *           + 2 N C  /  S C + 2 N C + 16 ncodes  /  32 N C   bytes of staging from the first call of that input form on, as predict's. */
+#define TNML_RESPONSE_CHUNK_DEFAULT 1024   /* option "response_chunk" */
+int tnml_response_u8 (tnml_ctx* ctx, int64_t n, const uint8_t* pixels, const int32_t* which /*[n] or NULL*/,
+                      double* resp /*[n][N][2]*/, double* weights /*[n][nl] or NULL*/, int32_t* pred /*[n] or NULL*/);
+int tnml_response_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/, const int32_t* which,
+                      double* resp, double* weights, int32_t* pred);
+
 /* ---- held-out evaluation during training ----------------------------------------------------------
  * A held-out set is an ordinary context created for the held-out images (one rank: nranks = 1, its own shard of the set in
  * a multi-rank run).  Once attached to a training context, every bond update of `train` also moves the two site tensors it
@@ -490,6 +525,7 @@ int tnml_synchronize(tnml_ctx* ctx);
                       1 (TNML_PREDICT_F32) the fp32 chain kernel on an fp32 copy of W made per call, bonds up to 1 024; any other value is refused
    Memory and transport:
      "predict_chunk"  images per trip of the host loop of tnml_predict_* = per launch of the chain kernel (1..2^20, default 8192); sizes its workspace
+     "response_chunk" images per trip of the host loop of tnml_response_* = per launch of k_response (1..2^20, default 1024); sizes its workspace
      "env_budget_mb"  cap on the environment slabs held on the device, the rest spills to host memory (0: none)
      "env_async"      the host tier's copies beside the compute stream (default 1)
      "comm_timeout_s" how long a rank of an in-process or one-shot communicator waits for its peers (>= 1, default 120)

@@ -186,6 +186,22 @@ static int evaluate_workspace(tnml_ctx* c) {
     if (rc) predict_release(c);
     return rc;
 }
+// One chunk's way from the caller's arrays into the staging buffers of a chunk loop (tnml_predict_* / tnml_evaluate_*: pk_*;
+// tnml_response_*: rs_*): copy in, then the input map's block sums or one transposing pre-kernel; images off .. off + cnt - 1
+struct ChunkStage { uint8_t* mraw; uint16_t* codes; uint8_t *raw8, *x8; double* rawphi; int cap; };
+template <typename E>
+static int stage_chunk(tnml_ctx* c, const ChunkStage& b, bool mapped, const StageGeom& sg, const uint8_t* pixels, const double* phi, int64_t off, int cnt, E* xphi) {
+    const bool bytes_form = pixels != nullptr;
+    const size_t per_img = mapped ? (size_t)sg.S : (size_t)c->N * (bytes_form ? 1 : 2 * sizeof(double));
+    if (mapped) {
+        HIPCK(c, hipMemcpyAsync(b.mraw, pixels + (size_t)off * per_img, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+        ProfScope ps(c, KC_PACK);
+        return launch_stage_codes(c, b.mraw, sg, cnt, b.cap, b.codes);
+    }
+    if (bytes_form) HIPCK(c, hipMemcpyAsync(b.raw8, pixels + (size_t)off * c->N, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+    else            HIPCK(c, hipMemcpyAsync(b.rawphi, phi + (size_t)off * c->N * 2, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+    return launch_chain_stage<E>(c, bytes_form ? b.raw8 : nullptr, bytes_form ? nullptr : b.rawphi, c->N, cnt, b.cap, b.x8, xphi);
+}
 // the chunk loop of predict_impl in the element type E of option predict_dtype: per chunk stage (map, bytes or phi), ONE chain launch, copy back;
 // labels (tnml_evaluate_*): the chunk's labels are staged with its images and ONE k_eval_tally launch behind the chain adds its tallies to pk_acc
 template <typename E>
@@ -194,7 +210,7 @@ static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t
     const bool bytes_form = pixels != nullptr;
     const bool mapped = bytes_form && c->im_set;                // the input map: S bytes per image -> block sums -> table look-ups inside the chain kernel
     const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
-    const size_t per_img = mapped ? (size_t)sg.S : (size_t)c->N * (bytes_form ? 1 : 2 * sizeof(double));
+    const ChunkStage stage{c->pk_mraw, c->pk_codes, c->pk_raw8, c->pk_x8, c->pk_rawphi, c->pk_cap};
     const int nl = c->nl();
     ChainArgs<E> a;
     a.N = c->N; a.cs = c->single() ? 1 : c->c0; a.nl = nl; a.single = c->single() ? 1 : 0;       // the centre tnml_classify takes
@@ -213,14 +229,7 @@ static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t
     else a.phiT = xphi;
     for (int64_t off = 0; off < n; off += c->predict_chunk) {
         a.cnt = (int)std::min<int64_t>(c->predict_chunk, n - off);
-        if (mapped) {
-            HIPCK(c, hipMemcpyAsync(c->pk_mraw, pixels + (size_t)off * per_img, per_img * a.cnt, hipMemcpyHostToDevice, c->stream));
-            { ProfScope ps(c, KC_PACK); TCK(launch_stage_codes(c, c->pk_mraw, sg, a.cnt, c->pk_cap, c->pk_codes)); }
-        } else {
-            if (bytes_form) HIPCK(c, hipMemcpyAsync(c->pk_raw8, pixels + (size_t)off * c->N, per_img * a.cnt, hipMemcpyHostToDevice, c->stream));
-            else            HIPCK(c, hipMemcpyAsync(c->pk_rawphi, phi + (size_t)off * c->N * 2, per_img * a.cnt, hipMemcpyHostToDevice, c->stream));
-            TCK(launch_chain_stage<E>(c, bytes_form ? c->pk_raw8 : nullptr, bytes_form ? nullptr : c->pk_rawphi, c->N, a.cnt, c->pk_cap, c->pk_x8, xphi));
-        }
+        TCK(stage_chunk<E>(c, stage, mapped, sg, pixels, phi, off, a.cnt, xphi));
         if (labels) HIPCK(c, hipMemcpyAsync(c->pk_lab, labels + off, sizeof(int32_t) * (size_t)a.cnt, hipMemcpyHostToDevice, c->stream));
         TCK(launch_chain<E>(c, a, maxbond, chain_tile<E>(c, maxbond, a.cnt), park, park_elems));
         if (labels) TCK(launch_eval_tally(c, c->pk_w, c->pk_pred, c->pk_lab, a.cnt, nl, a.single, c->target(), c->pk_acc));
@@ -304,4 +313,131 @@ int tnml_evaluate_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const int32_
 int tnml_evaluate_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* labels, tnml_eval_report* rep, double* weights, int32_t* pred) {
     if (n > 0 && !phi) return tnml_fail(c, "tnml_evaluate_phi: null argument");
     return predict_impl(c, "tnml_evaluate_phi", n, nullptr, phi, weights, pred, true, labels, rep);
+}
+
+// ---- streamed site responses (kernels_response.hip): every site's effect on an image's output ---------------------
+// The chunk loop of tnml_predict_* with option response_chunk: a chunk is staged as predict stages it, ONE k_response launch walks the
+// chain inward and outward, the result [N][2][C] is turned into [C][N][2] on the device and copied back; one synchronisation per chunk.
+// Reads W only, like tnml_predict_*.  The workspace is its own (tnml.h has its size): the predict workspace keeps its bytes.
+void response_release(tnml_ctx* c) {
+    void** slots[] = {(void**)&c->rs_tab, (void**)&c->rs_w, (void**)&c->rs_pred, (void**)&c->rs_which, (void**)&c->rs_rowoff, (void**)&c->rs_out, (void**)&c->rs_outT, (void**)&c->rs_tape,
+                      (void**)&c->rs_raw8, (void**)&c->rs_x8, (void**)&c->rs_rawphi, (void**)&c->rs_xphi, (void**)&c->rs_mraw, (void**)&c->rs_codes, (void**)&c->rs_mtab};
+    for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    c->bytes -= c->rs_bytes;
+    c->rs_bytes = 0; c->rs_cap = 0; c->rs_tape_rows = 0;
+}
+static int response_alloc(tnml_ctx* c, void** p, size_t bytes) {
+    TCK(dalloc(c, p, bytes));
+    c->rs_bytes += (int64_t)bytes;
+    return 0;
+}
+// rows: the rows of a workgroup's tape slice that W asks for now
+static int response_workspace(tnml_ctx* c, const char* who, bool bytes_form, size_t rows) {
+    const int cap = (c->response_chunk + 63) / 64 * 64;
+    int rc = 0;
+    if (c->rs_cap != cap) {                               // first call, or option response_chunk has changed since
+        if (c->rs_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); response_release(c); }
+        rc = response_alloc(c, (void**)&c->rs_tab, (size_t)c->N * sizeof(ChainSite<double>));
+        if (!rc) rc = response_alloc(c, (void**)&c->rs_w, (size_t)cap * c->nl() * sizeof(double));
+        if (!rc) rc = response_alloc(c, (void**)&c->rs_pred, (size_t)cap * sizeof(int));
+        if (!rc) rc = response_alloc(c, (void**)&c->rs_which, (size_t)cap * sizeof(int));
+        if (!rc) rc = response_alloc(c, (void**)&c->rs_rowoff, (size_t)(c->N + 4) * sizeof(int));
+        if (!rc) rc = response_alloc(c, (void**)&c->rs_out, (size_t)2 * c->N * cap * sizeof(double));
+        if (!rc) rc = response_alloc(c, (void**)&c->rs_outT, (size_t)2 * c->N * cap * sizeof(double));
+        if (rc) { response_release(c); return rc; }
+        c->rs_cap = cap;
+    }
+    if (rows > c->rs_tape_rows) {                          // the tape follows the bonds W has: grown when W has grown
+        if (c->rs_tape) {
+            HIPCK(c, hipStreamSynchronize(c->stream));
+            (void)hipFree(c->rs_tape); c->rs_tape = nullptr;
+            const int64_t old = (int64_t)(c->rs_tape_rows * (size_t)cap * sizeof(double));
+            c->bytes -= old; c->rs_bytes -= old; c->rs_tape_rows = 0;
+        }
+        rc = response_alloc(c, (void**)&c->rs_tape, rows * (size_t)cap * sizeof(double));
+        if (rc) { response_release(c); return rc; }
+        c->rs_tape_rows = rows;
+    }
+    if (bytes_form && c->im_set) {
+        if (c->rs_codes) return 0;
+        const size_t S = (size_t)c->im.src_rows * c->im.src_cols, tabb = c->im_table.size() * sizeof(double);
+        rc = response_alloc(c, (void**)&c->rs_mraw, S * cap);
+        if (!rc) rc = response_alloc(c, (void**)&c->rs_codes, (size_t)cap * c->N * sizeof(uint16_t));
+        if (!rc) rc = response_alloc(c, (void**)&c->rs_mtab, tabb);
+        if (!rc && hipMemcpyAsync(c->rs_mtab, c->im_table.data(), tabb, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "%s: copy of the input map's table failed", who);
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "%s: hipStreamSynchronize failed", who);
+        if (rc) response_release(c);
+        return rc;
+    }
+    if (bytes_form && !c->rs_x8) { rc = response_alloc(c, (void**)&c->rs_raw8, (size_t)cap * c->N); if (!rc) rc = response_alloc(c, (void**)&c->rs_x8, (size_t)cap * c->N); }
+    if (!bytes_form && !c->rs_xphi) { rc = response_alloc(c, (void**)&c->rs_rawphi, (size_t)2 * cap * c->N * sizeof(double)); if (!rc) rc = response_alloc(c, (void**)&c->rs_xphi, (size_t)2 * cap * c->N * sizeof(double)); }
+    if (rc) response_release(c);
+    return rc;
+}
+static int response_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* which, double* resp, double* weights, int32_t* pred) {
+    if (!c) return tnml_fail(c, "%s: null argument", who);
+    if (n < 0) return tnml_fail(c, "%s: n = %lld, must be >= 0", who, (long long)n);
+    if (c->pend_count > 0) return tnml_fail(c, "%s: a bond update is in flight (tnml_bond_update_end first)", who);
+    TCK(ho_locked(c, who));
+    TCK(check_W(c));
+    int maxbond = 1;
+    for (int j = 1; j <= c->N; ++j) maxbond = std::max(maxbond, std::max(c->W[j].ml, c->W[j].mr));
+    if (maxbond > TNML_CHAIN_MAXM)
+        return tnml_fail(c, "%s: W has a bond of dimension %d, the chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, maxbond, TNML_CHAIN_MAXM);
+    if (c->predict_dtype != TNML_PREDICT_F64)
+        return tnml_fail(c, "%s: option predict_dtype = %d (fp32): site responses are computed in fp64 only (set predict_dtype = 0)", who, c->predict_dtype);
+    if (n == 0) return 0;
+    if ((!pixels && !phi) || !resp) return tnml_fail(c, "%s: null argument", who);
+    const int nl = c->nl();
+    if (which)
+        for (int64_t i = 0; i < n; ++i)
+            if (which[i] < 0 || which[i] >= nl) return tnml_fail(c, "%s: which = %d of image %lld out of range 0..%d", who, which[i], (long long)i, nl - 1);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const int N = c->N, cs = c->single() ? 1 : c->c0;
+    // tape regions: the vector on bond b = 0..N (dimension 1 at the two ends), then X and Y of the centre (kernels_response.hip)
+    std::vector<int> rowoff(N + 4);
+    int rows = 0;
+    auto ru16 = [](int m) { return (m + 15) / 16 * 16; };
+    for (int b = 0; b <= N; ++b) { rowoff[b] = rows; rows += ru16(b == 0 ? 1 : c->W[b].mr); }
+    rowoff[N + 1] = rows; rows += ru16(c->W[cs].ml);
+    rowoff[N + 2] = rows; rows += ru16(c->W[cs].mr);
+    rowoff[N + 3] = rows;
+    const bool bytes_form = pixels != nullptr;
+    TCK(response_workspace(c, who, bytes_form, (size_t)rows));
+    std::vector<ChainSite<double>> tab(N);
+    for (int j = 1; j <= N; ++j) tab[j - 1] = ChainSite<double>{c->W[j].a, c->W[j].ml, c->W[j].mr};
+    HIPCK(c, hipMemcpyAsync(c->rs_tab, tab.data(), sizeof(ChainSite<double>) * N, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(c->rs_rowoff, rowoff.data(), sizeof(int) * (N + 4), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));                  // (tab and rowoff leave scope with this call)
+    const bool mapped = bytes_form && c->im_set;
+    const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
+    const ChunkStage stage{c->rs_mraw, c->rs_codes, c->rs_raw8, c->rs_x8, c->rs_rawphi, c->rs_cap};
+    RespArgs a;
+    a.ch.sites = c->rs_tab; a.ch.N = N; a.ch.cs = cs; a.ch.nl = nl; a.ch.single = c->single() ? 1 : 0;
+    a.ch.ld = c->rs_cap; a.ch.wout = c->rs_w; a.ch.pred = c->rs_pred;
+    a.ch.xT = nullptr; a.ch.phiT = nullptr;
+    if (mapped) { a.ch.codeT = c->rs_codes; a.ch.table = c->rs_mtab; }
+    else if (bytes_form) a.ch.xT = c->rs_x8;
+    else a.ch.phiT = c->rs_xphi;
+    a.which = which ? c->rs_which : nullptr; a.rowoff = c->rs_rowoff; a.tape = c->rs_tape; a.resp = c->rs_out;
+    const size_t tape_elems = c->rs_tape_rows * (size_t)c->rs_cap;
+    for (int64_t off = 0; off < n; off += c->response_chunk) {
+        a.ch.cnt = (int)std::min<int64_t>(c->response_chunk, n - off);
+        TCK(stage_chunk<double>(c, stage, mapped, sg, pixels, phi, off, a.ch.cnt, c->rs_xphi));
+        if (which) HIPCK(c, hipMemcpyAsync(c->rs_which, which + off, sizeof(int32_t) * (size_t)a.ch.cnt, hipMemcpyHostToDevice, c->stream));
+        TCK(launch_response(c, a, maxbond, chain_tile<double>(c, maxbond, a.ch.cnt), rows, tape_elems, c->rs_outT));
+        HIPCK(c, hipMemcpyAsync(resp + (size_t)off * N * 2, c->rs_outT, sizeof(double) * (size_t)a.ch.cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
+        if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->rs_w, sizeof(double) * (size_t)a.ch.cnt * nl, hipMemcpyDeviceToHost, c->stream));
+        if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->rs_pred, sizeof(int32_t) * (size_t)a.ch.cnt, hipMemcpyDeviceToHost, c->stream));
+        SYNCK(c, c->stream);                                    // the staging buffers are reused by the next chunk
+    }
+    return 0;
+}
+int tnml_response_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const int32_t* which, double* resp, double* weights, int32_t* pred) {
+    if (n > 0 && !pixels) return tnml_fail(c, "tnml_response_u8: null argument");
+    return response_impl(c, "tnml_response_u8", n, pixels, nullptr, which, resp, weights, pred);
+}
+int tnml_response_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* which, double* resp, double* weights, int32_t* pred) {
+    if (n > 0 && !phi) return tnml_fail(c, "tnml_response_phi: null argument");
+    return response_impl(c, "tnml_response_phi", n, nullptr, phi, which, resp, weights, pred);
 }

@@ -33,11 +33,11 @@
 
 enum KClass {
     KC_FGEMM_FWD = 0, KC_FGEMM_SHIFT, KC_LABELDOT, KC_ZPRIME, KC_BGEMM, KC_SLABRED, KC_PACK, KC_VEC,
-    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_EVAL_TALLY, KC_COUNT
+    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_EVAL_TALLY, KC_SITE_RESP, KC_COUNT
 };
 static const char* const kclass_names[KC_COUNT] = {
     "fgemm_fwd", "fgemm_shift", "labeldot", "zprime", "bgemm", "slab_reduce", "pack", "cg_vec",
-    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain", "eval_tally"};
+    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain", "eval_tally", "site_resp"};
 
 // device accumulator block of tnml_evaluate_*: the part of tnml_eval_report that k_eval_tally (kernels_eval.hip) adds up
 struct EvalAcc {
@@ -321,6 +321,20 @@ struct tnml_ctx {
     // streamed evaluation (tnml_evaluate_u8 / tnml_evaluate_phi, kernels_eval.hip): allocated by the first such call, counted in `bytes` and pk_bytes, freed with the rest
     int* pk_lab = nullptr;           // [pk_cap] labels of a chunk
     EvalAcc* pk_acc = nullptr;       // the tallies of the call in progress (k_eval_tally adds a chunk, the host reads them once at the end)
+    // streamed site responses (tnml_response_u8 / tnml_response_phi, kernels_response.hip): a workspace of its own, allocated by the first
+    // call, counted in `bytes` and rs_bytes, re-made when option response_chunk changes, freed by tnml_destroy; the predict workspace is not touched
+    int response_chunk = TNML_RESPONSE_CHUNK_DEFAULT;      // option "response_chunk": images per launch of k_response
+    bool attr_response[2] = {};      // [input map]: the LDS attribute of those k_response instantiations is set
+    int rs_cap = 0; int64_t rs_bytes = 0;                  // response_chunk rounded up to 64 when the workspace was sized
+    ChainSite<double>* rs_tab = nullptr;                   // [N] per-site table
+    double* rs_w = nullptr; int* rs_pred = nullptr;        // [rs_cap][nl], [rs_cap]: weights and pred of a chunk
+    int* rs_which = nullptr;                               // [rs_cap] labels asked for
+    int* rs_rowoff = nullptr;                              // [N + 4] rows of the tape regions (kernels_response.hip)
+    double *rs_out = nullptr, *rs_outT = nullptr;          // the result of a chunk as the kernel leaves it [N][2][rs_cap] and as the caller gets it [rs_cap][N][2]
+    double* rs_tape = nullptr; size_t rs_tape_rows = 0;    // [rs_cap / T][rs_tape_rows][T]: every chain vector of every image; grown when W has grown
+    uint8_t *rs_raw8 = nullptr, *rs_x8 = nullptr;          // staging as the predict workspace has it, sized by rs_cap (first call of the input form)
+    double *rs_rawphi = nullptr, *rs_xphi = nullptr;
+    uint8_t* rs_mraw = nullptr; uint16_t* rs_codes = nullptr; double* rs_mtab = nullptr;   // under an input map (released by every tnml_set_input_map call, with the rest)
     // input map (tnml_set_input_map): geometry + host copy of the fp64 table; consulted by tnml_set_data_u8 / tnml_predict_u8 only
     bool im_set = false;
     tnml_input_map im = {};          // geometry (table = nullptr)
@@ -583,6 +597,16 @@ int launch_chain_pack32(tnml_ctx* c, const ChainSite<double>* src, const ChainSi
 template <typename E> int chain_tile(tnml_ctx* c, int maxbond, int cnt);
 template <typename E> int launch_chain(tnml_ctx* c, ChainArgs<E> a, int maxbond, int T, E* park_ws, size_t park_elems);
 
+// ---- kernels_response.hip: streamed site responses, two walks of the chain for a tile of images in one launch ----
+struct RespArgs {
+    ChainArgs<double> ch;              // sites, sources, ld, cnt, wout, pred as k_chain takes them (park and flag unused)
+    const int* which;                  // [cnt] label whose output is differentiated, or null: the image's own pred
+    const int* rowoff;                 // [N + 4] device: first row of the tape region of bond b = 0..N, of X, of Y; then the rows of a slice
+    double* tape;                      // [grid][rows][T]
+    double* resp;                      // [N][2][ld]
+};
+// rows: rowoff[N + 3] as the host knows it; tape_elems: doubles behind a.tape; outT [cnt][N][2] receives the transposed a.resp; class site_resp
+int launch_response(tnml_ctx* c, RespArgs a, int maxbond, int T, int rows, size_t tape_elems, double* outT);
 
 // ---- kernels_eval.hip: the tallies of streamed evaluation over the results of a chunk ----
 // w [cnt][nl], pred [cnt] (what k_chain left in pk_w / pk_pred), lab [cnt] in 0..9 (the host has checked them) -> acc += the chunk's

@@ -303,6 +303,32 @@ class TrainStates:
         rep = EvalReport(r)
         return (rep, (w, pred)) if want_weights else rep
 
+    def site_response(self, pixels=None, phi=None, which=None, want_weights=False):
+        """streamed site responses (tnml_response_u8 / tnml_response_phi) of images this context does not hold, in the input forms of
+        predict(): resp[n, N, 2], where resp[n, j, s] is the output of label which[n] for image n with the feature of site j + 1
+        replaced by the unit vector e_s, so that the output for any replacement psi is psi @ resp[n, j].  which None: every image's
+        own prediction.  With want_weights (resp, (weights[n, nl], pred[n])), both bit for bit those of predict() in fp64.  Reads W
+        only; fp64 only (refused under predict_dtype = 1)."""
+        x = self._streamed_input(pixels, phi, None)
+        n = int(x.shape[0])
+        resp = np.zeros((n, self.N, 2))
+        wh = wp_ = None
+        if which is not None:
+            wh = np.ascontiguousarray(which, dtype=np.int32)
+            if wh.shape != (n,):
+                raise ValueError("which must have shape [%d], got %s" % (n, wh.shape))
+            wp_ = wh.ctypes.data_as(C.POINTER(C.c_int32))
+        w = pred = wp = pp = None
+        if want_weights:
+            w = np.zeros((n, self.nl))
+            pred = np.zeros(n, dtype=np.int32)
+            wp, pp = _lib.dptr(w), pred.ctypes.data_as(C.POINTER(C.c_int32))
+        if pixels is not None:
+            self._ck(self._L.tnml_response_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), wp_, _lib.dptr(resp), wp, pp))
+        else:
+            self._ck(self._L.tnml_response_phi(self._h, n, _lib.dptr(x), wp_, _lib.dptr(resp), wp, pp))
+        return (resp, (w, pred)) if want_weights else resp
+
     # -- W
     def set_mps(self, W):
         for j, A in enumerate(W, start=1):

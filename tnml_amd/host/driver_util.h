@@ -152,6 +152,20 @@ inline bool predict_dtype_option(tnml_ctx* ctx, bool predict, const std::string&
     CK(ctx, tnml_set_option(ctx, "predict_dtype", value == "f32" ? TNML_PREDICT_F32 : TNML_PREDICT_F64));
     return value == "f32";
 }
+// the key `response` of fulltest: a [n][N][2] array of doubles as a NumPy .npy file (format 1.0, little-endian float64, C order)
+inline void write_npy_f64_3d(const std::string& path, const double* a, long n0, long n1, long n2) {
+    char dict[128];
+    std::snprintf(dict, sizeof dict, "{'descr': '<f8', 'fortran_order': False, 'shape': (%ld, %ld, %ld), }", n0, n1, n2);
+    std::string hdr(dict);
+    while ((10 + hdr.size() + 1) % 64) hdr += ' ';                              // magic, version and length are 10 bytes; the data start at a multiple of 64
+    hdr += '\n';
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) { std::printf("Couldn't write file '%s'\n", path.c_str()); std::exit(1); }
+    const unsigned char head[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char)(hdr.size() & 255), (unsigned char)(hdr.size() >> 8)};
+    const size_t cnt = (size_t)n0 * n1 * n2;
+    const bool ok = std::fwrite(head, 1, 10, f) == 10 && std::fwrite(hdr.data(), 1, hdr.size(), f) == hdr.size() && std::fwrite(a, sizeof(double), cnt, f) == cnt;
+    if (std::fclose(f) != 0 || !ok) { std::printf("Couldn't write file '%s'\n", path.c_str()); std::exit(1); }
+}
 // fullTest's result table (util.h:186-199) from the images and the misclassified images per label
 inline void print_fulltest_table(const int64_t counts[10], const int64_t nincorrect[10]) {
     long nte = 0, tninc = 0;

@@ -9,7 +9,11 @@
 // default no): a data-less context sized by W alone, the test set streamed through tnml_predict_u8 / tnml_predict_phi
 // in chunks of `predict_chunk` images (0: the library's default) and counted on the host, `predict_dtype` (f64 | f32, default f64)
 // choosing the chain kernel's arithmetic; `input_map` (yes | no, default no): the
-// images reach the device as the bytes of the idx file, the device does reduce(), the feature map and the transpose (tnml_set_input_map).
+// images reach the device as the bytes of the idx file, the device does reduce(), the feature map and the transpose (tnml_set_input_map);
+// `response` (a file name, default none): the site responses of the first `response_n` test images (default 100) for their predicted
+// label, through tnml_response_u8 / tnml_response_phi in the input form the run uses, written as a NumPy .npy file of float64
+// [n][N][2]; the table is not affected.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -38,6 +42,8 @@ int main(int argc, const char* argv[]) {
         const long predict_chunk = input.getInt("predict_chunk", 0);
         const std::string predict_dtype = input.getString("predict_dtype", "f64");
         const bool input_map = input.getYesNo("input_map", false);
+        const std::string response = input.getString("response", "");
+        const long response_n = input.getInt("response_n", 100);
         int dtype;
         if (!parse_dtype(precision, false, &dtype)) return 1;
 
@@ -77,6 +83,14 @@ int main(int argc, const char* argv[]) {
             else CK(ctx, tnml_set_data_phi(ctx, phi.data(), test.labels.data()));
         }
         upload_mps(ctx, psi);
+        if (!response.empty()) {                                                       // (before predict_dtype is set: site responses are fp64 only)
+            const long nr = std::max(0L, std::min<long>(response_n, totNtest));
+            std::printf("Device path: site responses (%s), %d images per chunk\n", bytes_in ? "tnml_response_u8" : "tnml_response_phi", TNML_RESPONSE_CHUNK_DEFAULT);
+            std::vector<double> resp((size_t)nr * N * 2);
+            if (bytes_in) CK(ctx, tnml_response_u8(ctx, nr, bytes, nullptr, resp.data(), nullptr, nullptr));
+            else CK(ctx, tnml_response_phi(ctx, nr, phi.data(), nullptr, resp.data(), nullptr, nullptr));
+            write_npy_f64_3d(response, resp.data(), nr, N, 2);
+        }
         const bool p32 = predict_dtype_option(ctx, predict, predict_dtype);
 
         std::printf("Running full test of %s\n", fname.c_str());                       // :97
