@@ -419,6 +419,46 @@ int tnml_response_u8 (tnml_ctx* ctx, int64_t n, const uint8_t* pixels, const int
 int tnml_response_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/, const int32_t* which,
                       double* resp, double* weights, int32_t* pred);
 
+/* ---- streamed site gradients: dC/dA of every site tensor, on images the context does not hold ----------------------
+ * For n images and coefficients c[n][l] = dC/dW_l(x_n) (nl = 10; nl = 1 in TNML_MODE_SINGLE, where site 1 plays the Label site)
+ *     G_j[a,s,r]   = sum_n sum_l c_nl dW_l(x_n)/dA_j[a,s,r]          (j not the Label site)
+ *     G_c[a,s,r,l] = sum_n       c_nl dW_l(x_n)/dA_c[a,s,r,l]        (the Label site),
+ * the gradient with respect to W of any function C of the outputs (a vector-Jacobian product).  Exactly one of coef and labels is
+ * non-NULL: coef [n][nl] gives c directly; labels [n] makes the call form c_nl = 2 (W_l(x_n) - y_nl) on the device from its own inward
+ * pass, with the targets of tnml_evaluate_* (y_nl = [l == label_n]; TNML_MODE_SINGLE: y_n = [label_n == target_label]), so that G is
+ * dC/dA of the cost tnml_evaluate_* reports on the same images.  Mini-batch gradient descent on data that does not fit on the card,
+ * or fine-tuning a trained W, is host arithmetic on this array and tnml_set_site.
+ * grad receives the sites concatenated in site order, each in the layout of tnml_get_site for W as it is now ([ml][2][mr], x nl on
+ * the Label site, first index fastest); tnml_site_gradient_size gives the element count and, when offsets is non-NULL, the N + 1
+ * starts (offsets[N] = elems).  grad is overwritten, not added to; it is copied back once, at the end of the call; weights and pred,
+ * either may be NULL, are bit for bit those of tnml_predict_* under predict_dtype = 0 and are copied back chunk by chunk.
+ * Inputs as tnml_response_*: bytes through the built-in expression or the input map in force, or features; any context with a complete
+ * W, data-less ones included.  Reads W only and enters no collective.
+ * The host loop cuts n into chunks of option "gradient_chunk" images (default 512).  Per chunk ONE launch of k_site_backward
+ * (kernels_sitegrad.hip) walks the chain inward as k_response does, keeping every chain vector on a tape, forms the coefficients at
+ * the Label site and walks outward, keeping every outward vector on a second tape; ONE launch of k_site_grad then adds, for every site,
+ * the outer products over the chunk's images with v_mfma_f64_16x16x4_f64.  The sum has a fixed order (the kernel file's header states
+ * it; no atomics): grad is bit-identical on repeats and independent of the tile width ("predict_tile" is honoured); its last bits
+ * may depend on gradient_chunk.
+ * Refused as tnml_response_* is, in the same words: on a context attached as a held-out set, while a bond update is in flight, when W
+ * is incomplete, when W has a bond dimension above 512, under predict_dtype = 1.  Also refused: both or neither of labels and coef, a
+ * label outside 0..9 and a coefficient that is not finite (the message names the image).  A refused call leaves grad untouched; n = 0
+ * succeeds and zeroes grad.
+ * Workspace: its own, allocated by the first call, counted by tnml_device_bytes, re-made when gradient_chunk changes, released by
+ * tnml_set_input_map and freed by tnml_destroy.  With C = gradient_chunk rounded up to 64, B = 32 + the sum over the N - 1 inner bonds
+ * of W as it is now of ru16(bond), and E = the elements of grad:
+ *             16 N + 16 nl C + 8 C + 4 (N + 2) + 8 (N + 1) + 4 (N + nl)   bytes (site table, weights and coefficients, pred and labels,
+ *                                                         tape regions, site starts, output blocks)
+ *           + 8 E                                         bytes, the gradient until it is copied back (grown when W has grown)
+ *           + 16 B C                                      bytes of the two tapes (grown when W has grown; 0.8 GB at N = 784, m = 120, C = 512)
+ *           + 2 N C  /  S C + 2 N C + 16 ncodes  /  32 N C   bytes of staging from the first call of that input form on, as predict's. */
+#define TNML_GRADIENT_CHUNK_DEFAULT 512    /* option "gradient_chunk" */
+int tnml_site_gradient_size(tnml_ctx* ctx, int64_t* elems, int64_t* offsets /*[N+1] or NULL*/);
+int tnml_site_gradient_u8 (tnml_ctx* ctx, int64_t n, const uint8_t* pixels, const int32_t* labels /*[n] or NULL*/, const double* coef /*[n][nl] or NULL*/,
+                           double* grad /*[elems]*/, double* weights /*[n][nl] or NULL*/, int32_t* pred /*[n] or NULL*/);
+int tnml_site_gradient_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/, const int32_t* labels, const double* coef,
+                           double* grad, double* weights, int32_t* pred);
+
 /* ---- held-out evaluation during training ----------------------------------------------------------
  * A held-out set is an ordinary context created for the held-out images (one rank: nranks = 1, its own shard of the set in
  * a multi-rank run).  Once attached to a training context, every bond update of `train` also moves the two site tensors it
@@ -526,6 +566,7 @@ int tnml_synchronize(tnml_ctx* ctx);
    Memory and transport:
      "predict_chunk"  images per trip of the host loop of tnml_predict_* = per launch of the chain kernel (1..2^20, default 8192); sizes its workspace
      "response_chunk" images per trip of the host loop of tnml_response_* = per launch of k_response (1..2^20, default 1024); sizes its workspace
+     "gradient_chunk" images per trip of the host loop of tnml_site_gradient_* = per launch of k_site_backward and k_site_grad (1..2^20, default 512); sizes its workspace
      "env_budget_mb"  cap on the environment slabs held on the device, the rest spills to host memory (0: none)
      "env_async"      the host tier's copies beside the compute stream (default 1)
      "comm_timeout_s" how long a rank of an in-process or one-shot communicator waits for its peers (>= 1, default 120)

@@ -1,0 +1,245 @@
+"""Site gradients restated in numpy (fp64): the yardstick of tests/test_sitegrad_gpu.py, itself proved by
+tests/test_sitegrad_model_host.py (finite differences of the cost of tests/eval_model.py on the oracle's weights, the Euler identity,
+the tie to tests/response_model.py).
+
+For n images and coefficients c[n, l] = dC/dW_l(x_n)
+
+    G_j[a, s, r]    = sum_n L_j[n, a] phi[n, j, s] Xr_j[n, r]         (j left of the Label site c)
+    G_j[a, s, r]    = sum_n Yl_j[n, a] phi[n, j, s] R_j[n, r]         (j right of it)
+    G_c[a, s, r, l] = sum_n c[n, l] L_c[n, a] phi[n, c, s] R_c[n, r]
+
+with explicit environments: L_j everything left of site j, R_j everything right of it (Label-free), Xr_j everything right of site j
+with the Label site's tensor contracted with c, Yl_j everything left of site j likewise.  Sites are 0-based here.  W is a list of N
+arrays [ml, 2, mr]; at most one of them, the Label site, is [ml, 2, mr, nl].  Without one (the per-label variant) there is a single
+output, site 0 plays the Label site and its gradient is [ml, 2, mr].
+
+The bound
+---------
+Every element of G is a sum of products of one factor per site, the features and a coefficient, so a first-order rounding analysis
+bounds its error by gamma x the same contraction on absolute values (abs_gradient), gamma = K 2^-53, K the number of roundings on the
+longest path from the inputs to an element.  For the device's order (kernels_sitegrad.hip), with N sites, m the largest bond and n
+images:
+  * a chain step forms fl(phi_s v[k]) (1 rounding) and accumulates 2 m such terms in the MFMA unit; counting a rounding for every
+    product and one for every addition, a step adds at most 4 m + 1 roundings to a path.  An element's path crosses every site but
+    its own, inward and outward steps together: (N - 1)(4 m + 1);
+  * the seed at the Label site accumulates nl labels in one chain step, (nl - 1) 4 m further terms, and forms fl(c phi_s): + 1;
+  * the GEMM forms fl(phi_s X[r]) or fl(fl(c phi_s) R[r]) (2), multiplies and accumulates n images (2 n).
+K_dev = (N - 1)(4 m + 1) + (nl - 1) 4 m + 2 n + 3.  The model's own einsum / BLAS sums have the same term counts in another order: the
+comparison is bounded with K = 2 K_dev.
+In the labels mode c = 2 (W - y) carries the error of the weight itself.  A weight is N chain steps and a dot of m terms: at most
+K_w = N (4 m + 1) + 2 m + 1 roundings on each side (+ 1 for the subtraction), so |dc| <= 2 (2 K_w + 1) 2^-53 (Wabs + |y|), Wabs the
+weight's contraction on absolute values; the term abs_gradient(.., |dc|) is added.
+"""
+import numpy as np
+
+U = 2.0 ** -53
+
+
+def mps_with_dims(dims, seed, label_site=None):
+    """random weight MPS with the bond dimensions d_0 = 1, d_1, ..., d_N = 1, the Label index on site label_site (1-based; default
+    N // 2; 0: none), near-identity so that chain vectors keep their scale"""
+    rng = np.random.default_rng(seed)
+    N = len(dims) - 1
+    c = N // 2 if label_site is None else label_site
+    W = []
+    for j in range(1, N + 1):
+        ml, mr = dims[j - 1], dims[j]
+        shape = (ml, 2, mr, 10) if j == c else (ml, 2, mr)
+        A = rng.standard_normal(shape) / np.sqrt(2. * max(ml, mr) * (10 if j == c else 1))
+        A[:, 0] += (np.eye(ml, mr) if A.ndim == 3 else np.eye(ml, mr)[:, :, None] / np.sqrt(10.))
+        W.append(A)
+    return W
+
+
+def targets(labels, nl, target_label=None):
+    """y[n, nl] as tnml_evaluate_* has them"""
+    lab = np.asarray(labels).astype(np.int64)
+    if target_label is None:
+        assert nl == 10
+        return np.eye(10)[lab]
+    assert nl == 1
+    return (lab == target_label).astype(np.float64)[:, None]
+
+
+def _contract(W, phi, coef_of, defect=None):
+    """the contraction on W and phi as given; coef_of(weights) -> c[n, nl].  -> (grads, weights, c)"""
+    n, N = phi.shape[0], len(W)
+    assert phi.shape == (n, N, 2)
+    lab_sites = [j for j, A in enumerate(W) if A.ndim == 4]
+    assert len(lab_sites) <= 1
+    c = lab_sites[0] if lab_sites else 0
+    Wc = W[c] if lab_sites else W[c][..., None]
+    nl = Wc.shape[3]
+    M = [np.tensordot(phi[:, j], W[j], axes=(1, 1)) if j != c else None for j in range(N)]          # [n, a, r]
+    L = [np.ones((n, 1))]
+    for j in range(c):
+        L.append(np.einsum("na,nar->nr", L[-1], M[j]))
+    R = {N - 1: np.ones((n, 1))}
+    for j in range(N - 1, c, -1):
+        R[j - 1] = np.einsum("nar,nr->na", M[j], R[j])
+    LA = np.tensordot(L[c], Wc, axes=(1, 0))                                       # [n, s, r, l]
+    LAs = np.einsum("ns,nsrl->nrl", phi[:, c], LA)                                 # [n, r, l]
+    weights = np.einsum("nrl,nr->nl", LAs, R[c])
+    coef = np.asarray(coef_of(weights), dtype=np.float64)
+    assert coef.shape == (n, nl), coef.shape
+    seed = coef
+    if defect == "argmax_seed":                                                    # the seed of k_response: one label, coefficient 1
+        seed = np.zeros_like(coef)
+        seed[np.arange(n), np.abs(weights).argmax(axis=1)] = 1.
+    Xr, Yl = {}, {}
+    if c > 0:
+        AR = np.tensordot(R[c], Wc, axes=(1, 2))                                   # [n, a, s, l]
+        Xr[c - 1] = np.einsum("nl,ns,nasl->na", seed, phi[:, c], AR)
+        for j in range(c - 1, 0, -1):
+            Xr[j - 1] = np.einsum("nar,nr->na", M[j], Xr[j])
+    if c < N - 1:
+        Yl[c + 1] = np.einsum("nl,nrl->nr", seed, LAs)
+        for j in range(c + 1, N - 1):
+            Yl[j + 1] = np.einsum("na,nar->nr", Yl[j], M[j])
+    grads = []
+    for j in range(N):
+        f = phi[:, j]
+        if defect == "swap_s" and j == (c + 1 if c + 1 < N else c - 1):
+            f = f[:, ::-1]
+        if j == c:
+            left, right = L[c], (R[c][:, :, None] * coef[:, None, :]).reshape(n, -1)
+        elif j < c:
+            left, right = L[j], Xr[j]
+        else:
+            left, right = Yl[j], R[j]
+        lf = (left[:, :, None] * f[:, None, :]).reshape(n, -1)                     # [n, (a, s)]
+        if defect == "drop_image" and j == max(c - 1, 0):
+            lf = lf[:-1]
+            right = right[:-1]
+        G = (lf.T @ right).reshape((left.shape[1], 2) + ((R[c].shape[1], nl) if j == c else (right.shape[1],)))
+        grads.append(G if (j != c or lab_sites) else G[..., 0])
+    return grads, weights, coef
+
+
+def site_gradient(W, phi, coef=None, labels=None, target_label=None, defect=None):
+    """-> (grads, weights): grads a list of N arrays shaped like W's, weights[n, nl].  Exactly one of coef[n, nl] and labels[n]
+    (then c = 2 (weights - y), y by targets()).  defect: one of the planted defects of test_sitegrad_model_host.py."""
+    assert (coef is None) != (labels is None)
+    W = [np.asarray(A, dtype=np.float64) for A in W]
+    phi = np.asarray(phi, dtype=np.float64)
+    if coef is not None:
+        coef_of = lambda w: np.asarray(coef, dtype=np.float64)
+    else:
+        factor = 1. if defect == "no_factor2" else 2.
+        coef_of = lambda w: factor * (w - targets(labels, w.shape[1], target_label))
+    grads, weights, _ = _contract(W, phi, coef_of, defect)
+    return grads, weights
+
+
+def rounding_counts(N, m, n, nl):
+    """(K of the comparison of two fp64 evaluations of G, K of c's own error in the labels mode): see the module's header"""
+    k_dev = (N - 1) * (4 * m + 1) + (nl - 1) * 4 * m + 2 * n + 3
+    k_w = N * (4 * m + 1) + 2 * m + 1
+    return 2 * k_dev, 2 * k_w + 1
+
+
+def abs_gradient(W, phi, coef=None, labels=None, target_label=None):
+    """the same contraction on |A|, |phi| and |c| (labels mode: c of the true contraction) -> (grads_abs, weights_abs, |c|)"""
+    W = [np.asarray(A, dtype=np.float64) for A in W]
+    phi = np.asarray(phi, dtype=np.float64)
+    if coef is None:
+        _, w = site_gradient(W, phi, labels=labels, target_label=target_label)
+        coef = 2. * (w - targets(labels, w.shape[1], target_label))
+    c_abs = np.abs(np.asarray(coef, dtype=np.float64))
+    g, w_abs, _ = _contract([np.abs(A) for A in W], np.abs(phi), lambda w: c_abs)
+    return g, w_abs, c_abs
+
+
+def bound(W, phi, coef=None, labels=None, target_label=None):
+    """elementwise bound on |G_a - G_b| between two fp64 evaluations (the device's and the model's): a list shaped like the gradients"""
+    W = [np.asarray(A, dtype=np.float64) for A in W]
+    n, N = np.shape(phi)[0], len(W)
+    m = max(max(A.shape[0], A.shape[2]) for A in W)
+    g_abs, w_abs, c_abs = abs_gradient(W, phi, coef, labels, target_label)
+    nl = c_abs.shape[1]
+    K, Kc = rounding_counts(N, m, n, nl)
+    out = [K * U * g for g in g_abs]
+    if labels is not None:                                                         # c's own error, carried through the same contraction
+        dc = 2. * Kc * U * (w_abs + targets(labels, nl, target_label))
+        g_dc, _, _ = _contract([np.abs(A) for A in W], np.abs(np.asarray(phi, dtype=np.float64)), lambda w: dc)
+        out = [a + b for a, b in zip(out, g_dc)]
+    return out
+
+
+def worst_ratio(got, want, bnd):
+    """max over sites and elements of |got - want| / bound (0 / 0 counts as 0)"""
+    worst = 0.
+    for g, w, b in zip(got, want, bnd):
+        assert g.shape == w.shape == b.shape, (g.shape, w.shape, b.shape)
+        d = np.abs(g - w)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.where(d == 0, 0., d / b)
+        worst = max(worst, float(r.max()))
+    return worst
+
+
+# ---- the data of tests/test_sitegrad_gpu.py, shared with the planted defects of tests/test_sitegrad_model_host.py ----
+DIMS = [[1, 2, 3, 5, 9, 17, 33, 65, 120, 2, 1],
+        [1, 2, 120, 97, 64, 60, 61, 128, 33, 2, 1],
+        [1, 2, 4, 150, 129, 200, 300, 257, 16, 2, 1],
+        [1, 2, 16, 512, 511, 130, 64, 2, 1]]          # the Label site (N = 8, site 4) carries 512 x 2 x 511 x 10
+_CACHE = {}
+
+
+def _images(N, n, seed):
+    from conftest import make_problem
+    from oracle import pyoracle
+    pixels, labels, phi, _ = make_problem(N, n, 2, seed, pixel_boost=200.0)
+    return dict(pixels=pixels, labels=np.asarray(labels, dtype=np.int32), phi=phi, phi8=pyoracle.features_series(pixels),
+                coef=np.random.default_rng(seed + n).standard_normal((n, 10)))
+
+
+def odd_case(k, n):
+    """n images on the k-th list of bond dimensions: dict(pixels, labels, phi (boosted features), phi8 (the bytes' features), coef, W)"""
+    if ("odd", k, n) not in _CACHE:
+        d = _images(len(DIMS[k]) - 1, n, 5)
+        d["W"] = mps_with_dims(DIMS[k], 11)
+        _CACHE[("odd", k, n)] = d
+    return _CACHE[("odd", k, n)]
+
+
+def small_case(N, m, n=70):
+    if ("small", N, m, n) not in _CACHE:
+        from tnml_amd import synth
+        d = _images(N, n, 3)
+        d["W"] = synth.random_mps(N, m, seed=10)
+        _CACHE[("small", N, m, n)] = d
+    return _CACHE[("small", N, m, n)]
+
+
+def model_of(case, form, mode, target_label=None):
+    """(grads, weights, bound) of the model on a case, once per (case, input form, mode)"""
+    key = ("model", id(case), form, mode, target_label)
+    if key not in _CACHE:
+        f = case["phi"] if form == "phi" else case["phi8"]
+        kw = dict(labels=case["labels"], target_label=target_label) if mode == "labels" else dict(coef=case["coef"][:, :1 if target_label is not None else 10])
+        g, w = site_gradient(case["W"], f, **kw)
+        _CACHE[key] = (g, w, bound(case["W"], f, **kw))
+    return _CACHE[key]
+
+
+def fd_allowed(W, phi, labels, j, D, eps, bnd_j, target_label=None):
+    """what a central difference (C(A_j + eps D) - C(A_j - eps D)) / (2 eps) of the cost may differ from <G_j, D> by, C being exactly
+    quadratic in A_j: the rounding of the two costs over 2 eps, plus the bound of G_j against |D|.  Every term (w - y)^2 of a cost is
+    off by at most 2 Kc u (Wabs + |y|)^2, Wabs the weight's contraction on absolute values at |A_j| + eps |D|; the sum of the n nl
+    terms in any order adds n nl roundings, the difference and the division 2 more."""
+    W = [np.asarray(A, dtype=np.float64) for A in W]
+    phi = np.asarray(phi, dtype=np.float64)
+    n, N = phi.shape[0], len(W)
+    m = max(max(A.shape[0], A.shape[2]) for A in W)
+    wide = [np.abs(A) if k != j else np.abs(A) + eps * np.abs(D) for k, A in enumerate(W)]
+    _, w_abs, _ = _contract(wide, np.abs(phi), lambda w: np.zeros_like(w))
+    nl = w_abs.shape[1]
+    _, Kc = rounding_counts(N, m, n, nl)
+    c_abs = ((w_abs + targets(labels, nl, target_label)) ** 2).sum()
+    return 2 * (2 * Kc + n * nl + 2) * U * c_abs / (2 * eps) + (bnd_j * np.abs(D)).sum()
+
+
+def fd_eps(A, D):
+    """a power of two near 2^-8 max|A| / max|D|"""
+    return 2.0 ** np.round(np.log2(2.0 ** -8 * np.abs(A).max() / np.abs(D).max()))

@@ -1,5 +1,5 @@
-// chain_common.h -- what the chain kernels share: k_chain (kernels_chain.hip, streamed inference) and k_response (kernels_response.hip,
-// streamed site responses).  The element-type traits ChainT<E>, the features of a site (chain_features), the A fragment of a 16-wide k block
+// chain_common.h -- what the chain kernels share: k_chain (kernels_chain.hip, streamed inference), k_response (kernels_response.hip,
+// streamed site responses) and k_site_backward / k_site_grad (kernels_sitegrad.hip, streamed site gradients).  The element-type traits ChainT<E>, the features of a site (chain_features), the A fragment of a 16-wide k block
 // (chain_load_a) and one site of a chain (chain_step); the fragment maps, the k blocks and the arithmetic order are described in the header
 // of kernels_chain.hip.
 #pragma once

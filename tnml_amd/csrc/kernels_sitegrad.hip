@@ -1,0 +1,370 @@
+// kernels_sitegrad.hip -- streamed site gradients (tnml_site_gradient_u8 / tnml_site_gradient_phi): for a chunk of images and
+// coefficients c[n][l] = dC/dW_l(x_n), the gradient of C with respect to every site tensor,
+//
+//   j < c:   G_j[a,s,r]   += sum_n L_{j-1,n}[a] phi_{n,j}[s] X_{j,n}[r]
+//   j > c:   G_j[a,s,r]   += sum_n Y_{j-1,n}[a] phi_{n,j}[s] R_{j+1,n}[r]
+//   j = c:   G_c[a,s,r,l] += sum_n c_nl L_{c-1,n}[a] phi_{n,c}[s] R_{c+1,n}[r]
+//
+// L and R are the inward chain vectors of k_chain / k_response, X and Y the outward vectors on the left and on the right of the Label
+// site c (site 1 in the per-label variant), seeded at c with
+//   X_{c-1}[a] = sum_l c_nl sum_s phi_{n,c}[s] sum_r A_c[a,s,r,l] R_{c+1}[r],     Y_c[r] = sum_l c_nl sum_s phi_{n,c}[s] sum_a A_c[a,s,r,l] L_{c-1}[a]
+// and carried outward by X_{j-1} = (phi_j A_j) X_j, Y_j = Y_{j-1} (phi_j A_j).  Two launches per chunk.
+//
+// 1. k_site_backward (class site_bwd): one workgroup (8 waves) per tile of T = 64 / 32 / 16 images (chain_tile<double>), two walks.
+//    Phase A is k_response's, call for call: k_chain's walk, so that weights and pred are bit for bit those of k_chain<double>, with
+//    every chain vector also written to the workgroup's slice of a tape (one region of ru16(bond) x T doubles per bond b = 0..N, in the
+//    LDS tile's element order ChainT<double>::idx<NCT>; L_b for b < c, R_{b+1} for b >= c, the two ends holding the 1 that starts a chain).
+//    Centre: the coefficients of the tile go to LDS [nl][T] -- given (coef), or formed from the weight just computed as
+//    c_nl = 2 (W_l(x_n) - y_nl) (labels; y as tnml_evaluate_*: [l == label_n], per-label variant [label_n == target]) and written to the
+//    [C][nl] buffer the GEMM reads; columns beyond the chunk get 0.  The seeds are chain steps over the compound index (l, s, r):
+//    operand fl(fl(c_nl phi_s) R[r]) (resp. L[a]), accumulated by v_mfma_f64_16x16x4_f64 with l ascending and, inside a label, the k
+//    blocks of chain_step.  Phase B carries X and Y outward with chain_step itself (the products of k_response without its dots) and
+//    writes every outward vector to a second tape with the same region table: X_b on bond b < c, Y_b on bond b >= c.
+//    LDS: two chain tiles [mcap][T] and the coefficients [nl][T]: k_chain's tile thresholds carry over.
+//
+// 2. k_site_grad (class site_grad), the hot path: per site an fp64 GEMM whose reduction index is the image.  The grid runs over
+//    (virtual site, 32 x 32 output block), a virtual site being a site or one label of the Label site; a prefix table gives the first
+//    block of each.  A workgroup of 4 waves stages, per tile of the chunk, 32 rows of the a-side vector and 32 rows of the r-side
+//    vector into LDS, the r side multiplied by the feature while staging (fl(phi_s X[r]); Label site: fl(fl(c_nl phi_s) R[r])); each wave
+//    owns a 16 (a) x 16 (r) output tile for both s and issues v_mfma_f64_16x16x4_f64 with the r side as the row operand, so that a
+//    lane's outputs are contiguous in a.
+//    Summation order, fixed: the accumulators are loaded from G at the chunk's start (the host zeroes G before the first chunk) and
+//    stored at its end, chunks in chunk order; inside a chunk the tiles this launch's k_site_backward wrote, in tile order, images
+//    ascending, four per MFMA step (step t of a tile multiplies images 4 t .. 4 t + 3, lane group q holding image 4 t + q).  Images
+//    beyond the chunk contribute exact zeros: both operands are masked, the r side through its feature / coefficient operand (the
+//    tape holds 1 on bonds 0 and N for every column).  Rows beyond a bond are neither read nor stored.
+//    G is therefore bit-identical on repeats and independent of the tile width (predict_tile: a narrower tile only moves the same
+//    MFMA steps to other tiles, and trailing steps of zeros change nothing).  Its last bits may depend on gradient_chunk: a chunk
+//    that is no multiple of 4 images shifts the grouping of the images into MFMA steps.
+//
+// No atomics; compiled with -ffp-contract=off like its neighbours.
+#include "chain_common.h"
+
+#define SG_THREADS 256
+#define SG_BLK 32                   /* output block: SG_BLK (a) x SG_BLK (r), both s */
+
+// the seed of an outward walk (see the header): vout[M][T] = sum_l (site matrix of label l) x (c_l phi . vin); vin an LDS tile, vout a tape region
+template <int NCT, bool LEFT>
+static __device__ __forceinline__ void seed_step(const double* __restrict__ A, size_t lstride, int nl, int ml, int mr, const double* vin, double* vout,
+                                                 const double (&p0)[NCT], const double (&p1)[NCT], const double* cl, int wave, int lane) {
+    typedef ChainT<double> Tr;
+    constexpr int T = 16 * NCT;
+    const int c16 = lane & 15, q = lane >> 4;
+    const int K = LEFT ? 2 * ml : 2 * mr, M = LEFT ? mr : ml;
+    const int nrt = (M + 15) >> 4;
+    for (int rt = wave; rt < nrt; rt += CHAIN_WAVES) {
+        const int orow = rt * 16 + c16;
+        Tr::v4 acc[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) acc[ct] = Tr::v4{0, 0, 0, 0};
+        for (int l = 0; l < nl; ++l) {
+            double c0[NCT], c1[NCT];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                const double cv = cl[l * T + 16 * ct + c16];
+                c0[ct] = cv * p0[ct]; c1[ct] = cv * p1[ct];
+            }
+            const double* const Al = A + (size_t)l * lstride;
+            for (int base = 0; base < K; base += 16) {
+                double a[4];
+                chain_load_a<double, LEFT>(Al, ml, M, K, orow, base + 4 * q, a);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int kk = base + 4 * q + i;
+                    const bool kok = kk < K;
+                    int s, vr;
+                    if (LEFT) { s = kk >= ml ? 1 : 0; vr = kk - (s ? ml : 0); }
+                    else      { s = kk & 1; vr = kk >> 1; }
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct) {
+                        double b = 0;
+                        if (kok) b = (s ? c1[ct] : c0[ct]) * vin[Tr::template idx<NCT>(vr, 16 * ct + c16)];
+                        acc[ct] = Tr::mfma(a[i], b, acc[ct]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = Tr::row(rt, q, r);
+                if (row < M) vout[Tr::template idx<NCT>(row, 16 * ct + c16)] = acc[ct][r];
+            }
+    }
+}
+
+template <int NCT, int SRC>
+__global__ __launch_bounds__(CHAIN_THREADS) void k_site_backward(const SiteGradArgs g) {
+    typedef ChainT<double> Tr;
+    constexpr int T = 16 * NCT;
+    extern __shared__ __attribute__((aligned(16))) unsigned char sg_lds_raw[];
+    double* const lds = reinterpret_cast<double*>(sg_lds_raw);
+    const ChainArgs<double>& ch = g.ch;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tile0 = blockIdx.x * T;
+    const size_t tile_elems = (size_t)ch.mcap * T;
+    double* buf[2] = {lds, lds + tile_elems};
+    double* const cl = lds + 2 * tile_elems;                           // [nl][T] coefficients of the tile
+    const int N = ch.N, cs = ch.cs, nright = N - cs;
+    const size_t slice = (size_t)blockIdx.x * g.rowoff[N + 1] * T;
+    double* const tp = g.tape + slice;                                 // inward vectors: L_b (b < cs), R_{b+1} (b >= cs) on bond b
+    double* const tq = g.tape2 + slice;                                // outward vectors: X_b (b < cs), Y_b (b >= cs) on bond b
+    auto bond = [&](int b) { return tp + (size_t)g.rowoff[b] * T; };
+    auto bond2 = [&](int b) { return tq + (size_t)g.rowoff[b] * T; };
+    auto copy_rows = [&](const double* src, double* dst, int rows) { for (int i = tid; i < rows * T; i += CHAIN_THREADS) dst[i] = src[i]; };
+
+    // ---- phase A: k_chain's walk as k_response has it, every chain vector also to the tape ----
+    auto site_at = [&](int t) { return t < nright ? N - t : (t < N - 1 ? t - nright + 1 : cs); };
+    double p0[NCT], p1[NCT], q0[NCT], q1[NCT];
+    const int img0 = tile0 + (lane & 15);
+    chain_features<double, NCT, SRC>(ch, site_at(0), img0, p0, p1);
+    double* const park = bond(cs);                                     // R_{cs+1}
+    if (tid < T) {
+        const int at = Tr::template idx<NCT>(0, tid);
+        buf[0][at] = 1; bond(N)[at] = 1; bond(0)[at] = 1;
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int t = 0; t < N - 1; ++t) {
+        const int j = site_at(t);
+        chain_features<double, NCT, SRC>(ch, site_at(t + 1), img0, q0, q1);
+        const ChainSite<double> st = ch.sites[j - 1];
+        const bool right = t < nright, last = t == nright - 1;
+        if (right) {
+            chain_step<double, NCT, false>(st.a, st.ml, st.mr, buf[cur], last ? park : buf[cur ^ 1], p0, p1, wave, lane);
+            if (last) { if (tid < T) buf[cur ^ 1][Tr::template idx<NCT>(0, tid)] = 1; }        // the left chain starts from 1
+        } else {
+            chain_step<double, NCT, true>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
+        }
+        cur ^= 1;
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) { p0[ct] = q0[ct]; p1[ct] = q1[ct]; }
+        __syncthreads();
+        if (!last) copy_rows(buf[cur], right ? bond(j - 1) : bond(j), right ? st.ml : st.mr);  // R_j on bond j-1, L_j on bond j
+    }
+    // centre site as k_chain has it; p0, p1 are the centre's features from here on.  The coefficients of the tile go to cl.
+    const ChainSite<double> sc = ch.sites[cs - 1];
+    const size_t lstride = (size_t)sc.ml * 2 * sc.mr;
+    const int img = tile0 + tid;
+    double best = 0, w0 = 0; int arg = 0;
+    for (int l = 0; l < ch.nl; ++l) {
+        chain_step<double, NCT, true>(sc.a + l * lstride, sc.ml, sc.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
+        __syncthreads();
+        if (tid < T) {
+            double cv = 0;
+            if (img < ch.cnt) {
+                double w = 0;
+                for (int r = 0; r < sc.mr; ++r) w = Tr::fma(buf[cur ^ 1][Tr::template idx<NCT>(r, tid)], park[Tr::template idx<NCT>(r, tid)], w);
+                ch.wout[(size_t)img * ch.nl + l] = w;
+                const double wa = Tr::abs(w);
+                if (l == 0) { best = wa; w0 = w; } else if (wa > best) { best = wa; arg = l; }      // first maximum of |W_l| (util.h:42-57)
+                if (g.lab) {
+                    const int lb = g.lab[img];
+                    const double y = (ch.single ? lb == g.target : lb == l) ? 1. : 0.;
+                    cv = 2. * (w - y);
+                    g.coef[(size_t)img * ch.nl + l] = cv;
+                } else {
+                    cv = g.coef[(size_t)img * ch.nl + l];
+                }
+            }
+            cl[l * T + tid] = cv;
+        }
+        __syncthreads();
+    }
+    if (tid < T && img < ch.cnt) ch.pred[img] = ch.single ? (w0 > 0.5 ? 1 : 0) : arg;
+    copy_rows(park, buf[cur ^ 1], sc.mr);                              // R into the free tile: the operand of the right-type seed
+    __syncthreads();
+
+    // ---- centre: the seeds X_{cs-1} (second tape, bond cs-1) and Y_cs (bond cs) ----
+    if (cs > 1) seed_step<NCT, false>(sc.a, lstride, ch.nl, sc.ml, sc.mr, buf[cur ^ 1], bond2(cs - 1), p0, p1, cl, wave, lane);
+    if (cs < N) seed_step<NCT, true>(sc.a, lstride, ch.nl, sc.ml, sc.mr, buf[cur], bond2(cs), p0, p1, cl, wave, lane);
+
+    // ---- phase B, left of the centre: X_{j-1} = (phi_j A_j) X_j, j = cs-1 .. 2 ----
+    if (cs > 2) {
+        __syncthreads();                                               // the seeds are written, the tiles free
+        copy_rows(bond2(cs - 1), buf[0], sc.ml);
+        chain_features<double, NCT, SRC>(ch, cs - 1, img0, p0, p1);
+        __syncthreads();
+        cur = 0;
+        for (int j = cs - 1; j >= 2; --j) {
+            chain_features<double, NCT, SRC>(ch, j - 1, img0, q0, q1);
+            const ChainSite<double> st = ch.sites[j - 1];
+            chain_step<double, NCT, false>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
+            cur ^= 1;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) { p0[ct] = q0[ct]; p1[ct] = q1[ct]; }
+            __syncthreads();
+            copy_rows(buf[cur], bond2(j - 1), st.ml);
+        }
+    }
+    // ---- phase B, right of the centre: Y_j = Y_{j-1} (phi_j A_j), j = cs+1 .. N-1 ----
+    if (cs < N - 1) {
+        __syncthreads();
+        copy_rows(bond2(cs), buf[0], sc.mr);
+        chain_features<double, NCT, SRC>(ch, cs + 1, img0, p0, p1);
+        __syncthreads();
+        cur = 0;
+        for (int j = cs + 1; j <= N - 1; ++j) {
+            chain_features<double, NCT, SRC>(ch, j + 1, img0, q0, q1);
+            const ChainSite<double> st = ch.sites[j - 1];
+            chain_step<double, NCT, true>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
+            cur ^= 1;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) { p0[ct] = q0[ct]; p1[ct] = q1[ct]; }
+            __syncthreads();
+            copy_rows(buf[cur], bond2(j), st.mr);
+        }
+    }
+}
+
+// ---- the GEMM over the image index ----
+template <int NCT, int SRC>
+__global__ __launch_bounds__(SG_THREADS) void k_site_grad(const SiteGradArgs g) {
+    typedef ChainT<double> Tr;
+    constexpr int T = 16 * NCT, P = T + 4;                            // row pitch of the staged operands (doubles)
+    __shared__ double sa[SG_BLK * P];                                  // a side [32][P]
+    __shared__ double sr[2 * SG_BLK * P];                              // r side [s][32][P], the feature multiplied in
+    __shared__ double fs[2][2][T];                                     // [parity][s][image of the tile]: the feature / coefficient operand
+    const ChainArgs<double>& ch = g.ch;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c16 = lane & 15, q = lane >> 4;
+    const int N = ch.N, cs = ch.cs, nl = ch.nl, NV = N - 1 + nl;
+    // the virtual site of this block: the last v with blk0[v] <= blockIdx.x
+    int lo = 0, hi = NV;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (g.blk0[mid] <= (int)blockIdx.x) lo = mid; else hi = mid; }
+    const int v = lo;
+    int j, l = 0;
+    if (v < cs - 1) j = v + 1; else if (v < cs - 1 + nl) { j = cs; l = v - (cs - 1); } else j = v - nl + 2;
+    const ChainSite<double> st = ch.sites[j - 1];
+    const int ml = st.ml, mr = st.mr;
+    const int nrb = (mr + SG_BLK - 1) / SG_BLK;
+    const int bi = (int)blockIdx.x - g.blk0[v];
+    const int a0 = (bi / nrb) * SG_BLK, r0 = (bi % nrb) * SG_BLK;
+    // a side on bond j-1: L_{j-1} (first tape) up to the centre, Y_{j-1} (second tape) right of it;
+    // r side on bond j: X_j (second tape) left of the centre, R_{j+1} (first tape) from the centre on
+    const size_t rows = g.rowoff[N + 1];
+    const double* const abase = (j <= cs ? g.tape : g.tape2) + (size_t)g.rowoff[j - 1] * T;
+    const double* const rbase = (j < cs ? g.tape2 : g.tape) + (size_t)g.rowoff[j] * T;
+    const bool centre = j == cs;
+    double* const G = g.grad + g.goff[j - 1] + (centre ? (size_t)l * ml * 2 * mr : 0);
+
+    // this wave's output tile: rows of the MFMA = r (r0 + 16 wr + ..), columns = a (a0 + 16 wa + ..); accumulators from G
+    const int wa = wave & 1, wr = wave >> 1;
+    const int oa = a0 + 16 * wa + c16;
+    Tr::v4 acc[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int orr = r0 + 16 * wr + q + 4 * reg;
+            acc[s][reg] = (oa < ml && orr < mr) ? G[oa + (size_t)ml * (s + 2 * orr)] : 0.;
+        }
+
+    // the feature operand of a tile: phi_s of site j (x c_nl at the Label site), (0, 0) beyond the chunk
+    auto features = [&](int tile, int par) {
+        if (tid < T) {
+            const int img = tile * T + tid;
+            double f0[1], f1[1];
+            chain_features<double, 1, SRC>(ch, j, img, f0, f1);
+            if (centre) {
+                const double cv = img < ch.cnt ? g.coef[(size_t)img * nl + l] : 0.;
+                f0[0] = cv * f0[0]; f1[0] = cv * f1[0];
+            }
+            fs[par][0][tid] = f0[0]; fs[par][1][tid] = f1[0];
+        }
+    };
+    const int ntiles = (ch.cnt + T - 1) / T;                          // the tiles this launch's k_site_backward wrote, and no more
+    features(0, 0);
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const int par = tile & 1;
+        const double* const at = abase + (size_t)tile * rows * T;
+        const double* const rt = rbase + (size_t)tile * rows * T;
+        __syncthreads();                                               // the MFMAs of the tile before have read sa / sr; fs[par] is there
+        // stage: thread -> (row, a pair of physical columns); the tape's odd rows have their 16-column halves swapped for T >= 32
+        for (int e = tid; e < SG_BLK * (T / 2); e += SG_THREADS) {
+            const int row = e / (T / 2), pc = (e - row * (T / 2)) * 2;
+            const bool live = tile * T + T <= ch.cnt;                  // every image of the tile is inside the chunk
+            {
+                const int ar = a0 + row;
+                const int col = NCT > 1 ? (pc ^ ((ar & 1) << 4)) : pc;
+                Tr::v2 x = {0, 0};
+                if (ar < ml) x = *(const Tr::v2*)(at + (size_t)ar * T + pc);
+                if (!live) { if (tile * T + col >= ch.cnt) x.x = 0; if (tile * T + col + 1 >= ch.cnt) x.y = 0; }
+                sa[row * P + col] = x.x; sa[row * P + col + 1] = x.y;
+            }
+            {
+                const int rr = r0 + row;
+                const int col = NCT > 1 ? (pc ^ ((rr & 1) << 4)) : pc;
+                Tr::v2 x = {0, 0};
+                if (rr < mr) x = *(const Tr::v2*)(rt + (size_t)rr * T + pc);
+                double y00 = fs[par][0][col] * x.x, y01 = fs[par][0][col + 1] * x.y;
+                double y10 = fs[par][1][col] * x.x, y11 = fs[par][1][col + 1] * x.y;
+                if (!live) {                                           // the zero comes from the feature operand, as a select
+                    if (tile * T + col >= ch.cnt) { y00 = 0; y10 = 0; }
+                    if (tile * T + col + 1 >= ch.cnt) { y01 = 0; y11 = 0; }
+                }
+                sr[row * P + col] = y00; sr[row * P + col + 1] = y01;
+                sr[(SG_BLK + row) * P + col] = y10; sr[(SG_BLK + row) * P + col + 1] = y11;
+            }
+        }
+        if (tile + 1 < ntiles) features(tile + 1, par ^ 1);
+        __syncthreads();
+        const double* const pa = sa + (16 * wa + c16) * P + q;
+        const double* const pr0 = sr + (16 * wr + c16) * P + q;
+        const double* const pr1 = pr0 + SG_BLK * P;
+#pragma unroll 4
+        for (int t = 0; t < T / 4; ++t) {
+            const double a = pa[4 * t];
+            acc[0] = Tr::mfma(pr0[4 * t], a, acc[0]);
+            acc[1] = Tr::mfma(pr1[4 * t], a, acc[1]);
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int orr = r0 + 16 * wr + q + 4 * reg;
+            if (oa < ml && orr < mr) G[oa + (size_t)ml * (s + 2 * orr)] = acc[s][reg];
+        }
+}
+
+size_t sitegrad_lds_bytes(int mcap, int T, int nl) {
+    return ((size_t)2 * mcap * T + (size_t)nl * T) * sizeof(double);
+}
+
+// a.ch.mcap and the grids follow from T; rows: a.rowoff[N + 1] as the host knows it; tape_elems: doubles behind each of the two tapes;
+// nblocks: a.blk0[N - 1 + nl] as the host knows it
+int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int rows, size_t tape_elems, int nblocks) {
+    if (maxbond < 1 || maxbond > TNML_CHAIN_MAXM) return tnml_fail(c, "site gradient kernel: bond dimension %d outside 1..%d", maxbond, TNML_CHAIN_MAXM);
+    if (a.ch.cnt < 1 || a.ch.cnt > a.ch.ld) return tnml_fail(c, "site gradient kernel: %d images in a chunk of %d", a.ch.cnt, a.ch.ld);
+    if (T != 64 && T != 32 && T != 16) return tnml_fail(c, "site gradient kernel: tile width %d", T);
+    if (nblocks < 1) return tnml_fail(c, "site gradient kernel: %d output blocks", nblocks);
+    a.ch.mcap = (maxbond + 15) / 16 * 16;
+    a.ch.park = nullptr;
+    const int grid = (a.ch.cnt + T - 1) / T;
+    const size_t lds = sitegrad_lds_bytes(a.ch.mcap, T, a.ch.nl);
+    if (lds > TNML_CHAIN_LDS) return tnml_fail(c, "site gradient kernel: two tiles of %d x %d do not fit the LDS", a.ch.mcap, T);
+    if ((size_t)grid * T * rows > tape_elems) return tnml_fail(c, "site gradient kernel: tapes of %zu doubles too small for %d tiles of %d x %d", tape_elems, grid, rows, T);
+    const bool codes = a.ch.codeT != nullptr;
+    if (codes && !a.ch.table) return tnml_fail(c, "site gradient kernel: block sums without a table");
+    typedef void (*kern_t)(const SiteGradArgs);
+    static const kern_t bwd[2][3] = {{k_site_backward<1, 0>, k_site_backward<2, 0>, k_site_backward<4, 0>}, {k_site_backward<1, 1>, k_site_backward<2, 1>, k_site_backward<4, 1>}};   // [SRC][T / 32]
+    static const kern_t gemm[2][3] = {{k_site_grad<1, 0>, k_site_grad<2, 0>, k_site_grad<4, 0>}, {k_site_grad<1, 1>, k_site_grad<2, 1>, k_site_grad<4, 1>}};
+    bool& attr = c->attr_sitegrad[codes];
+    if (!attr) {
+        for (kern_t fn : bwd[codes])
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, TNML_CHAIN_LDS) != hipSuccess)
+                return tnml_fail(c, "site gradient kernel: hipFuncSetAttribute failed");
+        attr = true;
+    }
+    {
+        ProfScope ps(c, KC_SITE_BWD);
+        hipLaunchKernelGGL(bwd[codes][T / 32], dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
+        HIPCK(c, hipGetLastError());
+    }
+    ProfScope ps(c, KC_SITE_GRAD);
+    hipLaunchKernelGGL(gemm[codes][T / 32], dim3(nblocks), dim3(SG_THREADS), 0, c->stream, a);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}

@@ -120,6 +120,7 @@ static const OptDef k_options[] = {
     {"predict_tile",     nullptr,               OPT_INT,  &tnml_ctx::predict_tile,        nullptr,          0, 64,      HK_PREDICT_TILE},
     {"predict_dtype",    nullptr,               OPT_INT,  &tnml_ctx::predict_dtype,       nullptr,          0, 1,       HK_NONE},   // TNML_PREDICT_F64 / TNML_PREDICT_F32
     {"response_chunk",   nullptr,               OPT_INT,  &tnml_ctx::response_chunk,      nullptr,          1, 1 << 20, HK_NONE},
+    {"gradient_chunk",   nullptr,               OPT_INT,  &tnml_ctx::gradient_chunk,      nullptr,          1, 1 << 20, HK_NONE},
     {"fg64_cfg",         "TNML_FG64_CFG",       OPT_INT,  &tnml_ctx::opt_fg64_cfg,        nullptr,          0, 2,       HK_NONE},
     {"ldot_cfg",         "TNML_LDOT_CFG",       OPT_INT,  &tnml_ctx::opt_ldot_cfg,        nullptr,          0, 2,       HK_NONE},
     {"pcut",             nullptr,               OPT_REAL, nullptr,                        &tnml_ctx::pcut,  0, HUGE_VAL, HK_NONE},
@@ -446,6 +447,7 @@ int tnml_destroy(tnml_ctx* c) {
     if (c->psave) (void)hipFree(c->psave);                // (option spec_predict)
     predict_release(c);                                   // the workspace of tnml_predict_* (first call)
     response_release(c);                                  // and of tnml_response_*
+    sitegrad_release(c);                                  // and of tnml_site_gradient_*
     for (auto& sl : c->slabs) if (sl.base) (void)hipFree(sl.base);
     if (c->hrep) (void)hipHostFree(c->hrep);
     if (c->hcost) (void)hipHostFree(c->hcost);

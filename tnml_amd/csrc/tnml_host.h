@@ -99,6 +99,7 @@ int shift_env_impl(tnml_ctx* c, int b, int from_left);
 void predict_release_map(tnml_ctx* c);
 void predict_release(tnml_ctx* c);
 void response_release(tnml_ctx* c);                    // the workspace of tnml_response_* (synchronise first)
+void sitegrad_release(tnml_ctx* c);                    // the workspace of tnml_site_gradient_* (synchronise first)
 
 // ---- tnml_bond.hip ----------------------------------------------------------------------------
 PackDesc bond_pack_desc(const BondPlan& p);

@@ -441,3 +441,191 @@ int tnml_response_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* 
     if (n > 0 && !phi) return tnml_fail(c, "tnml_response_phi: null argument");
     return response_impl(c, "tnml_response_phi", n, nullptr, phi, which, resp, weights, pred);
 }
+
+// ---- streamed site gradients (kernels_sitegrad.hip): dC/dA of every site, on images the context does not hold ----------------
+// The chunk loop of tnml_response_* with option gradient_chunk: a chunk is staged as predict stages it, ONE k_site_backward launch walks
+// the chain inward and outward and leaves two tapes, ONE k_site_grad launch adds the chunk's outer products to the gradient, which stays
+// on the device until the last chunk and is copied back once.  Reads W only.  The workspace is its own (tnml.h has its size).
+void sitegrad_release(tnml_ctx* c) {
+    void** slots[] = {(void**)&c->sg_tab, (void**)&c->sg_w, (void**)&c->sg_pred, (void**)&c->sg_lab, (void**)&c->sg_coef, (void**)&c->sg_rowoff, (void**)&c->sg_goff, (void**)&c->sg_blk0,
+                      (void**)&c->sg_grad, (void**)&c->sg_tape, (void**)&c->sg_tape2,
+                      (void**)&c->sg_raw8, (void**)&c->sg_x8, (void**)&c->sg_rawphi, (void**)&c->sg_xphi, (void**)&c->sg_mraw, (void**)&c->sg_codes, (void**)&c->sg_mtab};
+    for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    c->bytes -= c->sg_bytes;
+    c->sg_bytes = 0; c->sg_cap = 0; c->sg_tape_rows = 0; c->sg_grad_elems = 0;
+}
+static int sitegrad_alloc(tnml_ctx* c, void** p, size_t bytes) {
+    TCK(dalloc(c, p, bytes));
+    c->sg_bytes += (int64_t)bytes;
+    return 0;
+}
+static int sitegrad_free(tnml_ctx* c, void** p, size_t bytes) {
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(*p); *p = nullptr;
+    c->bytes -= (int64_t)bytes; c->sg_bytes -= (int64_t)bytes;
+    return 0;
+}
+// rows: the rows of a workgroup's tape slice that W asks for now; elems: the elements of the gradient of W as it is now
+static int sitegrad_workspace(tnml_ctx* c, const char* who, bool bytes_form, size_t rows, size_t elems) {
+    const int cap = (c->gradient_chunk + 63) / 64 * 64;
+    const int nl = c->nl();
+    int rc = 0;
+    if (c->sg_cap != cap) {                               // first call, or option gradient_chunk has changed since
+        if (c->sg_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); sitegrad_release(c); }
+        rc = sitegrad_alloc(c, (void**)&c->sg_tab, (size_t)c->N * sizeof(ChainSite<double>));
+        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_w, (size_t)cap * nl * sizeof(double));
+        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_coef, (size_t)cap * nl * sizeof(double));
+        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_pred, (size_t)cap * sizeof(int));
+        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_lab, (size_t)cap * sizeof(int));
+        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_rowoff, (size_t)(c->N + 2) * sizeof(int));
+        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_goff, (size_t)(c->N + 1) * sizeof(long long));
+        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_blk0, (size_t)(c->N + nl) * sizeof(int));
+        if (rc) { sitegrad_release(c); return rc; }
+        c->sg_cap = cap;
+    }
+    if (rows > c->sg_tape_rows) {                          // the tapes follow the bonds W has: grown when W has grown
+        const size_t old = c->sg_tape_rows * (size_t)cap * sizeof(double);
+        if (c->sg_tape) TCK(sitegrad_free(c, (void**)&c->sg_tape, old));
+        if (c->sg_tape2) TCK(sitegrad_free(c, (void**)&c->sg_tape2, old));
+        c->sg_tape_rows = 0;
+        rc = sitegrad_alloc(c, (void**)&c->sg_tape, rows * (size_t)cap * sizeof(double));
+        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_tape2, rows * (size_t)cap * sizeof(double));
+        if (rc) { sitegrad_release(c); return rc; }
+        c->sg_tape_rows = rows;
+    }
+    if (elems > c->sg_grad_elems) {                        // and so does the gradient
+        if (c->sg_grad) TCK(sitegrad_free(c, (void**)&c->sg_grad, c->sg_grad_elems * sizeof(double)));
+        c->sg_grad_elems = 0;
+        rc = sitegrad_alloc(c, (void**)&c->sg_grad, elems * sizeof(double));
+        if (rc) { sitegrad_release(c); return rc; }
+        c->sg_grad_elems = elems;
+    }
+    if (bytes_form && c->im_set) {
+        if (c->sg_codes) return 0;
+        const size_t S = (size_t)c->im.src_rows * c->im.src_cols, tabb = c->im_table.size() * sizeof(double);
+        rc = sitegrad_alloc(c, (void**)&c->sg_mraw, S * cap);
+        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_codes, (size_t)cap * c->N * sizeof(uint16_t));
+        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_mtab, tabb);
+        if (!rc && hipMemcpyAsync(c->sg_mtab, c->im_table.data(), tabb, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "%s: copy of the input map's table failed", who);
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "%s: hipStreamSynchronize failed", who);
+        if (rc) sitegrad_release(c);
+        return rc;
+    }
+    if (bytes_form && !c->sg_x8) { rc = sitegrad_alloc(c, (void**)&c->sg_raw8, (size_t)cap * c->N); if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_x8, (size_t)cap * c->N); }
+    if (!bytes_form && !c->sg_xphi) { rc = sitegrad_alloc(c, (void**)&c->sg_rawphi, (size_t)2 * cap * c->N * sizeof(double)); if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_xphi, (size_t)2 * cap * c->N * sizeof(double)); }
+    if (rc) sitegrad_release(c);
+    return rc;
+}
+// the refusals of tnml_response_*, in the same words and the same order; *maxbond: the largest bond of W
+static int streamed_fp64_refusals(tnml_ctx* c, const char* who, const char* what, int64_t n, int* maxbond) {
+    if (!c) return tnml_fail(c, "%s: null argument", who);
+    if (n < 0) return tnml_fail(c, "%s: n = %lld, must be >= 0", who, (long long)n);
+    if (c->pend_count > 0) return tnml_fail(c, "%s: a bond update is in flight (tnml_bond_update_end first)", who);
+    TCK(ho_locked(c, who));
+    TCK(check_W(c));
+    int mb = 1;
+    for (int j = 1; j <= c->N; ++j) mb = std::max(mb, std::max(c->W[j].ml, c->W[j].mr));
+    if (mb > TNML_CHAIN_MAXM)
+        return tnml_fail(c, "%s: W has a bond of dimension %d, the chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, mb, TNML_CHAIN_MAXM);
+    if (c->predict_dtype != TNML_PREDICT_F64)
+        return tnml_fail(c, "%s: option predict_dtype = %d (fp32): %s are computed in fp64 only (set predict_dtype = 0)", who, c->predict_dtype, what);
+    *maxbond = mb;
+    return 0;
+}
+// elements of the gradient and where every site starts (off: N + 1 entries or null); W is complete
+static size_t sitegrad_layout(tnml_ctx* c, long long* off) {
+    size_t e = 0;
+    for (int j = 1; j <= c->N; ++j) {
+        if (off) off[j - 1] = (long long)e;
+        e += (size_t)2 * c->W[j].ml * c->W[j].mr * c->W[j].L;
+    }
+    if (off) off[c->N] = (long long)e;
+    return e;
+}
+int tnml_site_gradient_size(tnml_ctx* c, int64_t* elems, int64_t* offsets) {
+    if (!c || !elems) return tnml_fail(c, "tnml_site_gradient_size: null argument");
+    TCK(check_W(c));
+    std::vector<long long> off(c->N + 1);
+    *elems = (int64_t)sitegrad_layout(c, off.data());
+    if (offsets) for (int j = 0; j <= c->N; ++j) offsets[j] = off[j];
+    return 0;
+}
+static int sitegrad_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
+                         double* grad, double* weights, int32_t* pred) {
+    int maxbond = 1;
+    TCK(streamed_fp64_refusals(c, who, "site gradients", n, &maxbond));
+    if (!grad) return tnml_fail(c, "%s: null argument", who);
+    const int N = c->N, nl = c->nl(), cs = c->single() ? 1 : c->c0;
+    if (c->W[cs].L != nl) return tnml_fail(c, "%s: the Label site %d of W carries %d labels, the context has %d", who, cs, c->W[cs].L, nl);
+    std::vector<long long> goff(N + 1);
+    const size_t elems = sitegrad_layout(c, goff.data());
+    if (n == 0) { memset(grad, 0, elems * sizeof(double)); return 0; }
+    if (!pixels && !phi) return tnml_fail(c, "%s: null argument", who);
+    if ((labels != nullptr) == (coef != nullptr)) return tnml_fail(c, "%s: exactly one of labels and coef must be given (%s are)", who, labels ? "both" : "neither");
+    if (labels)
+        for (int64_t i = 0; i < n; ++i)
+            if (labels[i] < 0 || labels[i] >= TNML_NL) return tnml_fail(c, "%s: label %d of image %lld out of range", who, labels[i], (long long)i);
+    if (coef)
+        for (int64_t i = 0; i < n * nl; ++i)
+            if (!std::isfinite(coef[i])) return tnml_fail(c, "%s: coefficient %d of image %lld is not finite", who, (int)(i % nl), (long long)(i / nl));
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    // tape regions: the vector on bond b = 0..N (dimension 1 at the two ends); both tapes share the table (kernels_sitegrad.hip)
+    std::vector<int> rowoff(N + 2);
+    int rows = 0;
+    auto ru16 = [](int m) { return (m + 15) / 16 * 16; };
+    for (int b = 0; b <= N; ++b) { rowoff[b] = rows; rows += ru16(b == 0 ? 1 : c->W[b].mr); }
+    rowoff[N + 1] = rows;
+    // output blocks of 32 x 32 per virtual site: the sites in order, the Label site once per label
+    std::vector<int> blk0(N + nl);
+    int nblocks = 0, v = 0;
+    for (int j = 1; j <= N; ++j) {
+        const int nb = ((c->W[j].ml + 31) / 32) * ((c->W[j].mr + 31) / 32);
+        for (int l = 0; l < (j == cs ? nl : 1); ++l) { blk0[v++] = nblocks; nblocks += nb; }
+    }
+    blk0[v] = nblocks;
+    const bool bytes_form = pixels != nullptr;
+    TCK(sitegrad_workspace(c, who, bytes_form, (size_t)rows, elems));
+    std::vector<ChainSite<double>> tab(N);
+    for (int j = 1; j <= N; ++j) tab[j - 1] = ChainSite<double>{c->W[j].a, c->W[j].ml, c->W[j].mr};
+    HIPCK(c, hipMemcpyAsync(c->sg_tab, tab.data(), sizeof(ChainSite<double>) * N, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(c->sg_rowoff, rowoff.data(), sizeof(int) * (N + 2), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(c->sg_goff, goff.data(), sizeof(long long) * (N + 1), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(c->sg_blk0, blk0.data(), sizeof(int) * (N + nl), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemsetAsync(c->sg_grad, 0, elems * sizeof(double), c->stream));       // the sum starts from zero: grad is overwritten
+    HIPCK(c, hipStreamSynchronize(c->stream));                  // (the tables leave scope with this call)
+    const bool mapped = bytes_form && c->im_set;
+    const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
+    const ChunkStage stage{c->sg_mraw, c->sg_codes, c->sg_raw8, c->sg_x8, c->sg_rawphi, c->sg_cap};
+    SiteGradArgs a;
+    a.ch.sites = c->sg_tab; a.ch.N = N; a.ch.cs = cs; a.ch.nl = nl; a.ch.single = c->single() ? 1 : 0;
+    a.ch.ld = c->sg_cap; a.ch.wout = c->sg_w; a.ch.pred = c->sg_pred;
+    a.ch.xT = nullptr; a.ch.phiT = nullptr;
+    if (mapped) { a.ch.codeT = c->sg_codes; a.ch.table = c->sg_mtab; }
+    else if (bytes_form) a.ch.xT = c->sg_x8;
+    else a.ch.phiT = c->sg_xphi;
+    a.rowoff = c->sg_rowoff; a.tape = c->sg_tape; a.tape2 = c->sg_tape2;
+    a.lab = labels ? c->sg_lab : nullptr; a.target = c->target(); a.coef = c->sg_coef;
+    a.grad = c->sg_grad; a.goff = c->sg_goff; a.blk0 = c->sg_blk0;
+    const size_t tape_elems = c->sg_tape_rows * (size_t)c->sg_cap;
+    for (int64_t off = 0; off < n; off += c->gradient_chunk) {
+        a.ch.cnt = (int)std::min<int64_t>(c->gradient_chunk, n - off);
+        TCK(stage_chunk<double>(c, stage, mapped, sg, pixels, phi, off, a.ch.cnt, c->sg_xphi));
+        if (labels) HIPCK(c, hipMemcpyAsync(c->sg_lab, labels + off, sizeof(int32_t) * (size_t)a.ch.cnt, hipMemcpyHostToDevice, c->stream));
+        else        HIPCK(c, hipMemcpyAsync(c->sg_coef, coef + (size_t)off * nl, sizeof(double) * (size_t)a.ch.cnt * nl, hipMemcpyHostToDevice, c->stream));
+        TCK(launch_site_gradient(c, a, maxbond, chain_tile<double>(c, maxbond, a.ch.cnt), rows, tape_elems, nblocks));
+        if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->sg_w, sizeof(double) * (size_t)a.ch.cnt * nl, hipMemcpyDeviceToHost, c->stream));
+        if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->sg_pred, sizeof(int32_t) * (size_t)a.ch.cnt, hipMemcpyDeviceToHost, c->stream));
+        SYNCK(c, c->stream);                                    // the staging buffers are reused by the next chunk
+    }
+    HIPCK(c, hipMemcpyAsync(grad, c->sg_grad, elems * sizeof(double), hipMemcpyDeviceToHost, c->stream));   // the one copy of the gradient
+    SYNCK(c, c->stream);
+    return 0;
+}
+int tnml_site_gradient_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const int32_t* labels, const double* coef, double* grad, double* weights, int32_t* pred) {
+    if (n > 0 && !pixels) return tnml_fail(c, "tnml_site_gradient_u8: null argument");
+    return sitegrad_impl(c, "tnml_site_gradient_u8", n, pixels, nullptr, labels, coef, grad, weights, pred);
+}
+int tnml_site_gradient_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* labels, const double* coef, double* grad, double* weights, int32_t* pred) {
+    if (n > 0 && !phi) return tnml_fail(c, "tnml_site_gradient_phi: null argument");
+    return sitegrad_impl(c, "tnml_site_gradient_phi", n, nullptr, phi, labels, coef, grad, weights, pred);
+}

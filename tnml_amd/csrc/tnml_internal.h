@@ -33,11 +33,11 @@
 
 enum KClass {
     KC_FGEMM_FWD = 0, KC_FGEMM_SHIFT, KC_LABELDOT, KC_ZPRIME, KC_BGEMM, KC_SLABRED, KC_PACK, KC_VEC,
-    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_EVAL_TALLY, KC_SITE_RESP, KC_COUNT
+    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_EVAL_TALLY, KC_SITE_RESP, KC_SITE_BWD, KC_SITE_GRAD, KC_COUNT
 };
 static const char* const kclass_names[KC_COUNT] = {
     "fgemm_fwd", "fgemm_shift", "labeldot", "zprime", "bgemm", "slab_reduce", "pack", "cg_vec",
-    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain", "eval_tally", "site_resp"};
+    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain", "eval_tally", "site_resp", "site_bwd", "site_grad"};
 
 // device accumulator block of tnml_evaluate_*: the part of tnml_eval_report that k_eval_tally (kernels_eval.hip) adds up
 struct EvalAcc {
@@ -335,6 +335,21 @@ struct tnml_ctx {
     uint8_t *rs_raw8 = nullptr, *rs_x8 = nullptr;          // staging as the predict workspace has it, sized by rs_cap (first call of the input form)
     double *rs_rawphi = nullptr, *rs_xphi = nullptr;
     uint8_t* rs_mraw = nullptr; uint16_t* rs_codes = nullptr; double* rs_mtab = nullptr;   // under an input map (released by every tnml_set_input_map call, with the rest)
+    // streamed site gradients (tnml_site_gradient_u8 / tnml_site_gradient_phi, kernels_sitegrad.hip): a workspace of its own under the rules of
+    // the response workspace (allocated by the first call, counted in `bytes` and sg_bytes, re-made when option gradient_chunk changes)
+    int gradient_chunk = TNML_GRADIENT_CHUNK_DEFAULT;      // option "gradient_chunk": images per launch of k_site_backward / k_site_grad
+    bool attr_sitegrad[2] = {};      // [input map]: the LDS attribute of those k_site_backward instantiations is set
+    int sg_cap = 0; int64_t sg_bytes = 0;                  // gradient_chunk rounded up to 64 when the workspace was sized
+    ChainSite<double>* sg_tab = nullptr;                   // [N] per-site table
+    double* sg_w = nullptr; int* sg_pred = nullptr;        // [sg_cap][nl], [sg_cap]: weights and pred of a chunk
+    int* sg_lab = nullptr; double* sg_coef = nullptr;      // [sg_cap] labels of a chunk; [sg_cap][nl] its coefficients (given, or formed by k_site_backward)
+    int* sg_rowoff = nullptr;                              // [N + 2] rows of the tape regions of bond 0..N, then the rows of a slice
+    long long* sg_goff = nullptr; int* sg_blk0 = nullptr;  // [N + 1] first element of every site in sg_grad; [N + nl] first output block of every virtual site, then the block count
+    double* sg_grad = nullptr; size_t sg_grad_elems = 0;   // the gradient of the call in progress, every site in tnml_get_site's layout; grown when W has grown
+    double *sg_tape = nullptr, *sg_tape2 = nullptr; size_t sg_tape_rows = 0;   // [sg_cap / T][sg_tape_rows][T] each: inward and outward vectors; grown when W has grown
+    uint8_t *sg_raw8 = nullptr, *sg_x8 = nullptr;          // staging as the predict workspace has it, sized by sg_cap (first call of the input form)
+    double *sg_rawphi = nullptr, *sg_xphi = nullptr;
+    uint8_t* sg_mraw = nullptr; uint16_t* sg_codes = nullptr; double* sg_mtab = nullptr;   // under an input map (released by every tnml_set_input_map call, with the rest)
     // input map (tnml_set_input_map): geometry + host copy of the fp64 table; consulted by tnml_set_data_u8 / tnml_predict_u8 only
     bool im_set = false;
     tnml_input_map im = {};          // geometry (table = nullptr)
@@ -607,6 +622,21 @@ struct RespArgs {
 };
 // rows: rowoff[N + 3] as the host knows it; tape_elems: doubles behind a.tape; outT [cnt][N][2] receives the transposed a.resp; class site_resp
 int launch_response(tnml_ctx* c, RespArgs a, int maxbond, int T, int rows, size_t tape_elems, double* outT);
+
+// ---- kernels_sitegrad.hip: streamed site gradients, k_site_backward (two walks, two tapes) and k_site_grad (the GEMM over the image index) ----
+struct SiteGradArgs {
+    ChainArgs<double> ch;              // sites, sources, ld, cnt, wout, pred as k_chain takes them (park and flag unused)
+    const int* rowoff;                 // [N + 2] device: first row of the tape region of bond b = 0..N, then the rows of a slice
+    double* tape;                      // [grid][rows][T] inward vectors
+    double* tape2;                     // [grid][rows][T] outward vectors
+    const int* lab; int target;        // labels of the chunk (coef is then written: c_nl = 2 (W_l - y_nl)) or null (coef is read); the per-label variant's target
+    double* coef;                      // [ld][nl]
+    double* grad;                      // every site in tnml_get_site's layout, site j at goff[j - 1]
+    const long long* goff;             // [N + 1] device
+    const int* blk0;                   // [N + nl] device: first output block of every virtual site (sites in order, the Label site once per label), then the block count
+};
+// rows: rowoff[N + 1] as the host knows it; tape_elems: doubles behind each tape; nblocks: the block count; classes site_bwd, site_grad
+int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int rows, size_t tape_elems, int nblocks);
 
 // ---- kernels_eval.hip: the tallies of streamed evaluation over the results of a chunk ----
 // w [cnt][nl], pred [cnt] (what k_chain left in pk_w / pk_pred), lab [cnt] in 0..9 (the host has checked them) -> acc += the chunk's

@@ -329,6 +329,64 @@ class TrainStates:
             self._ck(self._L.tnml_response_phi(self._h, n, _lib.dptr(x), wp_, _lib.dptr(resp), wp, pp))
         return (resp, (w, pred)) if want_weights else resp
 
+    def site_gradient(self, labels=None, coef=None, pixels=None, phi=None, want_weights=False):
+        """streamed site gradients (tnml_site_gradient_u8 / tnml_site_gradient_phi) on images this context does not hold, in the input
+        forms of predict(): a list of N arrays shaped like get_site()'s, G_j = sum_n sum_l c[n, l] dW_l(x_n)/dA_j.  Exactly one of
+        coef[n, nl] (c as given) and labels[n] (c = 2 (W - y) with the targets of evaluate(): the gradient of the cost evaluate()
+        reports).  With want_weights (grads, (weights[n, nl], pred[n])), both bit for bit those of predict() in fp64.  Reads W only;
+        fp64 only (refused under predict_dtype = 1)."""
+        x = self._streamed_input(pixels, phi, None)
+        n = int(x.shape[0])
+        lp = cp = None
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.shape != (n,):
+                raise ValueError("labels must have shape [%d], got %s" % (n, lab.shape))
+            lp = lab.ctypes.data_as(C.POINTER(C.c_int32))
+        if coef is not None:
+            cf = np.ascontiguousarray(coef, dtype=np.float64)
+            if cf.shape != (n, self.nl):
+                raise ValueError("coef must have shape [%d, %d], got %s" % (n, self.nl, cf.shape))
+            cp = _lib.dptr(cf)
+        elems = C.c_int64()
+        offs = np.zeros(self.N + 1, dtype=np.int64)
+        self._ck(self._L.tnml_site_gradient_size(self._h, C.byref(elems), offs.ctypes.data_as(C.POINTER(C.c_int64))))
+        grad = np.zeros(max(elems.value, 1))
+        w = pred = wp = pp = None
+        if want_weights:
+            w = np.zeros((n, self.nl))
+            pred = np.zeros(n, dtype=np.int32)
+            wp, pp = _lib.dptr(w), pred.ctypes.data_as(C.POINTER(C.c_int32))
+        if pixels is not None:
+            self._ck(self._L.tnml_site_gradient_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), lp, cp, _lib.dptr(grad), wp, pp))
+        else:
+            self._ck(self._L.tnml_site_gradient_phi(self._h, n, _lib.dptr(x), lp, cp, _lib.dptr(grad), wp, pp))
+        grads = []
+        for j in range(1, self.N + 1):
+            ml, mr, hl = C.c_int(), C.c_int(), C.c_int()
+            self._ck(self._L.tnml_site_dims(self._h, j, ml, mr, hl))
+            shape = (ml.value, 2, mr.value) + ((NL,) if hl.value else ())
+            grads.append(grad[offs[j - 1]:offs[j]].reshape(shape, order="F").copy(order="F"))
+        return (grads, (w, pred)) if want_weights else grads
+
+    def descent_step(self, grads, cost_fn, step):
+        """one step of gradient descent with backtracking, for contexts that hold no environments (a context that does must call
+        init() again after W has changed): sets A_j - step G_j on every site as set_mps() does and halves step until cost_fn() is
+        below its value at the W it started from; after 30 halvings without that it puts W back and raises TnmlError.  cost_fn takes
+        no argument and reads this context's W, e.g. lambda: ts.evaluate(labels, pixels=x).cost.  Returns the step taken."""
+        old = self.get_mps()
+        if len(grads) != len(old) or any(np.shape(g) != A.shape for g, A in zip(grads, old)):
+            raise ValueError("grads must be %d arrays shaped like get_mps()'s" % len(old))
+        start = cost_fn()
+        step = float(step)
+        for _ in range(31):                                   # the step as given and at most 30 halvings
+            self.set_mps([A - step * np.asarray(g, dtype=np.float64) for A, g in zip(old, grads)])
+            if cost_fn() < start:
+                return step
+            step *= 0.5
+        self.set_mps(old)
+        raise TnmlError("descent_step: the cost did not fall below %.17g after 30 halvings of the step" % start)
+
     # -- W
     def set_mps(self, W):
         for j, A in enumerate(W, start=1):

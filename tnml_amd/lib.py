@@ -37,6 +37,7 @@ EXPORTS = [
     "tnml_predict_u8", "tnml_predict_phi", "tnml_evaluate_u8", "tnml_evaluate_phi",
     "tnml_set_input_map", "tnml_get_input_map",
     "tnml_response_u8", "tnml_response_phi",
+    "tnml_site_gradient_size", "tnml_site_gradient_u8", "tnml_site_gradient_phi",
 ]
 
 
@@ -149,6 +150,9 @@ def load():
     L.tnml_evaluate_phi.argtypes = [vp, C.c_int64, dp, C.POINTER(C.c_int32), C.POINTER(EvalReport), dp, C.POINTER(C.c_int32)]
     L.tnml_response_u8.argtypes = [vp, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_int32)]
     L.tnml_response_phi.argtypes = [vp, C.c_int64, dp, C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_int32)]
+    L.tnml_site_gradient_size.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.tnml_site_gradient_u8.argtypes = [vp, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), dp, dp, dp, C.POINTER(C.c_int32)]
+    L.tnml_site_gradient_phi.argtypes = [vp, C.c_int64, dp, C.POINTER(C.c_int32), dp, dp, dp, C.POINTER(C.c_int32)]
     L.tnml_set_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_get_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_replica_check.argtypes = [vp, ip]
