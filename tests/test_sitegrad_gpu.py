@@ -259,15 +259,42 @@ def test_gradient_leaves_a_training_context_alone():
     assert ratio <= 1.
 
 
-def _formula(W, chunk, staging, nl=10):
+def _ru16(m):
+    return (m + 15) // 16 * 16
+
+
+def _staging(N, C, forms, imap=None):
+    """the staging of the input forms a streamed workspace has served since it was made, as include/tnml.h states it"""
+    per = {"u8": 2 * N * C, "phi": 32 * N * C}
+    if imap is not None:
+        per["map"] = imap.S * C + 2 * N * C + 16 * imap.ncodes
+    return sum(per[f] for f in ([forms] if isinstance(forms, str) else forms))
+
+
+def _formula(W, chunk, staging, nl=10, imap=None):
     """the workspace of tnml_site_gradient_* as include/tnml.h states it"""
     N = len(W)
     C = (chunk + 63) // 64 * 64
-    ru16 = lambda m: (m + 15) // 16 * 16
-    B = 32 + sum(ru16(A.shape[2]) for A in W[:-1])
+    B = 32 + sum(_ru16(A.shape[2]) for A in W[:-1])
     E = sum(A.size for A in W)
-    stage = {"u8": 2 * N * C, "phi": 32 * N * C}[staging]
-    return 16 * N + 16 * nl * C + 8 * C + 4 * (N + 2) + 8 * (N + 1) + 4 * (N + nl) + 8 * E + 16 * B * C + stage
+    return 16 * N + 16 * nl * C + 8 * C + 4 * (N + 2) + 8 * (N + 1) + 4 * (N + nl) + 8 * E + 16 * B * C + _staging(N, C, staging, imap)
+
+
+def _formula_response(W, chunk, staging, nl=10, imap=None):
+    """the workspace of tnml_response_* as include/tnml.h states it"""
+    N = len(W)
+    C = (chunk + 63) // 64 * 64
+    label_site = next(A for A in W if A.ndim == 4)
+    B = 32 + sum(_ru16(A.shape[2]) for A in W[:-1]) + _ru16(label_site.shape[0]) + _ru16(label_site.shape[2])
+    return 16 * N + 8 * nl * C + 8 * C + 4 * (N + 4) + 32 * N * C + 8 * B * C + _staging(N, C, staging, imap)
+
+
+def _formula_predict(W, chunk, staging, nl=10, imap=None):
+    """the fp64 workspace of tnml_predict_* as include/tnml.h states it, on a context whose maxm is the largest bond of W"""
+    N = len(W)
+    C = (chunk + 63) // 64 * 64
+    M = _ru16(min(max(max(A.shape[0], A.shape[2]) for A in W), 512))
+    return 16 * N + 8 * nl * C + 4 * C + 8 * M * C + _staging(N, C, staging, imap)
 
 
 def test_gradient_bookkeeping():
@@ -376,4 +403,73 @@ def test_descent_step_lowers_the_cost():
         costs.append(cost())
     print("costs", costs, "steps", steps)
     assert all(b < a for a, b in zip(costs, costs[1:])) and all(s > 0 for s in steps)
+    ts.close()
+
+
+def _leaves(x):
+    return [x] if isinstance(x, np.ndarray) else [a for part in x for a in _leaves(part)]
+
+
+def test_the_three_streamed_workspaces_leave_one_another_alone():
+    """predict, response and gradient interleaved on one context: N = 12, bonds up to 5, 70 images in chunks of 64 (two chunks, a ragged
+    tail of 6).  After every round each result is what a fresh context gives that makes that one call alone, bit for bit, and the
+    context holds the sum of the three workspaces of include/tnml.h for the input forms each has served since it was made."""
+    from tnml_amd import hostlib
+    from tnml_amd.input_map import InputMap
+    case = sm.small_case(12, 5)
+    W = case["W"]
+    imap = InputMap(6, 8, 2, 0, 0, 3, 4, hostlib.feature_table("normal", 1.0, 2), feature="normal")      # 48 bytes -> 3 x 4 sites
+    raw = np.random.default_rng(12).integers(0, 256, size=(70, imap.S)).astype(np.uint8)
+    sources = {"phi": dict(phi=case["phi"]), "u8": dict(pixels=case["pixels"]), "map": dict(pixels=raw)}
+    kinds = ("predict", "response", "gradient")
+    chunk = dict.fromkeys(kinds, 64)
+    formula = dict(predict=_formula_predict, response=_formula_response, gradient=_formula)
+
+    def call(ctx, kind, form):
+        if kind == "predict":
+            return ctx.predict(**sources[form])
+        if kind == "response":
+            return ctx.site_response(want_weights=True, **sources[form])
+        return ctx.site_gradient(labels=case["labels"], want_weights=True, **sources[form])
+
+    alone = {}
+
+    def fresh(kind, form):
+        """that one call on a context of its own, in the options and the map of the moment; once per (call, form, chunk)"""
+        key = (kind, form, chunk[kind])
+        if key not in alone:
+            ctx = _dataless(W)
+            for k in kinds:
+                ctx.set_option(k + "_chunk", chunk[k])
+            if form == "map":
+                ctx.set_input_map(imap)
+            alone[key] = _leaves(call(ctx, kind, form))
+            ctx.close()
+        return alone[key]
+
+    ts = _dataless(W)
+    before = ts.device_bytes()
+    for k in kinds:
+        ts.set_option(k + "_chunk", 64)
+    served = {k: [] for k in kinds}                                # the input forms a workspace has staged since it was made
+
+    def round_of(form):
+        for k in kinds:
+            got = _leaves(call(ts, k, form))
+            assert _same(got, fresh(k, form)), (k, form, chunk[k])
+            assert all(a.any() for a in got if a.dtype.kind == "f"), (k, form)
+            if form not in served[k]:
+                served[k].append(form)
+        want = sum(formula[k](W, chunk[k], served[k], imap=imap) for k in kinds)
+        print(form, chunk, "device bytes", ts.device_bytes() - before, "tnml.h", want)
+        assert ts.device_bytes() - before == want, (form, served)
+
+    round_of("phi")
+    round_of("u8")
+    ts.set_input_map(imap)          # predict keeps its workspace but for the map's part; response and gradient are released whole
+    served["response"], served["gradient"] = [], []
+    round_of("map")
+    ts.set_option("response_chunk", 128)                            # re-makes the response workspace alone
+    chunk["response"], served["response"] = 128, []
+    round_of("map")
     ts.close()

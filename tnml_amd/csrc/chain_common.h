@@ -1,7 +1,11 @@
 // chain_common.h -- what the chain kernels share: k_chain (kernels_chain.hip, streamed inference), k_response (kernels_response.hip,
-// streamed site responses) and k_site_backward / k_site_grad (kernels_sitegrad.hip, streamed site gradients).  The element-type traits ChainT<E>, the features of a site (chain_features), the A fragment of a 16-wide k block
-// (chain_load_a) and one site of a chain (chain_step); the fragment maps, the k blocks and the arithmetic order are described in the header
-// of kernels_chain.hip.
+// streamed site responses) and k_site_backward / k_site_grad (kernels_sitegrad.hip, streamed site gradients).
+//   * All of them: the element-type traits ChainT<E>, the features of a site (chain_features), the A fragment of a 16-wide k block
+//     (chain_load_a) and one site of a chain (chain_step); the fragment maps, the k blocks and the arithmetic order are described in the
+//     header of kernels_chain.hip.
+//   * k_response and k_site_backward, which walk the chain inward and then outward: the tape (ChainTape), the taped inward walk
+//     (chain_walk_taped), the centre site with weights and pred (chain_centre_taped) and the host side of their launches (taped_launch).
+//     The inward walk and the centre are k_chain's, call for call and in its order; that order is stated once, above chain_walk_taped.
 #pragma once
 #include "tnml_internal.h"
 
@@ -145,4 +149,118 @@ static __device__ __forceinline__ void chain_step(const E* __restrict__ A, int m
                 if (row < M) vout[Tr::template idx<NCT>(row, 16 * ct + c16)] = acc[ct][r];
             }
     }
+}
+
+// ---- the taped walk: what k_response and k_site_backward share ----
+// A workgroup's slice of a tape: one region of ru16(bond) x T doubles per bond b = 0..N (between sites b and b + 1; b = 0 and b = N: the 1
+// that starts a chain), in the LDS tile's own element order ChainT<double>::idx<NCT>, region b at row rowoff[b].  The inward tape holds L_b
+// for b < cs and R_{b+1} for b >= cs.  A slice is written and read by its own workgroup (and by the launch behind it).
+template <int T> struct ChainTape {
+    double* tp; const int* rowoff;
+    __device__ __forceinline__ double* bond(int b) const { return tp + (size_t)rowoff[b] * T; }
+};
+template <int T>
+static __device__ __forceinline__ void chain_copy_rows(const double* src, double* dst, int rows, int tid) {
+    for (int i = tid; i < rows * T; i += CHAIN_THREADS) dst[i] = src[i];
+}
+
+// The inward walk of k_chain<double>, call for call and in its order -- right chain N -> cs+1, whose last vector R_{cs+1} is parked on bond
+// cs of the tape, then left chain 1 -> cs-1 -- with every chain vector also copied to the tape (R_j on bond j-1, L_j on bond j).  On return
+// buf[cur] holds L_{cs-1}, p0 / p1 the features of the centre site, and every thread has passed the last barrier.
+template <int NCT, int SRC>
+static __device__ __forceinline__ int chain_walk_taped(const ChainArgs<double>& ch, double* const (&buf)[2], const ChainTape<16 * NCT>& tape,
+                                                       double (&p0)[NCT], double (&p1)[NCT], int tile0, int tid) {
+    typedef ChainT<double> Tr;
+    constexpr int T = 16 * NCT;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int N = ch.N, cs = ch.cs, nright = N - cs;
+    auto site_at = [&](int t) { return t < nright ? N - t : (t < N - 1 ? t - nright + 1 : cs); };
+    double q0[NCT], q1[NCT];
+    const int img0 = tile0 + (lane & 15);
+    chain_features<double, NCT, SRC>(ch, site_at(0), img0, p0, p1);
+    double* const park = tape.bond(cs);                                // R_{cs+1}
+    if (tid < T) {
+        const int at = Tr::template idx<NCT>(0, tid);
+        buf[0][at] = 1; tape.bond(N)[at] = 1; tape.bond(0)[at] = 1;
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int t = 0; t < N - 1; ++t) {
+        const int j = site_at(t);
+        chain_features<double, NCT, SRC>(ch, site_at(t + 1), img0, q0, q1);
+        const ChainSite<double> st = ch.sites[j - 1];
+        const bool right = t < nright, last = t == nright - 1;
+        if (right) {
+            chain_step<double, NCT, false>(st.a, st.ml, st.mr, buf[cur], last ? park : buf[cur ^ 1], p0, p1, wave, lane);
+            if (last) { if (tid < T) buf[cur ^ 1][Tr::template idx<NCT>(0, tid)] = 1; }        // the left chain starts from 1
+        } else {
+            chain_step<double, NCT, true>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
+        }
+        cur ^= 1;
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) { p0[ct] = q0[ct]; p1[ct] = q1[ct]; }
+        __syncthreads();
+        if (!last) chain_copy_rows<T>(buf[cur], right ? tape.bond(j - 1) : tape.bond(j), right ? st.ml : st.mr, tid);
+    }
+    return cur;
+}
+
+// The centre site as k_chain<double> has it: per label l ascending one left-chain step into buf[cur ^ 1] and, by thread tid < T for image
+// tile0 + tid, the dot with R (park) over r ascending, w = fma(T[r], R[r], w) from 0 -> wout; pred = the first maximum of |W_l|
+// (util.h:42-57; per-label variant [W_0 > 1/2]) -> pred.  weights and pred are therefore bit for bit those of k_chain<double>.
+// hook(l, w, tid, img) runs in the threads tid < T between the two barriers of label l (w = 0 for an image beyond the chunk).
+// Returns pred of the thread's image (threads tid < T inside the chunk).
+template <int NCT, typename Hook>
+static __device__ __forceinline__ int chain_centre_taped(const ChainArgs<double>& ch, double* const (&buf)[2], int cur, const double* park,
+                                                         const double (&p0)[NCT], const double (&p1)[NCT], int tile0, int tid, Hook hook) {
+    typedef ChainT<double> Tr;
+    constexpr int T = 16 * NCT;
+    const ChainSite<double> sc = ch.sites[ch.cs - 1];
+    const size_t lstride = (size_t)sc.ml * 2 * sc.mr;
+    const int img = tile0 + tid;
+    double best = 0, w0 = 0; int arg = 0;
+    for (int l = 0; l < ch.nl; ++l) {
+        chain_step<double, NCT, true>(sc.a + l * lstride, sc.ml, sc.mr, buf[cur], buf[cur ^ 1], p0, p1, tid >> 6, tid & 63);
+        __syncthreads();
+        if (tid < T) {
+            double w = 0;
+            if (img < ch.cnt) {
+                for (int r = 0; r < sc.mr; ++r) w = Tr::fma(buf[cur ^ 1][Tr::template idx<NCT>(r, tid)], park[Tr::template idx<NCT>(r, tid)], w);
+                ch.wout[(size_t)img * ch.nl + l] = w;
+                const double wa = Tr::abs(w);
+                if (l == 0) { best = wa; w0 = w; } else if (wa > best) { best = wa; arg = l; }
+            }
+            hook(l, w, tid, img);
+        }
+        __syncthreads();
+    }
+    const int pr = ch.single ? (w0 > 0.5 ? 1 : 0) : arg;
+    if (tid < T && img < ch.cnt) ch.pred[img] = pr;
+    return pr;
+}
+
+// The host side of a launch of k_response / k_site_backward (name and tape_word in the messages): the argument checks, ch.mcap, the grid and
+// the dynamic LDS (two tiles + lds_extra bytes), and once per context the LDS attribute of the three tile widths kern[input map][T / 32]
+struct TapedLaunch { int grid; size_t lds; bool codes; };
+template <typename K>
+static inline int taped_launch(tnml_ctx* c, const char* name, const char* tape_word, ChainArgs<double>& ch, int maxbond, int T, int rows, size_t tape_elems,
+                               size_t lds_extra, const K (&kern)[2][3], bool (&attr)[2], TapedLaunch* o) {
+    if (maxbond < 1 || maxbond > TNML_CHAIN_MAXM) return tnml_fail(c, "%s: bond dimension %d outside 1..%d", name, maxbond, TNML_CHAIN_MAXM);
+    if (ch.cnt < 1 || ch.cnt > ch.ld) return tnml_fail(c, "%s: %d images in a chunk of %d", name, ch.cnt, ch.ld);
+    if (T != 64 && T != 32 && T != 16) return tnml_fail(c, "%s: tile width %d", name, T);
+    ch.mcap = (maxbond + 15) / 16 * 16;
+    ch.park = nullptr;
+    o->grid = (ch.cnt + T - 1) / T;
+    o->lds = (size_t)2 * ch.mcap * T * sizeof(double) + lds_extra;
+    if (o->lds > TNML_CHAIN_LDS) return tnml_fail(c, "%s: two tiles of %d x %d do not fit the LDS", name, ch.mcap, T);
+    if ((size_t)o->grid * T * rows > tape_elems) return tnml_fail(c, "%s: %s of %zu doubles too small for %d tiles of %d x %d", name, tape_word, tape_elems, o->grid, rows, T);
+    o->codes = ch.codeT != nullptr;
+    if (o->codes && !ch.table) return tnml_fail(c, "%s: block sums without a table", name);
+    if (!attr[o->codes]) {
+        for (K fn : kern[o->codes])
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, TNML_CHAIN_LDS) != hipSuccess)
+                return tnml_fail(c, "%s: hipFuncSetAttribute failed", name);
+        attr[o->codes] = true;
+    }
+    return 0;
 }

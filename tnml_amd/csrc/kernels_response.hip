@@ -8,10 +8,9 @@
 // One workgroup (8 waves) owns one tile, as in k_chain (kernels_chain.hip; the fragment maps, the k blocks, the masking and the tile
 // thresholds are those of that kernel, the shared code is chain_common.h), and walks the chain twice.
 //
-// Phase A is k_chain's walk, call for call and in its order: right chain N -> c+1, left chain 1 -> c-1, then per label one left-chain
-// step and the dot with R over r ascending.  weights and pred are therefore bit for bit those of k_chain<double>.  Every chain vector
-// additionally goes to the workgroup's slice of a global tape (one region of ru16(bond) x T doubles per bond, in the LDS tile's own
-// element order); the slice is written once and read once, by this workgroup only.
+// Phase A is the taped inward walk and the centre of chain_common.h (chain_walk_taped, chain_centre_taped; their order is stated
+// there): k_chain's walk, so that weights and pred are bit for bit those of k_chain<double>, with every chain vector also written to
+// the workgroup's slice of a global tape (ChainTape); the slice is written once and read once, by this workgroup only.
 //
 // Centre.  l_n = which[n], or pred[n] when which is null.  For every label l that some image of the tile has chosen, the columns of
 // those images take
@@ -117,7 +116,6 @@ static __device__ __forceinline__ void resp_step(const double* __restrict__ A, i
 
 template <int NCT, int SRC>
 __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
-    typedef ChainT<double> Tr;
     constexpr int T = 16 * NCT;
     extern __shared__ __attribute__((aligned(16))) unsigned char rs_lds_raw[];
     double* const lds = reinterpret_cast<double*>(rs_lds_raw);
@@ -129,12 +127,9 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
     double* const redb = lds + 2 * tile_elems;                         // [2][CHAIN_WAVES][2][T]
     int* const lsel = reinterpret_cast<int*>(redb + 2 * CHAIN_WAVES * 2 * T);     // [T], then the set of chosen labels
     int* const lmask = lsel + T;
-    const int N = ch.N, cs = ch.cs, nright = N - cs;
-    // the tape of this workgroup: the vector on bond b (between sites b and b + 1; b = 0 and b = N: the 1 that starts a chain) at
-    // rowoff[b] rows: L_b for b < cs, R_{b+1} for b >= cs; then X and Y of the centre at rowoff[N + 1], rowoff[N + 2]
-    double* const tp = g.tape + (size_t)blockIdx.x * g.rowoff[N + 3] * T;
-    auto bond = [&](int b) { return tp + (size_t)g.rowoff[b] * T; };
-    auto copy_rows = [&](const double* src, double* dst, int rows) { for (int i = tid; i < rows * T; i += CHAIN_THREADS) dst[i] = src[i]; };
+    const int N = ch.N, cs = ch.cs;
+    // the inward tape of this workgroup (chain_common.h), then X and Y of the centre at rowoff[N + 1], rowoff[N + 2]
+    const ChainTape<T> tape{g.tape + (size_t)blockIdx.x * g.rowoff[N + 3] * T, g.rowoff};
     // the block of wave sums of the step before -> resp[j][s] of the columns that chose l (lsel null: all)
     auto finish = [&](const double* red, int j, bool all, int l) {
         if (tid < 2 * T) {
@@ -147,64 +142,24 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
         }
     };
 
-    // ---- phase A: k_chain's walk, every chain vector also to the tape ----
-    auto site_at = [&](int t) { return t < nright ? N - t : (t < N - 1 ? t - nright + 1 : cs); };
+    // ---- phase A: k_chain's walk and centre, every chain vector also to the tape (chain_common.h) ----
     double p0[NCT], p1[NCT], q0[NCT], q1[NCT];
-    const int img0 = tile0 + (lane & 15);
-    chain_features<double, NCT, SRC>(ch, site_at(0), img0, p0, p1);
-    double* const park = bond(cs);                                     // R_{cs+1}
-    if (tid < T) {
-        const int at = Tr::template idx<NCT>(0, tid);
-        buf[0][at] = 1; bond(N)[at] = 1; bond(0)[at] = 1;
-    }
-    if (tid == 0) *lmask = 0;
-    __syncthreads();
-    int cur = 0;
-    for (int t = 0; t < N - 1; ++t) {
-        const int j = site_at(t);
-        chain_features<double, NCT, SRC>(ch, site_at(t + 1), img0, q0, q1);
-        const ChainSite<double> st = ch.sites[j - 1];
-        const bool right = t < nright, last = t == nright - 1;
-        if (right) {
-            chain_step<double, NCT, false>(st.a, st.ml, st.mr, buf[cur], last ? park : buf[cur ^ 1], p0, p1, wave, lane);
-            if (last) { if (tid < T) buf[cur ^ 1][Tr::template idx<NCT>(0, tid)] = 1; }        // the left chain starts from 1
-        } else {
-            chain_step<double, NCT, true>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
-        }
-        cur ^= 1;
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) { p0[ct] = q0[ct]; p1[ct] = q1[ct]; }
-        __syncthreads();
-        if (!last) copy_rows(buf[cur], right ? bond(j - 1) : bond(j), right ? st.ml : st.mr);  // R_j on bond j-1, L_j on bond j
-    }
-    // centre site as k_chain has it; p0, p1 are the centre's features from here on
+    const int img0 = tile0 + (lane & 15), img = tile0 + tid;
+    if (tid == 0) *lmask = 0;                                          // (ahead of the walk: behind it the kernel measured 0.6 % slower)
+    int cur = chain_walk_taped<NCT, SRC>(ch, buf, tape, p0, p1, tile0, tid);
+    double* const park = tape.bond(cs);                                // R_{cs+1}
+    const int pr = chain_centre_taped<NCT>(ch, buf, cur, park, p0, p1, tile0, tid, [](int, double, int, int) {});
     const ChainSite<double> sc = ch.sites[cs - 1];
     const size_t lstride = (size_t)sc.ml * 2 * sc.mr;
-    const int img = tile0 + tid;
-    double best = 0, w0 = 0; int arg = 0;
-    for (int l = 0; l < ch.nl; ++l) {
-        chain_step<double, NCT, true>(sc.a + l * lstride, sc.ml, sc.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
-        __syncthreads();
-        if (tid < T && img < ch.cnt) {
-            double w = 0;
-            for (int r = 0; r < sc.mr; ++r) w = Tr::fma(buf[cur ^ 1][Tr::template idx<NCT>(r, tid)], park[Tr::template idx<NCT>(r, tid)], w);
-            ch.wout[(size_t)img * ch.nl + l] = (double)w;
-            const double wa = Tr::abs(w);
-            if (l == 0) { best = wa; w0 = w; } else if (wa > best) { best = wa; arg = l; }      // first maximum of |W_l| (util.h:42-57)
-        }
-        __syncthreads();
-    }
     if (tid < T) {
         int ln = -1;
         if (img < ch.cnt) {
-            const int pr = ch.single ? (w0 > 0.5 ? 1 : 0) : arg;
-            ch.pred[img] = pr;
             ln = ch.single ? 0 : (g.which ? g.which[img] : pr);
             atomicOr(lmask, 1 << ln);                                  // an LDS integer
         }
         lsel[tid] = ln;
     }
-    copy_rows(park, buf[cur ^ 1], sc.mr);                              // R into the free tile: the operand of the right-type product
+    chain_copy_rows<T>(park, buf[cur ^ 1], sc.mr, tid);                // R into the free tile: the operand of the right-type product
     __syncthreads();
     const int mask = *lmask;
     if (tid < T && lsel[tid] < 0) lsel[tid] = __ffs(mask) - 1;         // columns beyond the chunk (all zero) ride with the first chosen label
@@ -215,12 +170,12 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
     for (int l = 0; l < ch.nl; ++l) {
         if (!((mask >> l) & 1)) continue;
         double* const red = redb + (size_t)par * CHAIN_WAVES * 2 * T;
-        resp_step<NCT, true>(sc.a + l * lstride, sc.ml, sc.mr, buf[cur], park, bond(N + 2), p0, p1, lsel, l, red, wave, lane);
+        resp_step<NCT, true>(sc.a + l * lstride, sc.ml, sc.mr, buf[cur], park, tape.bond(N + 2), p0, p1, lsel, l, red, wave, lane);
         __syncthreads();
         finish(red, cs, false, l);
         par ^= 1;
         if (cs > 1) {                                                  // (its dot with L would give resp[cs] once more: not stored)
-            resp_step<NCT, false>(sc.a + l * lstride, sc.ml, sc.mr, buf[cur ^ 1], bond(cs - 1), bond(N + 1), p0, p1, lsel, l, redb + (size_t)par * CHAIN_WAVES * 2 * T, wave, lane);
+            resp_step<NCT, false>(sc.a + l * lstride, sc.ml, sc.mr, buf[cur ^ 1], tape.bond(cs - 1), tape.bond(N + 1), p0, p1, lsel, l, redb + (size_t)par * CHAIN_WAVES * 2 * T, wave, lane);
             __syncthreads();
             par ^= 1;
         }
@@ -228,7 +183,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
 
     // ---- phase B, left of the centre: j = cs-1 .. 1 ----
     if (cs > 1) {
-        copy_rows(bond(N + 1), buf[0], sc.ml);
+        chain_copy_rows<T>(tape.bond(N + 1), buf[0], sc.ml, tid);
         chain_features<double, NCT, SRC>(ch, cs - 1, img0, p0, p1);
         __syncthreads();
         cur = 0;
@@ -236,7 +191,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
             if (j > 1) chain_features<double, NCT, SRC>(ch, j - 1, img0, q0, q1);
             const ChainSite<double> st = ch.sites[j - 1];
             double* const red = redb + (size_t)par * CHAIN_WAVES * 2 * T;
-            resp_step<NCT, false>(st.a, st.ml, st.mr, buf[cur], bond(j - 1), buf[cur ^ 1], p0, p1, nullptr, 0, red, wave, lane);
+            resp_step<NCT, false>(st.a, st.ml, st.mr, buf[cur], tape.bond(j - 1), buf[cur ^ 1], p0, p1, nullptr, 0, red, wave, lane);
             __syncthreads();
             finish(red, j, true, 0);
             par ^= 1; cur ^= 1;
@@ -247,7 +202,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
     // ---- phase B, right of the centre: j = cs+1 .. N ----
     if (cs < N) {
         __syncthreads();                                               // the tiles are free: every wave has left the loop above
-        copy_rows(bond(N + 2), buf[0], sc.mr);
+        chain_copy_rows<T>(tape.bond(N + 2), buf[0], sc.mr, tid);
         chain_features<double, NCT, SRC>(ch, cs + 1, img0, p0, p1);
         __syncthreads();
         cur = 0;
@@ -255,7 +210,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
             if (j < N) chain_features<double, NCT, SRC>(ch, j + 1, img0, q0, q1);
             const ChainSite<double> st = ch.sites[j - 1];
             double* const red = redb + (size_t)par * CHAIN_WAVES * 2 * T;
-            resp_step<NCT, true>(st.a, st.ml, st.mr, buf[cur], bond(j), buf[cur ^ 1], p0, p1, nullptr, 0, red, wave, lane);
+            resp_step<NCT, true>(st.a, st.ml, st.mr, buf[cur], tape.bond(j), buf[cur ^ 1], p0, p1, nullptr, 0, red, wave, lane);
             __syncthreads();
             finish(red, j, true, 0);
             par ^= 1; cur ^= 1;
@@ -277,35 +232,14 @@ __global__ __launch_bounds__(256) void k_response_transpose(const double* __rest
         if (n0 + i < cnt && r0 + tx < rows) out[(size_t)(n0 + i) * rows + r0 + tx] = tile[tx][i];
 }
 
-size_t response_lds_bytes(int mcap, int T) {
-    return ((size_t)2 * mcap * T + (size_t)2 * CHAIN_WAVES * 2 * T) * sizeof(double) + (size_t)(T + 1) * sizeof(int);
-}
-
-// a.ch.mcap and the grid follow from T; tape_rows: the rows of a workgroup's slice the workspace was sized for (>= a.rowoff[N + 3] on the device,
-// whose host value is rows)
+// a.ch.mcap and the grid follow from T; rows: the rows of a workgroup's slice (a.rowoff[N + 3] on the device) as the host knows them
 int launch_response(tnml_ctx* c, RespArgs a, int maxbond, int T, int rows, size_t tape_elems, double* outT) {
-    if (maxbond < 1 || maxbond > TNML_CHAIN_MAXM) return tnml_fail(c, "response kernel: bond dimension %d outside 1..%d", maxbond, TNML_CHAIN_MAXM);
-    if (a.ch.cnt < 1 || a.ch.cnt > a.ch.ld) return tnml_fail(c, "response kernel: %d images in a chunk of %d", a.ch.cnt, a.ch.ld);
-    if (T != 64 && T != 32 && T != 16) return tnml_fail(c, "response kernel: tile width %d", T);
-    a.ch.mcap = (maxbond + 15) / 16 * 16;
-    a.ch.park = nullptr;
-    const int grid = (a.ch.cnt + T - 1) / T;
-    const size_t lds = response_lds_bytes(a.ch.mcap, T);
-    if (lds > TNML_CHAIN_LDS) return tnml_fail(c, "response kernel: two tiles of %d x %d do not fit the LDS", a.ch.mcap, T);
-    if ((size_t)grid * T * rows > tape_elems) return tnml_fail(c, "response kernel: tape of %zu doubles too small for %d tiles of %d x %d", tape_elems, grid, rows, T);
-    const bool codes = a.ch.codeT != nullptr;
-    if (codes && !a.ch.table) return tnml_fail(c, "response kernel: block sums without a table");
     typedef void (*kern_t)(const RespArgs);
     static const kern_t kern[2][3] = {{k_response<1, 0>, k_response<2, 0>, k_response<4, 0>}, {k_response<1, 1>, k_response<2, 1>, k_response<4, 1>}};   // [SRC][T / 32]
-    bool& attr = c->attr_response[codes];
-    if (!attr) {
-        for (kern_t fn : kern[codes])
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, TNML_CHAIN_LDS) != hipSuccess)
-                return tnml_fail(c, "response kernel: hipFuncSetAttribute failed");
-        attr = true;
-    }
+    TapedLaunch L;                                                     // beside the two tiles: the wave sums [2][8][2][T], l_n [T] and the set of chosen labels
+    TCK(taped_launch(c, "response kernel", "tape", a.ch, maxbond, T, rows, tape_elems, (size_t)2 * CHAIN_WAVES * 2 * T * sizeof(double) + (size_t)(T + 1) * sizeof(int), kern, c->attr_response, &L));
     ProfScope ps(c, KC_SITE_RESP);
-    hipLaunchKernelGGL(kern[codes][T / 32], dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
+    hipLaunchKernelGGL(kern[L.codes][T / 32], dim3(L.grid), dim3(CHAIN_THREADS), L.lds, c->stream, a);
     HIPCK(c, hipGetLastError());
     const int rows2 = 2 * a.ch.N;
     hipLaunchKernelGGL(k_response_transpose, dim3((a.ch.cnt + 31) / 32, (rows2 + 31) / 32), dim3(256), 0, c->stream, a.resp, rows2, a.ch.cnt, a.ch.ld, outT);

@@ -11,10 +11,10 @@
 // and carried outward by X_{j-1} = (phi_j A_j) X_j, Y_j = Y_{j-1} (phi_j A_j).  Two launches per chunk.
 //
 // 1. k_site_backward (class site_bwd): one workgroup (8 waves) per tile of T = 64 / 32 / 16 images (chain_tile<double>), two walks.
-//    Phase A is k_response's, call for call: k_chain's walk, so that weights and pred are bit for bit those of k_chain<double>, with
-//    every chain vector also written to the workgroup's slice of a tape (one region of ru16(bond) x T doubles per bond b = 0..N, in the
-//    LDS tile's element order ChainT<double>::idx<NCT>; L_b for b < c, R_{b+1} for b >= c, the two ends holding the 1 that starts a chain).
-//    Centre: the coefficients of the tile go to LDS [nl][T] -- given (coef), or formed from the weight just computed as
+//    Phase A is k_response's, the same code: the taped inward walk and the centre of chain_common.h (chain_walk_taped,
+//    chain_centre_taped; their order and the tape's layout, ChainTape, are stated there), so that weights and pred are bit for bit
+//    those of k_chain<double>.
+//    Centre: the coefficients of the tile go to LDS [nl][T] (the per-label hook of chain_centre_taped) -- given (coef), or formed from the weight just computed as
 //    c_nl = 2 (W_l(x_n) - y_nl) (labels; y as tnml_evaluate_*: [l == label_n], per-label variant [label_n == target]) and written to the
 //    [C][nl] buffer the GEMM reads; columns beyond the chunk get 0.  The seeds are chain steps over the compound index (l, s, r):
 //    operand fl(fl(c_nl phi_s) R[r]) (resp. L[a]), accumulated by v_mfma_f64_16x16x4_f64 with l ascending and, inside a label, the k
@@ -94,9 +94,36 @@ static __device__ __forceinline__ void seed_step(const double* __restrict__ A, s
     }
 }
 
+// One outward walk from the seed on the second tape with chain_step itself, every vector to the second tape.  LEFT is chain_step's:
+// false carries X left of the centre (seed of seed_rows on bond cs-1; site j = cs-1 .. 2 writes bond j-1), true carries Y right of it
+// (seed on bond cs; site j = cs+1 .. N-1 writes bond j).  Opens with a barrier: the seeds are written, the tiles free.
+template <int NCT, int SRC, bool LEFT>
+static __device__ __forceinline__ void carry_outward(const ChainArgs<double>& ch, double* const (&buf)[2], const ChainTape<16 * NCT>& tape2, int seed_rows,
+                                                     double (&p0)[NCT], double (&p1)[NCT], int tile0, int tid) {
+    constexpr int T = 16 * NCT, D = LEFT ? 1 : -1;
+    const int lane = tid & 63, wave = tid >> 6, img0 = tile0 + (lane & 15);
+    const int N = ch.N, cs = ch.cs;
+    if (LEFT ? cs >= N - 1 : cs <= 2) return;
+    double q0[NCT], q1[NCT];
+    __syncthreads();
+    chain_copy_rows<T>(tape2.bond(LEFT ? cs : cs - 1), buf[0], seed_rows, tid);
+    chain_features<double, NCT, SRC>(ch, cs + D, img0, p0, p1);
+    __syncthreads();
+    int cur = 0;
+    for (int j = cs + D; LEFT ? j <= N - 1 : j >= 2; j += D) {
+        chain_features<double, NCT, SRC>(ch, j + D, img0, q0, q1);
+        const ChainSite<double> st = ch.sites[j - 1];
+        chain_step<double, NCT, LEFT>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
+        cur ^= 1;
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) { p0[ct] = q0[ct]; p1[ct] = q1[ct]; }
+        __syncthreads();
+        chain_copy_rows<T>(buf[cur], tape2.bond(LEFT ? j : j - 1), LEFT ? st.mr : st.ml, tid);
+    }
+}
+
 template <int NCT, int SRC>
 __global__ __launch_bounds__(CHAIN_THREADS) void k_site_backward(const SiteGradArgs g) {
-    typedef ChainT<double> Tr;
     constexpr int T = 16 * NCT;
     extern __shared__ __attribute__((aligned(16))) unsigned char sg_lds_raw[];
     double* const lds = reinterpret_cast<double*>(sg_lds_raw);
@@ -106,116 +133,41 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_site_backward(const SiteGradA
     const size_t tile_elems = (size_t)ch.mcap * T;
     double* buf[2] = {lds, lds + tile_elems};
     double* const cl = lds + 2 * tile_elems;                           // [nl][T] coefficients of the tile
-    const int N = ch.N, cs = ch.cs, nright = N - cs;
+    const int N = ch.N, cs = ch.cs;
     const size_t slice = (size_t)blockIdx.x * g.rowoff[N + 1] * T;
-    double* const tp = g.tape + slice;                                 // inward vectors: L_b (b < cs), R_{b+1} (b >= cs) on bond b
-    double* const tq = g.tape2 + slice;                                // outward vectors: X_b (b < cs), Y_b (b >= cs) on bond b
-    auto bond = [&](int b) { return tp + (size_t)g.rowoff[b] * T; };
-    auto bond2 = [&](int b) { return tq + (size_t)g.rowoff[b] * T; };
-    auto copy_rows = [&](const double* src, double* dst, int rows) { for (int i = tid; i < rows * T; i += CHAIN_THREADS) dst[i] = src[i]; };
+    const ChainTape<T> tape{g.tape + slice, g.rowoff};                 // inward vectors (chain_common.h)
+    const ChainTape<T> tape2{g.tape2 + slice, g.rowoff};               // outward vectors: X_b (b < cs), Y_b (b >= cs) on bond b
 
-    // ---- phase A: k_chain's walk as k_response has it, every chain vector also to the tape ----
-    auto site_at = [&](int t) { return t < nright ? N - t : (t < N - 1 ? t - nright + 1 : cs); };
-    double p0[NCT], p1[NCT], q0[NCT], q1[NCT];
-    const int img0 = tile0 + (lane & 15);
-    chain_features<double, NCT, SRC>(ch, site_at(0), img0, p0, p1);
-    double* const park = bond(cs);                                     // R_{cs+1}
-    if (tid < T) {
-        const int at = Tr::template idx<NCT>(0, tid);
-        buf[0][at] = 1; bond(N)[at] = 1; bond(0)[at] = 1;
-    }
-    __syncthreads();
-    int cur = 0;
-    for (int t = 0; t < N - 1; ++t) {
-        const int j = site_at(t);
-        chain_features<double, NCT, SRC>(ch, site_at(t + 1), img0, q0, q1);
-        const ChainSite<double> st = ch.sites[j - 1];
-        const bool right = t < nright, last = t == nright - 1;
-        if (right) {
-            chain_step<double, NCT, false>(st.a, st.ml, st.mr, buf[cur], last ? park : buf[cur ^ 1], p0, p1, wave, lane);
-            if (last) { if (tid < T) buf[cur ^ 1][Tr::template idx<NCT>(0, tid)] = 1; }        // the left chain starts from 1
-        } else {
-            chain_step<double, NCT, true>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
+    // ---- phase A: k_chain's walk and centre, every chain vector also to the tape (chain_common.h).  The coefficients of the tile go to cl. ----
+    double p0[NCT], p1[NCT];
+    int cur = chain_walk_taped<NCT, SRC>(ch, buf, tape, p0, p1, tile0, tid);
+    double* const park = tape.bond(cs);                                // R_{cs+1}
+    chain_centre_taped<NCT>(ch, buf, cur, park, p0, p1, tile0, tid, [&](int l, double w, int col, int img) {
+        double cv = 0;
+        if (img < ch.cnt) {
+            if (g.lab) {
+                const int lb = g.lab[img];
+                const double y = (ch.single ? lb == g.target : lb == l) ? 1. : 0.;
+                cv = 2. * (w - y);
+                g.coef[(size_t)img * ch.nl + l] = cv;
+            } else {
+                cv = g.coef[(size_t)img * ch.nl + l];
+            }
         }
-        cur ^= 1;
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) { p0[ct] = q0[ct]; p1[ct] = q1[ct]; }
-        __syncthreads();
-        if (!last) copy_rows(buf[cur], right ? bond(j - 1) : bond(j), right ? st.ml : st.mr);  // R_j on bond j-1, L_j on bond j
-    }
-    // centre site as k_chain has it; p0, p1 are the centre's features from here on.  The coefficients of the tile go to cl.
+        cl[l * T + col] = cv;
+    });
     const ChainSite<double> sc = ch.sites[cs - 1];
     const size_t lstride = (size_t)sc.ml * 2 * sc.mr;
-    const int img = tile0 + tid;
-    double best = 0, w0 = 0; int arg = 0;
-    for (int l = 0; l < ch.nl; ++l) {
-        chain_step<double, NCT, true>(sc.a + l * lstride, sc.ml, sc.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
-        __syncthreads();
-        if (tid < T) {
-            double cv = 0;
-            if (img < ch.cnt) {
-                double w = 0;
-                for (int r = 0; r < sc.mr; ++r) w = Tr::fma(buf[cur ^ 1][Tr::template idx<NCT>(r, tid)], park[Tr::template idx<NCT>(r, tid)], w);
-                ch.wout[(size_t)img * ch.nl + l] = w;
-                const double wa = Tr::abs(w);
-                if (l == 0) { best = wa; w0 = w; } else if (wa > best) { best = wa; arg = l; }      // first maximum of |W_l| (util.h:42-57)
-                if (g.lab) {
-                    const int lb = g.lab[img];
-                    const double y = (ch.single ? lb == g.target : lb == l) ? 1. : 0.;
-                    cv = 2. * (w - y);
-                    g.coef[(size_t)img * ch.nl + l] = cv;
-                } else {
-                    cv = g.coef[(size_t)img * ch.nl + l];
-                }
-            }
-            cl[l * T + tid] = cv;
-        }
-        __syncthreads();
-    }
-    if (tid < T && img < ch.cnt) ch.pred[img] = ch.single ? (w0 > 0.5 ? 1 : 0) : arg;
-    copy_rows(park, buf[cur ^ 1], sc.mr);                              // R into the free tile: the operand of the right-type seed
+    chain_copy_rows<T>(park, buf[cur ^ 1], sc.mr, tid);                // R into the free tile: the operand of the right-type seed
     __syncthreads();
 
     // ---- centre: the seeds X_{cs-1} (second tape, bond cs-1) and Y_cs (bond cs) ----
-    if (cs > 1) seed_step<NCT, false>(sc.a, lstride, ch.nl, sc.ml, sc.mr, buf[cur ^ 1], bond2(cs - 1), p0, p1, cl, wave, lane);
-    if (cs < N) seed_step<NCT, true>(sc.a, lstride, ch.nl, sc.ml, sc.mr, buf[cur], bond2(cs), p0, p1, cl, wave, lane);
+    if (cs > 1) seed_step<NCT, false>(sc.a, lstride, ch.nl, sc.ml, sc.mr, buf[cur ^ 1], tape2.bond(cs - 1), p0, p1, cl, wave, lane);
+    if (cs < N) seed_step<NCT, true>(sc.a, lstride, ch.nl, sc.ml, sc.mr, buf[cur], tape2.bond(cs), p0, p1, cl, wave, lane);
 
-    // ---- phase B, left of the centre: X_{j-1} = (phi_j A_j) X_j, j = cs-1 .. 2 ----
-    if (cs > 2) {
-        __syncthreads();                                               // the seeds are written, the tiles free
-        copy_rows(bond2(cs - 1), buf[0], sc.ml);
-        chain_features<double, NCT, SRC>(ch, cs - 1, img0, p0, p1);
-        __syncthreads();
-        cur = 0;
-        for (int j = cs - 1; j >= 2; --j) {
-            chain_features<double, NCT, SRC>(ch, j - 1, img0, q0, q1);
-            const ChainSite<double> st = ch.sites[j - 1];
-            chain_step<double, NCT, false>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
-            cur ^= 1;
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) { p0[ct] = q0[ct]; p1[ct] = q1[ct]; }
-            __syncthreads();
-            copy_rows(buf[cur], bond2(j - 1), st.ml);
-        }
-    }
-    // ---- phase B, right of the centre: Y_j = Y_{j-1} (phi_j A_j), j = cs+1 .. N-1 ----
-    if (cs < N - 1) {
-        __syncthreads();
-        copy_rows(bond2(cs), buf[0], sc.mr);
-        chain_features<double, NCT, SRC>(ch, cs + 1, img0, p0, p1);
-        __syncthreads();
-        cur = 0;
-        for (int j = cs + 1; j <= N - 1; ++j) {
-            chain_features<double, NCT, SRC>(ch, j + 1, img0, q0, q1);
-            const ChainSite<double> st = ch.sites[j - 1];
-            chain_step<double, NCT, true>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
-            cur ^= 1;
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) { p0[ct] = q0[ct]; p1[ct] = q1[ct]; }
-            __syncthreads();
-            copy_rows(buf[cur], bond2(j), st.mr);
-        }
-    }
+    // ---- phase B: X_{j-1} = (phi_j A_j) X_j, j = cs-1 .. 2, then Y_j = Y_{j-1} (phi_j A_j), j = cs+1 .. N-1 ----
+    carry_outward<NCT, SRC, false>(ch, buf, tape2, sc.ml, p0, p1, tile0, tid);
+    carry_outward<NCT, SRC, true>(ch, buf, tape2, sc.mr, p0, p1, tile0, tid);
 }
 
 // ---- the GEMM over the image index ----
@@ -329,42 +281,22 @@ __global__ __launch_bounds__(SG_THREADS) void k_site_grad(const SiteGradArgs g) 
         }
 }
 
-size_t sitegrad_lds_bytes(int mcap, int T, int nl) {
-    return ((size_t)2 * mcap * T + (size_t)nl * T) * sizeof(double);
-}
-
 // a.ch.mcap and the grids follow from T; rows: a.rowoff[N + 1] as the host knows it; tape_elems: doubles behind each of the two tapes;
 // nblocks: a.blk0[N - 1 + nl] as the host knows it
 int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int rows, size_t tape_elems, int nblocks) {
-    if (maxbond < 1 || maxbond > TNML_CHAIN_MAXM) return tnml_fail(c, "site gradient kernel: bond dimension %d outside 1..%d", maxbond, TNML_CHAIN_MAXM);
-    if (a.ch.cnt < 1 || a.ch.cnt > a.ch.ld) return tnml_fail(c, "site gradient kernel: %d images in a chunk of %d", a.ch.cnt, a.ch.ld);
-    if (T != 64 && T != 32 && T != 16) return tnml_fail(c, "site gradient kernel: tile width %d", T);
     if (nblocks < 1) return tnml_fail(c, "site gradient kernel: %d output blocks", nblocks);
-    a.ch.mcap = (maxbond + 15) / 16 * 16;
-    a.ch.park = nullptr;
-    const int grid = (a.ch.cnt + T - 1) / T;
-    const size_t lds = sitegrad_lds_bytes(a.ch.mcap, T, a.ch.nl);
-    if (lds > TNML_CHAIN_LDS) return tnml_fail(c, "site gradient kernel: two tiles of %d x %d do not fit the LDS", a.ch.mcap, T);
-    if ((size_t)grid * T * rows > tape_elems) return tnml_fail(c, "site gradient kernel: tapes of %zu doubles too small for %d tiles of %d x %d", tape_elems, grid, rows, T);
-    const bool codes = a.ch.codeT != nullptr;
-    if (codes && !a.ch.table) return tnml_fail(c, "site gradient kernel: block sums without a table");
     typedef void (*kern_t)(const SiteGradArgs);
     static const kern_t bwd[2][3] = {{k_site_backward<1, 0>, k_site_backward<2, 0>, k_site_backward<4, 0>}, {k_site_backward<1, 1>, k_site_backward<2, 1>, k_site_backward<4, 1>}};   // [SRC][T / 32]
     static const kern_t gemm[2][3] = {{k_site_grad<1, 0>, k_site_grad<2, 0>, k_site_grad<4, 0>}, {k_site_grad<1, 1>, k_site_grad<2, 1>, k_site_grad<4, 1>}};
-    bool& attr = c->attr_sitegrad[codes];
-    if (!attr) {
-        for (kern_t fn : bwd[codes])
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, TNML_CHAIN_LDS) != hipSuccess)
-                return tnml_fail(c, "site gradient kernel: hipFuncSetAttribute failed");
-        attr = true;
-    }
+    TapedLaunch L;                                                     // beside the two tiles: the coefficients [nl][T]
+    TCK(taped_launch(c, "site gradient kernel", "tapes", a.ch, maxbond, T, rows, tape_elems, (size_t)a.ch.nl * T * sizeof(double), bwd, c->attr_sitegrad, &L));
     {
         ProfScope ps(c, KC_SITE_BWD);
-        hipLaunchKernelGGL(bwd[codes][T / 32], dim3(grid), dim3(CHAIN_THREADS), lds, c->stream, a);
+        hipLaunchKernelGGL(bwd[L.codes][T / 32], dim3(L.grid), dim3(CHAIN_THREADS), L.lds, c->stream, a);
         HIPCK(c, hipGetLastError());
     }
     ProfScope ps(c, KC_SITE_GRAD);
-    hipLaunchKernelGGL(gemm[codes][T / 32], dim3(nblocks), dim3(SG_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(gemm[L.codes][T / 32], dim3(nblocks), dim3(SG_THREADS), 0, c->stream, a);
     HIPCK(c, hipGetLastError());
     return 0;
 }

@@ -60,8 +60,8 @@ int tnml_set_input_map(tnml_ctx* c, const tnml_input_map* m) {
     }
     HIPCK(c, hipSetDevice(c->cfg.device));
     if (c->pk_map_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); predict_release_map(c); }
-    if (c->rs_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); response_release(c); }
-    if (c->sg_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); sitegrad_release(c); }
+    if (c->rs.bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); response_release(c); }
+    if (c->sg.bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); sitegrad_release(c); }
     if (!m) { c->im_set = false; c->im = tnml_input_map{}; c->im_table.clear(); return 0; }
     c->im_table.assign(m->table, m->table + (size_t)2 * m->ncodes);
     c->im = *m; c->im.table = nullptr;

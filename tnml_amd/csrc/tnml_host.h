@@ -96,10 +96,11 @@ int env_init_impl(tnml_ctx* c);
 int shift_env_impl(tnml_ctx* c, int b, int from_left);
 
 // ---- tnml_infer.hip ---------------------------------------------------------------------------
-void predict_release_map(tnml_ctx* c);
+// the streamed workspaces (tnml_ctx::pk, rs, sg with the fields beside them); synchronise first
+void predict_release_map(tnml_ctx* c);                 // of tnml_predict_*, the part that follows the input map
 void predict_release(tnml_ctx* c);
-void response_release(tnml_ctx* c);                    // the workspace of tnml_response_* (synchronise first)
-void sitegrad_release(tnml_ctx* c);                    // the workspace of tnml_site_gradient_* (synchronise first)
+void response_release(tnml_ctx* c);
+void sitegrad_release(tnml_ctx* c);
 
 // ---- tnml_bond.hip ----------------------------------------------------------------------------
 PackDesc bond_pack_desc(const BondPlan& p);

@@ -74,76 +74,187 @@ int tnml_classify(tnml_ctx* c, double* weights, int32_t* pred, int64_t count[TNM
     return 0;
 }
 
-// ---- streamed inference: images the context does not hold (util.h:19-40 toverlap + argmax, util.h:42-57) ----------
-// The host loop cuts the n images into chunks of option predict_chunk; a chunk is staged (copy + one transposing pre-kernel), contracted by
-// ONE k_chain launch (kernels_chain.hip) and copied back.  Reads W only: no training data, environment, bond plan, P or p_valid is touched,
-// no collective is entered.  The workspace is allocated by the first call (see tnml.h for its size) and lives until tnml_destroy.
-// the workspace of tnml_predict_u8 under a map follows the map: released here, re-made by the next such call
-void predict_release_map(tnml_ctx* c) {
-    void** slots[] = {(void**)&c->pk_mraw, (void**)&c->pk_codes, (void**)&c->pk_mtab};
-    for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (c->pk_mtab32) {                                   // (the fp32 copy of the table: 8 ncodes bytes)
-        (void)hipFree(c->pk_mtab32); c->pk_mtab32 = nullptr;
-        c->pk_map_bytes += c->pk_mtab32_bytes; c->pk_mtab32_bytes = 0;
-    }
-    c->bytes -= c->pk_map_bytes; c->pk_bytes -= c->pk_map_bytes;
-    c->pk_map_bytes = 0;
-}
-void predict_release(tnml_ctx* c) {
-    void** slots[] = {(void**)&c->pk_tab, (void**)&c->pk_w, (void**)&c->pk_pred, (void**)&c->pk_park, (void**)&c->pk_raw8, (void**)&c->pk_x8, (void**)&c->pk_rawphi, (void**)&c->pk_xphi,
-                      (void**)&c->pk_w32, (void**)&c->pk_tab32, (void**)&c->pk_flag, (void**)&c->pk_xphi32, (void**)&c->pk_lab, (void**)&c->pk_acc};
-    for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    c->pk_w32_cap = 0;
-    predict_release_map(c);
-    c->bytes -= c->pk_bytes;
-    c->pk_bytes = 0; c->pk_cap = 0; c->pk_park_elems = 0;
-}
-static int predict_alloc(tnml_ctx* c, void** p, size_t bytes) {
+// ---- streamed calls: images the context does not hold (util.h:19-40 toverlap + argmax, util.h:42-57) ----------
+// tnml_predict_* / tnml_evaluate_*, tnml_response_* and tnml_site_gradient_* cut the n images into chunks of their chunk option; a chunk is
+// staged (copy + the input map's block sums or one transposing pre-kernel), contracted by the call's own launches and copied back, with one
+// synchronisation per chunk.  They read W only: no training data, environment, bond plan, P or p_valid is touched, no collective is entered.
+// Each has a workspace of its own (a StreamWs and the fields beside it in tnml_ctx; tnml.h has the sizes), allocated by its first call; what
+// the three share is written once, here.
+static int ws_alloc(tnml_ctx* c, StreamWs& s, void** p, size_t bytes) {
     TCK(dalloc(c, p, bytes));
-    c->pk_bytes += (int64_t)bytes;
+    s.bytes += (int64_t)bytes;
     return 0;
 }
-static int predict_workspace(tnml_ctx* c, bool bytes_form, bool f32) {
-    const int cap = (c->predict_chunk + 63) / 64 * 64;
-    if (c->pk_cap != cap) {                               // first call, or option predict_chunk has changed since
-        if (c->pk_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); predict_release(c); }
-        const size_t mc = (size_t)(std::min(c->maxm, TNML_CHAIN_MAXM) + 15) / 16 * 16;
-        int rc = predict_alloc(c, (void**)&c->pk_tab, (size_t)c->N * sizeof(ChainSite<double>));
-        if (!rc) rc = predict_alloc(c, (void**)&c->pk_w, (size_t)cap * c->nl() * sizeof(double));
-        if (!rc) rc = predict_alloc(c, (void**)&c->pk_pred, (size_t)cap * sizeof(int));
-        if (!rc) rc = predict_alloc(c, (void**)&c->pk_park, (size_t)cap * mc * sizeof(double));
-        if (rc) { predict_release(c); return rc; }
-        c->pk_park_elems = (size_t)cap * mc;
-        c->pk_cap = cap;
-    }
-    int rc = 0;
-    if (bytes_form && c->im_set) {                        // S C + 2 N C + 16 ncodes: bytes as given, block sums site-first, the fp64 table
-        if (c->pk_codes) return 0;
+// frees the shared buffers and `slots`, the buffers that this workspace alone has (synchronise first); the caller clears the sizes that go with them
+static void ws_release(tnml_ctx* c, StreamWs& s, std::vector<void**> slots) {
+    for (void** p : {(void**)&s.tab, (void**)&s.w, (void**)&s.pred, (void**)&s.raw8, (void**)&s.x8, (void**)&s.rawphi, (void**)&s.xphi, (void**)&s.mraw, (void**)&s.codes, (void**)&s.mtab})
+        slots.push_back(p);
+    for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    c->bytes -= s.bytes;
+    s.bytes = 0; s.cap = 0;
+}
+// the part of the predict workspace that follows the input map: released by tnml_set_input_map, re-made by the next tnml_predict_u8 under a map
+void predict_release_map(tnml_ctx* c) {
+    for (void** p : {(void**)&c->pk.mraw, (void**)&c->pk.codes, (void**)&c->pk.mtab, (void**)&c->pk_mtab32}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    const int64_t freed = c->pk_map_bytes + c->pk_mtab32_bytes;        // (the fp32 copy of the table: 8 ncodes bytes)
+    c->bytes -= freed; c->pk.bytes -= freed;
+    c->pk_map_bytes = 0; c->pk_mtab32_bytes = 0;
+}
+void predict_release(tnml_ctx* c) {
+    ws_release(c, c->pk, {(void**)&c->pk_park, (void**)&c->pk_w32, (void**)&c->pk_tab32, (void**)&c->pk_flag, (void**)&c->pk_xphi32, (void**)&c->pk_mtab32, (void**)&c->pk_lab, (void**)&c->pk_acc});
+    c->pk_w32_cap = 0; c->pk_park_elems = 0; c->pk_map_bytes = 0; c->pk_mtab32_bytes = 0;
+}
+void response_release(tnml_ctx* c) {
+    ws_release(c, c->rs, {(void**)&c->rs_which, (void**)&c->rs_rowoff, (void**)&c->rs_out, (void**)&c->rs_outT, (void**)&c->rs_tape});
+    c->rs_tape_rows = 0;
+}
+void sitegrad_release(tnml_ctx* c) {
+    ws_release(c, c->sg, {(void**)&c->sg_lab, (void**)&c->sg_coef, (void**)&c->sg_rowoff, (void**)&c->sg_goff, (void**)&c->sg_blk0, (void**)&c->sg_grad, (void**)&c->sg_tape, (void**)&c->sg_tape2});
+    c->sg_tape_rows = 0; c->sg_grad_elems = 0;
+}
+// First call, or the chunk option has changed since: the old workspace goes (release), tab, w and pred are made for the new capacity;
+// *fresh then tells the caller to allocate what it alone has.  On an error here and in the helpers below the caller releases the workspace.
+static int ws_remake(tnml_ctx* c, StreamWs& s, int chunk, void (*release)(tnml_ctx*), bool* fresh) {
+    const int cap = (chunk + 63) / 64 * 64;
+    *fresh = s.cap != cap;
+    if (!*fresh) return 0;
+    if (s.bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); release(c); }
+    TCK(ws_alloc(c, s, (void**)&s.tab, (size_t)c->N * sizeof(ChainSite<double>)));
+    TCK(ws_alloc(c, s, (void**)&s.w, (size_t)cap * c->nl() * sizeof(double)));
+    TCK(ws_alloc(c, s, (void**)&s.pred, (size_t)cap * sizeof(int)));
+    s.cap = cap;
+    return 0;
+}
+// Buffers that follow W (a tape, the gradient): each holds *have units of `unit` bytes and is re-made for `want` units when W has grown
+static int ws_grow(tnml_ctx* c, StreamWs& s, size_t want, size_t* have, size_t unit, std::initializer_list<double**> bufs) {
+    if (want <= *have) return 0;
+    for (double** p : bufs)
+        if (*p) {
+            HIPCK(c, hipStreamSynchronize(c->stream));
+            (void)hipFree(*p); *p = nullptr;
+            c->bytes -= (int64_t)(*have * unit); s.bytes -= (int64_t)(*have * unit);
+        }
+    *have = 0;
+    for (double** p : bufs) TCK(ws_alloc(c, s, (void**)p, want * unit));
+    *have = want;
+    return 0;
+}
+// The staging buffers of the call's input form, made by the first call of that form.  Under an input map S C + 2 N C + 16 ncodes bytes: the
+// bytes as given, the block sums site-first, the fp64 table (uploaded here).  xphi false: the caller keeps the site-first features itself (fp32)
+static int ws_staging(tnml_ctx* c, StreamWs& s, const char* who, bool bytes_form, bool xphi = true) {
+    const size_t cap = s.cap, N = c->N;
+    if (bytes_form && c->im_set) {
+        if (s.codes) return 0;
         const size_t S = (size_t)c->im.src_rows * c->im.src_cols, tabb = c->im_table.size() * sizeof(double);
-        const int64_t before = c->pk_bytes;
-        rc = predict_alloc(c, (void**)&c->pk_mraw, S * cap);
-        if (!rc) rc = predict_alloc(c, (void**)&c->pk_codes, (size_t)cap * c->N * sizeof(uint16_t));
-        if (!rc) rc = predict_alloc(c, (void**)&c->pk_mtab, tabb);
-        c->pk_map_bytes = c->pk_bytes - before;
-        if (!rc && hipMemcpyAsync(c->pk_mtab, c->im_table.data(), tabb, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict_u8: copy of the input map's table failed");
-        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict_u8: hipStreamSynchronize failed");
-        if (rc) predict_release(c);
-        return rc;
+        TCK(ws_alloc(c, s, (void**)&s.mraw, S * cap));
+        TCK(ws_alloc(c, s, (void**)&s.codes, cap * N * sizeof(uint16_t)));
+        TCK(ws_alloc(c, s, (void**)&s.mtab, tabb));
+        if (hipMemcpyAsync(s.mtab, c->im_table.data(), tabb, hipMemcpyHostToDevice, c->stream) != hipSuccess) return tnml_fail(c, "%s: copy of the input map's table failed", who);
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return tnml_fail(c, "%s: hipStreamSynchronize failed", who);
+        return 0;
     }
-    if (bytes_form && !c->pk_x8) { rc = predict_alloc(c, (void**)&c->pk_raw8, (size_t)cap * c->N); if (!rc) rc = predict_alloc(c, (void**)&c->pk_x8, (size_t)cap * c->N); }
-    if (!bytes_form && !c->pk_rawphi) rc = predict_alloc(c, (void**)&c->pk_rawphi, (size_t)2 * cap * c->N * sizeof(double));
-    if (!bytes_form && !f32 && !rc && !c->pk_xphi) rc = predict_alloc(c, (void**)&c->pk_xphi, (size_t)2 * cap * c->N * sizeof(double));
-    if (!bytes_form && f32 && !rc && !c->pk_xphi32) rc = predict_alloc(c, (void**)&c->pk_xphi32, (size_t)2 * cap * c->N * sizeof(float));
+    if (bytes_form && !s.x8) { TCK(ws_alloc(c, s, (void**)&s.raw8, cap * N)); TCK(ws_alloc(c, s, (void**)&s.x8, cap * N)); }
+    if (!bytes_form && !s.rawphi) TCK(ws_alloc(c, s, (void**)&s.rawphi, 2 * cap * N * sizeof(double)));
+    if (!bytes_form && xphi && !s.xphi) TCK(ws_alloc(c, s, (void**)&s.xphi, 2 * cap * N * sizeof(double)));
+    return 0;
+}
+// The refusals every streamed call opens with, in this order.  fp64_only: what the call computes when it serves predict_dtype = 0 alone
+// (null: tnml_predict_* / tnml_evaluate_*, which take fp32 too); *maxbond: the largest bond of W
+static int streamed_refusals(tnml_ctx* c, const char* who, const char* fp64_only, int64_t n, int* maxbond) {
+    if (!c) return tnml_fail(c, "%s: null argument", who);
+    if (n < 0) return tnml_fail(c, "%s: n = %lld, must be >= 0", who, (long long)n);
+    if (c->pend_count > 0) return tnml_fail(c, "%s: a bond update is in flight (tnml_bond_update_end first)", who);
+    TCK(ho_locked(c, who));                                     // attached as a held-out set: its W is rewritten from the training context's stream, as tnml_classify refuses it
+    TCK(check_W(c));
+    int mb = 1;
+    for (int j = 1; j <= c->N; ++j) mb = std::max(mb, std::max(c->W[j].ml, c->W[j].mr));
+    const bool f32 = !fp64_only && c->predict_dtype == TNML_PREDICT_F32;
+    if (f32 && mb > TNML_CHAIN32_MAXM)
+        return tnml_fail(c, "%s: W has a bond of dimension %d, the fp32 chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, mb, TNML_CHAIN32_MAXM);
+    if (!f32 && mb > TNML_CHAIN_MAXM)
+        return tnml_fail(c, "%s: W has a bond of dimension %d, the chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, mb, TNML_CHAIN_MAXM);
+    if (fp64_only && c->predict_dtype != TNML_PREDICT_F64)
+        return tnml_fail(c, "%s: option predict_dtype = %d (fp32): %s are computed in fp64 only (set predict_dtype = 0)", who, c->predict_dtype, fp64_only);
+    *maxbond = mb;
+    return 0;
+}
+// the site table of W as it is now, on its way to s.tab: the caller synchronises before tab leaves scope
+static int upload_sites(tnml_ctx* c, const StreamWs& s, std::vector<ChainSite<double>>& tab) {
+    tab.resize(c->N);
+    for (int j = 1; j <= c->N; ++j) tab[j - 1] = ChainSite<double>{c->W[j].a, c->W[j].ml, c->W[j].mr};
+    HIPCK(c, hipMemcpyAsync(s.tab, tab.data(), sizeof(ChainSite<double>) * c->N, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+// what a chain kernel takes from the context and the workspace: the centre tnml_classify takes, the results of a chunk and the source of the
+// features -- block sums with the table (input map), bytes, or staged features
+template <typename E>
+static void chain_args(const tnml_ctx* c, const StreamWs& s, const ChainSite<E>* sites, bool bytes_form, const E* table, const E* xphi, ChainArgs<E>& a) {
+    a.sites = sites; a.N = c->N; a.cs = c->single() ? 1 : c->c0; a.nl = c->nl(); a.single = c->single() ? 1 : 0;
+    a.ld = s.cap; a.wout = s.w; a.pred = s.pred;
+    a.xT = nullptr; a.phiT = nullptr;
+    if (bytes_form && c->im_set) { a.codeT = s.codes; a.table = table; }
+    else if (bytes_form) a.xT = s.x8;
+    else a.phiT = xphi;
+}
+// tape regions (kernels_response.hip, kernels_sitegrad.hip): the vector on bond b = 0..N (dimension 1 at the two ends) starts at row
+// rowoff[b]; rowoff[N + 1] and the return value: the rows so far
+static int tape_rows(const tnml_ctx* c, std::vector<int>& rowoff) {
+    int rows = 0;
+    for (int b = 0; b <= c->N; ++b) { rowoff[b] = rows; rows += ru16(b == 0 ? 1 : c->W[b].mr); }
+    return rowoff[c->N + 1] = rows;
+}
+// the end of a chunk: weights and pred of images off .. off + cnt - 1 to the caller, then the synchronisation after which the staging buffers are reused
+static int chunk_results(tnml_ctx* c, const StreamWs& s, int64_t off, int cnt, double* weights, int32_t* pred) {
+    const int nl = c->nl();
+    if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, s.w, sizeof(double) * (size_t)cnt * nl, hipMemcpyDeviceToHost, c->stream));
+    if (pred) HIPCK(c, hipMemcpyAsync(pred + off, s.pred, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+    SYNCK(c, c->stream);
+    return 0;
+}
+// One chunk's way from the caller's arrays into the staging buffers of a workspace: copy in, then the input map's block sums or one
+// transposing pre-kernel; images off .. off + cnt - 1
+template <typename E>
+static int stage_chunk(tnml_ctx* c, const StreamWs& b, bool mapped, const StageGeom& sg, const uint8_t* pixels, const double* phi, int64_t off, int cnt, E* xphi) {
+    const bool bytes_form = pixels != nullptr;
+    const size_t per_img = mapped ? (size_t)sg.S : (size_t)c->N * (bytes_form ? 1 : 2 * sizeof(double));
+    if (mapped) {
+        HIPCK(c, hipMemcpyAsync(b.mraw, pixels + (size_t)off * per_img, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+        ProfScope ps(c, KC_PACK);
+        return launch_stage_codes(c, b.mraw, sg, cnt, b.cap, b.codes);
+    }
+    if (bytes_form) HIPCK(c, hipMemcpyAsync(b.raw8, pixels + (size_t)off * c->N, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+    else            HIPCK(c, hipMemcpyAsync(b.rawphi, phi + (size_t)off * c->N * 2, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+    return launch_chain_stage<E>(c, bytes_form ? b.raw8 : nullptr, bytes_form ? nullptr : b.rawphi, c->N, cnt, b.cap, b.x8, xphi);
+}
+
+// ---- streamed inference (kernels_chain.hip): ONE k_chain launch per chunk ----------
+// the workspace: the shared part, the parked vectors, the staging of the input form (the map's part counted in pk_map_bytes, the site-first
+// features in the element type of option predict_dtype) and, for tnml_evaluate_*, 4 C + sizeof(EvalAcc) bytes: the labels of a chunk and the tallies of a call
+static int predict_workspace(tnml_ctx* c, const char* who, bool bytes_form, bool f32, bool evaluate) {
+    StreamWs& s = c->pk;
+    bool fresh;
+    int rc = ws_remake(c, s, c->predict_chunk, predict_release, &fresh);
+    if (!rc && fresh) {
+        c->pk_park_elems = (size_t)s.cap * ru16(std::min(c->maxm, TNML_CHAIN_MAXM));
+        rc = ws_alloc(c, s, (void**)&c->pk_park, c->pk_park_elems * sizeof(double));
+    }
+    const int64_t before = s.bytes;
+    if (!rc) rc = ws_staging(c, s, who, bytes_form, !f32);
+    if (bytes_form && c->im_set) c->pk_map_bytes += s.bytes - before;
+    if (!rc && !bytes_form && f32 && !c->pk_xphi32) rc = ws_alloc(c, s, (void**)&c->pk_xphi32, (size_t)2 * s.cap * c->N * sizeof(float));
+    if (!rc && evaluate && !c->pk_lab) rc = ws_alloc(c, s, (void**)&c->pk_lab, (size_t)s.cap * sizeof(int));
+    if (!rc && evaluate && !c->pk_acc) rc = ws_alloc(c, s, (void**)&c->pk_acc, sizeof(EvalAcc));
     if (rc) predict_release(c);
     return rc;
 }
 // The fp32 side of the workspace (first call under predict_dtype = 1): the site table of the fp32 copy of W, the range flag, the copy itself
 // (grown when W has grown) and, under an input map, the table rounded to fp32.  Then the copy is made: W may have changed since the last call.
 static int predict_workspace32(tnml_ctx* c, bool mapped, const std::vector<ChainSite<double>>& tab) {
+    StreamWs& s = c->pk;
     int rc = 0;
-    if (!c->pk_tab32) rc = predict_alloc(c, (void**)&c->pk_tab32, (size_t)c->N * sizeof(ChainSite<float>));
+    if (!c->pk_tab32) rc = ws_alloc(c, s, (void**)&c->pk_tab32, (size_t)c->N * sizeof(ChainSite<float>));
     if (!rc && !c->pk_flag) {
-        rc = predict_alloc(c, (void**)&c->pk_flag, sizeof(int));
+        rc = ws_alloc(c, s, (void**)&c->pk_flag, sizeof(int));
         if (!rc && hipMemsetAsync(c->pk_flag, 0, sizeof(int), c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict: memset failed");
     }
     std::vector<size_t> off(c->N);
@@ -156,17 +267,17 @@ static int predict_workspace32(tnml_ctx* c, bool mapped, const std::vector<Chain
         if (c->pk_w32) {
             if (hipStreamSynchronize(c->stream) != hipSuccess) return tnml_fail(c, "tnml_predict: hipStreamSynchronize failed");
             (void)hipFree(c->pk_w32); c->pk_w32 = nullptr;
-            c->bytes -= (int64_t)(c->pk_w32_cap * sizeof(float)); c->pk_bytes -= (int64_t)(c->pk_w32_cap * sizeof(float)); c->pk_w32_cap = 0;
+            c->bytes -= (int64_t)(c->pk_w32_cap * sizeof(float)); s.bytes -= (int64_t)(c->pk_w32_cap * sizeof(float)); c->pk_w32_cap = 0;
         }
-        rc = predict_alloc(c, (void**)&c->pk_w32, total * sizeof(float));
+        rc = ws_alloc(c, s, (void**)&c->pk_w32, total * sizeof(float));
         if (!rc) c->pk_w32_cap = total;
     }
     if (!rc && mapped && !c->pk_mtab32) {
         std::vector<float> t32(c->im_table.size());
         for (size_t k = 0; k < t32.size(); ++k) t32[k] = (float)c->im_table[k];
-        const int64_t before = c->pk_bytes;
-        rc = predict_alloc(c, (void**)&c->pk_mtab32, t32.size() * sizeof(float));
-        if (!rc) c->pk_mtab32_bytes = c->pk_bytes - before;
+        const int64_t before = s.bytes;
+        rc = ws_alloc(c, s, (void**)&c->pk_mtab32, t32.size() * sizeof(float));
+        if (!rc) c->pk_mtab32_bytes = s.bytes - before;
         if (!rc && hipMemcpyAsync(c->pk_mtab32, t32.data(), t32.size() * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict_u8: copy of the input map's table failed");
         if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict_u8: hipStreamSynchronize failed");
     }
@@ -174,70 +285,40 @@ static int predict_workspace32(tnml_ctx* c, bool mapped, const std::vector<Chain
     std::vector<ChainSite<float>> t32(c->N);
     for (int j = 1; j <= c->N; ++j) t32[j - 1] = ChainSite<float>{c->pk_w32 + off[j - 1], tab[j - 1].ml, tab[j - 1].mr};
     HIPCK(c, hipMemcpyAsync(c->pk_tab32, t32.data(), sizeof(ChainSite<float>) * c->N, hipMemcpyHostToDevice, c->stream));
-    TCK(launch_chain_pack32(c, c->pk_tab, c->pk_tab32, c->N, c->c0, c->nl(), largest));
+    TCK(launch_chain_pack32(c, s.tab, c->pk_tab32, c->N, c->c0, c->nl(), largest));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (t32 leaves scope with this call)
     return 0;
-}
-// tnml_evaluate_*: the labels of a chunk and the accumulator block of a call, 4 C + sizeof(EvalAcc) bytes on top of the predict workspace (first such call)
-static int evaluate_workspace(tnml_ctx* c) {
-    int rc = 0;
-    if (!c->pk_lab) rc = predict_alloc(c, (void**)&c->pk_lab, (size_t)c->pk_cap * sizeof(int));
-    if (!rc && !c->pk_acc) rc = predict_alloc(c, (void**)&c->pk_acc, sizeof(EvalAcc));
-    if (rc) predict_release(c);
-    return rc;
-}
-// One chunk's way from the caller's arrays into the staging buffers of a chunk loop (tnml_predict_* / tnml_evaluate_*: pk_*;
-// tnml_response_*: rs_*): copy in, then the input map's block sums or one transposing pre-kernel; images off .. off + cnt - 1
-struct ChunkStage { uint8_t* mraw; uint16_t* codes; uint8_t *raw8, *x8; double* rawphi; int cap; };
-template <typename E>
-static int stage_chunk(tnml_ctx* c, const ChunkStage& b, bool mapped, const StageGeom& sg, const uint8_t* pixels, const double* phi, int64_t off, int cnt, E* xphi) {
-    const bool bytes_form = pixels != nullptr;
-    const size_t per_img = mapped ? (size_t)sg.S : (size_t)c->N * (bytes_form ? 1 : 2 * sizeof(double));
-    if (mapped) {
-        HIPCK(c, hipMemcpyAsync(b.mraw, pixels + (size_t)off * per_img, per_img * cnt, hipMemcpyHostToDevice, c->stream));
-        ProfScope ps(c, KC_PACK);
-        return launch_stage_codes(c, b.mraw, sg, cnt, b.cap, b.codes);
-    }
-    if (bytes_form) HIPCK(c, hipMemcpyAsync(b.raw8, pixels + (size_t)off * c->N, per_img * cnt, hipMemcpyHostToDevice, c->stream));
-    else            HIPCK(c, hipMemcpyAsync(b.rawphi, phi + (size_t)off * c->N * 2, per_img * cnt, hipMemcpyHostToDevice, c->stream));
-    return launch_chain_stage<E>(c, bytes_form ? b.raw8 : nullptr, bytes_form ? nullptr : b.rawphi, c->N, cnt, b.cap, b.x8, xphi);
 }
 // the chunk loop of predict_impl in the element type E of option predict_dtype: per chunk stage (map, bytes or phi), ONE chain launch, copy back;
 // labels (tnml_evaluate_*): the chunk's labels are staged with its images and ONE k_eval_tally launch behind the chain adds its tallies to pk_acc
 template <typename E>
 static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, double* weights, int32_t* pred, int maxbond) {
     constexpr bool f32 = sizeof(E) == sizeof(float);
+    const StreamWs& s = c->pk;
     const bool bytes_form = pixels != nullptr;
     const bool mapped = bytes_form && c->im_set;                // the input map: S bytes per image -> block sums -> table look-ups inside the chain kernel
     const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
-    const ChunkStage stage{c->pk_mraw, c->pk_codes, c->pk_raw8, c->pk_x8, c->pk_rawphi, c->pk_cap};
-    const int nl = c->nl();
     ChainArgs<E> a;
-    a.N = c->N; a.cs = c->single() ? 1 : c->c0; a.nl = nl; a.single = c->single() ? 1 : 0;       // the centre tnml_classify takes
-    a.ld = c->pk_cap; a.wout = c->pk_w; a.pred = c->pk_pred;
-    E *xphi, *park; const E* table; size_t park_elems = c->pk_park_elems;
+    E *xphi, *park; size_t park_elems = c->pk_park_elems;
     if constexpr (f32) {
         // fp32: the copy of W, the features and the table rounded to fp32; the scratch of the parked vectors is the fp64 path's:
         // cap x ru16(min(maxm, 512)) doubles hold cap x ru16(min(maxm, 1024)) floats
-        a.sites = c->pk_tab32; a.flag = c->pk_flag; table = c->pk_mtab32; xphi = c->pk_xphi32; park = (float*)c->pk_park; park_elems *= 2;
+        xphi = c->pk_xphi32; park = (float*)c->pk_park; park_elems *= 2;
+        chain_args(c, s, c->pk_tab32, bytes_form, c->pk_mtab32, xphi, a);
+        a.flag = c->pk_flag;
     } else {
-        a.sites = c->pk_tab; table = c->pk_mtab; xphi = c->pk_xphi; park = c->pk_park;
+        xphi = s.xphi; park = c->pk_park;
+        chain_args(c, s, s.tab, bytes_form, s.mtab, xphi, a);
     }
-    a.xT = nullptr; a.phiT = nullptr;
-    if (mapped) { a.codeT = c->pk_codes; a.table = table; }
-    else if (bytes_form) a.xT = c->pk_x8;
-    else a.phiT = xphi;
     for (int64_t off = 0; off < n; off += c->predict_chunk) {
         a.cnt = (int)std::min<int64_t>(c->predict_chunk, n - off);
-        TCK(stage_chunk<E>(c, stage, mapped, sg, pixels, phi, off, a.cnt, xphi));
+        TCK(stage_chunk<E>(c, s, mapped, sg, pixels, phi, off, a.cnt, xphi));
         if (labels) HIPCK(c, hipMemcpyAsync(c->pk_lab, labels + off, sizeof(int32_t) * (size_t)a.cnt, hipMemcpyHostToDevice, c->stream));
         TCK(launch_chain<E>(c, a, maxbond, chain_tile<E>(c, maxbond, a.cnt), park, park_elems));
-        if (labels) TCK(launch_eval_tally(c, c->pk_w, c->pk_pred, c->pk_lab, a.cnt, nl, a.single, c->target(), c->pk_acc));
+        if (labels) TCK(launch_eval_tally(c, s.w, s.pred, c->pk_lab, a.cnt, a.nl, a.single, c->target(), c->pk_acc));
         int flag = 0;
-        if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->pk_w, sizeof(double) * (size_t)a.cnt * nl, hipMemcpyDeviceToHost, c->stream));
-        if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->pk_pred, sizeof(int32_t) * (size_t)a.cnt, hipMemcpyDeviceToHost, c->stream));
         if (f32) HIPCK(c, hipMemcpyAsync(&flag, c->pk_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        SYNCK(c, c->stream);                                    // the staging buffers are reused by the next chunk
+        TCK(chunk_results(c, s, off, a.cnt, weights, pred));
         if (flag) {
             HIPCK(c, hipMemsetAsync(c->pk_flag, 0, sizeof(int), c->stream));
             HIPCK(c, hipStreamSynchronize(c->stream));
@@ -249,18 +330,8 @@ static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t
 // rep: the call is tnml_evaluate_* (labels are then required when n > 0); *rep is written once, after everything has succeeded
 static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, double* weights, int32_t* pred,
                         bool evaluate = false, const int32_t* labels = nullptr, tnml_eval_report* rep = nullptr) {
-    if (!c) return tnml_fail(c, "%s: null argument", who);
-    if (n < 0) return tnml_fail(c, "%s: n = %lld, must be >= 0", who, (long long)n);
-    if (c->pend_count > 0) return tnml_fail(c, "%s: a bond update is in flight (tnml_bond_update_end first)", who);
-    TCK(ho_locked(c, who));                                     // attached as a held-out set: its W is rewritten from the training context's stream, as tnml_classify refuses it
-    TCK(check_W(c));
     int maxbond = 1;
-    for (int j = 1; j <= c->N; ++j) maxbond = std::max(maxbond, std::max(c->W[j].ml, c->W[j].mr));
-    const bool f32 = c->predict_dtype == TNML_PREDICT_F32;
-    if (f32 && maxbond > TNML_CHAIN32_MAXM)
-        return tnml_fail(c, "%s: W has a bond of dimension %d, the fp32 chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, maxbond, TNML_CHAIN32_MAXM);
-    if (!f32 && maxbond > TNML_CHAIN_MAXM)
-        return tnml_fail(c, "%s: W has a bond of dimension %d, the chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, maxbond, TNML_CHAIN_MAXM);
+    TCK(streamed_refusals(c, who, nullptr, n, &maxbond));
     if (n == 0) { if (rep) memset(rep, 0, sizeof(*rep)); return 0; }
     if (!pixels && !phi) return tnml_fail(c, "%s: null argument", who);
     if (evaluate) {
@@ -269,15 +340,11 @@ static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* 
             if (labels[i] < 0 || labels[i] >= TNML_NL) return tnml_fail(c, "%s: label %d of image %lld out of range", who, labels[i], (long long)i);
     }
     HIPCK(c, hipSetDevice(c->cfg.device));
-    const bool bytes_form = pixels != nullptr;
-    TCK(predict_workspace(c, bytes_form, f32));
-    if (evaluate) {
-        TCK(evaluate_workspace(c));
-        HIPCK(c, hipMemsetAsync(c->pk_acc, 0, sizeof(EvalAcc), c->stream));
-    }
-    std::vector<ChainSite<double>> tab(c->N);
-    for (int j = 1; j <= c->N; ++j) tab[j - 1] = ChainSite<double>{c->W[j].a, c->W[j].ml, c->W[j].mr};
-    HIPCK(c, hipMemcpyAsync(c->pk_tab, tab.data(), sizeof(ChainSite<double>) * c->N, hipMemcpyHostToDevice, c->stream));
+    const bool bytes_form = pixels != nullptr, f32 = c->predict_dtype == TNML_PREDICT_F32;
+    TCK(predict_workspace(c, who, bytes_form, f32, evaluate));
+    if (evaluate) HIPCK(c, hipMemsetAsync(c->pk_acc, 0, sizeof(EvalAcc), c->stream));
+    std::vector<ChainSite<double>> tab;
+    TCK(upload_sites(c, c->pk, tab));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (tab leaves scope with this call)
     if (f32) TCK(predict_workspace32(c, bytes_form && c->im_set, tab));
     TCK(f32 ? predict_chunks<float>(c, who, n, pixels, phi, labels, weights, pred, maxbond) : predict_chunks<double>(c, who, n, pixels, phi, labels, weights, pred, maxbond));
@@ -316,76 +383,28 @@ int tnml_evaluate_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* 
 }
 
 // ---- streamed site responses (kernels_response.hip): every site's effect on an image's output ---------------------
-// The chunk loop of tnml_predict_* with option response_chunk: a chunk is staged as predict stages it, ONE k_response launch walks the
-// chain inward and outward, the result [N][2][C] is turned into [C][N][2] on the device and copied back; one synchronisation per chunk.
-// Reads W only, like tnml_predict_*.  The workspace is its own (tnml.h has its size): the predict workspace keeps its bytes.
-void response_release(tnml_ctx* c) {
-    void** slots[] = {(void**)&c->rs_tab, (void**)&c->rs_w, (void**)&c->rs_pred, (void**)&c->rs_which, (void**)&c->rs_rowoff, (void**)&c->rs_out, (void**)&c->rs_outT, (void**)&c->rs_tape,
-                      (void**)&c->rs_raw8, (void**)&c->rs_x8, (void**)&c->rs_rawphi, (void**)&c->rs_xphi, (void**)&c->rs_mraw, (void**)&c->rs_codes, (void**)&c->rs_mtab};
-    for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    c->bytes -= c->rs_bytes;
-    c->rs_bytes = 0; c->rs_cap = 0; c->rs_tape_rows = 0;
-}
-static int response_alloc(tnml_ctx* c, void** p, size_t bytes) {
-    TCK(dalloc(c, p, bytes));
-    c->rs_bytes += (int64_t)bytes;
-    return 0;
-}
+// Per chunk of option response_chunk ONE k_response launch walks the chain inward and outward, the result [N][2][C] is turned into
+// [C][N][2] on the device and copied back.
 // rows: the rows of a workgroup's tape slice that W asks for now
 static int response_workspace(tnml_ctx* c, const char* who, bool bytes_form, size_t rows) {
-    const int cap = (c->response_chunk + 63) / 64 * 64;
-    int rc = 0;
-    if (c->rs_cap != cap) {                               // first call, or option response_chunk has changed since
-        if (c->rs_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); response_release(c); }
-        rc = response_alloc(c, (void**)&c->rs_tab, (size_t)c->N * sizeof(ChainSite<double>));
-        if (!rc) rc = response_alloc(c, (void**)&c->rs_w, (size_t)cap * c->nl() * sizeof(double));
-        if (!rc) rc = response_alloc(c, (void**)&c->rs_pred, (size_t)cap * sizeof(int));
-        if (!rc) rc = response_alloc(c, (void**)&c->rs_which, (size_t)cap * sizeof(int));
-        if (!rc) rc = response_alloc(c, (void**)&c->rs_rowoff, (size_t)(c->N + 4) * sizeof(int));
-        if (!rc) rc = response_alloc(c, (void**)&c->rs_out, (size_t)2 * c->N * cap * sizeof(double));
-        if (!rc) rc = response_alloc(c, (void**)&c->rs_outT, (size_t)2 * c->N * cap * sizeof(double));
-        if (rc) { response_release(c); return rc; }
-        c->rs_cap = cap;
+    StreamWs& s = c->rs;
+    bool fresh;
+    int rc = ws_remake(c, s, c->response_chunk, response_release, &fresh);
+    const size_t cap = s.cap;
+    if (!rc && fresh) {
+        rc = ws_alloc(c, s, (void**)&c->rs_which, cap * sizeof(int));
+        if (!rc) rc = ws_alloc(c, s, (void**)&c->rs_rowoff, (size_t)(c->N + 4) * sizeof(int));
+        if (!rc) rc = ws_alloc(c, s, (void**)&c->rs_out, 2 * c->N * cap * sizeof(double));
+        if (!rc) rc = ws_alloc(c, s, (void**)&c->rs_outT, 2 * c->N * cap * sizeof(double));
     }
-    if (rows > c->rs_tape_rows) {                          // the tape follows the bonds W has: grown when W has grown
-        if (c->rs_tape) {
-            HIPCK(c, hipStreamSynchronize(c->stream));
-            (void)hipFree(c->rs_tape); c->rs_tape = nullptr;
-            const int64_t old = (int64_t)(c->rs_tape_rows * (size_t)cap * sizeof(double));
-            c->bytes -= old; c->rs_bytes -= old; c->rs_tape_rows = 0;
-        }
-        rc = response_alloc(c, (void**)&c->rs_tape, rows * (size_t)cap * sizeof(double));
-        if (rc) { response_release(c); return rc; }
-        c->rs_tape_rows = rows;
-    }
-    if (bytes_form && c->im_set) {
-        if (c->rs_codes) return 0;
-        const size_t S = (size_t)c->im.src_rows * c->im.src_cols, tabb = c->im_table.size() * sizeof(double);
-        rc = response_alloc(c, (void**)&c->rs_mraw, S * cap);
-        if (!rc) rc = response_alloc(c, (void**)&c->rs_codes, (size_t)cap * c->N * sizeof(uint16_t));
-        if (!rc) rc = response_alloc(c, (void**)&c->rs_mtab, tabb);
-        if (!rc && hipMemcpyAsync(c->rs_mtab, c->im_table.data(), tabb, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "%s: copy of the input map's table failed", who);
-        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "%s: hipStreamSynchronize failed", who);
-        if (rc) response_release(c);
-        return rc;
-    }
-    if (bytes_form && !c->rs_x8) { rc = response_alloc(c, (void**)&c->rs_raw8, (size_t)cap * c->N); if (!rc) rc = response_alloc(c, (void**)&c->rs_x8, (size_t)cap * c->N); }
-    if (!bytes_form && !c->rs_xphi) { rc = response_alloc(c, (void**)&c->rs_rawphi, (size_t)2 * cap * c->N * sizeof(double)); if (!rc) rc = response_alloc(c, (void**)&c->rs_xphi, (size_t)2 * cap * c->N * sizeof(double)); }
+    if (!rc) rc = ws_grow(c, s, rows, &c->rs_tape_rows, cap * sizeof(double), {&c->rs_tape});
+    if (!rc) rc = ws_staging(c, s, who, bytes_form);
     if (rc) response_release(c);
     return rc;
 }
 static int response_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* which, double* resp, double* weights, int32_t* pred) {
-    if (!c) return tnml_fail(c, "%s: null argument", who);
-    if (n < 0) return tnml_fail(c, "%s: n = %lld, must be >= 0", who, (long long)n);
-    if (c->pend_count > 0) return tnml_fail(c, "%s: a bond update is in flight (tnml_bond_update_end first)", who);
-    TCK(ho_locked(c, who));
-    TCK(check_W(c));
     int maxbond = 1;
-    for (int j = 1; j <= c->N; ++j) maxbond = std::max(maxbond, std::max(c->W[j].ml, c->W[j].mr));
-    if (maxbond > TNML_CHAIN_MAXM)
-        return tnml_fail(c, "%s: W has a bond of dimension %d, the chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, maxbond, TNML_CHAIN_MAXM);
-    if (c->predict_dtype != TNML_PREDICT_F64)
-        return tnml_fail(c, "%s: option predict_dtype = %d (fp32): site responses are computed in fp64 only (set predict_dtype = 0)", who, c->predict_dtype);
+    TCK(streamed_refusals(c, who, "site responses", n, &maxbond));
     if (n == 0) return 0;
     if ((!pixels && !phi) || !resp) return tnml_fail(c, "%s: null argument", who);
     const int nl = c->nl();
@@ -393,43 +412,33 @@ static int response_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t*
         for (int64_t i = 0; i < n; ++i)
             if (which[i] < 0 || which[i] >= nl) return tnml_fail(c, "%s: which = %d of image %lld out of range 0..%d", who, which[i], (long long)i, nl - 1);
     HIPCK(c, hipSetDevice(c->cfg.device));
+    const StreamWs& s = c->rs;
     const int N = c->N, cs = c->single() ? 1 : c->c0;
-    // tape regions: the vector on bond b = 0..N (dimension 1 at the two ends), then X and Y of the centre (kernels_response.hip)
+    // the tape: the regions of the bonds, then X and Y of the centre (kernels_response.hip)
     std::vector<int> rowoff(N + 4);
-    int rows = 0;
-    auto ru16 = [](int m) { return (m + 15) / 16 * 16; };
-    for (int b = 0; b <= N; ++b) { rowoff[b] = rows; rows += ru16(b == 0 ? 1 : c->W[b].mr); }
-    rowoff[N + 1] = rows; rows += ru16(c->W[cs].ml);
+    int rows = tape_rows(c, rowoff);
+    rows += ru16(c->W[cs].ml);
     rowoff[N + 2] = rows; rows += ru16(c->W[cs].mr);
     rowoff[N + 3] = rows;
     const bool bytes_form = pixels != nullptr;
     TCK(response_workspace(c, who, bytes_form, (size_t)rows));
-    std::vector<ChainSite<double>> tab(N);
-    for (int j = 1; j <= N; ++j) tab[j - 1] = ChainSite<double>{c->W[j].a, c->W[j].ml, c->W[j].mr};
-    HIPCK(c, hipMemcpyAsync(c->rs_tab, tab.data(), sizeof(ChainSite<double>) * N, hipMemcpyHostToDevice, c->stream));
+    std::vector<ChainSite<double>> tab;
+    TCK(upload_sites(c, s, tab));
     HIPCK(c, hipMemcpyAsync(c->rs_rowoff, rowoff.data(), sizeof(int) * (N + 4), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (tab and rowoff leave scope with this call)
     const bool mapped = bytes_form && c->im_set;
     const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
-    const ChunkStage stage{c->rs_mraw, c->rs_codes, c->rs_raw8, c->rs_x8, c->rs_rawphi, c->rs_cap};
     RespArgs a;
-    a.ch.sites = c->rs_tab; a.ch.N = N; a.ch.cs = cs; a.ch.nl = nl; a.ch.single = c->single() ? 1 : 0;
-    a.ch.ld = c->rs_cap; a.ch.wout = c->rs_w; a.ch.pred = c->rs_pred;
-    a.ch.xT = nullptr; a.ch.phiT = nullptr;
-    if (mapped) { a.ch.codeT = c->rs_codes; a.ch.table = c->rs_mtab; }
-    else if (bytes_form) a.ch.xT = c->rs_x8;
-    else a.ch.phiT = c->rs_xphi;
+    chain_args(c, s, s.tab, bytes_form, s.mtab, s.xphi, a.ch);
     a.which = which ? c->rs_which : nullptr; a.rowoff = c->rs_rowoff; a.tape = c->rs_tape; a.resp = c->rs_out;
-    const size_t tape_elems = c->rs_tape_rows * (size_t)c->rs_cap;
+    const size_t tape_elems = c->rs_tape_rows * (size_t)s.cap;
     for (int64_t off = 0; off < n; off += c->response_chunk) {
         a.ch.cnt = (int)std::min<int64_t>(c->response_chunk, n - off);
-        TCK(stage_chunk<double>(c, stage, mapped, sg, pixels, phi, off, a.ch.cnt, c->rs_xphi));
+        TCK(stage_chunk<double>(c, s, mapped, sg, pixels, phi, off, a.ch.cnt, s.xphi));
         if (which) HIPCK(c, hipMemcpyAsync(c->rs_which, which + off, sizeof(int32_t) * (size_t)a.ch.cnt, hipMemcpyHostToDevice, c->stream));
         TCK(launch_response(c, a, maxbond, chain_tile<double>(c, maxbond, a.ch.cnt), rows, tape_elems, c->rs_outT));
         HIPCK(c, hipMemcpyAsync(resp + (size_t)off * N * 2, c->rs_outT, sizeof(double) * (size_t)a.ch.cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
-        if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->rs_w, sizeof(double) * (size_t)a.ch.cnt * nl, hipMemcpyDeviceToHost, c->stream));
-        if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->rs_pred, sizeof(int32_t) * (size_t)a.ch.cnt, hipMemcpyDeviceToHost, c->stream));
-        SYNCK(c, c->stream);                                    // the staging buffers are reused by the next chunk
+        TCK(chunk_results(c, s, off, a.ch.cnt, weights, pred));
     }
     return 0;
 }
@@ -443,94 +452,27 @@ int tnml_response_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* 
 }
 
 // ---- streamed site gradients (kernels_sitegrad.hip): dC/dA of every site, on images the context does not hold ----------------
-// The chunk loop of tnml_response_* with option gradient_chunk: a chunk is staged as predict stages it, ONE k_site_backward launch walks
-// the chain inward and outward and leaves two tapes, ONE k_site_grad launch adds the chunk's outer products to the gradient, which stays
-// on the device until the last chunk and is copied back once.  Reads W only.  The workspace is its own (tnml.h has its size).
-void sitegrad_release(tnml_ctx* c) {
-    void** slots[] = {(void**)&c->sg_tab, (void**)&c->sg_w, (void**)&c->sg_pred, (void**)&c->sg_lab, (void**)&c->sg_coef, (void**)&c->sg_rowoff, (void**)&c->sg_goff, (void**)&c->sg_blk0,
-                      (void**)&c->sg_grad, (void**)&c->sg_tape, (void**)&c->sg_tape2,
-                      (void**)&c->sg_raw8, (void**)&c->sg_x8, (void**)&c->sg_rawphi, (void**)&c->sg_xphi, (void**)&c->sg_mraw, (void**)&c->sg_codes, (void**)&c->sg_mtab};
-    for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    c->bytes -= c->sg_bytes;
-    c->sg_bytes = 0; c->sg_cap = 0; c->sg_tape_rows = 0; c->sg_grad_elems = 0;
-}
-static int sitegrad_alloc(tnml_ctx* c, void** p, size_t bytes) {
-    TCK(dalloc(c, p, bytes));
-    c->sg_bytes += (int64_t)bytes;
-    return 0;
-}
-static int sitegrad_free(tnml_ctx* c, void** p, size_t bytes) {
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(*p); *p = nullptr;
-    c->bytes -= (int64_t)bytes; c->sg_bytes -= (int64_t)bytes;
-    return 0;
-}
+// Per chunk of option gradient_chunk ONE k_site_backward launch walks the chain inward and outward and leaves two tapes, ONE k_site_grad
+// launch adds the chunk's outer products to the gradient, which stays on the device until the last chunk and is copied back once.
 // rows: the rows of a workgroup's tape slice that W asks for now; elems: the elements of the gradient of W as it is now
 static int sitegrad_workspace(tnml_ctx* c, const char* who, bool bytes_form, size_t rows, size_t elems) {
-    const int cap = (c->gradient_chunk + 63) / 64 * 64;
+    StreamWs& s = c->sg;
     const int nl = c->nl();
-    int rc = 0;
-    if (c->sg_cap != cap) {                               // first call, or option gradient_chunk has changed since
-        if (c->sg_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); sitegrad_release(c); }
-        rc = sitegrad_alloc(c, (void**)&c->sg_tab, (size_t)c->N * sizeof(ChainSite<double>));
-        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_w, (size_t)cap * nl * sizeof(double));
-        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_coef, (size_t)cap * nl * sizeof(double));
-        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_pred, (size_t)cap * sizeof(int));
-        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_lab, (size_t)cap * sizeof(int));
-        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_rowoff, (size_t)(c->N + 2) * sizeof(int));
-        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_goff, (size_t)(c->N + 1) * sizeof(long long));
-        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_blk0, (size_t)(c->N + nl) * sizeof(int));
-        if (rc) { sitegrad_release(c); return rc; }
-        c->sg_cap = cap;
+    bool fresh;
+    int rc = ws_remake(c, s, c->gradient_chunk, sitegrad_release, &fresh);
+    const size_t cap = s.cap;
+    if (!rc && fresh) {
+        rc = ws_alloc(c, s, (void**)&c->sg_coef, cap * nl * sizeof(double));
+        if (!rc) rc = ws_alloc(c, s, (void**)&c->sg_lab, cap * sizeof(int));
+        if (!rc) rc = ws_alloc(c, s, (void**)&c->sg_rowoff, (size_t)(c->N + 2) * sizeof(int));
+        if (!rc) rc = ws_alloc(c, s, (void**)&c->sg_goff, (size_t)(c->N + 1) * sizeof(long long));
+        if (!rc) rc = ws_alloc(c, s, (void**)&c->sg_blk0, (size_t)(c->N + nl) * sizeof(int));
     }
-    if (rows > c->sg_tape_rows) {                          // the tapes follow the bonds W has: grown when W has grown
-        const size_t old = c->sg_tape_rows * (size_t)cap * sizeof(double);
-        if (c->sg_tape) TCK(sitegrad_free(c, (void**)&c->sg_tape, old));
-        if (c->sg_tape2) TCK(sitegrad_free(c, (void**)&c->sg_tape2, old));
-        c->sg_tape_rows = 0;
-        rc = sitegrad_alloc(c, (void**)&c->sg_tape, rows * (size_t)cap * sizeof(double));
-        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_tape2, rows * (size_t)cap * sizeof(double));
-        if (rc) { sitegrad_release(c); return rc; }
-        c->sg_tape_rows = rows;
-    }
-    if (elems > c->sg_grad_elems) {                        // and so does the gradient
-        if (c->sg_grad) TCK(sitegrad_free(c, (void**)&c->sg_grad, c->sg_grad_elems * sizeof(double)));
-        c->sg_grad_elems = 0;
-        rc = sitegrad_alloc(c, (void**)&c->sg_grad, elems * sizeof(double));
-        if (rc) { sitegrad_release(c); return rc; }
-        c->sg_grad_elems = elems;
-    }
-    if (bytes_form && c->im_set) {
-        if (c->sg_codes) return 0;
-        const size_t S = (size_t)c->im.src_rows * c->im.src_cols, tabb = c->im_table.size() * sizeof(double);
-        rc = sitegrad_alloc(c, (void**)&c->sg_mraw, S * cap);
-        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_codes, (size_t)cap * c->N * sizeof(uint16_t));
-        if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_mtab, tabb);
-        if (!rc && hipMemcpyAsync(c->sg_mtab, c->im_table.data(), tabb, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "%s: copy of the input map's table failed", who);
-        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "%s: hipStreamSynchronize failed", who);
-        if (rc) sitegrad_release(c);
-        return rc;
-    }
-    if (bytes_form && !c->sg_x8) { rc = sitegrad_alloc(c, (void**)&c->sg_raw8, (size_t)cap * c->N); if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_x8, (size_t)cap * c->N); }
-    if (!bytes_form && !c->sg_xphi) { rc = sitegrad_alloc(c, (void**)&c->sg_rawphi, (size_t)2 * cap * c->N * sizeof(double)); if (!rc) rc = sitegrad_alloc(c, (void**)&c->sg_xphi, (size_t)2 * cap * c->N * sizeof(double)); }
+    if (!rc) rc = ws_grow(c, s, rows, &c->sg_tape_rows, cap * sizeof(double), {&c->sg_tape, &c->sg_tape2});
+    if (!rc) rc = ws_grow(c, s, elems, &c->sg_grad_elems, sizeof(double), {&c->sg_grad});
+    if (!rc) rc = ws_staging(c, s, who, bytes_form);
     if (rc) sitegrad_release(c);
     return rc;
-}
-// the refusals of tnml_response_*, in the same words and the same order; *maxbond: the largest bond of W
-static int streamed_fp64_refusals(tnml_ctx* c, const char* who, const char* what, int64_t n, int* maxbond) {
-    if (!c) return tnml_fail(c, "%s: null argument", who);
-    if (n < 0) return tnml_fail(c, "%s: n = %lld, must be >= 0", who, (long long)n);
-    if (c->pend_count > 0) return tnml_fail(c, "%s: a bond update is in flight (tnml_bond_update_end first)", who);
-    TCK(ho_locked(c, who));
-    TCK(check_W(c));
-    int mb = 1;
-    for (int j = 1; j <= c->N; ++j) mb = std::max(mb, std::max(c->W[j].ml, c->W[j].mr));
-    if (mb > TNML_CHAIN_MAXM)
-        return tnml_fail(c, "%s: W has a bond of dimension %d, the chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, mb, TNML_CHAIN_MAXM);
-    if (c->predict_dtype != TNML_PREDICT_F64)
-        return tnml_fail(c, "%s: option predict_dtype = %d (fp32): %s are computed in fp64 only (set predict_dtype = 0)", who, c->predict_dtype, what);
-    *maxbond = mb;
-    return 0;
 }
 // elements of the gradient and where every site starts (off: N + 1 entries or null); W is complete
 static size_t sitegrad_layout(tnml_ctx* c, long long* off) {
@@ -553,7 +495,7 @@ int tnml_site_gradient_size(tnml_ctx* c, int64_t* elems, int64_t* offsets) {
 static int sitegrad_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
                          double* grad, double* weights, int32_t* pred) {
     int maxbond = 1;
-    TCK(streamed_fp64_refusals(c, who, "site gradients", n, &maxbond));
+    TCK(streamed_refusals(c, who, "site gradients", n, &maxbond));
     if (!grad) return tnml_fail(c, "%s: null argument", who);
     const int N = c->N, nl = c->nl(), cs = c->single() ? 1 : c->c0;
     if (c->W[cs].L != nl) return tnml_fail(c, "%s: the Label site %d of W carries %d labels, the context has %d", who, cs, c->W[cs].L, nl);
@@ -569,12 +511,9 @@ static int sitegrad_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t*
         for (int64_t i = 0; i < n * nl; ++i)
             if (!std::isfinite(coef[i])) return tnml_fail(c, "%s: coefficient %d of image %lld is not finite", who, (int)(i % nl), (long long)(i / nl));
     HIPCK(c, hipSetDevice(c->cfg.device));
-    // tape regions: the vector on bond b = 0..N (dimension 1 at the two ends); both tapes share the table (kernels_sitegrad.hip)
-    std::vector<int> rowoff(N + 2);
-    int rows = 0;
-    auto ru16 = [](int m) { return (m + 15) / 16 * 16; };
-    for (int b = 0; b <= N; ++b) { rowoff[b] = rows; rows += ru16(b == 0 ? 1 : c->W[b].mr); }
-    rowoff[N + 1] = rows;
+    const StreamWs& s = c->sg;
+    std::vector<int> rowoff(N + 2);                             // both tapes share the region table (kernels_sitegrad.hip)
+    const int rows = tape_rows(c, rowoff);
     // output blocks of 32 x 32 per virtual site: the sites in order, the Label site once per label
     std::vector<int> blk0(N + nl);
     int nblocks = 0, v = 0;
@@ -585,9 +524,8 @@ static int sitegrad_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t*
     blk0[v] = nblocks;
     const bool bytes_form = pixels != nullptr;
     TCK(sitegrad_workspace(c, who, bytes_form, (size_t)rows, elems));
-    std::vector<ChainSite<double>> tab(N);
-    for (int j = 1; j <= N; ++j) tab[j - 1] = ChainSite<double>{c->W[j].a, c->W[j].ml, c->W[j].mr};
-    HIPCK(c, hipMemcpyAsync(c->sg_tab, tab.data(), sizeof(ChainSite<double>) * N, hipMemcpyHostToDevice, c->stream));
+    std::vector<ChainSite<double>> tab;
+    TCK(upload_sites(c, s, tab));
     HIPCK(c, hipMemcpyAsync(c->sg_rowoff, rowoff.data(), sizeof(int) * (N + 2), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipMemcpyAsync(c->sg_goff, goff.data(), sizeof(long long) * (N + 1), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipMemcpyAsync(c->sg_blk0, blk0.data(), sizeof(int) * (N + nl), hipMemcpyHostToDevice, c->stream));
@@ -595,27 +533,19 @@ static int sitegrad_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t*
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (the tables leave scope with this call)
     const bool mapped = bytes_form && c->im_set;
     const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
-    const ChunkStage stage{c->sg_mraw, c->sg_codes, c->sg_raw8, c->sg_x8, c->sg_rawphi, c->sg_cap};
     SiteGradArgs a;
-    a.ch.sites = c->sg_tab; a.ch.N = N; a.ch.cs = cs; a.ch.nl = nl; a.ch.single = c->single() ? 1 : 0;
-    a.ch.ld = c->sg_cap; a.ch.wout = c->sg_w; a.ch.pred = c->sg_pred;
-    a.ch.xT = nullptr; a.ch.phiT = nullptr;
-    if (mapped) { a.ch.codeT = c->sg_codes; a.ch.table = c->sg_mtab; }
-    else if (bytes_form) a.ch.xT = c->sg_x8;
-    else a.ch.phiT = c->sg_xphi;
+    chain_args(c, s, s.tab, bytes_form, s.mtab, s.xphi, a.ch);
     a.rowoff = c->sg_rowoff; a.tape = c->sg_tape; a.tape2 = c->sg_tape2;
     a.lab = labels ? c->sg_lab : nullptr; a.target = c->target(); a.coef = c->sg_coef;
     a.grad = c->sg_grad; a.goff = c->sg_goff; a.blk0 = c->sg_blk0;
-    const size_t tape_elems = c->sg_tape_rows * (size_t)c->sg_cap;
+    const size_t tape_elems = c->sg_tape_rows * (size_t)s.cap;
     for (int64_t off = 0; off < n; off += c->gradient_chunk) {
         a.ch.cnt = (int)std::min<int64_t>(c->gradient_chunk, n - off);
-        TCK(stage_chunk<double>(c, stage, mapped, sg, pixels, phi, off, a.ch.cnt, c->sg_xphi));
+        TCK(stage_chunk<double>(c, s, mapped, sg, pixels, phi, off, a.ch.cnt, s.xphi));
         if (labels) HIPCK(c, hipMemcpyAsync(c->sg_lab, labels + off, sizeof(int32_t) * (size_t)a.ch.cnt, hipMemcpyHostToDevice, c->stream));
         else        HIPCK(c, hipMemcpyAsync(c->sg_coef, coef + (size_t)off * nl, sizeof(double) * (size_t)a.ch.cnt * nl, hipMemcpyHostToDevice, c->stream));
         TCK(launch_site_gradient(c, a, maxbond, chain_tile<double>(c, maxbond, a.ch.cnt), rows, tape_elems, nblocks));
-        if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, c->sg_w, sizeof(double) * (size_t)a.ch.cnt * nl, hipMemcpyDeviceToHost, c->stream));
-        if (pred) HIPCK(c, hipMemcpyAsync(pred + off, c->sg_pred, sizeof(int32_t) * (size_t)a.ch.cnt, hipMemcpyDeviceToHost, c->stream));
-        SYNCK(c, c->stream);                                    // the staging buffers are reused by the next chunk
+        TCK(chunk_results(c, s, off, a.ch.cnt, weights, pred));
     }
     HIPCK(c, hipMemcpyAsync(grad, c->sg_grad, elems * sizeof(double), hipMemcpyDeviceToHost, c->stream));   // the one copy of the gradient
     SYNCK(c, c->stream);

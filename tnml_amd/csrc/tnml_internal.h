@@ -130,6 +130,18 @@ struct HeldOut {
 
 template <typename E> struct ChainSite;      // kernels_chain.hip, below
 
+// What the workspaces of the streamed calls share (tnml_infer.hip): the results and the staging buffers of one chunk of `cap` images.
+// The staging buffers are allocated by the first call of their input form.
+struct StreamWs {
+    int cap = 0; int64_t bytes = 0;                   // the chunk option rounded up to 64 when the workspace was sized; everything allocated for it
+    ChainSite<double>* tab = nullptr;                 // [N] per-site table (ml, mr, address)
+    double* w = nullptr; int* pred = nullptr;         // [cap][nl], [cap]: weights and pred of a chunk
+    uint8_t *raw8 = nullptr, *x8 = nullptr;           // bytes of a chunk as given [cap][N] and site-first [N][cap]
+    double *rawphi = nullptr, *xphi = nullptr;        // features of a chunk as given [cap][N][2] and site-first [N][2][cap]
+    uint8_t* mraw = nullptr;                          // under an input map: bytes of a chunk as given [cap][S],
+    uint16_t* codes = nullptr; double* mtab = nullptr;   // its block sums site-first [N][cap] and the fp64 table [ncodes][2]
+};
+
 struct tnml_ctx {
     tnml_config cfg;
     int N = 0, NT = 0, NTp = 0, c0 = 0, maxm = 0;
@@ -302,63 +314,43 @@ struct tnml_ctx {
     int predict_tile = 0;            // test knob (option "predict_tile"): images per workgroup of k_chain, 16 / 32 / 64 (capped by the LDS budget); 0: by bond dimension and image count
     bool attr_chain[2][2] = {};      // [fp32][input map]: the LDS attribute of those k_chain instantiations is set
     // option "predict_dtype": 0 k_chain<double>, 1 k_chain<float> (both kernels_chain.hip).  The fp32 workspace, allocated by the
-    // first fp32 call (counted in `bytes` and pk_bytes, freed with the rest): the fp32 copy of W, re-made by every call and grown when W has grown,
+    // first fp32 call (counted in `bytes` and pk.bytes, freed with the rest): the fp32 copy of W, re-made by every call and grown when W has grown,
     // its site table, the range flag, and what the staging of the input form needs
     int predict_dtype = 0;
     float* pk_w32 = nullptr; size_t pk_w32_cap = 0;   // [pk_w32_cap] floats: every site tensor, each starting at a multiple of 4 floats
     ChainSite<float>* pk_tab32 = nullptr;              // [N] per-site table of the copy
     int* pk_flag = nullptr;                            // raised by k_chain<float> when a weight is not finite
-    float* pk_xphi32 = nullptr;                        // features of a chunk site-first [N][2][pk_cap], rounded to fp32 (first fp32 tnml_predict_phi)
+    float* pk_xphi32 = nullptr;                        // features of a chunk site-first [N][2][pk.cap], rounded to fp32 (first fp32 tnml_predict_phi)
     int64_t pk_mtab32_bytes = 0;
     float* pk_mtab32 = nullptr;                        // the input map's table rounded to fp32 [ncodes][2] (first fp32 tnml_predict_u8 under a map)
-    // its workspace, allocated by the first predict call (counted in `bytes`, freed by tnml_destroy); pk_cap = predict_chunk rounded up to 64 when it was sized
-    int pk_cap = 0; int64_t pk_bytes = 0;
-    ChainSite<double>* pk_tab = nullptr;  // [N] per-site table (ml, mr, address)
-    double* pk_w = nullptr; int* pk_pred = nullptr;   // [pk_cap][nl], [pk_cap]: results of a chunk
-    double* pk_park = nullptr; size_t pk_park_elems = 0;   // [pk_cap / T][ru16(m)][T]: the parked right-chain vectors of the workgroups (when three tiles do not fit the LDS)
-    uint8_t *pk_raw8 = nullptr, *pk_x8 = nullptr;     // bytes of a chunk as given [pk_cap][N] and site-first [N][pk_cap] (first tnml_predict_u8)
-    double *pk_rawphi = nullptr, *pk_xphi = nullptr;  // features of a chunk as given [pk_cap][N][2] and site-first [N][2][pk_cap] (first tnml_predict_phi)
-    // streamed evaluation (tnml_evaluate_u8 / tnml_evaluate_phi, kernels_eval.hip): allocated by the first such call, counted in `bytes` and pk_bytes, freed with the rest
-    int* pk_lab = nullptr;           // [pk_cap] labels of a chunk
+    // The three streamed workspaces (StreamWs above): allocated by the first call, counted in `bytes` and in their own `bytes`, re-made when their
+    // chunk option changes, freed by tnml_destroy; none touches another.  Beside each, the fields it alone has.
+    StreamWs pk;                     // tnml_predict_* / tnml_evaluate_* (cap: predict_chunk rounded up to 64).  tnml_set_input_map releases its map part only (pk_map_bytes)
+    double* pk_park = nullptr; size_t pk_park_elems = 0;   // [cap / T][ru16(m)][T]: the parked right-chain vectors of the workgroups (when three tiles do not fit the LDS)
+    int* pk_lab = nullptr;           // [cap] labels of a chunk (first tnml_evaluate_* call)
     EvalAcc* pk_acc = nullptr;       // the tallies of the call in progress (k_eval_tally adds a chunk, the host reads them once at the end)
-    // streamed site responses (tnml_response_u8 / tnml_response_phi, kernels_response.hip): a workspace of its own, allocated by the first
-    // call, counted in `bytes` and rs_bytes, re-made when option response_chunk changes, freed by tnml_destroy; the predict workspace is not touched
+    int64_t pk_map_bytes = 0;        // of pk.bytes, what pk.mraw, pk.codes and pk.mtab take
+    // streamed site responses (tnml_response_u8 / tnml_response_phi, kernels_response.hip)
     int response_chunk = TNML_RESPONSE_CHUNK_DEFAULT;      // option "response_chunk": images per launch of k_response
     bool attr_response[2] = {};      // [input map]: the LDS attribute of those k_response instantiations is set
-    int rs_cap = 0; int64_t rs_bytes = 0;                  // response_chunk rounded up to 64 when the workspace was sized
-    ChainSite<double>* rs_tab = nullptr;                   // [N] per-site table
-    double* rs_w = nullptr; int* rs_pred = nullptr;        // [rs_cap][nl], [rs_cap]: weights and pred of a chunk
-    int* rs_which = nullptr;                               // [rs_cap] labels asked for
+    StreamWs rs;                     // released whole by every tnml_set_input_map call
+    int* rs_which = nullptr;                               // [cap] labels asked for
     int* rs_rowoff = nullptr;                              // [N + 4] rows of the tape regions (kernels_response.hip)
-    double *rs_out = nullptr, *rs_outT = nullptr;          // the result of a chunk as the kernel leaves it [N][2][rs_cap] and as the caller gets it [rs_cap][N][2]
-    double* rs_tape = nullptr; size_t rs_tape_rows = 0;    // [rs_cap / T][rs_tape_rows][T]: every chain vector of every image; grown when W has grown
-    uint8_t *rs_raw8 = nullptr, *rs_x8 = nullptr;          // staging as the predict workspace has it, sized by rs_cap (first call of the input form)
-    double *rs_rawphi = nullptr, *rs_xphi = nullptr;
-    uint8_t* rs_mraw = nullptr; uint16_t* rs_codes = nullptr; double* rs_mtab = nullptr;   // under an input map (released by every tnml_set_input_map call, with the rest)
-    // streamed site gradients (tnml_site_gradient_u8 / tnml_site_gradient_phi, kernels_sitegrad.hip): a workspace of its own under the rules of
-    // the response workspace (allocated by the first call, counted in `bytes` and sg_bytes, re-made when option gradient_chunk changes)
+    double *rs_out = nullptr, *rs_outT = nullptr;          // the result of a chunk as the kernel leaves it [N][2][cap] and as the caller gets it [cap][N][2]
+    double* rs_tape = nullptr; size_t rs_tape_rows = 0;    // [cap / T][rs_tape_rows][T]: every chain vector of every image; grown when W has grown
+    // streamed site gradients (tnml_site_gradient_u8 / tnml_site_gradient_phi, kernels_sitegrad.hip)
     int gradient_chunk = TNML_GRADIENT_CHUNK_DEFAULT;      // option "gradient_chunk": images per launch of k_site_backward / k_site_grad
     bool attr_sitegrad[2] = {};      // [input map]: the LDS attribute of those k_site_backward instantiations is set
-    int sg_cap = 0; int64_t sg_bytes = 0;                  // gradient_chunk rounded up to 64 when the workspace was sized
-    ChainSite<double>* sg_tab = nullptr;                   // [N] per-site table
-    double* sg_w = nullptr; int* sg_pred = nullptr;        // [sg_cap][nl], [sg_cap]: weights and pred of a chunk
-    int* sg_lab = nullptr; double* sg_coef = nullptr;      // [sg_cap] labels of a chunk; [sg_cap][nl] its coefficients (given, or formed by k_site_backward)
+    StreamWs sg;                     // released whole by every tnml_set_input_map call
+    int* sg_lab = nullptr; double* sg_coef = nullptr;      // [cap] labels of a chunk; [cap][nl] its coefficients (given, or formed by k_site_backward)
     int* sg_rowoff = nullptr;                              // [N + 2] rows of the tape regions of bond 0..N, then the rows of a slice
     long long* sg_goff = nullptr; int* sg_blk0 = nullptr;  // [N + 1] first element of every site in sg_grad; [N + nl] first output block of every virtual site, then the block count
     double* sg_grad = nullptr; size_t sg_grad_elems = 0;   // the gradient of the call in progress, every site in tnml_get_site's layout; grown when W has grown
-    double *sg_tape = nullptr, *sg_tape2 = nullptr; size_t sg_tape_rows = 0;   // [sg_cap / T][sg_tape_rows][T] each: inward and outward vectors; grown when W has grown
-    uint8_t *sg_raw8 = nullptr, *sg_x8 = nullptr;          // staging as the predict workspace has it, sized by sg_cap (first call of the input form)
-    double *sg_rawphi = nullptr, *sg_xphi = nullptr;
-    uint8_t* sg_mraw = nullptr; uint16_t* sg_codes = nullptr; double* sg_mtab = nullptr;   // under an input map (released by every tnml_set_input_map call, with the rest)
-    // input map (tnml_set_input_map): geometry + host copy of the fp64 table; consulted by tnml_set_data_u8 / tnml_predict_u8 only
+    double *sg_tape = nullptr, *sg_tape2 = nullptr; size_t sg_tape_rows = 0;   // [cap / T][sg_tape_rows][T] each: inward and outward vectors; grown when W has grown
+    // input map (tnml_set_input_map): geometry + host copy of the fp64 table; consulted by tnml_set_data_u8 and the *_u8 streamed calls only
     bool im_set = false;
     tnml_input_map im = {};          // geometry (table = nullptr)
     std::vector<double> im_table;    // [ncodes][2]
-    // workspace of tnml_predict_u8 under a map (first such call; released by every tnml_set_input_map call)
-    uint8_t* pk_mraw = nullptr;      // bytes of a chunk as given [pk_cap][S]
-    uint16_t* pk_codes = nullptr;    // block sums, site-first [N][pk_cap]
-    double* pk_mtab = nullptr;       // the fp64 table [ncodes][2]
-    int64_t pk_map_bytes = 0;
 
     // profiling
     bool prof = false;
@@ -639,7 +631,7 @@ struct SiteGradArgs {
 int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int rows, size_t tape_elems, int nblocks);
 
 // ---- kernels_eval.hip: the tallies of streamed evaluation over the results of a chunk ----
-// w [cnt][nl], pred [cnt] (what k_chain left in pk_w / pk_pred), lab [cnt] in 0..9 (the host has checked them) -> acc += the chunk's
+// w [cnt][nl], pred [cnt] (what k_chain left in pk.w / pk.pred), lab [cnt] in 0..9 (the host has checked them) -> acc += the chunk's
 // label_cost, count, nincorrect, confusion; one workgroup, fixed summation order (the kernel's header states it); class eval_tally
 int launch_eval_tally(tnml_ctx* c, const double* w, const int* pred, const int* lab, int cnt, int nl, int single, int target, EvalAcc* acc);
 
