@@ -273,6 +273,11 @@ int tnml_quadcost(tnml_ctx* ctx, const double* B, double lambda, double* cost,
                   double label_cost[TNML_NL], double* reg_cost, int64_t* ncorrect);
 /* cgrad (fixedL.cc:349-445): B is updated in place */
 int tnml_cgrad(tnml_ctx* ctx, double* B, int npass, double lambda, double cconv, tnml_cg_trace* trace);
+/* test entry: a copy of what the last tnml_cgrad left on the device, for the per-pass tests of the CG.  which = "R", "Pv", "G": the fp64
+   CG vectors (residual, direction, image sum) in the host layout of B; "P", "Pp", "dP": the model outputs, p*t.v of the last pAp pass and the
+   residuals tgt - P as [NT padded to 256][10] doubles (a label extent of 1 in TNML_MODE_SINGLE), padded rows included, widened from the
+   context's type.  count: the number of doubles `out` holds, which has to be that size.  Changes no state. */
+int tnml_cg_state(tnml_ctx* ctx, const char* which, double* out, int64_t count);
 
 /* exact (single.h:117-160; TNML_MODE_SINGLE, TNML_F64, one rank): B = y Phi^+ through the SVD of the D x NT design matrix of the
    v_n (D = 4 mL mR <= 4096; its rows come from D forward passes of unit tensors, the SVD is a one-sided Jacobi on the host so

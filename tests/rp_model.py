@@ -271,20 +271,25 @@ class Model:
         u_mfma = U32 if mode == "f32" else UBF
         return P, ((n_mfma + 4) * u_mfma + (n_epi + mO + 15) * U32) * Pa
 
-    def gradient_model(self, mode, kind, EI, phiI, phiO, EX, P, labels, per, Bndim, target=None, bf16_grad=True, chain=None):
+    def gradient_model(self, mode, kind, EI, phiI, phiO, EX, P, labels, per, Bndim, target=None, bf16_grad=True, chain=None, weights=None):
         """G in the shape of B (TrainStates.gradient) and its bound.  P: what the device's forward pass returned for the same B
         ([NT, L]); per: images per slab (bgemm_cut); target: the per-label variant's label; bf16_grad False: k_bgemm on the fp32 pipe
         in a bf16 mode; chain: the length of the longest fp32 accumulation chain where it is shorter than min(per, NT) -- the largest
-        number of images of ONE slab whose product is not zero (adding an exact zero does not round, so the bound stays a worst case)."""
+        number of images of ONE slab whose product is not zero (adding an exact zero does not round, so the bound stays a worst case);
+        weights ([NT, L]): the per-image weights of the sum as the device holds them, in place of fl32(target - P) -- the dP a CG pass left, or
+        p*t.v for the image sum A p of the merged CG and of fast_conj (P is then not read)."""
         EI, phiI, phiO, EX = self.f32(EI), self.f32(phiI), self.f32(phiO), self.f32(EX)
-        P = np.asarray(P, dtype=np.float64).reshape(EI.shape[0], -1)
         labels = np.asarray(labels)
         NT, mI = EI.shape
-        if target is None:
-            tgt = (labels[:, None] == np.arange(NL)[None, :]).astype(np.float64)
+        if weights is not None:
+            dP = self.f32(np.asarray(weights, dtype=np.float64).reshape(NT, -1))
         else:
-            tgt = (labels == target).astype(np.float64)[:, None]
-        dP = self.f32(tgt - P)
+            P = np.asarray(P, dtype=np.float64).reshape(NT, -1)
+            if target is None:
+                tgt = (labels[:, None] == np.arange(NL)[None, :]).astype(np.float64)
+            else:
+                tgt = (labels == target).astype(np.float64)[:, None]
+            dP = self.f32(tgt - P)
         X = self.f32(EI[:, :, None] * phiI[:, None, :]).reshape(NT, 2 * mI)
         if kind == 2:
             z = self.f32(EX[:, None, :] * dP[:, :, None])                                   # [n, l, q]

@@ -15,8 +15,11 @@ f32, bf16 and bf16x3 are covered PER KERNEL up to 25 000 images, not here: tests
 holds every kernel of theirs inside its derived bound -- at up to 700 images every tile class, and at 24 320 / 24 576 / 25 000 images the
 default dispatch of the label dot on either side of its threshold (the streaming form k_labeldot<8, 2, NLT, float, float, float> included),
 cost / per-label costs / #correct / pAp as exact functions of the device's own outputs, and the gradient GEMM at its real slab cuts (12 slabs
-of 2 048 images, a short last slab, 79 slabs) on sparse probes and on dense data.  Still open in these modes at scale: the CG and whole bond
-updates, whose fp32 accumulation over the passes has no model, and image counts above 25 000 (the slab grows to 5 024 images at 60 000).  Only
+of 2 048 images, a short last slab, 79 slabs) on sparse probes and on dense data.  The CG is closed pass by pass: test_cg_model_gpu.py
+holds every pass of it, from the device's own state before the pass, to the bounds of those kernels and its fast output update P = fma(alpha, Pp, P)
+bit for bit -- every path at 300 images (fp64 included, at 1e-13 where the parity tolerance is 1e-5) and the default dispatch at 24 320 / 24 576
+images on sparse probes (tests/cg_model.py).  Still open in these modes at scale: whole bond updates (the split and the shift after the CG), and
+image counts above 25 000 (the slab grows to 5 024 images at 60 000).  Only
 f64_e32 (fp32 storage, fp64 accumulation: its rounding does not depend on the image count) gets a case at scale in this file."""
 import os
 

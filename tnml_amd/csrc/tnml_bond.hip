@@ -538,6 +538,34 @@ int tnml_cgrad(tnml_ctx* c, double* B, int npass, double lambda, double cconv, t
     TCK(cgrad_fetch_trace(c, npass, trace));
     return download_bond(c, c->vB, B);
 }
+// test entry: what the last tnml_cgrad left on the device.  "R" / "Pv" / "G": the fp64 CG vectors vR / vP / vG in the host layout of B;
+// "P" / "Pp" / "dP": [NTp][nl] doubles, padded rows included, widened from the context's type.  A copy after a synchronisation: no CG
+// state changes (the vectors pass through the unpack scratch tB2, as every downloaded bond tensor does).
+int tnml_cg_state(tnml_ctx* c, const char* which, double* out, int64_t count) {
+    if (!c || !which || !out) return tnml_fail(c, "tnml_cg_state: null argument");
+    TCK(ho_locked(c, "tnml_cg_state"));
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if (c->currb < 1) return tnml_fail(c, "tnml_cg_state: setBond has not been called");
+    const BondPlan& p = c->plan;
+    const double* vec = !strcmp(which, "R") ? c->vR : !strcmp(which, "Pv") ? c->vP : !strcmp(which, "G") ? c->vG : nullptr;
+    if (vec) {
+        const int64_t ne = (int64_t)p.mL * 4 * p.mR * p.LB;
+        if (count != ne) return tnml_fail(c, "tnml_cg_state: %s has %lld elements, count = %lld", which, (long long)ne, (long long)count);
+        return download_bond(c, vec, out);
+    }
+    const void* src = !strcmp(which, "P") ? c->P : !strcmp(which, "Pp") ? c->Pp : !strcmp(which, "dP") ? c->dP : nullptr;
+    if (!src) return tnml_fail(c, "tnml_cg_state: unknown array \"%s\" (R, Pv, G, P, Pp, dP)", which);
+    const int nl = c->nl();
+    const size_t ne = (size_t)nl * c->NTp;
+    if (count != (int64_t)ne) return tnml_fail(c, "tnml_cg_state: %s has %lld elements, count = %lld", which, (long long)ne, (long long)count);
+    std::vector<char> h(ne * c->esz());
+    SYNCK(c, c->stream);
+    HIPCK(c, hipMemcpy(h.data(), src, h.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < c->NTp; ++i)
+        for (int l = 0; l < nl; ++l)
+            out[(size_t)i * nl + l] = c->f64() ? ((const double*)h.data())[(size_t)l * c->NTp + i] : (double)((const float*)h.data())[(size_t)l * c->NTp + i];
+    return 0;
+}
 int tnml_svd_split(tnml_ctx* c, const double* B, int b, int ha, double cutoff, int maxm, int minm,
                    double* truncerr, int* newm, double* sv, int* nsv) {
     CollScope coll_(c);

@@ -516,6 +516,18 @@ class TrainStates:
         self._ck(self._L.tnml_cgrad(self._h, _lib.dptr(buf), npass, lam, cconv, C.byref(tr)))
         return buf.reshape(B.shape, order="F"), _trace_dict(tr)
 
+    def cg_state(self, which, shape=None):
+        """test entry (tnml_cg_state): what the last cgrad left on the device.  "R", "Pv", "G": the fp64 CG vectors in the shape of the bond
+        tensor (`shape`: that of the B given to cgrad); "P", "Pp", "dP": [NT padded, nl], padded rows included"""
+        if which in ("R", "Pv", "G"):
+            buf = np.empty(int(np.prod(shape)))
+            self._ck(self._L.tnml_cg_state(self._h, which.encode(), _lib.dptr(buf), buf.size))
+            return buf.reshape(shape, order="F")
+        NTp = -(-self.NT // 256) * 256
+        buf = np.empty((NTp, self.nl))
+        self._ck(self._L.tnml_cg_state(self._h, which.encode(), _lib.dptr(buf), buf.size))
+        return buf
+
     def exact(self, b, lam, pcut=1e-8):
         """single.h:117-160 on the bond chosen by setBond(b) (per-label variant): the solved bond tensor"""
         shape = self.bond_tensor(b).shape
