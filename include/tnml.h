@@ -464,6 +464,68 @@ int tnml_site_gradient_u8 (tnml_ctx* ctx, int64_t n, const uint8_t* pixels, cons
 int tnml_site_gradient_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/, const int32_t* labels, const double* coef,
                            double* grad, double* weights, int32_t* pred);
 
+/* ---- gradient steps on the device: SGD with momentum and Adam on the streamed site gradient ---------------------------
+ * One call is one optimiser step on W.  The gradient G of the n images is summed on the device exactly as tnml_site_gradient_* sums
+ * it (same inputs, labels / coef rule, gradient_chunk, predict_tile, input map, per-label variant and order: the same bits), then the
+ * optimiser reads it where it lies and rewrites the site tensors in place.  Nothing of the size of W crosses the bus in either
+ * direction: after the stream is synchronised only the report is copied back.  A context that holds no data can so be trained by
+ * mini-batch SGD or Adam at the speed of its kernels.
+ * The arithmetic (kernels_sitestep.hip states it in full; tests/sitestep_model.py restates it in numpy).  Every operation is one IEEE
+ * fp64 rounding, nothing is contracted, quotient and root are the correctly rounded ones:
+ *   total     = the sum of g^2 over the flat gradient as grad of tnml_site_gradient_* lays it out, in a fixed order: blocks of
+ *               65 536 consecutive elements, one workgroup of 256 threads each (thread t adds elements t, t + 256, ... in ascending
+ *               order, then the tree of k_eval_tally over the threads), the block sums added in block order by one thread; no atomics
+ *   grad_norm = |scale| sqrt(total);  factor f = scale, or scale (clip / grad_norm) when clip > 0 and grad_norm > clip (clipped = 1)
+ *   gh        = f g
+ *   SGD:   v <- mu v + gh;  A <- A - lr v
+ *   Adam:  p1 <- p1 beta1, p2 <- p2 beta2 (both start at 1: one multiplication per step, never a pow); c1 = 1 - p1, c2 = 1 - p2;
+ *          m <- beta1 m + (1 - beta1) gh;  v <- beta2 v + ((1 - beta2) gh) gh;  A <- A - lr ((m / c1) / (sqrt(v / c2) + eps))
+ * When total is not finite nothing is applied: W, the optimiser state and t stay bit for bit as they were, the call fails with a
+ * message that gives the norm, and the context stays usable.  The decision is taken on the device (the update kernel reads the flag
+ * the norm pass left).
+ * The report: t, grad_norm, factor, clipped; eval -- in the labels mode the report tnml_evaluate_* gives for the batch at the W BEFORE
+ * the step under predict_chunk = gradient_chunk (one k_eval_tally launch per chunk on the chunk's weights), in the coef mode zero but
+ * for n.  rep may be NULL.
+ * The optimiser state (v for SGD; m and v for Adam, each laid out like grad) is allocated by the first step, for that method and for
+ * the site shapes of W at that moment; hyper-parameters may change from call to call.  A step under the other method, or on a W whose
+ * site shapes have changed, is refused with a message that names the site and tnml_site_step_reset.  The state is counted by
+ * tnml_device_bytes, freed by tnml_site_step_reset (t then starts over) and tnml_destroy, and is no part of the gradient workspace:
+ * it survives a change of gradient_chunk and tnml_set_input_map.  With E = the elements of grad and k = 1 (SGD) or 2 (Adam):
+ *             8 k E + 8 ceil(E / 65536) + 4 (N + 1) + 64 + 1040   bytes (the state, the block sums, the first update block of every
+ *                                                         site, the norm pass's result, the tallies of the call)
+ * on top of the workspace of tnml_site_gradient_* for the input form.
+ * A step does to the context what tnml_set_site on every site does: environments, bond and outputs are no longer current
+ * (tnml_env_init before the next bond update), placements and the bond histories start over.
+ * Refused as tnml_site_gradient_* is, in the same words (in flight, attached as a held-out set, W incomplete, a bond above 512,
+ * predict_dtype = 1, both or neither of labels and coef, a bad label, a coefficient that is not finite); as tnml_set_site is on a
+ * training context with a held-out context attached; on a context of a multi-rank run (nranks != 1: no collective is entered, the
+ * replicas would part); with p NULL or a parameter outside its range (the message names it).  n = 0 succeeds: no step is taken, the
+ * report is zeroed.
+ * tnml_site_step_state is a test entry like tnml_cg_state: "m" (Adam) or "v" (both methods), count = E doubles. */
+#define TNML_STEP_SGD  0
+#define TNML_STEP_ADAM 1
+typedef struct {
+    int    method;              /* TNML_STEP_SGD | TNML_STEP_ADAM */
+    double lr;                  /* finite, > 0 */
+    double momentum;            /* SGD:  mu in [0, 1) */
+    double beta1, beta2, eps;   /* Adam: betas in [0, 1), eps > 0 */
+    double clip;                /* > 0: bound on the norm of the scaled gradient; 0: none */
+    double scale;               /* finite, non-zero: the gradient is multiplied by it (1/n, say) */
+} tnml_step_params;
+typedef struct {
+    int64_t t;                  /* steps this state has taken, this one included */
+    double  grad_norm;          /* |scale| ||G||_2 over all sites */
+    double  factor;             /* f above: what G was multiplied by */
+    int     clipped;
+    tnml_eval_report eval;      /* labels mode: the batch at the W BEFORE the step; coef mode: zero but for n */
+} tnml_step_report;
+int tnml_site_step_u8 (tnml_ctx* ctx, int64_t n, const uint8_t* pixels, const int32_t* labels /*[n] or NULL*/, const double* coef /*[n][nl] or NULL*/,
+                       const tnml_step_params* p, tnml_step_report* rep /* or NULL */);
+int tnml_site_step_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/, const int32_t* labels, const double* coef,
+                       const tnml_step_params* p, tnml_step_report* rep);
+int tnml_site_step_reset(tnml_ctx* ctx);                                                    /* frees the optimiser state; t starts over */
+int tnml_site_step_state(tnml_ctx* ctx, const char* which /* "m" | "v" */, double* out, int64_t count);
+
 /* ---- held-out evaluation during training ----------------------------------------------------------
  * A held-out set is an ordinary context created for the held-out images (one rank: nranks = 1, its own shard of the set in
  * a multi-rank run).  Once attached to a training context, every bond update of `train` also moves the two site tensors it

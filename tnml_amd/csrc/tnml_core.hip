@@ -448,6 +448,7 @@ int tnml_destroy(tnml_ctx* c) {
     predict_release(c);                                   // the workspace of tnml_predict_* (first call)
     response_release(c);                                  // and of tnml_response_*
     sitegrad_release(c);                                  // and of tnml_site_gradient_*
+    step_release(c);                                      // the optimiser state of tnml_site_step_*
     for (auto& sl : c->slabs) if (sl.base) (void)hipFree(sl.base);
     if (c->hrep) (void)hipHostFree(c->hrep);
     if (c->hcost) (void)hipHostFree(c->hcost);

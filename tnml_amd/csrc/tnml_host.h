@@ -101,6 +101,7 @@ void predict_release_map(tnml_ctx* c);                 // of tnml_predict_*, the
 void predict_release(tnml_ctx* c);
 void response_release(tnml_ctx* c);
 void sitegrad_release(tnml_ctx* c);
+void step_release(tnml_ctx* c);                        // the optimiser state of tnml_site_step_* (the st_ fields); synchronise first
 
 // ---- tnml_bond.hip ----------------------------------------------------------------------------
 PackDesc bond_pack_desc(const BondPlan& p);

@@ -327,6 +327,20 @@ static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t
     }
     return 0;
 }
+// the report of n images from the tallies the k_eval_tally launches of a call have added up (cost: the label costs in index order)
+static tnml_eval_report eval_report_of(const EvalAcc& h, int64_t n) {
+    tnml_eval_report r;
+    memset(&r, 0, sizeof(r));
+    r.n = n;
+    int64_t wrong = 0;
+    for (int l = 0; l < TNML_NL; ++l) {
+        r.label_cost[l] = h.label_cost[l]; r.cost += h.label_cost[l];
+        r.count[l] = h.count[l]; r.nincorrect[l] = h.nincorrect[l]; wrong += h.nincorrect[l];
+        for (int p = 0; p < TNML_NL; ++p) r.confusion[l][p] = h.confusion[l][p];
+    }
+    r.ncorrect = n - wrong;
+    return r;
+}
 // rep: the call is tnml_evaluate_* (labels are then required when n > 0); *rep is written once, after everything has succeeded
 static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, double* weights, int32_t* pred,
                         bool evaluate = false, const int32_t* labels = nullptr, tnml_eval_report* rep = nullptr) {
@@ -352,17 +366,7 @@ static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* 
     EvalAcc h;                                                  // the one copy of the tallies: every chunk has been added (the loop ends on a synchronisation)
     HIPCK(c, hipMemcpyAsync(&h, c->pk_acc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     SYNCK(c, c->stream);
-    tnml_eval_report r;
-    memset(&r, 0, sizeof(r));
-    r.n = n;
-    int64_t wrong = 0;
-    for (int l = 0; l < TNML_NL; ++l) {
-        r.label_cost[l] = h.label_cost[l]; r.cost += h.label_cost[l];
-        r.count[l] = h.count[l]; r.nincorrect[l] = h.nincorrect[l]; wrong += h.nincorrect[l];
-        for (int p = 0; p < TNML_NL; ++p) r.confusion[l][p] = h.confusion[l][p];
-    }
-    r.ncorrect = n - wrong;
-    *rep = r;
+    *rep = eval_report_of(h, n);
     return 0;
 }
 int tnml_predict_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, double* weights, int32_t* pred) {
@@ -492,16 +496,9 @@ int tnml_site_gradient_size(tnml_ctx* c, int64_t* elems, int64_t* offsets) {
     if (offsets) for (int j = 0; j <= c->N; ++j) offsets[j] = off[j];
     return 0;
 }
-static int sitegrad_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
-                         double* grad, double* weights, int32_t* pred) {
-    int maxbond = 1;
-    TCK(streamed_refusals(c, who, "site gradients", n, &maxbond));
-    if (!grad) return tnml_fail(c, "%s: null argument", who);
-    const int N = c->N, nl = c->nl(), cs = c->single() ? 1 : c->c0;
-    if (c->W[cs].L != nl) return tnml_fail(c, "%s: the Label site %d of W carries %d labels, the context has %d", who, cs, c->W[cs].L, nl);
-    std::vector<long long> goff(N + 1);
-    const size_t elems = sitegrad_layout(c, goff.data());
-    if (n == 0) { memset(grad, 0, elems * sizeof(double)); return 0; }
+// what a gradient call with n > 0 asks of its arrays: images, exactly one of labels and coef, labels in range, finite coefficients
+static int sitegrad_inputs(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef) {
+    const int nl = c->nl();
     if (!pixels && !phi) return tnml_fail(c, "%s: null argument", who);
     if ((labels != nullptr) == (coef != nullptr)) return tnml_fail(c, "%s: exactly one of labels and coef must be given (%s are)", who, labels ? "both" : "neither");
     if (labels)
@@ -510,6 +507,24 @@ static int sitegrad_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t*
     if (coef)
         for (int64_t i = 0; i < n * nl; ++i)
             if (!std::isfinite(coef[i])) return tnml_fail(c, "%s: coefficient %d of image %lld is not finite", who, (int)(i % nl), (long long)(i / nl));
+    return 0;
+}
+// The part the gradient calls and the step calls share: refusals, staging, tables and the chunk loop.  It leaves the gradient of the n
+// images in c->sg_grad (*elems of them) with the stream synchronised behind the last chunk; n = 0: nothing is launched, *elems alone is
+// set.  out: where the caller's result goes (refused when null).  acc (tnml_site_step_* in the labels mode): a device accumulator
+// block that is zeroed here and gets one k_eval_tally launch per chunk, on the chunk's weights and sg_lab.
+static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
+                           const void* out, double* weights, int32_t* pred, size_t* elems_out, EvalAcc* acc = nullptr) {
+    int maxbond = 1;
+    TCK(streamed_refusals(c, who, "site gradients", n, &maxbond));
+    if (!out) return tnml_fail(c, "%s: null argument", who);
+    const int N = c->N, nl = c->nl(), cs = c->single() ? 1 : c->c0;
+    if (c->W[cs].L != nl) return tnml_fail(c, "%s: the Label site %d of W carries %d labels, the context has %d", who, cs, c->W[cs].L, nl);
+    std::vector<long long> goff(N + 1);
+    const size_t elems = sitegrad_layout(c, goff.data());
+    *elems_out = elems;
+    if (n == 0) return 0;
+    TCK(sitegrad_inputs(c, who, n, pixels, phi, labels, coef));
     HIPCK(c, hipSetDevice(c->cfg.device));
     const StreamWs& s = c->sg;
     std::vector<int> rowoff(N + 2);                             // both tapes share the region table (kernels_sitegrad.hip)
@@ -530,6 +545,7 @@ static int sitegrad_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t*
     HIPCK(c, hipMemcpyAsync(c->sg_goff, goff.data(), sizeof(long long) * (N + 1), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipMemcpyAsync(c->sg_blk0, blk0.data(), sizeof(int) * (N + nl), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipMemsetAsync(c->sg_grad, 0, elems * sizeof(double), c->stream));       // the sum starts from zero: grad is overwritten
+    if (acc) HIPCK(c, hipMemsetAsync(acc, 0, sizeof(EvalAcc), c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (the tables leave scope with this call)
     const bool mapped = bytes_form && c->im_set;
     const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
@@ -545,8 +561,16 @@ static int sitegrad_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t*
         if (labels) HIPCK(c, hipMemcpyAsync(c->sg_lab, labels + off, sizeof(int32_t) * (size_t)a.ch.cnt, hipMemcpyHostToDevice, c->stream));
         else        HIPCK(c, hipMemcpyAsync(c->sg_coef, coef + (size_t)off * nl, sizeof(double) * (size_t)a.ch.cnt * nl, hipMemcpyHostToDevice, c->stream));
         TCK(launch_site_gradient(c, a, maxbond, chain_tile<double>(c, maxbond, a.ch.cnt), rows, tape_elems, nblocks));
+        if (acc && labels) TCK(launch_eval_tally(c, s.w, s.pred, c->sg_lab, a.ch.cnt, nl, a.ch.single, c->target(), acc));
         TCK(chunk_results(c, s, off, a.ch.cnt, weights, pred));
     }
+    return 0;
+}
+static int sitegrad_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
+                         double* grad, double* weights, int32_t* pred) {
+    size_t elems = 0;
+    TCK(sitegrad_device(c, who, n, pixels, phi, labels, coef, grad, weights, pred, &elems));
+    if (n == 0) { memset(grad, 0, elems * sizeof(double)); return 0; }
     HIPCK(c, hipMemcpyAsync(grad, c->sg_grad, elems * sizeof(double), hipMemcpyDeviceToHost, c->stream));   // the one copy of the gradient
     SYNCK(c, c->stream);
     return 0;
@@ -558,4 +582,143 @@ int tnml_site_gradient_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const i
 int tnml_site_gradient_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* labels, const double* coef, double* grad, double* weights, int32_t* pred) {
     if (n > 0 && !phi) return tnml_fail(c, "tnml_site_gradient_phi: null argument");
     return sitegrad_impl(c, "tnml_site_gradient_phi", n, nullptr, phi, labels, coef, grad, weights, pred);
+}
+
+// ---- gradient steps on the device (kernels_sitestep.hip): the gradient above, then ONE optimiser step on W where it lies ----------------
+// The optimiser state (the st_ fields of tnml_ctx) is no part of the workspace `sg`: tnml.h has its size.
+void step_release(tnml_ctx* c) {
+    for (void** p : {(void**)&c->st_m, (void**)&c->st_v, (void**)&c->st_bsum, (void**)&c->st_res, (void**)&c->st_wg0, (void**)&c->st_acc})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    c->bytes -= c->st_bytes;
+    c->st_bytes = 0; c->st_method = -1; c->st_shape.clear(); c->st_elems = 0; c->st_nblk = 0; c->st_nwg = 0;
+    c->st_t = 0; c->st_p1 = 1.; c->st_p2 = 1.;
+}
+int tnml_site_step_reset(tnml_ctx* c) {
+    if (!c) return tnml_fail(c, "tnml_site_step_reset: null argument");
+    if (c->st_method < 0) return 0;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    step_release(c);
+    return 0;
+}
+static const char* step_method_name(int m) { return m == TNML_STEP_ADAM ? "adam" : "sgd"; }
+// The state for `method` and W as it is now (complete): made by the first step, zeroed; afterwards the method and every site's shape must be those it was made for
+static int step_state_for(tnml_ctx* c, const char* who, int method) {
+    const int N = c->N;
+    if (c->st_method >= 0) {
+        if (c->st_method != method)
+            return tnml_fail(c, "%s: the optimiser state was made for method %s, this step asks for %s (tnml_site_step_reset first)", who, step_method_name(c->st_method), step_method_name(method));
+        for (int j = 1; j <= N; ++j)
+            if (c->st_shape[3 * (j - 1)] != c->W[j].ml || c->st_shape[3 * (j - 1) + 1] != c->W[j].mr || c->st_shape[3 * (j - 1) + 2] != c->W[j].L)
+                return tnml_fail(c, "%s: site %d of W is %d x 2 x %d now, the optimiser state was made for %d x 2 x %d (tnml_site_step_reset first)", who, j,
+                                 c->W[j].ml, c->W[j].mr, c->st_shape[3 * (j - 1)], c->st_shape[3 * (j - 1) + 1]);
+        return 0;
+    }
+    std::vector<int> wg0(N + 1);
+    int nwg = 0;
+    for (int j = 1; j <= N; ++j) {
+        wg0[j - 1] = nwg;
+        nwg += (int)(((size_t)2 * c->W[j].ml * c->W[j].mr * c->W[j].L + STEP_WG_ELEMS - 1) / STEP_WG_ELEMS);
+    }
+    wg0[N] = nwg;
+    const size_t E = sitegrad_layout(c, nullptr);
+    const int nblk = (int)((E + STEP_NORM_BLOCK - 1) / STEP_NORM_BLOCK);
+    auto alloc = [&](void** p, size_t bytes) { int rc = dalloc(c, p, bytes); if (!rc) c->st_bytes += (int64_t)bytes; return rc; };
+    int rc = 0;
+    if (method == TNML_STEP_ADAM) rc = alloc((void**)&c->st_m, E * sizeof(double));
+    if (!rc) rc = alloc((void**)&c->st_v, E * sizeof(double));
+    if (!rc) rc = alloc((void**)&c->st_bsum, (size_t)nblk * sizeof(double));
+    if (!rc) rc = alloc((void**)&c->st_wg0, (size_t)(N + 1) * sizeof(int));
+    if (!rc) rc = alloc((void**)&c->st_res, SR_N * sizeof(double));
+    if (!rc) rc = alloc((void**)&c->st_acc, sizeof(EvalAcc));
+    hipError_t e = hipSuccess;
+    if (!rc && c->st_m) e = hipMemsetAsync(c->st_m, 0, E * sizeof(double), c->stream);
+    if (!rc && e == hipSuccess) e = hipMemsetAsync(c->st_v, 0, E * sizeof(double), c->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(c->st_wg0, wg0.data(), sizeof(int) * (N + 1), hipMemcpyHostToDevice, c->stream);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(c->stream);                    // (wg0 leaves scope with this call)
+    if (!rc && e != hipSuccess) rc = tnml_fail(c, "%s: setting up the optimiser state failed: %s", who, hipGetErrorString(e));
+    if (rc) { step_release(c); return rc; }
+    c->st_method = method; c->st_elems = E; c->st_nblk = nblk; c->st_nwg = nwg;
+    c->st_shape.resize(3 * (size_t)N);
+    for (int j = 1; j <= N; ++j) { c->st_shape[3 * (j - 1)] = c->W[j].ml; c->st_shape[3 * (j - 1) + 1] = c->W[j].mr; c->st_shape[3 * (j - 1) + 2] = c->W[j].L; }
+    return 0;
+}
+static int step_check_params(tnml_ctx* c, const char* who, const tnml_step_params* p) {
+    if (!p) return tnml_fail(c, "%s: null argument (the step parameters p)", who);
+    if (p->method != TNML_STEP_SGD && p->method != TNML_STEP_ADAM) return tnml_fail(c, "%s: method = %d, must be TNML_STEP_SGD (0) or TNML_STEP_ADAM (1)", who, p->method);
+    if (!(std::isfinite(p->lr) && p->lr > 0.)) return tnml_fail(c, "%s: lr = %g, must be finite and > 0", who, p->lr);
+    if (!(std::isfinite(p->clip) && p->clip >= 0.)) return tnml_fail(c, "%s: clip = %g, must be finite and >= 0 (0: no clipping)", who, p->clip);
+    if (!(std::isfinite(p->scale) && p->scale != 0.)) return tnml_fail(c, "%s: scale = %g, must be finite and non-zero", who, p->scale);
+    if (p->method == TNML_STEP_SGD) {
+        if (!(p->momentum >= 0. && p->momentum < 1.)) return tnml_fail(c, "%s: momentum = %g, must lie in [0, 1)", who, p->momentum);
+    } else {
+        if (!(p->beta1 >= 0. && p->beta1 < 1.)) return tnml_fail(c, "%s: beta1 = %g, must lie in [0, 1)", who, p->beta1);
+        if (!(p->beta2 >= 0. && p->beta2 < 1.)) return tnml_fail(c, "%s: beta2 = %g, must lie in [0, 1)", who, p->beta2);
+        if (!(std::isfinite(p->eps) && p->eps > 0.)) return tnml_fail(c, "%s: eps = %g, must be finite and > 0", who, p->eps);
+    }
+    return 0;
+}
+static int sitestep_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
+                         const tnml_step_params* p, tnml_step_report* rep) {
+    int maxbond = 1;
+    TCK(streamed_refusals(c, who, "site gradients", n, &maxbond));
+    TCK(ho_locked(c, who, true));                               // as tnml_set_site: W of a training context with a held-out context attached changes in bond updates only
+    if (c->cfg.nranks != 1) return tnml_fail(c, "%s: the context is rank %d of %d: a step enters no collective, the replicas of W would part (one rank only)", who, c->cfg.rank, c->cfg.nranks);
+    TCK(step_check_params(c, who, p));
+    if (n == 0) { if (rep) memset(rep, 0, sizeof(*rep)); return 0; }
+    const int cs = c->single() ? 1 : c->c0;
+    if (c->W[cs].L != c->nl()) return tnml_fail(c, "%s: the Label site %d of W carries %d labels, the context has %d", who, cs, c->W[cs].L, c->nl());
+    TCK(sitegrad_inputs(c, who, n, pixels, phi, labels, coef)); // (before the state is made: a refused call leaves nothing behind)
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    TCK(step_state_for(c, who, p->method));
+    size_t elems = 0;
+    TCK(sitegrad_device(c, who, n, pixels, phi, labels, coef, p, nullptr, nullptr, &elems, c->st_acc));
+    if (elems != c->st_elems) return tnml_fail(c, "%s: the gradient has %zu elements, the optimiser state %zu (tnml_site_step_reset first)", who, elems, c->st_elems);
+    SiteStepArgs a;
+    a.sites = c->sg.tab; a.goff = c->sg_goff; a.wg0 = c->st_wg0; a.N = c->N;
+    a.grad = c->sg_grad; a.elems = elems; a.m = c->st_m; a.v = c->st_v; a.bsum = c->st_bsum; a.nblk = c->st_nblk; a.res = c->st_res;
+    a.method = p->method; a.lr = p->lr; a.mu = p->momentum; a.beta1 = p->beta1; a.beta2 = p->beta2; a.eps = p->eps; a.clip = p->clip; a.scale = p->scale;
+    // Adam's powers: one multiplication per step, kept only when the step is applied
+    const double p1 = c->st_p1 * p->beta1, p2 = c->st_p2 * p->beta2;
+    a.o1 = 1. - p->beta1; a.o2 = 1. - p->beta2; a.c1 = 1. - p1; a.c2 = 1. - p2;
+    TCK(launch_site_step(c, a, c->st_nwg));
+    double res[SR_N];
+    EvalAcc h;
+    HIPCK(c, hipMemcpyAsync(res, c->st_res, sizeof(res), hipMemcpyDeviceToHost, c->stream));            // the report: all that crosses the bus
+    if (labels) HIPCK(c, hipMemcpyAsync(&h, c->st_acc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    SYNCK(c, c->stream);
+    if (res[SR_APPLIED] == 0.)
+        return tnml_fail(c, "%s: the gradient is out of range (sum of squares %g, norm %g): no step was taken, W and the optimiser state are as they were", who, res[SR_TOTAL], res[SR_NORM]);
+    c->st_t += 1;
+    if (p->method == TNML_STEP_ADAM) { c->st_p1 = p1; c->st_p2 = p2; }
+    // W has changed under the context, as by tnml_set_site on every site
+    for (int j = 1; j <= c->N; ++j) c->W[j].placed = false;
+    c->currb = -1; c->p_valid = false; c->sweep_start = false;
+    for (auto& bh : c->bond_hist) bh = tnml_ctx::BondHist();
+    if (rep) {
+        memset(rep, 0, sizeof(*rep));
+        rep->t = c->st_t; rep->grad_norm = res[SR_NORM]; rep->factor = res[SR_FACTOR]; rep->clipped = res[SR_CLIPPED] != 0.;
+        if (labels) rep->eval = eval_report_of(h, n); else rep->eval.n = n;
+    }
+    return 0;
+}
+int tnml_site_step_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const int32_t* labels, const double* coef, const tnml_step_params* p, tnml_step_report* rep) {
+    if (n > 0 && !pixels) return tnml_fail(c, "tnml_site_step_u8: null argument");
+    return sitestep_impl(c, "tnml_site_step_u8", n, pixels, nullptr, labels, coef, p, rep);
+}
+int tnml_site_step_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* labels, const double* coef, const tnml_step_params* p, tnml_step_report* rep) {
+    if (n > 0 && !phi) return tnml_fail(c, "tnml_site_step_phi: null argument");
+    return sitestep_impl(c, "tnml_site_step_phi", n, nullptr, phi, labels, coef, p, rep);
+}
+int tnml_site_step_state(tnml_ctx* c, const char* which, double* out, int64_t count) {
+    if (!c || !which || !out) return tnml_fail(c, "tnml_site_step_state: null argument");
+    if (c->st_method < 0) return tnml_fail(c, "tnml_site_step_state: no step has been taken since the state was reset");
+    const double* src = !strcmp(which, "v") ? c->st_v : !strcmp(which, "m") ? c->st_m : nullptr;
+    if (strcmp(which, "v") && strcmp(which, "m")) return tnml_fail(c, "tnml_site_step_state: unknown array \"%s\" (m, v)", which);
+    if (!src) return tnml_fail(c, "tnml_site_step_state: method %s keeps no array \"%s\"", step_method_name(c->st_method), which);
+    if (count != (int64_t)c->st_elems) return tnml_fail(c, "tnml_site_step_state: %s has %lld elements, count = %lld", which, (long long)c->st_elems, (long long)count);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    SYNCK(c, c->stream);
+    HIPCK(c, hipMemcpy(out, src, sizeof(double) * c->st_elems, hipMemcpyDeviceToHost));
+    return 0;
 }

@@ -33,11 +33,11 @@
 
 enum KClass {
     KC_FGEMM_FWD = 0, KC_FGEMM_SHIFT, KC_LABELDOT, KC_ZPRIME, KC_BGEMM, KC_SLABRED, KC_PACK, KC_VEC,
-    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_EVAL_TALLY, KC_SITE_RESP, KC_SITE_BWD, KC_SITE_GRAD, KC_COUNT
+    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_EVAL_TALLY, KC_SITE_RESP, KC_SITE_BWD, KC_SITE_GRAD, KC_STEP_NORM, KC_SITE_STEP, KC_COUNT
 };
 static const char* const kclass_names[KC_COUNT] = {
     "fgemm_fwd", "fgemm_shift", "labeldot", "zprime", "bgemm", "slab_reduce", "pack", "cg_vec",
-    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain", "eval_tally", "site_resp", "site_bwd", "site_grad"};
+    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain", "eval_tally", "site_resp", "site_bwd", "site_grad", "step_norm", "site_step"};
 
 // device accumulator block of tnml_evaluate_*: the part of tnml_eval_report that k_eval_tally (kernels_eval.hip) adds up
 struct EvalAcc {
@@ -347,6 +347,19 @@ struct tnml_ctx {
     long long* sg_goff = nullptr; int* sg_blk0 = nullptr;  // [N + 1] first element of every site in sg_grad; [N + nl] first output block of every virtual site, then the block count
     double* sg_grad = nullptr; size_t sg_grad_elems = 0;   // the gradient of the call in progress, every site in tnml_get_site's layout; grown when W has grown
     double *sg_tape = nullptr, *sg_tape2 = nullptr; size_t sg_tape_rows = 0;   // [cap / T][sg_tape_rows][T] each: inward and outward vectors; grown when W has grown
+    // gradient steps on the device (tnml_site_step_u8 / tnml_site_step_phi, kernels_sitestep.hip): the optimiser state.  Allocated by the first
+    // step for a method and the site shapes of W at that moment, counted in `bytes` and st_bytes, freed by tnml_site_step_reset and tnml_destroy;
+    // no part of `sg`: a change of gradient_chunk and tnml_set_input_map leave it alone
+    int st_method = -1;                                    // TNML_STEP_SGD / TNML_STEP_ADAM; -1: no state
+    std::vector<int> st_shape;                             // [3 N] ml, mr, L of every site when the state was made
+    size_t st_elems = 0; int st_nblk = 0, st_nwg = 0;      // E; norm blocks ceil(E / STEP_NORM_BLOCK); workgroups of the update
+    double *st_m = nullptr, *st_v = nullptr;               // [E] each, laid out like sg_grad (st_m: Adam only)
+    double* st_bsum = nullptr;                             // [st_nblk] block sums of g^2
+    double* st_res = nullptr;                              // [8] what the norm pass leaves: total, grad_norm, factor, clipped, applied
+    int* st_wg0 = nullptr;                                 // [N + 1] first update workgroup of every site, then their count
+    EvalAcc* st_acc = nullptr;                             // the tallies of the call in progress (labels mode)
+    int64_t st_t = 0; double st_p1 = 1., st_p2 = 1.;       // steps taken; Adam's running powers beta1^t, beta2^t
+    int64_t st_bytes = 0;
     // input map (tnml_set_input_map): geometry + host copy of the fp64 table; consulted by tnml_set_data_u8 and the *_u8 streamed calls only
     bool im_set = false;
     tnml_input_map im = {};          // geometry (table = nullptr)
@@ -629,6 +642,25 @@ struct SiteGradArgs {
 };
 // rows: rowoff[N + 1] as the host knows it; tape_elems: doubles behind each tape; nblocks: the block count; classes site_bwd, site_grad
 int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int rows, size_t tape_elems, int nblocks);
+
+// ---- kernels_sitestep.hip: one optimiser step on W from the gradient tnml_site_gradient_*'s kernels left on the device ----
+#define STEP_NORM_BLOCK 65536      /* elements per block sum of the norm pass */
+#define STEP_WG_ELEMS 4096         /* elements per workgroup of the update */
+enum { SR_TOTAL = 0, SR_NORM = 1, SR_FACTOR = 2, SR_CLIPPED = 3, SR_APPLIED = 4, SR_N = 8 };   // tnml_ctx::st_res
+struct SiteStepArgs {
+    const ChainSite<double>* sites;    // [N] device: the site tensors, rewritten in place
+    const long long* goff;             // [N + 1] device: first element of every site in grad, m and v
+    const int* wg0;                    // [N + 1] device: first update workgroup of every site
+    int N;
+    const double* grad; size_t elems;  // the flat gradient
+    double *m, *v;                     // the state (m: Adam only)
+    double* bsum; int nblk;            // block sums of g^2
+    double* res;                       // [SR_N]
+    int method;
+    double lr, mu, beta1, beta2, o1, o2, c1, c2, eps, clip, scale;   // o = 1 - beta, c = 1 - beta^t: formed once on the host
+};
+// three launches: k_step_norm (st_nblk workgroups) and k_step_total (one thread), class step_norm; k_site_step (nwg workgroups), class site_step
+int launch_site_step(tnml_ctx* c, const SiteStepArgs& a, int nwg);
 
 // ---- kernels_eval.hip: the tallies of streamed evaluation over the results of a chunk ----
 // w [cnt][nl], pred [cnt] (what k_chain left in pk.w / pk.pred), lab [cnt] in 0..9 (the host has checked them) -> acc += the chunk's

@@ -41,6 +41,19 @@ class EvalReport:
         return "EvalReport(n=%d, ncorrect=%d, cost=%r)" % (self.n, self.ncorrect, self.cost)
 
 
+class StepReport:
+    """tnml_step_report: t (steps the optimiser state has taken, this one included), grad_norm (|scale| ||G||_2 over all sites),
+    factor (what G was multiplied by), clipped, eval (an EvalReport: in the labels mode the batch at the W before the step, in the
+    coef mode zero but for n)"""
+
+    def __init__(self, r):
+        self.t, self.grad_norm, self.factor, self.clipped = int(r.t), float(r.grad_norm), float(r.factor), bool(r.clipped)
+        self.eval = EvalReport(r.eval)
+
+    def __repr__(self):
+        return "StepReport(t=%d, grad_norm=%r, factor=%r, clipped=%r, eval=%r)" % (self.t, self.grad_norm, self.factor, self.clipped, self.eval)
+
+
 class TrainStates:
     """Training set + environments + W replica of one rank (TrainStates + MPS W of fixedL.cc)."""
 
@@ -368,6 +381,63 @@ class TrainStates:
             shape = (ml.value, 2, mr.value) + ((NL,) if hl.value else ())
             grads.append(grad[offs[j - 1]:offs[j]].reshape(shape, order="F").copy(order="F"))
         return (grads, (w, pred)) if want_weights else grads
+
+    def _split_sites(self, flat):
+        """a flat array in the layout of tnml_site_gradient_*'s grad -> a list of N arrays shaped like get_site()'s"""
+        out, at = [], 0
+        for j in range(1, self.N + 1):
+            ml, mr, hl = C.c_int(), C.c_int(), C.c_int()
+            self._ck(self._L.tnml_site_dims(self._h, j, ml, mr, hl))
+            shape = (ml.value, 2, mr.value) + ((NL,) if hl.value else ())
+            size = int(np.prod(shape))
+            out.append(flat[at:at + size].reshape(shape, order="F").copy(order="F"))
+            at += size
+        return out
+
+    def gradient_step(self, labels=None, coef=None, pixels=None, phi=None, method="sgd", lr=None, momentum=0., beta1=.9, beta2=.999,
+                      eps=1e-8, clip=0., scale=1.):
+        """one optimiser step on W on the device (tnml_site_step_u8 / tnml_site_step_phi): the gradient of site_gradient() on the same
+        arguments, summed as site_gradient() sums it, multiplied by scale, clipped to the norm clip (0: not), then
+        method "sgd": v <- momentum v + g, A <- A - lr v, or "adam" with beta1, beta2, eps and bias correction.  Neither the gradient
+        nor W crosses the bus; returns a StepReport.  The optimiser state lives on the device, is made by the first step for its
+        method and the shapes of W, and goes with step_reset().  Environments are stale afterwards, as after set_mps()."""
+        if method not in _lib.STEP_METHODS:
+            raise ValueError("method must be one of %s, got %r" % (sorted(_lib.STEP_METHODS), method))
+        if lr is None:
+            raise ValueError("lr is required")
+        x = self._streamed_input(pixels, phi, None)
+        n = int(x.shape[0])
+        lp = cp = None
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.shape != (n,):
+                raise ValueError("labels must have shape [%d], got %s" % (n, lab.shape))
+            lp = lab.ctypes.data_as(C.POINTER(C.c_int32))
+        if coef is not None:
+            cf = np.ascontiguousarray(coef, dtype=np.float64)
+            if cf.shape != (n, self.nl):
+                raise ValueError("coef must have shape [%d, %d], got %s" % (n, self.nl, cf.shape))
+            cp = _lib.dptr(cf)
+        par = _lib.StepParams(_lib.STEP_METHODS[method], float(lr), float(momentum), float(beta1), float(beta2), float(eps), float(clip), float(scale))
+        r = _lib.StepReport()
+        if pixels is not None:
+            self._ck(self._L.tnml_site_step_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), lp, cp, C.byref(par), C.byref(r)))
+        else:
+            self._ck(self._L.tnml_site_step_phi(self._h, n, _lib.dptr(x), lp, cp, C.byref(par), C.byref(r)))
+        return StepReport(r)
+
+    def step_reset(self):
+        """tnml_site_step_reset: frees the optimiser state of gradient_step(); the next step starts from t = 1"""
+        self._ck(self._L.tnml_site_step_reset(self._h))
+
+    def step_state(self, which):
+        """test entry (tnml_site_step_state): the optimiser state "m" (adam) or "v" (both methods) as a list of N arrays shaped like
+        get_site()'s"""
+        elems = C.c_int64()
+        self._ck(self._L.tnml_site_gradient_size(self._h, C.byref(elems), None))
+        buf = np.zeros(max(elems.value, 1))
+        self._ck(self._L.tnml_site_step_state(self._h, which.encode(), _lib.dptr(buf), elems.value))
+        return self._split_sites(buf)
 
     def descent_step(self, grads, cost_fn, step):
         """one step of gradient descent with backtracking, for contexts that hold no environments (a context that does must call

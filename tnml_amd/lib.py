@@ -38,6 +38,7 @@ EXPORTS = [
     "tnml_set_input_map", "tnml_get_input_map",
     "tnml_response_u8", "tnml_response_phi",
     "tnml_site_gradient_size", "tnml_site_gradient_u8", "tnml_site_gradient_phi",
+    "tnml_site_step_u8", "tnml_site_step_phi", "tnml_site_step_reset", "tnml_site_step_state",
 ]
 
 
@@ -74,6 +75,18 @@ class HeldoutReport(C.Structure):
 class EvalReport(C.Structure):
     _fields_ = [("n", C.c_int64), ("ncorrect", C.c_int64), ("cost", C.c_double), ("label_cost", C.c_double * NL),
                 ("count", C.c_int64 * NL), ("nincorrect", C.c_int64 * NL), ("confusion", (C.c_int64 * NL) * NL)]
+
+
+STEP_METHODS = {"sgd": 0, "adam": 1}    # TNML_STEP_SGD / TNML_STEP_ADAM
+
+
+class StepParams(C.Structure):
+    _fields_ = [("method", C.c_int), ("lr", C.c_double), ("momentum", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("clip", C.c_double), ("scale", C.c_double)]
+
+
+class StepReport(C.Structure):
+    _fields_ = [("t", C.c_int64), ("grad_norm", C.c_double), ("factor", C.c_double), ("clipped", C.c_int), ("eval", EvalReport)]
 
 
 class CompressReport(C.Structure):
@@ -154,6 +167,10 @@ def load():
     L.tnml_site_gradient_size.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.tnml_site_gradient_u8.argtypes = [vp, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), dp, dp, dp, C.POINTER(C.c_int32)]
     L.tnml_site_gradient_phi.argtypes = [vp, C.c_int64, dp, C.POINTER(C.c_int32), dp, dp, dp, C.POINTER(C.c_int32)]
+    L.tnml_site_step_u8.argtypes = [vp, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), dp, C.POINTER(StepParams), C.POINTER(StepReport)]
+    L.tnml_site_step_phi.argtypes = [vp, C.c_int64, dp, C.POINTER(C.c_int32), dp, C.POINTER(StepParams), C.POINTER(StepReport)]
+    L.tnml_site_step_reset.argtypes = [vp]
+    L.tnml_site_step_state.argtypes = [vp, C.c_char_p, dp, C.c_int64]
     L.tnml_set_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_get_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_replica_check.argtypes = [vp, ip]
