@@ -8,8 +8,24 @@ image: Lf[j] is everything left of site j, Rf[j] everything right of it, both wi
     resp[n, j, s] = sum_{a, r} Lf[j][n, a] A_j[a, s, r] Rf[j][n, r].
 
 W is a list of N arrays [ml, 2, mr]; at most one of them, the Label site, is [ml, 2, mr, nl].  Without one (the per-label
-variant) there is a single output and `which` must be None or all zero."""
+variant) there is a single output and `which` must be None or all zero.
+
+The bound
+---------
+Every resp[n, j, s] is a sum of products of one factor per site, so a first-order rounding analysis bounds its error by K 2^-53 x the
+same contraction on absolute values, K the number of roundings on the longest path from the inputs to an element.  For the device's
+order (kernels_response.hip), with N sites and m the largest bond, counting a rounding for every product and one for every addition:
+  * every site but j is crossed by a chain step.  An inward step (chain_step) forms fl(phi_s v[k]) and accumulates 2 m such terms: at
+    most 4 m + 1 roundings.  An outward step forms U_s from m terms (2 m) and fl(fl(phi_0 U_0) + fl(phi_1 U_1)) (2): 2 m + 2, no more
+    than 4 m + 1.  The Label site, when it is not site j, is one outward step on the chosen label: (N - 1)(4 m + 1);
+  * site j itself: U_s from m terms (2 m), then the dot with the environment over at most m rows: an fma per row of a lane (at most 4
+    per row tile), three additions over the q groups, one per row tile of the wave, eight over the waves -- never more than the 2 m of a
+    product and an addition per term, + 16 for the fixed additions when m is small: 4 m + 16.
+K_dev = (N - 1)(4 m + 1) + 4 m + 16.  The model's einsum / tensordot sums have the same term counts in another order and no more
+roundings than that: the comparison of the two is bounded with K = 2 K_dev."""
 import numpy as np
+
+U = 2.0 ** -53
 
 
 def _site_matrices(A, phi_j):
@@ -66,3 +82,17 @@ def response(W, phi, which=None):
         else:
             resp[:, j] = np.einsum("nsr,nr->ns", np.tensordot(Lf[j], W[j], axes=(1, 0)), Rf[j])
     return resp, weights, label.astype(np.int32)
+
+
+def rounding_count(N, m):
+    """K of the comparison of two fp64 evaluations of resp (the device's and the model's): see the module's header"""
+    return 2 * ((N - 1) * (4 * m + 1) + 4 * m + 16)
+
+
+def bound(W, phi, label):
+    """elementwise bound [n, N, 2] on |resp_a - resp_b| between two fp64 evaluations for the labels `label` (as response() returns
+    them): K 2^-53 x the same contraction on |A| and |phi|"""
+    W = [np.abs(np.asarray(A, dtype=np.float64)) for A in W]
+    m = max(max(A.shape[0], A.shape[2]) for A in W)
+    lab = None if not any(A.ndim == 4 for A in W) else np.asarray(label)
+    return rounding_count(len(W), m) * U * response(W, np.abs(np.asarray(phi, dtype=np.float64)), lab)[0]

@@ -37,7 +37,8 @@ U = 2.0 ** -53
 
 def mps_with_dims(dims, seed, label_site=None):
     """random weight MPS with the bond dimensions d_0 = 1, d_1, ..., d_N = 1, the Label index on site label_site (1-based; default
-    N // 2; 0: none), near-identity so that chain vectors keep their scale"""
+    N // 2; 0: none), near-identity so that chain vectors keep their scale over the ten sites of the lists below.  Over hundreds of
+    sites they do not: at N = 784 the weights reach 1e20 and the bound is nan; tests/long_chain_cases.py has the generator for those"""
     rng = np.random.default_rng(seed)
     N = len(dims) - 1
     c = N // 2 if label_site is None else label_site

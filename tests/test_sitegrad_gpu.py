@@ -89,7 +89,8 @@ def test_gradient_per_label_variant(N, mode):
 @pytest.mark.parametrize("side,imglen", [(8, 4), (28, 14)])
 def test_gradient_under_an_input_map(side, imglen):
     """raw bytes through the device input map, a 2 x 2 block mean: the bits of the feature path on the features the map defines, and
-    inside the model's bound (which has teeth at 16 sites; over 196 sites the contraction on absolute values is orders above |G|)"""
+    inside the model's bound (which has teeth at 16 sites; on this W the contraction on absolute values is orders above |G| over 196
+    sites: tests/test_long_chain_gpu.py holds the call to a bound with teeth at 196 and 784 sites under the map)"""
     from tnml_amd import synth
     from tnml_amd.input_map import InputMap
     m = InputMap.from_imglen(side, imglen, "normal")
