@@ -604,6 +604,8 @@ int tnml_synchronize(tnml_ctx* ctx);
                       fwd_res 3 = the general form on 120 x 120 bonds too
      "shift_skip"     (TNML_SHIFT_SKIP) the resident-operand shift walks a tile's images zero features first and leaves out the odd-row
                       products of 16-image groups whose phi[1] is 0 throughout (default 1; 0 = natural order, every product; same values)
+     "fwd_skip"       (TNML_FWD_SKIP) the same in the GEMM waves of the resident-operand forward pass on 120 x 120 bonds: 32-image tiles,
+                      the odd-row chain of a group left out (default 1; 0 = natural order, every product; same values)
      "grad_quad"      (TNML_GRAD_QUAD) the resident-accumulator gradient GEMM (kernels_grad.hip)
      "grad_pair"      (TNML_GRAD_PAIR) its pair form for bonds up to 64 x 64 (default 1; 0 = the quad form)
      "bgs_chol"       (TNML_BGS_CHOL) block Gram-Schmidt Cholesky QR of a kept basis of 129-384 columns (default 1; 0 = dpotrf + dtrsm)
@@ -616,7 +618,8 @@ int tnml_synchronize(tnml_ctx* ctx);
                       tnml_svd_split and tnml_mps_compress neither read nor write it (default 0; tnml_spec_predict_stats)
      "bf16_grad", "bf16_once"  the bf16 modes: gradient GEMM on the bf16 pipe / operands converted once (default 1 each)
    Tuning and test knobs (0: the default):
-     "res_pace"       (TNML_RES_PACE) 0-4, pause pattern of the GEMM waves of k_fwd_res
+     "res_pace"       (TNML_RES_PACE) 0-4, pause pattern of the GEMM waves of k_fwd_res (0: the default of the form that runs -- natural
+                      order and zero features first have their own)
      "res_grid"       workgroups of the resident-operand kernels
      "bgemm_wgs", "bgemm_per"  (TNML_BGEMM_WGS, TNML_BGEMM_PER) workgroups the gradient GEMM aims at / images per slab in units of 32
      "mc_spin_max"    polls before the workgroup cluster of the tridiagonalisation gives up (-1 default; 0 forces the fallback)
@@ -662,6 +665,9 @@ int tnml_truncate_device(tnml_ctx* ctx, const double* evals_ascending, int n, in
    are set: for site 1..N the number of 16-image groups (padded image count / 16) and how many of them hold only images with phi[1] == 0
    once each 64-image tile is walked zero features first -- the groups whose odd-row products are left out. */
 int tnml_shift_skip_stats(tnml_ctx* ctx, int site, int64_t* groups, int64_t* skipped);
+/* The same for the tile order table of the resident-operand forward pass (option "fwd_skip"; the same contexts): the groups that hold only
+   images with phi[1] == 0 once each 32-image tile is walked zero features first -- the groups whose odd-row chain is left out. */
+int tnml_fwd_skip_stats(tnml_ctx* ctx, int site, int64_t* groups, int64_t* skipped);
 /* health of the in-house eigensolver: number of fallbacks to rocSOLVER so far, number of splits whose kept basis
    held an eigenvalue cluster and was re-orthonormalised by Cholesky QR, and max|Q^T Q - I| of the kept basis
    before the first / second Newton-Schulz polish step of the last split */

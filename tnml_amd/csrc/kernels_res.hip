@@ -12,6 +12,8 @@
 //                therefore streams only ITS rows of the Label-carrying environment -- the 577 MB stream is still read exactly once.
 //                What the split costs: each workgroup holds the label dot over its own q only, so the launch leaves two partial
 //                output vectors Ppart[half][l][n]; k_pfinish adds them (fixed order) and does the per-image epilogue.
+//                On 120 x 120 bonds the GEMM waves walk a tile's images zero features first and leave out the odd-row chain of 16-image
+//                groups whose phi[1] is 0 throughout (option "fwd_skip", table of k_fwd_order; see ZS below): same values, fewer MFMAs.
 //   k_pfinish  : P = Ppart[0] + Ppart[1], then dP = delta - P, per-label cost partials, argmax count or |P|^2 (the tail of
 //                k_labeldot) per 64-image wave; k_reduce_partials sums them.  (A "last workgroup to arrive reduces" form of this kernel
 //                cost 26 us per launch instead of 8 + 5: its __threadfence() is an L2 write-back on this multi-XCD part.)
@@ -56,10 +58,82 @@ static __device__ __forceinline__ void fr_barrier() {
 // environment's first rows (cache hits) and weighs them zero, so that the hand-counted waits hold on every path.
 // GEN = false: the 120 x 120 bond of the benchmark with its extents as constants (NKA = 30).
 // NST = steps of the streaming waves per tile: 8, or 4 where no half has more than four column tiles (mO <= 64).
-template <int PS, int PK, int ABL, int NKA = 30, bool GEN = false, int NST = 8>
+// ZS (zero features first; the table of launch_fwd_order is given; the constant-extent form only): phi[1] = 0 exactly wherever a pixel is 0, and
+// then the odd-row product of that image is multiplied by zero in the epilogue.  The products are per image (the reduction runs over the link
+// index), so the GEMM waves may walk the 32 images of a tile in any order: slot j of group grp is image ord[16 grp + j], the images with
+// phi[1] == 0 first, and the first s of the tile's two 16-image groups (s rides in spare bits of the order bytes, the same for every wave and
+// both workgroups of the pair) run WITHOUT their odd-row chain and take pO-fold(phi[0] ce): fma(0, co, x) = x.  Three variants of one k-loop
+// (fr_tile_zs<.., NSK>): 4, 3 or 2 accumulator chains per wave.  A lane's two slots feed its fragment reads, its feature reads and its U
+// column; U is written at the image's natural position, so the streaming role is the same code with the same counted waits.  The GEMM waves
+// fetch the slots themselves (one 16-bit load per lane, the compiler's waits; the table is 1 byte per image and site): two k-steps before the
+// end of a tile's loop, where the fragment prefetch registers fall free, they read this tile's slots again for the epilogue and the next tile's
+// for the coming round -- nothing but one register of slots lives across the 120 MFMAs.  Registers: 168 of 168, no scratch, like natural order
+// (slots fetched at the top of a round and kept across the loop: 4 VGPRs spilled).
+// the slots 16 grp + i of a tile, one byte per group (bits 0..4: the image; bits 6, 7: the tile's leading groups of zero features only)
+static __device__ __forceinline__ unsigned fr_slots(const uint8_t* ord, int ln) { return (unsigned)*(const unsigned short*)(ord + 2 * (ln & 15)); }
+// one tile of the GEMM role, the first NSK groups without odd rows.  sl: this tile's slots (in: fetched a round ago; out: the next tile's);
+// cord, nord: the order bytes of this tile and of the next
+template <int PS, int PK, int ABL, int NKA, int NSK>
+static __device__ __forceinline__ void fr_tile_zs(const double* Eb, double* Ub, const double (&me)[NKA], const double (&mo)[NKA], int lane, int w, unsigned& sl, const uint8_t* cord, const uint8_t* nord) {
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    int g = ln >> 4;
+    unsigned sle = 0, sln = 0;
+    // (odd rows of the staged operand hold their two 16-image halves swapped: the swap goes on the slot)
+    const double* ep0 = Eb + g * FR_TI + ((sl & 31) ^ (16 * (g & 1)));                 // E[4 ks + g][image of slot i]
+    const double* ep1 = Eb + g * FR_TI + (((sl >> 8) & 31) ^ (16 * (g & 1)));          // E[4 ks + g][image of slot 16 + i]
+    f64x4r ce0 = {0., 0., 0., 0.}, co0 = {0., 0., 0., 0.}, ce1 = {0., 0., 0., 0.}, co1 = {0., 0., 0., 0.};
+    double a0 = ep0[0], b0 = ep1[0], a1 = ep0[4 * FR_TI], b1 = ep1[4 * FR_TI];
+    __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+#pragma unroll
+    for (int ks = 0; ks < (ABL == 2 ? 1 : NKA); ++ks) {
+        const double xa = a0, xb = b0;
+        a0 = a1; b0 = b1;
+        if (ks + 2 < NKA) { a1 = ep0[4 * (ks + 2) * FR_TI]; b1 = ep1[4 * (ks + 2) * FR_TI]; __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); }
+        ce0 = __builtin_amdgcn_mfma_f64_16x16x4f64(me[ks], xa, ce0, 0, 0, 0);
+        if (NSK < 1) co0 = __builtin_amdgcn_mfma_f64_16x16x4f64(mo[ks], xa, co0, 0, 0, 0);
+        ce1 = __builtin_amdgcn_mfma_f64_16x16x4f64(me[ks], xb, ce1, 0, 0, 0);
+        if (NSK < 2) co1 = __builtin_amdgcn_mfma_f64_16x16x4f64(mo[ks], xb, co1, 0, 0, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 4 - NSK, 0);
+        if (PS > 0 && ks % PK == PK - 1) { __builtin_amdgcn_s_sleep(PS); __builtin_amdgcn_sched_barrier(0); }
+        // two k-steps before the end the fragment prefetch registers fall free: this tile's slots again (for the epilogue) and the next
+        // tile's, two k-steps and an epilogue ahead of their use
+        if (ks == (ABL == 2 ? 0 : NKA - 2)) {
+            ln = lane;
+            asm volatile("" : "+v"(ln));
+            sle = fr_slots(cord, ln); sln = fr_slots(nord, ln);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    // lane (g, i) holds rows g + 4e of its tile for the images of its two slots: output links q = 8 ct + g (e = 0, 2: t = 0, 1) and q + 4 (e = 1, 3)
+    ln = lane;
+    asm volatile("" : "+v"(ln));
+    g = ln >> 4;
+    sl = sln;
+#pragma unroll
+    for (int grp = 0; grp < 2; ++grp) {
+        const int im = (sle >> (8 * grp)) & 31;
+        const double pI0 = Eb[(4 * NKA) * FR_TI + im];
+        const double pO0 = Eb[(4 * NKA + 2) * FR_TI + im], pO1 = Eb[(4 * NKA + 3) * FR_TI + (im ^ 16)];
+        const f64x4r ce = grp ? ce1 : ce0, co = grp ? co1 : co0;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            double t0, t1;
+            if (grp < NSK) { t0 = pI0 * ce[e]; t1 = pI0 * ce[e + 2]; }                  // (phi[1] == 0: fma(0, co, x) = x)
+            else {
+                const double pI1 = Eb[(4 * NKA + 1) * FR_TI + (im ^ 16)];
+                t0 = fma(pI1, co[e], pI0 * ce[e]); t1 = fma(pI1, co[e + 2], pI0 * ce[e + 2]);
+            }
+            Ub[(8 * w + g + 4 * e) * FR_TI + im] = fma(pO1, t1, pO0 * t0);
+        }
+    }
+}
+
+template <int PS, int PK, int ABL, int NKA = 30, bool GEN = false, int NST = 8, bool ZS = false>
 __global__ __launch_bounds__(768) void k_fwd_res(FwdResArgs A) {
     static_assert(GEN || NKA == 30, "the constant-extent form is the 120 x 120 bond");
     static_assert(NST == 8 || (NST == 4 && GEN), "four or eight streaming steps per tile");
+    static_assert(!ZS || !GEN, "zero features first: the constant-extent form");
     constexpr int EIS = FR_EIS(NKA);
     const int mI = GEN ? A.mI : 120, mO = GEN ? A.mO : 120, Kp = GEN ? A.Kp : 240, Np = GEN ? A.Np : 240;
     extern __shared__ __attribute__((aligned(16))) double fr_lds[];
@@ -98,13 +172,29 @@ __global__ __launch_bounds__(768) void k_fwd_res(FwdResArgs A) {
                 mo[ks] = in ? A.M[(size_t)(2 * (4 * ks + g) + 1) * Np + col] : 0.;
             }
         }
+        unsigned sl = 0;                         // ZS: this lane's two slots of the coming tile
+        if constexpr (ZS) { if (act) sl = fr_slots(A.ord + (size_t)pair * FR_TI, lane); }
         fr_barrier();                            // prologue: the first tile's image operand is in X[0]
         long long t_mma = 0, t_epi = 0, t_bar = 0;
         const long long wc0 = ABL == 5 ? (long long)wall_clock64() : 0;
         for (int it = 0; it < niter + 2; ++it) {
             const long long c0 = ABL == 5 ? clock64() : 0;
             long long c1 = c0, c2 = c0;
-            if (it < niter && act) {
+            if constexpr (ZS) {
+                if (it < niter && act) {
+                    const double* Eb = EIs + (it & 1) * EIS;
+                    double* Ub = Us + (it & 1) * 64 * FR_TI;
+                    const uint8_t* cord = A.ord + (size_t)(pair + it * npairs) * FR_TI;
+                    const uint8_t* nord = it + 1 < niter ? cord + (size_t)npairs * FR_TI : cord;       // (no next tile: this one again)
+                    // (ABL 6, probe builds only: the order is walked and no group is skipped -- what the permuted reads cost by themselves)
+                    const int s = ABL == 6 ? 0 : __builtin_amdgcn_readfirstlane((int)((sl >> 6) & 3));      // groups 0 .. s - 1: zero features only
+                    switch (s) {
+                        case 0:  fr_tile_zs<PS, PK, ABL, NKA, 0>(Eb, Ub, me, mo, lane, w, sl, cord, nord); break;
+                        case 1:  fr_tile_zs<PS, PK, ABL, NKA, 1>(Eb, Ub, me, mo, lane, w, sl, cord, nord); break;
+                        default: fr_tile_zs<PS, PK, ABL, NKA, 2>(Eb, Ub, me, mo, lane, w, sl, cord, nord); break;
+                    }
+                }
+            } else if (it < niter && act) {
                 const double* Eb = EIs + (it & 1) * EIS;
                 double* Ub = Us + (it & 1) * 64 * FR_TI;
                 // (the lane index passes through an empty asm before the MFMA loop and again before the epilogue: everything derived
@@ -636,6 +726,33 @@ int launch_shift_order(tnml_ctx* c, const double* phi, int N, int NTp, uint8_t* 
     HIPCK(c, hipGetLastError());
     return 0;
 }
+// ---- tile order table of k_fwd_res (ZS) ----
+// One wave per (site, 64 images = two 32-image tiles).  Per tile: the stable partition of 0..31 with the images whose stored phi[1] equals 0.0
+// first (padding images are classified by the value stored for them, like real ones); slot 16 grp + i is byte 2 i + grp of the tile (a GEMM
+// lane fetches its two slots with one 16-bit load): bits 0..4 the image, bits 6, 7 of EVERY byte nz / 16 = 0..2, the number of leading
+// 16-image groups that run without odd rows; the site's counter takes that number (integer atomics: the sum does not depend on the order).
+__global__ __launch_bounds__(256) void k_fwd_order(const double* __restrict__ phi, int N, int NTp, uint8_t* __restrict__ ord, int* __restrict__ cnt) {
+    const int lane = threadIdx.x & 63, tpl = NTp / 64;
+    const size_t wave = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wave >= (size_t)N * tpl) return;                        // (uniform per wave)
+    const int j = (int)(wave / tpl), ti = (int)(wave - (size_t)j * tpl);
+    const bool z = phi[((size_t)j * 2 + 1) * NTp + (size_t)ti * 64 + lane] == 0.0;
+    const int h = lane >> 5, im = lane & 31;
+    const unsigned mz = (unsigned)(__ballot(z) >> (32 * h)), below = (1u << im) - 1;
+    const int nzc = __popc(mz);
+    const int slot = z ? __popc(mz & below) : nzc + __popc(~mz & below);
+    ord[(size_t)j * NTp + (size_t)ti * 64 + FR_TI * h + 2 * (slot & 15) + (slot >> 4)] = (uint8_t)(im | (nzc >> 4) << 6);
+    if (im == 0 && nzc >= 16) atomicAdd(cnt + j, nzc >> 4);
+}
+int launch_fwd_order(tnml_ctx* c, const double* phi, int N, int NTp, uint8_t* ord, int* cnt) {
+    if (NTp % 64) return tnml_fail(c, "fwd_order: image count not a multiple of 64");
+    ProfScope ps(c, KC_PACK);
+    HIPCK(c, hipMemsetAsync(cnt, 0, sizeof(int) * N, c->stream));
+    const size_t waves = (size_t)N * (NTp / 64);
+    hipLaunchKernelGGL(k_fwd_order, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, c->stream, phi, N, NTp, ord, cnt);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
 
 // wave-level cost buckets of 64 images -> out[12] (the epilogue of k_labeldot / k_fwd_fused)
 static __device__ __forceinline__ void res_wave_partials(double val, int lab, int cor, bool pap, double* out, int lane) {
@@ -697,18 +814,28 @@ __global__ __launch_bounds__(256) void k_pfinish(PfinishArgs A) {
     res_wave_partials(val, lab, cor, A.mode == LD_MODE_PAP, A.partials + ((size_t)blockIdx.x * 4 + (tid >> 6)) * 12, lane);
 }
 
-template <int PS, int PK, int NKA, bool GEN, int NST = 8>
+// (probe builds only: -DFR_PROBE_ABL=6 launches the zero-first form with no group skipped, see k_fwd_res)
+#ifndef FR_PROBE_ABL
+#define FR_PROBE_ABL 0
+#endif
+template <int PS, int PK, int NKA, bool GEN, int NST = 8, bool ZS = false>
 static int fwd_res_go(tnml_ctx* c, const FwdResArgs& a, int grid) {
     const size_t lds = sizeof(double) * FR_LDS_DOUBLES_N(NKA);
+    constexpr int ABL = ZS ? FR_PROBE_ABL : 0;
     bool& done = c->attr_fr[2 * (GEN ? 1 : 0) + (NST == 4 ? 1 : 0)][NKA];
-    if (!done || !GEN) {                              // (the constant-extent form has one slot for its five pacings: set every time, as before)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_fwd_res<PS, PK, 0, NKA, GEN, NST>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (!done || !GEN) {                              // (the constant-extent form has one slot for its pacings and orders: set every time, as before)
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_fwd_res<PS, PK, ABL, NKA, GEN, NST, ZS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return tnml_fail(c, "fwd_res: cannot reserve %zu bytes of LDS", lds);
         done = true;
     }
     ProfScope ps(c, KC_FWD_RES);
-    hipLaunchKernelGGL((k_fwd_res<PS, PK, 0, NKA, GEN, NST>), dim3(grid), dim3(768), lds, c->stream, a);
+    hipLaunchKernelGGL((k_fwd_res<PS, PK, ABL, NKA, GEN, NST, ZS>), dim3(grid), dim3(768), lds, c->stream, a);
     return 0;
+}
+// the constant-extent form in natural order or, given the order table, zero features first
+template <int PS, int PK>
+static int fwd_res_go120(tnml_ctx* c, const FwdResArgs& a, int grid) {
+    return a.ord ? fwd_res_go<PS, PK, 30, false, 8, true>(c, a, grid) : fwd_res_go<PS, PK, 30, false>(c, a, grid);
 }
 // the instantiations built for other bonds than 120 x 120: input dimensions up to 4 NKA
 static const int fr_nka_list[] = {12, 16, 18, 20, 22, 24, 26, 28, 30};
@@ -730,15 +857,18 @@ int launch_fwd_res(tnml_ctx* c, const FwdResArgs& a) {
     while (grid > 16 && (grid / 2) > a.ntiles) grid -= 16;                        // every pair of workgroups has at least one tile
     // pacing of the GEMM waves (see k_fwd_res): 384 cycles every 8 MFMAs measured best (tools/probe/kbench_res.hip,
     // profiles/r04_probe_fwd_res.txt); option "res_pace" selects the others (120 x 120 bonds only)
+    // zero features first (a.ord): 384 cycles every third k-step measured best of the five (profiles/fwd_zero_skip_a_b.txt) -- a k-step has
+    // 2..4 MFMAs there, not 4
     if (a.mI == 120 && a.mO == 120 && a.Kp == 240 && a.Np == 240 && c->fwd_res != 3) {
-        switch (c->res_pace) {
-            case 1:  TCK((fwd_res_go<0, 1, 30, false>(c, a, grid))); break;      // no pauses
-            case 2:  TCK((fwd_res_go<4, 2, 30, false>(c, a, grid))); break;
-            case 3:  TCK((fwd_res_go<6, 3, 30, false>(c, a, grid))); break;
-            case 4:  TCK((fwd_res_go<4, 1, 30, false>(c, a, grid))); break;
-            default: TCK((fwd_res_go<6, 2, 30, false>(c, a, grid))); break;
+        switch (c->res_pace ? c->res_pace : (a.ord ? 3 : 0)) {
+            case 1:  TCK((fwd_res_go120<0, 1>(c, a, grid))); break;      // no pauses
+            case 2:  TCK((fwd_res_go120<4, 2>(c, a, grid))); break;
+            case 3:  TCK((fwd_res_go120<6, 3>(c, a, grid))); break;
+            case 4:  TCK((fwd_res_go120<4, 1>(c, a, grid))); break;
+            default: TCK((fwd_res_go120<6, 2>(c, a, grid))); break;
         }
-    } else if (a.Np <= 128) {                                                       // mO <= 64: at most four column tiles per half, four streaming steps per tile
+    } else if (a.Np <= 128) {                                                       // (the general forms keep natural order whatever a.ord says)
+        // mO <= 64: at most four column tiles per half, four streaming steps per tile
         switch (fr_nka_for(a.mI)) {
             case 12: TCK((fwd_res_go<6, 2, 12, true, 4>(c, a, grid))); break;
             case 16: TCK((fwd_res_go<6, 2, 16, true, 4>(c, a, grid))); break;

@@ -104,6 +104,8 @@ int forward_pass(tnml_ctx* c, const double* vec, int mode, double* tail, bool wa
             (c->fwd_res >= 2 || c->NTp >= 7680) &&
             (size_t)TNML_NL * ustride * sizeof(double) < ((size_t)1 << 32)) {           // (32-bit lane offsets of k_fwd_res: larger shards fall through to the kernels below)
             FwdResArgs fr{(const double*)p.EI, (const double*)p.phiI, vec, (const double*)p.phiO, (const double*)p.EX, ustride, c->NTp, c->NTp / 32, c->Ppart, p.mI, p.mO, p.Kp, p.Np};
+            // zero features first in the GEMM waves (120 x 120 bonds): the order table of the site whose feature is phiI -- site b, or b + 1 with the Label on the left
+            if (c->fwd_skip && c->zf_ord) fr.ord = c->zf_ord + (size_t)((p.kind == 1 ? p.b + 1 : p.b) - 1) * c->NTp;
             TCK(launch_fwd_res(c, fr));
             PfinishArgs pf{2, c->Ppart, nullptr, nullptr, nullptr, nullptr, c->label, c->NTp, (double*)a.P, (double*)a.dP, mode, c->partials, c->counters, tail, mode == LD_MODE_PAP ? 1 : 0};
             TCK(launch_pfinish(c, pf));

@@ -95,6 +95,7 @@ static const OptDef k_options[] = {
     {"fwd_res",          "TNML_FWD_RES",        OPT_INT,  &tnml_ctx::fwd_res,             nullptr,          0, 3,       HK_NONE},   // 3: the general form on 120 x 120 bonds too
     {"shift_res",        "TNML_SHIFT_RES",      OPT_INT,  &tnml_ctx::shift_res,           nullptr,          0, 2,       HK_NONE},
     {"shift_skip",       "TNML_SHIFT_SKIP",     OPT_BOOL, &tnml_ctx::shift_skip,          nullptr,          0, 1,       HK_NONE},
+    {"fwd_skip",         "TNML_FWD_SKIP",       OPT_BOOL, &tnml_ctx::fwd_skip,            nullptr,          0, 1,       HK_NONE},
     {"res_grid",         nullptr,               OPT_INT,  &tnml_ctx::res_grid,            nullptr,          0, INT_MAX, HK_NONE},
     {"res_pace",         "TNML_RES_PACE",       OPT_INT,  &tnml_ctx::res_pace,            nullptr,          0, 4,       HK_NONE},
     {"grad_quad",        "TNML_GRAD_QUAD",      OPT_INT,  &tnml_ctx::grad_quad,           nullptr,          0, 2,       HK_NONE},
@@ -295,6 +296,7 @@ static std::vector<DevBuf> device_buffers(tnml_ctx* c) {
     // tile order tables of k_shift_res (input dimensions 33..120, fp64-stored environments): one byte per site and image, one per site and 64-image tile
     const bool zs = c->cfg.dtype == TNML_F64 && c->cfg.mode == TNML_MODE_FIXEDL && m >= 33;
     add(c->zs_ord, c->N * NTp, zs); add(c->zs_nz, c->N * (NTp / 64), zs); add(c->zs_cnt, c->N * sizeof(int), zs);
+    add(c->zf_ord, c->N * NTp, zs); add(c->zf_cnt, c->N * sizeof(int), zs);        // the order table of k_fwd_res's 32-image tiles: one byte per site and image
     add(c->ebt, c->ebt_cap * sizeof(unsigned short), c->bf16() != 0); add(c->mbt, c->mbt_cap * sizeof(unsigned short), c->bf16() != 0);
     add(c->vB, c->mcap * D); add(c->vR, c->mcap * D); add(c->vP, c->mcap * D); add(c->arbuf, (c->mcap + TNML_TAILN) * D); add(c->locals, 32 * D);
     add(c->scal, (SC_N + 4 * TNML_MAX_PASS) * D);      // CG scalars, then the per-pass trace: one copy to the host

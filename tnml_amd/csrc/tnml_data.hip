@@ -23,7 +23,20 @@ static int shift_order_build(tnml_ctx* c) {
     TCK(launch_shift_order(c, (const double*)c->phi, c->N, c->NTp, c->zs_ord, c->zs_nz, c->zs_cnt));
     c->zs_groups.assign(c->N, 0);
     HIPCK(c, hipMemcpyAsync(c->zs_groups.data(), c->zs_cnt, sizeof(int) * c->N, hipMemcpyDeviceToHost, c->stream));
+    if (c->zf_ord) {                                  // the table of k_fwd_res's 32-image tiles
+        TCK(launch_fwd_order(c, (const double*)c->phi, c->N, c->NTp, c->zf_ord, c->zf_cnt));
+        c->zf_groups.assign(c->N, 0);
+        HIPCK(c, hipMemcpyAsync(c->zf_groups.data(), c->zf_cnt, sizeof(int) * c->N, hipMemcpyDeviceToHost, c->stream));
+    }
     SYNCK(c, c->stream);
+    return 0;
+}
+int tnml_fwd_skip_stats(tnml_ctx* c, int site, int64_t* groups, int64_t* skipped) {
+    if (!c) return tnml_fail(c, "tnml_fwd_skip_stats: null argument");
+    if (site < 1 || site > c->N) return tnml_fail(c, "tnml_fwd_skip_stats: site %d out of range", site);
+    if (!c->zf_ord || !c->data_set || c->zf_groups.size() != (size_t)c->N) return tnml_fail(c, "tnml_fwd_skip_stats: this context has no tile order tables (fp64 storage, fixedL, maxm >= 33, data set)");
+    if (groups) *groups = (int64_t)(c->NTp / 16);
+    if (skipped) *skipped = c->zf_groups[site - 1];
     return 0;
 }
 int tnml_shift_skip_stats(tnml_ctx* c, int site, int64_t* groups, int64_t* skipped) {

@@ -252,6 +252,9 @@ struct tnml_ctx {
     int shift_skip = 1;              // k_shift_res walks a tile's images zero features first and leaves out the odd-row products of 16-image groups whose phi[1] is 0 throughout (tables zs_ord / zs_nz, built when the data are set); 0: natural order, every product; option "shift_skip", env TNML_SHIFT_SKIP
     uint8_t* zs_ord = nullptr; uint8_t* zs_nz = nullptr; int* zs_cnt = nullptr;   // [N][NTp / 64][64], [N][NTp / 64], [N]: launch_shift_order (fp64-stored fixedL contexts with maxm >= 33)
     std::vector<int> zs_groups;      // host copy of zs_cnt (tnml_shift_skip_stats)
+    int fwd_skip = 1;                // the GEMM waves of k_fwd_res (constant-extent form) walk a tile's images zero features first and leave out the odd-row chain of 16-image groups whose phi[1] is 0 throughout (table zf_ord, built with the shift's); 0: natural order, every product; option "fwd_skip", env TNML_FWD_SKIP
+    uint8_t* zf_ord = nullptr; int* zf_cnt = nullptr;   // [N][NTp / 32][32], [N]: launch_fwd_order (the same contexts as zs_ord)
+    std::vector<int> zf_groups;      // host copy of zf_cnt (tnml_fwd_skip_stats)
     int res_grid = 0;                // test knob: workgroups of the resident-operand kernels (0: one per CU); option "res_grid"
     int grad_quad = 1;               // gradient GEMM on k_grad_quad (kernels_grad.hip; m = 120, fp64 storage, Label on an environment): 1 = from 4 096 images per rank on, 0 never, 2 always; option "grad_quad", env TNML_GRAD_QUAD
     bool attr_gq = false, attr_gp = false;
@@ -497,6 +500,7 @@ struct FwdResArgs {
     double* Ppart;                                    // out: [2][10][NTp], the label dot over the output links of each half
     int mI = 120, mO = 120, Kp = 240, Np = 240;       // bond dimensions and the M-layout extents Kp = ru16(2 mI), Np = ru16(2 mO)
     long long* dbg = nullptr;                         // probe builds: per-wave cycle counters of workgroup 0
+    const uint8_t* ord = nullptr;                     // tile order of the site of phiI [NTp / 32][32] (launch_fwd_order; spare bits: nz / 16); null: natural image order, every product computed
 };
 bool fwd_res_applies(int mI, int mO);
 int launch_fwd_res(tnml_ctx* c, const FwdResArgs& a);
@@ -529,6 +533,8 @@ int launch_shift_res(tnml_ctx* c, const ShiftResArgs& a);
 // tile order tables of every site from the stored features phi [N][2][NTp] (fp64): ord [N][NTp / 64][64], nz [N][NTp / 64], and per site the
 // number of 16-image groups whose images all have phi[1] == 0 -> cnt [N] (device)
 int launch_shift_order(tnml_ctx* c, const double* phi, int N, int NTp, uint8_t* ord, uint8_t* nz, int* cnt);
+// the same for the 32-image tiles of k_fwd_res: ord [N][NTp / 32][32] (slot 16 grp + i at byte 2 i + grp), cnt [N] (device)
+int launch_fwd_order(tnml_ctx* c, const double* phi, int N, int NTp, uint8_t* ord, int* cnt);
 
 // ---- kernels_small.hip --------------------------------------------------------------------
 struct PackDesc {       // M[l][2x+s][TO==2 ? 2y+t : y] <-> T[off + x*sx + s*ss + y*sy + t*st + l*sl]

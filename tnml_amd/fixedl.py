@@ -221,6 +221,13 @@ class TrainStates:
         self._ck(self._L.tnml_shift_skip_stats(self._h, int(j), C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def fwd_skip_stats(self, j):
+        """site j (1..N): (16-image groups, groups of zero features only once each 32-image tile is walked zero features first) --
+        the share of odd-row products the resident-operand forward pass leaves out (tnml_fwd_skip_stats)"""
+        a, b = C.c_int64(), C.c_int64()
+        self._ck(self._L.tnml_fwd_skip_stats(self._h, int(j), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def device_bytes(self):
         return self._L.tnml_device_bytes(self._h)
 

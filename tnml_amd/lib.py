@@ -28,7 +28,7 @@ EXPORTS = [
     "tnml_shard_bounds", "tnml_profile_enable", "tnml_profile_select", "tnml_profile_count", "tnml_profile_get",
     "tnml_profile_reset", "tnml_synchronize", "tnml_device_bytes", "tnml_svd_stats", "tnml_classify", "tnml_replica_check",
     "tnml_estimate_bytes", "tnml_device_memory", "tnml_plan_maxm", "tnml_set_option", "tnml_comm_init_local", "tnml_comm_init_oneshot", "tnml_collective_mode", "tnml_bond_update_begin", "tnml_bond_update_end", "tnml_replica_repairs", "tnml_pAp", "tnml_collective_stats", "tnml_last_warning",
-    "tnml_exact", "tnml_set_option_real", "tnml_pinv", "tnml_env_stats", "tnml_oneshot_export", "tnml_oneshot_connect", "tnml_oneshot_mem_kind", "tnml_split_stats", "tnml_oneshot_region_bytes", "tnml_shift_skip_stats",
+    "tnml_exact", "tnml_set_option_real", "tnml_pinv", "tnml_env_stats", "tnml_oneshot_export", "tnml_oneshot_connect", "tnml_oneshot_mem_kind", "tnml_split_stats", "tnml_oneshot_region_bytes", "tnml_shift_skip_stats", "tnml_fwd_skip_stats",
     "tnml_spec_predict_stats", "tnml_truncate_device", "tnml_cg_state",
     "tnml_lin_create", "tnml_lin_destroy", "tnml_lin_last_error", "tnml_lin_set_data_u8", "tnml_lin_set_data_f64", "tnml_lin_set_labels",
     "tnml_lin_cg_start", "tnml_lin_cg_run", "tnml_lin_get_v", "tnml_lin_evaluate",
@@ -190,6 +190,7 @@ def load():
     L.tnml_spec_predict_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.tnml_truncate_device.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, ip, ip]
     L.tnml_shift_skip_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.tnml_fwd_skip_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.tnml_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     L.tnml_estimate_bytes.argtypes = [C.POINTER(Config)]
     L.tnml_estimate_bytes.restype = C.c_int64
