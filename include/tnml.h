@@ -34,6 +34,7 @@ extern "C" {
 
 #define TNML_NL 10           /* label dimension, fixedL.cc:15 */
 #define TNML_MAX_PASS 64
+enum { TNML_LOSS_QUADRATIC = 0, TNML_LOSS_SOFTMAX = 1 };   /* option "loss": the loss of tnml_evaluate_* and of the labels mode of tnml_site_gradient_* / tnml_site_step_* */
 enum { TNML_PREDICT_F64 = 0, TNML_PREDICT_F32 = 1 };   /* option "predict_dtype": arithmetic of tnml_predict_u8 / tnml_predict_phi */
 #define TNML_PREDICT_CHUNK_DEFAULT 8192   /* option "predict_chunk": images per chunk of tnml_predict_u8 / tnml_predict_phi */
 
@@ -374,7 +375,14 @@ int tnml_predict_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/, 
  * untouched; n = 0 succeeds with a zeroed report.
  * Workspace: that of tnml_predict_* for the input form, plus -- from the first tnml_evaluate_* call on, counted by tnml_device_bytes and
  * freed with the predict workspace (re-made with it when predict_chunk changes) --
- *             4 C + 1040                    bytes (the labels of a chunk; the accumulator block: label_cost, count, nincorrect, confusion). */
+ *             4 C + 1040                    bytes (the labels of a chunk; the accumulator block: label_cost, count, nincorrect, confusion).
+ * Option "loss" = TNML_LOSS_SOFTMAX (refused in TNML_MODE_SINGLE) changes what k_eval_tally forms from an image's weights, and nothing
+ * else: the image's term is the softmax cross-entropy C = log sum_l exp(beta (W_l - max W)) - beta (W_y - max W), beta = "loss_beta",
+ * in the fixed arithmetic of tnml_amd/csrc/loss_dev.h (DESIGN.md states it; under predict_dtype = 1 in fp64 from the widened fp32
+ * weights), summed in the order stated above; ncorrect, nincorrect and confusion count the signed decision d = the first maximum of
+ * W_l.  The pred array the call returns stays tnml_predict_*'s, bit for bit (the first maximum of |W_l|, the reference's rule), and so
+ * do weights: the two decisions differ on an image whose largest |W_l| is a negative output, which a softmax loss rewards for a wrong
+ * label and the |W| rule then picks.  Chain launches, chunking, workspace and refusals are untouched. */
 typedef struct {
     int64_t n;                               /* images evaluated */
     int64_t ncorrect;                        /* decision rule of tnml_classify for the context's mode */
@@ -456,13 +464,20 @@ int tnml_response_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/,
  *                                                         tape regions, site starts, output blocks)
  *           + 8 E                                         bytes, the gradient until it is copied back (grown when W has grown)
  *           + 16 B C                                      bytes of the two tapes (grown when W has grown; 0.8 GB at N = 784, m = 120, C = 512)
- *           + 2 N C  /  S C + 2 N C + 16 ncodes  /  32 N C   bytes of staging from the first call of that input form on, as predict's. */
+ *           + 2 N C  /  S C + 2 N C + 16 ncodes  /  32 N C   bytes of staging from the first call of that input form on, as predict's.
+ * Option "loss" = TNML_LOSS_SOFTMAX changes the labels mode alone: the thread that owns the image forms, from its ten weights,
+ * c_nl = beta (softmax_l(beta W(x_n)) - [l == label_n]) in the fixed arithmetic of tnml_amd/csrc/loss_dev.h (beta = "loss_beta"), so that G is
+ * dC/dA of the cost tnml_evaluate_* reports under the same option.  The coef mode, weights, pred, both walks, the GEMM, its order,
+ * the workspace and every refusal are untouched; a weight that is not finite makes the image's coefficients NaN.
+ * tnml_site_gradient_coef is a test entry like tnml_cg_state: the coefficients [cnt][nl] of the LAST chunk of the last gradient or
+ * step call, as given or as formed; count must be cnt nl; refused before any such call since the workspace was made. */
 #define TNML_GRADIENT_CHUNK_DEFAULT 512    /* option "gradient_chunk" */
 int tnml_site_gradient_size(tnml_ctx* ctx, int64_t* elems, int64_t* offsets /*[N+1] or NULL*/);
 int tnml_site_gradient_u8 (tnml_ctx* ctx, int64_t n, const uint8_t* pixels, const int32_t* labels /*[n] or NULL*/, const double* coef /*[n][nl] or NULL*/,
                            double* grad /*[elems]*/, double* weights /*[n][nl] or NULL*/, int32_t* pred /*[n] or NULL*/);
 int tnml_site_gradient_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/, const int32_t* labels, const double* coef,
                            double* grad, double* weights, int32_t* pred);
+int tnml_site_gradient_coef(tnml_ctx* ctx, double* out /*[cnt][nl]*/, int64_t count);
 
 /* ---- gradient steps on the device: SGD with momentum and Adam on the streamed site gradient ---------------------------
  * One call is one optimiser step on W.  The gradient G of the n images is summed on the device exactly as tnml_site_gradient_* sums
@@ -501,6 +516,9 @@ int tnml_site_gradient_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][
  * training context with a held-out context attached; on a context of a multi-rank run (nranks != 1: no collective is entered, the
  * replicas would part); with p NULL or a parameter outside its range (the message names it).  n = 0 succeeds: no step is taken, the
  * report is zeroed.
+ * Option "loss" = TNML_LOSS_SOFTMAX: in the labels mode the gradient is tnml_site_gradient_*'s under that option and eval is
+ * tnml_evaluate_*'s under it (cross-entropy cost, signed decision).  The optimiser, the coef mode, the state and the refusals are
+ * untouched; coefficients that are NaN (a weight that is not finite) make total not finite, and the step is refused as above.
  * tnml_site_step_state is a test entry like tnml_cg_state: "m" (Adam) or "v" (both methods), count = E doubles. */
 #define TNML_STEP_SGD  0
 #define TNML_STEP_ADAM 1
@@ -636,6 +654,8 @@ int tnml_synchronize(tnml_ctx* ctx);
    Memory and transport:
      "predict_chunk"  images per trip of the host loop of tnml_predict_* = per launch of the chain kernel (1..2^20, default 8192); sizes its workspace
      "response_chunk" images per trip of the host loop of tnml_response_* = per launch of k_response (1..2^20, default 1024); sizes its workspace
+     "loss"           the loss of tnml_evaluate_* and of the labels mode of tnml_site_gradient_* / tnml_site_step_*: 0 (TNML_LOSS_QUADRATIC, default)
+                      sum (W_l - y_l)^2; 1 (TNML_LOSS_SOFTMAX) softmax cross-entropy on the logits loss_beta W_l, refused in TNML_MODE_SINGLE; any other value is refused
      "gradient_chunk" images per trip of the host loop of tnml_site_gradient_* = per launch of k_site_backward and k_site_grad (1..2^20, default 512); sizes its workspace
      "env_budget_mb"  cap on the environment slabs held on the device, the rest spills to host memory (0: none)
      "env_async"      the host tier's copies beside the compute stream (default 1)
@@ -644,7 +664,10 @@ int tnml_synchronize(tnml_ctx* ctx);
 int tnml_set_option(tnml_ctx* ctx, const char* name, int value);
 /* real-valued options: "pcut" (PCut of the exact solver inside tnml_bond_update, single.cc:50, default 1E-8);
    "noise" (TNML_MODE_SINGLE, fp64 storage: the noise of the sweeps, single.cc:25,222 -- from 1E-14 on tnml_svd_split / tnml_bond_update split
-   through the density matrix of site c plus noise * sum_n dr_n dr_n^dag, single.h:648-672: W_c = UU, W_{c+dc} = UU * B) */
+   through the density matrix of site c plus noise * sum_n dr_n dr_n^dag, single.h:648-672: W_c = UU, W_{c+dc} = UU * B);
+   "loss_beta" (the inverse temperature of option "loss" = TNML_LOSS_SOFTMAX: the logits are loss_beta W_l; default 1, must be finite and > 0.
+   A W trained by the sweep has outputs in about [0, 1], where 1 gives nearly flat probabilities).  Neither "loss" nor "loss_beta" has an
+   environment variable. */
 int tnml_set_option_real(tnml_ctx* ctx, const char* name, double value);
 /* The speculative split (minm >= the columns the split may keep: no host synchronisation inside tnml_bond_update_begin): how many splits
    ran speculatively, how many were ROLLED BACK by tnml_bond_update_end because their deferred orthogonality check failed (each repeats

@@ -13,15 +13,20 @@
 //   integers  count, nincorrect and confusion are counted in LDS with integer atomics and added to the accumulator block by one thread
 //             per counter: exact, whatever the chunking.
 // Plain loads and stores; the single workgroup exchanges nothing with any other and waits for nothing.
+//
+// k_eval_tally<1> (option "loss" = TNML_LOSS_SOFTMAX; never the per-label variant): the image's term is the cross-entropy C of loss_dev.h
+// in place of the sum of squares, added into the same partial sums and carried through the same tree and chunk order; nincorrect and
+// confusion count the signed decision d of loss_dev.h, not pred.  k_eval_tally<0> is the code as it was.
 #include <hip/hip_runtime.h>
 
-#include "tnml_internal.h"
+#include "loss_dev.h"
 
 #define EVAL_THREADS 256
 #define EVAL_NCNT (2 * TNML_NL + TNML_NL * TNML_NL)      // LDS counters: count | nincorrect | confusion
 
+template <int LOSS>
 __global__ __launch_bounds__(EVAL_THREADS) void k_eval_tally(const double* __restrict__ w, const int* __restrict__ pred, const int* __restrict__ lab,
-                                                             int cnt, int nl, int single, int target, EvalAcc* __restrict__ acc) {
+                                                             int cnt, int nl, int single, int target, double beta, EvalAcc* __restrict__ acc) {
     __shared__ double red[TNML_NL][EVAL_THREADS];
     __shared__ int tally[EVAL_NCNT];
     const int t = threadIdx.x;
@@ -31,9 +36,19 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_eval_tally(const double* __res
 #pragma unroll
     for (int l = 0; l < TNML_NL; ++l) s[l] = 0.;
     for (int i = t; i < cnt; i += EVAL_THREADS) {
-        const int y = lab[i], p = pred[i];
+        const int y = lab[i];
+        int p = pred[i];
         bool wrong;
-        if (single) {
+        if constexpr (LOSS == 1) {
+            const double* wi = w + (size_t)i * nl;
+            double wv[TNML_NL];
+#pragma unroll
+            for (int l = 0; l < TNML_NL; ++l) wv[l] = wi[l];
+            const double per = loss_softmax(wv, y, beta, &p);
+#pragma unroll
+            for (int l = 0; l < TNML_NL; ++l) s[l] += l == y ? per : 0.;
+            wrong = p != y;
+        } else if (single) {
             const int yt = y == target ? 1 : 0;
             const double d = w[i] - (double)yt, dd = d * d;
 #pragma unroll
@@ -71,11 +86,13 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_eval_tally(const double* __res
     }
 }
 
-int launch_eval_tally(tnml_ctx* c, const double* w, const int* pred, const int* lab, int cnt, int nl, int single, int target, EvalAcc* acc) {
+// loss, beta: options "loss" and "loss_beta" of the context
+int launch_eval_tally(tnml_ctx* c, const double* w, const int* pred, const int* lab, int cnt, int nl, int single, int target, EvalAcc* acc, int loss, double beta) {
     if (cnt <= 0) return 0;
     if (nl != (single ? 1 : TNML_NL)) return tnml_fail(c, "launch_eval_tally: label extent %d", nl);
+    if (loss != TNML_LOSS_QUADRATIC && (loss != TNML_LOSS_SOFTMAX || single)) return tnml_fail(c, "launch_eval_tally: loss %d%s", loss, single ? " in the per-label variant" : "");
     ProfScope ps(c, KC_EVAL_TALLY);
-    hipLaunchKernelGGL(k_eval_tally, dim3(1), dim3(EVAL_THREADS), 0, c->stream, w, pred, lab, cnt, nl, single, target, acc);
+    hipLaunchKernelGGL(loss == TNML_LOSS_SOFTMAX ? k_eval_tally<1> : k_eval_tally<0>, dim3(1), dim3(EVAL_THREADS), 0, c->stream, w, pred, lab, cnt, nl, single, target, beta, acc);
     HIPCK(c, hipGetLastError());
     return 0;
 }

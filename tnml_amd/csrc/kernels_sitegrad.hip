@@ -37,8 +37,13 @@
 //    MFMA steps to other tiles, and trailing steps of zeros change nothing).  Its last bits may depend on gradient_chunk: a chunk
 //    that is no multiple of 4 images shifts the grouping of the images into MFMA steps.
 //
+//    k_site_backward<.., .., 1> (labels under option "loss" = TNML_LOSS_SOFTMAX; never the per-label variant): the hook parks the weight
+//    itself in the thread's column of the LDS coefficients; after the centre the thread that owns the image turns its column into the
+//    coefficients of the softmax cross-entropy (loss_dev.h) and writes them to LDS and to the [C][nl] buffer.  Everything after is shared.
+//
 // No atomics; compiled with -ffp-contract=off like its neighbours.
 #include "chain_common.h"
+#include "loss_dev.h"
 
 #define SG_THREADS 256
 #define SG_BLK 32                   /* output block: SG_BLK (a) x SG_BLK (r), both s */
@@ -122,7 +127,7 @@ static __device__ __forceinline__ void carry_outward(const ChainArgs<double>& ch
     }
 }
 
-template <int NCT, int SRC>
+template <int NCT, int SRC, int LOSS = 0>
 __global__ __launch_bounds__(CHAIN_THREADS) void k_site_backward(const SiteGradArgs g) {
     constexpr int T = 16 * NCT;
     extern __shared__ __attribute__((aligned(16))) unsigned char sg_lds_raw[];
@@ -145,7 +150,9 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_site_backward(const SiteGradA
     chain_centre_taped<NCT>(ch, buf, cur, park, p0, p1, tile0, tid, [&](int l, double w, int col, int img) {
         double cv = 0;
         if (img < ch.cnt) {
-            if (g.lab) {
+            if constexpr (LOSS == 1) {
+                cv = w;                                                // parked: the softmax block below needs all ten
+            } else if (g.lab) {
                 const int lb = g.lab[img];
                 const double y = (ch.single ? lb == g.target : lb == l) ? 1. : 0.;
                 cv = 2. * (w - y);
@@ -156,6 +163,18 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_site_backward(const SiteGradA
         }
         cl[l * T + col] = cv;
     });
+    if constexpr (LOSS == 1) {                                         // (the centre ends on a barrier; the one below orders this before seed_step)
+        const int img = tile0 + tid;
+        if (tid < T && img < ch.cnt) {
+            double wv[TNML_NL];
+#pragma unroll
+            for (int l = 0; l < TNML_NL; ++l) wv[l] = cl[l * T + tid];
+            int d;
+            (void)loss_softmax(wv, g.lab[img], g.beta, &d);
+#pragma unroll
+            for (int l = 0; l < TNML_NL; ++l) { cl[l * T + tid] = wv[l]; g.coef[(size_t)img * TNML_NL + l] = wv[l]; }
+        }
+    }
     const ChainSite<double> sc = ch.sites[cs - 1];
     const size_t lstride = (size_t)sc.ml * 2 * sc.mr;
     chain_copy_rows<T>(park, buf[cur ^ 1], sc.mr, tid);                // R into the free tile: the operand of the right-type seed
@@ -288,11 +307,15 @@ int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int ro
     typedef void (*kern_t)(const SiteGradArgs);
     static const kern_t bwd[2][3] = {{k_site_backward<1, 0>, k_site_backward<2, 0>, k_site_backward<4, 0>}, {k_site_backward<1, 1>, k_site_backward<2, 1>, k_site_backward<4, 1>}};   // [SRC][T / 32]
     static const kern_t gemm[2][3] = {{k_site_grad<1, 0>, k_site_grad<2, 0>, k_site_grad<4, 0>}, {k_site_grad<1, 1>, k_site_grad<2, 1>, k_site_grad<4, 1>}};
+    static const kern_t bwd_sm[2][3] = {{k_site_backward<1, 0, 1>, k_site_backward<2, 0, 1>, k_site_backward<4, 0, 1>}, {k_site_backward<1, 1, 1>, k_site_backward<2, 1, 1>, k_site_backward<4, 1, 1>}};
+    const bool softmax = a.loss == TNML_LOSS_SOFTMAX;                  // (the host sets it in the labels mode only)
+    if (softmax && (!a.lab || a.ch.single || a.ch.nl != TNML_NL)) return tnml_fail(c, "site gradient kernel: the softmax loss needs labels and %d outputs", TNML_NL);
     TapedLaunch L;                                                     // beside the two tiles: the coefficients [nl][T]
-    TCK(taped_launch(c, "site gradient kernel", "tapes", a.ch, maxbond, T, rows, tape_elems, (size_t)a.ch.nl * T * sizeof(double), bwd, c->attr_sitegrad, &L));
+    TCK(taped_launch(c, "site gradient kernel", "tapes", a.ch, maxbond, T, rows, tape_elems, (size_t)a.ch.nl * T * sizeof(double), softmax ? bwd_sm : bwd,
+                     softmax ? c->attr_sitegrad_sm : c->attr_sitegrad, &L));
     {
         ProfScope ps(c, KC_SITE_BWD);
-        hipLaunchKernelGGL(bwd[L.codes][T / 32], dim3(L.grid), dim3(CHAIN_THREADS), L.lds, c->stream, a);
+        hipLaunchKernelGGL((softmax ? bwd_sm : bwd)[L.codes][T / 32], dim3(L.grid), dim3(CHAIN_THREADS), L.lds, c->stream, a);
         HIPCK(c, hipGetLastError());
     }
     ProfScope ps(c, KC_SITE_GRAD);

@@ -78,7 +78,7 @@ int tnml_profile_reset(tnml_ctx* c) {
 // One row per option of tnml_set_option / tnml_set_option_real: its name, the environment variable that supplies its default at
 // tnml_create (or none), the field it sets, its kind and the values it accepts.  A bool option takes any value (nonzero: on).
 enum OptKind { OPT_BOOL, OPT_INT, OPT_REAL };
-enum OptHook { HK_NONE, HK_REUSE_P, HK_DEFER_TAIL, HK_CHECK_REPLICAS, HK_ENV_BUDGET, HK_COMM_TIMEOUT, HK_FAIL_SPLIT, HK_MISPREDICT, HK_SVD_PRINT, HK_CG_METHOD, HK_NOISE, HK_PREDICT_TILE };
+enum OptHook { HK_NONE, HK_REUSE_P, HK_DEFER_TAIL, HK_CHECK_REPLICAS, HK_ENV_BUDGET, HK_COMM_TIMEOUT, HK_FAIL_SPLIT, HK_MISPREDICT, HK_SVD_PRINT, HK_CG_METHOD, HK_NOISE, HK_PREDICT_TILE, HK_LOSS, HK_LOSS_BETA };
 struct OptDef {
     const char* name; const char* env; OptKind kind;
     int tnml_ctx::* ifield; double tnml_ctx::* rfield;    // the field set (none for env_budget_mb: its hook stores bytes)
@@ -124,6 +124,8 @@ static const OptDef k_options[] = {
     {"gradient_chunk",   nullptr,               OPT_INT,  &tnml_ctx::gradient_chunk,      nullptr,          1, 1 << 20, HK_NONE},
     {"fg64_cfg",         "TNML_FG64_CFG",       OPT_INT,  &tnml_ctx::opt_fg64_cfg,        nullptr,          0, 2,       HK_NONE},
     {"ldot_cfg",         "TNML_LDOT_CFG",       OPT_INT,  &tnml_ctx::opt_ldot_cfg,        nullptr,          0, 2,       HK_NONE},
+    {"loss",             nullptr,               OPT_INT,  &tnml_ctx::loss,                nullptr,          0, 1,       HK_LOSS},   // TNML_LOSS_QUADRATIC / TNML_LOSS_SOFTMAX
+    {"loss_beta",        nullptr,               OPT_REAL, nullptr,                        &tnml_ctx::loss_beta, 0, HUGE_VAL, HK_LOSS_BETA},
     {"pcut",             nullptr,               OPT_REAL, nullptr,                        &tnml_ctx::pcut,  0, HUGE_VAL, HK_NONE},
     {"noise",            nullptr,               OPT_REAL, nullptr,                        &tnml_ctx::noise, 0, HUGE_VAL, HK_NOISE},
 };
@@ -149,6 +151,12 @@ static int apply_option(tnml_ctx* c, const OptDef& d, double v, const char* who,
             break;
         case HK_PREDICT_TILE:
             if (v != 0 && v != 16 && v != 32 && v != 64) return tnml_fail(c, "%s: %s = %.15g, must be 0, 16, 32 or 64", who, what, v);
+            break;
+        case HK_LOSS:
+            if (v >= 1 && c->single()) return tnml_fail(c, "loss: 0 (quadratic) in TNML_MODE_SINGLE: one output has no softmax");
+            break;
+        case HK_LOSS_BETA:                                             // (NaN has failed the range check above)
+            if (!(v > 0 && std::isfinite(v))) return tnml_fail(c, "%s: %s = %.15g, must be finite and > 0", who, what, v);
             break;
         case HK_NOISE:                                                 // single.cc:25,222: the noise of every sweep
             if (v >= 1e-14 && !c->single()) return tnml_fail(c, "noise: the density-matrix split exists in the per-label variant only (single.h:648-672)");

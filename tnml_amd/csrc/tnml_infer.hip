@@ -110,7 +110,7 @@ void response_release(tnml_ctx* c) {
 }
 void sitegrad_release(tnml_ctx* c) {
     ws_release(c, c->sg, {(void**)&c->sg_lab, (void**)&c->sg_coef, (void**)&c->sg_rowoff, (void**)&c->sg_goff, (void**)&c->sg_blk0, (void**)&c->sg_grad, (void**)&c->sg_tape, (void**)&c->sg_tape2});
-    c->sg_tape_rows = 0; c->sg_grad_elems = 0;
+    c->sg_tape_rows = 0; c->sg_grad_elems = 0; c->sg_last_cnt = -1;
 }
 // First call, or the chunk option has changed since: the old workspace goes (release), tab, w and pred are made for the new capacity;
 // *fresh then tells the caller to allocate what it alone has.  On an error here and in the helpers below the caller releases the workspace.
@@ -315,7 +315,7 @@ static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t
         TCK(stage_chunk<E>(c, s, mapped, sg, pixels, phi, off, a.cnt, xphi));
         if (labels) HIPCK(c, hipMemcpyAsync(c->pk_lab, labels + off, sizeof(int32_t) * (size_t)a.cnt, hipMemcpyHostToDevice, c->stream));
         TCK(launch_chain<E>(c, a, maxbond, chain_tile<E>(c, maxbond, a.cnt), park, park_elems));
-        if (labels) TCK(launch_eval_tally(c, s.w, s.pred, c->pk_lab, a.cnt, a.nl, a.single, c->target(), c->pk_acc));
+        if (labels) TCK(launch_eval_tally(c, s.w, s.pred, c->pk_lab, a.cnt, a.nl, a.single, c->target(), c->pk_acc, c->loss, c->loss_beta));
         int flag = 0;
         if (f32) HIPCK(c, hipMemcpyAsync(&flag, c->pk_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         TCK(chunk_results(c, s, off, a.cnt, weights, pred));
@@ -554,6 +554,7 @@ static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_
     a.rowoff = c->sg_rowoff; a.tape = c->sg_tape; a.tape2 = c->sg_tape2;
     a.lab = labels ? c->sg_lab : nullptr; a.target = c->target(); a.coef = c->sg_coef;
     a.grad = c->sg_grad; a.goff = c->sg_goff; a.blk0 = c->sg_blk0;
+    a.loss = labels ? c->loss : TNML_LOSS_QUADRATIC; a.beta = c->loss_beta;      // (coefficients as given know no loss)
     const size_t tape_elems = c->sg_tape_rows * (size_t)s.cap;
     for (int64_t off = 0; off < n; off += c->gradient_chunk) {
         a.ch.cnt = (int)std::min<int64_t>(c->gradient_chunk, n - off);
@@ -561,7 +562,8 @@ static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_
         if (labels) HIPCK(c, hipMemcpyAsync(c->sg_lab, labels + off, sizeof(int32_t) * (size_t)a.ch.cnt, hipMemcpyHostToDevice, c->stream));
         else        HIPCK(c, hipMemcpyAsync(c->sg_coef, coef + (size_t)off * nl, sizeof(double) * (size_t)a.ch.cnt * nl, hipMemcpyHostToDevice, c->stream));
         TCK(launch_site_gradient(c, a, maxbond, chain_tile<double>(c, maxbond, a.ch.cnt), rows, tape_elems, nblocks));
-        if (acc && labels) TCK(launch_eval_tally(c, s.w, s.pred, c->sg_lab, a.ch.cnt, nl, a.ch.single, c->target(), acc));
+        if (acc && labels) TCK(launch_eval_tally(c, s.w, s.pred, c->sg_lab, a.ch.cnt, nl, a.ch.single, c->target(), acc, c->loss, c->loss_beta));
+        c->sg_last_cnt = a.ch.cnt;
         TCK(chunk_results(c, s, off, a.ch.cnt, weights, pred));
     }
     return 0;
@@ -709,6 +711,16 @@ int tnml_site_step_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const int32
 int tnml_site_step_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* labels, const double* coef, const tnml_step_params* p, tnml_step_report* rep) {
     if (n > 0 && !phi) return tnml_fail(c, "tnml_site_step_phi: null argument");
     return sitestep_impl(c, "tnml_site_step_phi", n, nullptr, phi, labels, coef, p, rep);
+}
+int tnml_site_gradient_coef(tnml_ctx* c, double* out, int64_t count) {
+    if (!c || !out) return tnml_fail(c, "tnml_site_gradient_coef: null argument");
+    if (c->sg_last_cnt < 0 || !c->sg_coef) return tnml_fail(c, "tnml_site_gradient_coef: no gradient or step call has been made since the workspace was made (count = %lld)", (long long)count);
+    const int64_t have = (int64_t)c->sg_last_cnt * c->nl();
+    if (count != have) return tnml_fail(c, "tnml_site_gradient_coef: the last chunk has %d x %d coefficients, count = %lld", c->sg_last_cnt, c->nl(), (long long)count);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    SYNCK(c, c->stream);
+    HIPCK(c, hipMemcpy(out, c->sg_coef, sizeof(double) * (size_t)have, hipMemcpyDeviceToHost));
+    return 0;
 }
 int tnml_site_step_state(tnml_ctx* c, const char* which, double* out, int64_t count) {
     if (!c || !which || !out) return tnml_fail(c, "tnml_site_step_state: null argument");

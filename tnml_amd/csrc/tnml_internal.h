@@ -344,6 +344,10 @@ struct tnml_ctx {
     // streamed site gradients (tnml_site_gradient_u8 / tnml_site_gradient_phi, kernels_sitegrad.hip)
     int gradient_chunk = TNML_GRADIENT_CHUNK_DEFAULT;      // option "gradient_chunk": images per launch of k_site_backward / k_site_grad
     bool attr_sitegrad[2] = {};      // [input map]: the LDS attribute of those k_site_backward instantiations is set
+    bool attr_sitegrad_sm[2] = {};   // the same for the instantiations of the softmax loss
+    int loss = TNML_LOSS_QUADRATIC;  // option "loss": the loss of tnml_evaluate_* and of the labels mode of tnml_site_gradient_* / tnml_site_step_*
+    double loss_beta = 1.;           // tnml_set_option_real "loss_beta": the inverse temperature of the softmax loss, logits beta W_l
+    int sg_last_cnt = -1;            // images of the last chunk a gradient or step call ran in this workspace (tnml_site_gradient_coef); -1: none yet
     StreamWs sg;                     // released whole by every tnml_set_input_map call
     int* sg_lab = nullptr; double* sg_coef = nullptr;      // [cap] labels of a chunk; [cap][nl] its coefficients (given, or formed by k_site_backward)
     int* sg_rowoff = nullptr;                              // [N + 2] rows of the tape regions of bond 0..N, then the rows of a slice
@@ -645,6 +649,7 @@ struct SiteGradArgs {
     double* grad;                      // every site in tnml_get_site's layout, site j at goff[j - 1]
     const long long* goff;             // [N + 1] device
     const int* blk0;                   // [N + nl] device: first output block of every virtual site (sites in order, the Label site once per label), then the block count
+    int loss = 0; double beta = 1.;    // labels mode: TNML_LOSS_SOFTMAX forms coef by loss_dev.h with the logits beta W_l (k_site_backward<.., .., 1>)
 };
 // rows: rowoff[N + 1] as the host knows it; tape_elems: doubles behind each tape; nblocks: the block count; classes site_bwd, site_grad
 int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int rows, size_t tape_elems, int nblocks);
@@ -671,7 +676,8 @@ int launch_site_step(tnml_ctx* c, const SiteStepArgs& a, int nwg);
 // ---- kernels_eval.hip: the tallies of streamed evaluation over the results of a chunk ----
 // w [cnt][nl], pred [cnt] (what k_chain left in pk.w / pk.pred), lab [cnt] in 0..9 (the host has checked them) -> acc += the chunk's
 // label_cost, count, nincorrect, confusion; one workgroup, fixed summation order (the kernel's header states it); class eval_tally
-int launch_eval_tally(tnml_ctx* c, const double* w, const int* pred, const int* lab, int cnt, int nl, int single, int target, EvalAcc* acc);
+// loss, beta: options "loss" and "loss_beta"; TNML_LOSS_SOFTMAX: the cost and the decision of loss_dev.h (refused with single)
+int launch_eval_tally(tnml_ctx* c, const double* w, const int* pred, const int* lab, int cnt, int nl, int single, int target, EvalAcc* acc, int loss, double beta);
 
 // ---- eigh.hip -----------------------------------------------------------------------------
 int eigh_tridiagonalize(tnml_ctx* c, const double* A, int n, double* D, double* E, double* tau, double* V, double psd_tol = 0.);   // tau: n doubles, tau[n-1] = number of reflectors

@@ -84,6 +84,8 @@ class TrainStates:
             self._h = C.c_void_p()
             raise TnmlError(self._L.tnml_last_error(None).decode())
         self._bytes_per_image = self.N
+        self._loss = "quadratic"
+        self._last_chunk = None
         if input_map is not None:
             self.set_input_map(input_map)
         if pixels is not None:
@@ -182,6 +184,25 @@ class TrainStates:
 
     def set_option(self, name, value):
         self._ck(self._L.tnml_set_option(self._h, name.encode(), int(value)))
+        if name == "gradient_chunk":
+            self._gchunk = int(value)
+        elif name == "loss":
+            self._loss = {v: k for k, v in _lib.LOSSES.items()}[int(value)]
+
+    def set_loss(self, loss="quadratic", beta=1.0):
+        """options loss and loss_beta: the loss of evaluate() and of the labels mode of site_gradient() / gradient_step().
+        "quadratic" (the default, the reference's cost) or "softmax": cross-entropy on the logits beta W_l (refused on a per-label
+        context); beta must be finite and > 0.  Nothing else is touched: predict(), the coef mode, training."""
+        if loss not in _lib.LOSSES:
+            raise ValueError("loss must be one of %s, got %r" % (sorted(_lib.LOSSES), loss))
+        self._ck(self._L.tnml_set_option_real(self._h, b"loss_beta", float(beta)))
+        self.set_option("loss", _lib.LOSSES[loss])
+        self._loss = loss
+
+    @property
+    def loss(self):
+        """the loss set_loss() has set: "quadratic" or "softmax" """
+        return self._loss
 
     def size(self):
         return self.NT
@@ -303,7 +324,9 @@ class TrainStates:
         """streamed evaluation of labelled images this context does not hold (tnml_evaluate_u8 / tnml_evaluate_phi): the path of
         predict() plus one tally launch per chunk.  Returns an EvalReport (fields as tnml_eval_report: n, ncorrect, cost,
         label_cost[10], count[10], nincorrect[10], confusion[10, 10]); with want_weights (report, (weights[n, nl], pred[n])), both
-        bit for bit those of predict().  Without it only the report leaves the device.  Reads W only."""
+        bit for bit those of predict().  Without it only the report leaves the device.  Reads W only.
+        Under set_loss("softmax") cost and label_cost are the cross-entropy of the logits beta W_l, and ncorrect, nincorrect and
+        confusion follow the signed decision (first maximum of W_l); weights and pred stay predict()'s (pred: first maximum of |W_l|)."""
         x = self._streamed_input(pixels, phi, dtype)
         n = int(x.shape[0])
         lab = np.ascontiguousarray(labels, dtype=np.int32)
@@ -354,7 +377,9 @@ class TrainStates:
         forms of predict(): a list of N arrays shaped like get_site()'s, G_j = sum_n sum_l c[n, l] dW_l(x_n)/dA_j.  Exactly one of
         coef[n, nl] (c as given) and labels[n] (c = 2 (W - y) with the targets of evaluate(): the gradient of the cost evaluate()
         reports).  With want_weights (grads, (weights[n, nl], pred[n])), both bit for bit those of predict() in fp64.  Reads W only;
-        fp64 only (refused under predict_dtype = 1)."""
+        fp64 only (refused under predict_dtype = 1).
+        Under set_loss("softmax") the labels mode forms c = beta (softmax(beta W) - y) on the device instead: the gradient of the
+        cross-entropy evaluate() then reports.  The coef mode does not know the loss."""
         x = self._streamed_input(pixels, phi, None)
         n = int(x.shape[0])
         lp = cp = None
@@ -387,7 +412,26 @@ class TrainStates:
             self._ck(self._L.tnml_site_dims(self._h, j, ml, mr, hl))
             shape = (ml.value, 2, mr.value) + ((NL,) if hl.value else ())
             grads.append(grad[offs[j - 1]:offs[j]].reshape(shape, order="F").copy(order="F"))
+        self._note_chunk(n)
         return (grads, (w, pred)) if want_weights else grads
+
+    def _note_chunk(self, n):
+        """the size of the last chunk of a gradient or step call on n images (gradient_coef)"""
+        if n > 0:
+            chunk = self._gradient_chunk()
+            self._last_chunk = n - (n - 1) // chunk * chunk
+
+    def _gradient_chunk(self):
+        return getattr(self, "_gchunk", _lib.GRADIENT_CHUNK_DEFAULT)
+
+    def gradient_coef(self, cnt=None):
+        """test entry (tnml_site_gradient_coef): the coefficients [cnt, nl] of the last chunk of the last site_gradient() or
+        gradient_step() call, as given (coef) or as the device formed them (labels).  cnt: that chunk's images (None: what this
+        object has seen go by; another value is refused by the library)"""
+        cnt = int(cnt) if cnt is not None else (self._last_chunk or 0)
+        out = np.zeros((max(cnt, 1), self.nl))
+        self._ck(self._L.tnml_site_gradient_coef(self._h, _lib.dptr(out), cnt * self.nl))
+        return out[:cnt]
 
     def _split_sites(self, flat):
         """a flat array in the layout of tnml_site_gradient_*'s grad -> a list of N arrays shaped like get_site()'s"""
@@ -407,7 +451,9 @@ class TrainStates:
         arguments, summed as site_gradient() sums it, multiplied by scale, clipped to the norm clip (0: not), then
         method "sgd": v <- momentum v + g, A <- A - lr v, or "adam" with beta1, beta2, eps and bias correction.  Neither the gradient
         nor W crosses the bus; returns a StepReport.  The optimiser state lives on the device, is made by the first step for its
-        method and the shapes of W, and goes with step_reset().  Environments are stale afterwards, as after set_mps()."""
+        method and the shapes of W, and goes with step_reset().  Environments are stale afterwards, as after set_mps().
+        Under set_loss("softmax") the labels mode takes the gradient of the cross-entropy and the report's eval is evaluate()'s under
+        that loss; the optimiser and the coef mode are the same."""
         if method not in _lib.STEP_METHODS:
             raise ValueError("method must be one of %s, got %r" % (sorted(_lib.STEP_METHODS), method))
         if lr is None:
@@ -431,6 +477,7 @@ class TrainStates:
             self._ck(self._L.tnml_site_step_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), lp, cp, C.byref(par), C.byref(r)))
         else:
             self._ck(self._L.tnml_site_step_phi(self._h, n, _lib.dptr(x), lp, cp, C.byref(par), C.byref(r)))
+        self._note_chunk(n)
         return StepReport(r)
 
     def step_reset(self):

@@ -15,6 +15,8 @@ import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 NL = 10
 MAX_PASS = 64
 DTYPES = {"f32": 0, "f64_e32": 1, "f64": 2, "bf16": 3, "bf16x3": 4}    # TNML_F32 / TNML_F64_E32 / TNML_F64 / TNML_BF16 / TNML_BF16X3 (include/tnml.h)
+GRADIENT_CHUNK_DEFAULT = 512             # TNML_GRADIENT_CHUNK_DEFAULT
+LOSSES = {"quadratic": 0, "softmax": 1}    # TNML_LOSS_QUADRATIC / TNML_LOSS_SOFTMAX: option loss
 PREDICT_DTYPES = {"f64": 0, "f32": 1}    # TNML_PREDICT_F64 / TNML_PREDICT_F32: option predict_dtype
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtnml.so")
@@ -39,6 +41,7 @@ EXPORTS = [
     "tnml_response_u8", "tnml_response_phi",
     "tnml_site_gradient_size", "tnml_site_gradient_u8", "tnml_site_gradient_phi",
     "tnml_site_step_u8", "tnml_site_step_phi", "tnml_site_step_reset", "tnml_site_step_state",
+    "tnml_site_gradient_coef",
 ]
 
 
@@ -171,6 +174,7 @@ def load():
     L.tnml_site_step_phi.argtypes = [vp, C.c_int64, dp, C.POINTER(C.c_int32), dp, C.POINTER(StepParams), C.POINTER(StepReport)]
     L.tnml_site_step_reset.argtypes = [vp]
     L.tnml_site_step_state.argtypes = [vp, C.c_char_p, dp, C.c_int64]
+    L.tnml_site_gradient_coef.argtypes = [vp, dp, C.c_int64]
     L.tnml_set_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_get_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_replica_check.argtypes = [vp, ip]

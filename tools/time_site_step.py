@@ -9,7 +9,13 @@ the GPU).  Per image count: one warm-up leg of each path (discarded), then the p
 its context and takes three steps (calls) from the same start: the first untimed (code objects, first-touch allocations: workspace
 and optimiser state are allocated there), the second timed, the third with the profile API on for the kernel time by class.  The
 device and the host legs report a digest of W after their three steps: the two must agree bit for bit, the host path being the model
-the device is tested against.  No pass / fail time: the figures are written down with the spread of the repeats."""
+the device is tested against.  No pass / fail time: the figures are written down with the spread of the repeats.
+
+    python tools/time_site_step.py --loss quadratic,softmax [--loss-beta 8] [--n 256] [--out profiles/site_step_loss_time.txt]
+
+times the device step alone under each of the named losses (option loss; softmax: the cross-entropy of tnml_amd/csrc/loss_dev.h), the
+losses alternated leg by leg as the paths are above.  A loss may be named twice: the two series of legs then show the spread of one
+and the same code."""
 import argparse
 import hashlib
 import json
@@ -24,7 +30,7 @@ LR = 1e-3
 PATHS = ("gradient", "host", "device")
 
 
-def child(path, n):
+def child(path, n, loss="quadratic", beta=1.0):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import numpy as np
@@ -36,6 +42,8 @@ def child(path, n):
     W = synth.random_mps(N, M, seed=1)
     ts = TrainStates(np.zeros(1, dtype=np.int32), N, M, no_data=True, device=0)
     ts.set_mps(W)
+    if loss != "quadratic":
+        ts.set_loss(loss, beta)
     box = dict(W=W, state=None, rep=None)
 
     def call():
@@ -60,7 +68,7 @@ def child(path, n):
     call()
     prof = {k: v for k, v in ts.profile_read().items() if v[0]}
     ts.profile(False)
-    out = dict(path=path, n=n, seconds_call=dt, device_bytes=ts.device_bytes(), launches={k: v[0] for k, v in prof.items()},
+    out = dict(path=path, n=n, loss=loss, seconds_call=dt, device_bytes=ts.device_bytes(), launches={k: v[0] for k, v in prof.items()},
                kernel_ms={k: v[1] for k, v in prof.items()})
     if path != "gradient":
         h = hashlib.sha256()
@@ -78,11 +86,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--timeout", type=int, default=300)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "site_step_time.txt"))
+    ap.add_argument("--loss", default="", help="comma-separated losses: time the device step under each, alternated")
+    ap.add_argument("--loss-beta", type=float, default=8.0)
     ap.add_argument("--child", default="")
     a = ap.parse_args()
     if a.child:
-        path, n = a.child.split(",")
-        child(path, int(n))
+        path, n, loss = a.child.split(",")
+        child(path, int(n), loss, a.loss_beta)
         return 0
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     open(a.out, "w").close()
@@ -92,8 +102,8 @@ def main():
         with open(a.out, "a") as f:
             f.write(s + "\n")
 
-    def leg(path, n):
-        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", "%s,%d" % (path, n)]
+    def leg(path, n, loss="quadratic"):
+        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--loss-beta", repr(a.loss_beta), "--child", "%s,%d,%s" % (path, n, loss)]
         p = subprocess.run(cmd, capture_output=True, text=True)
         line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
         if p.returncode != 0 or not line:
@@ -109,6 +119,8 @@ def main():
 
     def kernels(legs, classes):
         return "; ".join("%s %s" % (k, spread([r["kernel_ms"].get(k, 0.) for r in legs], "ms")) for k in classes)
+    if a.loss:
+        return loss_legs(a, say, leg, spread, kernels)
     say("gradient steps from bytes (labels mode, Adam, lr = %g, scale = 1 / n), N = %d, m = %d, fp64: tnml_site_step_u8 against site_gradient + numpy update + set_mps "
         "and against a plain tnml_site_gradient_u8 call; per leg three steps from the same start: one untimed, one timed, one profiled; median (min, max) of %d legs"
         % (LR, N, M, a.repeats))
@@ -139,6 +151,32 @@ def main():
         say("  W after three steps, device against host path: %s (t = %d, grad_norm of the third step %.17g device, %.17g host)"
             % ("bit for bit the same" if same else "DIFFERENT", d[0]["t"], d[0]["grad_norm"], h[0]["grad_norm"]))
         results.append(dict(n=n, gradient=g, host=h, device=d, same=same))
+    with open(a.out, "a") as f:
+        f.write(json.dumps(results) + "\n")
+    return 0
+
+
+def loss_legs(a, say, leg, spread, kernels):
+    """--loss: the device step under each named loss (series k of the list: a loss named twice gives two series), alternated"""
+    losses = a.loss.split(",")
+    say("gradient steps from bytes (labels mode, Adam, lr = %g, scale = 1 / n), N = %d, m = %d, fp64: tnml_site_step_u8 under option loss = %s (loss_beta = %g), "
+        "the series alternated leg by leg; per leg three steps from the same start: one untimed, one timed, one profiled; median (min, max) of %d legs"
+        % (LR, N, M, " | ".join(losses), a.loss_beta, a.repeats))
+    results = []
+    for n in (int(x) for x in a.n.split(",")):
+        if any(leg("device", n, loss) is None for loss in dict.fromkeys(losses)):      # warm-up of each loss, discarded
+            return 1
+        res = [[] for _ in losses]
+        for _ in range(a.repeats):
+            for k, loss in enumerate(losses):
+                r = leg("device", n, loss)
+                if r is None:
+                    return 1
+                res[k].append(r)
+        say("n = %d" % n)
+        for k, loss in enumerate(losses):
+            say("  series %d, loss = %-9s  step %s; kernels: %s" % (k, loss, spread([r["seconds_call"] for r in res[k]]), kernels(res[k], ("site_bwd", "site_grad", "eval_tally", "step_norm", "site_step"))))
+        results.append(dict(n=n, losses=losses, legs=res))
     with open(a.out, "a") as f:
         f.write(json.dumps(results) + "\n")
     return 0
