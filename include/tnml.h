@@ -479,6 +479,30 @@ int tnml_site_gradient_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][
                            double* grad, double* weights, int32_t* pred);
 int tnml_site_gradient_coef(tnml_ctx* ctx, double* out /*[cnt][nl]*/, int64_t count);
 
+/* ---- streamed input gradients: dC/dphi of every site's feature, beside or instead of dC/dA -----------------------------
+ * The other half of a backward pass.  For n images and the coefficients c[n][l] = dC/dW_l(x_n) of tnml_site_gradient_*
+ *     dphi[n][j][s] = sum_l c_nl dW_l(x_n)/dphi_{n,j}[s],
+ * the vector-Jacobian product with respect to the inputs.  W is linear in the feature of each site, so dphi[n][j] is also the pair of
+ * outputs sum_l c_nl W_l(x_n with phi_j := e_s), and sum_s phi_{n,j}[s] dphi[n][j][s] = sum_l c_nl W_l(x_n) at every site.
+ * Inputs, the labels / coef rule, the options "loss" / "loss_beta", "gradient_chunk" and "predict_tile", the input map and the per-label
+ * variant are those of tnml_site_gradient_*; the call shares that call's workspace and its k_site_backward launch.  Under an input map
+ * dphi is the gradient with respect to the features of the N reduced sites (the table rows the block sums select).
+ * grad non-NULL: k_site_grad runs and grad is bit for bit what tnml_site_gradient_* returns on the same arguments.  grad NULL: that launch
+ * is left out.  dphi non-NULL: per chunk ONE launch of k_input_grad (kernels_inputgrad.hip) reads the two tapes and forms one bilinear
+ * form per site, feature component and image with v_mfma_f64_16x16x4_f64, in a fixed order (the kernel file's header states it; no
+ * atomics): an image's values do not depend on n, on the chunk, on the tile width or on the tile it lands in, and repeats are
+ * bit-identical.  dphi is copied back chunk by chunk.  weights and pred, either may be NULL, are bit for bit those of tnml_predict_*.
+ * Refused as tnml_site_gradient_* is, in the same words; also refused: grad and dphi both NULL.  A refused call leaves grad and dphi
+ * untouched; n = 0 succeeds, zeroes grad (when given) and touches nothing else.  Reads W only and enters no collective.
+ * Workspace: that of tnml_site_gradient_* (same formula, same bytes) and, from the first call that asks for dphi on,
+ *             32 N C    bytes (dphi of a chunk as the kernel leaves it [N][2][C] and as the caller gets it [C][N][2]; C = gradient_chunk
+ *                       rounded up to 64), counted by tnml_device_bytes, re-made when gradient_chunk changes, released by
+ *                       tnml_set_input_map with the gradient workspace and freed by tnml_destroy. */
+int tnml_backward_u8 (tnml_ctx* ctx, int64_t n, const uint8_t* pixels, const int32_t* labels /*[n] or NULL*/, const double* coef /*[n][nl] or NULL*/,
+                      double* grad /*[elems] or NULL*/, double* dphi /*[n][N][2] or NULL*/, double* weights /*[n][nl] or NULL*/, int32_t* pred /*[n] or NULL*/);
+int tnml_backward_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/, const int32_t* labels, const double* coef,
+                      double* grad, double* dphi, double* weights, int32_t* pred);
+
 /* ---- gradient steps on the device: SGD with momentum and Adam on the streamed site gradient ---------------------------
  * One call is one optimiser step on W.  The gradient G of the n images is summed on the device exactly as tnml_site_gradient_* sums
  * it (same inputs, labels / coef rule, gradient_chunk, predict_tile, input map, per-label variant and order: the same bits), then the

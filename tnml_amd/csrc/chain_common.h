@@ -3,6 +3,7 @@
 //   * All of them: the element-type traits ChainT<E>, the features of a site (chain_features), the A fragment of a 16-wide k block
 //     (chain_load_a) and one site of a chain (chain_step); the fragment maps, the k blocks and the arithmetic order are described in the
 //     header of kernels_chain.hip.
+//     k_input_grad (kernels_inputgrad.hip, streamed input gradients) takes the traits, the fragment maps and the tape's layout from here.
 //   * k_response and k_site_backward, which walk the chain inward and then outward: the tape (ChainTape), the taped inward walk
 //     (chain_walk_taped), the centre site with weights and pred (chain_centre_taped) and the host side of their launches (taped_launch).
 //     The inward walk and the centre are k_chain's, call for call and in its order; that order is stated once, above chain_walk_taped.

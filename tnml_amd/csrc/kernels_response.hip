@@ -232,6 +232,12 @@ __global__ __launch_bounds__(256) void k_response_transpose(const double* __rest
         if (n0 + i < cnt && r0 + tx < rows) out[(size_t)(n0 + i) * rows + r0 + tx] = tile[tx][i];
 }
 
+int launch_response_transpose(tnml_ctx* c, const double* in, int rows, int cnt, int ld, double* out) {
+    hipLaunchKernelGGL(k_response_transpose, dim3((cnt + 31) / 32, (rows + 31) / 32), dim3(256), 0, c->stream, in, rows, cnt, ld, out);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+
 // a.ch.mcap and the grid follow from T; rows: the rows of a workgroup's slice (a.rowoff[N + 3] on the device) as the host knows them
 int launch_response(tnml_ctx* c, RespArgs a, int maxbond, int T, int rows, size_t tape_elems, double* outT) {
     typedef void (*kern_t)(const RespArgs);
@@ -241,8 +247,5 @@ int launch_response(tnml_ctx* c, RespArgs a, int maxbond, int T, int rows, size_
     ProfScope ps(c, KC_SITE_RESP);
     hipLaunchKernelGGL(kern[L.codes][T / 32], dim3(L.grid), dim3(CHAIN_THREADS), L.lds, c->stream, a);
     HIPCK(c, hipGetLastError());
-    const int rows2 = 2 * a.ch.N;
-    hipLaunchKernelGGL(k_response_transpose, dim3((a.ch.cnt + 31) / 32, (rows2 + 31) / 32), dim3(256), 0, c->stream, a.resp, rows2, a.ch.cnt, a.ch.ld, outT);
-    HIPCK(c, hipGetLastError());
-    return 0;
+    return launch_response_transpose(c, a.resp, 2 * a.ch.N, a.ch.cnt, a.ch.ld, outT);
 }

@@ -302,7 +302,8 @@ __global__ __launch_bounds__(SG_THREADS) void k_site_grad(const SiteGradArgs g) 
 
 // a.ch.mcap and the grids follow from T; rows: a.rowoff[N + 1] as the host knows it; tape_elems: doubles behind each of the two tapes;
 // nblocks: a.blk0[N - 1 + nl] as the host knows it
-int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int rows, size_t tape_elems, int nblocks) {
+// run_gemm false: k_site_backward alone (tnml_backward_* without grad)
+int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int rows, size_t tape_elems, int nblocks, bool run_gemm) {
     if (nblocks < 1) return tnml_fail(c, "site gradient kernel: %d output blocks", nblocks);
     typedef void (*kern_t)(const SiteGradArgs);
     static const kern_t bwd[2][3] = {{k_site_backward<1, 0>, k_site_backward<2, 0>, k_site_backward<4, 0>}, {k_site_backward<1, 1>, k_site_backward<2, 1>, k_site_backward<4, 1>}};   // [SRC][T / 32]
@@ -318,6 +319,7 @@ int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int ro
         hipLaunchKernelGGL((softmax ? bwd_sm : bwd)[L.codes][T / 32], dim3(L.grid), dim3(CHAIN_THREADS), L.lds, c->stream, a);
         HIPCK(c, hipGetLastError());
     }
+    if (!run_gemm) return 0;
     ProfScope ps(c, KC_SITE_GRAD);
     hipLaunchKernelGGL(gemm[L.codes][T / 32], dim3(nblocks), dim3(SG_THREADS), 0, c->stream, a);
     HIPCK(c, hipGetLastError());

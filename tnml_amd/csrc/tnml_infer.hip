@@ -109,7 +109,8 @@ void response_release(tnml_ctx* c) {
     c->rs_tape_rows = 0;
 }
 void sitegrad_release(tnml_ctx* c) {
-    ws_release(c, c->sg, {(void**)&c->sg_lab, (void**)&c->sg_coef, (void**)&c->sg_rowoff, (void**)&c->sg_goff, (void**)&c->sg_blk0, (void**)&c->sg_grad, (void**)&c->sg_tape, (void**)&c->sg_tape2});
+    ws_release(c, c->sg, {(void**)&c->sg_lab, (void**)&c->sg_coef, (void**)&c->sg_rowoff, (void**)&c->sg_goff, (void**)&c->sg_blk0, (void**)&c->sg_grad, (void**)&c->sg_tape, (void**)&c->sg_tape2,
+                          (void**)&c->bw_out, (void**)&c->bw_outT});
     c->sg_tape_rows = 0; c->sg_grad_elems = 0; c->sg_last_cnt = -1;
 }
 // First call, or the chunk option has changed since: the old workspace goes (release), tab, w and pred are made for the new capacity;
@@ -513,8 +514,10 @@ static int sitegrad_inputs(tnml_ctx* c, const char* who, int64_t n, const uint8_
 // images in c->sg_grad (*elems of them) with the stream synchronised behind the last chunk; n = 0: nothing is launched, *elems alone is
 // set.  out: where the caller's result goes (refused when null).  acc (tnml_site_step_* in the labels mode): a device accumulator
 // block that is zeroed here and gets one k_eval_tally launch per chunk, on the chunk's weights and sg_lab.
+// tnml_backward_*: dphi (or null) receives the input gradients [n][N][2] chunk by chunk, from ONE k_input_grad launch behind the chunk's
+// k_site_backward; want_grad false leaves k_site_grad out.
 static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
-                           const void* out, double* weights, int32_t* pred, size_t* elems_out, EvalAcc* acc = nullptr) {
+                           const void* out, double* weights, int32_t* pred, size_t* elems_out, EvalAcc* acc = nullptr, double* dphi = nullptr, bool want_grad = true) {
     int maxbond = 1;
     TCK(streamed_refusals(c, who, "site gradients", n, &maxbond));
     if (!out) return tnml_fail(c, "%s: null argument", who);
@@ -539,6 +542,11 @@ static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_
     blk0[v] = nblocks;
     const bool bytes_form = pixels != nullptr;
     TCK(sitegrad_workspace(c, who, bytes_form, (size_t)rows, elems));
+    if (dphi && !c->bw_out) {                                   // the first call that asks for dphi: the result as the kernel leaves it and as the caller gets it
+        int rc = ws_alloc(c, c->sg, (void**)&c->bw_out, (size_t)2 * N * s.cap * sizeof(double));
+        if (!rc) rc = ws_alloc(c, c->sg, (void**)&c->bw_outT, (size_t)2 * N * s.cap * sizeof(double));
+        if (rc) { sitegrad_release(c); return rc; }
+    }
     std::vector<ChainSite<double>> tab;
     TCK(upload_sites(c, s, tab));
     HIPCK(c, hipMemcpyAsync(c->sg_rowoff, rowoff.data(), sizeof(int) * (N + 2), hipMemcpyHostToDevice, c->stream));
@@ -561,7 +569,15 @@ static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_
         TCK(stage_chunk<double>(c, s, mapped, sg, pixels, phi, off, a.ch.cnt, s.xphi));
         if (labels) HIPCK(c, hipMemcpyAsync(c->sg_lab, labels + off, sizeof(int32_t) * (size_t)a.ch.cnt, hipMemcpyHostToDevice, c->stream));
         else        HIPCK(c, hipMemcpyAsync(c->sg_coef, coef + (size_t)off * nl, sizeof(double) * (size_t)a.ch.cnt * nl, hipMemcpyHostToDevice, c->stream));
-        TCK(launch_site_gradient(c, a, maxbond, chain_tile<double>(c, maxbond, a.ch.cnt), rows, tape_elems, nblocks));
+        const int T = chain_tile<double>(c, maxbond, a.ch.cnt);
+        TCK(launch_site_gradient(c, a, maxbond, T, rows, tape_elems, nblocks, want_grad));
+        if (dphi) {
+            InputGradArgs ig;
+            ig.sites = s.tab; ig.N = N; ig.cs = cs; ig.nl = nl; ig.ld = s.cap; ig.cnt = a.ch.cnt;
+            ig.rowoff = c->sg_rowoff; ig.tape = c->sg_tape; ig.tape2 = c->sg_tape2; ig.coef = c->sg_coef; ig.dphi = c->bw_out;
+            TCK(launch_input_grad(c, ig, maxbond, T, rows, tape_elems, c->bw_outT));
+            HIPCK(c, hipMemcpyAsync(dphi + (size_t)off * N * 2, c->bw_outT, sizeof(double) * (size_t)a.ch.cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
+        }
         if (acc && labels) TCK(launch_eval_tally(c, s.w, s.pred, c->sg_lab, a.ch.cnt, nl, a.ch.single, c->target(), acc, c->loss, c->loss_beta));
         c->sg_last_cnt = a.ch.cnt;
         TCK(chunk_results(c, s, off, a.ch.cnt, weights, pred));
@@ -584,6 +600,29 @@ int tnml_site_gradient_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const i
 int tnml_site_gradient_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* labels, const double* coef, double* grad, double* weights, int32_t* pred) {
     if (n > 0 && !phi) return tnml_fail(c, "tnml_site_gradient_phi: null argument");
     return sitegrad_impl(c, "tnml_site_gradient_phi", n, nullptr, phi, labels, coef, grad, weights, pred);
+}
+
+// ---- streamed input gradients (kernels_inputgrad.hip): dC/dphi of every site of every image, beside or instead of dC/dA ----------------
+// The gradient call's refusals, workspace, staging and k_site_backward launch; per chunk k_site_grad runs when grad is asked for and ONE
+// k_input_grad launch on the two tapes when dphi is, its result transposed on the device and copied back with the chunk.
+static int backward_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
+                         double* grad, double* dphi, double* weights, int32_t* pred) {
+    if (c && !grad && !dphi) return tnml_fail(c, "%s: grad and dphi are both NULL: the call would compute nothing", who);
+    size_t elems = 0;
+    TCK(sitegrad_device(c, who, n, pixels, phi, labels, coef, grad ? (const void*)grad : (const void*)dphi, weights, pred, &elems, nullptr, dphi, grad != nullptr));
+    if (n == 0) { if (grad) memset(grad, 0, elems * sizeof(double)); return 0; }
+    if (!grad) return 0;                                        // (the chunk loop ends on a synchronisation)
+    HIPCK(c, hipMemcpyAsync(grad, c->sg_grad, elems * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    SYNCK(c, c->stream);
+    return 0;
+}
+int tnml_backward_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const int32_t* labels, const double* coef, double* grad, double* dphi, double* weights, int32_t* pred) {
+    if (n > 0 && !pixels) return tnml_fail(c, "tnml_backward_u8: null argument");
+    return backward_impl(c, "tnml_backward_u8", n, pixels, nullptr, labels, coef, grad, dphi, weights, pred);
+}
+int tnml_backward_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* labels, const double* coef, double* grad, double* dphi, double* weights, int32_t* pred) {
+    if (n > 0 && !phi) return tnml_fail(c, "tnml_backward_phi: null argument");
+    return backward_impl(c, "tnml_backward_phi", n, nullptr, phi, labels, coef, grad, dphi, weights, pred);
 }
 
 // ---- gradient steps on the device (kernels_sitestep.hip): the gradient above, then ONE optimiser step on W where it lies ----------------

@@ -33,11 +33,11 @@
 
 enum KClass {
     KC_FGEMM_FWD = 0, KC_FGEMM_SHIFT, KC_LABELDOT, KC_ZPRIME, KC_BGEMM, KC_SLABRED, KC_PACK, KC_VEC,
-    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_EVAL_TALLY, KC_SITE_RESP, KC_SITE_BWD, KC_SITE_GRAD, KC_STEP_NORM, KC_SITE_STEP, KC_COUNT
+    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_EVAL_TALLY, KC_SITE_RESP, KC_SITE_BWD, KC_SITE_GRAD, KC_STEP_NORM, KC_SITE_STEP, KC_INPUT_GRAD, KC_COUNT
 };
 static const char* const kclass_names[KC_COUNT] = {
     "fgemm_fwd", "fgemm_shift", "labeldot", "zprime", "bgemm", "slab_reduce", "pack", "cg_vec",
-    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain", "eval_tally", "site_resp", "site_bwd", "site_grad", "step_norm", "site_step"};
+    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain", "eval_tally", "site_resp", "site_bwd", "site_grad", "step_norm", "site_step", "input_grad"};
 
 // device accumulator block of tnml_evaluate_*: the part of tnml_eval_report that k_eval_tally (kernels_eval.hip) adds up
 struct EvalAcc {
@@ -354,6 +354,10 @@ struct tnml_ctx {
     long long* sg_goff = nullptr; int* sg_blk0 = nullptr;  // [N + 1] first element of every site in sg_grad; [N + nl] first output block of every virtual site, then the block count
     double* sg_grad = nullptr; size_t sg_grad_elems = 0;   // the gradient of the call in progress, every site in tnml_get_site's layout; grown when W has grown
     double *sg_tape = nullptr, *sg_tape2 = nullptr; size_t sg_tape_rows = 0;   // [cap / T][sg_tape_rows][T] each: inward and outward vectors; grown when W has grown
+    // streamed input gradients (tnml_backward_u8 / tnml_backward_phi, kernels_inputgrad.hip): the gradient workspace `sg` and, from the first call
+    // that asks for dphi on, two buffers of their own, counted in sg.bytes and released with it
+    double *bw_out = nullptr, *bw_outT = nullptr;          // dphi of a chunk as the kernel leaves it [N][2][cap] and as the caller gets it [cap][N][2]
+    bool attr_inputgrad = false;     // the LDS attribute of the k_input_grad instantiations is set
     // gradient steps on the device (tnml_site_step_u8 / tnml_site_step_phi, kernels_sitestep.hip): the optimiser state.  Allocated by the first
     // step for a method and the site shapes of W at that moment, counted in `bytes` and st_bytes, freed by tnml_site_step_reset and tnml_destroy;
     // no part of `sg`: a change of gradient_chunk and tnml_set_input_map leave it alone
@@ -637,6 +641,8 @@ struct RespArgs {
 };
 // rows: rowoff[N + 3] as the host knows it; tape_elems: doubles behind a.tape; outT [cnt][N][2] receives the transposed a.resp; class site_resp
 int launch_response(tnml_ctx* c, RespArgs a, int maxbond, int T, int rows, size_t tape_elems, double* outT);
+// in [rows][ld] (images fastest) -> out [cnt][rows] (k_response_transpose); no ProfScope of its own
+int launch_response_transpose(tnml_ctx* c, const double* in, int rows, int cnt, int ld, double* out);
 
 // ---- kernels_sitegrad.hip: streamed site gradients, k_site_backward (two walks, two tapes) and k_site_grad (the GEMM over the image index) ----
 struct SiteGradArgs {
@@ -652,7 +658,23 @@ struct SiteGradArgs {
     int loss = 0; double beta = 1.;    // labels mode: TNML_LOSS_SOFTMAX forms coef by loss_dev.h with the logits beta W_l (k_site_backward<.., .., 1>)
 };
 // rows: rowoff[N + 1] as the host knows it; tape_elems: doubles behind each tape; nblocks: the block count; classes site_bwd, site_grad
-int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int rows, size_t tape_elems, int nblocks);
+// run_gemm false (tnml_backward_* without grad): k_site_backward alone
+int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int rows, size_t tape_elems, int nblocks, bool run_gemm = true);
+
+// ---- kernels_inputgrad.hip: streamed input gradients, one bilinear form per site, feature component and image on the tapes of k_site_backward ----
+struct InputGradArgs {
+    const ChainSite<double>* sites;    // [N] device
+    int N, cs, nl, ld, cnt;            // as ChainArgs has them
+    const int* rowoff;                 // [N + 2] device: the region table of the two tapes
+    const double* tape;                // [grid][rows][T] inward vectors, as k_site_backward left them for this chunk
+    const double* tape2;               // [grid][rows][T] outward vectors
+    const double* coef;                // [ld][nl]: given, or formed by k_site_backward
+    double* dphi;                      // [N][2][ld]
+    int mcap = 0;                      // set by launch_input_grad
+};
+// T: the tile width k_site_backward ran this chunk with; rows: rowoff[N + 1] as the host knows it; outT [cnt][N][2] receives the transposed
+// a.dphi; class input_grad (the transposing copy: class pack)
+int launch_input_grad(tnml_ctx* c, InputGradArgs a, int maxbond, int T, int rows, size_t tape_elems, double* outT);
 
 // ---- kernels_sitestep.hip: one optimiser step on W from the gradient tnml_site_gradient_*'s kernels left on the device ----
 #define STEP_NORM_BLOCK 65536      /* elements per block sum of the norm pass */

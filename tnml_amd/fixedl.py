@@ -415,6 +415,47 @@ class TrainStates:
         self._note_chunk(n)
         return (grads, (w, pred)) if want_weights else grads
 
+    def backward(self, labels=None, coef=None, pixels=None, phi=None, want_sites=True, want_inputs=True, want_weights=False):
+        """streamed backward pass (tnml_backward_u8 / tnml_backward_phi) in the input forms and the labels / coef rule of
+        site_gradient(): -> (grads | None, dphi | None[, (weights, pred)]).  grads (want_sites) is site_gradient()'s list, bit for
+        bit; dphi[n, N, 2] (want_inputs) is the gradient with respect to the features, dphi[n, j, s] = sum_l c[n, l] dW_l(x_n)/dphi[n, j, s]
+        (under an input map: the features of the N reduced sites).  Without want_sites the gradient GEMM is not launched.  At least
+        one of the two must be asked for.  Reads W only; fp64 only."""
+        x = self._streamed_input(pixels, phi, None)
+        n = int(x.shape[0])
+        lp = cp = None
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.shape != (n,):
+                raise ValueError("labels must have shape [%d], got %s" % (n, lab.shape))
+            lp = lab.ctypes.data_as(C.POINTER(C.c_int32))
+        if coef is not None:
+            cf = np.ascontiguousarray(coef, dtype=np.float64)
+            if cf.shape != (n, self.nl):
+                raise ValueError("coef must have shape [%d, %d], got %s" % (n, self.nl, cf.shape))
+            cp = _lib.dptr(cf)
+        grad = gp = dphi = dp = None
+        if want_sites:
+            elems = C.c_int64()
+            self._ck(self._L.tnml_site_gradient_size(self._h, C.byref(elems), None))
+            grad = np.zeros(max(elems.value, 1))
+            gp = _lib.dptr(grad)
+        if want_inputs:
+            dphi = np.zeros((n, self.N, 2))
+            dp = _lib.dptr(dphi)
+        w = pred = wp = pp = None
+        if want_weights:
+            w = np.zeros((n, self.nl))
+            pred = np.zeros(n, dtype=np.int32)
+            wp, pp = _lib.dptr(w), pred.ctypes.data_as(C.POINTER(C.c_int32))
+        if pixels is not None:
+            self._ck(self._L.tnml_backward_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), lp, cp, gp, dp, wp, pp))
+        else:
+            self._ck(self._L.tnml_backward_phi(self._h, n, _lib.dptr(x), lp, cp, gp, dp, wp, pp))
+        grads = self._split_sites(grad) if want_sites else None
+        self._note_chunk(n)
+        return (grads, dphi, (w, pred)) if want_weights else (grads, dphi)
+
     def _note_chunk(self, n):
         """the size of the last chunk of a gradient or step call on n images (gradient_coef)"""
         if n > 0:

@@ -42,6 +42,7 @@ EXPORTS = [
     "tnml_site_gradient_size", "tnml_site_gradient_u8", "tnml_site_gradient_phi",
     "tnml_site_step_u8", "tnml_site_step_phi", "tnml_site_step_reset", "tnml_site_step_state",
     "tnml_site_gradient_coef",
+    "tnml_backward_u8", "tnml_backward_phi",
 ]
 
 
@@ -175,6 +176,8 @@ def load():
     L.tnml_site_step_reset.argtypes = [vp]
     L.tnml_site_step_state.argtypes = [vp, C.c_char_p, dp, C.c_int64]
     L.tnml_site_gradient_coef.argtypes = [vp, dp, C.c_int64]
+    L.tnml_backward_u8.argtypes = [vp, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), dp, dp, dp, dp, C.POINTER(C.c_int32)]
+    L.tnml_backward_phi.argtypes = [vp, C.c_int64, dp, C.POINTER(C.c_int32), dp, dp, dp, dp, C.POINTER(C.c_int32)]
     L.tnml_set_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_get_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_replica_check.argtypes = [vp, ip]
