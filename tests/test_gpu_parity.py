@@ -1736,6 +1736,14 @@ def test_environments_spill_to_host_memory_and_the_sweep_does_not_notice():
         for j in free["envs"]:
             assert np.array_equal(tight["envs"][j], free["envs"][j]), (j, async_copies)
         assert np.array_equal(tight["acc"][0], free["acc"][0]) and np.array_equal(tight["acc"][1], free["acc"][1])
+    # ... and the oracle's: the second sweep ended at bond 1 of half 2, so the environments of sites 3..N are the right environments of the
+    # final W.  TOL["f64"]["E"] was set for the 12-site chain of test_envs_after_init and the rounding error of a shifted environment grows
+    # with the number of shifts behind it: the gate is that tolerance times N / 12.  (The budgeted runs equal the resident one bit for bit.)
+    from oracle import pyoracle
+    o = pyoracle.Oracle(phi, labels, free["W"])
+    o.init()
+    for j in range(3, N + 1):
+        assert _relmax(free["envs"][j], o.env(j)) < TOL["f64"]["E"] * N / 12, j
 
 
 def test_fixedl_driver_with_an_environment_budget_prints_the_same_log(tmp_path):
