@@ -568,6 +568,75 @@ int tnml_site_step_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/
 int tnml_site_step_reset(tnml_ctx* ctx);                                                    /* frees the optimiser state; t starts over */
 int tnml_site_step_state(tnml_ctx* ctx, const char* which /* "m" | "v" */, double* out, int64_t count);
 
+/* ---- device-resident arguments: the streamed calls on arrays that already live on the device ---------------------------
+ * tnml_predict_dev, tnml_evaluate_dev, tnml_response_dev, tnml_backward_dev (which covers tnml_site_gradient_*: give grad alone) and
+ * tnml_site_step_dev are the host-pointer calls of their names with every array of the batch and every output in device memory of the
+ * context's device: a tensor another library made there (a torch CUDA tensor's data_ptr(), say) is served without crossing the bus.
+ * Same meaning: the labels / coef rule, "loss" / "loss_beta", the input map (pixels is then [n][src_rows*src_cols]), the per-label
+ * variant, "predict_dtype" for predict and evaluate, the chunk options and "predict_tile", the refusals in the same words, n = 0 and
+ * what a step does to the context are those of the host-pointer calls.  Same code, same kernels, same bits: both families run the
+ * same chunk loop with the memory space as a parameter, and every output is bit for bit the host-pointer call's on the same values.
+ * The batch: exactly one of pixels, phi and phi32.  phi32 holds fp32 features; k_chain_stage_phi widens them (exactly) while it
+ * stages, so the results are those of phi on the widened values.  The outputs: any may be NULL; what a call does not produce is
+ * ignored (predict / evaluate: weights, pred; response: resp, weights, pred; backward: grad, dphi or dphi32, weights, pred).  At most
+ * one of dphi and dphi32; dphi32 is dphi rounded once to fp32 by the transposing kernel.  rep stays a host pointer.
+ * What moves: nothing of the size of the images.  The stage kernels (k_chain_stage_u8, k_chain_stage_phi, k_stage_codes) read the
+ * caller's array at the chunk's offset; the chain kernels write weights and pred into the caller's arrays at the chunk's offset; the
+ * transposing kernel writes resp, dphi and dphi32 into the caller's arrays.  Device-to-device copies that remain, and why:
+ *   labels, coef, which : a chunk's worth into the small staging arrays of the workspace (4 C, 8 nl C, 4 C bytes): the labels mode
+ *                         overwrites the coefficients in that array, and tnml_site_gradient_coef reads it afterwards;
+ *   grad                : ONE copy of 8 E bytes at the end of the call: the sum is made in the workspace's gradient, where
+ *                         tnml_site_step_dev's optimiser reads it, so that the call's bits and launches are the host call's.
+ * Stream contract.  batch->stream is the hipStream_t that last wrote the inputs (NULL: the null stream).  On entry the call records an
+ * event on it and makes the context's stream wait for that event; the caller's stream is never synchronised by the host.  Before it
+ * returns, the call synchronises the context's stream, as every streamed call does: on return the outputs are complete for any
+ * stream, and no argument is read any more (an allocator may recycle it).  One event per context, made by the first _dev call with
+ * timing disabled, released with the check block (below) and by tnml_destroy.
+ * Pointer checks, made before hipSetDevice and before anything is launched or allocated.  Every non-NULL array of the batch and every
+ * non-NULL output the call produces must be, as hipPointerGetAttributes and hipMemGetAddressRange describe it: device memory (what
+ * the runtime does not know -- plain malloc memory --, managed memory and host memory registered with the runtime are refused and
+ * never dereferenced); on the context's device; aligned to its element (8 bytes for doubles, 4 for int32 and float); with the bytes
+ * the call needs lying inside its allocation (a pointer into the middle of an allocation is fine).  No output may share a byte with
+ * an input or another output.  The message names the argument and the reason.
+ * Value checks.  Where the host-pointer calls walk labels / coef / which on the CPU, these calls make ONE launch of k_check_batch
+ * (kernels_iocheck.hip, profile class "io_check") over the whole batch before the chunk loop -- a call with none of the three arrays
+ * makes the launch too, with nothing to walk, and does not read the block back --, read its 24-byte block once, and refuse in the host
+ * path's words ("label %d of image %lld out of range",
+ * "coefficient %d of image %lld is not finite", "which = %d of image %lld out of range 0..%d": the smallest offending index, as the
+ * host loop finds it).  A refused call leaves every output untouched.  Beyond that launch the launches of a call, class by class,
+ * are the host-pointer call's.
+ * Workspace: the host-pointer call's formulas without the buffer the images are copied into (2 N C of the bytes form's 2 N C, S C of
+ * the map form's, 16 N C of the features form's 32 N C; predict's fp32 features form: 16 N C of its 24 N C) and without the transposed
+ * result (16 N C of response's and of backward's 32 N C); a later host-pointer call of that form adds them, and host-pointer calls
+ * allocate exactly what they allocated before.  On top, made by the first _dev call (n > 0):
+ *             24    bytes (the block of k_check_batch), counted by tnml_device_bytes.  The block and the event are released with the
+ *                   workspaces -- when the last of the predict, response and gradient workspaces is released (a changed chunk option,
+ *                   tnml_set_input_map, tnml_destroy) -- and made again by the next _dev call.
+ * tnml_set_site_dev / tnml_get_site_dev are tnml_set_site / tnml_get_site (same rules, same words) on a device array in
+ * tnml_get_site's layout: the same pointer checks, the same entry wait on `stream`, ONE device-to-device copy on the context's
+ * stream and a synchronisation before they return.
+ * tnml_abi_layout is a test entry: for name = "tnml_dev_batch" / "tnml_dev_out" it writes sizeof and then the offset of every field
+ * in declaration order to sizes_out (16 entries suffice) and returns how many it wrote; -1 for another name. */
+typedef struct {
+    int64_t        n;
+    const uint8_t* pixels;   /* device [n][N], or [n][S] under an input map */
+    const double*  phi;      /* device [n][N][2] */
+    const float*   phi32;    /* device [n][N][2], widened exactly to fp64 while staging */   /* exactly one of the three */
+    const int32_t* labels;   /* device [n] or NULL */
+    const double*  coef;     /* device [n][nl] or NULL */
+    const int32_t* which;    /* device [n] or NULL (responses only) */
+    void*          stream;   /* hipStream_t that last wrote the inputs; NULL = the null stream */
+} tnml_dev_batch;
+typedef struct { double* weights; int32_t* pred; double* resp; double* grad; double* dphi; float* dphi32; } tnml_dev_out;  /* device, any may be NULL */
+int tnml_predict_dev  (tnml_ctx* ctx, const tnml_dev_batch* batch, const tnml_dev_out* out);
+int tnml_evaluate_dev (tnml_ctx* ctx, const tnml_dev_batch* batch, const tnml_dev_out* out, tnml_eval_report* rep /* host */);
+int tnml_response_dev (tnml_ctx* ctx, const tnml_dev_batch* batch, const tnml_dev_out* out);
+int tnml_backward_dev (tnml_ctx* ctx, const tnml_dev_batch* batch, const tnml_dev_out* out);
+int tnml_site_step_dev(tnml_ctx* ctx, const tnml_dev_batch* batch, const tnml_step_params* p, tnml_step_report* rep /* host, or NULL */);
+int tnml_set_site_dev (tnml_ctx* ctx, int j, int ml, int mr, int has_label, const double* A_dev, void* stream);
+int tnml_get_site_dev (tnml_ctx* ctx, int j, double* A_dev, void* stream);
+int tnml_abi_layout(const char* name, int64_t* sizes_out);
+
 /* ---- held-out evaluation during training ----------------------------------------------------------
  * A held-out set is an ordinary context created for the held-out images (one rank: nranks = 1, its own shard of the set in
  * a multi-rank run).  Once attached to a training context, every bond update of `train` also moves the two site tensors it

@@ -119,8 +119,9 @@ __global__ void k_chain_stage_u8(const uint8_t* __restrict__ pix, int N, int cnt
         xT[(size_t)j * ld + n] = pix[(size_t)n * N + j];
     }
 }
-template <typename E>
-__global__ void k_chain_stage_phi(const double* __restrict__ phi, int N, int cnt, int ld, E* __restrict__ phiT) {
+// S: the element type of the caller's features (double; float for the phi32 of a device-resident batch, which widens exactly)
+template <typename E, typename S>
+__global__ void k_chain_stage_phi(const S* __restrict__ phi, int N, int cnt, int ld, E* __restrict__ phiT) {
     const size_t total = (size_t)N * 2 * cnt;
     for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int js = (int)(idx / cnt), n = (int)(idx % cnt);          // js = 2 (j - 1) + s
@@ -205,17 +206,18 @@ int launch_codes_phi(tnml_ctx* c, const uint16_t* codes, const void* tab, int N,
 }
 
 template <typename E>
-int launch_chain_stage(tnml_ctx* c, const uint8_t* pix, const double* phi, int N, int cnt, int ld, uint8_t* xT, E* phiT) {
+int launch_chain_stage(tnml_ctx* c, const uint8_t* pix, const double* phi, int N, int cnt, int ld, uint8_t* xT, E* phiT, const float* phi32) {
     ProfScope ps(c, KC_PACK);
     const size_t total = (size_t)N * cnt * (pix ? 1 : 2);
     const int grid = (int)std::min<size_t>((total + 255) / 256, 4096);
-    if (pix) hipLaunchKernelGGL(k_chain_stage_u8, dim3(grid), dim3(256), 0, c->stream, pix, N, cnt, ld, xT);
-    else     hipLaunchKernelGGL(k_chain_stage_phi<E>, dim3(grid), dim3(256), 0, c->stream, phi, N, cnt, ld, phiT);
+    if (pix)      hipLaunchKernelGGL(k_chain_stage_u8, dim3(grid), dim3(256), 0, c->stream, pix, N, cnt, ld, xT);
+    else if (phi) hipLaunchKernelGGL((k_chain_stage_phi<E, double>), dim3(grid), dim3(256), 0, c->stream, phi, N, cnt, ld, phiT);
+    else          hipLaunchKernelGGL((k_chain_stage_phi<E, float>), dim3(grid), dim3(256), 0, c->stream, phi32, N, cnt, ld, phiT);
     HIPCK(c, hipGetLastError());
     return 0;
 }
-template int launch_chain_stage<double>(tnml_ctx*, const uint8_t*, const double*, int, int, int, uint8_t*, double*);
-template int launch_chain_stage<float>(tnml_ctx*, const uint8_t*, const double*, int, int, int, uint8_t*, float*);
+template int launch_chain_stage<double>(tnml_ctx*, const uint8_t*, const double*, int, int, int, uint8_t*, double*, const float*);
+template int launch_chain_stage<float>(tnml_ctx*, const uint8_t*, const double*, int, int, int, uint8_t*, float*, const float*);
 
 // W -> its fp32 copy: blockIdx.y is the site, src[site] the fp64 tensor where it lives, dst[site] its place in the packed workspace;
 // the Label site `lsite` (1-indexed; none: <= 0) carries nl times the elements

@@ -140,12 +140,12 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_input_grad(const InputGradArg
 }
 
 // a.mcap and the grid follow from T and maxbond; rows: a.rowoff[N + 1] as the host knows it; tape_elems: doubles behind each of the two tapes
-int launch_input_grad(tnml_ctx* c, InputGradArgs a, int maxbond, int T, int rows, size_t tape_elems, double* outT) {
+int launch_input_grad(tnml_ctx* c, InputGradArgs a, int maxbond, int T, int rows, size_t tape_elems, double* outT, float* outT32) {
     const char* const name = "input gradient kernel";
     if (maxbond < 1 || maxbond > TNML_CHAIN_MAXM) return tnml_fail(c, "%s: bond dimension %d outside 1..%d", name, maxbond, TNML_CHAIN_MAXM);
     if (a.cnt < 1 || a.cnt > a.ld) return tnml_fail(c, "%s: %d images in a chunk of %d", name, a.cnt, a.ld);
     if (T != 64 && T != 32 && T != 16) return tnml_fail(c, "%s: tile width %d", name, T);
-    if (!a.tape || !a.tape2 || !a.coef || !a.dphi || !outT) return tnml_fail(c, "%s: null argument", name);
+    if (!a.tape || !a.tape2 || !a.coef || !a.dphi || (!outT && !outT32)) return tnml_fail(c, "%s: null argument", name);
     a.mcap = (maxbond + 15) / 16 * 16;
     const int grid = (a.cnt + T - 1) / T;
     const size_t lds = ((size_t)a.mcap * T + (size_t)CHAIN_WAVES * 2 * T) * sizeof(double);
@@ -165,5 +165,5 @@ int launch_input_grad(tnml_ctx* c, InputGradArgs a, int maxbond, int T, int rows
         HIPCK(c, hipGetLastError());
     }
     ProfScope ps(c, KC_PACK);
-    return launch_response_transpose(c, a.dphi, 2 * a.N, a.cnt, a.ld, outT);
+    return launch_response_transpose(c, a.dphi, 2 * a.N, a.cnt, a.ld, outT, outT32);
 }

@@ -221,7 +221,8 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
 }
 
 // the staged result [2 N][ld] (images fastest) -> [cnt][2 N]: 32 x 32 tiles through LDS, both sides in whole lines
-__global__ __launch_bounds__(256) void k_response_transpose(const double* __restrict__ in, int rows, int cnt, int ld, double* __restrict__ out) {
+template <typename D>                                                  // D: double, or float (the result rounded once: dphi32 of a device-resident call)
+__global__ __launch_bounds__(256) void k_response_transpose(const double* __restrict__ in, int rows, int cnt, int ld, D* __restrict__ out) {
     __shared__ double tile[32][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int n0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
@@ -229,11 +230,13 @@ __global__ __launch_bounds__(256) void k_response_transpose(const double* __rest
         if (r0 + i < rows && n0 + tx < cnt) tile[i][tx] = in[(size_t)(r0 + i) * ld + n0 + tx];
     __syncthreads();
     for (int i = ty; i < 32; i += 8)
-        if (n0 + i < cnt && r0 + tx < rows) out[(size_t)(n0 + i) * rows + r0 + tx] = tile[tx][i];
+        if (n0 + i < cnt && r0 + tx < rows) out[(size_t)(n0 + i) * rows + r0 + tx] = (D)tile[tx][i];
 }
 
-int launch_response_transpose(tnml_ctx* c, const double* in, int rows, int cnt, int ld, double* out) {
-    hipLaunchKernelGGL(k_response_transpose, dim3((cnt + 31) / 32, (rows + 31) / 32), dim3(256), 0, c->stream, in, rows, cnt, ld, out);
+int launch_response_transpose(tnml_ctx* c, const double* in, int rows, int cnt, int ld, double* out, float* out32) {
+    const dim3 grid((cnt + 31) / 32, (rows + 31) / 32);
+    if (out) hipLaunchKernelGGL(k_response_transpose<double>, grid, dim3(256), 0, c->stream, in, rows, cnt, ld, out);
+    else     hipLaunchKernelGGL(k_response_transpose<float>, grid, dim3(256), 0, c->stream, in, rows, cnt, ld, out32);
     HIPCK(c, hipGetLastError());
     return 0;
 }

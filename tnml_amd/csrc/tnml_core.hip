@@ -459,6 +459,7 @@ int tnml_destroy(tnml_ctx* c) {
     response_release(c);                                  // and of tnml_response_*
     sitegrad_release(c);                                  // and of tnml_site_gradient_*
     step_release(c);                                      // the optimiser state of tnml_site_step_*
+    io_release(c);                                        // the check block and the entry event of the tnml_*_dev calls
     for (auto& sl : c->slabs) if (sl.base) (void)hipFree(sl.base);
     if (c->hrep) (void)hipHostFree(c->hrep);
     if (c->hcost) (void)hipHostFree(c->hcost);

@@ -157,13 +157,18 @@ int tnml_set_data_phi(tnml_ctx* c, const double* phi, const int32_t* labels) {
 }
 
 // ---- weight MPS replica -------------------------------------------------------------------------
-int tnml_set_site(tnml_ctx* c, int j, int ml, int mr, int has_label, const double* A) {
-    TCK(ho_locked(c, "tnml_set_site", true));
+// what tnml_set_site asks of its arguments, in its words
+static int set_site_rules(tnml_ctx* c, int j, int ml, int mr, int has_label) {
     if (j < 1 || j > c->N) return tnml_fail(c, "tnml_set_site: site %d out of range", j);
     if (c->single() && has_label) return tnml_fail(c, "tnml_set_site: the per-label variant has no Label index");
     if ((j == c->c0) != (has_label != 0)) return tnml_fail(c, "Label Index not on site %d", c->c0);     // fixedL.cc:734
     if (ml < 1 || mr < 1 || ml > c->maxm || mr > c->maxm) return tnml_fail(c, "tnml_set_site: bond dimension outside 1..maxm");
     if ((j == 1 && ml != 1) || (j == c->N && mr != 1)) return tnml_fail(c, "tnml_set_site: edge sites must have outer dimension 1");
+    return 0;
+}
+int tnml_set_site(tnml_ctx* c, int j, int ml, int mr, int has_label, const double* A) {
+    TCK(ho_locked(c, "tnml_set_site", true));
+    TCK(set_site_rules(c, j, ml, mr, has_label));
     SiteT& s = c->W[j];
     s.ml = ml; s.mr = mr; s.L = has_label ? TNML_NL : 1; s.set = true; s.placed = false;
     HIPCK(c, hipMemcpy(s.a, A, sizeof(double) * (size_t)ml * 2 * mr * s.L, hipMemcpyHostToDevice));
@@ -181,6 +186,75 @@ int tnml_get_site(tnml_ctx* c, int j, double* A) {
     const SiteT& s = c->W[j];
     SYNCK(c, c->stream);
     HIPCK(c, hipMemcpy(A, s.a, sizeof(double) * (size_t)s.ml * 2 * s.mr * s.L, hipMemcpyDeviceToHost));
+    return 0;
+}
+// ---- device-resident arguments (tnml.h, "device-resident arguments") ------------------------------------------------
+int dev_check_args(tnml_ctx* c, const char* who, const std::vector<DevArg>& args) {
+    struct Range { const char* name; uintptr_t lo, hi; bool out; };
+    std::vector<Range> seen;
+    for (const DevArg& a : args) {
+        if (!a.p) continue;
+        hipPointerAttribute_t at;
+        memset(&at, 0, sizeof(at));
+        const hipError_t e = hipPointerGetAttributes(&at, a.p);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();                      // (the runtime keeps the error of a pointer it does not know)
+            return tnml_fail(c, "%s: %s = %p is not device memory: the runtime does not know the pointer (%s)", who, a.name, a.p, hipGetErrorString(e));
+        }
+        if (at.type != hipMemoryTypeDevice || at.isManaged)
+            return tnml_fail(c, "%s: %s = %p is not device memory (%s): the _dev calls take plain device allocations only", who, a.name, a.p,
+                             at.isManaged || at.type == hipMemoryTypeManaged ? "managed memory" : at.type == hipMemoryTypeHost ? "host memory known to the runtime" : "memory the runtime does not describe");
+        if (at.device != c->cfg.device) return tnml_fail(c, "%s: %s = %p lies on device %d, the context is on device %d", who, a.name, a.p, at.device, c->cfg.device);
+        const uintptr_t lo = (uintptr_t)a.p;
+        if (a.align > 1 && lo % a.align) return tnml_fail(c, "%s: %s = %p is not aligned to %zu bytes", who, a.name, a.p, a.align);
+        hipDeviceptr_t base = nullptr; size_t size = 0;
+        const hipError_t r = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)a.p);
+        if (r != hipSuccess) {
+            (void)hipGetLastError();
+            return tnml_fail(c, "%s: %s = %p: the runtime gives no allocation for the pointer (%s)", who, a.name, a.p, hipGetErrorString(r));
+        }
+        const uintptr_t b0 = (uintptr_t)base;
+        if (lo < b0 || a.bytes > size || lo - b0 > size - a.bytes)
+            return tnml_fail(c, "%s: %s = %p needs %zu bytes, its allocation ends %zu bytes behind it", who, a.name, a.p, a.bytes, (size_t)(b0 + size > lo ? b0 + size - lo : 0));
+        for (const Range& o : seen)
+            if ((a.out || o.out) && a.bytes && lo < o.hi && o.lo < lo + a.bytes)
+                return tnml_fail(c, "%s: %s overlaps %s: an output may share no byte with another argument", who, a.name, o.name);
+        if (a.bytes) seen.push_back({a.name, lo, lo + a.bytes, a.out});
+    }
+    return 0;
+}
+int dev_entry_wait(tnml_ctx* c, const char* who, void* stream) {
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if (!c->io_ev && hipEventCreateWithFlags(&c->io_ev, hipEventDisableTiming) != hipSuccess) { c->io_ev = nullptr; return tnml_fail(c, "%s: hipEventCreate failed", who); }
+    if ((hipStream_t)stream == c->stream) return 0;
+    HIPCK(c, hipEventRecord(c->io_ev, (hipStream_t)stream));
+    HIPCK(c, hipStreamWaitEvent(c->stream, c->io_ev, 0));
+    return 0;
+}
+int tnml_set_site_dev(tnml_ctx* c, int j, int ml, int mr, int has_label, const double* A_dev, void* stream) {
+    if (!c || !A_dev) return tnml_fail(c, "tnml_set_site_dev: null argument");
+    TCK(ho_locked(c, "tnml_set_site_dev", true));
+    TCK(set_site_rules(c, j, ml, mr, has_label));
+    const size_t bytes = sizeof(double) * (size_t)ml * 2 * mr * (has_label ? TNML_NL : 1);
+    TCK(dev_check_args(c, "tnml_set_site_dev", {{"A_dev", A_dev, bytes, 8, false}}));
+    TCK(dev_entry_wait(c, "tnml_set_site_dev", stream));
+    SiteT& s = c->W[j];
+    HIPCK(c, hipMemcpyAsync(s.a, A_dev, bytes, hipMemcpyDeviceToDevice, c->stream));
+    SYNCK(c, c->stream);
+    s.ml = ml; s.mr = mr; s.L = has_label ? TNML_NL : 1; s.set = true; s.placed = false;
+    c->currb = -1; c->p_valid = false; c->sweep_start = false;
+    for (int b = j - 1; b <= j; ++b) if (b >= 1 && b < (int)c->bond_hist.size()) c->bond_hist[b] = tnml_ctx::BondHist();
+    return 0;
+}
+int tnml_get_site_dev(tnml_ctx* c, int j, double* A_dev, void* stream) {
+    if (!c || !A_dev) return tnml_fail(c, "tnml_get_site_dev: null argument");
+    if (j < 1 || j > c->N || !c->W[j].set) return tnml_fail(c, "tnml_get_site: site %d not set", j);
+    const SiteT& s = c->W[j];
+    const size_t bytes = sizeof(double) * (size_t)s.ml * 2 * s.mr * s.L;
+    TCK(dev_check_args(c, "tnml_get_site_dev", {{"A_dev", A_dev, bytes, 8, true}}));
+    TCK(dev_entry_wait(c, "tnml_get_site_dev", stream));
+    HIPCK(c, hipMemcpyAsync(A_dev, s.a, bytes, hipMemcpyDeviceToDevice, c->stream));
+    SYNCK(c, c->stream);
     return 0;
 }
 int check_W(tnml_ctx* c) {

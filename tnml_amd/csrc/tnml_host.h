@@ -84,6 +84,22 @@ bool fingerprint_agrees(const double* sums8, int nranks);
 StageGeom stage_geom(const tnml_ctx* c);
 int check_W(tnml_ctx* c);
 
+// device-resident arguments (the tnml_*_dev calls, tnml.h): the memory space of a streamed call's arrays, and what goes with it
+struct StreamIO {
+    bool dev = false;                  // the arrays of the call are device memory (false: host pointers, every other field unused)
+    const float* phi32 = nullptr;      // fp32 features [n][N][2] instead of phi: widened exactly while staging
+    float* dphi32 = nullptr;           // the input gradients rounded once to fp32, instead of dphi
+    void* stream = nullptr;            // the hipStream_t that last wrote the inputs
+    bool entered = false;              // the pointer checks, the entry wait and the value check of this call have been made
+    hipMemcpyKind in() const { return dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; }
+};
+struct DevArg { const char* name; const void* p; size_t bytes; size_t align; bool out; };
+// Every argument with p non-null: device memory of the context's device as the runtime describes it, aligned, [p, p + bytes) inside
+// its allocation, no output range overlapping another argument's.  Nothing is dereferenced, launched or allocated.
+int dev_check_args(tnml_ctx* c, const char* who, const std::vector<DevArg>& args);
+// hipSetDevice, then the context's stream waits for what `stream` holds now (the one event of the context, made by the first call)
+int dev_entry_wait(tnml_ctx* c, const char* who, void* stream);
+
 // ---- tnml_env.hip -----------------------------------------------------------------------------
 void slot_release(tnml_ctx* c, EnvSlot& e);
 // consumer: the stream whose work will touch the new unit first (it waits for a copy to the host that may still be reading the slab)
@@ -101,6 +117,7 @@ void predict_release_map(tnml_ctx* c);                 // of tnml_predict_*, the
 void predict_release(tnml_ctx* c);
 void response_release(tnml_ctx* c);
 void sitegrad_release(tnml_ctx* c);
+void io_release(tnml_ctx* c);                          // what the tnml_*_dev calls keep: the check block and the entry event; synchronise first
 void step_release(tnml_ctx* c);                        // the optimiser state of tnml_site_step_* (the st_ fields); synchronise first
 
 // ---- tnml_bond.hip ----------------------------------------------------------------------------

@@ -92,6 +92,12 @@ static void ws_release(tnml_ctx* c, StreamWs& s, std::vector<void**> slots) {
     for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
     c->bytes -= s.bytes;
     s.bytes = 0; s.cap = 0;
+    if (!c->pk.bytes && !c->rs.bytes && !c->sg.bytes) io_release(c);     // the last streamed workspace has gone: what the _dev calls keep goes with it
+}
+// the check block and the entry event of the tnml_*_dev calls (made by the first such call; the next one makes them again)
+void io_release(tnml_ctx* c) {
+    if (c->io_blk) { (void)hipFree(c->io_blk); c->io_blk = nullptr; c->bytes -= 3 * (int64_t)sizeof(unsigned long long); }
+    if (c->io_ev) { (void)hipEventDestroy(c->io_ev); c->io_ev = nullptr; }
 }
 // the part of the predict workspace that follows the input map: released by tnml_set_input_map, re-made by the next tnml_predict_u8 under a map
 void predict_release_map(tnml_ctx* c) {
@@ -142,20 +148,23 @@ static int ws_grow(tnml_ctx* c, StreamWs& s, size_t want, size_t* have, size_t u
 }
 // The staging buffers of the call's input form, made by the first call of that form.  Under an input map S C + 2 N C + 16 ncodes bytes: the
 // bytes as given, the block sums site-first, the fp64 table (uploaded here).  xphi false: the caller keeps the site-first features itself (fp32)
-static int ws_staging(tnml_ctx* c, StreamWs& s, const char* who, bool bytes_form, bool xphi = true) {
+// dev (the arrays of the call are device memory): the stage kernels read the caller's array, so the buffer the images are copied into
+// (mraw, raw8, rawphi) is left out; the first host-pointer call of that form makes it
+static int ws_staging(tnml_ctx* c, StreamWs& s, const char* who, bool bytes_form, bool xphi = true, bool dev = false) {
     const size_t cap = s.cap, N = c->N;
     if (bytes_form && c->im_set) {
-        if (s.codes) return 0;
         const size_t S = (size_t)c->im.src_rows * c->im.src_cols, tabb = c->im_table.size() * sizeof(double);
-        TCK(ws_alloc(c, s, (void**)&s.mraw, S * cap));
+        if (!dev && !s.mraw) TCK(ws_alloc(c, s, (void**)&s.mraw, S * cap));
+        if (s.codes) return 0;
         TCK(ws_alloc(c, s, (void**)&s.codes, cap * N * sizeof(uint16_t)));
         TCK(ws_alloc(c, s, (void**)&s.mtab, tabb));
         if (hipMemcpyAsync(s.mtab, c->im_table.data(), tabb, hipMemcpyHostToDevice, c->stream) != hipSuccess) return tnml_fail(c, "%s: copy of the input map's table failed", who);
         if (hipStreamSynchronize(c->stream) != hipSuccess) return tnml_fail(c, "%s: hipStreamSynchronize failed", who);
         return 0;
     }
-    if (bytes_form && !s.x8) { TCK(ws_alloc(c, s, (void**)&s.raw8, cap * N)); TCK(ws_alloc(c, s, (void**)&s.x8, cap * N)); }
-    if (!bytes_form && !s.rawphi) TCK(ws_alloc(c, s, (void**)&s.rawphi, 2 * cap * N * sizeof(double)));
+    if (bytes_form && !dev && !s.raw8) TCK(ws_alloc(c, s, (void**)&s.raw8, cap * N));
+    if (bytes_form && !s.x8) TCK(ws_alloc(c, s, (void**)&s.x8, cap * N));
+    if (!bytes_form && !dev && !s.rawphi) TCK(ws_alloc(c, s, (void**)&s.rawphi, 2 * cap * N * sizeof(double)));
     if (!bytes_form && xphi && !s.xphi) TCK(ws_alloc(c, s, (void**)&s.xphi, 2 * cap * N * sizeof(double)));
     return 0;
 }
@@ -205,19 +214,32 @@ static int tape_rows(const tnml_ctx* c, std::vector<int>& rowoff) {
     return rowoff[c->N + 1] = rows;
 }
 // the end of a chunk: weights and pred of images off .. off + cnt - 1 to the caller, then the synchronisation after which the staging buffers are reused
-static int chunk_results(tnml_ctx* c, const StreamWs& s, int64_t off, int cnt, double* weights, int32_t* pred) {
+// (device-resident arrays: the kernels have written them where the caller wants them, see chunk_dest)
+static int chunk_results(tnml_ctx* c, const StreamWs& s, int64_t off, int cnt, double* weights, int32_t* pred, bool dev = false) {
     const int nl = c->nl();
+    if (dev) { SYNCK(c, c->stream); return 0; }
     if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, s.w, sizeof(double) * (size_t)cnt * nl, hipMemcpyDeviceToHost, c->stream));
     if (pred) HIPCK(c, hipMemcpyAsync(pred + off, s.pred, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
     SYNCK(c, c->stream);
     return 0;
 }
+// where the kernels of a chunk leave weights and pred: the workspace, or -- device-resident arrays -- the caller's arrays at the chunk's offset
+static void chunk_dest(const tnml_ctx* c, const StreamWs& s, const StreamIO& io, int64_t off, double* weights, int32_t* pred, double** wout, int** pout) {
+    *wout = io.dev && weights ? weights + (size_t)off * c->nl() : s.w;
+    *pout = io.dev && pred ? pred + off : s.pred;
+}
 // One chunk's way from the caller's arrays into the staging buffers of a workspace: copy in, then the input map's block sums or one
-// transposing pre-kernel; images off .. off + cnt - 1
+// transposing pre-kernel; images off .. off + cnt - 1.  Device-resident arrays: no copy, the same kernel reads the caller's array at the
+// chunk's offset
 template <typename E>
-static int stage_chunk(tnml_ctx* c, const StreamWs& b, bool mapped, const StageGeom& sg, const uint8_t* pixels, const double* phi, int64_t off, int cnt, E* xphi) {
+static int stage_chunk(tnml_ctx* c, const StreamWs& b, bool mapped, const StageGeom& sg, const uint8_t* pixels, const double* phi, int64_t off, int cnt, E* xphi, const StreamIO& io) {
     const bool bytes_form = pixels != nullptr;
     const size_t per_img = mapped ? (size_t)sg.S : (size_t)c->N * (bytes_form ? 1 : 2 * sizeof(double));
+    if (io.dev) {
+        if (mapped) { ProfScope ps(c, KC_PACK); return launch_stage_codes(c, pixels + (size_t)off * per_img, sg, cnt, b.cap, b.codes); }
+        const size_t at = (size_t)off * c->N * 2;
+        return launch_chain_stage<E>(c, bytes_form ? pixels + (size_t)off * c->N : nullptr, phi ? phi + at : nullptr, c->N, cnt, b.cap, b.x8, xphi, io.phi32 ? io.phi32 + at : nullptr);
+    }
     if (mapped) {
         HIPCK(c, hipMemcpyAsync(b.mraw, pixels + (size_t)off * per_img, per_img * cnt, hipMemcpyHostToDevice, c->stream));
         ProfScope ps(c, KC_PACK);
@@ -228,10 +250,51 @@ static int stage_chunk(tnml_ctx* c, const StreamWs& b, bool mapped, const StageG
     return launch_chain_stage<E>(c, bytes_form ? b.raw8 : nullptr, bytes_form ? nullptr : b.rawphi, c->N, cnt, b.cap, b.x8, xphi);
 }
 
+// ---- device-resident arguments: what a tnml_*_dev call does where the host-pointer call walks its arrays on the CPU ----------
+// The arguments of the call as the runtime must know them (dev_check_args: nothing is launched or allocated before every one has
+// passed), then the entry wait on the caller's stream, then ONE k_check_batch launch over labels / coef / which -- every call makes
+// it, so that a device call is the host call's launches plus exactly this one; with none of the three arrays it has nothing to walk and
+// its block is not read back -- and the refusal in the host path's words.  The block is made by the first call, after the pointer checks.
+static size_t sitegrad_layout(tnml_ctx* c, long long* off);
+struct DevOuts { double* weights; int32_t* pred; double* resp; double* grad; double* dphi; };
+static int dev_enter(tnml_ctx* c, const char* who, StreamIO& io, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
+                     const int32_t* which, const DevOuts& o) {
+    if (io.entered) return 0;
+    const size_t N = c->N, nl = c->nl(), un = (size_t)n;
+    const size_t per_img = c->im_set ? (size_t)c->im.src_rows * c->im.src_cols : N;
+    TCK(dev_check_args(c, who, {
+        {"pixels", pixels, un * per_img, 1, false}, {"phi", phi, un * N * 2 * sizeof(double), 8, false}, {"phi32", io.phi32, un * N * 2 * sizeof(float), 4, false},
+        {"labels", labels, un * sizeof(int32_t), 4, false}, {"coef", coef, un * nl * sizeof(double), 8, false}, {"which", which, un * sizeof(int32_t), 4, false},
+        {"weights", o.weights, un * nl * sizeof(double), 8, true}, {"pred", o.pred, un * sizeof(int32_t), 4, true}, {"resp", o.resp, un * N * 2 * sizeof(double), 8, true},
+        {"grad", o.grad, o.grad ? sitegrad_layout(c, nullptr) * sizeof(double) : 0, 8, true}, {"dphi", o.dphi, un * N * 2 * sizeof(double), 8, true},
+        {"dphi32", io.dphi32, un * N * 2 * sizeof(float), 4, true}}));
+    TCK(dev_entry_wait(c, who, io.stream));
+    io.entered = true;
+    if (!c->io_blk) TCK(dalloc(c, (void**)&c->io_blk, 3 * sizeof(unsigned long long)));
+    HIPCK(c, hipMemsetAsync(c->io_blk, 0xff, 3 * sizeof(unsigned long long), c->stream));
+    TCK(launch_check_batch(c, labels, coef, which, n, (int)nl, c->io_blk));
+    if (!labels && !coef && !which) return 0;
+    unsigned long long h[3];
+    HIPCK(c, hipMemcpyAsync(h, c->io_blk, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    SYNCK(c, c->stream);
+    if (labels && h[0] != ~0ull) {
+        int32_t v = 0;
+        HIPCK(c, hipMemcpy(&v, labels + h[0], sizeof(v), hipMemcpyDeviceToHost));
+        return tnml_fail(c, "%s: label %d of image %lld out of range", who, v, (long long)h[0]);
+    }
+    if (coef && h[1] != ~0ull) return tnml_fail(c, "%s: coefficient %d of image %lld is not finite", who, (int)(h[1] % nl), (long long)(h[1] / nl));
+    if (which && h[2] != ~0ull) {
+        int32_t v = 0;
+        HIPCK(c, hipMemcpy(&v, which + h[2], sizeof(v), hipMemcpyDeviceToHost));
+        return tnml_fail(c, "%s: which = %d of image %lld out of range 0..%d", who, v, (long long)h[2], (int)nl - 1);
+    }
+    return 0;
+}
+
 // ---- streamed inference (kernels_chain.hip): ONE k_chain launch per chunk ----------
 // the workspace: the shared part, the parked vectors, the staging of the input form (the map's part counted in pk_map_bytes, the site-first
 // features in the element type of option predict_dtype) and, for tnml_evaluate_*, 4 C + sizeof(EvalAcc) bytes: the labels of a chunk and the tallies of a call
-static int predict_workspace(tnml_ctx* c, const char* who, bool bytes_form, bool f32, bool evaluate) {
+static int predict_workspace(tnml_ctx* c, const char* who, bool bytes_form, bool f32, bool evaluate, bool dev) {
     StreamWs& s = c->pk;
     bool fresh;
     int rc = ws_remake(c, s, c->predict_chunk, predict_release, &fresh);
@@ -240,7 +303,7 @@ static int predict_workspace(tnml_ctx* c, const char* who, bool bytes_form, bool
         rc = ws_alloc(c, s, (void**)&c->pk_park, c->pk_park_elems * sizeof(double));
     }
     const int64_t before = s.bytes;
-    if (!rc) rc = ws_staging(c, s, who, bytes_form, !f32);
+    if (!rc) rc = ws_staging(c, s, who, bytes_form, !f32, dev);
     if (bytes_form && c->im_set) c->pk_map_bytes += s.bytes - before;
     if (!rc && !bytes_form && f32 && !c->pk_xphi32) rc = ws_alloc(c, s, (void**)&c->pk_xphi32, (size_t)2 * s.cap * c->N * sizeof(float));
     if (!rc && evaluate && !c->pk_lab) rc = ws_alloc(c, s, (void**)&c->pk_lab, (size_t)s.cap * sizeof(int));
@@ -293,7 +356,7 @@ static int predict_workspace32(tnml_ctx* c, bool mapped, const std::vector<Chain
 // the chunk loop of predict_impl in the element type E of option predict_dtype: per chunk stage (map, bytes or phi), ONE chain launch, copy back;
 // labels (tnml_evaluate_*): the chunk's labels are staged with its images and ONE k_eval_tally launch behind the chain adds its tallies to pk_acc
 template <typename E>
-static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, double* weights, int32_t* pred, int maxbond) {
+static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, double* weights, int32_t* pred, int maxbond, const StreamIO& io) {
     constexpr bool f32 = sizeof(E) == sizeof(float);
     const StreamWs& s = c->pk;
     const bool bytes_form = pixels != nullptr;
@@ -313,13 +376,14 @@ static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t
     }
     for (int64_t off = 0; off < n; off += c->predict_chunk) {
         a.cnt = (int)std::min<int64_t>(c->predict_chunk, n - off);
-        TCK(stage_chunk<E>(c, s, mapped, sg, pixels, phi, off, a.cnt, xphi));
-        if (labels) HIPCK(c, hipMemcpyAsync(c->pk_lab, labels + off, sizeof(int32_t) * (size_t)a.cnt, hipMemcpyHostToDevice, c->stream));
+        TCK(stage_chunk<E>(c, s, mapped, sg, pixels, phi, off, a.cnt, xphi, io));
+        chunk_dest(c, s, io, off, weights, pred, &a.wout, &a.pred);
+        if (labels) HIPCK(c, hipMemcpyAsync(c->pk_lab, labels + off, sizeof(int32_t) * (size_t)a.cnt, io.in(), c->stream));
         TCK(launch_chain<E>(c, a, maxbond, chain_tile<E>(c, maxbond, a.cnt), park, park_elems));
-        if (labels) TCK(launch_eval_tally(c, s.w, s.pred, c->pk_lab, a.cnt, a.nl, a.single, c->target(), c->pk_acc, c->loss, c->loss_beta));
+        if (labels) TCK(launch_eval_tally(c, a.wout, a.pred, c->pk_lab, a.cnt, a.nl, a.single, c->target(), c->pk_acc, c->loss, c->loss_beta));
         int flag = 0;
         if (f32) HIPCK(c, hipMemcpyAsync(&flag, c->pk_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        TCK(chunk_results(c, s, off, a.cnt, weights, pred));
+        TCK(chunk_results(c, s, off, a.cnt, weights, pred, io.dev));
         if (flag) {
             HIPCK(c, hipMemsetAsync(c->pk_flag, 0, sizeof(int), c->stream));
             HIPCK(c, hipStreamSynchronize(c->stream));
@@ -344,25 +408,27 @@ static tnml_eval_report eval_report_of(const EvalAcc& h, int64_t n) {
 }
 // rep: the call is tnml_evaluate_* (labels are then required when n > 0); *rep is written once, after everything has succeeded
 static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, double* weights, int32_t* pred,
-                        bool evaluate = false, const int32_t* labels = nullptr, tnml_eval_report* rep = nullptr) {
+                        bool evaluate = false, const int32_t* labels = nullptr, tnml_eval_report* rep = nullptr, StreamIO io = StreamIO()) {
     int maxbond = 1;
     TCK(streamed_refusals(c, who, nullptr, n, &maxbond));
     if (n == 0) { if (rep) memset(rep, 0, sizeof(*rep)); return 0; }
-    if (!pixels && !phi) return tnml_fail(c, "%s: null argument", who);
+    if (!pixels && !phi && !io.phi32) return tnml_fail(c, "%s: null argument", who);
     if (evaluate) {
         if (!labels || !rep) return tnml_fail(c, "%s: null argument (labels and rep are required)", who);
-        for (int64_t i = 0; i < n; ++i)
-            if (labels[i] < 0 || labels[i] >= TNML_NL) return tnml_fail(c, "%s: label %d of image %lld out of range", who, labels[i], (long long)i);
+        if (!io.dev)
+            for (int64_t i = 0; i < n; ++i)
+                if (labels[i] < 0 || labels[i] >= TNML_NL) return tnml_fail(c, "%s: label %d of image %lld out of range", who, labels[i], (long long)i);
     }
+    if (io.dev) TCK(dev_enter(c, who, io, n, pixels, phi, evaluate ? labels : nullptr, nullptr, nullptr, DevOuts{weights, pred, nullptr, nullptr, nullptr}));
     HIPCK(c, hipSetDevice(c->cfg.device));
     const bool bytes_form = pixels != nullptr, f32 = c->predict_dtype == TNML_PREDICT_F32;
-    TCK(predict_workspace(c, who, bytes_form, f32, evaluate));
+    TCK(predict_workspace(c, who, bytes_form, f32, evaluate, io.dev));
     if (evaluate) HIPCK(c, hipMemsetAsync(c->pk_acc, 0, sizeof(EvalAcc), c->stream));
     std::vector<ChainSite<double>> tab;
     TCK(upload_sites(c, c->pk, tab));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (tab leaves scope with this call)
     if (f32) TCK(predict_workspace32(c, bytes_form && c->im_set, tab));
-    TCK(f32 ? predict_chunks<float>(c, who, n, pixels, phi, labels, weights, pred, maxbond) : predict_chunks<double>(c, who, n, pixels, phi, labels, weights, pred, maxbond));
+    TCK(f32 ? predict_chunks<float>(c, who, n, pixels, phi, labels, weights, pred, maxbond, io) : predict_chunks<double>(c, who, n, pixels, phi, labels, weights, pred, maxbond, io));
     if (!evaluate) return 0;
     EvalAcc h;                                                  // the one copy of the tallies: every chunk has been added (the loop ends on a synchronisation)
     HIPCK(c, hipMemcpyAsync(&h, c->pk_acc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -391,7 +457,7 @@ int tnml_evaluate_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* 
 // Per chunk of option response_chunk ONE k_response launch walks the chain inward and outward, the result [N][2][C] is turned into
 // [C][N][2] on the device and copied back.
 // rows: the rows of a workgroup's tape slice that W asks for now
-static int response_workspace(tnml_ctx* c, const char* who, bool bytes_form, size_t rows) {
+static int response_workspace(tnml_ctx* c, const char* who, bool bytes_form, size_t rows, bool dev) {
     StreamWs& s = c->rs;
     bool fresh;
     int rc = ws_remake(c, s, c->response_chunk, response_release, &fresh);
@@ -400,20 +466,22 @@ static int response_workspace(tnml_ctx* c, const char* who, bool bytes_form, siz
         rc = ws_alloc(c, s, (void**)&c->rs_which, cap * sizeof(int));
         if (!rc) rc = ws_alloc(c, s, (void**)&c->rs_rowoff, (size_t)(c->N + 4) * sizeof(int));
         if (!rc) rc = ws_alloc(c, s, (void**)&c->rs_out, 2 * c->N * cap * sizeof(double));
-        if (!rc) rc = ws_alloc(c, s, (void**)&c->rs_outT, 2 * c->N * cap * sizeof(double));
     }
+    if (!rc && !dev && !c->rs_outT) rc = ws_alloc(c, s, (void**)&c->rs_outT, 2 * c->N * cap * sizeof(double));    // (device-resident resp: the transposition writes the caller's array)
     if (!rc) rc = ws_grow(c, s, rows, &c->rs_tape_rows, cap * sizeof(double), {&c->rs_tape});
-    if (!rc) rc = ws_staging(c, s, who, bytes_form);
+    if (!rc) rc = ws_staging(c, s, who, bytes_form, true, dev);
     if (rc) response_release(c);
     return rc;
 }
-static int response_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* which, double* resp, double* weights, int32_t* pred) {
+static int response_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* which, double* resp, double* weights, int32_t* pred,
+                         StreamIO io = StreamIO()) {
     int maxbond = 1;
     TCK(streamed_refusals(c, who, "site responses", n, &maxbond));
     if (n == 0) return 0;
-    if ((!pixels && !phi) || !resp) return tnml_fail(c, "%s: null argument", who);
+    if ((!pixels && !phi && !io.phi32) || !resp) return tnml_fail(c, "%s: null argument", who);
     const int nl = c->nl();
-    if (which)
+    if (io.dev) TCK(dev_enter(c, who, io, n, pixels, phi, nullptr, nullptr, which, DevOuts{weights, pred, resp, nullptr, nullptr}));
+    else if (which)
         for (int64_t i = 0; i < n; ++i)
             if (which[i] < 0 || which[i] >= nl) return tnml_fail(c, "%s: which = %d of image %lld out of range 0..%d", who, which[i], (long long)i, nl - 1);
     HIPCK(c, hipSetDevice(c->cfg.device));
@@ -426,7 +494,7 @@ static int response_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t*
     rowoff[N + 2] = rows; rows += ru16(c->W[cs].mr);
     rowoff[N + 3] = rows;
     const bool bytes_form = pixels != nullptr;
-    TCK(response_workspace(c, who, bytes_form, (size_t)rows));
+    TCK(response_workspace(c, who, bytes_form, (size_t)rows, io.dev));
     std::vector<ChainSite<double>> tab;
     TCK(upload_sites(c, s, tab));
     HIPCK(c, hipMemcpyAsync(c->rs_rowoff, rowoff.data(), sizeof(int) * (N + 4), hipMemcpyHostToDevice, c->stream));
@@ -439,11 +507,12 @@ static int response_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t*
     const size_t tape_elems = c->rs_tape_rows * (size_t)s.cap;
     for (int64_t off = 0; off < n; off += c->response_chunk) {
         a.ch.cnt = (int)std::min<int64_t>(c->response_chunk, n - off);
-        TCK(stage_chunk<double>(c, s, mapped, sg, pixels, phi, off, a.ch.cnt, s.xphi));
-        if (which) HIPCK(c, hipMemcpyAsync(c->rs_which, which + off, sizeof(int32_t) * (size_t)a.ch.cnt, hipMemcpyHostToDevice, c->stream));
-        TCK(launch_response(c, a, maxbond, chain_tile<double>(c, maxbond, a.ch.cnt), rows, tape_elems, c->rs_outT));
-        HIPCK(c, hipMemcpyAsync(resp + (size_t)off * N * 2, c->rs_outT, sizeof(double) * (size_t)a.ch.cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
-        TCK(chunk_results(c, s, off, a.ch.cnt, weights, pred));
+        TCK(stage_chunk<double>(c, s, mapped, sg, pixels, phi, off, a.ch.cnt, s.xphi, io));
+        chunk_dest(c, s, io, off, weights, pred, &a.ch.wout, &a.ch.pred);
+        if (which) HIPCK(c, hipMemcpyAsync(c->rs_which, which + off, sizeof(int32_t) * (size_t)a.ch.cnt, io.in(), c->stream));
+        TCK(launch_response(c, a, maxbond, chain_tile<double>(c, maxbond, a.ch.cnt), rows, tape_elems, io.dev ? resp + (size_t)off * N * 2 : c->rs_outT));
+        if (!io.dev) HIPCK(c, hipMemcpyAsync(resp + (size_t)off * N * 2, c->rs_outT, sizeof(double) * (size_t)a.ch.cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
+        TCK(chunk_results(c, s, off, a.ch.cnt, weights, pred, io.dev));
     }
     return 0;
 }
@@ -460,7 +529,7 @@ int tnml_response_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* 
 // Per chunk of option gradient_chunk ONE k_site_backward launch walks the chain inward and outward and leaves two tapes, ONE k_site_grad
 // launch adds the chunk's outer products to the gradient, which stays on the device until the last chunk and is copied back once.
 // rows: the rows of a workgroup's tape slice that W asks for now; elems: the elements of the gradient of W as it is now
-static int sitegrad_workspace(tnml_ctx* c, const char* who, bool bytes_form, size_t rows, size_t elems) {
+static int sitegrad_workspace(tnml_ctx* c, const char* who, bool bytes_form, size_t rows, size_t elems, bool dev) {
     StreamWs& s = c->sg;
     const int nl = c->nl();
     bool fresh;
@@ -475,7 +544,7 @@ static int sitegrad_workspace(tnml_ctx* c, const char* who, bool bytes_form, siz
     }
     if (!rc) rc = ws_grow(c, s, rows, &c->sg_tape_rows, cap * sizeof(double), {&c->sg_tape, &c->sg_tape2});
     if (!rc) rc = ws_grow(c, s, elems, &c->sg_grad_elems, sizeof(double), {&c->sg_grad});
-    if (!rc) rc = ws_staging(c, s, who, bytes_form);
+    if (!rc) rc = ws_staging(c, s, who, bytes_form, true, dev);
     if (rc) sitegrad_release(c);
     return rc;
 }
@@ -498,10 +567,13 @@ int tnml_site_gradient_size(tnml_ctx* c, int64_t* elems, int64_t* offsets) {
     return 0;
 }
 // what a gradient call with n > 0 asks of its arrays: images, exactly one of labels and coef, labels in range, finite coefficients
-static int sitegrad_inputs(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef) {
+// device-resident arrays: the same through dev_enter (o: the outputs of the call, for its pointer checks), once per call
+static int sitegrad_inputs(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
+                           StreamIO& io, const DevOuts& o) {
     const int nl = c->nl();
-    if (!pixels && !phi) return tnml_fail(c, "%s: null argument", who);
+    if (!pixels && !phi && !io.phi32) return tnml_fail(c, "%s: null argument", who);
     if ((labels != nullptr) == (coef != nullptr)) return tnml_fail(c, "%s: exactly one of labels and coef must be given (%s are)", who, labels ? "both" : "neither");
+    if (io.dev) return dev_enter(c, who, io, n, pixels, phi, labels, coef, nullptr, o);
     if (labels)
         for (int64_t i = 0; i < n; ++i)
             if (labels[i] < 0 || labels[i] >= TNML_NL) return tnml_fail(c, "%s: label %d of image %lld out of range", who, labels[i], (long long)i);
@@ -516,8 +588,10 @@ static int sitegrad_inputs(tnml_ctx* c, const char* who, int64_t n, const uint8_
 // block that is zeroed here and gets one k_eval_tally launch per chunk, on the chunk's weights and sg_lab.
 // tnml_backward_*: dphi (or null) receives the input gradients [n][N][2] chunk by chunk, from ONE k_input_grad launch behind the chunk's
 // k_site_backward; want_grad false leaves k_site_grad out.
+// io (device-resident arrays): grad is the caller's device array or null (it enters the pointer checks only: the sum is made in sg_grad as
+// ever); dphi or io.dphi32 receives the transposition directly.
 static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
-                           const void* out, double* weights, int32_t* pred, size_t* elems_out, EvalAcc* acc = nullptr, double* dphi = nullptr, bool want_grad = true) {
+                           const void* out, double* weights, int32_t* pred, size_t* elems_out, EvalAcc* acc, double* dphi, bool want_grad, StreamIO& io, double* grad) {
     int maxbond = 1;
     TCK(streamed_refusals(c, who, "site gradients", n, &maxbond));
     if (!out) return tnml_fail(c, "%s: null argument", who);
@@ -527,9 +601,10 @@ static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_
     const size_t elems = sitegrad_layout(c, goff.data());
     *elems_out = elems;
     if (n == 0) return 0;
-    TCK(sitegrad_inputs(c, who, n, pixels, phi, labels, coef));
+    TCK(sitegrad_inputs(c, who, n, pixels, phi, labels, coef, io, DevOuts{weights, pred, nullptr, grad, dphi}));
     HIPCK(c, hipSetDevice(c->cfg.device));
     const StreamWs& s = c->sg;
+    const bool want_dphi = dphi || io.dphi32;
     std::vector<int> rowoff(N + 2);                             // both tapes share the region table (kernels_sitegrad.hip)
     const int rows = tape_rows(c, rowoff);
     // output blocks of 32 x 32 per virtual site: the sites in order, the Label site once per label
@@ -541,10 +616,11 @@ static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_
     }
     blk0[v] = nblocks;
     const bool bytes_form = pixels != nullptr;
-    TCK(sitegrad_workspace(c, who, bytes_form, (size_t)rows, elems));
-    if (dphi && !c->bw_out) {                                   // the first call that asks for dphi: the result as the kernel leaves it and as the caller gets it
-        int rc = ws_alloc(c, c->sg, (void**)&c->bw_out, (size_t)2 * N * s.cap * sizeof(double));
-        if (!rc) rc = ws_alloc(c, c->sg, (void**)&c->bw_outT, (size_t)2 * N * s.cap * sizeof(double));
+    TCK(sitegrad_workspace(c, who, bytes_form, (size_t)rows, elems, io.dev));
+    if (want_dphi) {                                            // the first call that asks for dphi: the result as the kernel leaves it and as a host caller gets it
+        int rc = 0;
+        if (!c->bw_out) rc = ws_alloc(c, c->sg, (void**)&c->bw_out, (size_t)2 * N * s.cap * sizeof(double));
+        if (!rc && !io.dev && !c->bw_outT) rc = ws_alloc(c, c->sg, (void**)&c->bw_outT, (size_t)2 * N * s.cap * sizeof(double));
         if (rc) { sitegrad_release(c); return rc; }
     }
     std::vector<ChainSite<double>> tab;
@@ -566,28 +642,34 @@ static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_
     const size_t tape_elems = c->sg_tape_rows * (size_t)s.cap;
     for (int64_t off = 0; off < n; off += c->gradient_chunk) {
         a.ch.cnt = (int)std::min<int64_t>(c->gradient_chunk, n - off);
-        TCK(stage_chunk<double>(c, s, mapped, sg, pixels, phi, off, a.ch.cnt, s.xphi));
-        if (labels) HIPCK(c, hipMemcpyAsync(c->sg_lab, labels + off, sizeof(int32_t) * (size_t)a.ch.cnt, hipMemcpyHostToDevice, c->stream));
-        else        HIPCK(c, hipMemcpyAsync(c->sg_coef, coef + (size_t)off * nl, sizeof(double) * (size_t)a.ch.cnt * nl, hipMemcpyHostToDevice, c->stream));
+        TCK(stage_chunk<double>(c, s, mapped, sg, pixels, phi, off, a.ch.cnt, s.xphi, io));
+        chunk_dest(c, s, io, off, weights, pred, &a.ch.wout, &a.ch.pred);
+        if (labels) HIPCK(c, hipMemcpyAsync(c->sg_lab, labels + off, sizeof(int32_t) * (size_t)a.ch.cnt, io.in(), c->stream));
+        else        HIPCK(c, hipMemcpyAsync(c->sg_coef, coef + (size_t)off * nl, sizeof(double) * (size_t)a.ch.cnt * nl, io.in(), c->stream));
         const int T = chain_tile<double>(c, maxbond, a.ch.cnt);
         TCK(launch_site_gradient(c, a, maxbond, T, rows, tape_elems, nblocks, want_grad));
-        if (dphi) {
+        if (want_dphi) {
             InputGradArgs ig;
             ig.sites = s.tab; ig.N = N; ig.cs = cs; ig.nl = nl; ig.ld = s.cap; ig.cnt = a.ch.cnt;
             ig.rowoff = c->sg_rowoff; ig.tape = c->sg_tape; ig.tape2 = c->sg_tape2; ig.coef = c->sg_coef; ig.dphi = c->bw_out;
-            TCK(launch_input_grad(c, ig, maxbond, T, rows, tape_elems, c->bw_outT));
-            HIPCK(c, hipMemcpyAsync(dphi + (size_t)off * N * 2, c->bw_outT, sizeof(double) * (size_t)a.ch.cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
+            const size_t at = (size_t)off * N * 2;
+            if (io.dev) TCK(launch_input_grad(c, ig, maxbond, T, rows, tape_elems, dphi ? dphi + at : nullptr, dphi ? nullptr : io.dphi32 + at));
+            else {
+                TCK(launch_input_grad(c, ig, maxbond, T, rows, tape_elems, c->bw_outT));
+                HIPCK(c, hipMemcpyAsync(dphi + at, c->bw_outT, sizeof(double) * (size_t)a.ch.cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
+            }
         }
-        if (acc && labels) TCK(launch_eval_tally(c, s.w, s.pred, c->sg_lab, a.ch.cnt, nl, a.ch.single, c->target(), acc, c->loss, c->loss_beta));
+        if (acc && labels) TCK(launch_eval_tally(c, a.ch.wout, a.ch.pred, c->sg_lab, a.ch.cnt, nl, a.ch.single, c->target(), acc, c->loss, c->loss_beta));
         c->sg_last_cnt = a.ch.cnt;
-        TCK(chunk_results(c, s, off, a.ch.cnt, weights, pred));
+        TCK(chunk_results(c, s, off, a.ch.cnt, weights, pred, io.dev));
     }
     return 0;
 }
 static int sitegrad_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
                          double* grad, double* weights, int32_t* pred) {
     size_t elems = 0;
-    TCK(sitegrad_device(c, who, n, pixels, phi, labels, coef, grad, weights, pred, &elems));
+    StreamIO io;
+    TCK(sitegrad_device(c, who, n, pixels, phi, labels, coef, grad, weights, pred, &elems, nullptr, nullptr, true, io, nullptr));
     if (n == 0) { memset(grad, 0, elems * sizeof(double)); return 0; }
     HIPCK(c, hipMemcpyAsync(grad, c->sg_grad, elems * sizeof(double), hipMemcpyDeviceToHost, c->stream));   // the one copy of the gradient
     SYNCK(c, c->stream);
@@ -606,13 +688,23 @@ int tnml_site_gradient_phi(tnml_ctx* c, int64_t n, const double* phi, const int3
 // The gradient call's refusals, workspace, staging and k_site_backward launch; per chunk k_site_grad runs when grad is asked for and ONE
 // k_input_grad launch on the two tapes when dphi is, its result transposed on the device and copied back with the chunk.
 static int backward_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
-                         double* grad, double* dphi, double* weights, int32_t* pred) {
-    if (c && !grad && !dphi) return tnml_fail(c, "%s: grad and dphi are both NULL: the call would compute nothing", who);
+                         double* grad, double* dphi, double* weights, int32_t* pred, StreamIO io = StreamIO()) {
+    if (c && !grad && !dphi && !io.dphi32) return tnml_fail(c, "%s: grad and dphi are both NULL: the call would compute nothing", who);
     size_t elems = 0;
-    TCK(sitegrad_device(c, who, n, pixels, phi, labels, coef, grad ? (const void*)grad : (const void*)dphi, weights, pred, &elems, nullptr, dphi, grad != nullptr));
-    if (n == 0) { if (grad) memset(grad, 0, elems * sizeof(double)); return 0; }
+    const void* out = grad ? (const void*)grad : dphi ? (const void*)dphi : (const void*)io.dphi32;
+    TCK(sitegrad_device(c, who, n, pixels, phi, labels, coef, out, weights, pred, &elems, nullptr, dphi, grad != nullptr, io, io.dev ? grad : nullptr));
+    if (n == 0) {
+        if (grad && !io.dev) memset(grad, 0, elems * sizeof(double));
+        if (grad && io.dev) {                                   // (no chunk has run: the checks of the one array the call touches, made here)
+            TCK(dev_check_args(c, who, {{"grad", grad, elems * sizeof(double), 8, true}}));
+            TCK(dev_entry_wait(c, who, io.stream));
+            HIPCK(c, hipMemsetAsync(grad, 0, elems * sizeof(double), c->stream));
+            SYNCK(c, c->stream);
+        }
+        return 0;
+    }
     if (!grad) return 0;                                        // (the chunk loop ends on a synchronisation)
-    HIPCK(c, hipMemcpyAsync(grad, c->sg_grad, elems * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(grad, c->sg_grad, elems * sizeof(double), io.dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     SYNCK(c, c->stream);
     return 0;
 }
@@ -700,7 +792,7 @@ static int step_check_params(tnml_ctx* c, const char* who, const tnml_step_param
     return 0;
 }
 static int sitestep_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
-                         const tnml_step_params* p, tnml_step_report* rep) {
+                         const tnml_step_params* p, tnml_step_report* rep, StreamIO io = StreamIO()) {
     int maxbond = 1;
     TCK(streamed_refusals(c, who, "site gradients", n, &maxbond));
     TCK(ho_locked(c, who, true));                               // as tnml_set_site: W of a training context with a held-out context attached changes in bond updates only
@@ -709,11 +801,11 @@ static int sitestep_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t*
     if (n == 0) { if (rep) memset(rep, 0, sizeof(*rep)); return 0; }
     const int cs = c->single() ? 1 : c->c0;
     if (c->W[cs].L != c->nl()) return tnml_fail(c, "%s: the Label site %d of W carries %d labels, the context has %d", who, cs, c->W[cs].L, c->nl());
-    TCK(sitegrad_inputs(c, who, n, pixels, phi, labels, coef)); // (before the state is made: a refused call leaves nothing behind)
+    TCK(sitegrad_inputs(c, who, n, pixels, phi, labels, coef, io, DevOuts{})); // (before the state is made: a refused call leaves nothing behind)
     HIPCK(c, hipSetDevice(c->cfg.device));
     TCK(step_state_for(c, who, p->method));
     size_t elems = 0;
-    TCK(sitegrad_device(c, who, n, pixels, phi, labels, coef, p, nullptr, nullptr, &elems, c->st_acc));
+    TCK(sitegrad_device(c, who, n, pixels, phi, labels, coef, p, nullptr, nullptr, &elems, c->st_acc, nullptr, true, io, nullptr));
     if (elems != c->st_elems) return tnml_fail(c, "%s: the gradient has %zu elements, the optimiser state %zu (tnml_site_step_reset first)", who, elems, c->st_elems);
     SiteStepArgs a;
     a.sites = c->sg.tab; a.goff = c->sg_goff; a.wg0 = c->st_wg0; a.N = c->N;
@@ -772,4 +864,59 @@ int tnml_site_step_state(tnml_ctx* c, const char* which, double* out, int64_t co
     SYNCK(c, c->stream);
     HIPCK(c, hipMemcpy(out, src, sizeof(double) * c->st_elems, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// ---- device-resident arguments: the tnml_*_dev entry points (tnml.h) ----------
+// Each is the host-pointer call of its name on the same *_impl, with the memory space of the arrays set to the device.
+static int dev_batch_io(tnml_ctx* c, const char* who, const tnml_dev_batch* b, StreamIO* io) {
+    if (!c || !b) return tnml_fail(c, "%s: null argument", who);
+    const int given = (b->pixels != nullptr) + (b->phi != nullptr) + (b->phi32 != nullptr);
+    if (given > 1) return tnml_fail(c, "%s: exactly one of pixels, phi and phi32 must be given (%d are)", who, given);
+    if (b->n > 0 && !given) return tnml_fail(c, "%s: null argument", who);
+    io->dev = true; io->phi32 = b->phi32; io->stream = b->stream;
+    return 0;
+}
+int tnml_predict_dev(tnml_ctx* c, const tnml_dev_batch* b, const tnml_dev_out* o) {
+    StreamIO io;
+    TCK(dev_batch_io(c, "tnml_predict_dev", b, &io));
+    return predict_impl(c, "tnml_predict_dev", b->n, b->pixels, b->phi, o ? o->weights : nullptr, o ? o->pred : nullptr, false, nullptr, nullptr, io);
+}
+int tnml_evaluate_dev(tnml_ctx* c, const tnml_dev_batch* b, const tnml_dev_out* o, tnml_eval_report* rep) {
+    StreamIO io;
+    TCK(dev_batch_io(c, "tnml_evaluate_dev", b, &io));
+    return predict_impl(c, "tnml_evaluate_dev", b->n, b->pixels, b->phi, o ? o->weights : nullptr, o ? o->pred : nullptr, true, b->labels, rep, io);
+}
+int tnml_response_dev(tnml_ctx* c, const tnml_dev_batch* b, const tnml_dev_out* o) {
+    StreamIO io;
+    TCK(dev_batch_io(c, "tnml_response_dev", b, &io));
+    return response_impl(c, "tnml_response_dev", b->n, b->pixels, b->phi, b->which, o ? o->resp : nullptr, o ? o->weights : nullptr, o ? o->pred : nullptr, io);
+}
+int tnml_backward_dev(tnml_ctx* c, const tnml_dev_batch* b, const tnml_dev_out* o) {
+    StreamIO io;
+    TCK(dev_batch_io(c, "tnml_backward_dev", b, &io));
+    if (o && o->dphi && o->dphi32) return tnml_fail(c, "tnml_backward_dev: dphi and dphi32 are both given: at most one of the two");
+    io.dphi32 = o ? o->dphi32 : nullptr;
+    return backward_impl(c, "tnml_backward_dev", b->n, b->pixels, b->phi, b->labels, b->coef, o ? o->grad : nullptr, o ? o->dphi : nullptr, o ? o->weights : nullptr, o ? o->pred : nullptr, io);
+}
+int tnml_site_step_dev(tnml_ctx* c, const tnml_dev_batch* b, const tnml_step_params* p, tnml_step_report* rep) {
+    StreamIO io;
+    TCK(dev_batch_io(c, "tnml_site_step_dev", b, &io));
+    return sitestep_impl(c, "tnml_site_step_dev", b->n, b->pixels, b->phi, b->labels, b->coef, p, rep, io);
+}
+// test entry: sizeof and the field offsets, in declaration order, of the two structs of this section as this library was compiled
+int tnml_abi_layout(const char* name, int64_t* sizes_out) {
+    if (!name || !sizes_out) return -1;
+    if (!strcmp(name, "tnml_dev_batch")) {
+        const size_t v[] = {sizeof(tnml_dev_batch), offsetof(tnml_dev_batch, n), offsetof(tnml_dev_batch, pixels), offsetof(tnml_dev_batch, phi), offsetof(tnml_dev_batch, phi32),
+                            offsetof(tnml_dev_batch, labels), offsetof(tnml_dev_batch, coef), offsetof(tnml_dev_batch, which), offsetof(tnml_dev_batch, stream)};
+        for (size_t k = 0; k < sizeof(v) / sizeof(v[0]); ++k) sizes_out[k] = (int64_t)v[k];
+        return (int)(sizeof(v) / sizeof(v[0]));
+    }
+    if (!strcmp(name, "tnml_dev_out")) {
+        const size_t v[] = {sizeof(tnml_dev_out), offsetof(tnml_dev_out, weights), offsetof(tnml_dev_out, pred), offsetof(tnml_dev_out, resp), offsetof(tnml_dev_out, grad),
+                            offsetof(tnml_dev_out, dphi), offsetof(tnml_dev_out, dphi32)};
+        for (size_t k = 0; k < sizeof(v) / sizeof(v[0]); ++k) sizes_out[k] = (int64_t)v[k];
+        return (int)(sizeof(v) / sizeof(v[0]));
+    }
+    return -1;
 }

@@ -33,11 +33,11 @@
 
 enum KClass {
     KC_FGEMM_FWD = 0, KC_FGEMM_SHIFT, KC_LABELDOT, KC_ZPRIME, KC_BGEMM, KC_SLABRED, KC_PACK, KC_VEC,
-    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_EVAL_TALLY, KC_SITE_RESP, KC_SITE_BWD, KC_SITE_GRAD, KC_STEP_NORM, KC_SITE_STEP, KC_INPUT_GRAD, KC_COUNT
+    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_EVAL_TALLY, KC_SITE_RESP, KC_SITE_BWD, KC_SITE_GRAD, KC_STEP_NORM, KC_SITE_STEP, KC_INPUT_GRAD, KC_IO_CHECK, KC_COUNT
 };
 static const char* const kclass_names[KC_COUNT] = {
     "fgemm_fwd", "fgemm_shift", "labeldot", "zprime", "bgemm", "slab_reduce", "pack", "cg_vec",
-    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain", "eval_tally", "site_resp", "site_bwd", "site_grad", "step_norm", "site_step", "input_grad"};
+    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain", "eval_tally", "site_resp", "site_bwd", "site_grad", "step_norm", "site_step", "input_grad", "io_check"};
 
 // device accumulator block of tnml_evaluate_*: the part of tnml_eval_report that k_eval_tally (kernels_eval.hip) adds up
 struct EvalAcc {
@@ -371,6 +371,10 @@ struct tnml_ctx {
     EvalAcc* st_acc = nullptr;                             // the tallies of the call in progress (labels mode)
     int64_t st_t = 0; double st_p1 = 1., st_p2 = 1.;       // steps taken; Adam's running powers beta1^t, beta2^t
     int64_t st_bytes = 0;
+    // device-resident arguments (the tnml_*_dev calls): made by the first such call, released with the last of the three streamed
+    // workspaces (io_release) and by tnml_destroy
+    hipEvent_t io_ev = nullptr;                            // recorded on the caller's stream on entry; the context's stream waits for it (timing disabled)
+    unsigned long long* io_blk = nullptr;                  // [3] the block of k_check_batch (kernels_iocheck.hip): 24 bytes, counted in `bytes`
     // input map (tnml_set_input_map): geometry + host copy of the fp64 table; consulted by tnml_set_data_u8 and the *_u8 streamed calls only
     bool im_set = false;
     tnml_input_map im = {};          // geometry (table = nullptr)
@@ -623,8 +627,9 @@ struct StageGeom { int S, src_cols, block, row0, col0, out_rows, out_cols; };
 int launch_stage_codes(tnml_ctx* c, const uint8_t* raw, const StageGeom& g, int cnt, int ld, uint16_t* codes);
 // block sums codes[N][NTp] -> stored features phi[N][2][NTp] in the context's storage type through tab ([ncodes][2] of that type); padding images get (0, 0)
 int launch_codes_phi(tnml_ctx* c, const uint16_t* codes, const void* tab, int N, int NT, int NTp, void* phi);
-// exactly one of pix [cnt][N] -> xT [N][ld] / phi [cnt][N][2] -> phiT [N][2][ld], rounded once to E; class pack
-template <typename E> int launch_chain_stage(tnml_ctx* c, const uint8_t* pix, const double* phi, int N, int cnt, int ld, uint8_t* xT, E* phiT);
+// exactly one of pix [cnt][N] -> xT [N][ld] / phi [cnt][N][2] -> phiT [N][2][ld], rounded once to E / phi32 (fp32 features, widened
+// exactly) -> phiT; class pack
+template <typename E> int launch_chain_stage(tnml_ctx* c, const uint8_t* pix, const double* phi, int N, int cnt, int ld, uint8_t* xT, E* phiT, const float* phi32 = nullptr);
 // dst[j].a = fl32(src[j].a) for the N sites (tables on the device); lsite: the Label site (1-indexed, <= 0: none) carries nl times the elements;
 // largest: the element count of the largest site (sizes the grid); class pack
 int launch_chain_pack32(tnml_ctx* c, const ChainSite<double>* src, const ChainSite<float>* dst, int N, int lsite, int nl, size_t largest);
@@ -641,8 +646,9 @@ struct RespArgs {
 };
 // rows: rowoff[N + 3] as the host knows it; tape_elems: doubles behind a.tape; outT [cnt][N][2] receives the transposed a.resp; class site_resp
 int launch_response(tnml_ctx* c, RespArgs a, int maxbond, int T, int rows, size_t tape_elems, double* outT);
-// in [rows][ld] (images fastest) -> out [cnt][rows] (k_response_transpose); no ProfScope of its own
-int launch_response_transpose(tnml_ctx* c, const double* in, int rows, int cnt, int ld, double* out);
+// in [rows][ld] (images fastest) -> out [cnt][rows] (k_response_transpose); out32 (out is then null): the same, rounded once to fp32;
+// no ProfScope of its own
+int launch_response_transpose(tnml_ctx* c, const double* in, int rows, int cnt, int ld, double* out, float* out32 = nullptr);
 
 // ---- kernels_sitegrad.hip: streamed site gradients, k_site_backward (two walks, two tapes) and k_site_grad (the GEMM over the image index) ----
 struct SiteGradArgs {
@@ -674,7 +680,13 @@ struct InputGradArgs {
 };
 // T: the tile width k_site_backward ran this chunk with; rows: rowoff[N + 1] as the host knows it; outT [cnt][N][2] receives the transposed
 // a.dphi; class input_grad (the transposing copy: class pack)
-int launch_input_grad(tnml_ctx* c, InputGradArgs a, int maxbond, int T, int rows, size_t tape_elems, double* outT);
+// outT32 (outT is then null): the transposed a.dphi rounded once to fp32
+int launch_input_grad(tnml_ctx* c, InputGradArgs a, int maxbond, int T, int rows, size_t tape_elems, double* outT, float* outT32 = nullptr);
+
+// ---- kernels_iocheck.hip: the value checks of the device-resident calls ----
+// ONE launch over labels [n], coef [n][nl] and which [n] (any may be null): blk[0..2], all ones before the launch, receive the smallest
+// offending flat index of each array (integer atomicMin); class io_check
+int launch_check_batch(tnml_ctx* c, const int* labels, const double* coef, const int* which, int64_t n, int nl, unsigned long long* blk);
 
 // ---- kernels_sitestep.hip: one optimiser step on W from the gradient tnml_site_gradient_*'s kernels left on the device ----
 #define STEP_NORM_BLOCK 65536      /* elements per block sum of the norm pass */

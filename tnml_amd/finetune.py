@@ -3,7 +3,10 @@
 
 Keys of the `input` group: datadir, Ntrain, Ntest, imglen, feature_scale, input_map as tnml_amd.train reads them (the images reach the
 device in the form train.py takes for heldout = stream); infile (W) and outfile (W_ft); epochs (1), batch (256), optimizer = sgd | adam
-(adam), lr, momentum, beta1, beta2, eps, clip; loss = quadratic | softmax (softmax), loss_beta (1); seed (1); log (none).
+(adam), lr, momentum, beta1, beta2, eps, clip; loss = quadratic | softmax (softmax), loss_beta (1); seed (1); log (none);
+device_data = yes | no (no): with yes the training images and labels are uploaded once as torch tensors, every mini-batch is gathered
+on the device and every step goes through tnml_site_step_dev, so that no image crosses the bus after the upload.  The numbers of a
+run do not depend on the key; with yes one more line is printed, which says so.
 
 W is read from infile into a context that holds no data, sized by W's largest bond.  The t10k set is evaluated before the first
 epoch and after every epoch.  Epoch e (1-based) walks the permutation numpy.random.default_rng(seed + e).permutation(NT) in batches
@@ -77,6 +80,7 @@ def _run(inp):
         raise BadInput("epochs = %d, batch = %d: epochs must be >= 0 and batch >= 1" % (epochs, batch))
     try:
         use_map = hostlib.input_yesno(inp, "input_map", False)
+        device_data = hostlib.input_yesno(inp, "device_data", False)
         px, lab, _ = hostlib.read_mnist(datadir, True, Ntrain)
         tpx, tlab, _ = hostlib.read_mnist(datadir, False, Ntest)
         W = hostlib.read_mps(infile)
@@ -123,6 +127,11 @@ def _run(inp):
             e = ts.evaluate(tlab, **{form: held})
             print("Held-out: Percent correct = %.4f%%, # incorrect = %d/%d, Cost = %.10f" % (e.ncorrect * 100.0 / e.n, e.n - e.ncorrect, e.n, e.cost / e.n), flush=True)
         say_heldout()
+        if device_data:
+            import torch
+            print("device_data = yes: the training set lives on the device, batches are gathered there (tnml_site_step_dev)", flush=True)
+            dev = torch.device("cuda", ts.device)
+            train_d, lab_d = torch.from_numpy(np.ascontiguousarray(train)).to(dev), torch.from_numpy(lab).to(dev)
         if logfile:
             log = open(logfile, "w")
             log.write(LOG_HEADER + "\n")
@@ -132,7 +141,11 @@ def _run(inp):
             cost, clipped = 0.0, 0
             for at in range(0, NT, batch):
                 rows = perm[at:at + batch]
-                rep = ts.gradient_step(labels=lab[rows], scale=1.0 / len(rows), **{form: train[rows]}, **par)
+                if device_data:
+                    idx = torch.from_numpy(rows).to(dev)
+                    rep = ts.gradient_step(labels=lab_d[idx], scale=1.0 / len(rows), **{form: train_d[idx]}, **par)
+                else:
+                    rep = ts.gradient_step(labels=lab[rows], scale=1.0 / len(rows), **{form: train[rows]}, **par)
                 step += 1
                 cost += rep.eval.cost / len(rows)
                 clipped += int(rep.clipped)

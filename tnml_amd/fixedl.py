@@ -11,6 +11,7 @@ back to the CPU and nothing imports the oracle.
 import ctypes as C
 
 import numpy as np
+import torch
 
 from . import lib as _lib
 
@@ -74,6 +75,7 @@ class TrainStates:
         self.nl = 1 if self.single else NL
         self.maxm = int(maxm)
         self.rank, self.nranks = rank, nranks
+        self.device = int(device)
         self.NT_total = int(NT_total if NT_total is not None else self.NT)
         self.dtype = dtype
         cfg = _lib.Config(device, rank, nranks, self.N, self.NT, self.NT_total, self.maxm, _lib.DTYPES[dtype], int(svd_backend),
@@ -291,7 +293,16 @@ class TrainStates:
         """streamed inference on images this context does not hold (tnml_predict_u8 / tnml_predict_phi): pixels[n, N] bytes
         (under an input map: [n, S] raw bytes) or phi[n, N, 2] features -> (weights[n, nl], pred[n]); pred is argmax_l |W_l|
         (per-label variant: [f > 1/2]).  Reads W only.  dtype "f64" / "f32" sets option predict_dtype for this call and the ones
-        after it (None: leave it): "f32" runs the fp32 chain kernel, weights are its fp32 results widened."""
+        after it (None: leave it): "f32" runs the fp32 chain kernel, weights are its fp32 results widened.
+        Device tensors: here and in evaluate / site_response / site_gradient / backward / gradient_step the arrays may be torch
+        tensors on the context's device (all of a call's arrays, or none; phi float64 or float32).  The call then goes through the
+        tnml_*_dev entry point on torch's current stream, nothing crosses the bus, the results are device tensors, and every number
+        is bit for bit the host path's."""
+        if self._on_device(pixels, phi):
+            b, keep = self._dev_batch(pixels, phi, dtype=dtype)
+            w, pred, o = self._dev_weights(b.n, True)
+            self._ck(self._L.tnml_predict_dev(self._h, C.byref(b), C.byref(o)))
+            return w, pred
         x = self._streamed_input(pixels, phi, dtype)
         n = int(x.shape[0])
         w = np.zeros((n, self.nl))
@@ -302,6 +313,117 @@ class TrainStates:
         else:
             self._ck(self._L.tnml_predict_phi(self._h, n, _lib.dptr(x), _lib.dptr(w), pp))
         return w, pred
+
+    # -- device-resident arguments (the tnml_*_dev calls): torch tensors on the context's device, results as device tensors
+    def _on_device(self, *arrays):
+        """True when the array arguments of a streamed call are torch tensors on the context's device, False when none is a device
+        tensor (numpy arrays and CPU tensors: the host-pointer path); a mix, or another device, is a ValueError"""
+        given = [a for a in arrays if a is not None]
+        dev = [isinstance(a, torch.Tensor) and a.is_cuda for a in given]
+        if not any(dev):
+            return False
+        if not all(dev):
+            raise ValueError("the array arguments of one call must all be device tensors, or none of them (%d of %d are)" % (sum(dev), len(dev)))
+        for a in given:
+            if a.device.index != self.device:
+                raise ValueError("a tensor lies on device %s, the context is on device %d" % (a.device.index, self.device))
+        return True
+
+    def _dev_batch(self, pixels, phi, labels=None, coef=None, which=None, dtype=None):
+        """-> (DevBatch, the tensors it points at): every array contiguous and of the call's dtype (made so on the device), phi
+        float64 or float32, the stream torch's current one"""
+        if (pixels is None) == (phi is None):
+            raise ValueError("need exactly one of pixels or phi")
+        if dtype is not None:
+            if dtype not in _lib.PREDICT_DTYPES:
+                raise ValueError("dtype must be one of %s, got %r" % (sorted(_lib.PREDICT_DTYPES), dtype))
+            self.set_option("predict_dtype", _lib.PREDICT_DTYPES[dtype])
+        b = _lib.DevBatch()
+        if pixels is not None:
+            x = pixels.to(torch.uint8).contiguous()
+            if x.ndim != 2 or x.shape[1] != self._bytes_per_image:
+                raise ValueError("pixels must have shape [n, %d], got %s" % (self._bytes_per_image, tuple(x.shape)))
+            b.pixels = x.data_ptr()
+        else:
+            x = (phi if phi.dtype in (torch.float64, torch.float32) else phi.to(torch.float64)).contiguous()
+            if x.ndim != 3 or tuple(x.shape[1:]) != (self.N, 2):
+                raise ValueError("phi must have shape [n, %d, 2], got %s" % (self.N, tuple(x.shape)))
+            if x.dtype == torch.float32:
+                b.phi32 = x.data_ptr()
+            else:
+                b.phi = x.data_ptr()
+        n = int(x.shape[0])
+        keep = [x]
+        for name, a, dt, shape in (("labels", labels, torch.int32, (n,)), ("coef", coef, torch.float64, (n, self.nl)), ("which", which, torch.int32, (n,))):
+            if a is None:
+                continue
+            a = a.to(dt).contiguous()
+            if tuple(a.shape) != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, list(shape), tuple(a.shape)))
+            setattr(b, name, a.data_ptr())
+            keep.append(a)
+        b.n = n
+        b.stream = torch.cuda.current_stream(x.device).cuda_stream
+        return b, keep
+
+    def _dev_weights(self, n, want, out=None):
+        """-> (weights | None, pred | None, DevOut with both set when want)"""
+        o = out if out is not None else _lib.DevOut()
+        if not want:
+            return None, None, o
+        dev = torch.device("cuda", self.device)
+        w = torch.empty((n, self.nl), dtype=torch.float64, device=dev)
+        pred = torch.empty(n, dtype=torch.int32, device=dev)
+        o.weights, o.pred = w.data_ptr(), pred.data_ptr()
+        return w, pred, o
+
+    def _site_shapes(self):
+        out = []
+        for j in range(1, self.N + 1):
+            ml, mr, hl = C.c_int(), C.c_int(), C.c_int()
+            self._ck(self._L.tnml_site_dims(self._h, j, ml, mr, hl))
+            out.append((ml.value, 2, mr.value) + ((NL,) if hl.value else ()))
+        return out
+
+    @staticmethod
+    def _fstrides(shape):
+        """first-index-fastest strides (elements) of a tensor of that shape: the library's layout of a site"""
+        st, acc = [], 1
+        for d in shape:
+            st.append(acc)
+            acc *= d
+        return tuple(st)
+
+    def _split_sites_dev(self, flat):
+        """a flat device tensor in the layout of grad -> N strided views shaped like get_site()'s (no copy)"""
+        out, at = [], 0
+        for shape in self._site_shapes():
+            out.append(torch.as_strided(flat, shape, self._fstrides(shape), at))
+            at += int(np.prod(shape))
+        return out
+
+    def _backward_dev(self, labels, coef, pixels, phi, want_sites, want_inputs, want_weights):
+        b, keep = self._dev_batch(pixels, phi, labels, coef)
+        n = int(b.n)
+        dev = torch.device("cuda", self.device)
+        w, pred, o = self._dev_weights(n, want_weights)
+        grad = dphi = None
+        if want_sites:
+            elems = C.c_int64()
+            self._ck(self._L.tnml_site_gradient_size(self._h, C.byref(elems), None))
+            grad = torch.empty(max(elems.value, 1), dtype=torch.float64, device=dev)
+            o.grad = grad.data_ptr()
+        if want_inputs:
+            f32 = phi is not None and keep[0].dtype == torch.float32
+            dphi = torch.empty((n, self.N, 2), dtype=torch.float32 if f32 else torch.float64, device=dev)
+            if f32:
+                o.dphi32 = dphi.data_ptr()
+            else:
+                o.dphi = dphi.data_ptr()
+        self._ck(self._L.tnml_backward_dev(self._h, C.byref(b), C.byref(o)))
+        grads = self._split_sites_dev(grad) if want_sites else None
+        self._note_chunk(n)
+        return (grads, dphi, (w, pred)) if want_weights else (grads, dphi)
 
     def _streamed_input(self, pixels, phi, dtype):
         """the images of predict / evaluate as the C call takes them; dtype (when given) becomes option predict_dtype"""
@@ -327,6 +449,12 @@ class TrainStates:
         bit for bit those of predict().  Without it only the report leaves the device.  Reads W only.
         Under set_loss("softmax") cost and label_cost are the cross-entropy of the logits beta W_l, and ncorrect, nincorrect and
         confusion follow the signed decision (first maximum of W_l); weights and pred stay predict()'s (pred: first maximum of |W_l|)."""
+        if self._on_device(pixels, phi, labels):
+            b, keep = self._dev_batch(pixels, phi, labels, dtype=dtype)
+            w, pred, o = self._dev_weights(b.n, want_weights)
+            r = _lib.EvalReport()
+            self._ck(self._L.tnml_evaluate_dev(self._h, C.byref(b), C.byref(o), C.byref(r)))
+            return (EvalReport(r), (w, pred)) if want_weights else EvalReport(r)
         x = self._streamed_input(pixels, phi, dtype)
         n = int(x.shape[0])
         lab = np.ascontiguousarray(labels, dtype=np.int32)
@@ -352,6 +480,13 @@ class TrainStates:
         replaced by the unit vector e_s, so that the output for any replacement psi is psi @ resp[n, j].  which None: every image's
         own prediction.  With want_weights (resp, (weights[n, nl], pred[n])), both bit for bit those of predict() in fp64.  Reads W
         only; fp64 only (refused under predict_dtype = 1)."""
+        if self._on_device(pixels, phi, which):
+            b, keep = self._dev_batch(pixels, phi, which=which)
+            w, pred, o = self._dev_weights(b.n, want_weights)
+            resp = torch.empty((int(b.n), self.N, 2), dtype=torch.float64, device=torch.device("cuda", self.device))
+            o.resp = resp.data_ptr()
+            self._ck(self._L.tnml_response_dev(self._h, C.byref(b), C.byref(o)))
+            return (resp, (w, pred)) if want_weights else resp
         x = self._streamed_input(pixels, phi, None)
         n = int(x.shape[0])
         resp = np.zeros((n, self.N, 2))
@@ -380,6 +515,9 @@ class TrainStates:
         fp64 only (refused under predict_dtype = 1).
         Under set_loss("softmax") the labels mode forms c = beta (softmax(beta W) - y) on the device instead: the gradient of the
         cross-entropy evaluate() then reports.  The coef mode does not know the loss."""
+        if self._on_device(pixels, phi, labels, coef):
+            r = self._backward_dev(labels, coef, pixels, phi, True, False, want_weights)
+            return (r[0], r[2]) if want_weights else r[0]
         x = self._streamed_input(pixels, phi, None)
         n = int(x.shape[0])
         lp = cp = None
@@ -420,7 +558,11 @@ class TrainStates:
         site_gradient(): -> (grads | None, dphi | None[, (weights, pred)]).  grads (want_sites) is site_gradient()'s list, bit for
         bit; dphi[n, N, 2] (want_inputs) is the gradient with respect to the features, dphi[n, j, s] = sum_l c[n, l] dW_l(x_n)/dphi[n, j, s]
         (under an input map: the features of the N reduced sites).  Without want_sites the gradient GEMM is not launched.  At least
-        one of the two must be asked for.  Reads W only; fp64 only."""
+        one of the two must be asked for.  Reads W only; fp64 only.
+        Device tensors (every array argument a torch tensor on the context's device; tnml_backward_dev): grads are strided views
+        of one flat device buffer, dphi a device tensor in phi's dtype (float32 phi: the fp64 result rounded once)."""
+        if self._on_device(pixels, phi, labels, coef):
+            return self._backward_dev(labels, coef, pixels, phi, want_sites, want_inputs, want_weights)
         x = self._streamed_input(pixels, phi, None)
         n = int(x.shape[0])
         lp = cp = None
@@ -499,6 +641,13 @@ class TrainStates:
             raise ValueError("method must be one of %s, got %r" % (sorted(_lib.STEP_METHODS), method))
         if lr is None:
             raise ValueError("lr is required")
+        if self._on_device(pixels, phi, labels, coef):
+            b, keep = self._dev_batch(pixels, phi, labels, coef)
+            par = _lib.StepParams(_lib.STEP_METHODS[method], float(lr), float(momentum), float(beta1), float(beta2), float(eps), float(clip), float(scale))
+            r = _lib.StepReport()
+            self._ck(self._L.tnml_site_step_dev(self._h, C.byref(b), C.byref(par), C.byref(r)))
+            self._note_chunk(int(b.n))
+            return StepReport(r)
         x = self._streamed_input(pixels, phi, None)
         n = int(x.shape[0])
         lp = cp = None
@@ -559,10 +708,29 @@ class TrainStates:
             self._ck(self._L.tnml_set_site(self._h, j, A.shape[0], A.shape[2], int(A.ndim == 4), _lib.dptr(_lib.flat(A))))
 
     def set_site(self, j, A):
+        """A: a numpy array or CPU tensor (tnml_set_site), or a tensor on the context's device (tnml_set_site_dev: one
+        device-to-device copy; a tensor that is not fp64 in first-index-fastest strides is first brought into that layout on the device)"""
+        if self._on_device(A):
+            shape = tuple(A.shape)
+            if A.dtype != torch.float64 or A.stride() != self._fstrides(shape):
+                A = torch.empty_strided(shape, self._fstrides(shape), dtype=torch.float64, device=A.device).copy_(A)
+            self._ck(self._L.tnml_set_site_dev(self._h, j, shape[0], shape[2], int(len(shape) == 4), A.data_ptr(),
+                                               torch.cuda.current_stream(A.device).cuda_stream))
+            return
         A = np.asarray(A, dtype=np.float64)
         self._ck(self._L.tnml_set_site(self._h, j, A.shape[0], A.shape[2], int(A.ndim == 4), _lib.dptr(_lib.flat(A))))
 
-    def get_site(self, j):
+    def get_site(self, j, device=False):
+        """site j as a numpy array [ml, 2, mr(, 10)]; device=True: as a tensor on the context's device in first-index-fastest
+        strides, the library's layout (tnml_get_site_dev: one device-to-device copy)"""
+        if device:
+            ml, mr, hl = C.c_int(), C.c_int(), C.c_int()
+            self._ck(self._L.tnml_site_dims(self._h, j, ml, mr, hl))
+            shape = (ml.value, 2, mr.value) + ((NL,) if hl.value else ())
+            dev = torch.device("cuda", self.device)
+            A = torch.empty_strided(shape, self._fstrides(shape), dtype=torch.float64, device=dev)
+            self._ck(self._L.tnml_get_site_dev(self._h, j, A.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            return A
         ml, mr, hl = C.c_int(), C.c_int(), C.c_int()
         self._ck(self._L.tnml_site_dims(self._h, j, ml, mr, hl))
         shape = (ml.value, 2, mr.value) + ((NL,) if hl.value else ())
@@ -570,8 +738,8 @@ class TrainStates:
         self._ck(self._L.tnml_get_site(self._h, j, _lib.dptr(buf)))
         return buf.reshape(shape, order="F")
 
-    def get_mps(self):
-        return [self.get_site(j) for j in range(1, self.N + 1)]
+    def get_mps(self, device=False):
+        return [self.get_site(j, device) for j in range(1, self.N + 1)]
 
     # -- MPS algebra: the W0..W9 start (fixedL.cc:682-701,729)
     def place(self, j, ML, MR, row0, col0, A, label=-1):

@@ -43,6 +43,8 @@ EXPORTS = [
     "tnml_site_step_u8", "tnml_site_step_phi", "tnml_site_step_reset", "tnml_site_step_state",
     "tnml_site_gradient_coef",
     "tnml_backward_u8", "tnml_backward_phi",
+    "tnml_predict_dev", "tnml_evaluate_dev", "tnml_response_dev", "tnml_backward_dev", "tnml_site_step_dev",
+    "tnml_set_site_dev", "tnml_get_site_dev", "tnml_abi_layout",
 ]
 
 
@@ -101,6 +103,18 @@ class CompressReport(C.Structure):
 class InputMapStruct(C.Structure):
     _fields_ = [("src_rows", C.c_int), ("src_cols", C.c_int), ("block", C.c_int), ("row0", C.c_int), ("col0", C.c_int),
                 ("out_rows", C.c_int), ("out_cols", C.c_int), ("ncodes", C.c_int), ("table", C.POINTER(C.c_double))]
+
+
+class DevBatch(C.Structure):
+    """tnml_dev_batch: the arrays of a device-resident call (device addresses; 0 / None: not given)"""
+    _fields_ = [("n", C.c_int64), ("pixels", C.c_void_p), ("phi", C.c_void_p), ("phi32", C.c_void_p), ("labels", C.c_void_p),
+                ("coef", C.c_void_p), ("which", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class DevOut(C.Structure):
+    """tnml_dev_out: where a device-resident call leaves its results (device addresses)"""
+    _fields_ = [("weights", C.c_void_p), ("pred", C.c_void_p), ("resp", C.c_void_p), ("grad", C.c_void_p), ("dphi", C.c_void_p),
+                ("dphi32", C.c_void_p)]
 
 
 _lib = None
@@ -178,6 +192,14 @@ def load():
     L.tnml_site_gradient_coef.argtypes = [vp, dp, C.c_int64]
     L.tnml_backward_u8.argtypes = [vp, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), dp, dp, dp, dp, C.POINTER(C.c_int32)]
     L.tnml_backward_phi.argtypes = [vp, C.c_int64, dp, C.POINTER(C.c_int32), dp, dp, dp, dp, C.POINTER(C.c_int32)]
+    L.tnml_predict_dev.argtypes = [vp, C.POINTER(DevBatch), C.POINTER(DevOut)]
+    L.tnml_evaluate_dev.argtypes = [vp, C.POINTER(DevBatch), C.POINTER(DevOut), C.POINTER(EvalReport)]
+    L.tnml_response_dev.argtypes = [vp, C.POINTER(DevBatch), C.POINTER(DevOut)]
+    L.tnml_backward_dev.argtypes = [vp, C.POINTER(DevBatch), C.POINTER(DevOut)]
+    L.tnml_site_step_dev.argtypes = [vp, C.POINTER(DevBatch), C.POINTER(StepParams), C.POINTER(StepReport)]
+    L.tnml_set_site_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.tnml_get_site_dev.argtypes = [vp, C.c_int, vp, vp]
+    L.tnml_abi_layout.argtypes = [C.c_char_p, C.POINTER(C.c_int64)]
     L.tnml_set_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_get_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_replica_check.argtypes = [vp, ip]

@@ -5,11 +5,15 @@ forward:  phi[n, N, 2] fp64 -> weights[n, nl], through TrainStates.predict();
 backward: ONE TrainStates.backward(coef=grad_output, ..) call (tnml_backward_phi): the gradient for phi and, when the layer was made
           with train_sites=True, one gradient per site tensor.
 
-Tensors cross the bus through host pointers, as every streamed call does: phi, grad_output and the site tensors are CPU tensors (or
-are brought to the CPU here), the library stages them chunk by chunk and copies the results back.  Device-resident torch tensors
-are not served.  W lives in the context; `layer.sites` mirrors it as fp64 CPU parameters shaped like get_site()'s, and a site whose
-tensor has changed since its last upload (an optimiser step, a load_state_dict) is uploaded again with set_site() before the next
-forward.
+Two paths, chosen by where phi lives.  A CPU phi (fp64) goes through host pointers, as the streamed calls always have: the library
+stages it chunk by chunk and copies the results back.  A phi on the context's device (fp64 or fp32) goes through the device-resident
+calls (tnml_predict_dev / tnml_backward_dev, include/tnml.h): the kernels read the tensor where it lies and write weights, the
+gradient for phi (in phi's dtype) and the site gradients into device tensors; nothing is brought to the CPU and torch's stream is
+not synchronised by the host on the way in (the library's stream waits for it through an event).
+W lives in the context; `layer.sites` mirrors it as fp64 parameters shaped like get_site()'s -- CPU tensors, or with
+MPSLayer(.., device=...) device tensors in the library's first-index-fastest layout -- and a site whose tensor has changed since its
+last upload (an optimiser step, a load_state_dict) is uploaded again before the next forward: set_site() from the host, one
+device-to-device copy (tnml_set_site_dev) from the device.
 
 The two directions on numpy arrays, forward_arrays() and backward_arrays(), are plain functions of a TrainStates: the autograd
 function only converts tensors and calls them."""
@@ -32,10 +36,22 @@ def backward_arrays(ts, phi, grad_output, want_sites, want_inputs=True):
 
 class MPSFunction(torch.autograd.Function):
     """apply(ts, phi, *sites): sites are the layer's parameters (or none).  They enter only so that autograd asks for their
-    gradients; the numbers are those of W in the context ts, which the caller keeps equal to them (MPSLayer does)."""
+    gradients; the numbers are those of W in the context ts, which the caller keeps equal to them (MPSLayer does).
+    The device path is taken when phi lies on the context's device and every site passed does too (none passed: phi alone decides),
+    so that every gradient comes back on the device of the tensor it belongs to.  Anything else -- a CPU phi, CPU parameters under
+    a CUDA phi, a phi on another GPU -- takes the host path: phi goes through the CPU and each gradient returns to its tensor's
+    device."""
 
     @staticmethod
     def forward(ctx, ts, phi, *sites):
+        ctx.site_devices = [s.device for s in sites]
+        ctx.on_device = phi.is_cuda and phi.device.index == ts.device and all(s.is_cuda and s.device == phi.device for s in sites)
+        if ctx.on_device:
+            if phi.dtype not in (torch.float64, torch.float32):
+                raise TypeError("MPSFunction: phi must be float64 or float32 on the device, got %s" % phi.dtype)
+            x = phi.detach().contiguous()
+            ctx.ts, ctx.x, ctx.nsites, ctx.device = ts, x, len(sites), phi.device
+            return ts.predict(phi=x)[0]
         if phi.dtype != torch.float64:
             raise TypeError("MPSFunction: phi must be float64, got %s" % phi.dtype)
         x = phi.detach().cpu().contiguous().numpy()
@@ -48,26 +64,45 @@ class MPSFunction(torch.autograd.Function):
         need_sites = ctx.nsites > 0 and any(ctx.needs_input_grad[2:])
         if not (need_phi or need_sites):
             return (None, None) + (None,) * ctx.nsites
+        if ctx.on_device:                                   # one tnml_backward_dev call, every result a device tensor
+            grads, gphi = ctx.ts.backward(coef=grad_output.detach().to(torch.float64), phi=ctx.x, want_sites=need_sites, want_inputs=need_phi)
+            gs = (None,) * ctx.nsites
+            if need_sites:
+                gs = tuple(g if ctx.needs_input_grad[2 + k] else None for k, g in enumerate(grads))
+            return (None, gphi) + gs
         go = grad_output.detach().cpu().contiguous().numpy()
         dphi, grads = backward_arrays(ctx.ts, ctx.x, go, need_sites, need_phi)
         gphi = torch.from_numpy(dphi).to(ctx.device) if need_phi else None
         gs = (None,) * ctx.nsites
         if need_sites:
-            gs = tuple(torch.from_numpy(np.ascontiguousarray(g)) if ctx.needs_input_grad[2 + k] else None for k, g in enumerate(grads))
+            gs = tuple(torch.from_numpy(np.ascontiguousarray(g)).to(ctx.site_devices[k]) if ctx.needs_input_grad[2 + k] else None for k, g in enumerate(grads))
         return (None, gphi) + gs
 
 
 class MPSLayer(torch.nn.Module):
-    """phi[n, N, 2] -> weights[n, nl] of the MPS the context ts holds.  train_sites=True: `sites`, a ParameterList of fp64 CPU
+    """phi[n, N, 2] -> weights[n, nl] of the MPS the context ts holds.  train_sites=True: `sites`, a ParameterList of fp64
     tensors shaped like get_site()'s, receives gradients and any torch optimiser can step it; False: W is fixed and only phi
-    is differentiated."""
+    is differentiated.
+    device None (or a CPU device): the sites are CPU tensors, as ever; phi may be a CPU tensor or, when the layer sits between GPU
+    modules, a CUDA tensor, which then goes through the CPU while the gradient for phi returns to phi's device.  A CUDA device (the context's): the sites are
+    device parameters in the library's layout (first-index-fastest strides, filled by tnml_get_site_dev), phi is a tensor on that
+    device, the optimiser steps on the device and sync_sites() uploads device to device.
+    The place of the parameters is fixed when the layer is made: layer.to(...) / .cuda() / .cpu() between host and device is not
+    supported (it would drop the strides the library reads); make a new layer instead."""
 
-    def __init__(self, ts, train_sites=False):
+    def __init__(self, ts, train_sites=False, device=None):
         super().__init__()
         self.ts = ts
         self.train_sites = bool(train_sites)
-        self.sites = torch.nn.ParameterList(
-            [torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(ts.get_site(j))), requires_grad=self.train_sites) for j in range(1, ts.N + 1)])
+        dev = torch.device(device) if device is not None else None
+        self.on_device = dev is not None and dev.type == "cuda"
+        if self.on_device:
+            if dev.index is not None and dev.index != ts.device:
+                raise ValueError("MPSLayer: device %s, the context is on device %d" % (dev, ts.device))
+            tensors = ts.get_mps(device=True)
+        else:
+            tensors = [torch.from_numpy(np.ascontiguousarray(ts.get_site(j))) for j in range(1, ts.N + 1)]
+        self.sites = torch.nn.ParameterList([torch.nn.Parameter(t, requires_grad=self.train_sites) for t in tensors])
         self._uploaded = [p._version for p in self.sites]
 
     def sync_sites(self):
@@ -75,7 +110,7 @@ class MPSLayer(torch.nn.Module):
         done = []
         for k, p in enumerate(self.sites):
             if p._version != self._uploaded[k]:
-                self.ts.set_site(k + 1, p.detach().numpy())
+                self.ts.set_site(k + 1, p.detach() if self.on_device else p.detach().numpy())
                 self._uploaded[k] = p._version
                 done.append(k + 1)
         return done
