@@ -36,6 +36,7 @@ extern "C" {
 #define TNML_MAX_PASS 64
 enum { TNML_LOSS_QUADRATIC = 0, TNML_LOSS_SOFTMAX = 1 };   /* option "loss": the loss of tnml_evaluate_* and of the labels mode of tnml_site_gradient_* / tnml_site_step_* */
 enum { TNML_PREDICT_F64 = 0, TNML_PREDICT_F32 = 1 };   /* option "predict_dtype": arithmetic of tnml_predict_u8 / tnml_predict_phi */
+enum { TNML_GRADIENT_F64 = 0, TNML_GRADIENT_F32 = 1 }; /* option "gradient_dtype": arithmetic of tnml_site_gradient_* / tnml_backward_* / tnml_site_step_* */
 #define TNML_PREDICT_CHUNK_DEFAULT 8192   /* option "predict_chunk": images per chunk of tnml_predict_u8 / tnml_predict_phi */
 
 typedef struct tnml_ctx tnml_ctx;
@@ -470,7 +471,28 @@ int tnml_response_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/,
  * dC/dA of the cost tnml_evaluate_* reports under the same option.  The coef mode, weights, pred, both walks, the GEMM, its order,
  * the workspace and every refusal are untouched; a weight that is not finite makes the image's coefficients NaN.
  * tnml_site_gradient_coef is a test entry like tnml_cg_state: the coefficients [cnt][nl] of the LAST chunk of the last gradient or
- * step call, as given or as formed; count must be cnt nl; refused before any such call since the workspace was made. */
+ * step call, as given or as formed; count must be cnt nl; refused before any such call since the workspace was made.
+ * Option "gradient_dtype" = TNML_GRADIENT_F32 runs tnml_site_gradient_*, tnml_backward_*, tnml_site_step_* and their _dev forms in fp32
+ * (the float instantiations of k_site_backward, k_site_grad and k_input_grad: v_mfma_f32_16x16x4_f32, tiles of 64 images up to bond 256,
+ * 32 up to 512, 16 up to 1 024) and nothing else; it is independent of "predict_dtype", under which = 1 these calls stay refused.
+ * Bonds up to 1 024 are served (above: refused in tnml_predict_*'s words under predict_dtype = 1).  W is rounded to fp32 once per call,
+ * features are formed in fp64 and rounded once, given coefficients are rounded once.  The inward pass is the fp32 chain kernel's:
+ * weights and pred are bit for bit those of tnml_predict_* under predict_dtype = 1.  In the labels mode c is formed in fp64 from the
+ * widened weights by the expressions above and rounded once; tnml_site_gradient_coef returns the rounded values.  Seeds, outward walk
+ * and both tapes are fp32.  k_site_grad<float> sums a chunk's images in fp32 from zero and adds the chunk's sum to the fp64 gradient
+ * with one fp64 addition per element, so chunk sums add up in fp64 and grad, the norm pass and the optimiser read fp64 as before: a step
+ * is mixed precision (fp32 gradient, fp64 master W and state).  dphi receives fp32 values widened exactly (dphi32 of tnml_dev_out: no
+ * second rounding).  Order and independence properties are those of the fp64 path (DESIGN.md "Streamed gradients in fp32").
+ * A weight that is not finite fails the call with a message that names gradient_dtype: nothing of that chunk or a later one reaches
+ * weights, pred or dphi, grad stays untouched, a step applies nothing, the context stays usable.
+ * Workspace under gradient_dtype = 1, with W32 = the sum over the sites of their elements rounded up to a multiple of 4:
+ *             the first line and 8 E as above
+ *           + 8 B C                                       bytes of the two tapes (floats: half)
+ *           + 4 W32 + 16 N + 4                            bytes: the fp32 copy of W (grown when W has grown), its site table, the range flag
+ *           + 2 N C  /  S C + 2 N C + 16 ncodes + 8 ncodes  /  16 N C + 8 N C   bytes of staging (bytes / input map with its table in fp64
+ *                                                         and fp32 / features as given and site-first in fp32).
+ * A change of the option frees the two tapes and makes them again in the new element size; what the other value allocated (the fp32
+ * copy and table, the site-first features of either type) stays until the workspace is released; the optimiser state is not touched. */
 #define TNML_GRADIENT_CHUNK_DEFAULT 512    /* option "gradient_chunk" */
 int tnml_site_gradient_size(tnml_ctx* ctx, int64_t* elems, int64_t* offsets /*[N+1] or NULL*/);
 int tnml_site_gradient_u8 (tnml_ctx* ctx, int64_t n, const uint8_t* pixels, const int32_t* labels /*[n] or NULL*/, const double* coef /*[n][nl] or NULL*/,
@@ -750,6 +772,9 @@ int tnml_synchronize(tnml_ctx* ctx);
      "loss"           the loss of tnml_evaluate_* and of the labels mode of tnml_site_gradient_* / tnml_site_step_*: 0 (TNML_LOSS_QUADRATIC, default)
                       sum (W_l - y_l)^2; 1 (TNML_LOSS_SOFTMAX) softmax cross-entropy on the logits loss_beta W_l, refused in TNML_MODE_SINGLE; any other value is refused
      "gradient_chunk" images per trip of the host loop of tnml_site_gradient_* = per launch of k_site_backward and k_site_grad (1..2^20, default 512); sizes its workspace
+     "gradient_dtype" arithmetic of tnml_site_gradient_* / tnml_backward_* / tnml_site_step_* and their _dev forms: 0 (TNML_GRADIENT_F64, default) fp64 on the
+                      master W, bonds up to 512; 1 (TNML_GRADIENT_F32) the fp32 gradient kernels on an fp32 copy of W made per call, bonds up to 1 024, tapes of
+                      half the bytes; any other value is refused.  No environment variable; independent of "predict_dtype"
      "env_budget_mb"  cap on the environment slabs held on the device, the rest spills to host memory (0: none)
      "env_async"      the host tier's copies beside the compute stream (default 1)
      "comm_timeout_s" how long a rank of an in-process or one-shot communicator waits for its peers (>= 1, default 120)

@@ -1,5 +1,7 @@
 // chain_common.h -- what the chain kernels share: k_chain (kernels_chain.hip, streamed inference), k_response (kernels_response.hip,
-// streamed site responses) and k_site_backward / k_site_grad (kernels_sitegrad.hip, streamed site gradients).
+// streamed site responses) and k_site_backward / k_site_grad (kernels_sitegrad.hip, streamed site gradients).  Everything here is written
+// once over the element type E: double, and float for k_chain<float> (option predict_dtype = 1) and the gradient kernels under option
+// gradient_dtype = 1.
 //   * All of them: the element-type traits ChainT<E>, the features of a site (chain_features), the A fragment of a 16-wide k block
 //     (chain_load_a) and one site of a chain (chain_step); the fragment maps, the k blocks and the arithmetic order are described in the
 //     header of kernels_chain.hip.
@@ -29,6 +31,12 @@ template <> struct ChainT<double> {
     }
     // C/D map of the fp64 MFMA: column = lane & 15, row = (lane >> 4) + 4 reg
     static __device__ __forceinline__ int row(int rt, int q, int r) { return rt * 16 + q + 4 * r; }
+    static __device__ __forceinline__ int rowq(int q, int r) { return q + 4 * r; }                 // the same inside a 16-row tile
+    // the swizzle taken apart, for code that walks a stored row: idx(k, n) = prow(k) * 16 NCT + pc with n = lcol(k, pc); rows 0 .. rows-1
+    // lie in the first span(rows) stored rows
+    template <int NCT> static __device__ __forceinline__ int prow(int k) { return k; }
+    template <int NCT> static __device__ __forceinline__ int lcol(int k, int pc) { return NCT > 1 ? (pc ^ ((k & 1) << 4)) : pc; }
+    template <int NCT> static __device__ __forceinline__ int span(int rows) { return rows; }
     static __device__ __forceinline__ v4 mfma(double a, double b, v4 acc) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0); }
     static __device__ __forceinline__ double fma(double a, double b, double c) { return ::fma(a, b, c); }
     static __device__ __forceinline__ double abs(double w) { return fabs(w); }
@@ -57,6 +65,11 @@ template <> struct ChainT<float> {
     }
     // C/D map of the f32 MFMA: column = lane & 15, row = 4 (lane >> 4) + reg -- not the fp64 form's (lane >> 4) + 4 reg
     static __device__ __forceinline__ int row(int rt, int q, int r) { return rt * 16 + 4 * q + r; }
+    static __device__ __forceinline__ int rowq(int q, int r) { return 4 * q + r; }
+    // the swizzle taken apart (see ChainT<double>): T = 16 permutes rows inside aligned groups of 8, so rows 0 .. rows-1 span ru8(rows) stored rows
+    template <int NCT> static __device__ __forceinline__ int prow(int k) { return NCT > 1 ? k : ((k & ~3) | ((k & 1) << 1) | (((k >> 1) ^ (k >> 2)) & 1)); }
+    template <int NCT> static __device__ __forceinline__ int lcol(int k, int pc) { return NCT > 1 ? (pc ^ ((((k >> 1) ^ (k >> 2)) & 1) << 4)) : pc; }
+    template <int NCT> static __device__ __forceinline__ int span(int rows) { return NCT > 1 ? rows : ((rows + 7) & ~7); }
     static __device__ __forceinline__ v4 mfma(float a, float b, v4 acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
     static __device__ __forceinline__ float fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
     static __device__ __forceinline__ float abs(float w) { return __builtin_fabsf(w); }
@@ -153,33 +166,37 @@ static __device__ __forceinline__ void chain_step(const E* __restrict__ A, int m
 }
 
 // ---- the taped walk: what k_response and k_site_backward share ----
-// A workgroup's slice of a tape: one region of ru16(bond) x T doubles per bond b = 0..N (between sites b and b + 1; b = 0 and b = N: the 1
-// that starts a chain), in the LDS tile's own element order ChainT<double>::idx<NCT>, region b at row rowoff[b].  The inward tape holds L_b
+// A workgroup's slice of a tape: one region of ru16(bond) x T elements per bond b = 0..N (between sites b and b + 1; b = 0 and b = N: the 1
+// that starts a chain), in the LDS tile's own element order ChainT<E>::idx<NCT>, region b at row rowoff[b].  The inward tape holds L_b
 // for b < cs and R_{b+1} for b >= cs.  A slice is written and read by its own workgroup (and by the launch behind it).
-template <int T> struct ChainTape {
-    double* tp; const int* rowoff;
-    __device__ __forceinline__ double* bond(int b) const { return tp + (size_t)rowoff[b] * T; }
+// E = double: k_response and the fp64 gradient kernels; E = float: the gradient kernels under option gradient_dtype = 1, whose tapes
+// hold floats in ChainT<float>'s order (T >= 32: the bank function g in address bit 4; T = 16: rows permuted inside groups of 8).
+template <typename E, int T> struct ChainTape {
+    E* tp; const int* rowoff;
+    __device__ __forceinline__ E* bond(int b) const { return tp + (size_t)rowoff[b] * T; }
 };
-template <int T>
-static __device__ __forceinline__ void chain_copy_rows(const double* src, double* dst, int rows, int tid) {
-    for (int i = tid; i < rows * T; i += CHAIN_THREADS) dst[i] = src[i];
+// rows 0 .. rows-1 of a tile or region, as stored: the first ChainT<E>::span(rows) physical rows (what lies beyond row rows-1 in them is never read)
+template <typename E, int T>
+static __device__ __forceinline__ void chain_copy_rows(const E* src, E* dst, int rows, int tid) {
+    const int n = ChainT<E>::template span<T / 16>(rows) * T;
+    for (int i = tid; i < n; i += CHAIN_THREADS) dst[i] = src[i];
 }
 
-// The inward walk of k_chain<double>, call for call and in its order -- right chain N -> cs+1, whose last vector R_{cs+1} is parked on bond
+// The inward walk of k_chain<E>, call for call and in its order -- right chain N -> cs+1, whose last vector R_{cs+1} is parked on bond
 // cs of the tape, then left chain 1 -> cs-1 -- with every chain vector also copied to the tape (R_j on bond j-1, L_j on bond j).  On return
 // buf[cur] holds L_{cs-1}, p0 / p1 the features of the centre site, and every thread has passed the last barrier.
-template <int NCT, int SRC>
-static __device__ __forceinline__ int chain_walk_taped(const ChainArgs<double>& ch, double* const (&buf)[2], const ChainTape<16 * NCT>& tape,
-                                                       double (&p0)[NCT], double (&p1)[NCT], int tile0, int tid) {
-    typedef ChainT<double> Tr;
+template <typename E, int NCT, int SRC>
+static __device__ __forceinline__ int chain_walk_taped(const ChainArgs<E>& ch, E* const (&buf)[2], const ChainTape<E, 16 * NCT>& tape,
+                                                       E (&p0)[NCT], E (&p1)[NCT], int tile0, int tid) {
+    typedef ChainT<E> Tr;
     constexpr int T = 16 * NCT;
     const int lane = tid & 63, wave = tid >> 6;
     const int N = ch.N, cs = ch.cs, nright = N - cs;
     auto site_at = [&](int t) { return t < nright ? N - t : (t < N - 1 ? t - nright + 1 : cs); };
-    double q0[NCT], q1[NCT];
+    E q0[NCT], q1[NCT];
     const int img0 = tile0 + (lane & 15);
-    chain_features<double, NCT, SRC>(ch, site_at(0), img0, p0, p1);
-    double* const park = tape.bond(cs);                                // R_{cs+1}
+    chain_features<E, NCT, SRC>(ch, site_at(0), img0, p0, p1);
+    E* const park = tape.bond(cs);                                     // R_{cs+1}
     if (tid < T) {
         const int at = Tr::template idx<NCT>(0, tid);
         buf[0][at] = 1; tape.bond(N)[at] = 1; tape.bond(0)[at] = 1;
@@ -188,54 +205,55 @@ static __device__ __forceinline__ int chain_walk_taped(const ChainArgs<double>& 
     int cur = 0;
     for (int t = 0; t < N - 1; ++t) {
         const int j = site_at(t);
-        chain_features<double, NCT, SRC>(ch, site_at(t + 1), img0, q0, q1);
-        const ChainSite<double> st = ch.sites[j - 1];
+        chain_features<E, NCT, SRC>(ch, site_at(t + 1), img0, q0, q1);
+        const ChainSite<E> st = ch.sites[j - 1];
         const bool right = t < nright, last = t == nright - 1;
         if (right) {
-            chain_step<double, NCT, false>(st.a, st.ml, st.mr, buf[cur], last ? park : buf[cur ^ 1], p0, p1, wave, lane);
+            chain_step<E, NCT, false>(st.a, st.ml, st.mr, buf[cur], last ? park : buf[cur ^ 1], p0, p1, wave, lane);
             if (last) { if (tid < T) buf[cur ^ 1][Tr::template idx<NCT>(0, tid)] = 1; }        // the left chain starts from 1
         } else {
-            chain_step<double, NCT, true>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
+            chain_step<E, NCT, true>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
         }
         cur ^= 1;
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) { p0[ct] = q0[ct]; p1[ct] = q1[ct]; }
         __syncthreads();
-        if (!last) chain_copy_rows<T>(buf[cur], right ? tape.bond(j - 1) : tape.bond(j), right ? st.ml : st.mr, tid);
+        if (!last) chain_copy_rows<E, T>(buf[cur], right ? tape.bond(j - 1) : tape.bond(j), right ? st.ml : st.mr, tid);
     }
     return cur;
 }
 
-// The centre site as k_chain<double> has it: per label l ascending one left-chain step into buf[cur ^ 1] and, by thread tid < T for image
-// tile0 + tid, the dot with R (park) over r ascending, w = fma(T[r], R[r], w) from 0 -> wout; pred = the first maximum of |W_l|
-// (util.h:42-57; per-label variant [W_0 > 1/2]) -> pred.  weights and pred are therefore bit for bit those of k_chain<double>.
+// The centre site as k_chain<E> has it: per label l ascending one left-chain step into buf[cur ^ 1] and, by thread tid < T for image
+// tile0 + tid, the dot with R (park) over r ascending, w = fma(T[r], R[r], w) from 0 -> wout (fp32: widened); pred = the first maximum of
+// |W_l| (util.h:42-57; per-label variant [W_0 > 1/2]), decided on the values of type E -> pred.  weights and pred are therefore bit for
+// bit those of k_chain<E>.
 // hook(l, w, tid, img) runs in the threads tid < T between the two barriers of label l (w = 0 for an image beyond the chunk).
 // Returns pred of the thread's image (threads tid < T inside the chunk).
-template <int NCT, typename Hook>
-static __device__ __forceinline__ int chain_centre_taped(const ChainArgs<double>& ch, double* const (&buf)[2], int cur, const double* park,
-                                                         const double (&p0)[NCT], const double (&p1)[NCT], int tile0, int tid, Hook hook) {
-    typedef ChainT<double> Tr;
+template <typename E, int NCT, typename Hook>
+static __device__ __forceinline__ int chain_centre_taped(const ChainArgs<E>& ch, E* const (&buf)[2], int cur, const E* park,
+                                                         const E (&p0)[NCT], const E (&p1)[NCT], int tile0, int tid, Hook hook) {
+    typedef ChainT<E> Tr;
     constexpr int T = 16 * NCT;
-    const ChainSite<double> sc = ch.sites[ch.cs - 1];
+    const ChainSite<E> sc = ch.sites[ch.cs - 1];
     const size_t lstride = (size_t)sc.ml * 2 * sc.mr;
     const int img = tile0 + tid;
-    double best = 0, w0 = 0; int arg = 0;
+    E best = 0, w0 = 0; int arg = 0;
     for (int l = 0; l < ch.nl; ++l) {
-        chain_step<double, NCT, true>(sc.a + l * lstride, sc.ml, sc.mr, buf[cur], buf[cur ^ 1], p0, p1, tid >> 6, tid & 63);
+        chain_step<E, NCT, true>(sc.a + l * lstride, sc.ml, sc.mr, buf[cur], buf[cur ^ 1], p0, p1, tid >> 6, tid & 63);
         __syncthreads();
         if (tid < T) {
-            double w = 0;
+            E w = 0;
             if (img < ch.cnt) {
                 for (int r = 0; r < sc.mr; ++r) w = Tr::fma(buf[cur ^ 1][Tr::template idx<NCT>(r, tid)], park[Tr::template idx<NCT>(r, tid)], w);
                 ch.wout[(size_t)img * ch.nl + l] = w;
-                const double wa = Tr::abs(w);
+                const E wa = Tr::abs(w);
                 if (l == 0) { best = wa; w0 = w; } else if (wa > best) { best = wa; arg = l; }
             }
             hook(l, w, tid, img);
         }
         __syncthreads();
     }
-    const int pr = ch.single ? (w0 > 0.5 ? 1 : 0) : arg;
+    const int pr = ch.single ? (w0 > (E)0.5 ? 1 : 0) : arg;
     if (tid < T && img < ch.cnt) ch.pred[img] = pr;
     return pr;
 }
@@ -243,18 +261,19 @@ static __device__ __forceinline__ int chain_centre_taped(const ChainArgs<double>
 // The host side of a launch of k_response / k_site_backward (name and tape_word in the messages): the argument checks, ch.mcap, the grid and
 // the dynamic LDS (two tiles + lds_extra bytes), and once per context the LDS attribute of the three tile widths kern[input map][T / 32]
 struct TapedLaunch { int grid; size_t lds; bool codes; };
-template <typename K>
-static inline int taped_launch(tnml_ctx* c, const char* name, const char* tape_word, ChainArgs<double>& ch, int maxbond, int T, int rows, size_t tape_elems,
+template <typename E, typename K>
+static inline int taped_launch(tnml_ctx* c, const char* name, const char* tape_word, ChainArgs<E>& ch, int maxbond, int T, int rows, size_t tape_elems,
                                size_t lds_extra, const K (&kern)[2][3], bool (&attr)[2], TapedLaunch* o) {
-    if (maxbond < 1 || maxbond > TNML_CHAIN_MAXM) return tnml_fail(c, "%s: bond dimension %d outside 1..%d", name, maxbond, TNML_CHAIN_MAXM);
+    typedef ChainT<E> Tr;
+    if (maxbond < 1 || maxbond > Tr::MAXM) return tnml_fail(c, "%s: bond dimension %d outside 1..%d", name, maxbond, Tr::MAXM);
     if (ch.cnt < 1 || ch.cnt > ch.ld) return tnml_fail(c, "%s: %d images in a chunk of %d", name, ch.cnt, ch.ld);
     if (T != 64 && T != 32 && T != 16) return tnml_fail(c, "%s: tile width %d", name, T);
     ch.mcap = (maxbond + 15) / 16 * 16;
     ch.park = nullptr;
     o->grid = (ch.cnt + T - 1) / T;
-    o->lds = (size_t)2 * ch.mcap * T * sizeof(double) + lds_extra;
+    o->lds = (size_t)2 * ch.mcap * T * sizeof(E) + lds_extra;
     if (o->lds > TNML_CHAIN_LDS) return tnml_fail(c, "%s: two tiles of %d x %d do not fit the LDS", name, ch.mcap, T);
-    if ((size_t)o->grid * T * rows > tape_elems) return tnml_fail(c, "%s: %s of %zu doubles too small for %d tiles of %d x %d", name, tape_word, tape_elems, o->grid, rows, T);
+    if ((size_t)o->grid * T * rows > tape_elems) return tnml_fail(c, "%s: %s of %zu %s too small for %d tiles of %d x %d", name, tape_word, tape_elems, Tr::elems, o->grid, rows, T);
     o->codes = ch.codeT != nullptr;
     if (o->codes && !ch.table) return tnml_fail(c, "%s: block sums without a table", name);
     if (!attr[o->codes]) {

@@ -37,20 +37,28 @@
 // Registers: 74 / 98 / 148 VGPRs at T = 16 / 32 / 64, no scratch.  At T = 64 it is therefore the registers, not the LDS, that hold a CU to
 // one workgroup (3 waves per SIMD where two workgroups need 4); a cap of 128 registers spills 28 of them and was not taken.
 // The kernel leaves [N][2][C] (images fastest); k_response_transpose turns it into [C][N][2] as the caller gets it.
+//
+// Element type.  The kernel is written once over E: double (option gradient_dtype = 0, everything above) and float (gradient_dtype = 1).
+// k_input_grad<float> reads the fp32 copy of W and the float tapes of k_site_backward<float> and takes ChainT<float> for the MFMA
+// (v_mfma_f32_16x16x4_f32), the C/D map (rows 16 rt + 4 q + reg), the element order of Z and the tapes (ChainT<float>::idx) and the tile
+// thresholds (64 up to bond 256, 32 up to 512, 16 up to 1 024: Z stays at 64 KiB).  At the Label site the Z operand is
+// fl32(fl32(c_nl) R[r]).  The four steps above run in fp32 in the same order (step 1 is one fmaf chain per element, see kernels_chain.hip;
+// steps 2 to 4 are fmaf and fp32 additions); dphi receives the fp32 result widened exactly, so dphi32 is rounded no second time.
+// Registers of k_input_grad<float>: 58 / 70 / 116 VGPRs at T = 16 / 32 / 64, no scratch (8 / 7 / 4 waves per SIMD).
 #include "chain_common.h"
 
-template <int NCT>
-__global__ __launch_bounds__(CHAIN_THREADS) void k_input_grad(const InputGradArgs g) {
-    typedef ChainT<double> Tr;
+template <typename E, int NCT>
+__global__ __launch_bounds__(CHAIN_THREADS) void k_input_grad(const InputGradArgsT<E> g) {
+    typedef ChainT<E> Tr;
     constexpr int T = 16 * NCT;
     extern __shared__ __attribute__((aligned(16))) unsigned char ig_lds_raw[];
-    double* const z = reinterpret_cast<double*>(ig_lds_raw);           // [mcap][T] the r-side vector, tape order
-    double* const red = z + (size_t)g.mcap * T;                        // [CHAIN_WAVES][2][T] wave sums
+    E* const z = reinterpret_cast<E*>(ig_lds_raw);                     // [mcap][T] the r-side vector, tape order
+    E* const red = z + (size_t)g.mcap * T;                             // [CHAIN_WAVES][2][T] wave sums
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c16 = lane & 15, q = lane >> 4;
     const int N = g.N, cs = g.cs, nl = g.nl;
     const int tile0 = blockIdx.x * T, j = (int)blockIdx.y + 1;
-    const ChainSite<double> st = g.sites[j - 1];
+    const ChainSite<E> st = g.sites[j - 1];
     const int ml = st.ml, mr = st.mr;
     const bool centre = j == cs;
     const int nlab = centre ? nl : 1;
@@ -58,32 +66,32 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_input_grad(const InputGradArg
     // a side on bond j-1: L_{j-1} (first tape) up to the centre, Y_{j-1} (second tape) right of it;
     // r side on bond j: X_j (second tape) left of the centre, R_{j+1} (first tape) from the centre on
     const size_t slice = (size_t)blockIdx.x * g.rowoff[N + 1] * T;
-    const double* const ev = (j <= cs ? g.tape : g.tape2) + slice + (size_t)g.rowoff[j - 1] * T;
-    const double* const zr = (j < cs ? g.tape2 : g.tape) + slice + (size_t)g.rowoff[j] * T;
-    for (int i = tid; i < mr * T; i += CHAIN_THREADS) z[i] = zr[i];     // (the swizzle permutes inside a row: rows < mr are the first mr T elements)
+    const E* const ev = (j <= cs ? g.tape : g.tape2) + slice + (size_t)g.rowoff[j - 1] * T;
+    const E* const zr = (j < cs ? g.tape2 : g.tape) + slice + (size_t)g.rowoff[j] * T;
+    for (int i = tid; i < Tr::template span<NCT>(mr) * T; i += CHAIN_THREADS) z[i] = zr[i];     // (rows < mr are the first span(mr) stored rows: chain_common.h)
     __syncthreads();
 
     const int nrt = (ml + 15) >> 4;
-    double v0[NCT], v1[NCT];
+    E v0[NCT], v1[NCT];
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) v0[ct] = v1[ct] = 0;
     for (int rt = wave; rt < nrt; rt += CHAIN_WAVES) {
         const int orow = rt * 16 + c16;                                 // the A fragment's row of this lane
         const bool rok = orow < ml;
-        Tr::v4 acc0[NCT], acc1[NCT];
+        typename Tr::v4 acc0[NCT], acc1[NCT];
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) { acc0[ct] = Tr::v4{0, 0, 0, 0}; acc1[ct] = Tr::v4{0, 0, 0, 0}; }
+        for (int ct = 0; ct < NCT; ++ct) { acc0[ct] = typename Tr::v4{0, 0, 0, 0}; acc1[ct] = typename Tr::v4{0, 0, 0, 0}; }
         for (int l = 0; l < nlab; ++l) {
-            double cv[NCT];
+            E cv[NCT];
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) {
                 const int img = tile0 + 16 * ct + c16;
-                cv[ct] = (centre && img < g.cnt) ? g.coef[(size_t)img * nl + l] : 0.;
+                cv[ct] = (centre && img < g.cnt) ? (E)g.coef[(size_t)img * nl + l] : (E)0;
             }
             // element (k, s) of output row orow: A[a = orow][s][r = k] ([ml][2][mr], first index fastest)
-            const double* const Ar = st.a + (size_t)l * lstride + orow;
+            const E* const Ar = st.a + (size_t)l * lstride + orow;
             for (int base = 0; base < mr; base += 16) {
-                double a0[4], a1[4];
+                E a0[4], a1[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int k = base + 4 * q + i;
@@ -95,7 +103,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_input_grad(const InputGradArg
                     const int k = base + 4 * q + i;
 #pragma unroll
                     for (int ct = 0; ct < NCT; ++ct) {
-                        double b = 0;
+                        E b = 0;
                         if (k < mr) {
                             b = z[Tr::template idx<NCT>(k, 16 * ct + c16)];
                             if (centre) b = cv[ct] * b;
@@ -112,7 +120,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_input_grad(const InputGradArg
             for (int r = 0; r < 4; ++r) {
                 const int row = Tr::row(rt, q, r);
                 if (row < ml) {
-                    const double e = ev[Tr::template idx<NCT>(row, 16 * ct + c16)];
+                    const E e = ev[Tr::template idx<NCT>(row, 16 * ct + c16)];
                     v0[ct] = Tr::fma(e, acc0[ct][r], v0[ct]);
                     v1[ct] = Tr::fma(e, acc1[ct][r], v1[ct]);
                 }
@@ -121,8 +129,8 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_input_grad(const InputGradArg
     // the four q groups in order: every lane forms the same sum
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
-        const double t0 = ((__shfl(v0[ct], c16) + __shfl(v0[ct], c16 + 16)) + __shfl(v0[ct], c16 + 32)) + __shfl(v0[ct], c16 + 48);
-        const double t1 = ((__shfl(v1[ct], c16) + __shfl(v1[ct], c16 + 16)) + __shfl(v1[ct], c16 + 32)) + __shfl(v1[ct], c16 + 48);
+        const E t0 = ((__shfl(v0[ct], c16) + __shfl(v0[ct], c16 + 16)) + __shfl(v0[ct], c16 + 32)) + __shfl(v0[ct], c16 + 48);
+        const E t1 = ((__shfl(v1[ct], c16) + __shfl(v1[ct], c16 + 16)) + __shfl(v1[ct], c16 + 32)) + __shfl(v1[ct], c16 + 48);
         if (q == 0) {
             red[(wave * 2 + 0) * T + 16 * ct + c16] = t0;
             red[(wave * 2 + 1) * T + 16 * ct + c16] = t1;
@@ -132,32 +140,35 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_input_grad(const InputGradArg
     if (tid < 2 * T) {
         const int s = tid / T, col = tid - s * T, img = tile0 + col;
         if (img < g.cnt) {
-            double sum = 0;
+            E sum = 0;
             for (int w = 0; w < CHAIN_WAVES; ++w) sum += red[(w * 2 + s) * T + col];
             g.dphi[((size_t)(j - 1) * 2 + s) * g.ld + img] = sum;
         }
     }
 }
 
-// a.mcap and the grid follow from T and maxbond; rows: a.rowoff[N + 1] as the host knows it; tape_elems: doubles behind each of the two tapes
-int launch_input_grad(tnml_ctx* c, InputGradArgs a, int maxbond, int T, int rows, size_t tape_elems, double* outT, float* outT32) {
+// a.mcap and the grid follow from T and maxbond; rows: a.rowoff[N + 1] as the host knows it; tape_elems: elements behind each of the two tapes
+template <typename E>
+int launch_input_grad(tnml_ctx* c, InputGradArgsT<E> a, int maxbond, int T, int rows, size_t tape_elems, double* outT, float* outT32) {
+    typedef ChainT<E> Tr;
+    constexpr bool f32 = sizeof(E) == sizeof(float);
     const char* const name = "input gradient kernel";
-    if (maxbond < 1 || maxbond > TNML_CHAIN_MAXM) return tnml_fail(c, "%s: bond dimension %d outside 1..%d", name, maxbond, TNML_CHAIN_MAXM);
+    if (maxbond < 1 || maxbond > Tr::MAXM) return tnml_fail(c, "%s: bond dimension %d outside 1..%d", name, maxbond, Tr::MAXM);
     if (a.cnt < 1 || a.cnt > a.ld) return tnml_fail(c, "%s: %d images in a chunk of %d", name, a.cnt, a.ld);
     if (T != 64 && T != 32 && T != 16) return tnml_fail(c, "%s: tile width %d", name, T);
     if (!a.tape || !a.tape2 || !a.coef || !a.dphi || (!outT && !outT32)) return tnml_fail(c, "%s: null argument", name);
     a.mcap = (maxbond + 15) / 16 * 16;
     const int grid = (a.cnt + T - 1) / T;
-    const size_t lds = ((size_t)a.mcap * T + (size_t)CHAIN_WAVES * 2 * T) * sizeof(double);
+    const size_t lds = ((size_t)a.mcap * T + (size_t)CHAIN_WAVES * 2 * T) * sizeof(E);
     if (lds > TNML_CHAIN_LDS / 2) return tnml_fail(c, "%s: a tile of %d x %d does not leave room for a second workgroup in the LDS", name, a.mcap, T);
-    if ((size_t)grid * T * rows > tape_elems) return tnml_fail(c, "%s: tapes of %zu doubles too small for %d tiles of %d x %d", name, tape_elems, grid, rows, T);
-    typedef void (*kern_t)(const InputGradArgs);
-    static const kern_t kern[3] = {k_input_grad<1>, k_input_grad<2>, k_input_grad<4>};     // [T / 32]
-    if (!c->attr_inputgrad) {
+    if ((size_t)grid * T * rows > tape_elems) return tnml_fail(c, "%s: tapes of %zu %s too small for %d tiles of %d x %d", name, tape_elems, Tr::elems, grid, rows, T);
+    typedef void (*kern_t)(const InputGradArgsT<E>);
+    static const kern_t kern[3] = {k_input_grad<E, 1>, k_input_grad<E, 2>, k_input_grad<E, 4>};     // [T / 32]
+    if (!c->attr_inputgrad[f32]) {
         for (kern_t fn : kern)
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, TNML_CHAIN_LDS / 2) != hipSuccess)
                 return tnml_fail(c, "%s: hipFuncSetAttribute failed", name);
-        c->attr_inputgrad = true;
+        c->attr_inputgrad[f32] = true;
     }
     {
         ProfScope ps(c, KC_INPUT_GRAD);
@@ -167,3 +178,5 @@ int launch_input_grad(tnml_ctx* c, InputGradArgs a, int maxbond, int T, int rows
     ProfScope ps(c, KC_PACK);
     return launch_response_transpose(c, a.dphi, 2 * a.N, a.cnt, a.ld, outT, outT32);
 }
+template int launch_input_grad<double>(tnml_ctx*, InputGradArgsT<double>, int, int, int, size_t, double*, float*);
+template int launch_input_grad<float>(tnml_ctx*, InputGradArgsT<float>, int, int, int, size_t, double*, float*);

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
     int* const lmask = lsel + T;
     const int N = ch.N, cs = ch.cs;
     // the inward tape of this workgroup (chain_common.h), then X and Y of the centre at rowoff[N + 1], rowoff[N + 2]
-    const ChainTape<T> tape{g.tape + (size_t)blockIdx.x * g.rowoff[N + 3] * T, g.rowoff};
+    const ChainTape<double, T> tape{g.tape + (size_t)blockIdx.x * g.rowoff[N + 3] * T, g.rowoff};
     // the block of wave sums of the step before -> resp[j][s] of the columns that chose l (lsel null: all)
     auto finish = [&](const double* red, int j, bool all, int l) {
         if (tid < 2 * T) {
@@ -146,9 +146,9 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
     double p0[NCT], p1[NCT], q0[NCT], q1[NCT];
     const int img0 = tile0 + (lane & 15), img = tile0 + tid;
     if (tid == 0) *lmask = 0;                                          // (ahead of the walk: behind it the kernel measured 0.6 % slower)
-    int cur = chain_walk_taped<NCT, SRC>(ch, buf, tape, p0, p1, tile0, tid);
+    int cur = chain_walk_taped<double, NCT, SRC>(ch, buf, tape, p0, p1, tile0, tid);
     double* const park = tape.bond(cs);                                // R_{cs+1}
-    const int pr = chain_centre_taped<NCT>(ch, buf, cur, park, p0, p1, tile0, tid, [](int, double, int, int) {});
+    const int pr = chain_centre_taped<double, NCT>(ch, buf, cur, park, p0, p1, tile0, tid, [](int, double, int, int) {});
     const ChainSite<double> sc = ch.sites[cs - 1];
     const size_t lstride = (size_t)sc.ml * 2 * sc.mr;
     if (tid < T) {
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
         }
         lsel[tid] = ln;
     }
-    chain_copy_rows<T>(park, buf[cur ^ 1], sc.mr, tid);                // R into the free tile: the operand of the right-type product
+    chain_copy_rows<double, T>(park, buf[cur ^ 1], sc.mr, tid);                // R into the free tile: the operand of the right-type product
     __syncthreads();
     const int mask = *lmask;
     if (tid < T && lsel[tid] < 0) lsel[tid] = __ffs(mask) - 1;         // columns beyond the chunk (all zero) ride with the first chosen label
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
 
     // ---- phase B, left of the centre: j = cs-1 .. 1 ----
     if (cs > 1) {
-        chain_copy_rows<T>(tape.bond(N + 1), buf[0], sc.ml, tid);
+        chain_copy_rows<double, T>(tape.bond(N + 1), buf[0], sc.ml, tid);
         chain_features<double, NCT, SRC>(ch, cs - 1, img0, p0, p1);
         __syncthreads();
         cur = 0;
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_response(const RespArgs g) {
     // ---- phase B, right of the centre: j = cs+1 .. N ----
     if (cs < N) {
         __syncthreads();                                               // the tiles are free: every wave has left the loop above
-        chain_copy_rows<T>(tape.bond(N + 2), buf[0], sc.mr, tid);
+        chain_copy_rows<double, T>(tape.bond(N + 2), buf[0], sc.mr, tid);
         chain_features<double, NCT, SRC>(ch, cs + 1, img0, p0, p1);
         __syncthreads();
         cur = 0;

@@ -41,6 +41,23 @@
 //    itself in the thread's column of the LDS coefficients; after the centre the thread that owns the image turns its column into the
 //    coefficients of the softmax cross-entropy (loss_dev.h) and writes them to LDS and to the [C][nl] buffer.  Everything after is shared.
 //
+// Element type.  Both kernels are written once over E: double (option gradient_dtype = 0, everything above) and float (gradient_dtype = 1),
+// which takes ChainT<float> for the MFMA (v_mfma_f32_16x16x4_f32), its C/D map (row = 16 rt + 4 q + reg), the element order of the LDS
+// tiles and of both tapes (ChainT<float>::idx) and the tile thresholds (64 up to bond 256, 32 up to 512, 16 up to 1 024).  In fp32:
+//   * operands: the fp32 copy of W (k_chain_pack32, once per call), features formed in fp64 and rounded once, as k_chain<float> has them;
+//     phase A is k_chain<float>'s walk and centre, so weights and pred are those of tnml_predict_* under predict_dtype = 1 bit for bit;
+//   * coefficients: the thread that owns the image widens its weights, forms c in fp64 by the expressions above (2 (W - y), or loss_dev.h),
+//     rounds once to fp32 and writes the rounded value, widened, to the [C][nl] buffer; given coefficients are rounded to fp32 once;
+//   * seeds and outward walk in fp32, the operand fl32(fl32(c phi_s) v); both tapes hold floats;
+//   * k_site_grad<float>: accumulators from 0 in every chunk, the fp32 MFMA over the tiles in the order above (per output element one
+//     fmaf chain over the images, four per MFMA step, q ascending), then G[e] = G[e] + (double)acc: one fp64 addition per element and
+//     chunk.  G, and so the sum over chunks, stays fp64;
+//   * a weight that is not finite raises ch.flag (a plain vector store of 1); the host fails the call.
+// tests/grad32_model.py restates this order.
+//
+// Registers (gfx950 cross-compile; VGPRs at T = 16 / 32 / 64, bytes / input map source alike to within 3; no scratch in any instantiation):
+//   k_site_backward<double>: 104 / 127 / 162      k_site_backward<float>: 94 / 99 / 121     (the softmax forms: the same counts, float T = 16: 96)
+//   k_site_grad<double>:     60 / 56 / 58 + 16 accumulator registers      k_site_grad<float>: 36 / 33 / 33 + 8
 // No atomics; compiled with -ffp-contract=off like its neighbours.
 #include "chain_common.h"
 #include "loss_dev.h"
@@ -49,30 +66,30 @@
 #define SG_BLK 32                   /* output block: SG_BLK (a) x SG_BLK (r), both s */
 
 // the seed of an outward walk (see the header): vout[M][T] = sum_l (site matrix of label l) x (c_l phi . vin); vin an LDS tile, vout a tape region
-template <int NCT, bool LEFT>
-static __device__ __forceinline__ void seed_step(const double* __restrict__ A, size_t lstride, int nl, int ml, int mr, const double* vin, double* vout,
-                                                 const double (&p0)[NCT], const double (&p1)[NCT], const double* cl, int wave, int lane) {
-    typedef ChainT<double> Tr;
+template <typename E, int NCT, bool LEFT>
+static __device__ __forceinline__ void seed_step(const E* __restrict__ A, size_t lstride, int nl, int ml, int mr, const E* vin, E* vout,
+                                                 const E (&p0)[NCT], const E (&p1)[NCT], const E* cl, int wave, int lane) {
+    typedef ChainT<E> Tr;
     constexpr int T = 16 * NCT;
     const int c16 = lane & 15, q = lane >> 4;
     const int K = LEFT ? 2 * ml : 2 * mr, M = LEFT ? mr : ml;
     const int nrt = (M + 15) >> 4;
     for (int rt = wave; rt < nrt; rt += CHAIN_WAVES) {
         const int orow = rt * 16 + c16;
-        Tr::v4 acc[NCT];
+        typename Tr::v4 acc[NCT];
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) acc[ct] = Tr::v4{0, 0, 0, 0};
+        for (int ct = 0; ct < NCT; ++ct) acc[ct] = typename Tr::v4{0, 0, 0, 0};
         for (int l = 0; l < nl; ++l) {
-            double c0[NCT], c1[NCT];
+            E c0[NCT], c1[NCT];
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) {
-                const double cv = cl[l * T + 16 * ct + c16];
+                const E cv = cl[l * T + 16 * ct + c16];
                 c0[ct] = cv * p0[ct]; c1[ct] = cv * p1[ct];
             }
-            const double* const Al = A + (size_t)l * lstride;
+            const E* const Al = A + (size_t)l * lstride;
             for (int base = 0; base < K; base += 16) {
-                double a[4];
-                chain_load_a<double, LEFT>(Al, ml, M, K, orow, base + 4 * q, a);
+                E a[4];
+                chain_load_a<E, LEFT>(Al, ml, M, K, orow, base + 4 * q, a);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int kk = base + 4 * q + i;
@@ -82,7 +99,7 @@ static __device__ __forceinline__ void seed_step(const double* __restrict__ A, s
                     else      { s = kk & 1; vr = kk >> 1; }
 #pragma unroll
                     for (int ct = 0; ct < NCT; ++ct) {
-                        double b = 0;
+                        E b = 0;
                         if (kok) b = (s ? c1[ct] : c0[ct]) * vin[Tr::template idx<NCT>(vr, 16 * ct + c16)];
                         acc[ct] = Tr::mfma(a[i], b, acc[ct]);
                     }
@@ -102,67 +119,72 @@ static __device__ __forceinline__ void seed_step(const double* __restrict__ A, s
 // One outward walk from the seed on the second tape with chain_step itself, every vector to the second tape.  LEFT is chain_step's:
 // false carries X left of the centre (seed of seed_rows on bond cs-1; site j = cs-1 .. 2 writes bond j-1), true carries Y right of it
 // (seed on bond cs; site j = cs+1 .. N-1 writes bond j).  Opens with a barrier: the seeds are written, the tiles free.
-template <int NCT, int SRC, bool LEFT>
-static __device__ __forceinline__ void carry_outward(const ChainArgs<double>& ch, double* const (&buf)[2], const ChainTape<16 * NCT>& tape2, int seed_rows,
-                                                     double (&p0)[NCT], double (&p1)[NCT], int tile0, int tid) {
+template <typename E, int NCT, int SRC, bool LEFT>
+static __device__ __forceinline__ void carry_outward(const ChainArgs<E>& ch, E* const (&buf)[2], const ChainTape<E, 16 * NCT>& tape2, int seed_rows,
+                                                     E (&p0)[NCT], E (&p1)[NCT], int tile0, int tid) {
     constexpr int T = 16 * NCT, D = LEFT ? 1 : -1;
     const int lane = tid & 63, wave = tid >> 6, img0 = tile0 + (lane & 15);
     const int N = ch.N, cs = ch.cs;
     if (LEFT ? cs >= N - 1 : cs <= 2) return;
-    double q0[NCT], q1[NCT];
+    E q0[NCT], q1[NCT];
     __syncthreads();
-    chain_copy_rows<T>(tape2.bond(LEFT ? cs : cs - 1), buf[0], seed_rows, tid);
-    chain_features<double, NCT, SRC>(ch, cs + D, img0, p0, p1);
+    chain_copy_rows<E, T>(tape2.bond(LEFT ? cs : cs - 1), buf[0], seed_rows, tid);
+    chain_features<E, NCT, SRC>(ch, cs + D, img0, p0, p1);
     __syncthreads();
     int cur = 0;
     for (int j = cs + D; LEFT ? j <= N - 1 : j >= 2; j += D) {
-        chain_features<double, NCT, SRC>(ch, j + D, img0, q0, q1);
-        const ChainSite<double> st = ch.sites[j - 1];
-        chain_step<double, NCT, LEFT>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
+        chain_features<E, NCT, SRC>(ch, j + D, img0, q0, q1);
+        const ChainSite<E> st = ch.sites[j - 1];
+        chain_step<E, NCT, LEFT>(st.a, st.ml, st.mr, buf[cur], buf[cur ^ 1], p0, p1, wave, lane);
         cur ^= 1;
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) { p0[ct] = q0[ct]; p1[ct] = q1[ct]; }
         __syncthreads();
-        chain_copy_rows<T>(buf[cur], tape2.bond(LEFT ? j : j - 1), LEFT ? st.mr : st.ml, tid);
+        chain_copy_rows<E, T>(buf[cur], tape2.bond(LEFT ? j : j - 1), LEFT ? st.mr : st.ml, tid);
     }
 }
 
-template <int NCT, int SRC, int LOSS = 0>
-__global__ __launch_bounds__(CHAIN_THREADS) void k_site_backward(const SiteGradArgs g) {
+template <typename E, int NCT, int SRC, int LOSS = 0>
+__global__ __launch_bounds__(CHAIN_THREADS) void k_site_backward(const SiteGradArgsT<E> g) {
+    typedef ChainT<E> Tr;
+    constexpr bool f32 = sizeof(E) == sizeof(float);
     constexpr int T = 16 * NCT;
     extern __shared__ __attribute__((aligned(16))) unsigned char sg_lds_raw[];
-    double* const lds = reinterpret_cast<double*>(sg_lds_raw);
-    const ChainArgs<double>& ch = g.ch;
+    E* const lds = reinterpret_cast<E*>(sg_lds_raw);
+    const ChainArgs<E>& ch = g.ch;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tile0 = blockIdx.x * T;
     const size_t tile_elems = (size_t)ch.mcap * T;
-    double* buf[2] = {lds, lds + tile_elems};
-    double* const cl = lds + 2 * tile_elems;                           // [nl][T] coefficients of the tile
+    E* buf[2] = {lds, lds + tile_elems};
+    E* const cl = lds + 2 * tile_elems;                                // [nl][T] coefficients of the tile
     const int N = ch.N, cs = ch.cs;
     const size_t slice = (size_t)blockIdx.x * g.rowoff[N + 1] * T;
-    const ChainTape<T> tape{g.tape + slice, g.rowoff};                 // inward vectors (chain_common.h)
-    const ChainTape<T> tape2{g.tape2 + slice, g.rowoff};               // outward vectors: X_b (b < cs), Y_b (b >= cs) on bond b
+    const ChainTape<E, T> tape{g.tape + slice, g.rowoff};              // inward vectors (chain_common.h)
+    const ChainTape<E, T> tape2{g.tape2 + slice, g.rowoff};              // outward vectors: X_b (b < cs), Y_b (b >= cs) on bond b
 
     // ---- phase A: k_chain's walk and centre, every chain vector also to the tape (chain_common.h).  The coefficients of the tile go to cl. ----
-    double p0[NCT], p1[NCT];
-    int cur = chain_walk_taped<NCT, SRC>(ch, buf, tape, p0, p1, tile0, tid);
-    double* const park = tape.bond(cs);                                // R_{cs+1}
-    chain_centre_taped<NCT>(ch, buf, cur, park, p0, p1, tile0, tid, [&](int l, double w, int col, int img) {
-        double cv = 0;
+    E p0[NCT], p1[NCT];
+    int cur = chain_walk_taped<E, NCT, SRC>(ch, buf, tape, p0, p1, tile0, tid);
+    E* const park = tape.bond(cs);                                     // R_{cs+1}
+    bool bad = false;                                                  // fp32: a weight of the thread's image is Inf or NaN
+    chain_centre_taped<E, NCT>(ch, buf, cur, park, p0, p1, tile0, tid, [&](int l, E w, int col, int img) {
+        E cv = 0;
         if (img < ch.cnt) {
+            if (Tr::bad(Tr::abs(w))) bad = true;
             if constexpr (LOSS == 1) {
                 cv = w;                                                // parked: the softmax block below needs all ten
-            } else if (g.lab) {
+            } else if (g.lab) {                                        // formed in fp64 from the (widened) weight, rounded once to E
                 const int lb = g.lab[img];
                 const double y = (ch.single ? lb == g.target : lb == l) ? 1. : 0.;
-                cv = 2. * (w - y);
+                cv = (E)(2. * ((double)w - y));
                 g.coef[(size_t)img * ch.nl + l] = cv;
             } else {
-                cv = g.coef[(size_t)img * ch.nl + l];
+                cv = (E)g.coef[(size_t)img * ch.nl + l];
             }
         }
         cl[l * T + col] = cv;
     });
+    if constexpr (f32) { if (bad) *ch.flag = 1; }
     if constexpr (LOSS == 1) {                                         // (the centre ends on a barrier; the one below orders this before seed_step)
         const int img = tile0 + tid;
         if (tid < T && img < ch.cnt) {
@@ -172,32 +194,35 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_site_backward(const SiteGradA
             int d;
             (void)loss_softmax(wv, g.lab[img], g.beta, &d);
 #pragma unroll
-            for (int l = 0; l < TNML_NL; ++l) { cl[l * T + tid] = wv[l]; g.coef[(size_t)img * TNML_NL + l] = wv[l]; }
+            for (int l = 0; l < TNML_NL; ++l) { const E cv = (E)wv[l]; cl[l * T + tid] = cv; g.coef[(size_t)img * TNML_NL + l] = cv; }
         }
     }
-    const ChainSite<double> sc = ch.sites[cs - 1];
+    const ChainSite<E> sc = ch.sites[cs - 1];
     const size_t lstride = (size_t)sc.ml * 2 * sc.mr;
-    chain_copy_rows<T>(park, buf[cur ^ 1], sc.mr, tid);                // R into the free tile: the operand of the right-type seed
+    chain_copy_rows<E, T>(park, buf[cur ^ 1], sc.mr, tid);                // R into the free tile: the operand of the right-type seed
     __syncthreads();
 
     // ---- centre: the seeds X_{cs-1} (second tape, bond cs-1) and Y_cs (bond cs) ----
-    if (cs > 1) seed_step<NCT, false>(sc.a, lstride, ch.nl, sc.ml, sc.mr, buf[cur ^ 1], tape2.bond(cs - 1), p0, p1, cl, wave, lane);
-    if (cs < N) seed_step<NCT, true>(sc.a, lstride, ch.nl, sc.ml, sc.mr, buf[cur], tape2.bond(cs), p0, p1, cl, wave, lane);
+    if (cs > 1) seed_step<E, NCT, false>(sc.a, lstride, ch.nl, sc.ml, sc.mr, buf[cur ^ 1], tape2.bond(cs - 1), p0, p1, cl, wave, lane);
+    if (cs < N) seed_step<E, NCT, true>(sc.a, lstride, ch.nl, sc.ml, sc.mr, buf[cur], tape2.bond(cs), p0, p1, cl, wave, lane);
 
     // ---- phase B: X_{j-1} = (phi_j A_j) X_j, j = cs-1 .. 2, then Y_j = Y_{j-1} (phi_j A_j), j = cs+1 .. N-1 ----
-    carry_outward<NCT, SRC, false>(ch, buf, tape2, sc.ml, p0, p1, tile0, tid);
-    carry_outward<NCT, SRC, true>(ch, buf, tape2, sc.mr, p0, p1, tile0, tid);
+    carry_outward<E, NCT, SRC, false>(ch, buf, tape2, sc.ml, p0, p1, tile0, tid);
+    carry_outward<E, NCT, SRC, true>(ch, buf, tape2, sc.mr, p0, p1, tile0, tid);
 }
 
 // ---- the GEMM over the image index ----
-template <int NCT, int SRC>
-__global__ __launch_bounds__(SG_THREADS) void k_site_grad(const SiteGradArgs g) {
-    typedef ChainT<double> Tr;
-    constexpr int T = 16 * NCT, P = T + 4;                            // row pitch of the staged operands (doubles)
-    __shared__ double sa[SG_BLK * P];                                  // a side [32][P]
-    __shared__ double sr[2 * SG_BLK * P];                              // r side [s][32][P], the feature multiplied in
-    __shared__ double fs[2][2][T];                                     // [parity][s][image of the tile]: the feature / coefficient operand
-    const ChainArgs<double>& ch = g.ch;
+template <typename E, int NCT, int SRC>
+__global__ __launch_bounds__(SG_THREADS) void k_site_grad(const SiteGradArgsT<E> g) {
+    typedef ChainT<E> Tr;
+    constexpr bool f32 = sizeof(E) == sizeof(float);
+    // row pitch of the staged operands (elements).  The MFMA loop reads element (16 w + c16) P + q + 4 t per lane: in fp32 a ds_read_b32
+    // serves 32 lanes (c16 = 0..15, two q) over 32 banks, and P = 2 mod 32 puts them on 32 different banks
+    constexpr int T = 16 * NCT, P = T + (f32 ? 2 : 4);
+    __shared__ E sa[SG_BLK * P];                                       // a side [32][P]
+    __shared__ E sr[2 * SG_BLK * P];                                   // r side [s][32][P], the feature multiplied in
+    __shared__ E fs[2][2][T];                                          // [parity][s][image of the tile]: the feature / coefficient operand
+    const ChainArgs<E>& ch = g.ch;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c16 = lane & 15, q = lane >> 4;
     const int N = ch.N, cs = ch.cs, nl = ch.nl, NV = N - 1 + nl;
@@ -207,7 +232,7 @@ __global__ __launch_bounds__(SG_THREADS) void k_site_grad(const SiteGradArgs g) 
     const int v = lo;
     int j, l = 0;
     if (v < cs - 1) j = v + 1; else if (v < cs - 1 + nl) { j = cs; l = v - (cs - 1); } else j = v - nl + 2;
-    const ChainSite<double> st = ch.sites[j - 1];
+    const ChainSite<E> st = ch.sites[j - 1];
     const int ml = st.ml, mr = st.mr;
     const int nrb = (mr + SG_BLK - 1) / SG_BLK;
     const int bi = (int)blockIdx.x - g.blk0[v];
@@ -215,31 +240,32 @@ __global__ __launch_bounds__(SG_THREADS) void k_site_grad(const SiteGradArgs g) 
     // a side on bond j-1: L_{j-1} (first tape) up to the centre, Y_{j-1} (second tape) right of it;
     // r side on bond j: X_j (second tape) left of the centre, R_{j+1} (first tape) from the centre on
     const size_t rows = g.rowoff[N + 1];
-    const double* const abase = (j <= cs ? g.tape : g.tape2) + (size_t)g.rowoff[j - 1] * T;
-    const double* const rbase = (j < cs ? g.tape2 : g.tape) + (size_t)g.rowoff[j] * T;
+    const E* const abase = (j <= cs ? g.tape : g.tape2) + (size_t)g.rowoff[j - 1] * T;
+    const E* const rbase = (j < cs ? g.tape2 : g.tape) + (size_t)g.rowoff[j] * T;
     const bool centre = j == cs;
     double* const G = g.grad + g.goff[j - 1] + (centre ? (size_t)l * ml * 2 * mr : 0);
 
-    // this wave's output tile: rows of the MFMA = r (r0 + 16 wr + ..), columns = a (a0 + 16 wa + ..); accumulators from G
+    // this wave's output tile: rows of the MFMA = r (r0 + 16 wr + ..), columns = a (a0 + 16 wa + ..); accumulators from G (fp32: from 0)
     const int wa = wave & 1, wr = wave >> 1;
     const int oa = a0 + 16 * wa + c16;
-    Tr::v4 acc[2];
+    typename Tr::v4 acc[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-            const int orr = r0 + 16 * wr + q + 4 * reg;
-            acc[s][reg] = (oa < ml && orr < mr) ? G[oa + (size_t)ml * (s + 2 * orr)] : 0.;
+            const int orr = r0 + 16 * wr + Tr::rowq(q, reg);
+            if constexpr (f32) acc[s][reg] = 0;
+            else acc[s][reg] = (oa < ml && orr < mr) ? G[oa + (size_t)ml * (s + 2 * orr)] : 0.;
         }
 
     // the feature operand of a tile: phi_s of site j (x c_nl at the Label site), (0, 0) beyond the chunk
     auto features = [&](int tile, int par) {
         if (tid < T) {
             const int img = tile * T + tid;
-            double f0[1], f1[1];
-            chain_features<double, 1, SRC>(ch, j, img, f0, f1);
-            if (centre) {
-                const double cv = img < ch.cnt ? g.coef[(size_t)img * nl + l] : 0.;
+            E f0[1], f1[1];
+            chain_features<E, 1, SRC>(ch, j, img, f0, f1);
+            if (centre) {                                              // (fp32: the buffer holds fp32 values widened, or given coefficients, rounded here)
+                const E cv = img < ch.cnt ? (E)g.coef[(size_t)img * nl + l] : (E)0;
                 f0[0] = cv * f0[0]; f1[0] = cv * f1[0];
             }
             fs[par][0][tid] = f0[0]; fs[par][1][tid] = f1[0];
@@ -249,28 +275,29 @@ __global__ __launch_bounds__(SG_THREADS) void k_site_grad(const SiteGradArgs g) 
     features(0, 0);
     for (int tile = 0; tile < ntiles; ++tile) {
         const int par = tile & 1;
-        const double* const at = abase + (size_t)tile * rows * T;
-        const double* const rt = rbase + (size_t)tile * rows * T;
+        const E* const at = abase + (size_t)tile * rows * T;
+        const E* const rt = rbase + (size_t)tile * rows * T;
         __syncthreads();                                               // the MFMAs of the tile before have read sa / sr; fs[par] is there
-        // stage: thread -> (row, a pair of physical columns); the tape's odd rows have their 16-column halves swapped for T >= 32
+        // stage: thread -> (row, a pair of physical columns); where the tape keeps them: ChainT<E>::prow / lcol (fp64: odd rows have their
+        // 16-column halves swapped for T >= 32)
         for (int e = tid; e < SG_BLK * (T / 2); e += SG_THREADS) {
             const int row = e / (T / 2), pc = (e - row * (T / 2)) * 2;
             const bool live = tile * T + T <= ch.cnt;                  // every image of the tile is inside the chunk
             {
                 const int ar = a0 + row;
-                const int col = NCT > 1 ? (pc ^ ((ar & 1) << 4)) : pc;
-                Tr::v2 x = {0, 0};
-                if (ar < ml) x = *(const Tr::v2*)(at + (size_t)ar * T + pc);
+                const int col = Tr::template lcol<NCT>(ar, pc);
+                typename Tr::v2 x = {0, 0};
+                if (ar < ml) x = *(const typename Tr::v2*)(at + (size_t)Tr::template prow<NCT>(ar) * T + pc);
                 if (!live) { if (tile * T + col >= ch.cnt) x.x = 0; if (tile * T + col + 1 >= ch.cnt) x.y = 0; }
                 sa[row * P + col] = x.x; sa[row * P + col + 1] = x.y;
             }
             {
                 const int rr = r0 + row;
-                const int col = NCT > 1 ? (pc ^ ((rr & 1) << 4)) : pc;
-                Tr::v2 x = {0, 0};
-                if (rr < mr) x = *(const Tr::v2*)(rt + (size_t)rr * T + pc);
-                double y00 = fs[par][0][col] * x.x, y01 = fs[par][0][col + 1] * x.y;
-                double y10 = fs[par][1][col] * x.x, y11 = fs[par][1][col + 1] * x.y;
+                const int col = Tr::template lcol<NCT>(rr, pc);
+                typename Tr::v2 x = {0, 0};
+                if (rr < mr) x = *(const typename Tr::v2*)(rt + (size_t)Tr::template prow<NCT>(rr) * T + pc);
+                E y00 = fs[par][0][col] * x.x, y01 = fs[par][0][col + 1] * x.y;
+                E y10 = fs[par][1][col] * x.x, y11 = fs[par][1][col + 1] * x.y;
                 if (!live) {                                           // the zero comes from the feature operand, as a select
                     if (tile * T + col >= ch.cnt) { y00 = 0; y10 = 0; }
                     if (tile * T + col + 1 >= ch.cnt) { y01 = 0; y11 = 0; }
@@ -281,12 +308,12 @@ __global__ __launch_bounds__(SG_THREADS) void k_site_grad(const SiteGradArgs g) 
         }
         if (tile + 1 < ntiles) features(tile + 1, par ^ 1);
         __syncthreads();
-        const double* const pa = sa + (16 * wa + c16) * P + q;
-        const double* const pr0 = sr + (16 * wr + c16) * P + q;
-        const double* const pr1 = pr0 + SG_BLK * P;
+        const E* const pa = sa + (16 * wa + c16) * P + q;
+        const E* const pr0 = sr + (16 * wr + c16) * P + q;
+        const E* const pr1 = pr0 + SG_BLK * P;
 #pragma unroll 4
         for (int t = 0; t < T / 4; ++t) {
-            const double a = pa[4 * t];
+            const E a = pa[4 * t];
             acc[0] = Tr::mfma(pr0[4 * t], a, acc[0]);
             acc[1] = Tr::mfma(pr1[4 * t], a, acc[1]);
         }
@@ -295,25 +322,32 @@ __global__ __launch_bounds__(SG_THREADS) void k_site_grad(const SiteGradArgs g) 
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-            const int orr = r0 + 16 * wr + q + 4 * reg;
-            if (oa < ml && orr < mr) G[oa + (size_t)ml * (s + 2 * orr)] = acc[s][reg];
+            const int orr = r0 + 16 * wr + Tr::rowq(q, reg);
+            if constexpr (f32) {                                       // the chunk's fp32 sum joins the fp64 gradient: one addition
+                if (oa < ml && orr < mr) G[oa + (size_t)ml * (s + 2 * orr)] = G[oa + (size_t)ml * (s + 2 * orr)] + (double)acc[s][reg];
+            } else {
+                if (oa < ml && orr < mr) G[oa + (size_t)ml * (s + 2 * orr)] = acc[s][reg];
+            }
         }
 }
 
-// a.ch.mcap and the grids follow from T; rows: a.rowoff[N + 1] as the host knows it; tape_elems: doubles behind each of the two tapes;
+// a.ch.mcap and the grids follow from T; rows: a.rowoff[N + 1] as the host knows it; tape_elems: elements behind each of the two tapes;
 // nblocks: a.blk0[N - 1 + nl] as the host knows it
 // run_gemm false: k_site_backward alone (tnml_backward_* without grad)
-int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int rows, size_t tape_elems, int nblocks, bool run_gemm) {
+template <typename E>
+int launch_site_gradient(tnml_ctx* c, SiteGradArgsT<E> a, int maxbond, int T, int rows, size_t tape_elems, int nblocks, bool run_gemm) {
+    constexpr bool f32 = sizeof(E) == sizeof(float);
     if (nblocks < 1) return tnml_fail(c, "site gradient kernel: %d output blocks", nblocks);
-    typedef void (*kern_t)(const SiteGradArgs);
-    static const kern_t bwd[2][3] = {{k_site_backward<1, 0>, k_site_backward<2, 0>, k_site_backward<4, 0>}, {k_site_backward<1, 1>, k_site_backward<2, 1>, k_site_backward<4, 1>}};   // [SRC][T / 32]
-    static const kern_t gemm[2][3] = {{k_site_grad<1, 0>, k_site_grad<2, 0>, k_site_grad<4, 0>}, {k_site_grad<1, 1>, k_site_grad<2, 1>, k_site_grad<4, 1>}};
-    static const kern_t bwd_sm[2][3] = {{k_site_backward<1, 0, 1>, k_site_backward<2, 0, 1>, k_site_backward<4, 0, 1>}, {k_site_backward<1, 1, 1>, k_site_backward<2, 1, 1>, k_site_backward<4, 1, 1>}};
+    if (f32 && !a.ch.flag) return tnml_fail(c, "site gradient kernel: no range flag");
+    typedef void (*kern_t)(const SiteGradArgsT<E>);
+    static const kern_t bwd[2][3] = {{k_site_backward<E, 1, 0>, k_site_backward<E, 2, 0>, k_site_backward<E, 4, 0>}, {k_site_backward<E, 1, 1>, k_site_backward<E, 2, 1>, k_site_backward<E, 4, 1>}};   // [SRC][T / 32]
+    static const kern_t gemm[2][3] = {{k_site_grad<E, 1, 0>, k_site_grad<E, 2, 0>, k_site_grad<E, 4, 0>}, {k_site_grad<E, 1, 1>, k_site_grad<E, 2, 1>, k_site_grad<E, 4, 1>}};
+    static const kern_t bwd_sm[2][3] = {{k_site_backward<E, 1, 0, 1>, k_site_backward<E, 2, 0, 1>, k_site_backward<E, 4, 0, 1>}, {k_site_backward<E, 1, 1, 1>, k_site_backward<E, 2, 1, 1>, k_site_backward<E, 4, 1, 1>}};
     const bool softmax = a.loss == TNML_LOSS_SOFTMAX;                  // (the host sets it in the labels mode only)
     if (softmax && (!a.lab || a.ch.single || a.ch.nl != TNML_NL)) return tnml_fail(c, "site gradient kernel: the softmax loss needs labels and %d outputs", TNML_NL);
     TapedLaunch L;                                                     // beside the two tiles: the coefficients [nl][T]
-    TCK(taped_launch(c, "site gradient kernel", "tapes", a.ch, maxbond, T, rows, tape_elems, (size_t)a.ch.nl * T * sizeof(double), softmax ? bwd_sm : bwd,
-                     softmax ? c->attr_sitegrad_sm : c->attr_sitegrad, &L));
+    TCK(taped_launch(c, "site gradient kernel", "tapes", a.ch, maxbond, T, rows, tape_elems, (size_t)a.ch.nl * T * sizeof(E), softmax ? bwd_sm : bwd,
+                     softmax ? c->attr_sitegrad_sm[f32] : c->attr_sitegrad[f32], &L));
     {
         ProfScope ps(c, KC_SITE_BWD);
         hipLaunchKernelGGL((softmax ? bwd_sm : bwd)[L.codes][T / 32], dim3(L.grid), dim3(CHAIN_THREADS), L.lds, c->stream, a);
@@ -325,3 +359,5 @@ int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int ro
     HIPCK(c, hipGetLastError());
     return 0;
 }
+template int launch_site_gradient<double>(tnml_ctx*, SiteGradArgsT<double>, int, int, int, size_t, int, bool);
+template int launch_site_gradient<float>(tnml_ctx*, SiteGradArgsT<float>, int, int, int, size_t, int, bool);

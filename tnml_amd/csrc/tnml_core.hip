@@ -122,6 +122,7 @@ static const OptDef k_options[] = {
     {"predict_dtype",    nullptr,               OPT_INT,  &tnml_ctx::predict_dtype,       nullptr,          0, 1,       HK_NONE},   // TNML_PREDICT_F64 / TNML_PREDICT_F32
     {"response_chunk",   nullptr,               OPT_INT,  &tnml_ctx::response_chunk,      nullptr,          1, 1 << 20, HK_NONE},
     {"gradient_chunk",   nullptr,               OPT_INT,  &tnml_ctx::gradient_chunk,      nullptr,          1, 1 << 20, HK_NONE},
+    {"gradient_dtype",   nullptr,               OPT_INT,  &tnml_ctx::gradient_dtype,      nullptr,          0, 1,       HK_NONE},   // TNML_GRADIENT_F64 / TNML_GRADIENT_F32
     {"fg64_cfg",         "TNML_FG64_CFG",       OPT_INT,  &tnml_ctx::opt_fg64_cfg,        nullptr,          0, 2,       HK_NONE},
     {"ldot_cfg",         "TNML_LDOT_CFG",       OPT_INT,  &tnml_ctx::opt_ldot_cfg,        nullptr,          0, 2,       HK_NONE},
     {"loss",             nullptr,               OPT_INT,  &tnml_ctx::loss,                nullptr,          0, 1,       HK_LOSS},   // TNML_LOSS_QUADRATIC / TNML_LOSS_SOFTMAX

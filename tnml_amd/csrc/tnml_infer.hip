@@ -116,8 +116,8 @@ void response_release(tnml_ctx* c) {
 }
 void sitegrad_release(tnml_ctx* c) {
     ws_release(c, c->sg, {(void**)&c->sg_lab, (void**)&c->sg_coef, (void**)&c->sg_rowoff, (void**)&c->sg_goff, (void**)&c->sg_blk0, (void**)&c->sg_grad, (void**)&c->sg_tape, (void**)&c->sg_tape2,
-                          (void**)&c->bw_out, (void**)&c->bw_outT});
-    c->sg_tape_rows = 0; c->sg_grad_elems = 0; c->sg_last_cnt = -1;
+                          (void**)&c->bw_out, (void**)&c->bw_outT, (void**)&c->sg_w32, (void**)&c->sg_tab32, (void**)&c->sg_flag, (void**)&c->sg_xphi32, (void**)&c->sg_mtab32});
+    c->sg_tape_rows = 0; c->sg_grad_elems = 0; c->sg_last_cnt = -1; c->sg_w32_cap = 0; c->sg_mtab32_bytes = 0;
 }
 // First call, or the chunk option has changed since: the old workspace goes (release), tab, w and pred are made for the new capacity;
 // *fresh then tells the caller to allocate what it alone has.  On an error here and in the helpers below the caller releases the workspace.
@@ -170,7 +170,8 @@ static int ws_staging(tnml_ctx* c, StreamWs& s, const char* who, bool bytes_form
 }
 // The refusals every streamed call opens with, in this order.  fp64_only: what the call computes when it serves predict_dtype = 0 alone
 // (null: tnml_predict_* / tnml_evaluate_*, which take fp32 too); *maxbond: the largest bond of W
-static int streamed_refusals(tnml_ctx* c, const char* who, const char* fp64_only, int64_t n, int* maxbond) {
+// grad: the call follows option gradient_dtype (the gradient, backward and step calls); under fp32 its bond cap is the fp32 chain kernel's
+static int streamed_refusals(tnml_ctx* c, const char* who, const char* fp64_only, int64_t n, int* maxbond, bool grad = false) {
     if (!c) return tnml_fail(c, "%s: null argument", who);
     if (n < 0) return tnml_fail(c, "%s: n = %lld, must be >= 0", who, (long long)n);
     if (c->pend_count > 0) return tnml_fail(c, "%s: a bond update is in flight (tnml_bond_update_end first)", who);
@@ -178,7 +179,7 @@ static int streamed_refusals(tnml_ctx* c, const char* who, const char* fp64_only
     TCK(check_W(c));
     int mb = 1;
     for (int j = 1; j <= c->N; ++j) mb = std::max(mb, std::max(c->W[j].ml, c->W[j].mr));
-    const bool f32 = !fp64_only && c->predict_dtype == TNML_PREDICT_F32;
+    const bool f32 = (!fp64_only && c->predict_dtype == TNML_PREDICT_F32) || (grad && c->gradient_dtype == TNML_GRADIENT_F32);
     if (f32 && mb > TNML_CHAIN32_MAXM)
         return tnml_fail(c, "%s: W has a bond of dimension %d, the fp32 chain kernel serves bond dimensions up to %d: use tnml_classify on a context that holds the images", who, mb, TNML_CHAIN32_MAXM);
     if (!f32 && mb > TNML_CHAIN_MAXM)
@@ -311,15 +312,16 @@ static int predict_workspace(tnml_ctx* c, const char* who, bool bytes_form, bool
     if (rc) predict_release(c);
     return rc;
 }
-// The fp32 side of the workspace (first call under predict_dtype = 1): the site table of the fp32 copy of W, the range flag, the copy itself
-// (grown when W has grown) and, under an input map, the table rounded to fp32.  Then the copy is made: W may have changed since the last call.
-static int predict_workspace32(tnml_ctx* c, bool mapped, const std::vector<ChainSite<double>>& tab) {
-    StreamWs& s = c->pk;
+// The fp32 side of a streamed workspace s (predict under predict_dtype = 1, the gradient calls under gradient_dtype = 1; made by the first
+// such call): the site table of the fp32 copy of W, the range flag, the copy itself (grown when W has grown) and, under an input map, the
+// table rounded to fp32.  Then the copy is made: W may have changed since the last call.  who / who_u8: the caller in the messages.
+struct Ws32 { ChainSite<float>** tab32; int** flag; float** w32; size_t* w32_cap; float** mtab32; int64_t* mtab32_bytes; void (*release)(tnml_ctx*); const char *who, *who_u8; };
+static int workspace32(tnml_ctx* c, StreamWs& s, const Ws32& f, bool mapped, const std::vector<ChainSite<double>>& tab) {
     int rc = 0;
-    if (!c->pk_tab32) rc = ws_alloc(c, s, (void**)&c->pk_tab32, (size_t)c->N * sizeof(ChainSite<float>));
-    if (!rc && !c->pk_flag) {
-        rc = ws_alloc(c, s, (void**)&c->pk_flag, sizeof(int));
-        if (!rc && hipMemsetAsync(c->pk_flag, 0, sizeof(int), c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict: memset failed");
+    if (!*f.tab32) rc = ws_alloc(c, s, (void**)f.tab32, (size_t)c->N * sizeof(ChainSite<float>));
+    if (!rc && !*f.flag) {
+        rc = ws_alloc(c, s, (void**)f.flag, sizeof(int));
+        if (!rc && hipMemsetAsync(*f.flag, 0, sizeof(int), c->stream) != hipSuccess) rc = tnml_fail(c, "%s: memset failed", f.who);
     }
     std::vector<size_t> off(c->N);
     size_t total = 0, largest = 0;
@@ -327,31 +329,34 @@ static int predict_workspace32(tnml_ctx* c, bool mapped, const std::vector<Chain
         const size_t e = (size_t)2 * tab[j - 1].ml * tab[j - 1].mr * (j == c->c0 ? c->nl() : 1);
         off[j - 1] = total; total += (e + 3) / 4 * 4; largest = std::max(largest, e);
     }
-    if (!rc && total > c->pk_w32_cap) {
-        if (c->pk_w32) {
-            if (hipStreamSynchronize(c->stream) != hipSuccess) return tnml_fail(c, "tnml_predict: hipStreamSynchronize failed");
-            (void)hipFree(c->pk_w32); c->pk_w32 = nullptr;
-            c->bytes -= (int64_t)(c->pk_w32_cap * sizeof(float)); s.bytes -= (int64_t)(c->pk_w32_cap * sizeof(float)); c->pk_w32_cap = 0;
+    if (!rc && total > *f.w32_cap) {
+        if (*f.w32) {
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return tnml_fail(c, "%s: hipStreamSynchronize failed", f.who);
+            (void)hipFree(*f.w32); *f.w32 = nullptr;
+            c->bytes -= (int64_t)(*f.w32_cap * sizeof(float)); s.bytes -= (int64_t)(*f.w32_cap * sizeof(float)); *f.w32_cap = 0;
         }
-        rc = ws_alloc(c, s, (void**)&c->pk_w32, total * sizeof(float));
-        if (!rc) c->pk_w32_cap = total;
+        rc = ws_alloc(c, s, (void**)f.w32, total * sizeof(float));
+        if (!rc) *f.w32_cap = total;
     }
-    if (!rc && mapped && !c->pk_mtab32) {
+    if (!rc && mapped && !*f.mtab32) {
         std::vector<float> t32(c->im_table.size());
         for (size_t k = 0; k < t32.size(); ++k) t32[k] = (float)c->im_table[k];
         const int64_t before = s.bytes;
-        rc = ws_alloc(c, s, (void**)&c->pk_mtab32, t32.size() * sizeof(float));
-        if (!rc) c->pk_mtab32_bytes = s.bytes - before;
-        if (!rc && hipMemcpyAsync(c->pk_mtab32, t32.data(), t32.size() * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict_u8: copy of the input map's table failed");
-        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "tnml_predict_u8: hipStreamSynchronize failed");
+        rc = ws_alloc(c, s, (void**)f.mtab32, t32.size() * sizeof(float));
+        if (!rc) *f.mtab32_bytes = s.bytes - before;
+        if (!rc && hipMemcpyAsync(*f.mtab32, t32.data(), t32.size() * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "%s: copy of the input map's table failed", f.who_u8);
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "%s: hipStreamSynchronize failed", f.who_u8);
     }
-    if (rc) { predict_release(c); return rc; }
+    if (rc) { f.release(c); return rc; }
     std::vector<ChainSite<float>> t32(c->N);
-    for (int j = 1; j <= c->N; ++j) t32[j - 1] = ChainSite<float>{c->pk_w32 + off[j - 1], tab[j - 1].ml, tab[j - 1].mr};
-    HIPCK(c, hipMemcpyAsync(c->pk_tab32, t32.data(), sizeof(ChainSite<float>) * c->N, hipMemcpyHostToDevice, c->stream));
-    TCK(launch_chain_pack32(c, s.tab, c->pk_tab32, c->N, c->c0, c->nl(), largest));
+    for (int j = 1; j <= c->N; ++j) t32[j - 1] = ChainSite<float>{*f.w32 + off[j - 1], tab[j - 1].ml, tab[j - 1].mr};
+    HIPCK(c, hipMemcpyAsync(*f.tab32, t32.data(), sizeof(ChainSite<float>) * c->N, hipMemcpyHostToDevice, c->stream));
+    TCK(launch_chain_pack32(c, s.tab, *f.tab32, c->N, c->c0, c->nl(), largest));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (t32 leaves scope with this call)
     return 0;
+}
+static int predict_workspace32(tnml_ctx* c, bool mapped, const std::vector<ChainSite<double>>& tab) {
+    return workspace32(c, c->pk, Ws32{&c->pk_tab32, &c->pk_flag, &c->pk_w32, &c->pk_w32_cap, &c->pk_mtab32, &c->pk_mtab32_bytes, predict_release, "tnml_predict", "tnml_predict_u8"}, mapped, tab);
 }
 // the chunk loop of predict_impl in the element type E of option predict_dtype: per chunk stage (map, bytes or phi), ONE chain launch, copy back;
 // labels (tnml_evaluate_*): the chunk's labels are staged with its images and ONE k_eval_tally launch behind the chain adds its tallies to pk_acc
@@ -529,12 +534,22 @@ int tnml_response_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* 
 // Per chunk of option gradient_chunk ONE k_site_backward launch walks the chain inward and outward and leaves two tapes, ONE k_site_grad
 // launch adds the chunk's outer products to the gradient, which stays on the device until the last chunk and is copied back once.
 // rows: the rows of a workgroup's tape slice that W asks for now; elems: the elements of the gradient of W as it is now
-static int sitegrad_workspace(tnml_ctx* c, const char* who, bool bytes_form, size_t rows, size_t elems, bool dev) {
+// f32 (option gradient_dtype = 1): the tapes hold floats -- a change of the option frees the two tapes and makes them again in the new
+// element size, and touches nothing else --, the site-first features of the phi form are the fp32 ones (sg_xphi32); the fp32 copy of W
+// follows in workspace32
+static int sitegrad_workspace(tnml_ctx* c, const char* who, bool bytes_form, size_t rows, size_t elems, bool dev, bool f32) {
     StreamWs& s = c->sg;
     const int nl = c->nl();
     bool fresh;
     int rc = ws_remake(c, s, c->gradient_chunk, sitegrad_release, &fresh);
-    const size_t cap = s.cap;
+    const size_t cap = s.cap, esz = f32 ? sizeof(float) : sizeof(double);
+    if (!rc && c->sg_tape_rows && (size_t)c->sg_esz != esz) {
+        if (hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "%s: hipStreamSynchronize failed", who);
+        for (double** p : {&c->sg_tape, &c->sg_tape2})
+            if (*p) { (void)hipFree(*p); *p = nullptr; c->bytes -= (int64_t)(c->sg_tape_rows * cap * c->sg_esz); s.bytes -= (int64_t)(c->sg_tape_rows * cap * c->sg_esz); }
+        c->sg_tape_rows = 0;
+    }
+    c->sg_esz = (int)esz;
     if (!rc && fresh) {
         rc = ws_alloc(c, s, (void**)&c->sg_coef, cap * nl * sizeof(double));
         if (!rc) rc = ws_alloc(c, s, (void**)&c->sg_lab, cap * sizeof(int));
@@ -542,9 +557,10 @@ static int sitegrad_workspace(tnml_ctx* c, const char* who, bool bytes_form, siz
         if (!rc) rc = ws_alloc(c, s, (void**)&c->sg_goff, (size_t)(c->N + 1) * sizeof(long long));
         if (!rc) rc = ws_alloc(c, s, (void**)&c->sg_blk0, (size_t)(c->N + nl) * sizeof(int));
     }
-    if (!rc) rc = ws_grow(c, s, rows, &c->sg_tape_rows, cap * sizeof(double), {&c->sg_tape, &c->sg_tape2});
+    if (!rc) rc = ws_grow(c, s, rows, &c->sg_tape_rows, cap * esz, {&c->sg_tape, &c->sg_tape2});
     if (!rc) rc = ws_grow(c, s, elems, &c->sg_grad_elems, sizeof(double), {&c->sg_grad});
-    if (!rc) rc = ws_staging(c, s, who, bytes_form, true, dev);
+    if (!rc) rc = ws_staging(c, s, who, bytes_form, !f32, dev);
+    if (!rc && !bytes_form && f32 && !c->sg_xphi32) rc = ws_alloc(c, s, (void**)&c->sg_xphi32, (size_t)2 * cap * c->N * sizeof(float));
     if (rc) sitegrad_release(c);
     return rc;
 }
@@ -582,6 +598,69 @@ static int sitegrad_inputs(tnml_ctx* c, const char* who, int64_t n, const uint8_
             if (!std::isfinite(coef[i])) return tnml_fail(c, "%s: coefficient %d of image %lld is not finite", who, (int)(i % nl), (long long)(i / nl));
     return 0;
 }
+// the chunk loop of sitegrad_device in the element type E of option gradient_dtype; the tables are on the device
+struct SiteGradCall {
+    const char* who; int64_t n; const uint8_t* pixels; const double* phi; const int32_t* labels; const double* coef; double* weights; int32_t* pred;
+    EvalAcc* acc; double* dphi; bool want_grad; int maxbond, rows, nblocks;
+};
+template <typename E>
+static int sitegrad_chunks(tnml_ctx* c, const SiteGradCall& k, StreamIO& io) {
+    constexpr bool f32 = sizeof(E) == sizeof(float);
+    const StreamWs& s = c->sg;
+    const int N = c->N, nl = c->nl(), cs = c->single() ? 1 : c->c0;
+    const bool bytes_form = k.pixels != nullptr, want_dphi = k.dphi || io.dphi32;
+    const bool mapped = bytes_form && c->im_set;
+    const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
+    SiteGradArgsT<E> a;
+    E* xphi; const ChainSite<E>* sites;
+    if constexpr (f32) {                                           // the copy of W, the features and the table rounded to fp32; the range flag
+        xphi = c->sg_xphi32; sites = c->sg_tab32;
+        chain_args(c, s, sites, bytes_form, (const float*)c->sg_mtab32, (const float*)xphi, a.ch);
+        a.ch.flag = c->sg_flag;
+    } else {
+        xphi = s.xphi; sites = s.tab;
+        chain_args(c, s, sites, bytes_form, (const double*)s.mtab, (const double*)xphi, a.ch);
+    }
+    a.rowoff = c->sg_rowoff; a.tape = (E*)c->sg_tape; a.tape2 = (E*)c->sg_tape2;
+    a.lab = k.labels ? c->sg_lab : nullptr; a.target = c->target(); a.coef = c->sg_coef;
+    a.grad = c->sg_grad; a.goff = c->sg_goff; a.blk0 = c->sg_blk0;
+    a.loss = k.labels ? c->loss : TNML_LOSS_QUADRATIC; a.beta = c->loss_beta;      // (coefficients as given know no loss)
+    const size_t tape_elems = c->sg_tape_rows * (size_t)s.cap;
+    for (int64_t off = 0; off < k.n; off += c->gradient_chunk) {
+        a.ch.cnt = (int)std::min<int64_t>(c->gradient_chunk, k.n - off);
+        TCK(stage_chunk<E>(c, s, mapped, sg, k.pixels, k.phi, off, a.ch.cnt, xphi, io));
+        chunk_dest(c, s, io, off, k.weights, k.pred, &a.ch.wout, &a.ch.pred);
+        if (k.labels) HIPCK(c, hipMemcpyAsync(c->sg_lab, k.labels + off, sizeof(int32_t) * (size_t)a.ch.cnt, io.in(), c->stream));
+        else          HIPCK(c, hipMemcpyAsync(c->sg_coef, k.coef + (size_t)off * nl, sizeof(double) * (size_t)a.ch.cnt * nl, io.in(), c->stream));
+        const int T = chain_tile<E>(c, k.maxbond, a.ch.cnt);
+        TCK(launch_site_gradient<E>(c, a, k.maxbond, T, k.rows, tape_elems, k.nblocks, k.want_grad));
+        if constexpr (f32) {                                       // the range flag, before anything of the chunk reaches the caller
+            int flag = 0;
+            HIPCK(c, hipMemcpyAsync(&flag, c->sg_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            SYNCK(c, c->stream);
+            if (flag) {
+                HIPCK(c, hipMemsetAsync(c->sg_flag, 0, sizeof(int), c->stream));
+                HIPCK(c, hipStreamSynchronize(c->stream));
+                return tnml_fail(c, "%s: gradient_dtype = 1 (fp32): a weight of images %lld..%lld is not finite, the chain has left the fp32 range: use fp64 (gradient_dtype = 0)", k.who, (long long)off, (long long)off + a.ch.cnt - 1);
+            }
+        }
+        if (want_dphi) {
+            InputGradArgsT<E> ig;
+            ig.sites = sites; ig.N = N; ig.cs = cs; ig.nl = nl; ig.ld = s.cap; ig.cnt = a.ch.cnt;
+            ig.rowoff = c->sg_rowoff; ig.tape = (const E*)c->sg_tape; ig.tape2 = (const E*)c->sg_tape2; ig.coef = c->sg_coef; ig.dphi = c->bw_out;
+            const size_t at = (size_t)off * N * 2;
+            if (io.dev) TCK(launch_input_grad<E>(c, ig, k.maxbond, T, k.rows, tape_elems, k.dphi ? k.dphi + at : nullptr, k.dphi ? nullptr : io.dphi32 + at));
+            else {
+                TCK(launch_input_grad<E>(c, ig, k.maxbond, T, k.rows, tape_elems, c->bw_outT));
+                HIPCK(c, hipMemcpyAsync(k.dphi + at, c->bw_outT, sizeof(double) * (size_t)a.ch.cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
+            }
+        }
+        if (k.acc && k.labels) TCK(launch_eval_tally(c, a.ch.wout, a.ch.pred, c->sg_lab, a.ch.cnt, nl, a.ch.single, c->target(), k.acc, c->loss, c->loss_beta));
+        c->sg_last_cnt = a.ch.cnt;
+        TCK(chunk_results(c, s, off, a.ch.cnt, k.weights, k.pred, io.dev));
+    }
+    return 0;
+}
 // The part the gradient calls and the step calls share: refusals, staging, tables and the chunk loop.  It leaves the gradient of the n
 // images in c->sg_grad (*elems of them) with the stream synchronised behind the last chunk; n = 0: nothing is launched, *elems alone is
 // set.  out: where the caller's result goes (refused when null).  acc (tnml_site_step_* in the labels mode): a device accumulator
@@ -593,7 +672,7 @@ static int sitegrad_inputs(tnml_ctx* c, const char* who, int64_t n, const uint8_
 static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
                            const void* out, double* weights, int32_t* pred, size_t* elems_out, EvalAcc* acc, double* dphi, bool want_grad, StreamIO& io, double* grad) {
     int maxbond = 1;
-    TCK(streamed_refusals(c, who, "site gradients", n, &maxbond));
+    TCK(streamed_refusals(c, who, "site gradients", n, &maxbond, true));
     if (!out) return tnml_fail(c, "%s: null argument", who);
     const int N = c->N, nl = c->nl(), cs = c->single() ? 1 : c->c0;
     if (c->W[cs].L != nl) return tnml_fail(c, "%s: the Label site %d of W carries %d labels, the context has %d", who, cs, c->W[cs].L, nl);
@@ -615,8 +694,8 @@ static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_
         for (int l = 0; l < (j == cs ? nl : 1); ++l) { blk0[v++] = nblocks; nblocks += nb; }
     }
     blk0[v] = nblocks;
-    const bool bytes_form = pixels != nullptr;
-    TCK(sitegrad_workspace(c, who, bytes_form, (size_t)rows, elems, io.dev));
+    const bool bytes_form = pixels != nullptr, f32 = c->gradient_dtype == TNML_GRADIENT_F32;
+    TCK(sitegrad_workspace(c, who, bytes_form, (size_t)rows, elems, io.dev, f32));
     if (want_dphi) {                                            // the first call that asks for dphi: the result as the kernel leaves it and as a host caller gets it
         int rc = 0;
         if (!c->bw_out) rc = ws_alloc(c, c->sg, (void**)&c->bw_out, (size_t)2 * N * s.cap * sizeof(double));
@@ -631,39 +710,9 @@ static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_
     HIPCK(c, hipMemsetAsync(c->sg_grad, 0, elems * sizeof(double), c->stream));       // the sum starts from zero: grad is overwritten
     if (acc) HIPCK(c, hipMemsetAsync(acc, 0, sizeof(EvalAcc), c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (the tables leave scope with this call)
-    const bool mapped = bytes_form && c->im_set;
-    const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
-    SiteGradArgs a;
-    chain_args(c, s, s.tab, bytes_form, s.mtab, s.xphi, a.ch);
-    a.rowoff = c->sg_rowoff; a.tape = c->sg_tape; a.tape2 = c->sg_tape2;
-    a.lab = labels ? c->sg_lab : nullptr; a.target = c->target(); a.coef = c->sg_coef;
-    a.grad = c->sg_grad; a.goff = c->sg_goff; a.blk0 = c->sg_blk0;
-    a.loss = labels ? c->loss : TNML_LOSS_QUADRATIC; a.beta = c->loss_beta;      // (coefficients as given know no loss)
-    const size_t tape_elems = c->sg_tape_rows * (size_t)s.cap;
-    for (int64_t off = 0; off < n; off += c->gradient_chunk) {
-        a.ch.cnt = (int)std::min<int64_t>(c->gradient_chunk, n - off);
-        TCK(stage_chunk<double>(c, s, mapped, sg, pixels, phi, off, a.ch.cnt, s.xphi, io));
-        chunk_dest(c, s, io, off, weights, pred, &a.ch.wout, &a.ch.pred);
-        if (labels) HIPCK(c, hipMemcpyAsync(c->sg_lab, labels + off, sizeof(int32_t) * (size_t)a.ch.cnt, io.in(), c->stream));
-        else        HIPCK(c, hipMemcpyAsync(c->sg_coef, coef + (size_t)off * nl, sizeof(double) * (size_t)a.ch.cnt * nl, io.in(), c->stream));
-        const int T = chain_tile<double>(c, maxbond, a.ch.cnt);
-        TCK(launch_site_gradient(c, a, maxbond, T, rows, tape_elems, nblocks, want_grad));
-        if (want_dphi) {
-            InputGradArgs ig;
-            ig.sites = s.tab; ig.N = N; ig.cs = cs; ig.nl = nl; ig.ld = s.cap; ig.cnt = a.ch.cnt;
-            ig.rowoff = c->sg_rowoff; ig.tape = c->sg_tape; ig.tape2 = c->sg_tape2; ig.coef = c->sg_coef; ig.dphi = c->bw_out;
-            const size_t at = (size_t)off * N * 2;
-            if (io.dev) TCK(launch_input_grad(c, ig, maxbond, T, rows, tape_elems, dphi ? dphi + at : nullptr, dphi ? nullptr : io.dphi32 + at));
-            else {
-                TCK(launch_input_grad(c, ig, maxbond, T, rows, tape_elems, c->bw_outT));
-                HIPCK(c, hipMemcpyAsync(dphi + at, c->bw_outT, sizeof(double) * (size_t)a.ch.cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
-            }
-        }
-        if (acc && labels) TCK(launch_eval_tally(c, a.ch.wout, a.ch.pred, c->sg_lab, a.ch.cnt, nl, a.ch.single, c->target(), acc, c->loss, c->loss_beta));
-        c->sg_last_cnt = a.ch.cnt;
-        TCK(chunk_results(c, s, off, a.ch.cnt, weights, pred, io.dev));
-    }
-    return 0;
+    if (f32) TCK(workspace32(c, c->sg, Ws32{&c->sg_tab32, &c->sg_flag, &c->sg_w32, &c->sg_w32_cap, &c->sg_mtab32, &c->sg_mtab32_bytes, sitegrad_release, who, who}, bytes_form && c->im_set, tab));
+    const SiteGradCall k{who, n, pixels, phi, labels, coef, weights, pred, acc, dphi, want_grad, maxbond, rows, nblocks};
+    return f32 ? sitegrad_chunks<float>(c, k, io) : sitegrad_chunks<double>(c, k, io);
 }
 static int sitegrad_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
                          double* grad, double* weights, int32_t* pred) {
@@ -794,7 +843,7 @@ static int step_check_params(tnml_ctx* c, const char* who, const tnml_step_param
 static int sitestep_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
                          const tnml_step_params* p, tnml_step_report* rep, StreamIO io = StreamIO()) {
     int maxbond = 1;
-    TCK(streamed_refusals(c, who, "site gradients", n, &maxbond));
+    TCK(streamed_refusals(c, who, "site gradients", n, &maxbond, true));
     TCK(ho_locked(c, who, true));                               // as tnml_set_site: W of a training context with a held-out context attached changes in bond updates only
     if (c->cfg.nranks != 1) return tnml_fail(c, "%s: the context is rank %d of %d: a step enters no collective, the replicas of W would part (one rank only)", who, c->cfg.rank, c->cfg.nranks);
     TCK(step_check_params(c, who, p));

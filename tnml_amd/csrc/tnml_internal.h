@@ -343,8 +343,19 @@ struct tnml_ctx {
     double* rs_tape = nullptr; size_t rs_tape_rows = 0;    // [cap / T][rs_tape_rows][T]: every chain vector of every image; grown when W has grown
     // streamed site gradients (tnml_site_gradient_u8 / tnml_site_gradient_phi, kernels_sitegrad.hip)
     int gradient_chunk = TNML_GRADIENT_CHUNK_DEFAULT;      // option "gradient_chunk": images per launch of k_site_backward / k_site_grad
-    bool attr_sitegrad[2] = {};      // [input map]: the LDS attribute of those k_site_backward instantiations is set
-    bool attr_sitegrad_sm[2] = {};   // the same for the instantiations of the softmax loss
+    bool attr_sitegrad[2][2] = {};   // [fp32][input map]: the LDS attribute of those k_site_backward instantiations is set
+    bool attr_sitegrad_sm[2][2] = {};   // the same for the instantiations of the softmax loss
+    // option "gradient_dtype": 0 the gradient kernels in fp64 on W where it lives, 1 their float instantiations on an fp32 copy of W
+    // (kernels_sitegrad.hip, kernels_inputgrad.hip).  The tapes hold elements of sg_esz bytes and are re-made when the option changes; the
+    // fp32 side of the workspace `sg` -- the copy of W (re-made by every call, grown when W has grown), its site table, the range flag
+    // and what the staging of the input form needs -- is made by the first fp32 call and released with the workspace
+    int gradient_dtype = 0;
+    int sg_esz = 8;
+    float* sg_w32 = nullptr; size_t sg_w32_cap = 0;
+    ChainSite<float>* sg_tab32 = nullptr;
+    int* sg_flag = nullptr;
+    float* sg_xphi32 = nullptr;                            // features of a chunk site-first [N][2][sg.cap], rounded to fp32
+    float* sg_mtab32 = nullptr; int64_t sg_mtab32_bytes = 0;   // the input map's table rounded to fp32
     int loss = TNML_LOSS_QUADRATIC;  // option "loss": the loss of tnml_evaluate_* and of the labels mode of tnml_site_gradient_* / tnml_site_step_*
     double loss_beta = 1.;           // tnml_set_option_real "loss_beta": the inverse temperature of the softmax loss, logits beta W_l
     int sg_last_cnt = -1;            // images of the last chunk a gradient or step call ran in this workspace (tnml_site_gradient_coef); -1: none yet
@@ -357,7 +368,7 @@ struct tnml_ctx {
     // streamed input gradients (tnml_backward_u8 / tnml_backward_phi, kernels_inputgrad.hip): the gradient workspace `sg` and, from the first call
     // that asks for dphi on, two buffers of their own, counted in sg.bytes and released with it
     double *bw_out = nullptr, *bw_outT = nullptr;          // dphi of a chunk as the kernel leaves it [N][2][cap] and as the caller gets it [cap][N][2]
-    bool attr_inputgrad = false;     // the LDS attribute of the k_input_grad instantiations is set
+    bool attr_inputgrad[2] = {};     // [fp32]: the LDS attribute of the k_input_grad instantiations is set
     // gradient steps on the device (tnml_site_step_u8 / tnml_site_step_phi, kernels_sitestep.hip): the optimiser state.  Allocated by the first
     // step for a method and the site shapes of W at that moment, counted in `bytes` and st_bytes, freed by tnml_site_step_reset and tnml_destroy;
     // no part of `sg`: a change of gradient_chunk and tnml_set_input_map leave it alone
@@ -651,37 +662,40 @@ int launch_response(tnml_ctx* c, RespArgs a, int maxbond, int T, int rows, size_
 int launch_response_transpose(tnml_ctx* c, const double* in, int rows, int cnt, int ld, double* out, float* out32 = nullptr);
 
 // ---- kernels_sitegrad.hip: streamed site gradients, k_site_backward (two walks, two tapes) and k_site_grad (the GEMM over the image index) ----
-struct SiteGradArgs {
-    ChainArgs<double> ch;              // sites, sources, ld, cnt, wout, pred as k_chain takes them (park and flag unused)
+// E: the element type of option gradient_dtype -- double on W where it lives, float on its fp32 copy (ch.flag is then the range flag)
+template <typename E> struct SiteGradArgsT {
+    ChainArgs<E> ch;                   // sites, sources, ld, cnt, wout, pred as k_chain takes them (park unused; flag: fp32 only)
     const int* rowoff;                 // [N + 2] device: first row of the tape region of bond b = 0..N, then the rows of a slice
-    double* tape;                      // [grid][rows][T] inward vectors
-    double* tape2;                     // [grid][rows][T] outward vectors
+    E* tape;                           // [grid][rows][T] inward vectors
+    E* tape2;                          // [grid][rows][T] outward vectors
     const int* lab; int target;        // labels of the chunk (coef is then written: c_nl = 2 (W_l - y_nl)) or null (coef is read); the per-label variant's target
-    double* coef;                      // [ld][nl]
-    double* grad;                      // every site in tnml_get_site's layout, site j at goff[j - 1]
+    double* coef;                      // [ld][nl] (fp32: fp32 values widened where the kernel formed them)
+    double* grad;                      // every site in tnml_get_site's layout, site j at goff[j - 1]; fp64 under either element type
     const long long* goff;             // [N + 1] device
     const int* blk0;                   // [N + nl] device: first output block of every virtual site (sites in order, the Label site once per label), then the block count
     int loss = 0; double beta = 1.;    // labels mode: TNML_LOSS_SOFTMAX forms coef by loss_dev.h with the logits beta W_l (k_site_backward<.., .., 1>)
 };
-// rows: rowoff[N + 1] as the host knows it; tape_elems: doubles behind each tape; nblocks: the block count; classes site_bwd, site_grad
+typedef SiteGradArgsT<double> SiteGradArgs;
+// rows: rowoff[N + 1] as the host knows it; tape_elems: elements behind each tape; nblocks: the block count; classes site_bwd, site_grad
 // run_gemm false (tnml_backward_* without grad): k_site_backward alone
-int launch_site_gradient(tnml_ctx* c, SiteGradArgs a, int maxbond, int T, int rows, size_t tape_elems, int nblocks, bool run_gemm = true);
+template <typename E> int launch_site_gradient(tnml_ctx* c, SiteGradArgsT<E> a, int maxbond, int T, int rows, size_t tape_elems, int nblocks, bool run_gemm = true);
 
 // ---- kernels_inputgrad.hip: streamed input gradients, one bilinear form per site, feature component and image on the tapes of k_site_backward ----
-struct InputGradArgs {
-    const ChainSite<double>* sites;    // [N] device
+template <typename E> struct InputGradArgsT {
+    const ChainSite<E>* sites;         // [N] device
     int N, cs, nl, ld, cnt;            // as ChainArgs has them
     const int* rowoff;                 // [N + 2] device: the region table of the two tapes
-    const double* tape;                // [grid][rows][T] inward vectors, as k_site_backward left them for this chunk
-    const double* tape2;               // [grid][rows][T] outward vectors
+    const E* tape;                     // [grid][rows][T] inward vectors, as k_site_backward<E> left them for this chunk
+    const E* tape2;                    // [grid][rows][T] outward vectors
     const double* coef;                // [ld][nl]: given, or formed by k_site_backward
-    double* dphi;                      // [N][2][ld]
+    double* dphi;                      // [N][2][ld] (fp32: the fp32 results widened)
     int mcap = 0;                      // set by launch_input_grad
 };
+typedef InputGradArgsT<double> InputGradArgs;
 // T: the tile width k_site_backward ran this chunk with; rows: rowoff[N + 1] as the host knows it; outT [cnt][N][2] receives the transposed
 // a.dphi; class input_grad (the transposing copy: class pack)
 // outT32 (outT is then null): the transposed a.dphi rounded once to fp32
-int launch_input_grad(tnml_ctx* c, InputGradArgs a, int maxbond, int T, int rows, size_t tape_elems, double* outT, float* outT32 = nullptr);
+template <typename E> int launch_input_grad(tnml_ctx* c, InputGradArgsT<E> a, int maxbond, int T, int rows, size_t tape_elems, double* outT, float* outT32 = nullptr);
 
 // ---- kernels_iocheck.hip: the value checks of the device-resident calls ----
 // ONE launch over labels [n], coef [n][nl] and which [n] (any may be null): blk[0..2], all ones before the launch, receive the smallest

@@ -4,6 +4,8 @@
 Keys of the `input` group: datadir, Ntrain, Ntest, imglen, feature_scale, input_map as tnml_amd.train reads them (the images reach the
 device in the form train.py takes for heldout = stream); infile (W) and outfile (W_ft); epochs (1), batch (256), optimizer = sgd | adam
 (adam), lr, momentum, beta1, beta2, eps, clip; loss = quadratic | softmax (softmax), loss_beta (1); seed (1); log (none);
+gradient_dtype = f64 | f32 (f64): the arithmetic of the gradient of every step (option gradient_dtype; f32: an fp32 gradient on the fp64
+master W and optimiser state, bonds up to 1 024), named in the "Device path" line;
 device_data = yes | no (no): with yes the training images and labels are uploaded once as torch tensors, every mini-batch is gathered
 on the device and every step goes through tnml_site_step_dev, so that no image crosses the bus after the upload.  The numbers of a
 run do not depend on the key; with yes one more line is printed, which says so.
@@ -70,6 +72,7 @@ def _run(inp):
     optimizer = choice("optimizer", "adam", ("sgd", "adam"))
     loss = choice("loss", "softmax", ("quadratic", "softmax"))
     loss_beta = key("loss_beta", 1.0, float)
+    gradient_dtype = choice("gradient_dtype", "f64", ("f64", "f32"))
     lr = key("lr", None, float)
     par = dict(method=optimizer, lr=lr, momentum=key("momentum", 0.0, float), beta1=key("beta1", 0.9, float), beta2=key("beta2", 0.999, float),
                eps=key("eps", 1e-8, float), clip=key("clip", 0.0, float))
@@ -122,6 +125,7 @@ def _run(inp):
     try:
         ts.set_mps(W)
         ts.set_loss(loss, loss_beta)
+        print("Device path: gradient steps on the device (tnml_site_step_%s), gradient_dtype = %s" % ("u8" if form == "pixels" else "phi", gradient_dtype), flush=True)
 
         def say_heldout():
             e = ts.evaluate(tlab, **{form: held})
@@ -143,9 +147,9 @@ def _run(inp):
                 rows = perm[at:at + batch]
                 if device_data:
                     idx = torch.from_numpy(rows).to(dev)
-                    rep = ts.gradient_step(labels=lab_d[idx], scale=1.0 / len(rows), **{form: train_d[idx]}, **par)
+                    rep = ts.gradient_step(labels=lab_d[idx], scale=1.0 / len(rows), **{form: train_d[idx]}, dtype=gradient_dtype, **par)
                 else:
-                    rep = ts.gradient_step(labels=lab[rows], scale=1.0 / len(rows), **{form: train[rows]}, **par)
+                    rep = ts.gradient_step(labels=lab[rows], scale=1.0 / len(rows), **{form: train[rows]}, dtype=gradient_dtype, **par)
                 step += 1
                 cost += rep.eval.cost / len(rows)
                 clipped += int(rep.clipped)

@@ -190,6 +190,12 @@ class TrainStates:
             self._gchunk = int(value)
         elif name == "loss":
             self._loss = {v: k for k, v in _lib.LOSSES.items()}[int(value)]
+        elif name in ("predict_dtype", "gradient_dtype"):
+            self._dtypes = dict(getattr(self, "_dtypes", {}), **{name: int(value)})
+
+    def get_dtype_option(self, name):
+        """the value set_option() last gave "predict_dtype" or "gradient_dtype" on this object (0, the library's default, before any)"""
+        return getattr(self, "_dtypes", {}).get(name, 0)
 
     def set_loss(self, loss="quadratic", beta=1.0):
         """options loss and loss_beta: the loss of evaluate() and of the labels mode of site_gradient() / gradient_step().
@@ -507,14 +513,18 @@ class TrainStates:
             self._ck(self._L.tnml_response_phi(self._h, n, _lib.dptr(x), wp_, _lib.dptr(resp), wp, pp))
         return (resp, (w, pred)) if want_weights else resp
 
-    def site_gradient(self, labels=None, coef=None, pixels=None, phi=None, want_weights=False):
+    def site_gradient(self, labels=None, coef=None, pixels=None, phi=None, want_weights=False, dtype=None):
         """streamed site gradients (tnml_site_gradient_u8 / tnml_site_gradient_phi) on images this context does not hold, in the input
         forms of predict(): a list of N arrays shaped like get_site()'s, G_j = sum_n sum_l c[n, l] dW_l(x_n)/dA_j.  Exactly one of
         coef[n, nl] (c as given) and labels[n] (c = 2 (W - y) with the targets of evaluate(): the gradient of the cost evaluate()
         reports).  With want_weights (grads, (weights[n, nl], pred[n])), both bit for bit those of predict() in fp64.  Reads W only;
         fp64 only (refused under predict_dtype = 1).
         Under set_loss("softmax") the labels mode forms c = beta (softmax(beta W) - y) on the device instead: the gradient of the
-        cross-entropy evaluate() then reports.  The coef mode does not know the loss."""
+        cross-entropy evaluate() then reports.  The coef mode does not know the loss.
+        dtype "f64" / "f32" sets option gradient_dtype for this call and the ones after it (None: as it is).  "f32": the fp32 gradient
+        kernels on an fp32 copy of W, bonds up to 1 024; weights and pred are then those of predict(dtype="f32"), the sum over a chunk's
+        images is fp32, the sum over chunks fp64."""
+        self._gradient_dtype(dtype)
         if self._on_device(pixels, phi, labels, coef):
             r = self._backward_dev(labels, coef, pixels, phi, True, False, want_weights)
             return (r[0], r[2]) if want_weights else r[0]
@@ -553,14 +563,17 @@ class TrainStates:
         self._note_chunk(n)
         return (grads, (w, pred)) if want_weights else grads
 
-    def backward(self, labels=None, coef=None, pixels=None, phi=None, want_sites=True, want_inputs=True, want_weights=False):
+    def backward(self, labels=None, coef=None, pixels=None, phi=None, want_sites=True, want_inputs=True, want_weights=False, dtype=None):
         """streamed backward pass (tnml_backward_u8 / tnml_backward_phi) in the input forms and the labels / coef rule of
         site_gradient(): -> (grads | None, dphi | None[, (weights, pred)]).  grads (want_sites) is site_gradient()'s list, bit for
         bit; dphi[n, N, 2] (want_inputs) is the gradient with respect to the features, dphi[n, j, s] = sum_l c[n, l] dW_l(x_n)/dphi[n, j, s]
         (under an input map: the features of the N reduced sites).  Without want_sites the gradient GEMM is not launched.  At least
         one of the two must be asked for.  Reads W only; fp64 only.
         Device tensors (every array argument a torch tensor on the context's device; tnml_backward_dev): grads are strided views
-        of one flat device buffer, dphi a device tensor in phi's dtype (float32 phi: the fp64 result rounded once)."""
+        of one flat device buffer, dphi a device tensor in phi's dtype (float32 phi: the fp64 result rounded once).
+        dtype: as site_gradient()'s.  Under "f32" every dphi value is an fp32 number (widened exactly; a float32 dphi is rounded no
+        second time)."""
+        self._gradient_dtype(dtype)
         if self._on_device(pixels, phi, labels, coef):
             return self._backward_dev(labels, coef, pixels, phi, want_sites, want_inputs, want_weights)
         x = self._streamed_input(pixels, phi, None)
@@ -598,6 +611,13 @@ class TrainStates:
         self._note_chunk(n)
         return (grads, dphi, (w, pred)) if want_weights else (grads, dphi)
 
+    def _gradient_dtype(self, dtype):
+        """dtype (when given) becomes option gradient_dtype, for this call and the ones after it, as predict(dtype=...) sets predict_dtype"""
+        if dtype is not None:
+            if dtype not in _lib.GRADIENT_DTYPES:
+                raise ValueError("dtype must be one of %s, got %r" % (sorted(_lib.GRADIENT_DTYPES), dtype))
+            self.set_option("gradient_dtype", _lib.GRADIENT_DTYPES[dtype])
+
     def _note_chunk(self, n):
         """the size of the last chunk of a gradient or step call on n images (gradient_coef)"""
         if n > 0:
@@ -629,14 +649,16 @@ class TrainStates:
         return out
 
     def gradient_step(self, labels=None, coef=None, pixels=None, phi=None, method="sgd", lr=None, momentum=0., beta1=.9, beta2=.999,
-                      eps=1e-8, clip=0., scale=1.):
+                      eps=1e-8, clip=0., scale=1., dtype=None):
         """one optimiser step on W on the device (tnml_site_step_u8 / tnml_site_step_phi): the gradient of site_gradient() on the same
         arguments, summed as site_gradient() sums it, multiplied by scale, clipped to the norm clip (0: not), then
         method "sgd": v <- momentum v + g, A <- A - lr v, or "adam" with beta1, beta2, eps and bias correction.  Neither the gradient
         nor W crosses the bus; returns a StepReport.  The optimiser state lives on the device, is made by the first step for its
         method and the shapes of W, and goes with step_reset().  Environments are stale afterwards, as after set_mps().
         Under set_loss("softmax") the labels mode takes the gradient of the cross-entropy and the report's eval is evaluate()'s under
-        that loss; the optimiser and the coef mode are the same."""
+        that loss; the optimiser and the coef mode are the same.
+        dtype: as site_gradient()'s.  Under "f32" the step is mixed precision: an fp32 gradient on an fp64 master W and fp64 state."""
+        self._gradient_dtype(dtype)
         if method not in _lib.STEP_METHODS:
             raise ValueError("method must be one of %s, got %r" % (sorted(_lib.STEP_METHODS), method))
         if lr is None:

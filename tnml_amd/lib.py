@@ -18,6 +18,7 @@ DTYPES = {"f32": 0, "f64_e32": 1, "f64": 2, "bf16": 3, "bf16x3": 4}    # TNML_F3
 GRADIENT_CHUNK_DEFAULT = 512             # TNML_GRADIENT_CHUNK_DEFAULT
 LOSSES = {"quadratic": 0, "softmax": 1}    # TNML_LOSS_QUADRATIC / TNML_LOSS_SOFTMAX: option loss
 PREDICT_DTYPES = {"f64": 0, "f32": 1}    # TNML_PREDICT_F64 / TNML_PREDICT_F32: option predict_dtype
+GRADIENT_DTYPES = {"f64": 0, "f32": 1}   # TNML_GRADIENT_F64 / TNML_GRADIENT_F32: option gradient_dtype
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtnml.so")
 

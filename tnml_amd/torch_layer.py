@@ -16,7 +16,11 @@ last upload (an optimiser step, a load_state_dict) is uploaded again before the 
 device-to-device copy (tnml_set_site_dev) from the device.
 
 The two directions on numpy arrays, forward_arrays() and backward_arrays(), are plain functions of a TrainStates: the autograd
-function only converts tensors and calls them."""
+function only converts tensors and calls them.
+
+MPSLayer(.., compute_dtype="f32") computes in float32 (MPSFunction32): the forward runs under option predict_dtype = 1 and the backward
+under gradient_dtype = 1, so that the weights the forward returns are those of the backward's own inward pass, bit for bit.  Both
+options are put back after each call; the default "f64" is the path described above, unchanged."""
 import numpy as np
 import torch
 
@@ -32,6 +36,21 @@ def backward_arrays(ts, phi, grad_output, want_sites, want_inputs=True):
     grads, dphi = ts.backward(coef=np.ascontiguousarray(grad_output, dtype=np.float64), phi=np.ascontiguousarray(phi, dtype=np.float64),
                               want_sites=bool(want_sites), want_inputs=bool(want_inputs))
     return dphi, grads
+
+
+class _option:
+    """with _option(ts, name, value): the context option holds value inside the block and what it held before after it"""
+
+    def __init__(self, ts, name, value):
+        self.ts, self.name, self.value = ts, name, value
+
+    def __enter__(self):
+        self.old = self.ts.get_dtype_option(self.name)
+        self.ts.set_option(self.name, self.value)
+
+    def __exit__(self, *exc):
+        self.ts.set_option(self.name, self.old)
+        return False
 
 
 class MPSFunction(torch.autograd.Function):
@@ -79,6 +98,21 @@ class MPSFunction(torch.autograd.Function):
         return (None, gphi) + gs
 
 
+class MPSFunction32(torch.autograd.Function):
+    """MPSFunction in float32 arithmetic: the same two calls, the forward under predict_dtype = 1 and the backward under
+    gradient_dtype = 1; each option is put back when its call returns, so other users of the context see it as they left it."""
+
+    @staticmethod
+    def forward(ctx, ts, phi, *sites):
+        with _option(ts, "predict_dtype", 1):
+            return MPSFunction.forward(ctx, ts, phi, *sites)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        with _option(ctx.ts, "gradient_dtype", 1):
+            return MPSFunction.backward(ctx, grad_output)
+
+
 class MPSLayer(torch.nn.Module):
     """phi[n, N, 2] -> weights[n, nl] of the MPS the context ts holds.  train_sites=True: `sites`, a ParameterList of fp64
     tensors shaped like get_site()'s, receives gradients and any torch optimiser can step it; False: W is fixed and only phi
@@ -88,10 +122,14 @@ class MPSLayer(torch.nn.Module):
     device parameters in the library's layout (first-index-fastest strides, filled by tnml_get_site_dev), phi is a tensor on that
     device, the optimiser steps on the device and sync_sites() uploads device to device.
     The place of the parameters is fixed when the layer is made: layer.to(...) / .cuda() / .cpu() between host and device is not
-    supported (it would drop the strides the library reads); make a new layer instead."""
+    supported (it would drop the strides the library reads); make a new layer instead.
+    compute_dtype "f64" (the default) or "f32": the arithmetic of both directions (the module's header); the parameters stay fp64."""
 
-    def __init__(self, ts, train_sites=False, device=None):
+    def __init__(self, ts, train_sites=False, device=None, compute_dtype="f64"):
         super().__init__()
+        if compute_dtype not in ("f64", "f32"):
+            raise ValueError("MPSLayer: compute_dtype must be \"f64\" or \"f32\", got %r" % (compute_dtype,))
+        self.compute_dtype = compute_dtype
         self.ts = ts
         self.train_sites = bool(train_sites)
         dev = torch.device(device) if device is not None else None
@@ -117,4 +155,5 @@ class MPSLayer(torch.nn.Module):
 
     def forward(self, phi):
         self.sync_sites()
-        return MPSFunction.apply(self.ts, phi, *(tuple(self.sites) if self.train_sites else ()))
+        fn = MPSFunction32 if self.compute_dtype == "f32" else MPSFunction
+        return fn.apply(self.ts, phi, *(tuple(self.sites) if self.train_sites else ()))
