@@ -284,6 +284,94 @@ def _formula(W, chunk, f32, nl=10):
     return shared + 8 * B * Cc + 4 * W32 + 16 * N + 4 + 16 * N * Cc + 8 * N * Cc
 
 
+def _equal(a, b):
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(_equal(x, y) for x, y in zip(a, b))
+    return np.array_equal(a, b)
+
+
+def test_workspace_life_cycle_across_predict_and_gradient():
+    """One context through fp32 and fp64 calls of the predict and the gradient workspace, two tnml_set_input_map calls and a changed
+    gradient_chunk: N = 8, bond dimension 12, 70 images in chunks of 64 and 6.  Every result is bit for bit what a fresh context
+    returns for that single call (the values themselves are held by the model tests above): the fp32 sides of the two workspaces share
+    nothing and a release leaves nothing stale.  After every step device_bytes() is the sum of what a context that only ever made
+    the predict calls and one that only ever made the gradient calls report at that point, and a context created after this one was
+    destroyed starts at the first one's figure.
+    The map is that of test_f32_under_an_input_map (2 x 2 blocks from (1, 0), row 0 covered by no block, the same random table) on a
+    9 x 4 source, so that it has 4 x 2 = 8 sites: that test's 7 x 6 source makes 9 sites, which a context of N = 8 refuses."""
+    from tnml_amd.input_map import InputMap
+    rng = np.random.default_rng(77)
+    ncodes = 255 * 4 + 1
+    table = np.stack([1. + 0.1 * rng.standard_normal(ncodes), 0.5 * rng.standard_normal(ncodes)], axis=-1)
+    m = InputMap(9, 4, 2, 1, 0, 4, 2, table)
+    assert m.N == 8
+    px = rng.integers(0, 256, (70, m.S), dtype=np.uint8)
+    px[0] = 0
+    px[1] = 255
+    phi = m.features(px)
+    labels = rng.integers(0, 10, 70).astype(np.int32)
+    W = cases.mps_with_dims([1] + [12] * 7 + [1], 5)
+
+    def new():
+        ts = _dataless(W)
+        ts.set_option("predict_chunk", 64)
+        ts.set_option("gradient_chunk", 64)
+        return ts
+
+    def predict32(ts, **images):
+        got = ts.predict(dtype="f32", **images)
+        ts.set_option("predict_dtype", 0)                                             # (the gradient calls refuse predict_dtype = 1)
+        return got
+
+    predict_phi = lambda ts: predict32(ts, phi=phi)
+    predict_map = lambda ts: predict32(ts, pixels=px)
+    back32_phi = lambda ts: ts.backward(labels=labels, phi=phi, want_weights=True, dtype="f32")
+    back64_phi = lambda ts: ts.backward(labels=labels, phi=phi, want_weights=True, dtype="f64")
+    back32_map = lambda ts: ts.backward(labels=labels, pixels=px, want_weights=True, dtype="f32")
+    set_map = lambda ts: ts.set_input_map(m)
+    chunk16 = lambda ts: ts.set_option("gradient_chunk", 16)
+    # the steps: (what is done, the set-up a fresh context needs before that single call, which workspace's history it belongs to)
+    steps = [(predict_phi, [], "pk"), (back32_phi, [], "sg"), (back64_phi, [], "sg"), (set_map, None, "both"), (predict_map, [set_map], "pk"),
+             (set_map, None, "both"), (back32_map, [set_map], "sg"), (chunk16, None, "sg"), (back32_map, [set_map, chunk16], "sg"),
+             (predict_map, [set_map], "pk")]
+    # the predict workspace in closed form, as include/tnml.h states it (C = 64, maxm = 12 -> 16 parked rows): the shared part and the
+    # parked vectors, fp32 features given from the host, the fp32 copy of W with its table and flag; under the map the bytes as given,
+    # the block sums and the table in fp64 and fp32
+    W32 = sum((A.size + 3) // 4 * 4 for A in W)
+    pk_phi = (16 * 8 + 8 * 10 * 64 + 4 * 64 + 8 * 16 * 64) + (16 * 8 * 64 + 8 * 8 * 64) + (4 * W32 + 16 * 8 + 4)
+    pk_map = m.S * 64 + 2 * 8 * 64 + 16 * ncodes + 8 * ncodes
+    ts, only = new(), {"pk": new(), "sg": new()}
+    base = ts.device_bytes()
+    start = {k: c.device_bytes() for k, c in only.items()}
+    assert start["pk"] == start["sg"] == base
+    for i, (op, setup, ws) in enumerate(steps):
+        got = op(ts)
+        for k, c in only.items():
+            if ws in (k, "both"):
+                op(c)
+        alive = {k: c.device_bytes() - start[k] for k, c in only.items()}
+        print("step", i, "device bytes", ts.device_bytes() - base, "predict alone", alive["pk"], "gradient alone", alive["sg"])
+        assert ts.device_bytes() - base == alive["pk"] + alive["sg"], i
+        assert alive["pk"] == pk_phi + (pk_map if i in (4, 9) else 0), i                 # in closed form: the second tnml_set_input_map takes the map part off again, the last predict re-makes it
+        if i == 1:
+            assert alive["sg"] == _formula(W, 64, True)
+        if i in (3, 5):
+            assert alive["sg"] == 0, i                                                # tnml_set_input_map releases the gradient workspace whole
+        if setup is not None:
+            fresh = new()
+            for s in setup:
+                s(fresh)
+            want = op(fresh)
+            fresh.close()
+            assert _equal(got, want), i
+    for c in only.values():
+        c.close()
+    ts.close()
+    again = new()
+    assert again.device_bytes() == base
+    again.close()
+
+
 def test_workspace_launches_and_switching_back():
     d = gm.case("small", (12, 4))
     W, phi, coef = d["W"], d["forms"]["phi"], d["coef"]

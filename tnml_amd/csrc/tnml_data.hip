@@ -72,7 +72,7 @@ int tnml_set_input_map(tnml_ctx* c, const tnml_input_map* m) {
             if (!std::isfinite(m->table[k])) return tnml_fail(c, "tnml_set_input_map: table[%d][%d] is not finite", k / 2, k % 2);
     }
     HIPCK(c, hipSetDevice(c->cfg.device));
-    if (c->pk_map_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); predict_release_map(c); }
+    if (c->pk.map_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); predict_release_map(c); }
     if (c->rs.bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); response_release(c); }
     if (c->sg.bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); sitegrad_release(c); }
     if (!m) { c->im_set = false; c->im = tnml_input_map{}; c->im_table.clear(); return 0; }

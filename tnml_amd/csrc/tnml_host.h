@@ -84,14 +84,21 @@ bool fingerprint_agrees(const double* sums8, int nranks);
 StageGeom stage_geom(const tnml_ctx* c);
 int check_W(tnml_ctx* c);
 
-// device-resident arguments (the tnml_*_dev calls, tnml.h): the memory space of a streamed call's arrays, and what goes with it
-struct StreamIO {
-    bool dev = false;                  // the arrays of the call are device memory (false: host pointers, every other field unused)
-    const float* phi32 = nullptr;      // fp32 features [n][N][2] instead of phi: widened exactly while staging
-    float* dphi32 = nullptr;           // the input gradients rounded once to fp32, instead of dphi
-    void* stream = nullptr;            // the hipStream_t that last wrote the inputs
-    bool entered = false;              // the pointer checks, the entry wait and the value check of this call have been made
+// The arrays of one streamed call (tnml_infer.hip): every entry point fills one record with what its call takes and hands it to its *_impl,
+// so a null field is an array the call was not given or does not produce.  What is no array travels beside it.
+struct StreamCall {
+    const char* who = nullptr; int64_t n = 0;          // the entry point, for the messages; the images of the call
+    // the images, exactly one: bytes [n][N] ([n][S] under an input map), features [n][N][2], or (tnml_*_dev only) fp32 features, widened exactly while staging
+    const uint8_t* pixels = nullptr; const double* phi = nullptr; const float* phi32 = nullptr;
+    const int32_t* labels = nullptr; const double* coef = nullptr; const int32_t* which = nullptr;   // [n], [n][nl], [n]
+    double* weights = nullptr; int32_t* pred = nullptr; double* resp = nullptr; double* grad = nullptr;   // [n][nl], [n], [n][N][2]; every site in tnml_get_site's layout
+    double* dphi = nullptr; float* dphi32 = nullptr;   // the input gradients [n][N][2]; dphi32 (tnml_*_dev only): rounded once to fp32, instead of dphi
+    bool dev = false; void* stream = nullptr;          // the tnml_*_dev calls (tnml.h): the arrays are device memory, last written by this hipStream_t,
+    bool entered = false;                              // and the pointer checks, the entry wait and the value check of this call have been made
     hipMemcpyKind in() const { return dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; }
+    bool bytes_form() const { return pixels != nullptr; }
+    bool has_images() const { return pixels || phi || phi32; }
+    bool want_dphi() const { return dphi || dphi32; }
 };
 struct DevArg { const char* name; const void* p; size_t bytes; size_t align; bool out; };
 // Every argument with p non-null: device memory of the context's device as the runtime describes it, aligned, [p, p + bytes) inside
@@ -112,11 +119,9 @@ int env_init_impl(tnml_ctx* c);
 int shift_env_impl(tnml_ctx* c, int b, int from_left);
 
 // ---- tnml_infer.hip ---------------------------------------------------------------------------
-// the streamed workspaces (tnml_ctx::pk, rs, sg with the fields beside them); synchronise first
+// the streamed workspaces (tnml_ctx::pk, rs, sg); synchronise first
 void predict_release_map(tnml_ctx* c);                 // of tnml_predict_*, the part that follows the input map
-void predict_release(tnml_ctx* c);
-void response_release(tnml_ctx* c);
-void sitegrad_release(tnml_ctx* c);
+void predict_release(tnml_ctx* c); void response_release(tnml_ctx* c); void sitegrad_release(tnml_ctx* c);
 void io_release(tnml_ctx* c);                          // what the tnml_*_dev calls keep: the check block and the entry event; synchronise first
 void step_release(tnml_ctx* c);                        // the optimiser state of tnml_site_step_* (the st_ fields); synchronise first
 

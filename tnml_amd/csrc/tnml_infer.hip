@@ -78,22 +78,25 @@ int tnml_classify(tnml_ctx* c, double* weights, int32_t* pred, int64_t count[TNM
 // tnml_predict_* / tnml_evaluate_*, tnml_response_* and tnml_site_gradient_* cut the n images into chunks of their chunk option; a chunk is
 // staged (copy + the input map's block sums or one transposing pre-kernel), contracted by the call's own launches and copied back, with one
 // synchronisation per chunk.  They read W only: no training data, environment, bond plan, P or p_valid is touched, no collective is entered.
-// Each has a workspace of its own (a StreamWs and the fields beside it in tnml_ctx; tnml.h has the sizes), allocated by its first call; what
-// the three share is written once, here.
+// Each has a workspace of its own (tnml_ctx::pk, rs, sg; tnml.h has the sizes), allocated by its first call; what the three share is
+// written once, here.
 static int ws_alloc(tnml_ctx* c, StreamWs& s, void** p, size_t bytes) {
     TCK(dalloc(c, p, bytes));
     s.bytes += (int64_t)bytes;
     return 0;
 }
-// frees the shared buffers and `slots`, the buffers that this workspace alone has (synchronise first); the caller clears the sizes that go with them
-static void ws_release(tnml_ctx* c, StreamWs& s, std::vector<void**> slots) {
-    for (void** p : {(void**)&s.tab, (void**)&s.w, (void**)&s.pred, (void**)&s.raw8, (void**)&s.x8, (void**)&s.rawphi, (void**)&s.xphi, (void**)&s.mraw, (void**)&s.codes, (void**)&s.mtab})
-        slots.push_back(p);
-    for (void** p : slots) if (*p) { (void)hipFree(*p); *p = nullptr; }
+// frees every buffer the workspace names (synchronise first) and starts it over: no pointer, size or capacity survives
+template <typename W>
+static void ws_release(tnml_ctx* c, W& s) {
+    for (const auto& list : {s.buffers(), s.own()})
+        for (void** p : list) if (*p) (void)hipFree(*p);
     c->bytes -= s.bytes;
-    s.bytes = 0; s.cap = 0;
+    s = W();
     if (!c->pk.bytes && !c->rs.bytes && !c->sg.bytes) io_release(c);     // the last streamed workspace has gone: what the _dev calls keep goes with it
 }
+void predict_release(tnml_ctx* c) { ws_release(c, c->pk); }
+void response_release(tnml_ctx* c) { ws_release(c, c->rs); }
+void sitegrad_release(tnml_ctx* c) { ws_release(c, c->sg); }
 // the check block and the entry event of the tnml_*_dev calls (made by the first such call; the next one makes them again)
 void io_release(tnml_ctx* c) {
     if (c->io_blk) { (void)hipFree(c->io_blk); c->io_blk = nullptr; c->bytes -= 3 * (int64_t)sizeof(unsigned long long); }
@@ -101,23 +104,10 @@ void io_release(tnml_ctx* c) {
 }
 // the part of the predict workspace that follows the input map: released by tnml_set_input_map, re-made by the next tnml_predict_u8 under a map
 void predict_release_map(tnml_ctx* c) {
-    for (void** p : {(void**)&c->pk.mraw, (void**)&c->pk.codes, (void**)&c->pk.mtab, (void**)&c->pk_mtab32}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    const int64_t freed = c->pk_map_bytes + c->pk_mtab32_bytes;        // (the fp32 copy of the table: 8 ncodes bytes)
+    for (void** p : {(void**)&c->pk.mraw, (void**)&c->pk.codes, (void**)&c->pk.mtab, (void**)&c->pk.f32.mtab32}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    const int64_t freed = c->pk.map_bytes + c->pk.f32.mtab32_bytes;        // (the fp32 copy of the table: 8 ncodes bytes)
     c->bytes -= freed; c->pk.bytes -= freed;
-    c->pk_map_bytes = 0; c->pk_mtab32_bytes = 0;
-}
-void predict_release(tnml_ctx* c) {
-    ws_release(c, c->pk, {(void**)&c->pk_park, (void**)&c->pk_w32, (void**)&c->pk_tab32, (void**)&c->pk_flag, (void**)&c->pk_xphi32, (void**)&c->pk_mtab32, (void**)&c->pk_lab, (void**)&c->pk_acc});
-    c->pk_w32_cap = 0; c->pk_park_elems = 0; c->pk_map_bytes = 0; c->pk_mtab32_bytes = 0;
-}
-void response_release(tnml_ctx* c) {
-    ws_release(c, c->rs, {(void**)&c->rs_which, (void**)&c->rs_rowoff, (void**)&c->rs_out, (void**)&c->rs_outT, (void**)&c->rs_tape});
-    c->rs_tape_rows = 0;
-}
-void sitegrad_release(tnml_ctx* c) {
-    ws_release(c, c->sg, {(void**)&c->sg_lab, (void**)&c->sg_coef, (void**)&c->sg_rowoff, (void**)&c->sg_goff, (void**)&c->sg_blk0, (void**)&c->sg_grad, (void**)&c->sg_tape, (void**)&c->sg_tape2,
-                          (void**)&c->bw_out, (void**)&c->bw_outT, (void**)&c->sg_w32, (void**)&c->sg_tab32, (void**)&c->sg_flag, (void**)&c->sg_xphi32, (void**)&c->sg_mtab32});
-    c->sg_tape_rows = 0; c->sg_grad_elems = 0; c->sg_last_cnt = -1; c->sg_w32_cap = 0; c->sg_mtab32_bytes = 0;
+    c->pk.map_bytes = 0; c->pk.f32.mtab32_bytes = 0;
 }
 // First call, or the chunk option has changed since: the old workspace goes (release), tab, w and pred are made for the new capacity;
 // *fresh then tells the caller to allocate what it alone has.  On an error here and in the helpers below the caller releases the workspace.
@@ -147,11 +137,13 @@ static int ws_grow(tnml_ctx* c, StreamWs& s, size_t want, size_t* have, size_t u
     return 0;
 }
 // The staging buffers of the call's input form, made by the first call of that form.  Under an input map S C + 2 N C + 16 ncodes bytes: the
-// bytes as given, the block sums site-first, the fp64 table (uploaded here).  xphi false: the caller keeps the site-first features itself (fp32)
-// dev (the arrays of the call are device memory): the stage kernels read the caller's array, so the buffer the images are copied into
+// bytes as given, the block sums site-first, the fp64 table (uploaded here).  f32: the site-first features are those of the fp32 side.
+// k.dev (the arrays of the call are device memory): the stage kernels read the caller's array, so the buffer the images are copied into
 // (mraw, raw8, rawphi) is left out; the first host-pointer call of that form makes it
-static int ws_staging(tnml_ctx* c, StreamWs& s, const char* who, bool bytes_form, bool xphi = true, bool dev = false) {
+static int ws_staging(tnml_ctx* c, StreamWs& s, const StreamCall& k, bool f32 = false) {
     const size_t cap = s.cap, N = c->N;
+    const bool bytes_form = k.bytes_form(), dev = k.dev;
+    const char* who = k.who;
     if (bytes_form && c->im_set) {
         const size_t S = (size_t)c->im.src_rows * c->im.src_cols, tabb = c->im_table.size() * sizeof(double);
         if (!dev && !s.mraw) TCK(ws_alloc(c, s, (void**)&s.mraw, S * cap));
@@ -165,13 +157,20 @@ static int ws_staging(tnml_ctx* c, StreamWs& s, const char* who, bool bytes_form
     if (bytes_form && !dev && !s.raw8) TCK(ws_alloc(c, s, (void**)&s.raw8, cap * N));
     if (bytes_form && !s.x8) TCK(ws_alloc(c, s, (void**)&s.x8, cap * N));
     if (!bytes_form && !dev && !s.rawphi) TCK(ws_alloc(c, s, (void**)&s.rawphi, 2 * cap * N * sizeof(double)));
-    if (!bytes_form && xphi && !s.xphi) TCK(ws_alloc(c, s, (void**)&s.xphi, 2 * cap * N * sizeof(double)));
+    if (!bytes_form && !f32 && !s.xphi) TCK(ws_alloc(c, s, (void**)&s.xphi, 2 * cap * N * sizeof(double)));
+    if (!bytes_form && f32 && !s.f32.xphi32) TCK(ws_alloc(c, s, (void**)&s.f32.xphi32, 2 * cap * N * sizeof(float)));
     return 0;
 }
-// The refusals every streamed call opens with, in this order.  fp64_only: what the call computes when it serves predict_dtype = 0 alone
+// what every entry point checks before anything else: a call on n > 0 images has been given them
+static int images_given(tnml_ctx* c, const StreamCall& k) {
+    return k.n > 0 && !k.has_images() ? tnml_fail(c, "%s: null argument", k.who) : 0;
+}
+// The refusals every streamed call goes on with, in this order.  fp64_only: what the call computes when it serves predict_dtype = 0 alone
 // (null: tnml_predict_* / tnml_evaluate_*, which take fp32 too); *maxbond: the largest bond of W
 // grad: the call follows option gradient_dtype (the gradient, backward and step calls); under fp32 its bond cap is the fp32 chain kernel's
-static int streamed_refusals(tnml_ctx* c, const char* who, const char* fp64_only, int64_t n, int* maxbond, bool grad = false) {
+static int streamed_refusals(tnml_ctx* c, const StreamCall& k, const char* fp64_only, int* maxbond, bool grad = false) {
+    const char* who = k.who;
+    const int64_t n = k.n;
     if (!c) return tnml_fail(c, "%s: null argument", who);
     if (n < 0) return tnml_fail(c, "%s: n = %lld, must be >= 0", who, (long long)n);
     if (c->pend_count > 0) return tnml_fail(c, "%s: a bond update is in flight (tnml_bond_update_end first)", who);
@@ -196,16 +195,29 @@ static int upload_sites(tnml_ctx* c, const StreamWs& s, std::vector<ChainSite<do
     HIPCK(c, hipMemcpyAsync(s.tab, tab.data(), sizeof(ChainSite<double>) * c->N, hipMemcpyHostToDevice, c->stream));
     return 0;
 }
+// what the kernels of element type E read in a workspace: the site table, the input map's table and the site-first features of a chunk --
+// the fp64 ones, or those of the fp32 side
+template <typename E> static const ChainSite<E>* sites(const StreamWs& s) { if constexpr (sizeof(E) == sizeof(float)) return s.f32.tab32; else return s.tab; }
+template <typename E> static const E* table(const StreamWs& s) { if constexpr (sizeof(E) == sizeof(float)) return s.f32.mtab32; else return s.mtab; }
+template <typename E> static E* xphi(const StreamWs& s) { if constexpr (sizeof(E) == sizeof(float)) return s.f32.xphi32; else return s.xphi; }
 // what a chain kernel takes from the context and the workspace: the centre tnml_classify takes, the results of a chunk and the source of the
-// features -- block sums with the table (input map), bytes, or staged features
+// features -- block sums with the table (input map), bytes, or staged features; fp32: the range flag
 template <typename E>
-static void chain_args(const tnml_ctx* c, const StreamWs& s, const ChainSite<E>* sites, bool bytes_form, const E* table, const E* xphi, ChainArgs<E>& a) {
-    a.sites = sites; a.N = c->N; a.cs = c->single() ? 1 : c->c0; a.nl = c->nl(); a.single = c->single() ? 1 : 0;
+static void chain_args(const tnml_ctx* c, const StreamWs& s, bool bytes_form, ChainArgs<E>& a) {
+    a.sites = sites<E>(s); a.N = c->N; a.cs = c->single() ? 1 : c->c0; a.nl = c->nl(); a.single = c->single() ? 1 : 0;
     a.ld = s.cap; a.wout = s.w; a.pred = s.pred;
     a.xT = nullptr; a.phiT = nullptr;
-    if (bytes_form && c->im_set) { a.codeT = s.codes; a.table = table; }
+    if (bytes_form && c->im_set) { a.codeT = s.codes; a.table = table<E>(s); }
     else if (bytes_form) a.xT = s.x8;
-    else a.phiT = xphi;
+    else a.phiT = xphi<E>(s);
+    if constexpr (sizeof(E) == sizeof(float)) a.flag = s.f32.flag;
+}
+// the shared part of the range-flag refusal of the fp32 calls (option: predict_dtype or gradient_dtype): the flag goes down again, the
+// call fails.  Where the flag is read back is the caller's: predict reads it with the chunk's results, the gradient loop before dphi leaves
+static int left_fp32_range(tnml_ctx* c, const StreamWs& s, const char* who, const char* option, int64_t off, int cnt) {
+    HIPCK(c, hipMemsetAsync(s.f32.flag, 0, sizeof(int), c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return tnml_fail(c, "%s: %s = 1 (fp32): a weight of images %lld..%lld is not finite, the chain has left the fp32 range: use fp64 (%s = 0)", who, option, (long long)off, (long long)off + cnt - 1, option);
 }
 // tape regions (kernels_response.hip, kernels_sitegrad.hip): the vector on bond b = 0..N (dimension 1 at the two ends) starts at row
 // rowoff[b]; rowoff[N + 1] and the return value: the rows so far
@@ -216,39 +228,39 @@ static int tape_rows(const tnml_ctx* c, std::vector<int>& rowoff) {
 }
 // the end of a chunk: weights and pred of images off .. off + cnt - 1 to the caller, then the synchronisation after which the staging buffers are reused
 // (device-resident arrays: the kernels have written them where the caller wants them, see chunk_dest)
-static int chunk_results(tnml_ctx* c, const StreamWs& s, int64_t off, int cnt, double* weights, int32_t* pred, bool dev = false) {
+static int chunk_results(tnml_ctx* c, const StreamWs& s, const StreamCall& k, int64_t off, int cnt) {
     const int nl = c->nl();
-    if (dev) { SYNCK(c, c->stream); return 0; }
-    if (weights) HIPCK(c, hipMemcpyAsync(weights + (size_t)off * nl, s.w, sizeof(double) * (size_t)cnt * nl, hipMemcpyDeviceToHost, c->stream));
-    if (pred) HIPCK(c, hipMemcpyAsync(pred + off, s.pred, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+    if (k.dev) { SYNCK(c, c->stream); return 0; }
+    if (k.weights) HIPCK(c, hipMemcpyAsync(k.weights + (size_t)off * nl, s.w, sizeof(double) * (size_t)cnt * nl, hipMemcpyDeviceToHost, c->stream));
+    if (k.pred) HIPCK(c, hipMemcpyAsync(k.pred + off, s.pred, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
     SYNCK(c, c->stream);
     return 0;
 }
 // where the kernels of a chunk leave weights and pred: the workspace, or -- device-resident arrays -- the caller's arrays at the chunk's offset
-static void chunk_dest(const tnml_ctx* c, const StreamWs& s, const StreamIO& io, int64_t off, double* weights, int32_t* pred, double** wout, int** pout) {
-    *wout = io.dev && weights ? weights + (size_t)off * c->nl() : s.w;
-    *pout = io.dev && pred ? pred + off : s.pred;
+static void chunk_dest(const tnml_ctx* c, const StreamWs& s, const StreamCall& k, int64_t off, double** wout, int** pout) {
+    *wout = k.dev && k.weights ? k.weights + (size_t)off * c->nl() : s.w;
+    *pout = k.dev && k.pred ? k.pred + off : s.pred;
 }
-// One chunk's way from the caller's arrays into the staging buffers of a workspace: copy in, then the input map's block sums or one
-// transposing pre-kernel; images off .. off + cnt - 1.  Device-resident arrays: no copy, the same kernel reads the caller's array at the
-// chunk's offset
+// One chunk's way from the caller's arrays into the staging buffers of a workspace: copy in, then the input map's block sums (sg: its
+// geometry) or one transposing pre-kernel; images off .. off + cnt - 1.  Device-resident arrays: no copy, the same kernel reads the
+// caller's array at the chunk's offset
 template <typename E>
-static int stage_chunk(tnml_ctx* c, const StreamWs& b, bool mapped, const StageGeom& sg, const uint8_t* pixels, const double* phi, int64_t off, int cnt, E* xphi, const StreamIO& io) {
-    const bool bytes_form = pixels != nullptr;
+static int stage_chunk(tnml_ctx* c, const StreamWs& b, const StreamCall& k, const StageGeom& sg, int64_t off, int cnt) {
+    const bool bytes_form = k.bytes_form(), mapped = bytes_form && c->im_set;
     const size_t per_img = mapped ? (size_t)sg.S : (size_t)c->N * (bytes_form ? 1 : 2 * sizeof(double));
-    if (io.dev) {
-        if (mapped) { ProfScope ps(c, KC_PACK); return launch_stage_codes(c, pixels + (size_t)off * per_img, sg, cnt, b.cap, b.codes); }
+    if (k.dev) {
+        if (mapped) { ProfScope ps(c, KC_PACK); return launch_stage_codes(c, k.pixels + (size_t)off * per_img, sg, cnt, b.cap, b.codes); }
         const size_t at = (size_t)off * c->N * 2;
-        return launch_chain_stage<E>(c, bytes_form ? pixels + (size_t)off * c->N : nullptr, phi ? phi + at : nullptr, c->N, cnt, b.cap, b.x8, xphi, io.phi32 ? io.phi32 + at : nullptr);
+        return launch_chain_stage<E>(c, bytes_form ? k.pixels + (size_t)off * c->N : nullptr, k.phi ? k.phi + at : nullptr, c->N, cnt, b.cap, b.x8, xphi<E>(b), k.phi32 ? k.phi32 + at : nullptr);
     }
     if (mapped) {
-        HIPCK(c, hipMemcpyAsync(b.mraw, pixels + (size_t)off * per_img, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+        HIPCK(c, hipMemcpyAsync(b.mraw, k.pixels + (size_t)off * per_img, per_img * cnt, hipMemcpyHostToDevice, c->stream));
         ProfScope ps(c, KC_PACK);
         return launch_stage_codes(c, b.mraw, sg, cnt, b.cap, b.codes);
     }
-    if (bytes_form) HIPCK(c, hipMemcpyAsync(b.raw8, pixels + (size_t)off * c->N, per_img * cnt, hipMemcpyHostToDevice, c->stream));
-    else            HIPCK(c, hipMemcpyAsync(b.rawphi, phi + (size_t)off * c->N * 2, per_img * cnt, hipMemcpyHostToDevice, c->stream));
-    return launch_chain_stage<E>(c, bytes_form ? b.raw8 : nullptr, bytes_form ? nullptr : b.rawphi, c->N, cnt, b.cap, b.x8, xphi);
+    if (bytes_form) HIPCK(c, hipMemcpyAsync(b.raw8, k.pixels + (size_t)off * c->N, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+    else            HIPCK(c, hipMemcpyAsync(b.rawphi, k.phi + (size_t)off * c->N * 2, per_img * cnt, hipMemcpyHostToDevice, c->stream));
+    return launch_chain_stage<E>(c, bytes_form ? b.raw8 : nullptr, bytes_form ? nullptr : b.rawphi, c->N, cnt, b.cap, b.x8, xphi<E>(b));
 }
 
 // ---- device-resident arguments: what a tnml_*_dev call does where the host-pointer call walks its arrays on the CPU ----------
@@ -257,23 +269,24 @@ static int stage_chunk(tnml_ctx* c, const StreamWs& b, bool mapped, const StageG
 // it, so that a device call is the host call's launches plus exactly this one; with none of the three arrays it has nothing to walk and
 // its block is not read back -- and the refusal in the host path's words.  The block is made by the first call, after the pointer checks.
 static size_t sitegrad_layout(tnml_ctx* c, long long* off);
-struct DevOuts { double* weights; int32_t* pred; double* resp; double* grad; double* dphi; };
-static int dev_enter(tnml_ctx* c, const char* who, StreamIO& io, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
-                     const int32_t* which, const DevOuts& o) {
-    if (io.entered) return 0;
-    const size_t N = c->N, nl = c->nl(), un = (size_t)n;
+static int dev_enter(tnml_ctx* c, StreamCall& k) {
+    if (k.entered) return 0;
+    const char* who = k.who;
+    const int32_t *labels = k.labels, *which = k.which;
+    const double* coef = k.coef;
+    const size_t N = c->N, nl = c->nl(), un = (size_t)k.n;
     const size_t per_img = c->im_set ? (size_t)c->im.src_rows * c->im.src_cols : N;
     TCK(dev_check_args(c, who, {
-        {"pixels", pixels, un * per_img, 1, false}, {"phi", phi, un * N * 2 * sizeof(double), 8, false}, {"phi32", io.phi32, un * N * 2 * sizeof(float), 4, false},
+        {"pixels", k.pixels, un * per_img, 1, false}, {"phi", k.phi, un * N * 2 * sizeof(double), 8, false}, {"phi32", k.phi32, un * N * 2 * sizeof(float), 4, false},
         {"labels", labels, un * sizeof(int32_t), 4, false}, {"coef", coef, un * nl * sizeof(double), 8, false}, {"which", which, un * sizeof(int32_t), 4, false},
-        {"weights", o.weights, un * nl * sizeof(double), 8, true}, {"pred", o.pred, un * sizeof(int32_t), 4, true}, {"resp", o.resp, un * N * 2 * sizeof(double), 8, true},
-        {"grad", o.grad, o.grad ? sitegrad_layout(c, nullptr) * sizeof(double) : 0, 8, true}, {"dphi", o.dphi, un * N * 2 * sizeof(double), 8, true},
-        {"dphi32", io.dphi32, un * N * 2 * sizeof(float), 4, true}}));
-    TCK(dev_entry_wait(c, who, io.stream));
-    io.entered = true;
+        {"weights", k.weights, un * nl * sizeof(double), 8, true}, {"pred", k.pred, un * sizeof(int32_t), 4, true}, {"resp", k.resp, un * N * 2 * sizeof(double), 8, true},
+        {"grad", k.grad, k.grad ? sitegrad_layout(c, nullptr) * sizeof(double) : 0, 8, true}, {"dphi", k.dphi, un * N * 2 * sizeof(double), 8, true},
+        {"dphi32", k.dphi32, un * N * 2 * sizeof(float), 4, true}}));
+    TCK(dev_entry_wait(c, who, k.stream));
+    k.entered = true;
     if (!c->io_blk) TCK(dalloc(c, (void**)&c->io_blk, 3 * sizeof(unsigned long long)));
     HIPCK(c, hipMemsetAsync(c->io_blk, 0xff, 3 * sizeof(unsigned long long), c->stream));
-    TCK(launch_check_batch(c, labels, coef, which, n, (int)nl, c->io_blk));
+    TCK(launch_check_batch(c, labels, coef, which, k.n, (int)nl, c->io_blk));
     if (!labels && !coef && !which) return 0;
     unsigned long long h[3];
     HIPCK(c, hipMemcpyAsync(h, c->io_blk, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -293,35 +306,34 @@ static int dev_enter(tnml_ctx* c, const char* who, StreamIO& io, int64_t n, cons
 }
 
 // ---- streamed inference (kernels_chain.hip): ONE k_chain launch per chunk ----------
-// the workspace: the shared part, the parked vectors, the staging of the input form (the map's part counted in pk_map_bytes, the site-first
+// the workspace: the shared part, the parked vectors, the staging of the input form (the map's part counted in pk.map_bytes, the site-first
 // features in the element type of option predict_dtype) and, for tnml_evaluate_*, 4 C + sizeof(EvalAcc) bytes: the labels of a chunk and the tallies of a call
-static int predict_workspace(tnml_ctx* c, const char* who, bool bytes_form, bool f32, bool evaluate, bool dev) {
-    StreamWs& s = c->pk;
+static int predict_workspace(tnml_ctx* c, const StreamCall& k, bool f32, bool evaluate) {
+    PredictWs& s = c->pk;
     bool fresh;
     int rc = ws_remake(c, s, c->predict_chunk, predict_release, &fresh);
     if (!rc && fresh) {
-        c->pk_park_elems = (size_t)s.cap * ru16(std::min(c->maxm, TNML_CHAIN_MAXM));
-        rc = ws_alloc(c, s, (void**)&c->pk_park, c->pk_park_elems * sizeof(double));
+        s.park_elems = (size_t)s.cap * ru16(std::min(c->maxm, TNML_CHAIN_MAXM));
+        rc = ws_alloc(c, s, (void**)&s.park, s.park_elems * sizeof(double));
     }
     const int64_t before = s.bytes;
-    if (!rc) rc = ws_staging(c, s, who, bytes_form, !f32, dev);
-    if (bytes_form && c->im_set) c->pk_map_bytes += s.bytes - before;
-    if (!rc && !bytes_form && f32 && !c->pk_xphi32) rc = ws_alloc(c, s, (void**)&c->pk_xphi32, (size_t)2 * s.cap * c->N * sizeof(float));
-    if (!rc && evaluate && !c->pk_lab) rc = ws_alloc(c, s, (void**)&c->pk_lab, (size_t)s.cap * sizeof(int));
-    if (!rc && evaluate && !c->pk_acc) rc = ws_alloc(c, s, (void**)&c->pk_acc, sizeof(EvalAcc));
+    if (!rc) rc = ws_staging(c, s, k, f32);
+    if (k.bytes_form() && c->im_set) s.map_bytes += s.bytes - before;
+    if (!rc && evaluate && !s.lab) rc = ws_alloc(c, s, (void**)&s.lab, (size_t)s.cap * sizeof(int));
+    if (!rc && evaluate && !s.acc) rc = ws_alloc(c, s, (void**)&s.acc, sizeof(EvalAcc));
     if (rc) predict_release(c);
     return rc;
 }
-// The fp32 side of a streamed workspace s (predict under predict_dtype = 1, the gradient calls under gradient_dtype = 1; made by the first
-// such call): the site table of the fp32 copy of W, the range flag, the copy itself (grown when W has grown) and, under an input map, the
-// table rounded to fp32.  Then the copy is made: W may have changed since the last call.  who / who_u8: the caller in the messages.
-struct Ws32 { ChainSite<float>** tab32; int** flag; float** w32; size_t* w32_cap; float** mtab32; int64_t* mtab32_bytes; void (*release)(tnml_ctx*); const char *who, *who_u8; };
-static int workspace32(tnml_ctx* c, StreamWs& s, const Ws32& f, bool mapped, const std::vector<ChainSite<double>>& tab) {
+// The fp32 side of a streamed workspace s: its site table, the range flag, the copy of W (grown when W has grown) and, under an input map,
+// the table rounded to fp32.  Then the copy is made: W may have changed since the last call.  release: of s, on an error; who / who_u8:
+// the caller in the messages
+static int workspace32(tnml_ctx* c, StreamWs& s, void (*release)(tnml_ctx*), const char* who, const char* who_u8, bool mapped, const std::vector<ChainSite<double>>& tab) {
+    StreamWs32& f = s.f32;
     int rc = 0;
-    if (!*f.tab32) rc = ws_alloc(c, s, (void**)f.tab32, (size_t)c->N * sizeof(ChainSite<float>));
-    if (!rc && !*f.flag) {
-        rc = ws_alloc(c, s, (void**)f.flag, sizeof(int));
-        if (!rc && hipMemsetAsync(*f.flag, 0, sizeof(int), c->stream) != hipSuccess) rc = tnml_fail(c, "%s: memset failed", f.who);
+    if (!f.tab32) rc = ws_alloc(c, s, (void**)&f.tab32, (size_t)c->N * sizeof(ChainSite<float>));
+    if (!rc && !f.flag) {
+        rc = ws_alloc(c, s, (void**)&f.flag, sizeof(int));
+        if (!rc && hipMemsetAsync(f.flag, 0, sizeof(int), c->stream) != hipSuccess) rc = tnml_fail(c, "%s: memset failed", who);
     }
     std::vector<size_t> off(c->N);
     size_t total = 0, largest = 0;
@@ -329,71 +341,54 @@ static int workspace32(tnml_ctx* c, StreamWs& s, const Ws32& f, bool mapped, con
         const size_t e = (size_t)2 * tab[j - 1].ml * tab[j - 1].mr * (j == c->c0 ? c->nl() : 1);
         off[j - 1] = total; total += (e + 3) / 4 * 4; largest = std::max(largest, e);
     }
-    if (!rc && total > *f.w32_cap) {
-        if (*f.w32) {
-            if (hipStreamSynchronize(c->stream) != hipSuccess) return tnml_fail(c, "%s: hipStreamSynchronize failed", f.who);
-            (void)hipFree(*f.w32); *f.w32 = nullptr;
-            c->bytes -= (int64_t)(*f.w32_cap * sizeof(float)); s.bytes -= (int64_t)(*f.w32_cap * sizeof(float)); *f.w32_cap = 0;
+    if (!rc && total > f.w32_cap) {
+        if (f.w32) {
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return tnml_fail(c, "%s: hipStreamSynchronize failed", who);
+            (void)hipFree(f.w32); f.w32 = nullptr;
+            c->bytes -= (int64_t)(f.w32_cap * sizeof(float)); s.bytes -= (int64_t)(f.w32_cap * sizeof(float)); f.w32_cap = 0;
         }
-        rc = ws_alloc(c, s, (void**)f.w32, total * sizeof(float));
-        if (!rc) *f.w32_cap = total;
+        rc = ws_alloc(c, s, (void**)&f.w32, total * sizeof(float));
+        if (!rc) f.w32_cap = total;
     }
-    if (!rc && mapped && !*f.mtab32) {
+    if (!rc && mapped && !f.mtab32) {
         std::vector<float> t32(c->im_table.size());
-        for (size_t k = 0; k < t32.size(); ++k) t32[k] = (float)c->im_table[k];
+        for (size_t i = 0; i < t32.size(); ++i) t32[i] = (float)c->im_table[i];
         const int64_t before = s.bytes;
-        rc = ws_alloc(c, s, (void**)f.mtab32, t32.size() * sizeof(float));
-        if (!rc) *f.mtab32_bytes = s.bytes - before;
-        if (!rc && hipMemcpyAsync(*f.mtab32, t32.data(), t32.size() * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "%s: copy of the input map's table failed", f.who_u8);
-        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "%s: hipStreamSynchronize failed", f.who_u8);
+        rc = ws_alloc(c, s, (void**)&f.mtab32, t32.size() * sizeof(float));
+        if (!rc) f.mtab32_bytes = s.bytes - before;
+        if (!rc && hipMemcpyAsync(f.mtab32, t32.data(), t32.size() * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = tnml_fail(c, "%s: copy of the input map's table failed", who_u8);
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "%s: hipStreamSynchronize failed", who_u8);
     }
-    if (rc) { f.release(c); return rc; }
+    if (rc) { release(c); return rc; }
     std::vector<ChainSite<float>> t32(c->N);
-    for (int j = 1; j <= c->N; ++j) t32[j - 1] = ChainSite<float>{*f.w32 + off[j - 1], tab[j - 1].ml, tab[j - 1].mr};
-    HIPCK(c, hipMemcpyAsync(*f.tab32, t32.data(), sizeof(ChainSite<float>) * c->N, hipMemcpyHostToDevice, c->stream));
-    TCK(launch_chain_pack32(c, s.tab, *f.tab32, c->N, c->c0, c->nl(), largest));
+    for (int j = 1; j <= c->N; ++j) t32[j - 1] = ChainSite<float>{f.w32 + off[j - 1], tab[j - 1].ml, tab[j - 1].mr};
+    HIPCK(c, hipMemcpyAsync(f.tab32, t32.data(), sizeof(ChainSite<float>) * c->N, hipMemcpyHostToDevice, c->stream));
+    TCK(launch_chain_pack32(c, s.tab, f.tab32, c->N, c->c0, c->nl(), largest));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (t32 leaves scope with this call)
     return 0;
 }
-static int predict_workspace32(tnml_ctx* c, bool mapped, const std::vector<ChainSite<double>>& tab) {
-    return workspace32(c, c->pk, Ws32{&c->pk_tab32, &c->pk_flag, &c->pk_w32, &c->pk_w32_cap, &c->pk_mtab32, &c->pk_mtab32_bytes, predict_release, "tnml_predict", "tnml_predict_u8"}, mapped, tab);
-}
 // the chunk loop of predict_impl in the element type E of option predict_dtype: per chunk stage (map, bytes or phi), ONE chain launch, copy back;
-// labels (tnml_evaluate_*): the chunk's labels are staged with its images and ONE k_eval_tally launch behind the chain adds its tallies to pk_acc
+// k.labels (tnml_evaluate_*): the chunk's labels are staged with its images and ONE k_eval_tally launch behind the chain adds its tallies to pk.acc
 template <typename E>
-static int predict_chunks(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, double* weights, int32_t* pred, int maxbond, const StreamIO& io) {
+static int predict_chunks(tnml_ctx* c, const StreamCall& k, int maxbond) {
     constexpr bool f32 = sizeof(E) == sizeof(float);
-    const StreamWs& s = c->pk;
-    const bool bytes_form = pixels != nullptr;
-    const bool mapped = bytes_form && c->im_set;                // the input map: S bytes per image -> block sums -> table look-ups inside the chain kernel
-    const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
+    const PredictWs& s = c->pk;
+    const StageGeom sg = k.bytes_form() && c->im_set ? stage_geom(c) : StageGeom{};   // the input map: S bytes per image -> block sums -> table look-ups inside the chain kernel
     ChainArgs<E> a;
-    E *xphi, *park; size_t park_elems = c->pk_park_elems;
-    if constexpr (f32) {
-        // fp32: the copy of W, the features and the table rounded to fp32; the scratch of the parked vectors is the fp64 path's:
-        // cap x ru16(min(maxm, 512)) doubles hold cap x ru16(min(maxm, 1024)) floats
-        xphi = c->pk_xphi32; park = (float*)c->pk_park; park_elems *= 2;
-        chain_args(c, s, c->pk_tab32, bytes_form, c->pk_mtab32, xphi, a);
-        a.flag = c->pk_flag;
-    } else {
-        xphi = s.xphi; park = c->pk_park;
-        chain_args(c, s, s.tab, bytes_form, s.mtab, xphi, a);
-    }
-    for (int64_t off = 0; off < n; off += c->predict_chunk) {
-        a.cnt = (int)std::min<int64_t>(c->predict_chunk, n - off);
-        TCK(stage_chunk<E>(c, s, mapped, sg, pixels, phi, off, a.cnt, xphi, io));
-        chunk_dest(c, s, io, off, weights, pred, &a.wout, &a.pred);
-        if (labels) HIPCK(c, hipMemcpyAsync(c->pk_lab, labels + off, sizeof(int32_t) * (size_t)a.cnt, io.in(), c->stream));
-        TCK(launch_chain<E>(c, a, maxbond, chain_tile<E>(c, maxbond, a.cnt), park, park_elems));
-        if (labels) TCK(launch_eval_tally(c, a.wout, a.pred, c->pk_lab, a.cnt, a.nl, a.single, c->target(), c->pk_acc, c->loss, c->loss_beta));
+    chain_args(c, s, k.bytes_form(), a);
+    // fp32: the scratch of the parked vectors is the fp64 path's: cap x ru16(min(maxm, 512)) doubles hold cap x ru16(min(maxm, 1024)) floats
+    const size_t park_elems = s.park_elems * (sizeof(double) / sizeof(E));
+    for (int64_t off = 0; off < k.n; off += c->predict_chunk) {
+        a.cnt = (int)std::min<int64_t>(c->predict_chunk, k.n - off);
+        TCK(stage_chunk<E>(c, s, k, sg, off, a.cnt));
+        chunk_dest(c, s, k, off, &a.wout, &a.pred);
+        if (k.labels) HIPCK(c, hipMemcpyAsync(s.lab, k.labels + off, sizeof(int32_t) * (size_t)a.cnt, k.in(), c->stream));
+        TCK(launch_chain<E>(c, a, maxbond, chain_tile<E>(c, maxbond, a.cnt), (E*)s.park, park_elems));
+        if (k.labels) TCK(launch_eval_tally(c, a.wout, a.pred, s.lab, a.cnt, a.nl, a.single, c->target(), s.acc, c->loss, c->loss_beta));
         int flag = 0;
-        if (f32) HIPCK(c, hipMemcpyAsync(&flag, c->pk_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        TCK(chunk_results(c, s, off, a.cnt, weights, pred, io.dev));
-        if (flag) {
-            HIPCK(c, hipMemsetAsync(c->pk_flag, 0, sizeof(int), c->stream));
-            HIPCK(c, hipStreamSynchronize(c->stream));
-            return tnml_fail(c, "%s: predict_dtype = 1 (fp32): a weight of images %lld..%lld is not finite, the chain has left the fp32 range: use fp64 (predict_dtype = 0)", who, (long long)off, (long long)off + a.cnt - 1);
-        }
+        if (f32) HIPCK(c, hipMemcpyAsync(&flag, s.f32.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        TCK(chunk_results(c, s, k, off, a.cnt));                // (the synchronisation the flag rides on)
+        if (flag) return left_fp32_range(c, s, k.who, "predict_dtype", off, a.cnt);
     }
     return 0;
 }
@@ -411,86 +406,89 @@ static tnml_eval_report eval_report_of(const EvalAcc& h, int64_t n) {
     r.ncorrect = n - wrong;
     return r;
 }
-// rep: the call is tnml_evaluate_* (labels are then required when n > 0); *rep is written once, after everything has succeeded
-static int predict_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, double* weights, int32_t* pred,
-                        bool evaluate = false, const int32_t* labels = nullptr, tnml_eval_report* rep = nullptr, StreamIO io = StreamIO()) {
+// evaluate: the call is tnml_evaluate_* (labels and rep are then required when n > 0); *rep is written once, after everything has succeeded
+static int predict_impl(tnml_ctx* c, StreamCall& k, bool evaluate = false, tnml_eval_report* rep = nullptr) {
     int maxbond = 1;
-    TCK(streamed_refusals(c, who, nullptr, n, &maxbond));
-    if (n == 0) { if (rep) memset(rep, 0, sizeof(*rep)); return 0; }
-    if (!pixels && !phi && !io.phi32) return tnml_fail(c, "%s: null argument", who);
+    TCK(images_given(c, k));
+    TCK(streamed_refusals(c, k, nullptr, &maxbond));
+    if (k.n == 0) { if (rep) memset(rep, 0, sizeof(*rep)); return 0; }
     if (evaluate) {
-        if (!labels || !rep) return tnml_fail(c, "%s: null argument (labels and rep are required)", who);
-        if (!io.dev)
-            for (int64_t i = 0; i < n; ++i)
-                if (labels[i] < 0 || labels[i] >= TNML_NL) return tnml_fail(c, "%s: label %d of image %lld out of range", who, labels[i], (long long)i);
+        if (!k.labels || !rep) return tnml_fail(c, "%s: null argument (labels and rep are required)", k.who);
+        if (!k.dev)
+            for (int64_t i = 0; i < k.n; ++i)
+                if (k.labels[i] < 0 || k.labels[i] >= TNML_NL) return tnml_fail(c, "%s: label %d of image %lld out of range", k.who, k.labels[i], (long long)i);
     }
-    if (io.dev) TCK(dev_enter(c, who, io, n, pixels, phi, evaluate ? labels : nullptr, nullptr, nullptr, DevOuts{weights, pred, nullptr, nullptr, nullptr}));
+    if (k.dev) TCK(dev_enter(c, k));
     HIPCK(c, hipSetDevice(c->cfg.device));
-    const bool bytes_form = pixels != nullptr, f32 = c->predict_dtype == TNML_PREDICT_F32;
-    TCK(predict_workspace(c, who, bytes_form, f32, evaluate, io.dev));
-    if (evaluate) HIPCK(c, hipMemsetAsync(c->pk_acc, 0, sizeof(EvalAcc), c->stream));
+    const bool f32 = c->predict_dtype == TNML_PREDICT_F32;
+    TCK(predict_workspace(c, k, f32, evaluate));
+    if (evaluate) HIPCK(c, hipMemsetAsync(c->pk.acc, 0, sizeof(EvalAcc), c->stream));
     std::vector<ChainSite<double>> tab;
     TCK(upload_sites(c, c->pk, tab));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (tab leaves scope with this call)
-    if (f32) TCK(predict_workspace32(c, bytes_form && c->im_set, tab));
-    TCK(f32 ? predict_chunks<float>(c, who, n, pixels, phi, labels, weights, pred, maxbond, io) : predict_chunks<double>(c, who, n, pixels, phi, labels, weights, pred, maxbond, io));
+    if (f32) TCK(workspace32(c, c->pk, predict_release, "tnml_predict", "tnml_predict_u8", k.bytes_form() && c->im_set, tab));
+    TCK(f32 ? predict_chunks<float>(c, k, maxbond) : predict_chunks<double>(c, k, maxbond));
     if (!evaluate) return 0;
     EvalAcc h;                                                  // the one copy of the tallies: every chunk has been added (the loop ends on a synchronisation)
-    HIPCK(c, hipMemcpyAsync(&h, c->pk_acc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(&h, c->pk.acc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     SYNCK(c, c->stream);
-    *rep = eval_report_of(h, n);
+    *rep = eval_report_of(h, k.n);
     return 0;
 }
 int tnml_predict_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, double* weights, int32_t* pred) {
-    if (n > 0 && !pixels) return tnml_fail(c, "tnml_predict_u8: null argument");
-    return predict_impl(c, "tnml_predict_u8", n, pixels, nullptr, weights, pred);
+    StreamCall k{"tnml_predict_u8", n, pixels};
+    k.weights = weights; k.pred = pred;
+    return predict_impl(c, k);
 }
 int tnml_predict_phi(tnml_ctx* c, int64_t n, const double* phi, double* weights, int32_t* pred) {
-    if (n > 0 && !phi) return tnml_fail(c, "tnml_predict_phi: null argument");
-    return predict_impl(c, "tnml_predict_phi", n, nullptr, phi, weights, pred);
+    StreamCall k{"tnml_predict_phi", n, nullptr, phi};
+    k.weights = weights; k.pred = pred;
+    return predict_impl(c, k);
 }
 int tnml_evaluate_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const int32_t* labels, tnml_eval_report* rep, double* weights, int32_t* pred) {
-    if (n > 0 && !pixels) return tnml_fail(c, "tnml_evaluate_u8: null argument");
-    return predict_impl(c, "tnml_evaluate_u8", n, pixels, nullptr, weights, pred, true, labels, rep);
+    StreamCall k{"tnml_evaluate_u8", n, pixels};
+    k.labels = labels; k.weights = weights; k.pred = pred;
+    return predict_impl(c, k, true, rep);
 }
 int tnml_evaluate_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* labels, tnml_eval_report* rep, double* weights, int32_t* pred) {
-    if (n > 0 && !phi) return tnml_fail(c, "tnml_evaluate_phi: null argument");
-    return predict_impl(c, "tnml_evaluate_phi", n, nullptr, phi, weights, pred, true, labels, rep);
+    StreamCall k{"tnml_evaluate_phi", n, nullptr, phi};
+    k.labels = labels; k.weights = weights; k.pred = pred;
+    return predict_impl(c, k, true, rep);
 }
 
 // ---- streamed site responses (kernels_response.hip): every site's effect on an image's output ---------------------
 // Per chunk of option response_chunk ONE k_response launch walks the chain inward and outward, the result [N][2][C] is turned into
 // [C][N][2] on the device and copied back.
 // rows: the rows of a workgroup's tape slice that W asks for now
-static int response_workspace(tnml_ctx* c, const char* who, bool bytes_form, size_t rows, bool dev) {
-    StreamWs& s = c->rs;
+static int response_workspace(tnml_ctx* c, const StreamCall& k, size_t rows) {
+    ResponseWs& s = c->rs;
     bool fresh;
     int rc = ws_remake(c, s, c->response_chunk, response_release, &fresh);
     const size_t cap = s.cap;
     if (!rc && fresh) {
-        rc = ws_alloc(c, s, (void**)&c->rs_which, cap * sizeof(int));
-        if (!rc) rc = ws_alloc(c, s, (void**)&c->rs_rowoff, (size_t)(c->N + 4) * sizeof(int));
-        if (!rc) rc = ws_alloc(c, s, (void**)&c->rs_out, 2 * c->N * cap * sizeof(double));
+        rc = ws_alloc(c, s, (void**)&s.which, cap * sizeof(int));
+        if (!rc) rc = ws_alloc(c, s, (void**)&s.rowoff, (size_t)(c->N + 4) * sizeof(int));
+        if (!rc) rc = ws_alloc(c, s, (void**)&s.out, 2 * c->N * cap * sizeof(double));
     }
-    if (!rc && !dev && !c->rs_outT) rc = ws_alloc(c, s, (void**)&c->rs_outT, 2 * c->N * cap * sizeof(double));    // (device-resident resp: the transposition writes the caller's array)
-    if (!rc) rc = ws_grow(c, s, rows, &c->rs_tape_rows, cap * sizeof(double), {&c->rs_tape});
-    if (!rc) rc = ws_staging(c, s, who, bytes_form, true, dev);
+    if (!rc && !k.dev && !s.outT) rc = ws_alloc(c, s, (void**)&s.outT, 2 * c->N * cap * sizeof(double));    // (device-resident resp: the transposition writes the caller's array)
+    if (!rc) rc = ws_grow(c, s, rows, &s.tape_rows, cap * sizeof(double), {&s.tape});
+    if (!rc) rc = ws_staging(c, s, k);
     if (rc) response_release(c);
     return rc;
 }
-static int response_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* which, double* resp, double* weights, int32_t* pred,
-                         StreamIO io = StreamIO()) {
+static int response_impl(tnml_ctx* c, StreamCall& k) {
     int maxbond = 1;
-    TCK(streamed_refusals(c, who, "site responses", n, &maxbond));
-    if (n == 0) return 0;
-    if ((!pixels && !phi && !io.phi32) || !resp) return tnml_fail(c, "%s: null argument", who);
+    TCK(images_given(c, k));
+    TCK(streamed_refusals(c, k, "site responses", &maxbond));
+    if (k.n == 0) return 0;
+    if (!k.resp) return tnml_fail(c, "%s: null argument", k.who);
     const int nl = c->nl();
-    if (io.dev) TCK(dev_enter(c, who, io, n, pixels, phi, nullptr, nullptr, which, DevOuts{weights, pred, resp, nullptr, nullptr}));
-    else if (which)
-        for (int64_t i = 0; i < n; ++i)
-            if (which[i] < 0 || which[i] >= nl) return tnml_fail(c, "%s: which = %d of image %lld out of range 0..%d", who, which[i], (long long)i, nl - 1);
+    if (k.dev) TCK(dev_enter(c, k));
+    else if (k.which)
+        for (int64_t i = 0; i < k.n; ++i)
+            if (k.which[i] < 0 || k.which[i] >= nl) return tnml_fail(c, "%s: which = %d of image %lld out of range 0..%d", k.who, k.which[i], (long long)i, nl - 1);
     HIPCK(c, hipSetDevice(c->cfg.device));
-    const StreamWs& s = c->rs;
+    const ResponseWs& s = c->rs;
     const int N = c->N, cs = c->single() ? 1 : c->c0;
     // the tape: the regions of the bonds, then X and Y of the centre (kernels_response.hip)
     std::vector<int> rowoff(N + 4);
@@ -498,36 +496,37 @@ static int response_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t*
     rows += ru16(c->W[cs].ml);
     rowoff[N + 2] = rows; rows += ru16(c->W[cs].mr);
     rowoff[N + 3] = rows;
-    const bool bytes_form = pixels != nullptr;
-    TCK(response_workspace(c, who, bytes_form, (size_t)rows, io.dev));
+    TCK(response_workspace(c, k, (size_t)rows));
     std::vector<ChainSite<double>> tab;
     TCK(upload_sites(c, s, tab));
-    HIPCK(c, hipMemcpyAsync(c->rs_rowoff, rowoff.data(), sizeof(int) * (N + 4), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(s.rowoff, rowoff.data(), sizeof(int) * (N + 4), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (tab and rowoff leave scope with this call)
-    const bool mapped = bytes_form && c->im_set;
-    const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
+    const StageGeom sg = k.bytes_form() && c->im_set ? stage_geom(c) : StageGeom{};
     RespArgs a;
-    chain_args(c, s, s.tab, bytes_form, s.mtab, s.xphi, a.ch);
-    a.which = which ? c->rs_which : nullptr; a.rowoff = c->rs_rowoff; a.tape = c->rs_tape; a.resp = c->rs_out;
-    const size_t tape_elems = c->rs_tape_rows * (size_t)s.cap;
-    for (int64_t off = 0; off < n; off += c->response_chunk) {
-        a.ch.cnt = (int)std::min<int64_t>(c->response_chunk, n - off);
-        TCK(stage_chunk<double>(c, s, mapped, sg, pixels, phi, off, a.ch.cnt, s.xphi, io));
-        chunk_dest(c, s, io, off, weights, pred, &a.ch.wout, &a.ch.pred);
-        if (which) HIPCK(c, hipMemcpyAsync(c->rs_which, which + off, sizeof(int32_t) * (size_t)a.ch.cnt, io.in(), c->stream));
-        TCK(launch_response(c, a, maxbond, chain_tile<double>(c, maxbond, a.ch.cnt), rows, tape_elems, io.dev ? resp + (size_t)off * N * 2 : c->rs_outT));
-        if (!io.dev) HIPCK(c, hipMemcpyAsync(resp + (size_t)off * N * 2, c->rs_outT, sizeof(double) * (size_t)a.ch.cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
-        TCK(chunk_results(c, s, off, a.ch.cnt, weights, pred, io.dev));
+    chain_args(c, s, k.bytes_form(), a.ch);
+    a.which = k.which ? s.which : nullptr; a.rowoff = s.rowoff; a.tape = s.tape; a.resp = s.out;
+    const size_t tape_elems = s.tape_rows * (size_t)s.cap;
+    for (int64_t off = 0; off < k.n; off += c->response_chunk) {
+        a.ch.cnt = (int)std::min<int64_t>(c->response_chunk, k.n - off);
+        double* const resp = k.resp + (size_t)off * N * 2;
+        TCK(stage_chunk<double>(c, s, k, sg, off, a.ch.cnt));
+        chunk_dest(c, s, k, off, &a.ch.wout, &a.ch.pred);
+        if (k.which) HIPCK(c, hipMemcpyAsync(s.which, k.which + off, sizeof(int32_t) * (size_t)a.ch.cnt, k.in(), c->stream));
+        TCK(launch_response(c, a, maxbond, chain_tile<double>(c, maxbond, a.ch.cnt), rows, tape_elems, k.dev ? resp : s.outT));
+        if (!k.dev) HIPCK(c, hipMemcpyAsync(resp, s.outT, sizeof(double) * (size_t)a.ch.cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
+        TCK(chunk_results(c, s, k, off, a.ch.cnt));
     }
     return 0;
 }
 int tnml_response_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const int32_t* which, double* resp, double* weights, int32_t* pred) {
-    if (n > 0 && !pixels) return tnml_fail(c, "tnml_response_u8: null argument");
-    return response_impl(c, "tnml_response_u8", n, pixels, nullptr, which, resp, weights, pred);
+    StreamCall k{"tnml_response_u8", n, pixels};
+    k.which = which; k.resp = resp; k.weights = weights; k.pred = pred;
+    return response_impl(c, k);
 }
 int tnml_response_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* which, double* resp, double* weights, int32_t* pred) {
-    if (n > 0 && !phi) return tnml_fail(c, "tnml_response_phi: null argument");
-    return response_impl(c, "tnml_response_phi", n, nullptr, phi, which, resp, weights, pred);
+    StreamCall k{"tnml_response_phi", n, nullptr, phi};
+    k.which = which; k.resp = resp; k.weights = weights; k.pred = pred;
+    return response_impl(c, k);
 }
 
 // ---- streamed site gradients (kernels_sitegrad.hip): dC/dA of every site, on images the context does not hold ----------------
@@ -535,32 +534,33 @@ int tnml_response_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* 
 // launch adds the chunk's outer products to the gradient, which stays on the device until the last chunk and is copied back once.
 // rows: the rows of a workgroup's tape slice that W asks for now; elems: the elements of the gradient of W as it is now
 // f32 (option gradient_dtype = 1): the tapes hold floats -- a change of the option frees the two tapes and makes them again in the new
-// element size, and touches nothing else --, the site-first features of the phi form are the fp32 ones (sg_xphi32); the fp32 copy of W
-// follows in workspace32
-static int sitegrad_workspace(tnml_ctx* c, const char* who, bool bytes_form, size_t rows, size_t elems, bool dev, bool f32) {
-    StreamWs& s = c->sg;
+// element size, and touches nothing else --, the site-first features of the phi form are the fp32 ones; the fp32 copy of W follows in
+// workspace32.  The first call that asks for input gradients adds their result as the kernel leaves it and as a host caller gets it
+static int sitegrad_workspace(tnml_ctx* c, const StreamCall& k, size_t rows, size_t elems, bool f32) {
+    GradientWs& s = c->sg;
     const int nl = c->nl();
     bool fresh;
     int rc = ws_remake(c, s, c->gradient_chunk, sitegrad_release, &fresh);
     const size_t cap = s.cap, esz = f32 ? sizeof(float) : sizeof(double);
-    if (!rc && c->sg_tape_rows && (size_t)c->sg_esz != esz) {
-        if (hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "%s: hipStreamSynchronize failed", who);
-        for (double** p : {&c->sg_tape, &c->sg_tape2})
-            if (*p) { (void)hipFree(*p); *p = nullptr; c->bytes -= (int64_t)(c->sg_tape_rows * cap * c->sg_esz); s.bytes -= (int64_t)(c->sg_tape_rows * cap * c->sg_esz); }
-        c->sg_tape_rows = 0;
+    if (!rc && s.tape_rows && (size_t)s.esz != esz) {
+        if (hipStreamSynchronize(c->stream) != hipSuccess) rc = tnml_fail(c, "%s: hipStreamSynchronize failed", k.who);
+        for (double** p : {&s.tape, &s.tape2})
+            if (*p) { (void)hipFree(*p); *p = nullptr; c->bytes -= (int64_t)(s.tape_rows * cap * s.esz); s.bytes -= (int64_t)(s.tape_rows * cap * s.esz); }
+        s.tape_rows = 0;
     }
-    c->sg_esz = (int)esz;
+    s.esz = (int)esz;
     if (!rc && fresh) {
-        rc = ws_alloc(c, s, (void**)&c->sg_coef, cap * nl * sizeof(double));
-        if (!rc) rc = ws_alloc(c, s, (void**)&c->sg_lab, cap * sizeof(int));
-        if (!rc) rc = ws_alloc(c, s, (void**)&c->sg_rowoff, (size_t)(c->N + 2) * sizeof(int));
-        if (!rc) rc = ws_alloc(c, s, (void**)&c->sg_goff, (size_t)(c->N + 1) * sizeof(long long));
-        if (!rc) rc = ws_alloc(c, s, (void**)&c->sg_blk0, (size_t)(c->N + nl) * sizeof(int));
+        rc = ws_alloc(c, s, (void**)&s.coef, cap * nl * sizeof(double));
+        if (!rc) rc = ws_alloc(c, s, (void**)&s.lab, cap * sizeof(int));
+        if (!rc) rc = ws_alloc(c, s, (void**)&s.rowoff, (size_t)(c->N + 2) * sizeof(int));
+        if (!rc) rc = ws_alloc(c, s, (void**)&s.goff, (size_t)(c->N + 1) * sizeof(long long));
+        if (!rc) rc = ws_alloc(c, s, (void**)&s.blk0, (size_t)(c->N + nl) * sizeof(int));
     }
-    if (!rc) rc = ws_grow(c, s, rows, &c->sg_tape_rows, cap * esz, {&c->sg_tape, &c->sg_tape2});
-    if (!rc) rc = ws_grow(c, s, elems, &c->sg_grad_elems, sizeof(double), {&c->sg_grad});
-    if (!rc) rc = ws_staging(c, s, who, bytes_form, !f32, dev);
-    if (!rc && !bytes_form && f32 && !c->sg_xphi32) rc = ws_alloc(c, s, (void**)&c->sg_xphi32, (size_t)2 * cap * c->N * sizeof(float));
+    if (!rc) rc = ws_grow(c, s, rows, &s.tape_rows, cap * esz, {&s.tape, &s.tape2});
+    if (!rc) rc = ws_grow(c, s, elems, &s.grad_elems, sizeof(double), {&s.grad});
+    if (!rc) rc = ws_staging(c, s, k, f32);
+    if (!rc && k.want_dphi() && !s.dphi) rc = ws_alloc(c, s, (void**)&s.dphi, (size_t)2 * c->N * cap * sizeof(double));
+    if (!rc && k.want_dphi() && !k.dev && !s.dphiT) rc = ws_alloc(c, s, (void**)&s.dphiT, (size_t)2 * c->N * cap * sizeof(double));
     if (rc) sitegrad_release(c);
     return rc;
 }
@@ -582,188 +582,163 @@ int tnml_site_gradient_size(tnml_ctx* c, int64_t* elems, int64_t* offsets) {
     if (offsets) for (int j = 0; j <= c->N; ++j) offsets[j] = off[j];
     return 0;
 }
-// what a gradient call with n > 0 asks of its arrays: images, exactly one of labels and coef, labels in range, finite coefficients
-// device-resident arrays: the same through dev_enter (o: the outputs of the call, for its pointer checks), once per call
-static int sitegrad_inputs(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
-                           StreamIO& io, const DevOuts& o) {
+// what a gradient call with n > 0 asks of its arrays: exactly one of labels and coef, labels in range, finite coefficients
+// device-resident arrays: the same through dev_enter, once per call
+static int sitegrad_inputs(tnml_ctx* c, StreamCall& k) {
     const int nl = c->nl();
-    if (!pixels && !phi && !io.phi32) return tnml_fail(c, "%s: null argument", who);
-    if ((labels != nullptr) == (coef != nullptr)) return tnml_fail(c, "%s: exactly one of labels and coef must be given (%s are)", who, labels ? "both" : "neither");
-    if (io.dev) return dev_enter(c, who, io, n, pixels, phi, labels, coef, nullptr, o);
-    if (labels)
-        for (int64_t i = 0; i < n; ++i)
-            if (labels[i] < 0 || labels[i] >= TNML_NL) return tnml_fail(c, "%s: label %d of image %lld out of range", who, labels[i], (long long)i);
-    if (coef)
-        for (int64_t i = 0; i < n * nl; ++i)
-            if (!std::isfinite(coef[i])) return tnml_fail(c, "%s: coefficient %d of image %lld is not finite", who, (int)(i % nl), (long long)(i / nl));
+    if ((k.labels != nullptr) == (k.coef != nullptr)) return tnml_fail(c, "%s: exactly one of labels and coef must be given (%s are)", k.who, k.labels ? "both" : "neither");
+    if (k.dev) return dev_enter(c, k);
+    if (k.labels)
+        for (int64_t i = 0; i < k.n; ++i)
+            if (k.labels[i] < 0 || k.labels[i] >= TNML_NL) return tnml_fail(c, "%s: label %d of image %lld out of range", k.who, k.labels[i], (long long)i);
+    if (k.coef)
+        for (int64_t i = 0; i < k.n * nl; ++i)
+            if (!std::isfinite(k.coef[i])) return tnml_fail(c, "%s: coefficient %d of image %lld is not finite", k.who, (int)(i % nl), (long long)(i / nl));
     return 0;
 }
+// what sitegrad_device works out for its chunk loop, and what its caller asks for beside the arrays: acc (tnml_site_step_* in the labels
+// mode), a device accumulator block that gets one k_eval_tally launch per chunk; want_grad false leaves k_site_grad out
+struct SiteGradPlan { EvalAcc* acc; bool want_grad; int maxbond, rows, nblocks; };
 // the chunk loop of sitegrad_device in the element type E of option gradient_dtype; the tables are on the device
-struct SiteGradCall {
-    const char* who; int64_t n; const uint8_t* pixels; const double* phi; const int32_t* labels; const double* coef; double* weights; int32_t* pred;
-    EvalAcc* acc; double* dphi; bool want_grad; int maxbond, rows, nblocks;
-};
 template <typename E>
-static int sitegrad_chunks(tnml_ctx* c, const SiteGradCall& k, StreamIO& io) {
+static int sitegrad_chunks(tnml_ctx* c, const StreamCall& k, const SiteGradPlan& g) {
     constexpr bool f32 = sizeof(E) == sizeof(float);
-    const StreamWs& s = c->sg;
+    GradientWs& s = c->sg;
     const int N = c->N, nl = c->nl(), cs = c->single() ? 1 : c->c0;
-    const bool bytes_form = k.pixels != nullptr, want_dphi = k.dphi || io.dphi32;
-    const bool mapped = bytes_form && c->im_set;
-    const StageGeom sg = mapped ? stage_geom(c) : StageGeom{};
+    const StageGeom sg = k.bytes_form() && c->im_set ? stage_geom(c) : StageGeom{};
     SiteGradArgsT<E> a;
-    E* xphi; const ChainSite<E>* sites;
-    if constexpr (f32) {                                           // the copy of W, the features and the table rounded to fp32; the range flag
-        xphi = c->sg_xphi32; sites = c->sg_tab32;
-        chain_args(c, s, sites, bytes_form, (const float*)c->sg_mtab32, (const float*)xphi, a.ch);
-        a.ch.flag = c->sg_flag;
-    } else {
-        xphi = s.xphi; sites = s.tab;
-        chain_args(c, s, sites, bytes_form, (const double*)s.mtab, (const double*)xphi, a.ch);
-    }
-    a.rowoff = c->sg_rowoff; a.tape = (E*)c->sg_tape; a.tape2 = (E*)c->sg_tape2;
-    a.lab = k.labels ? c->sg_lab : nullptr; a.target = c->target(); a.coef = c->sg_coef;
-    a.grad = c->sg_grad; a.goff = c->sg_goff; a.blk0 = c->sg_blk0;
+    chain_args(c, s, k.bytes_form(), a.ch);
+    a.rowoff = s.rowoff; a.tape = (E*)s.tape; a.tape2 = (E*)s.tape2;
+    a.lab = k.labels ? s.lab : nullptr; a.target = c->target(); a.coef = s.coef;
+    a.grad = s.grad; a.goff = s.goff; a.blk0 = s.blk0;
     a.loss = k.labels ? c->loss : TNML_LOSS_QUADRATIC; a.beta = c->loss_beta;      // (coefficients as given know no loss)
-    const size_t tape_elems = c->sg_tape_rows * (size_t)s.cap;
+    const size_t tape_elems = s.tape_rows * (size_t)s.cap;
     for (int64_t off = 0; off < k.n; off += c->gradient_chunk) {
         a.ch.cnt = (int)std::min<int64_t>(c->gradient_chunk, k.n - off);
-        TCK(stage_chunk<E>(c, s, mapped, sg, k.pixels, k.phi, off, a.ch.cnt, xphi, io));
-        chunk_dest(c, s, io, off, k.weights, k.pred, &a.ch.wout, &a.ch.pred);
-        if (k.labels) HIPCK(c, hipMemcpyAsync(c->sg_lab, k.labels + off, sizeof(int32_t) * (size_t)a.ch.cnt, io.in(), c->stream));
-        else          HIPCK(c, hipMemcpyAsync(c->sg_coef, k.coef + (size_t)off * nl, sizeof(double) * (size_t)a.ch.cnt * nl, io.in(), c->stream));
-        const int T = chain_tile<E>(c, k.maxbond, a.ch.cnt);
-        TCK(launch_site_gradient<E>(c, a, k.maxbond, T, k.rows, tape_elems, k.nblocks, k.want_grad));
+        TCK(stage_chunk<E>(c, s, k, sg, off, a.ch.cnt));
+        chunk_dest(c, s, k, off, &a.ch.wout, &a.ch.pred);
+        if (k.labels) HIPCK(c, hipMemcpyAsync(s.lab, k.labels + off, sizeof(int32_t) * (size_t)a.ch.cnt, k.in(), c->stream));
+        else          HIPCK(c, hipMemcpyAsync(s.coef, k.coef + (size_t)off * nl, sizeof(double) * (size_t)a.ch.cnt * nl, k.in(), c->stream));
+        const int T = chain_tile<E>(c, g.maxbond, a.ch.cnt);
+        TCK(launch_site_gradient<E>(c, a, g.maxbond, T, g.rows, tape_elems, g.nblocks, g.want_grad));
         if constexpr (f32) {                                       // the range flag, before anything of the chunk reaches the caller
             int flag = 0;
-            HIPCK(c, hipMemcpyAsync(&flag, c->sg_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            HIPCK(c, hipMemcpyAsync(&flag, s.f32.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
             SYNCK(c, c->stream);
-            if (flag) {
-                HIPCK(c, hipMemsetAsync(c->sg_flag, 0, sizeof(int), c->stream));
-                HIPCK(c, hipStreamSynchronize(c->stream));
-                return tnml_fail(c, "%s: gradient_dtype = 1 (fp32): a weight of images %lld..%lld is not finite, the chain has left the fp32 range: use fp64 (gradient_dtype = 0)", k.who, (long long)off, (long long)off + a.ch.cnt - 1);
-            }
+            if (flag) return left_fp32_range(c, s, k.who, "gradient_dtype", off, a.ch.cnt);
         }
-        if (want_dphi) {
+        if (k.want_dphi()) {
             InputGradArgsT<E> ig;
-            ig.sites = sites; ig.N = N; ig.cs = cs; ig.nl = nl; ig.ld = s.cap; ig.cnt = a.ch.cnt;
-            ig.rowoff = c->sg_rowoff; ig.tape = (const E*)c->sg_tape; ig.tape2 = (const E*)c->sg_tape2; ig.coef = c->sg_coef; ig.dphi = c->bw_out;
+            ig.sites = sites<E>(s); ig.N = N; ig.cs = cs; ig.nl = nl; ig.ld = s.cap; ig.cnt = a.ch.cnt;
+            ig.rowoff = s.rowoff; ig.tape = (const E*)s.tape; ig.tape2 = (const E*)s.tape2; ig.coef = s.coef; ig.dphi = s.dphi;
             const size_t at = (size_t)off * N * 2;
-            if (io.dev) TCK(launch_input_grad<E>(c, ig, k.maxbond, T, k.rows, tape_elems, k.dphi ? k.dphi + at : nullptr, k.dphi ? nullptr : io.dphi32 + at));
+            if (k.dev) TCK(launch_input_grad<E>(c, ig, g.maxbond, T, g.rows, tape_elems, k.dphi ? k.dphi + at : nullptr, k.dphi ? nullptr : k.dphi32 + at));
             else {
-                TCK(launch_input_grad<E>(c, ig, k.maxbond, T, k.rows, tape_elems, c->bw_outT));
-                HIPCK(c, hipMemcpyAsync(k.dphi + at, c->bw_outT, sizeof(double) * (size_t)a.ch.cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
+                TCK(launch_input_grad<E>(c, ig, g.maxbond, T, g.rows, tape_elems, s.dphiT));
+                HIPCK(c, hipMemcpyAsync(k.dphi + at, s.dphiT, sizeof(double) * (size_t)a.ch.cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
             }
         }
-        if (k.acc && k.labels) TCK(launch_eval_tally(c, a.ch.wout, a.ch.pred, c->sg_lab, a.ch.cnt, nl, a.ch.single, c->target(), k.acc, c->loss, c->loss_beta));
-        c->sg_last_cnt = a.ch.cnt;
-        TCK(chunk_results(c, s, off, a.ch.cnt, k.weights, k.pred, io.dev));
+        if (g.acc && k.labels) TCK(launch_eval_tally(c, a.ch.wout, a.ch.pred, s.lab, a.ch.cnt, nl, a.ch.single, c->target(), g.acc, c->loss, c->loss_beta));
+        s.last_cnt = a.ch.cnt;
+        TCK(chunk_results(c, s, k, off, a.ch.cnt));
     }
     return 0;
 }
 // The part the gradient calls and the step calls share: refusals, staging, tables and the chunk loop.  It leaves the gradient of the n
-// images in c->sg_grad (*elems of them) with the stream synchronised behind the last chunk; n = 0: nothing is launched, *elems alone is
-// set.  out: where the caller's result goes (refused when null).  acc (tnml_site_step_* in the labels mode): a device accumulator
-// block that is zeroed here and gets one k_eval_tally launch per chunk, on the chunk's weights and sg_lab.
-// tnml_backward_*: dphi (or null) receives the input gradients [n][N][2] chunk by chunk, from ONE k_input_grad launch behind the chunk's
-// k_site_backward; want_grad false leaves k_site_grad out.
-// io (device-resident arrays): grad is the caller's device array or null (it enters the pointer checks only: the sum is made in sg_grad as
-// ever); dphi or io.dphi32 receives the transposition directly.
-static int sitegrad_device(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
-                           const void* out, double* weights, int32_t* pred, size_t* elems_out, EvalAcc* acc, double* dphi, bool want_grad, StreamIO& io, double* grad) {
-    int maxbond = 1;
-    TCK(streamed_refusals(c, who, "site gradients", n, &maxbond, true));
-    if (!out) return tnml_fail(c, "%s: null argument", who);
+// images in c->sg.grad (*elems_out of them) with the stream synchronised behind the last chunk; n = 0: nothing is launched, *elems_out
+// alone is set.  A call that would leave nothing anywhere (tnml_site_gradient_* without grad) is refused.  acc is zeroed here.
+// tnml_backward_*: k.dphi (or k.dphi32) receives the input gradients [n][N][2] chunk by chunk, from ONE k_input_grad launch behind the
+// chunk's k_site_backward; device-resident arrays receive the transposition directly.  k.grad enters the pointer checks only: the sum
+// is made in sg.grad as ever, and the caller copies it out.
+static int sitegrad_device(tnml_ctx* c, StreamCall& k, EvalAcc* acc, bool want_grad, size_t* elems_out) {
+    SiteGradPlan g{acc, want_grad, 1, 0, 0};
+    TCK(streamed_refusals(c, k, "site gradients", &g.maxbond, true));
+    if (!k.grad && !k.want_dphi() && !acc) return tnml_fail(c, "%s: null argument", k.who);
     const int N = c->N, nl = c->nl(), cs = c->single() ? 1 : c->c0;
-    if (c->W[cs].L != nl) return tnml_fail(c, "%s: the Label site %d of W carries %d labels, the context has %d", who, cs, c->W[cs].L, nl);
+    if (c->W[cs].L != nl) return tnml_fail(c, "%s: the Label site %d of W carries %d labels, the context has %d", k.who, cs, c->W[cs].L, nl);
     std::vector<long long> goff(N + 1);
     const size_t elems = sitegrad_layout(c, goff.data());
     *elems_out = elems;
-    if (n == 0) return 0;
-    TCK(sitegrad_inputs(c, who, n, pixels, phi, labels, coef, io, DevOuts{weights, pred, nullptr, grad, dphi}));
+    if (k.n == 0) return 0;
+    TCK(sitegrad_inputs(c, k));
     HIPCK(c, hipSetDevice(c->cfg.device));
-    const StreamWs& s = c->sg;
-    const bool want_dphi = dphi || io.dphi32;
+    const GradientWs& s = c->sg;
     std::vector<int> rowoff(N + 2);                             // both tapes share the region table (kernels_sitegrad.hip)
-    const int rows = tape_rows(c, rowoff);
+    g.rows = tape_rows(c, rowoff);
     // output blocks of 32 x 32 per virtual site: the sites in order, the Label site once per label
     std::vector<int> blk0(N + nl);
-    int nblocks = 0, v = 0;
+    int v = 0;
     for (int j = 1; j <= N; ++j) {
         const int nb = ((c->W[j].ml + 31) / 32) * ((c->W[j].mr + 31) / 32);
-        for (int l = 0; l < (j == cs ? nl : 1); ++l) { blk0[v++] = nblocks; nblocks += nb; }
+        for (int l = 0; l < (j == cs ? nl : 1); ++l) { blk0[v++] = g.nblocks; g.nblocks += nb; }
     }
-    blk0[v] = nblocks;
-    const bool bytes_form = pixels != nullptr, f32 = c->gradient_dtype == TNML_GRADIENT_F32;
-    TCK(sitegrad_workspace(c, who, bytes_form, (size_t)rows, elems, io.dev, f32));
-    if (want_dphi) {                                            // the first call that asks for dphi: the result as the kernel leaves it and as a host caller gets it
-        int rc = 0;
-        if (!c->bw_out) rc = ws_alloc(c, c->sg, (void**)&c->bw_out, (size_t)2 * N * s.cap * sizeof(double));
-        if (!rc && !io.dev && !c->bw_outT) rc = ws_alloc(c, c->sg, (void**)&c->bw_outT, (size_t)2 * N * s.cap * sizeof(double));
-        if (rc) { sitegrad_release(c); return rc; }
-    }
+    blk0[v] = g.nblocks;
+    const bool f32 = c->gradient_dtype == TNML_GRADIENT_F32;
+    TCK(sitegrad_workspace(c, k, (size_t)g.rows, elems, f32));
     std::vector<ChainSite<double>> tab;
     TCK(upload_sites(c, s, tab));
-    HIPCK(c, hipMemcpyAsync(c->sg_rowoff, rowoff.data(), sizeof(int) * (N + 2), hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(c->sg_goff, goff.data(), sizeof(long long) * (N + 1), hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(c->sg_blk0, blk0.data(), sizeof(int) * (N + nl), hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemsetAsync(c->sg_grad, 0, elems * sizeof(double), c->stream));       // the sum starts from zero: grad is overwritten
+    HIPCK(c, hipMemcpyAsync(s.rowoff, rowoff.data(), sizeof(int) * (N + 2), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(s.goff, goff.data(), sizeof(long long) * (N + 1), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(s.blk0, blk0.data(), sizeof(int) * (N + nl), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemsetAsync(s.grad, 0, elems * sizeof(double), c->stream));       // the sum starts from zero: grad is overwritten
     if (acc) HIPCK(c, hipMemsetAsync(acc, 0, sizeof(EvalAcc), c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (the tables leave scope with this call)
-    if (f32) TCK(workspace32(c, c->sg, Ws32{&c->sg_tab32, &c->sg_flag, &c->sg_w32, &c->sg_w32_cap, &c->sg_mtab32, &c->sg_mtab32_bytes, sitegrad_release, who, who}, bytes_form && c->im_set, tab));
-    const SiteGradCall k{who, n, pixels, phi, labels, coef, weights, pred, acc, dphi, want_grad, maxbond, rows, nblocks};
-    return f32 ? sitegrad_chunks<float>(c, k, io) : sitegrad_chunks<double>(c, k, io);
+    if (f32) TCK(workspace32(c, c->sg, sitegrad_release, k.who, k.who, k.bytes_form() && c->im_set, tab));
+    return f32 ? sitegrad_chunks<float>(c, k, g) : sitegrad_chunks<double>(c, k, g);
 }
-static int sitegrad_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
-                         double* grad, double* weights, int32_t* pred) {
+static int sitegrad_impl(tnml_ctx* c, StreamCall& k) {
     size_t elems = 0;
-    StreamIO io;
-    TCK(sitegrad_device(c, who, n, pixels, phi, labels, coef, grad, weights, pred, &elems, nullptr, nullptr, true, io, nullptr));
-    if (n == 0) { memset(grad, 0, elems * sizeof(double)); return 0; }
-    HIPCK(c, hipMemcpyAsync(grad, c->sg_grad, elems * sizeof(double), hipMemcpyDeviceToHost, c->stream));   // the one copy of the gradient
+    TCK(images_given(c, k));
+    TCK(sitegrad_device(c, k, nullptr, true, &elems));
+    if (k.n == 0) { memset(k.grad, 0, elems * sizeof(double)); return 0; }
+    HIPCK(c, hipMemcpyAsync(k.grad, c->sg.grad, elems * sizeof(double), hipMemcpyDeviceToHost, c->stream));   // the one copy of the gradient
     SYNCK(c, c->stream);
     return 0;
 }
 int tnml_site_gradient_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const int32_t* labels, const double* coef, double* grad, double* weights, int32_t* pred) {
-    if (n > 0 && !pixels) return tnml_fail(c, "tnml_site_gradient_u8: null argument");
-    return sitegrad_impl(c, "tnml_site_gradient_u8", n, pixels, nullptr, labels, coef, grad, weights, pred);
+    StreamCall k{"tnml_site_gradient_u8", n, pixels};
+    k.labels = labels; k.coef = coef; k.grad = grad; k.weights = weights; k.pred = pred;
+    return sitegrad_impl(c, k);
 }
 int tnml_site_gradient_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* labels, const double* coef, double* grad, double* weights, int32_t* pred) {
-    if (n > 0 && !phi) return tnml_fail(c, "tnml_site_gradient_phi: null argument");
-    return sitegrad_impl(c, "tnml_site_gradient_phi", n, nullptr, phi, labels, coef, grad, weights, pred);
+    StreamCall k{"tnml_site_gradient_phi", n, nullptr, phi};
+    k.labels = labels; k.coef = coef; k.grad = grad; k.weights = weights; k.pred = pred;
+    return sitegrad_impl(c, k);
 }
 
 // ---- streamed input gradients (kernels_inputgrad.hip): dC/dphi of every site of every image, beside or instead of dC/dA ----------------
 // The gradient call's refusals, workspace, staging and k_site_backward launch; per chunk k_site_grad runs when grad is asked for and ONE
 // k_input_grad launch on the two tapes when dphi is, its result transposed on the device and copied back with the chunk.
-static int backward_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
-                         double* grad, double* dphi, double* weights, int32_t* pred, StreamIO io = StreamIO()) {
-    if (c && !grad && !dphi && !io.dphi32) return tnml_fail(c, "%s: grad and dphi are both NULL: the call would compute nothing", who);
+static int backward_impl(tnml_ctx* c, StreamCall& k) {
+    TCK(images_given(c, k));
+    if (c && !k.grad && !k.want_dphi()) return tnml_fail(c, "%s: grad and dphi are both NULL: the call would compute nothing", k.who);
     size_t elems = 0;
-    const void* out = grad ? (const void*)grad : dphi ? (const void*)dphi : (const void*)io.dphi32;
-    TCK(sitegrad_device(c, who, n, pixels, phi, labels, coef, out, weights, pred, &elems, nullptr, dphi, grad != nullptr, io, io.dev ? grad : nullptr));
-    if (n == 0) {
-        if (grad && !io.dev) memset(grad, 0, elems * sizeof(double));
-        if (grad && io.dev) {                                   // (no chunk has run: the checks of the one array the call touches, made here)
-            TCK(dev_check_args(c, who, {{"grad", grad, elems * sizeof(double), 8, true}}));
-            TCK(dev_entry_wait(c, who, io.stream));
+    TCK(sitegrad_device(c, k, nullptr, k.grad != nullptr, &elems));
+    double* const grad = k.grad;
+    if (k.n == 0) {
+        if (grad && !k.dev) memset(grad, 0, elems * sizeof(double));
+        if (grad && k.dev) {                                    // (no chunk has run: the checks of the one array the call touches, made here)
+            TCK(dev_check_args(c, k.who, {{"grad", grad, elems * sizeof(double), 8, true}}));
+            TCK(dev_entry_wait(c, k.who, k.stream));
             HIPCK(c, hipMemsetAsync(grad, 0, elems * sizeof(double), c->stream));
             SYNCK(c, c->stream);
         }
         return 0;
     }
     if (!grad) return 0;                                        // (the chunk loop ends on a synchronisation)
-    HIPCK(c, hipMemcpyAsync(grad, c->sg_grad, elems * sizeof(double), io.dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(grad, c->sg.grad, elems * sizeof(double), k.dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     SYNCK(c, c->stream);
     return 0;
 }
 int tnml_backward_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const int32_t* labels, const double* coef, double* grad, double* dphi, double* weights, int32_t* pred) {
-    if (n > 0 && !pixels) return tnml_fail(c, "tnml_backward_u8: null argument");
-    return backward_impl(c, "tnml_backward_u8", n, pixels, nullptr, labels, coef, grad, dphi, weights, pred);
+    StreamCall k{"tnml_backward_u8", n, pixels};
+    k.labels = labels; k.coef = coef; k.grad = grad; k.dphi = dphi; k.weights = weights; k.pred = pred;
+    return backward_impl(c, k);
 }
 int tnml_backward_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* labels, const double* coef, double* grad, double* dphi, double* weights, int32_t* pred) {
-    if (n > 0 && !phi) return tnml_fail(c, "tnml_backward_phi: null argument");
-    return backward_impl(c, "tnml_backward_phi", n, nullptr, phi, labels, coef, grad, dphi, weights, pred);
+    StreamCall k{"tnml_backward_phi", n, nullptr, phi};
+    k.labels = labels; k.coef = coef; k.grad = grad; k.dphi = dphi; k.weights = weights; k.pred = pred;
+    return backward_impl(c, k);
 }
 
 // ---- gradient steps on the device (kernels_sitestep.hip): the gradient above, then ONE optimiser step on W where it lies ----------------
@@ -840,25 +815,28 @@ static int step_check_params(tnml_ctx* c, const char* who, const tnml_step_param
     }
     return 0;
 }
-static int sitestep_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t* pixels, const double* phi, const int32_t* labels, const double* coef,
-                         const tnml_step_params* p, tnml_step_report* rep, StreamIO io = StreamIO()) {
+static int sitestep_impl(tnml_ctx* c, StreamCall& k, const tnml_step_params* p, tnml_step_report* rep) {
+    const char* who = k.who;
+    const int32_t* labels = k.labels;
+    const int64_t n = k.n;
     int maxbond = 1;
-    TCK(streamed_refusals(c, who, "site gradients", n, &maxbond, true));
+    TCK(images_given(c, k));
+    TCK(streamed_refusals(c, k, "site gradients", &maxbond, true));
     TCK(ho_locked(c, who, true));                               // as tnml_set_site: W of a training context with a held-out context attached changes in bond updates only
     if (c->cfg.nranks != 1) return tnml_fail(c, "%s: the context is rank %d of %d: a step enters no collective, the replicas of W would part (one rank only)", who, c->cfg.rank, c->cfg.nranks);
     TCK(step_check_params(c, who, p));
     if (n == 0) { if (rep) memset(rep, 0, sizeof(*rep)); return 0; }
     const int cs = c->single() ? 1 : c->c0;
     if (c->W[cs].L != c->nl()) return tnml_fail(c, "%s: the Label site %d of W carries %d labels, the context has %d", who, cs, c->W[cs].L, c->nl());
-    TCK(sitegrad_inputs(c, who, n, pixels, phi, labels, coef, io, DevOuts{})); // (before the state is made: a refused call leaves nothing behind)
+    TCK(sitegrad_inputs(c, k));                                 // (before the state is made: a refused call leaves nothing behind)
     HIPCK(c, hipSetDevice(c->cfg.device));
     TCK(step_state_for(c, who, p->method));
     size_t elems = 0;
-    TCK(sitegrad_device(c, who, n, pixels, phi, labels, coef, p, nullptr, nullptr, &elems, c->st_acc, nullptr, true, io, nullptr));
+    TCK(sitegrad_device(c, k, c->st_acc, true, &elems));
     if (elems != c->st_elems) return tnml_fail(c, "%s: the gradient has %zu elements, the optimiser state %zu (tnml_site_step_reset first)", who, elems, c->st_elems);
     SiteStepArgs a;
-    a.sites = c->sg.tab; a.goff = c->sg_goff; a.wg0 = c->st_wg0; a.N = c->N;
-    a.grad = c->sg_grad; a.elems = elems; a.m = c->st_m; a.v = c->st_v; a.bsum = c->st_bsum; a.nblk = c->st_nblk; a.res = c->st_res;
+    a.sites = c->sg.tab; a.goff = c->sg.goff; a.wg0 = c->st_wg0; a.N = c->N;
+    a.grad = c->sg.grad; a.elems = elems; a.m = c->st_m; a.v = c->st_v; a.bsum = c->st_bsum; a.nblk = c->st_nblk; a.res = c->st_res;
     a.method = p->method; a.lr = p->lr; a.mu = p->momentum; a.beta1 = p->beta1; a.beta2 = p->beta2; a.eps = p->eps; a.clip = p->clip; a.scale = p->scale;
     // Adam's powers: one multiplication per step, kept only when the step is applied
     const double p1 = c->st_p1 * p->beta1, p2 = c->st_p2 * p->beta2;
@@ -885,21 +863,23 @@ static int sitestep_impl(tnml_ctx* c, const char* who, int64_t n, const uint8_t*
     return 0;
 }
 int tnml_site_step_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, const int32_t* labels, const double* coef, const tnml_step_params* p, tnml_step_report* rep) {
-    if (n > 0 && !pixels) return tnml_fail(c, "tnml_site_step_u8: null argument");
-    return sitestep_impl(c, "tnml_site_step_u8", n, pixels, nullptr, labels, coef, p, rep);
+    StreamCall k{"tnml_site_step_u8", n, pixels};
+    k.labels = labels; k.coef = coef;
+    return sitestep_impl(c, k, p, rep);
 }
 int tnml_site_step_phi(tnml_ctx* c, int64_t n, const double* phi, const int32_t* labels, const double* coef, const tnml_step_params* p, tnml_step_report* rep) {
-    if (n > 0 && !phi) return tnml_fail(c, "tnml_site_step_phi: null argument");
-    return sitestep_impl(c, "tnml_site_step_phi", n, nullptr, phi, labels, coef, p, rep);
+    StreamCall k{"tnml_site_step_phi", n, nullptr, phi};
+    k.labels = labels; k.coef = coef;
+    return sitestep_impl(c, k, p, rep);
 }
 int tnml_site_gradient_coef(tnml_ctx* c, double* out, int64_t count) {
     if (!c || !out) return tnml_fail(c, "tnml_site_gradient_coef: null argument");
-    if (c->sg_last_cnt < 0 || !c->sg_coef) return tnml_fail(c, "tnml_site_gradient_coef: no gradient or step call has been made since the workspace was made (count = %lld)", (long long)count);
-    const int64_t have = (int64_t)c->sg_last_cnt * c->nl();
-    if (count != have) return tnml_fail(c, "tnml_site_gradient_coef: the last chunk has %d x %d coefficients, count = %lld", c->sg_last_cnt, c->nl(), (long long)count);
+    if (c->sg.last_cnt < 0 || !c->sg.coef) return tnml_fail(c, "tnml_site_gradient_coef: no gradient or step call has been made since the workspace was made (count = %lld)", (long long)count);
+    const int64_t have = (int64_t)c->sg.last_cnt * c->nl();
+    if (count != have) return tnml_fail(c, "tnml_site_gradient_coef: the last chunk has %d x %d coefficients, count = %lld", c->sg.last_cnt, c->nl(), (long long)count);
     HIPCK(c, hipSetDevice(c->cfg.device));
     SYNCK(c, c->stream);
-    HIPCK(c, hipMemcpy(out, c->sg_coef, sizeof(double) * (size_t)have, hipMemcpyDeviceToHost));
+    HIPCK(c, hipMemcpy(out, c->sg.coef, sizeof(double) * (size_t)have, hipMemcpyDeviceToHost));
     return 0;
 }
 int tnml_site_step_state(tnml_ctx* c, const char* which, double* out, int64_t count) {
@@ -917,40 +897,49 @@ int tnml_site_step_state(tnml_ctx* c, const char* which, double* out, int64_t co
 
 // ---- device-resident arguments: the tnml_*_dev entry points (tnml.h) ----------
 // Each is the host-pointer call of its name on the same *_impl, with the memory space of the arrays set to the device.
-static int dev_batch_io(tnml_ctx* c, const char* who, const tnml_dev_batch* b, StreamIO* io) {
+// The record of a device-resident call from its batch and its outputs (o may be null).  takes: what the call takes beside the images,
+// weights and pred; the other fields of b and o are not looked at, as tnml.h promises.
+enum { IN_LABELS = 1, IN_COEF = 2, IN_WHICH = 4, OUT_RESP = 8, OUT_GRADS = 16 };
+static int dev_call(tnml_ctx* c, const char* who, const tnml_dev_batch* b, const tnml_dev_out* o, int takes, StreamCall& k) {
     if (!c || !b) return tnml_fail(c, "%s: null argument", who);
     const int given = (b->pixels != nullptr) + (b->phi != nullptr) + (b->phi32 != nullptr);
     if (given > 1) return tnml_fail(c, "%s: exactly one of pixels, phi and phi32 must be given (%d are)", who, given);
     if (b->n > 0 && !given) return tnml_fail(c, "%s: null argument", who);
-    io->dev = true; io->phi32 = b->phi32; io->stream = b->stream;
+    k = StreamCall{who, b->n, b->pixels, b->phi, b->phi32};
+    if (takes & IN_LABELS) k.labels = b->labels;
+    if (takes & IN_COEF) k.coef = b->coef;
+    if (takes & IN_WHICH) k.which = b->which;
+    if (o) { k.weights = o->weights; k.pred = o->pred; }
+    if (o && (takes & OUT_RESP)) k.resp = o->resp;
+    if (o && (takes & OUT_GRADS)) { k.grad = o->grad; k.dphi = o->dphi; k.dphi32 = o->dphi32; }
+    k.dev = true; k.stream = b->stream;
     return 0;
 }
 int tnml_predict_dev(tnml_ctx* c, const tnml_dev_batch* b, const tnml_dev_out* o) {
-    StreamIO io;
-    TCK(dev_batch_io(c, "tnml_predict_dev", b, &io));
-    return predict_impl(c, "tnml_predict_dev", b->n, b->pixels, b->phi, o ? o->weights : nullptr, o ? o->pred : nullptr, false, nullptr, nullptr, io);
+    StreamCall k;
+    TCK(dev_call(c, "tnml_predict_dev", b, o, 0, k));
+    return predict_impl(c, k);
 }
 int tnml_evaluate_dev(tnml_ctx* c, const tnml_dev_batch* b, const tnml_dev_out* o, tnml_eval_report* rep) {
-    StreamIO io;
-    TCK(dev_batch_io(c, "tnml_evaluate_dev", b, &io));
-    return predict_impl(c, "tnml_evaluate_dev", b->n, b->pixels, b->phi, o ? o->weights : nullptr, o ? o->pred : nullptr, true, b->labels, rep, io);
+    StreamCall k;
+    TCK(dev_call(c, "tnml_evaluate_dev", b, o, IN_LABELS, k));
+    return predict_impl(c, k, true, rep);
 }
 int tnml_response_dev(tnml_ctx* c, const tnml_dev_batch* b, const tnml_dev_out* o) {
-    StreamIO io;
-    TCK(dev_batch_io(c, "tnml_response_dev", b, &io));
-    return response_impl(c, "tnml_response_dev", b->n, b->pixels, b->phi, b->which, o ? o->resp : nullptr, o ? o->weights : nullptr, o ? o->pred : nullptr, io);
+    StreamCall k;
+    TCK(dev_call(c, "tnml_response_dev", b, o, IN_WHICH | OUT_RESP, k));
+    return response_impl(c, k);
 }
 int tnml_backward_dev(tnml_ctx* c, const tnml_dev_batch* b, const tnml_dev_out* o) {
-    StreamIO io;
-    TCK(dev_batch_io(c, "tnml_backward_dev", b, &io));
-    if (o && o->dphi && o->dphi32) return tnml_fail(c, "tnml_backward_dev: dphi and dphi32 are both given: at most one of the two");
-    io.dphi32 = o ? o->dphi32 : nullptr;
-    return backward_impl(c, "tnml_backward_dev", b->n, b->pixels, b->phi, b->labels, b->coef, o ? o->grad : nullptr, o ? o->dphi : nullptr, o ? o->weights : nullptr, o ? o->pred : nullptr, io);
+    StreamCall k;
+    TCK(dev_call(c, "tnml_backward_dev", b, o, IN_LABELS | IN_COEF | OUT_GRADS, k));
+    if (k.dphi && k.dphi32) return tnml_fail(c, "tnml_backward_dev: dphi and dphi32 are both given: at most one of the two");
+    return backward_impl(c, k);
 }
 int tnml_site_step_dev(tnml_ctx* c, const tnml_dev_batch* b, const tnml_step_params* p, tnml_step_report* rep) {
-    StreamIO io;
-    TCK(dev_batch_io(c, "tnml_site_step_dev", b, &io));
-    return sitestep_impl(c, "tnml_site_step_dev", b->n, b->pixels, b->phi, b->labels, b->coef, p, rep, io);
+    StreamCall k;
+    TCK(dev_call(c, "tnml_site_step_dev", b, nullptr, IN_LABELS | IN_COEF, k));
+    return sitestep_impl(c, k, p, rep);
 }
 // test entry: sizeof and the field offsets, in declaration order, of the two structs of this section as this library was compiled
 int tnml_abi_layout(const char* name, int64_t* sizes_out) {

@@ -130,16 +130,49 @@ struct HeldOut {
 
 template <typename E> struct ChainSite;      // kernels_chain.hip, below
 
-// What the workspaces of the streamed calls share (tnml_infer.hip): the results and the staging buffers of one chunk of `cap` images.
-// The staging buffers are allocated by the first call of their input form.
+// The workspaces of the streamed calls (tnml_infer.hip).  Each is allocated by the first call, counted in tnml_ctx::bytes and its own `bytes`,
+// re-made when its chunk option changes and freed by tnml_destroy; none touches another.  A workspace names its device buffers once (buffers(),
+// and own() for those it alone has): release frees them and assigns a default-constructed struct, so every pointer, size and capacity starts over.
+template <typename... P> std::vector<void**> ws_ptrs(P**... p) { return {(void**)p...}; }
+// the fp32 side of a workspace (predict under predict_dtype = 1, the gradient calls under gradient_dtype = 1), made by the first such call
+struct StreamWs32 {
+    float* w32 = nullptr; size_t w32_cap = 0;         // the fp32 copy of W, re-made by every call and grown when W has grown: [w32_cap] floats, every site tensor starting at a multiple of 4 floats
+    ChainSite<float>* tab32 = nullptr; int* flag = nullptr;   // [N] per-site table of the copy; raised by the float kernels when a weight is not finite
+    float* xphi32 = nullptr;                          // features of a chunk site-first [N][2][cap], rounded to fp32 (first fp32 call of the features form)
+    float* mtab32 = nullptr; int64_t mtab32_bytes = 0;   // the input map's table rounded to fp32 [ncodes][2] (first fp32 call of the bytes form under a map)
+};
+// what the three share: the results and the staging buffers of one chunk of `cap` images, the latter allocated by the first call of their input form
 struct StreamWs {
     int cap = 0; int64_t bytes = 0;                   // the chunk option rounded up to 64 when the workspace was sized; everything allocated for it
     ChainSite<double>* tab = nullptr;                 // [N] per-site table (ml, mr, address)
     double* w = nullptr; int* pred = nullptr;         // [cap][nl], [cap]: weights and pred of a chunk
     uint8_t *raw8 = nullptr, *x8 = nullptr;           // bytes of a chunk as given [cap][N] and site-first [N][cap]
     double *rawphi = nullptr, *xphi = nullptr;        // features of a chunk as given [cap][N][2] and site-first [N][2][cap]
-    uint8_t* mraw = nullptr;                          // under an input map: bytes of a chunk as given [cap][S],
-    uint16_t* codes = nullptr; double* mtab = nullptr;   // its block sums site-first [N][cap] and the fp64 table [ncodes][2]
+    uint8_t* mraw = nullptr; uint16_t* codes = nullptr; double* mtab = nullptr;   // under an input map: bytes of a chunk as given [cap][S], its block sums site-first [N][cap] and the fp64 table [ncodes][2]
+    StreamWs32 f32;
+    std::vector<void**> buffers() { return ws_ptrs(&tab, &w, &pred, &raw8, &x8, &rawphi, &xphi, &mraw, &codes, &mtab, &f32.w32, &f32.tab32, &f32.flag, &f32.xphi32, &f32.mtab32); }
+};
+struct PredictWs : StreamWs {                         // tnml_predict_* / tnml_evaluate_* (cap: predict_chunk rounded up to 64)
+    double* park = nullptr; size_t park_elems = 0;    // [cap / T][ru16(m)][T]: the parked right-chain vectors of the workgroups (when three tiles do not fit the LDS)
+    int* lab = nullptr; EvalAcc* acc = nullptr;       // first tnml_evaluate_* call: [cap] labels of a chunk; the tallies of the call in progress (k_eval_tally adds a chunk, the host reads them once at the end)
+    int64_t map_bytes = 0;                            // of bytes, what mraw, codes and mtab take: tnml_set_input_map releases this part only
+    std::vector<void**> own() { return ws_ptrs(&park, &lab, &acc); }
+};
+struct ResponseWs : StreamWs {                        // tnml_response_*; released whole by every tnml_set_input_map call
+    int *which = nullptr, *rowoff = nullptr;          // [cap] labels asked for; [N + 4] rows of the tape regions (kernels_response.hip)
+    double *out = nullptr, *outT = nullptr;           // the result of a chunk as the kernel leaves it [N][2][cap] and as the caller gets it [cap][N][2]
+    double* tape = nullptr; size_t tape_rows = 0;     // [cap / T][tape_rows][T]: every chain vector of every image; grown when W has grown
+    std::vector<void**> own() { return ws_ptrs(&which, &rowoff, &out, &outT, &tape); }
+};
+struct GradientWs : StreamWs {                        // tnml_site_gradient_*, tnml_backward_*, tnml_site_step_*; released whole by every tnml_set_input_map call
+    int esz = 8, last_cnt = -1;                       // bytes of a tape element (the tapes are re-made when option gradient_dtype changes); images of the last chunk a gradient or step call ran in this workspace (tnml_site_gradient_coef), -1: none yet
+    int* lab = nullptr; double* coef = nullptr;       // [cap] labels of a chunk; [cap][nl] its coefficients (given, or formed by k_site_backward)
+    int* rowoff = nullptr;                            // [N + 2] rows of the tape regions of bond 0..N, then the rows of a slice
+    long long* goff = nullptr; int* blk0 = nullptr;   // [N + 1] first element of every site in grad; [N + nl] first output block of every virtual site, then the block count
+    double* grad = nullptr; size_t grad_elems = 0;    // the gradient of the call in progress, every site in tnml_get_site's layout; grown when W has grown
+    double *tape = nullptr, *tape2 = nullptr; size_t tape_rows = 0;   // [cap / T][tape_rows][T] each: inward and outward vectors; grown when W has grown
+    double *dphi = nullptr, *dphiT = nullptr;         // from the first call that asks for input gradients on: dphi of a chunk as the kernel leaves it [N][2][cap] and as the caller gets it [cap][N][2]
+    std::vector<void**> own() { return ws_ptrs(&lab, &coef, &rowoff, &goff, &blk0, &grad, &tape, &tape2, &dphi, &dphiT); }
 };
 
 struct tnml_ctx {
@@ -316,58 +349,20 @@ struct tnml_ctx {
     int predict_chunk = TNML_PREDICT_CHUNK_DEFAULT;        // option "predict_chunk": images staged, launched (one k_chain launch) and copied back per trip of the host loop
     int predict_tile = 0;            // test knob (option "predict_tile"): images per workgroup of k_chain, 16 / 32 / 64 (capped by the LDS budget); 0: by bond dimension and image count
     bool attr_chain[2][2] = {};      // [fp32][input map]: the LDS attribute of those k_chain instantiations is set
-    // option "predict_dtype": 0 k_chain<double>, 1 k_chain<float> (both kernels_chain.hip).  The fp32 workspace, allocated by the
-    // first fp32 call (counted in `bytes` and pk.bytes, freed with the rest): the fp32 copy of W, re-made by every call and grown when W has grown,
-    // its site table, the range flag, and what the staging of the input form needs
-    int predict_dtype = 0;
-    float* pk_w32 = nullptr; size_t pk_w32_cap = 0;   // [pk_w32_cap] floats: every site tensor, each starting at a multiple of 4 floats
-    ChainSite<float>* pk_tab32 = nullptr;              // [N] per-site table of the copy
-    int* pk_flag = nullptr;                            // raised by k_chain<float> when a weight is not finite
-    float* pk_xphi32 = nullptr;                        // features of a chunk site-first [N][2][pk.cap], rounded to fp32 (first fp32 tnml_predict_phi)
-    int64_t pk_mtab32_bytes = 0;
-    float* pk_mtab32 = nullptr;                        // the input map's table rounded to fp32 [ncodes][2] (first fp32 tnml_predict_u8 under a map)
-    // The three streamed workspaces (StreamWs above): allocated by the first call, counted in `bytes` and in their own `bytes`, re-made when their
-    // chunk option changes, freed by tnml_destroy; none touches another.  Beside each, the fields it alone has.
-    StreamWs pk;                     // tnml_predict_* / tnml_evaluate_* (cap: predict_chunk rounded up to 64).  tnml_set_input_map releases its map part only (pk_map_bytes)
-    double* pk_park = nullptr; size_t pk_park_elems = 0;   // [cap / T][ru16(m)][T]: the parked right-chain vectors of the workgroups (when three tiles do not fit the LDS)
-    int* pk_lab = nullptr;           // [cap] labels of a chunk (first tnml_evaluate_* call)
-    EvalAcc* pk_acc = nullptr;       // the tallies of the call in progress (k_eval_tally adds a chunk, the host reads them once at the end)
-    int64_t pk_map_bytes = 0;        // of pk.bytes, what pk.mraw, pk.codes and pk.mtab take
+    int predict_dtype = 0;           // option "predict_dtype": 0 k_chain<double>, 1 k_chain<float> on the fp32 side of `pk` (both kernels_chain.hip)
+    PredictWs pk;
     // streamed site responses (tnml_response_u8 / tnml_response_phi, kernels_response.hip)
     int response_chunk = TNML_RESPONSE_CHUNK_DEFAULT;      // option "response_chunk": images per launch of k_response
     bool attr_response[2] = {};      // [input map]: the LDS attribute of those k_response instantiations is set
-    StreamWs rs;                     // released whole by every tnml_set_input_map call
-    int* rs_which = nullptr;                               // [cap] labels asked for
-    int* rs_rowoff = nullptr;                              // [N + 4] rows of the tape regions (kernels_response.hip)
-    double *rs_out = nullptr, *rs_outT = nullptr;          // the result of a chunk as the kernel leaves it [N][2][cap] and as the caller gets it [cap][N][2]
-    double* rs_tape = nullptr; size_t rs_tape_rows = 0;    // [cap / T][rs_tape_rows][T]: every chain vector of every image; grown when W has grown
-    // streamed site gradients (tnml_site_gradient_u8 / tnml_site_gradient_phi, kernels_sitegrad.hip)
+    ResponseWs rs;
+    // streamed site gradients (tnml_site_gradient_*, kernels_sitegrad.hip) and input gradients (tnml_backward_*, kernels_inputgrad.hip)
     int gradient_chunk = TNML_GRADIENT_CHUNK_DEFAULT;      // option "gradient_chunk": images per launch of k_site_backward / k_site_grad
     bool attr_sitegrad[2][2] = {};   // [fp32][input map]: the LDS attribute of those k_site_backward instantiations is set
     bool attr_sitegrad_sm[2][2] = {};   // the same for the instantiations of the softmax loss
-    // option "gradient_dtype": 0 the gradient kernels in fp64 on W where it lives, 1 their float instantiations on an fp32 copy of W
-    // (kernels_sitegrad.hip, kernels_inputgrad.hip).  The tapes hold elements of sg_esz bytes and are re-made when the option changes; the
-    // fp32 side of the workspace `sg` -- the copy of W (re-made by every call, grown when W has grown), its site table, the range flag
-    // and what the staging of the input form needs -- is made by the first fp32 call and released with the workspace
-    int gradient_dtype = 0;
-    int sg_esz = 8;
-    float* sg_w32 = nullptr; size_t sg_w32_cap = 0;
-    ChainSite<float>* sg_tab32 = nullptr;
-    int* sg_flag = nullptr;
-    float* sg_xphi32 = nullptr;                            // features of a chunk site-first [N][2][sg.cap], rounded to fp32
-    float* sg_mtab32 = nullptr; int64_t sg_mtab32_bytes = 0;   // the input map's table rounded to fp32
+    int gradient_dtype = 0;          // option "gradient_dtype": 0 the gradient kernels in fp64 on W where it lives, 1 their float instantiations on the fp32 side of `sg`
     int loss = TNML_LOSS_QUADRATIC;  // option "loss": the loss of tnml_evaluate_* and of the labels mode of tnml_site_gradient_* / tnml_site_step_*
     double loss_beta = 1.;           // tnml_set_option_real "loss_beta": the inverse temperature of the softmax loss, logits beta W_l
-    int sg_last_cnt = -1;            // images of the last chunk a gradient or step call ran in this workspace (tnml_site_gradient_coef); -1: none yet
-    StreamWs sg;                     // released whole by every tnml_set_input_map call
-    int* sg_lab = nullptr; double* sg_coef = nullptr;      // [cap] labels of a chunk; [cap][nl] its coefficients (given, or formed by k_site_backward)
-    int* sg_rowoff = nullptr;                              // [N + 2] rows of the tape regions of bond 0..N, then the rows of a slice
-    long long* sg_goff = nullptr; int* sg_blk0 = nullptr;  // [N + 1] first element of every site in sg_grad; [N + nl] first output block of every virtual site, then the block count
-    double* sg_grad = nullptr; size_t sg_grad_elems = 0;   // the gradient of the call in progress, every site in tnml_get_site's layout; grown when W has grown
-    double *sg_tape = nullptr, *sg_tape2 = nullptr; size_t sg_tape_rows = 0;   // [cap / T][sg_tape_rows][T] each: inward and outward vectors; grown when W has grown
-    // streamed input gradients (tnml_backward_u8 / tnml_backward_phi, kernels_inputgrad.hip): the gradient workspace `sg` and, from the first call
-    // that asks for dphi on, two buffers of their own, counted in sg.bytes and released with it
-    double *bw_out = nullptr, *bw_outT = nullptr;          // dphi of a chunk as the kernel leaves it [N][2][cap] and as the caller gets it [cap][N][2]
+    GradientWs sg;
     bool attr_inputgrad[2] = {};     // [fp32]: the LDS attribute of the k_input_grad instantiations is set
     // gradient steps on the device (tnml_site_step_u8 / tnml_site_step_phi, kernels_sitestep.hip): the optimiser state.  Allocated by the first
     // step for a method and the site shapes of W at that moment, counted in `bytes` and st_bytes, freed by tnml_site_step_reset and tnml_destroy;
@@ -375,7 +370,7 @@ struct tnml_ctx {
     int st_method = -1;                                    // TNML_STEP_SGD / TNML_STEP_ADAM; -1: no state
     std::vector<int> st_shape;                             // [3 N] ml, mr, L of every site when the state was made
     size_t st_elems = 0; int st_nblk = 0, st_nwg = 0;      // E; norm blocks ceil(E / STEP_NORM_BLOCK); workgroups of the update
-    double *st_m = nullptr, *st_v = nullptr;               // [E] each, laid out like sg_grad (st_m: Adam only)
+    double *st_m = nullptr, *st_v = nullptr;               // [E] each, laid out like sg.grad (st_m: Adam only)
     double* st_bsum = nullptr;                             // [st_nblk] block sums of g^2
     double* st_res = nullptr;                              // [8] what the norm pass leaves: total, grad_norm, factor, clipped, applied
     int* st_wg0 = nullptr;                                 // [N + 1] first update workgroup of every site, then their count

@@ -306,18 +306,12 @@ class TrainStates:
         is bit for bit the host path's."""
         if self._on_device(pixels, phi):
             b, keep = self._dev_batch(pixels, phi, dtype=dtype)
-            w, pred, o = self._dev_weights(b.n, True)
+            w, pred, o = self._weights(b.n, True, dev=True)
             self._ck(self._L.tnml_predict_dev(self._h, C.byref(b), C.byref(o)))
             return w, pred
-        x = self._streamed_input(pixels, phi, dtype)
-        n = int(x.shape[0])
-        w = np.zeros((n, self.nl))
-        pred = np.zeros(n, dtype=np.int32)
-        pp = pred.ctypes.data_as(C.POINTER(C.c_int32))
-        if pixels is not None:
-            self._ck(self._L.tnml_predict_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(w), pp))
-        else:
-            self._ck(self._L.tnml_predict_phi(self._h, n, _lib.dptr(x), _lib.dptr(w), pp))
+        n, keep, (xp, _, _, _) = self._host_batch(pixels, phi, dtype=dtype)
+        w, pred, (wp, pp) = self._weights(n, True)
+        self._ck(self._entry("predict", pixels)(self._h, n, xp, wp, pp))
         return w, pred
 
     # -- device-resident arguments (the tnml_*_dev calls): torch tensors on the context's device, results as device tensors
@@ -340,10 +334,7 @@ class TrainStates:
         float64 or float32, the stream torch's current one"""
         if (pixels is None) == (phi is None):
             raise ValueError("need exactly one of pixels or phi")
-        if dtype is not None:
-            if dtype not in _lib.PREDICT_DTYPES:
-                raise ValueError("dtype must be one of %s, got %r" % (sorted(_lib.PREDICT_DTYPES), dtype))
-            self.set_option("predict_dtype", _lib.PREDICT_DTYPES[dtype])
+        self._set_dtype("predict_dtype", dtype)
         b = _lib.DevBatch()
         if pixels is not None:
             x = pixels.to(torch.uint8).contiguous()
@@ -372,24 +363,73 @@ class TrainStates:
         b.stream = torch.cuda.current_stream(x.device).cuda_stream
         return b, keep
 
-    def _dev_weights(self, n, want, out=None):
-        """-> (weights | None, pred | None, DevOut with both set when want)"""
-        o = out if out is not None else _lib.DevOut()
+    def _host_batch(self, pixels, phi, labels=None, coef=None, which=None, dtype=None):
+        """the host path's _dev_batch -> (n, the arrays the pointers point at, (images, labels, coef, which) as ctypes pointers):
+        every array contiguous and of the call's dtype, None where an array is absent; dtype (when given) becomes option predict_dtype"""
+        if (pixels is None) == (phi is None):
+            raise ValueError("need exactly one of pixels or phi")
+        self._set_dtype("predict_dtype", dtype)
+        if pixels is not None:
+            x = np.ascontiguousarray(pixels, dtype=np.uint8)
+            if x.ndim != 2 or x.shape[1] != self._bytes_per_image:
+                raise ValueError("pixels must have shape [n, %d], got %s" % (self._bytes_per_image, x.shape))
+        else:
+            x = np.ascontiguousarray(phi, dtype=np.float64)
+            assert x.ndim == 3 and x.shape[1:] == (self.N, 2), x.shape
+        n = int(x.shape[0])
+        keep, ptrs = [x], [x.ctypes.data_as(C.POINTER(C.c_uint8 if pixels is not None else C.c_double))]
+        for name, a, dt, ct, shape in (("labels", labels, np.int32, C.c_int32, (n,)), ("coef", coef, np.float64, C.c_double, (n, self.nl)),
+                                       ("which", which, np.int32, C.c_int32, (n,))):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=dt)
+                if a.shape != shape:
+                    raise ValueError("%s must have shape %s, got %s" % (name, list(shape), a.shape))
+                keep.append(a)
+            ptrs.append(None if a is None else a.ctypes.data_as(C.POINTER(ct)))
+        return n, keep, ptrs
+
+    def _entry(self, call, pixels):
+        """the C entry of a streamed call for the input form given: tnml_<call>_u8 or tnml_<call>_phi"""
+        return getattr(self._L, "tnml_%s_%s" % (call, "u8" if pixels is not None else "phi"))
+
+    def _set_dtype(self, option, dtype):
+        """dtype (when given) becomes option predict_dtype or gradient_dtype, for this call and the ones after it"""
+        if dtype is not None:
+            known = _lib.PREDICT_DTYPES if option == "predict_dtype" else _lib.GRADIENT_DTYPES
+            if dtype not in known:
+                raise ValueError("dtype must be one of %s, got %r" % (sorted(known), dtype))
+            self.set_option(option, known[dtype])
+
+    def _weights(self, n, want, dev=False):
+        """the want_weights pair of a call on n images -> (weights | None, pred | None, where the library leaves them): on the host
+        path their two ctypes pointers, on the device path (dev) a DevOut with both set; without want nothing is made or set"""
+        if dev:
+            o, where = _lib.DevOut(), torch.device("cuda", self.device)
+            if not want:
+                return None, None, o
+            w, pred = torch.empty((n, self.nl), dtype=torch.float64, device=where), torch.empty(n, dtype=torch.int32, device=where)
+            o.weights, o.pred = w.data_ptr(), pred.data_ptr()
+            return w, pred, o
         if not want:
-            return None, None, o
-        dev = torch.device("cuda", self.device)
-        w = torch.empty((n, self.nl), dtype=torch.float64, device=dev)
-        pred = torch.empty(n, dtype=torch.int32, device=dev)
-        o.weights, o.pred = w.data_ptr(), pred.data_ptr()
-        return w, pred, o
+            return None, None, (None, None)
+        w, pred = np.zeros((n, self.nl)), np.zeros(n, dtype=np.int32)
+        return w, pred, (_lib.dptr(w), pred.ctypes.data_as(C.POINTER(C.c_int32)))
+
+    def _gradient_buffer(self, dev=False):
+        """a flat zero array (device: an empty tensor) for the gradient of every site, in the layout of tnml_site_gradient_*'s grad"""
+        elems = C.c_int64()
+        self._ck(self._L.tnml_site_gradient_size(self._h, C.byref(elems), None))
+        if dev:
+            return torch.empty(max(elems.value, 1), dtype=torch.float64, device=torch.device("cuda", self.device))
+        return np.zeros(max(elems.value, 1))
+
+    def _site_shape(self, j):
+        ml, mr, hl = C.c_int(), C.c_int(), C.c_int()
+        self._ck(self._L.tnml_site_dims(self._h, j, ml, mr, hl))
+        return (ml.value, 2, mr.value) + ((NL,) if hl.value else ())
 
     def _site_shapes(self):
-        out = []
-        for j in range(1, self.N + 1):
-            ml, mr, hl = C.c_int(), C.c_int(), C.c_int()
-            self._ck(self._L.tnml_site_dims(self._h, j, ml, mr, hl))
-            out.append((ml.value, 2, mr.value) + ((NL,) if hl.value else ()))
-        return out
+        return [self._site_shape(j) for j in range(1, self.N + 1)]
 
     @staticmethod
     def _fstrides(shape):
@@ -411,17 +451,14 @@ class TrainStates:
     def _backward_dev(self, labels, coef, pixels, phi, want_sites, want_inputs, want_weights):
         b, keep = self._dev_batch(pixels, phi, labels, coef)
         n = int(b.n)
-        dev = torch.device("cuda", self.device)
-        w, pred, o = self._dev_weights(n, want_weights)
+        w, pred, o = self._weights(n, want_weights, dev=True)
         grad = dphi = None
         if want_sites:
-            elems = C.c_int64()
-            self._ck(self._L.tnml_site_gradient_size(self._h, C.byref(elems), None))
-            grad = torch.empty(max(elems.value, 1), dtype=torch.float64, device=dev)
+            grad = self._gradient_buffer(dev=True)
             o.grad = grad.data_ptr()
         if want_inputs:
             f32 = phi is not None and keep[0].dtype == torch.float32
-            dphi = torch.empty((n, self.N, 2), dtype=torch.float32 if f32 else torch.float64, device=dev)
+            dphi = torch.empty((n, self.N, 2), dtype=torch.float32 if f32 else torch.float64, device=torch.device("cuda", self.device))
             if f32:
                 o.dphi32 = dphi.data_ptr()
             else:
@@ -430,23 +467,6 @@ class TrainStates:
         grads = self._split_sites_dev(grad) if want_sites else None
         self._note_chunk(n)
         return (grads, dphi, (w, pred)) if want_weights else (grads, dphi)
-
-    def _streamed_input(self, pixels, phi, dtype):
-        """the images of predict / evaluate as the C call takes them; dtype (when given) becomes option predict_dtype"""
-        if (pixels is None) == (phi is None):
-            raise ValueError("need exactly one of pixels or phi")
-        if dtype is not None:
-            if dtype not in _lib.PREDICT_DTYPES:
-                raise ValueError("dtype must be one of %s, got %r" % (sorted(_lib.PREDICT_DTYPES), dtype))
-            self.set_option("predict_dtype", _lib.PREDICT_DTYPES[dtype])
-        if pixels is not None:
-            x = np.ascontiguousarray(pixels, dtype=np.uint8)
-            if x.ndim != 2 or x.shape[1] != self._bytes_per_image:
-                raise ValueError("pixels must have shape [n, %d], got %s" % (self._bytes_per_image, x.shape))
-        else:
-            x = np.ascontiguousarray(phi, dtype=np.float64)
-            assert x.ndim == 3 and x.shape[1:] == (self.N, 2), x.shape
-        return x
 
     def evaluate(self, labels, pixels=None, phi=None, dtype=None, want_weights=False):
         """streamed evaluation of labelled images this context does not hold (tnml_evaluate_u8 / tnml_evaluate_phi): the path of
@@ -457,28 +477,15 @@ class TrainStates:
         confusion follow the signed decision (first maximum of W_l); weights and pred stay predict()'s (pred: first maximum of |W_l|)."""
         if self._on_device(pixels, phi, labels):
             b, keep = self._dev_batch(pixels, phi, labels, dtype=dtype)
-            w, pred, o = self._dev_weights(b.n, want_weights)
+            w, pred, o = self._weights(b.n, want_weights, dev=True)
             r = _lib.EvalReport()
             self._ck(self._L.tnml_evaluate_dev(self._h, C.byref(b), C.byref(o), C.byref(r)))
             return (EvalReport(r), (w, pred)) if want_weights else EvalReport(r)
-        x = self._streamed_input(pixels, phi, dtype)
-        n = int(x.shape[0])
-        lab = np.ascontiguousarray(labels, dtype=np.int32)
-        if lab.shape != (n,):
-            raise ValueError("labels must have shape [%d], got %s" % (n, lab.shape))
-        w = pred = wp = pp = None
-        if want_weights:
-            w = np.zeros((n, self.nl))
-            pred = np.zeros(n, dtype=np.int32)
-            wp, pp = _lib.dptr(w), pred.ctypes.data_as(C.POINTER(C.c_int32))
+        n, keep, (xp, lp, _, _) = self._host_batch(pixels, phi, labels, dtype=dtype)
+        w, pred, (wp, pp) = self._weights(n, want_weights)
         r = _lib.EvalReport()
-        lp = lab.ctypes.data_as(C.POINTER(C.c_int32))
-        if pixels is not None:
-            self._ck(self._L.tnml_evaluate_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), lp, C.byref(r), wp, pp))
-        else:
-            self._ck(self._L.tnml_evaluate_phi(self._h, n, _lib.dptr(x), lp, C.byref(r), wp, pp))
-        rep = EvalReport(r)
-        return (rep, (w, pred)) if want_weights else rep
+        self._ck(self._entry("evaluate", pixels)(self._h, n, xp, lp, C.byref(r), wp, pp))
+        return (EvalReport(r), (w, pred)) if want_weights else EvalReport(r)
 
     def site_response(self, pixels=None, phi=None, which=None, want_weights=False):
         """streamed site responses (tnml_response_u8 / tnml_response_phi) of images this context does not hold, in the input forms of
@@ -488,29 +495,15 @@ class TrainStates:
         only; fp64 only (refused under predict_dtype = 1)."""
         if self._on_device(pixels, phi, which):
             b, keep = self._dev_batch(pixels, phi, which=which)
-            w, pred, o = self._dev_weights(b.n, want_weights)
+            w, pred, o = self._weights(b.n, want_weights, dev=True)
             resp = torch.empty((int(b.n), self.N, 2), dtype=torch.float64, device=torch.device("cuda", self.device))
             o.resp = resp.data_ptr()
             self._ck(self._L.tnml_response_dev(self._h, C.byref(b), C.byref(o)))
             return (resp, (w, pred)) if want_weights else resp
-        x = self._streamed_input(pixels, phi, None)
-        n = int(x.shape[0])
+        n, keep, (xp, _, _, whp) = self._host_batch(pixels, phi, which=which)
         resp = np.zeros((n, self.N, 2))
-        wh = wp_ = None
-        if which is not None:
-            wh = np.ascontiguousarray(which, dtype=np.int32)
-            if wh.shape != (n,):
-                raise ValueError("which must have shape [%d], got %s" % (n, wh.shape))
-            wp_ = wh.ctypes.data_as(C.POINTER(C.c_int32))
-        w = pred = wp = pp = None
-        if want_weights:
-            w = np.zeros((n, self.nl))
-            pred = np.zeros(n, dtype=np.int32)
-            wp, pp = _lib.dptr(w), pred.ctypes.data_as(C.POINTER(C.c_int32))
-        if pixels is not None:
-            self._ck(self._L.tnml_response_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), wp_, _lib.dptr(resp), wp, pp))
-        else:
-            self._ck(self._L.tnml_response_phi(self._h, n, _lib.dptr(x), wp_, _lib.dptr(resp), wp, pp))
+        w, pred, (wp, pp) = self._weights(n, want_weights)
+        self._ck(self._entry("response", pixels)(self._h, n, xp, whp, _lib.dptr(resp), wp, pp))
         return (resp, (w, pred)) if want_weights else resp
 
     def site_gradient(self, labels=None, coef=None, pixels=None, phi=None, want_weights=False, dtype=None):
@@ -524,42 +517,15 @@ class TrainStates:
         dtype "f64" / "f32" sets option gradient_dtype for this call and the ones after it (None: as it is).  "f32": the fp32 gradient
         kernels on an fp32 copy of W, bonds up to 1 024; weights and pred are then those of predict(dtype="f32"), the sum over a chunk's
         images is fp32, the sum over chunks fp64."""
-        self._gradient_dtype(dtype)
+        self._set_dtype("gradient_dtype", dtype)
         if self._on_device(pixels, phi, labels, coef):
             r = self._backward_dev(labels, coef, pixels, phi, True, False, want_weights)
             return (r[0], r[2]) if want_weights else r[0]
-        x = self._streamed_input(pixels, phi, None)
-        n = int(x.shape[0])
-        lp = cp = None
-        if labels is not None:
-            lab = np.ascontiguousarray(labels, dtype=np.int32)
-            if lab.shape != (n,):
-                raise ValueError("labels must have shape [%d], got %s" % (n, lab.shape))
-            lp = lab.ctypes.data_as(C.POINTER(C.c_int32))
-        if coef is not None:
-            cf = np.ascontiguousarray(coef, dtype=np.float64)
-            if cf.shape != (n, self.nl):
-                raise ValueError("coef must have shape [%d, %d], got %s" % (n, self.nl, cf.shape))
-            cp = _lib.dptr(cf)
-        elems = C.c_int64()
-        offs = np.zeros(self.N + 1, dtype=np.int64)
-        self._ck(self._L.tnml_site_gradient_size(self._h, C.byref(elems), offs.ctypes.data_as(C.POINTER(C.c_int64))))
-        grad = np.zeros(max(elems.value, 1))
-        w = pred = wp = pp = None
-        if want_weights:
-            w = np.zeros((n, self.nl))
-            pred = np.zeros(n, dtype=np.int32)
-            wp, pp = _lib.dptr(w), pred.ctypes.data_as(C.POINTER(C.c_int32))
-        if pixels is not None:
-            self._ck(self._L.tnml_site_gradient_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), lp, cp, _lib.dptr(grad), wp, pp))
-        else:
-            self._ck(self._L.tnml_site_gradient_phi(self._h, n, _lib.dptr(x), lp, cp, _lib.dptr(grad), wp, pp))
-        grads = []
-        for j in range(1, self.N + 1):
-            ml, mr, hl = C.c_int(), C.c_int(), C.c_int()
-            self._ck(self._L.tnml_site_dims(self._h, j, ml, mr, hl))
-            shape = (ml.value, 2, mr.value) + ((NL,) if hl.value else ())
-            grads.append(grad[offs[j - 1]:offs[j]].reshape(shape, order="F").copy(order="F"))
+        n, keep, (xp, lp, cp, _) = self._host_batch(pixels, phi, labels, coef)
+        grad = self._gradient_buffer()
+        w, pred, (wp, pp) = self._weights(n, want_weights)
+        self._ck(self._entry("site_gradient", pixels)(self._h, n, xp, lp, cp, _lib.dptr(grad), wp, pp))
+        grads = self._split_sites(grad)
         self._note_chunk(n)
         return (grads, (w, pred)) if want_weights else grads
 
@@ -573,50 +539,18 @@ class TrainStates:
         of one flat device buffer, dphi a device tensor in phi's dtype (float32 phi: the fp64 result rounded once).
         dtype: as site_gradient()'s.  Under "f32" every dphi value is an fp32 number (widened exactly; a float32 dphi is rounded no
         second time)."""
-        self._gradient_dtype(dtype)
+        self._set_dtype("gradient_dtype", dtype)
         if self._on_device(pixels, phi, labels, coef):
             return self._backward_dev(labels, coef, pixels, phi, want_sites, want_inputs, want_weights)
-        x = self._streamed_input(pixels, phi, None)
-        n = int(x.shape[0])
-        lp = cp = None
-        if labels is not None:
-            lab = np.ascontiguousarray(labels, dtype=np.int32)
-            if lab.shape != (n,):
-                raise ValueError("labels must have shape [%d], got %s" % (n, lab.shape))
-            lp = lab.ctypes.data_as(C.POINTER(C.c_int32))
-        if coef is not None:
-            cf = np.ascontiguousarray(coef, dtype=np.float64)
-            if cf.shape != (n, self.nl):
-                raise ValueError("coef must have shape [%d, %d], got %s" % (n, self.nl, cf.shape))
-            cp = _lib.dptr(cf)
-        grad = gp = dphi = dp = None
-        if want_sites:
-            elems = C.c_int64()
-            self._ck(self._L.tnml_site_gradient_size(self._h, C.byref(elems), None))
-            grad = np.zeros(max(elems.value, 1))
-            gp = _lib.dptr(grad)
-        if want_inputs:
-            dphi = np.zeros((n, self.N, 2))
-            dp = _lib.dptr(dphi)
-        w = pred = wp = pp = None
-        if want_weights:
-            w = np.zeros((n, self.nl))
-            pred = np.zeros(n, dtype=np.int32)
-            wp, pp = _lib.dptr(w), pred.ctypes.data_as(C.POINTER(C.c_int32))
-        if pixels is not None:
-            self._ck(self._L.tnml_backward_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), lp, cp, gp, dp, wp, pp))
-        else:
-            self._ck(self._L.tnml_backward_phi(self._h, n, _lib.dptr(x), lp, cp, gp, dp, wp, pp))
+        n, keep, (xp, lp, cp, _) = self._host_batch(pixels, phi, labels, coef)
+        grad = self._gradient_buffer() if want_sites else None
+        dphi = np.zeros((n, self.N, 2)) if want_inputs else None
+        w, pred, (wp, pp) = self._weights(n, want_weights)
+        self._ck(self._entry("backward", pixels)(self._h, n, xp, lp, cp, grad if grad is None else _lib.dptr(grad),
+                                                 dphi if dphi is None else _lib.dptr(dphi), wp, pp))
         grads = self._split_sites(grad) if want_sites else None
         self._note_chunk(n)
         return (grads, dphi, (w, pred)) if want_weights else (grads, dphi)
-
-    def _gradient_dtype(self, dtype):
-        """dtype (when given) becomes option gradient_dtype, for this call and the ones after it, as predict(dtype=...) sets predict_dtype"""
-        if dtype is not None:
-            if dtype not in _lib.GRADIENT_DTYPES:
-                raise ValueError("dtype must be one of %s, got %r" % (sorted(_lib.GRADIENT_DTYPES), dtype))
-            self.set_option("gradient_dtype", _lib.GRADIENT_DTYPES[dtype])
 
     def _note_chunk(self, n):
         """the size of the last chunk of a gradient or step call on n images (gradient_coef)"""
@@ -639,10 +573,7 @@ class TrainStates:
     def _split_sites(self, flat):
         """a flat array in the layout of tnml_site_gradient_*'s grad -> a list of N arrays shaped like get_site()'s"""
         out, at = [], 0
-        for j in range(1, self.N + 1):
-            ml, mr, hl = C.c_int(), C.c_int(), C.c_int()
-            self._ck(self._L.tnml_site_dims(self._h, j, ml, mr, hl))
-            shape = (ml.value, 2, mr.value) + ((NL,) if hl.value else ())
+        for shape in self._site_shapes():
             size = int(np.prod(shape))
             out.append(flat[at:at + size].reshape(shape, order="F").copy(order="F"))
             at += size
@@ -658,37 +589,23 @@ class TrainStates:
         Under set_loss("softmax") the labels mode takes the gradient of the cross-entropy and the report's eval is evaluate()'s under
         that loss; the optimiser and the coef mode are the same.
         dtype: as site_gradient()'s.  Under "f32" the step is mixed precision: an fp32 gradient on an fp64 master W and fp64 state."""
-        self._gradient_dtype(dtype)
+        self._set_dtype("gradient_dtype", dtype)
         if method not in _lib.STEP_METHODS:
             raise ValueError("method must be one of %s, got %r" % (sorted(_lib.STEP_METHODS), method))
         if lr is None:
             raise ValueError("lr is required")
-        if self._on_device(pixels, phi, labels, coef):
+        dev = self._on_device(pixels, phi, labels, coef)
+        if dev:
             b, keep = self._dev_batch(pixels, phi, labels, coef)
-            par = _lib.StepParams(_lib.STEP_METHODS[method], float(lr), float(momentum), float(beta1), float(beta2), float(eps), float(clip), float(scale))
-            r = _lib.StepReport()
-            self._ck(self._L.tnml_site_step_dev(self._h, C.byref(b), C.byref(par), C.byref(r)))
-            self._note_chunk(int(b.n))
-            return StepReport(r)
-        x = self._streamed_input(pixels, phi, None)
-        n = int(x.shape[0])
-        lp = cp = None
-        if labels is not None:
-            lab = np.ascontiguousarray(labels, dtype=np.int32)
-            if lab.shape != (n,):
-                raise ValueError("labels must have shape [%d], got %s" % (n, lab.shape))
-            lp = lab.ctypes.data_as(C.POINTER(C.c_int32))
-        if coef is not None:
-            cf = np.ascontiguousarray(coef, dtype=np.float64)
-            if cf.shape != (n, self.nl):
-                raise ValueError("coef must have shape [%d, %d], got %s" % (n, self.nl, cf.shape))
-            cp = _lib.dptr(cf)
+            n = int(b.n)
+        else:
+            n, keep, (xp, lp, cp, _) = self._host_batch(pixels, phi, labels, coef)
         par = _lib.StepParams(_lib.STEP_METHODS[method], float(lr), float(momentum), float(beta1), float(beta2), float(eps), float(clip), float(scale))
         r = _lib.StepReport()
-        if pixels is not None:
-            self._ck(self._L.tnml_site_step_u8(self._h, n, x.ctypes.data_as(C.POINTER(C.c_uint8)), lp, cp, C.byref(par), C.byref(r)))
+        if dev:
+            self._ck(self._L.tnml_site_step_dev(self._h, C.byref(b), C.byref(par), C.byref(r)))
         else:
-            self._ck(self._L.tnml_site_step_phi(self._h, n, _lib.dptr(x), lp, cp, C.byref(par), C.byref(r)))
+            self._ck(self._entry("site_step", pixels)(self._h, n, xp, lp, cp, C.byref(par), C.byref(r)))
         self._note_chunk(n)
         return StepReport(r)
 
@@ -745,17 +662,12 @@ class TrainStates:
     def get_site(self, j, device=False):
         """site j as a numpy array [ml, 2, mr(, 10)]; device=True: as a tensor on the context's device in first-index-fastest
         strides, the library's layout (tnml_get_site_dev: one device-to-device copy)"""
+        shape = self._site_shape(j)
         if device:
-            ml, mr, hl = C.c_int(), C.c_int(), C.c_int()
-            self._ck(self._L.tnml_site_dims(self._h, j, ml, mr, hl))
-            shape = (ml.value, 2, mr.value) + ((NL,) if hl.value else ())
             dev = torch.device("cuda", self.device)
             A = torch.empty_strided(shape, self._fstrides(shape), dtype=torch.float64, device=dev)
             self._ck(self._L.tnml_get_site_dev(self._h, j, A.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
             return A
-        ml, mr, hl = C.c_int(), C.c_int(), C.c_int()
-        self._ck(self._L.tnml_site_dims(self._h, j, ml, mr, hl))
-        shape = (ml.value, 2, mr.value) + ((NL,) if hl.value else ())
         buf = np.empty(int(np.prod(shape)))
         self._ck(self._L.tnml_get_site(self._h, j, _lib.dptr(buf)))
         return buf.reshape(shape, order="F")
