@@ -519,7 +519,10 @@ int tnml_site_gradient_coef(tnml_ctx* ctx, double* out /*[cnt][nl]*/, int64_t co
  * Workspace: that of tnml_site_gradient_* (same formula, same bytes) and, from the first call that asks for dphi on,
  *             32 N C    bytes (dphi of a chunk as the kernel leaves it [N][2][C] and as the caller gets it [C][N][2]; C = gradient_chunk
  *                       rounded up to 64), counted by tnml_device_bytes, re-made when gradient_chunk changes, released by
- *                       tnml_set_input_map with the gradient workspace and freed by tnml_destroy. */
+ *                       tnml_set_input_map with the gradient workspace and freed by tnml_destroy.
+ * tnml_forward_taped_* followed by tnml_backward_taped* (below) allocates exactly these bytes for the same input form and outputs:
+ * the forward everything but the 32 N C (16 N C for device-resident outputs), the first backward that asks for dphi those.
+ * tnml_set_sites_dev adds 32 N bytes (its table) from its first call on. */
 int tnml_backward_u8 (tnml_ctx* ctx, int64_t n, const uint8_t* pixels, const int32_t* labels /*[n] or NULL*/, const double* coef /*[n][nl] or NULL*/,
                       double* grad /*[elems] or NULL*/, double* dphi /*[n][N][2] or NULL*/, double* weights /*[n][nl] or NULL*/, int32_t* pred /*[n] or NULL*/);
 int tnml_backward_phi(tnml_ctx* ctx, int64_t n, const double* phi /*[n][N][2]*/, const int32_t* labels, const double* coef,
@@ -658,6 +661,47 @@ int tnml_site_step_dev(tnml_ctx* ctx, const tnml_dev_batch* batch, const tnml_st
 int tnml_set_site_dev (tnml_ctx* ctx, int j, int ml, int mr, int has_label, const double* A_dev, void* stream);
 int tnml_get_site_dev (tnml_ctx* ctx, int j, double* A_dev, void* stream);
 int tnml_abi_layout(const char* name, int64_t* sizes_out);
+
+/* ---- backward from the forward's tape: a training step that walks the chain inward once --------------------------------
+ * tnml_predict_* followed by tnml_backward_*(coef = ...) walks the chain inward twice: the backward's first half is the forward again.
+ * tnml_forward_taped_* is that first half alone, on the gradient workspace under option "gradient_dtype" (not "predict_dtype"): ONE
+ * launch of k_forward_taped (kernels_sitegrad.hip, profile class "fwd_taped") that leaves weights, pred and the inward tape.  It
+ * shares the refusals, the staging, the fp32 copy of W, "predict_tile" and the input map with tnml_backward_*, so weights and pred are
+ * bit for bit those of tnml_predict_* under the matching "predict_dtype".  n must not exceed "gradient_chunk" (a tape belongs to one
+ * chunk; a larger n is refused), n = 0 succeeds with *ticket = 0, which is never valid; under fp32 a weight outside the fp32 range
+ * fails the call as it fails tnml_backward_*, and leaves no ticket.  On success *ticket is a positive number this context has never
+ * given out before.
+ * tnml_backward_taped / tnml_backward_taped_dev take the ticket and coefficients [n][nl] (no labels: an autograd caller has
+ * grad_output), and return grad and / or dphi bit for bit as tnml_backward_* does for the same images and coefficients under the
+ * same options.  Per call: one copy of the coefficients, the gradient zeroed when grad is asked for, ONE launch of k_site_outward
+ * (class "site_out": the two outward walks in two workgroups per tile), k_site_grad when grad is asked for, k_input_grad when dphi
+ * is, the copies out.  No site table, fp32 copy of W or image is staged again.  The rules are tnml_backward_*'s: a coefficient that
+ * is not finite is refused (on the host, or by k_check_batch), grad and dphi both NULL is refused, and the _dev form makes the
+ * pointer checks and keeps the stream contract and dphi32 of the device-resident calls.  A backward of either memory space serves
+ * a forward of either.  The ticket stays valid after a backward: ten calls with unit coefficient rows give the Jacobian of one forward.
+ * tnml_site_gradient_coef afterwards returns the coefficients as given, under fp32 too: as tnml_backward_* leaves them (the kernels
+ * round them to fp32 as they read them).
+ * A context has at most one live ticket.  It dies -- and the context keeps the name of what took the tape, which a refused backward
+ * gives with the ticket -- with any other call that uses the gradient workspace on n > 0 images (tnml_site_gradient_*, tnml_backward_*,
+ * tnml_site_step_*, their _dev forms, a new tnml_forward_taped_*), with anything that writes W (tnml_set_site, tnml_set_site_dev,
+ * tnml_set_sites_dev, tnml_mps_place, tnml_mps_compress, a bond update, a step), and with a release or re-make of the workspace or
+ * its tapes (a changed "gradient_chunk" or "gradient_dtype" when the ticket is next looked at, tnml_set_input_map).  "predict_tile",
+ * "loss" and "predict_dtype" may change: the backward uses the tile width the forward ran with.  A refused backward leaves every output
+ * untouched and the context usable.  tnml_tape_ticket gives the live ticket and its image count, 0 and 0 when there is none.
+ * Workspace: forward and backward together allocate exactly what tnml_backward_* allocates for the same input form and outputs
+ * (the formulas above; the 32 N C of dphi with the first backward that asks for it).
+ * tnml_set_sites_dev is tnml_set_site_dev for count sites in the shapes W has now -- an optimiser step, not a change of bond
+ * dimensions: sites[k] in 1..N, set, none named twice, A_dev[k] a device array in tnml_get_site's layout under the pointer checks of
+ * the _dev calls.  Every check is made before anything is written.  Then one entry wait on `stream`, one upload of a table of
+ * (source, destination, elements, first block), ONE launch of k_sites_gather (class "sites_copy") and one synchronisation.  count = 0
+ * does nothing.  The table takes 32 N bytes from the first call on, counted by tnml_device_bytes and released with the check block. */
+int tnml_forward_taped_u8 (tnml_ctx* ctx, int64_t n, const uint8_t* pixels, double* weights, int32_t* pred, int64_t* ticket);
+int tnml_forward_taped_phi(tnml_ctx* ctx, int64_t n, const double* phi, double* weights, int32_t* pred, int64_t* ticket);
+int tnml_forward_taped_dev(tnml_ctx* ctx, const tnml_dev_batch* batch, const tnml_dev_out* out /* weights, pred */, int64_t* ticket);
+int tnml_backward_taped    (tnml_ctx* ctx, int64_t ticket, const double* coef /* host [n][nl] */, double* grad, double* dphi);
+int tnml_backward_taped_dev(tnml_ctx* ctx, int64_t ticket, const double* coef_dev, const tnml_dev_out* out /* grad, dphi | dphi32 */, void* stream);
+int tnml_tape_ticket(tnml_ctx* ctx, int64_t* ticket, int64_t* n);
+int tnml_set_sites_dev(tnml_ctx* ctx, int count, const int32_t* sites, const double* const* A_dev, void* stream);
 
 /* ---- held-out evaluation during training ----------------------------------------------------------
  * A held-out set is an ordinary context created for the held-out images (one rank: nranks = 1, its own shard of the set in

@@ -53,3 +53,24 @@ int launch_check_batch(tnml_ctx* c, const int* labels, const double* coef, const
     HIPCK(c, hipGetLastError());
     return 0;
 }
+
+// ---- tnml_set_sites_dev: many site tensors in ONE launch (class sites_copy) ----
+// Workgroup b serves the table entry with the last blk0 <= b (the entries' blk0 ascend from 0) and, of its elems doubles, those from
+// (b - blk0) SITES_COPY_BLOCK on: plain 8-byte vector loads and stores, consecutive lanes on consecutive doubles.  The host has checked that
+// every source holds its elems doubles; the destinations are W's own buffers at the shapes W has.
+__global__ __launch_bounds__(256) void k_sites_gather(const SiteCopy* __restrict__ tab, int count) {
+    int lo = 0, hi = count;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tab[mid].blk0 <= (long long)blockIdx.x) lo = mid; else hi = mid; }
+    const SiteCopy e = tab[lo];
+    const long long first = ((long long)blockIdx.x - e.blk0) * SITES_COPY_BLOCK;
+    const long long last = first + SITES_COPY_BLOCK < e.elems ? first + SITES_COPY_BLOCK : e.elems;
+    for (long long i = first + threadIdx.x; i < last; i += 256) e.dst[i] = e.src[i];
+}
+
+int launch_sites_gather(tnml_ctx* c, const SiteCopy* tab, int count, long long nblocks) {
+    if (!tab || count < 1 || nblocks < 1 || nblocks > 0x7fffffffll) return tnml_fail(c, "copy of the sites: %d sites in %lld blocks", count, nblocks);
+    ProfScope ps(c, KC_SITES_COPY);
+    hipLaunchKernelGGL(k_sites_gather, dim3((unsigned)nblocks), dim3(256), 0, c->stream, tab, count);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}

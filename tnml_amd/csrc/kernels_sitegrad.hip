@@ -58,7 +58,15 @@
 // Registers (gfx950 cross-compile; VGPRs at T = 16 / 32 / 64, bytes / input map source alike to within 3; no scratch in any instantiation):
 //   k_site_backward<double>: 104 / 127 / 162      k_site_backward<float>: 94 / 99 / 121     (the softmax forms: the same counts, float T = 16: 96)
 //   k_site_grad<double>:     60 / 56 / 58 + 16 accumulator registers      k_site_grad<float>: 36 / 33 / 33 + 8
+//   k_forward_taped<double>: 96 / 129 / 164       k_forward_taped<float>: 92 / 94 / 121     (input map source: within 2)
+//   k_site_outward<double>:  96 / 119 / 161       k_site_outward<float>:  86 / 90 / 115     (input map source at T = 16: 114 and 100)
 // No atomics; compiled with -ffp-contract=off like its neighbours.
+//
+// 3. The same work in two calls (tnml_forward_taped_* / tnml_backward_taped*; the kernels are at the end of this file).  k_forward_taped
+//    (class fwd_taped) is phase A alone and leaves weights, pred and the inward tape.  k_site_outward (class site_out) is the centre's seeds
+//    and phase B in the coef mode, started from that tape: a grid of (tiles, 2), one workgroup for X and one for Y, each with seed_step and
+//    carry_outward as k_site_backward calls them.  The second tape is k_site_backward's bit for bit, so k_site_grad and k_input_grad run
+//    behind it unchanged.  No existing kernel's instructions moved (tools/compare_isa.py against the commit before: 71 of 71 identical).
 #include "chain_common.h"
 #include "loss_dev.h"
 
@@ -361,3 +369,113 @@ int launch_site_gradient(tnml_ctx* c, SiteGradArgsT<E> a, int maxbond, int T, in
 }
 template int launch_site_gradient<double>(tnml_ctx*, SiteGradArgsT<double>, int, int, int, size_t, int, bool);
 template int launch_site_gradient<float>(tnml_ctx*, SiteGradArgsT<float>, int, int, int, size_t, int, bool);
+
+// ---- the forward that keeps its tape, and the backward that starts from it (tnml_forward_taped_* / tnml_backward_taped*) ----
+// k_forward_taped is phase A of k_site_backward and nothing else: the taped inward walk and the centre, so weights, pred and the inward tape
+// are those k_site_backward leaves, bit for bit; the hook keeps the fp32 range check alone.  Two tiles of LDS, no coefficients.
+template <typename E, int NCT, int SRC>
+__global__ __launch_bounds__(CHAIN_THREADS) void k_forward_taped(const SiteGradArgsT<E> g) {
+    typedef ChainT<E> Tr;
+    constexpr bool f32 = sizeof(E) == sizeof(float);
+    constexpr int T = 16 * NCT;
+    extern __shared__ __attribute__((aligned(16))) unsigned char sg_lds_raw[];
+    E* const lds = reinterpret_cast<E*>(sg_lds_raw);
+    const ChainArgs<E>& ch = g.ch;
+    const int tid = threadIdx.x;
+    const int tile0 = blockIdx.x * T;
+    const size_t tile_elems = (size_t)ch.mcap * T;
+    E* buf[2] = {lds, lds + tile_elems};
+    const size_t slice = (size_t)blockIdx.x * g.rowoff[ch.N + 1] * T;
+    const ChainTape<E, T> tape{g.tape + slice, g.rowoff};
+    E p0[NCT], p1[NCT];
+    const int cur = chain_walk_taped<E, NCT, SRC>(ch, buf, tape, p0, p1, tile0, tid);
+    bool bad = false;
+    chain_centre_taped<E, NCT>(ch, buf, cur, tape.bond(ch.cs), p0, p1, tile0, tid, [&](int, E w, int, int img) {
+        if (img < ch.cnt && Tr::bad(Tr::abs(w))) bad = true;
+    });
+    if constexpr (f32) { if (bad) *ch.flag = 1; }
+}
+
+// k_site_outward: the centre's seeds and phase B of k_site_backward in its coef mode, from the inward tape of a k_forward_taped launch with
+// the same tile width.  Grid (tiles, 2): the two outward walks share nothing but the tile's coefficients and the centre's features, so
+// workgroup y = 0 seeds and carries X (left of the Label site), y = 1 seeds and carries Y (right of it), with seed_step and
+// carry_outward as they are -- the operands of a seed are the tape's copies of R_{cs+1} (bond cs) and L_{cs-1} (bond cs-1; the 1 of a
+// chain's start when cs = 1), the very values k_site_backward has in its tiles, so the second tape comes out bit for bit.  A side with
+// nothing to do returns at once.  LDS as k_site_backward: two tiles and the coefficients [nl][T].
+template <typename E, int NCT, int SRC>
+__global__ __launch_bounds__(CHAIN_THREADS) void k_site_outward(const SiteGradArgsT<E> g) {
+    constexpr int T = 16 * NCT;
+    extern __shared__ __attribute__((aligned(16))) unsigned char sg_lds_raw[];
+    E* const lds = reinterpret_cast<E*>(sg_lds_raw);
+    const ChainArgs<E>& ch = g.ch;
+    const int N = ch.N, cs = ch.cs;
+    const bool right = blockIdx.y == 1;
+    if (right ? cs >= N : cs <= 1) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tile0 = blockIdx.x * T;
+    const size_t tile_elems = (size_t)ch.mcap * T;
+    E* buf[2] = {lds, lds + tile_elems};
+    E* const cl = lds + 2 * tile_elems;                                // [nl][T] coefficients of the tile
+    const size_t slice = (size_t)blockIdx.x * g.rowoff[N + 1] * T;
+    const ChainTape<E, T> tape{g.tape + slice, g.rowoff};
+    const ChainTape<E, T> tape2{g.tape2 + slice, g.rowoff};
+    if (tid < T) {                                                     // the coef branch of k_site_backward's hook: rounded once to E, 0 beyond the chunk
+        const int img = tile0 + tid;
+        for (int l = 0; l < ch.nl; ++l) cl[l * T + tid] = img < ch.cnt ? (E)g.coef[(size_t)img * ch.nl + l] : (E)0;
+    }
+    E p0[NCT], p1[NCT];
+    chain_features<E, NCT, SRC>(ch, cs, tile0 + (lane & 15), p0, p1);
+    const ChainSite<E> sc = ch.sites[cs - 1];
+    const size_t lstride = (size_t)sc.ml * 2 * sc.mr;
+    if (right) {
+        chain_copy_rows<E, T>(tape.bond(cs - 1), buf[0], sc.ml, tid);  // L_{cs-1}
+        __syncthreads();
+        seed_step<E, NCT, true>(sc.a, lstride, ch.nl, sc.ml, sc.mr, buf[0], tape2.bond(cs), p0, p1, cl, wave, lane);
+        carry_outward<E, NCT, SRC, true>(ch, buf, tape2, sc.mr, p0, p1, tile0, tid);
+    } else {
+        chain_copy_rows<E, T>(tape.bond(cs), buf[0], sc.mr, tid);      // R_{cs+1}
+        __syncthreads();
+        seed_step<E, NCT, false>(sc.a, lstride, ch.nl, sc.ml, sc.mr, buf[0], tape2.bond(cs - 1), p0, p1, cl, wave, lane);
+        carry_outward<E, NCT, SRC, false>(ch, buf, tape2, sc.ml, p0, p1, tile0, tid);
+    }
+}
+
+template <typename E>
+int launch_forward_taped(tnml_ctx* c, SiteGradArgsT<E> a, int maxbond, int T, int rows, size_t tape_elems) {
+    constexpr bool f32 = sizeof(E) == sizeof(float);
+    if (f32 && !a.ch.flag) return tnml_fail(c, "taped forward kernel: no range flag");
+    typedef void (*kern_t)(const SiteGradArgsT<E>);
+    static const kern_t fwd[2][3] = {{k_forward_taped<E, 1, 0>, k_forward_taped<E, 2, 0>, k_forward_taped<E, 4, 0>}, {k_forward_taped<E, 1, 1>, k_forward_taped<E, 2, 1>, k_forward_taped<E, 4, 1>}};   // [SRC][T / 32]
+    TapedLaunch L;
+    TCK(taped_launch(c, "taped forward kernel", "tape", a.ch, maxbond, T, rows, tape_elems, 0, fwd, c->attr_fwdtaped[f32], &L));
+    ProfScope ps(c, KC_FWD_TAPED);
+    hipLaunchKernelGGL(fwd[L.codes][T / 32], dim3(L.grid), dim3(CHAIN_THREADS), L.lds, c->stream, a);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+template int launch_forward_taped<double>(tnml_ctx*, SiteGradArgsT<double>, int, int, int, size_t);
+template int launch_forward_taped<float>(tnml_ctx*, SiteGradArgsT<float>, int, int, int, size_t);
+
+template <typename E>
+int launch_site_outward(tnml_ctx* c, SiteGradArgsT<E> a, int maxbond, int T, int rows, size_t tape_elems, int nblocks, bool run_gemm) {
+    constexpr bool f32 = sizeof(E) == sizeof(float);
+    if (nblocks < 1) return tnml_fail(c, "outward kernel: %d output blocks", nblocks);
+    if (!a.coef || !a.tape || !a.tape2) return tnml_fail(c, "outward kernel: null argument");
+    typedef void (*kern_t)(const SiteGradArgsT<E>);
+    static const kern_t out[2][3] = {{k_site_outward<E, 1, 0>, k_site_outward<E, 2, 0>, k_site_outward<E, 4, 0>}, {k_site_outward<E, 1, 1>, k_site_outward<E, 2, 1>, k_site_outward<E, 4, 1>}};   // [SRC][T / 32]
+    static const kern_t gemm[2][3] = {{k_site_grad<E, 1, 0>, k_site_grad<E, 2, 0>, k_site_grad<E, 4, 0>}, {k_site_grad<E, 1, 1>, k_site_grad<E, 2, 1>, k_site_grad<E, 4, 1>}};
+    TapedLaunch L;
+    TCK(taped_launch(c, "outward kernel", "tapes", a.ch, maxbond, T, rows, tape_elems, (size_t)a.ch.nl * T * sizeof(E), out, c->attr_siteout[f32], &L));
+    {
+        ProfScope ps(c, KC_SITE_OUT);
+        hipLaunchKernelGGL(out[L.codes][T / 32], dim3(L.grid, 2), dim3(CHAIN_THREADS), L.lds, c->stream, a);
+        HIPCK(c, hipGetLastError());
+    }
+    if (!run_gemm) return 0;
+    ProfScope ps(c, KC_SITE_GRAD);
+    hipLaunchKernelGGL(gemm[L.codes][T / 32], dim3(nblocks), dim3(SG_THREADS), 0, c->stream, a);
+    HIPCK(c, hipGetLastError());
+    return 0;
+}
+template int launch_site_outward<double>(tnml_ctx*, SiteGradArgsT<double>, int, int, int, size_t, int, bool);
+template int launch_site_outward<float>(tnml_ctx*, SiteGradArgsT<float>, int, int, int, size_t, int, bool);

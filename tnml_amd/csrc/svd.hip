@@ -512,5 +512,6 @@ int svd_split_device(tnml_ctx* c, const double* B_it, int b, int ha, double cuto
     if (labL) hipLaunchKernelGGL(k_perm_labL_back, dim3(nblk((size_t)nl * m)), dim3(256), 0, st, Lf, Sl.a, 2 * mL, m);
     HIPCK(c, hipGetLastError());
     Sl.mr = m; Sr.ml = m; Sl.placed = false; Sr.placed = false;
+    w_written(c, "a bond update");                              // (the split of tnml_bond_update* and tnml_svd_split; tnml_mps_compress says its own name after its splits)
     return 0;
 }

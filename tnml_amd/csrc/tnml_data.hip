@@ -74,6 +74,7 @@ int tnml_set_input_map(tnml_ctx* c, const tnml_input_map* m) {
     HIPCK(c, hipSetDevice(c->cfg.device));
     if (c->pk.map_bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); predict_release_map(c); }
     if (c->rs.bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); response_release(c); }
+    tape_kill(c, "tnml_set_input_map");
     if (c->sg.bytes) { HIPCK(c, hipStreamSynchronize(c->stream)); sitegrad_release(c); }
     if (!m) { c->im_set = false; c->im = tnml_input_map{}; c->im_table.clear(); return 0; }
     c->im_table.assign(m->table, m->table + (size_t)2 * m->ncodes);
@@ -171,6 +172,7 @@ int tnml_set_site(tnml_ctx* c, int j, int ml, int mr, int has_label, const doubl
     TCK(set_site_rules(c, j, ml, mr, has_label));
     SiteT& s = c->W[j];
     s.ml = ml; s.mr = mr; s.L = has_label ? TNML_NL : 1; s.set = true; s.placed = false;
+    w_written(c, "tnml_set_site");
     HIPCK(c, hipMemcpy(s.a, A, sizeof(double) * (size_t)ml * 2 * mr * s.L, hipMemcpyHostToDevice));
     c->currb = -1; c->p_valid = false; c->sweep_start = false;
     for (int b = j - 1; b <= j; ++b) if (b >= 1 && b < (int)c->bond_hist.size()) c->bond_hist[b] = tnml_ctx::BondHist();   // the bonds of this site start over (option spec_predict)
@@ -239,11 +241,55 @@ int tnml_set_site_dev(tnml_ctx* c, int j, int ml, int mr, int has_label, const d
     TCK(dev_check_args(c, "tnml_set_site_dev", {{"A_dev", A_dev, bytes, 8, false}}));
     TCK(dev_entry_wait(c, "tnml_set_site_dev", stream));
     SiteT& s = c->W[j];
+    w_written(c, "tnml_set_site_dev");
     HIPCK(c, hipMemcpyAsync(s.a, A_dev, bytes, hipMemcpyDeviceToDevice, c->stream));
     SYNCK(c, c->stream);
     s.ml = ml; s.mr = mr; s.L = has_label ? TNML_NL : 1; s.set = true; s.placed = false;
     c->currb = -1; c->p_valid = false; c->sweep_start = false;
     for (int b = j - 1; b <= j; ++b) if (b >= 1 && b < (int)c->bond_hist.size()) c->bond_hist[b] = tnml_ctx::BondHist();
+    return 0;
+}
+// tnml_set_site_dev for `count` sites in the shapes W has now: every check first, then one entry wait, one table upload, ONE k_sites_gather
+// launch (kernels_iocheck.hip) and one synchronisation
+int tnml_set_sites_dev(tnml_ctx* c, int count, const int32_t* sites, const double* const* A_dev, void* stream) {
+    const char* const who = "tnml_set_sites_dev";
+    if (!c) return tnml_fail(c, "%s: null argument", who);
+    if (count < 0) return tnml_fail(c, "%s: count = %d, must be >= 0", who, count);
+    if (count == 0) return 0;
+    if (!sites || !A_dev) return tnml_fail(c, "%s: null argument", who);
+    TCK(ho_locked(c, who, true));
+    std::vector<char> named(c->N + 1, 0);
+    std::vector<std::string> names(count);
+    std::vector<DevArg> args(count);
+    std::vector<SiteCopy> tab(count);
+    long long nblocks = 0;
+    for (int k = 0; k < count; ++k) {
+        const int j = sites[k];
+        if (j < 1 || j > c->N) return tnml_fail(c, "%s: site %d out of range 1..%d (entry %d)", who, j, c->N, k);
+        if (!c->W[j].set) return tnml_fail(c, "%s: site %d not set: the call takes the shapes W has (tnml_set_site first)", who, j);
+        if (named[j]) return tnml_fail(c, "%s: site %d named twice (entry %d)", who, j, k);
+        if (!A_dev[k]) return tnml_fail(c, "%s: null argument (the array of site %d)", who, j);
+        named[j] = 1;
+        const SiteT& s = c->W[j];
+        const long long elems = (long long)s.ml * 2 * s.mr * s.L;
+        names[k] = "A_dev of site " + std::to_string(j);
+        args[k] = DevArg{names[k].c_str(), A_dev[k], (size_t)elems * sizeof(double), 8, false};
+        tab[k] = SiteCopy{A_dev[k], s.a, elems, nblocks};
+        nblocks += (elems + SITES_COPY_BLOCK - 1) / SITES_COPY_BLOCK;
+    }
+    TCK(dev_check_args(c, who, args));
+    TCK(dev_entry_wait(c, who, stream));
+    if (!c->io_tab) TCK(dalloc(c, (void**)&c->io_tab, (size_t)c->N * sizeof(SiteCopy)));
+    w_written(c, who);
+    HIPCK(c, hipMemcpyAsync(c->io_tab, tab.data(), sizeof(SiteCopy) * (size_t)count, hipMemcpyHostToDevice, c->stream));
+    TCK(launch_sites_gather(c, c->io_tab, count, nblocks));
+    SYNCK(c, c->stream);                                        // (tab leaves scope with this call)
+    for (int k = 0; k < count; ++k) {
+        const int j = sites[k];
+        c->W[j].placed = false;
+        for (int b = j - 1; b <= j; ++b) if (b >= 1 && b < (int)c->bond_hist.size()) c->bond_hist[b] = tnml_ctx::BondHist();
+    }
+    c->currb = -1; c->p_valid = false; c->sweep_start = false;
     return 0;
 }
 int tnml_get_site_dev(tnml_ctx* c, int j, double* A_dev, void* stream) {

@@ -68,6 +68,10 @@ struct EnvProtect {                                     // the operands of one o
     ~EnvProtect() { for (int k = 0; k < 4; ++k) c->env_protect[k] = keep[k]; }
 };
 static inline int ru16(int x) { return (x + 15) / 16 * 16; }
+// Every place that writes W says so here, with the name a refused tnml_backward_taped* then gives: the one counter a tape's ticket is held to
+inline void w_written(tnml_ctx* c, const char* who) { ++c->w_epoch; c->w_writer = who; }
+// the live ticket dies (none: nothing happens); `who` took its tape
+inline void tape_kill(tnml_ctx* c, const char* who) { if (c->tape.id) { c->tape = TapeTicket(); c->tape_killer = who; } }
 
 // ---- tnml_core.hip ----------------------------------------------------------------------------
 int dalloc(tnml_ctx* c, void** p, size_t bytes);

@@ -96,10 +96,11 @@ static void ws_release(tnml_ctx* c, W& s) {
 }
 void predict_release(tnml_ctx* c) { ws_release(c, c->pk); }
 void response_release(tnml_ctx* c) { ws_release(c, c->rs); }
-void sitegrad_release(tnml_ctx* c) { ws_release(c, c->sg); }
+void sitegrad_release(tnml_ctx* c) { tape_kill(c, "a release of the gradient workspace"); ws_release(c, c->sg); }
 // the check block and the entry event of the tnml_*_dev calls (made by the first such call; the next one makes them again)
 void io_release(tnml_ctx* c) {
     if (c->io_blk) { (void)hipFree(c->io_blk); c->io_blk = nullptr; c->bytes -= 3 * (int64_t)sizeof(unsigned long long); }
+    if (c->io_tab) { (void)hipFree(c->io_tab); c->io_tab = nullptr; c->bytes -= (int64_t)c->N * (int64_t)sizeof(SiteCopy); }
     if (c->io_ev) { (void)hipEventDestroy(c->io_ev); c->io_ev = nullptr; }
 }
 // the part of the predict workspace that follows the input map: released by tnml_set_input_map, re-made by the next tnml_predict_u8 under a map
@@ -644,23 +645,20 @@ static int sitegrad_chunks(tnml_ctx* c, const StreamCall& k, const SiteGradPlan&
     }
     return 0;
 }
-// The part the gradient calls and the step calls share: refusals, staging, tables and the chunk loop.  It leaves the gradient of the n
-// images in c->sg.grad (*elems_out of them) with the stream synchronised behind the last chunk; n = 0: nothing is launched, *elems_out
-// alone is set.  A call that would leave nothing anywhere (tnml_site_gradient_* without grad) is refused.  acc is zeroed here.
-// tnml_backward_*: k.dphi (or k.dphi32) receives the input gradients [n][N][2] chunk by chunk, from ONE k_input_grad launch behind the
-// chunk's k_site_backward; device-resident arrays receive the transposition directly.  k.grad enters the pointer checks only: the sum
-// is made in sg.grad as ever, and the caller copies it out.
-static int sitegrad_device(tnml_ctx* c, StreamCall& k, EvalAcc* acc, bool want_grad, size_t* elems_out) {
-    SiteGradPlan g{acc, want_grad, 1, 0, 0};
-    TCK(streamed_refusals(c, k, "site gradients", &g.maxbond, true));
-    if (!k.grad && !k.want_dphi() && !acc) return tnml_fail(c, "%s: null argument", k.who);
+// W as the gradient kernels need it known: the Label site's extent, the gradient's layout -> goff (N + 1 entries), its elements
+static int sitegrad_shape(tnml_ctx* c, const char* who, std::vector<long long>& goff, size_t* elems) {
+    const int nl = c->nl(), cs = c->single() ? 1 : c->c0;
+    if (c->W[cs].L != nl) return tnml_fail(c, "%s: the Label site %d of W carries %d labels, the context has %d", who, cs, c->W[cs].L, nl);
+    goff.resize(c->N + 1);
+    *elems = sitegrad_layout(c, goff.data());
+    return 0;
+}
+// What a call on n > 0 images sets up in the gradient workspace before its chunk loop: the plan's rows and output blocks, the workspace
+// itself, the site table and the three small tables on the device, the gradient zeroed, the fp32 side under gradient_dtype = 1.  The
+// live ticket of a taped forward dies here: its tape is about to be written.
+static int sitegrad_prepare(tnml_ctx* c, const StreamCall& k, SiteGradPlan& g, const std::vector<long long>& goff, size_t elems) {
     const int N = c->N, nl = c->nl(), cs = c->single() ? 1 : c->c0;
-    if (c->W[cs].L != nl) return tnml_fail(c, "%s: the Label site %d of W carries %d labels, the context has %d", k.who, cs, c->W[cs].L, nl);
-    std::vector<long long> goff(N + 1);
-    const size_t elems = sitegrad_layout(c, goff.data());
-    *elems_out = elems;
-    if (k.n == 0) return 0;
-    TCK(sitegrad_inputs(c, k));
+    tape_kill(c, k.who);
     HIPCK(c, hipSetDevice(c->cfg.device));
     const GradientWs& s = c->sg;
     std::vector<int> rowoff(N + 2);                             // both tapes share the region table (kernels_sitegrad.hip)
@@ -681,10 +679,27 @@ static int sitegrad_device(tnml_ctx* c, StreamCall& k, EvalAcc* acc, bool want_g
     HIPCK(c, hipMemcpyAsync(s.goff, goff.data(), sizeof(long long) * (N + 1), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipMemcpyAsync(s.blk0, blk0.data(), sizeof(int) * (N + nl), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipMemsetAsync(s.grad, 0, elems * sizeof(double), c->stream));       // the sum starts from zero: grad is overwritten
-    if (acc) HIPCK(c, hipMemsetAsync(acc, 0, sizeof(EvalAcc), c->stream));
+    if (g.acc) HIPCK(c, hipMemsetAsync(g.acc, 0, sizeof(EvalAcc), c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));                  // (the tables leave scope with this call)
     if (f32) TCK(workspace32(c, c->sg, sitegrad_release, k.who, k.who, k.bytes_form() && c->im_set, tab));
-    return f32 ? sitegrad_chunks<float>(c, k, g) : sitegrad_chunks<double>(c, k, g);
+    return 0;
+}
+// The part the gradient calls and the step calls share: refusals, staging, tables and the chunk loop.  It leaves the gradient of the n
+// images in c->sg.grad (*elems_out of them) with the stream synchronised behind the last chunk; n = 0: nothing is launched, *elems_out
+// alone is set.  A call that would leave nothing anywhere (tnml_site_gradient_* without grad) is refused.  acc is zeroed here.
+// tnml_backward_*: k.dphi (or k.dphi32) receives the input gradients [n][N][2] chunk by chunk, from ONE k_input_grad launch behind the
+// chunk's k_site_backward; device-resident arrays receive the transposition directly.  k.grad enters the pointer checks only: the sum
+// is made in sg.grad as ever, and the caller copies it out.
+static int sitegrad_device(tnml_ctx* c, StreamCall& k, EvalAcc* acc, bool want_grad, size_t* elems_out) {
+    SiteGradPlan g{acc, want_grad, 1, 0, 0};
+    TCK(streamed_refusals(c, k, "site gradients", &g.maxbond, true));
+    if (!k.grad && !k.want_dphi() && !acc) return tnml_fail(c, "%s: null argument", k.who);
+    std::vector<long long> goff;
+    TCK(sitegrad_shape(c, k.who, goff, elems_out));
+    if (k.n == 0) return 0;
+    TCK(sitegrad_inputs(c, k));
+    TCK(sitegrad_prepare(c, k, g, goff, *elems_out));
+    return c->gradient_dtype == TNML_GRADIENT_F32 ? sitegrad_chunks<float>(c, k, g) : sitegrad_chunks<double>(c, k, g);
 }
 static int sitegrad_impl(tnml_ctx* c, StreamCall& k) {
     size_t elems = 0;
@@ -841,6 +856,7 @@ static int sitestep_impl(tnml_ctx* c, StreamCall& k, const tnml_step_params* p, 
     // Adam's powers: one multiplication per step, kept only when the step is applied
     const double p1 = c->st_p1 * p->beta1, p2 = c->st_p2 * p->beta2;
     a.o1 = 1. - p->beta1; a.o2 = 1. - p->beta2; a.c1 = 1. - p1; a.c2 = 1. - p2;
+    w_written(c, who);
     TCK(launch_site_step(c, a, c->st_nwg));
     double res[SR_N];
     EvalAcc h;
@@ -940,6 +956,167 @@ int tnml_site_step_dev(tnml_ctx* c, const tnml_dev_batch* b, const tnml_step_par
     StreamCall k;
     TCK(dev_call(c, "tnml_site_step_dev", b, nullptr, IN_LABELS | IN_COEF, k));
     return sitestep_impl(c, k, p, rep);
+}
+// ---- backward from the forward's tape (tnml.h): tnml_forward_taped_* keeps what tnml_backward_taped* starts from ----------------
+// The forward is the gradient call's setup (refusals, workspace, staging, tables, the fp32 side) and ONE k_forward_taped launch on one
+// chunk; the context then holds a ticket for the inward tape.  The backward checks the ticket and makes the outward half alone.
+// The ticket `t` is the live one and nothing has happened that takes its tape; otherwise it dies here, with the name of what took it
+static bool tape_live(tnml_ctx* c, int64_t t) {
+    if (t <= 0 || !c->tape.id || t != c->tape.id) return false;
+    if (c->tape.w_epoch != c->w_epoch) tape_kill(c, c->w_writer);
+    else if (c->tape.chunk != c->gradient_chunk) tape_kill(c, "a change of option gradient_chunk");
+    else if (c->tape.esz != (c->gradient_dtype == TNML_GRADIENT_F32 ? 4 : 8)) tape_kill(c, "a change of option gradient_dtype");
+    else if (!c->sg.tape || c->sg.cap != c->tape.cap) tape_kill(c, "a release of the gradient workspace");
+    return c->tape.id != 0;
+}
+template <typename E>
+static int forward_taped_chunk(tnml_ctx* c, const StreamCall& k, const SiteGradPlan& g, int* T_out) {
+    constexpr bool f32 = sizeof(E) == sizeof(float);
+    GradientWs& s = c->sg;
+    const StageGeom sg = k.bytes_form() && c->im_set ? stage_geom(c) : StageGeom{};
+    SiteGradArgsT<E> a;
+    chain_args(c, s, k.bytes_form(), a.ch);
+    a.rowoff = s.rowoff; a.tape = (E*)s.tape; a.tape2 = (E*)s.tape2;
+    a.lab = nullptr; a.target = c->target(); a.coef = s.coef; a.grad = s.grad; a.goff = s.goff; a.blk0 = s.blk0;
+    a.ch.cnt = (int)k.n;
+    TCK(stage_chunk<E>(c, s, k, sg, 0, a.ch.cnt));
+    chunk_dest(c, s, k, 0, &a.ch.wout, &a.ch.pred);
+    const int T = chain_tile<E>(c, g.maxbond, a.ch.cnt);
+    TCK(launch_forward_taped<E>(c, a, g.maxbond, T, g.rows, s.tape_rows * (size_t)s.cap));
+    int flag = 0;
+    if (f32) HIPCK(c, hipMemcpyAsync(&flag, s.f32.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    TCK(chunk_results(c, s, k, 0, a.ch.cnt));                   // (the synchronisation the flag rides on)
+    if (flag) return left_fp32_range(c, s, k.who, "gradient_dtype", 0, a.ch.cnt);
+    *T_out = T;
+    return 0;
+}
+static int forward_taped_impl(tnml_ctx* c, StreamCall& k, int64_t* ticket) {
+    if (!c || !ticket) return tnml_fail(c, "%s: null argument", k.who);
+    *ticket = 0;
+    TCK(images_given(c, k));
+    SiteGradPlan g{nullptr, false, 1, 0, 0};
+    TCK(streamed_refusals(c, k, "site gradients", &g.maxbond, true));
+    if (k.n > c->gradient_chunk)
+        return tnml_fail(c, "%s: n = %lld images, option gradient_chunk = %d: a tape belongs to one chunk (raise gradient_chunk, or use tnml_predict_* and tnml_backward_*)", k.who, (long long)k.n, c->gradient_chunk);
+    std::vector<long long> goff;
+    size_t elems = 0;
+    TCK(sitegrad_shape(c, k.who, goff, &elems));
+    if (k.n == 0) return 0;
+    if (k.dev) TCK(dev_enter(c, k));
+    TCK(sitegrad_prepare(c, k, g, goff, elems));
+    const bool f32 = c->gradient_dtype == TNML_GRADIENT_F32;
+    int T = 0;
+    TCK(f32 ? forward_taped_chunk<float>(c, k, g, &T) : forward_taped_chunk<double>(c, k, g, &T));
+    TapeTicket& t = c->tape;
+    t = TapeTicket();
+    t.id = c->next_ticket++; t.n = k.n; t.T = T; t.esz = f32 ? 4 : 8; t.cap = c->sg.cap; t.chunk = c->gradient_chunk; t.bytes_form = k.bytes_form();
+    t.maxbond = g.maxbond; t.rows = g.rows; t.nblocks = g.nblocks; t.elems = elems; t.w_epoch = c->w_epoch;
+    *ticket = t.id;
+    return 0;
+}
+int tnml_forward_taped_u8(tnml_ctx* c, int64_t n, const uint8_t* pixels, double* weights, int32_t* pred, int64_t* ticket) {
+    StreamCall k{"tnml_forward_taped_u8", n, pixels};
+    k.weights = weights; k.pred = pred;
+    return forward_taped_impl(c, k, ticket);
+}
+int tnml_forward_taped_phi(tnml_ctx* c, int64_t n, const double* phi, double* weights, int32_t* pred, int64_t* ticket) {
+    StreamCall k{"tnml_forward_taped_phi", n, nullptr, phi};
+    k.weights = weights; k.pred = pred;
+    return forward_taped_impl(c, k, ticket);
+}
+int tnml_forward_taped_dev(tnml_ctx* c, const tnml_dev_batch* b, const tnml_dev_out* o, int64_t* ticket) {
+    StreamCall k;
+    TCK(dev_call(c, "tnml_forward_taped_dev", b, o, 0, k));
+    return forward_taped_impl(c, k, ticket);
+}
+int tnml_tape_ticket(tnml_ctx* c, int64_t* ticket, int64_t* n) {
+    if (!c || !ticket || !n) return tnml_fail(c, "tnml_tape_ticket: null argument");
+    const bool live = tape_live(c, c->tape.id);
+    *ticket = live ? c->tape.id : 0; *n = live ? c->tape.n : 0;
+    return 0;
+}
+// the kernels of a backward from the tape in the element type E the forward ran in; k: coef, grad, dphi / dphi32 and the memory space
+template <typename E>
+static int backward_taped_kernels(tnml_ctx* c, const StreamCall& k) {
+    GradientWs& s = c->sg;
+    const TapeTicket& t = c->tape;
+    const int N = c->N, nl = c->nl(), cnt = (int)t.n;
+    SiteGradArgsT<E> a;
+    chain_args(c, s, t.bytes_form, a.ch);
+    a.ch.cnt = cnt;
+    a.rowoff = s.rowoff; a.tape = (E*)s.tape; a.tape2 = (E*)s.tape2;
+    a.lab = nullptr; a.target = c->target(); a.coef = s.coef; a.grad = s.grad; a.goff = s.goff; a.blk0 = s.blk0;
+    const size_t tape_elems = s.tape_rows * (size_t)s.cap;
+    HIPCK(c, hipMemcpyAsync(s.coef, k.coef, sizeof(double) * (size_t)cnt * nl, k.in(), c->stream));
+    if (k.grad) HIPCK(c, hipMemsetAsync(s.grad, 0, t.elems * sizeof(double), c->stream));
+    TCK(launch_site_outward<E>(c, a, t.maxbond, t.T, t.rows, tape_elems, t.nblocks, k.grad != nullptr));
+    if (k.want_dphi()) {
+        InputGradArgsT<E> ig;
+        ig.sites = sites<E>(s); ig.N = N; ig.cs = a.ch.cs; ig.nl = nl; ig.ld = s.cap; ig.cnt = cnt;
+        ig.rowoff = s.rowoff; ig.tape = (const E*)s.tape; ig.tape2 = (const E*)s.tape2; ig.coef = s.coef; ig.dphi = s.dphi;
+        if (k.dev) TCK(launch_input_grad<E>(c, ig, t.maxbond, t.T, t.rows, tape_elems, k.dphi, k.dphi ? nullptr : k.dphi32));
+        else {
+            TCK(launch_input_grad<E>(c, ig, t.maxbond, t.T, t.rows, tape_elems, s.dphiT));
+            HIPCK(c, hipMemcpyAsync(k.dphi, s.dphiT, sizeof(double) * (size_t)cnt * N * 2, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    s.last_cnt = cnt;
+    if (k.grad) HIPCK(c, hipMemcpyAsync(k.grad, s.grad, t.elems * sizeof(double), k.dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    SYNCK(c, c->stream);
+    return 0;
+}
+static int backward_taped_impl(tnml_ctx* c, int64_t ticket, StreamCall& k) {
+    const char* who = k.who;
+    if (!c) return tnml_fail(c, "%s: null argument", who);
+    if (!k.grad && !k.want_dphi()) return tnml_fail(c, "%s: grad and dphi are both NULL: the call would compute nothing", who);
+    if (k.dphi && k.dphi32) return tnml_fail(c, "%s: dphi and dphi32 are both given: at most one of the two", who);
+    if (c->pend_count > 0) return tnml_fail(c, "%s: a bond update is in flight (tnml_bond_update_end first)", who);
+    TCK(ho_locked(c, who));
+    if (!tape_live(c, ticket)) {
+        if (ticket > 0 && ticket < c->next_ticket)
+            return tnml_fail(c, "%s: ticket %lld is not live: its tape was taken by %s (tnml_forward_taped_* again, or tnml_backward_* on the images)", who, (long long)ticket,
+                             ticket == c->next_ticket - 1 && !c->tape.id ? c->tape_killer.c_str() : "a later tnml_forward_taped call, if nothing before it (the context keeps the name for its last ticket only)");
+        return tnml_fail(c, "%s: ticket %lld was never given out by this context", who, (long long)ticket);
+    }
+    if (!k.coef) return tnml_fail(c, "%s: null argument (coef)", who);
+    const TapeTicket& t = c->tape;
+    const int N = c->N, nl = c->nl();
+    const size_t un = (size_t)t.n;
+    k.n = t.n;
+    if (k.dev) {                                                // what dev_enter does for a batch: the checks of the arrays this call has
+        TCK(dev_check_args(c, who, {{"coef", k.coef, un * nl * sizeof(double), 8, false}, {"grad", k.grad, t.elems * sizeof(double), 8, true},
+                                    {"dphi", k.dphi, un * N * 2 * sizeof(double), 8, true}, {"dphi32", k.dphi32, un * N * 2 * sizeof(float), 4, true}}));
+        TCK(dev_entry_wait(c, who, k.stream));
+        if (!c->io_blk) TCK(dalloc(c, (void**)&c->io_blk, 3 * sizeof(unsigned long long)));
+        HIPCK(c, hipMemsetAsync(c->io_blk, 0xff, 3 * sizeof(unsigned long long), c->stream));
+        TCK(launch_check_batch(c, nullptr, k.coef, nullptr, t.n, nl, c->io_blk));
+        unsigned long long h[3];
+        HIPCK(c, hipMemcpyAsync(h, c->io_blk, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        SYNCK(c, c->stream);
+        if (h[1] != ~0ull) return tnml_fail(c, "%s: coefficient %d of image %lld is not finite", who, (int)(h[1] % nl), (long long)(h[1] / nl));
+    } else {
+        for (int64_t i = 0; i < t.n * nl; ++i)
+            if (!std::isfinite(k.coef[i])) return tnml_fail(c, "%s: coefficient %d of image %lld is not finite", who, (int)(i % nl), (long long)(i / nl));
+        HIPCK(c, hipSetDevice(c->cfg.device));
+    }
+    GradientWs& s = c->sg;                                      // the first call that asks for input gradients adds their two results, as sitegrad_workspace does
+    int rc = 0;
+    if (k.want_dphi() && !s.dphi) rc = ws_alloc(c, s, (void**)&s.dphi, (size_t)2 * N * s.cap * sizeof(double));
+    if (!rc && k.want_dphi() && !k.dev && !s.dphiT) rc = ws_alloc(c, s, (void**)&s.dphiT, (size_t)2 * N * s.cap * sizeof(double));
+    if (rc) { sitegrad_release(c); return rc; }
+    return t.esz == 4 ? backward_taped_kernels<float>(c, k) : backward_taped_kernels<double>(c, k);
+}
+int tnml_backward_taped(tnml_ctx* c, int64_t ticket, const double* coef, double* grad, double* dphi) {
+    StreamCall k{"tnml_backward_taped"};
+    k.coef = coef; k.grad = grad; k.dphi = dphi;
+    return backward_taped_impl(c, ticket, k);
+}
+int tnml_backward_taped_dev(tnml_ctx* c, int64_t ticket, const double* coef_dev, const tnml_dev_out* o, void* stream) {
+    StreamCall k{"tnml_backward_taped_dev"};
+    k.coef = coef_dev;
+    if (o) { k.grad = o->grad; k.dphi = o->dphi; k.dphi32 = o->dphi32; }
+    k.dev = true; k.stream = stream;
+    return backward_taped_impl(c, ticket, k);
 }
 // test entry: sizeof and the field offsets, in declaration order, of the two structs of this section as this library was compiled
 int tnml_abi_layout(const char* name, int64_t* sizes_out) {

@@ -33,11 +33,11 @@
 
 enum KClass {
     KC_FGEMM_FWD = 0, KC_FGEMM_SHIFT, KC_LABELDOT, KC_ZPRIME, KC_BGEMM, KC_SLABRED, KC_PACK, KC_VEC,
-    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_EVAL_TALLY, KC_SITE_RESP, KC_SITE_BWD, KC_SITE_GRAD, KC_STEP_NORM, KC_SITE_STEP, KC_INPUT_GRAD, KC_IO_CHECK, KC_COUNT
+    KC_SMALLGEMM, KC_SVD, KC_ALLREDUCE, KC_PUPDATE, KC_FWD_FUSED, KC_FWD_RES, KC_GRAD_QUAD, KC_CHAIN, KC_EVAL_TALLY, KC_SITE_RESP, KC_SITE_BWD, KC_SITE_GRAD, KC_STEP_NORM, KC_SITE_STEP, KC_INPUT_GRAD, KC_IO_CHECK, KC_FWD_TAPED, KC_SITE_OUT, KC_SITES_COPY, KC_COUNT
 };
 static const char* const kclass_names[KC_COUNT] = {
     "fgemm_fwd", "fgemm_shift", "labeldot", "zprime", "bgemm", "slab_reduce", "pack", "cg_vec",
-    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain", "eval_tally", "site_resp", "site_bwd", "site_grad", "step_norm", "site_step", "input_grad", "io_check"};
+    "small_gemm", "svd", "allreduce", "p_update", "fwd_fused", "fwd_res", "grad_quad", "chain", "eval_tally", "site_resp", "site_bwd", "site_grad", "step_norm", "site_step", "input_grad", "io_check", "fwd_taped", "site_out", "sites_copy"};
 
 // device accumulator block of tnml_evaluate_*: the part of tnml_eval_report that k_eval_tally (kernels_eval.hip) adds up
 struct EvalAcc {
@@ -173,6 +173,18 @@ struct GradientWs : StreamWs {                        // tnml_site_gradient_*, t
     double *tape = nullptr, *tape2 = nullptr; size_t tape_rows = 0;   // [cap / T][tape_rows][T] each: inward and outward vectors; grown when W has grown
     double *dphi = nullptr, *dphiT = nullptr;         // from the first call that asks for input gradients on: dphi of a chunk as the kernel leaves it [N][2][cap] and as the caller gets it [cap][N][2]
     std::vector<void**> own() { return ws_ptrs(&lab, &coef, &rowoff, &goff, &blk0, &grad, &tape, &tape2, &dphi, &dphiT); }
+};
+
+// The one tape a context may keep between tnml_forward_taped_* and tnml_backward_taped* (tnml.h, "backward from the forward's tape"): what the
+// forward ran with, so that the backward reads the two tapes' slices in the element order they were written in.  id 0: no live ticket
+struct TapeTicket {
+    int64_t id = 0, n = 0;             // the ticket the forward gave out; its images (one chunk)
+    int T = 0, esz = 8, cap = 0;       // tile width, bytes of a tape element and capacity of the workspace the forward ran with
+    int chunk = 0;                     // option gradient_chunk at the forward: any other value kills the ticket, whatever it rounds to
+    bool bytes_form = false;           // the staged images are bytes (block sums under the input map in force) -- SRC follows from it and the map
+    int maxbond = 1, rows = 0, nblocks = 0;   // of W at the forward: largest bond, rows of a tape slice, output blocks of k_site_grad
+    size_t elems = 0;                  // elements of the gradient
+    uint64_t w_epoch = 0;              // tnml_ctx::w_epoch at the forward
 };
 
 struct tnml_ctx {
@@ -364,6 +376,13 @@ struct tnml_ctx {
     double loss_beta = 1.;           // tnml_set_option_real "loss_beta": the inverse temperature of the softmax loss, logits beta W_l
     GradientWs sg;
     bool attr_inputgrad[2] = {};     // [fp32]: the LDS attribute of the k_input_grad instantiations is set
+    // the forward's tape kept for the backward (tnml_forward_taped_* / tnml_backward_taped*): at most one live ticket
+    bool attr_fwdtaped[2][2] = {}, attr_siteout[2][2] = {};   // [fp32][input map]: the LDS attribute of the k_forward_taped / k_site_outward instantiations is set
+    TapeTicket tape;                 // the live ticket (id 0: none)
+    int64_t next_ticket = 1;         // tickets are never given out twice
+    std::string tape_killer;         // the call that took the tape of the last ticket that died
+    uint64_t w_epoch = 0;            // advances with every write of W (w_written, tnml_host.h); a ticket whose epoch is another one is dead
+    const char* w_writer = "";       // the call that advanced it last
     // gradient steps on the device (tnml_site_step_u8 / tnml_site_step_phi, kernels_sitestep.hip): the optimiser state.  Allocated by the first
     // step for a method and the site shapes of W at that moment, counted in `bytes` and st_bytes, freed by tnml_site_step_reset and tnml_destroy;
     // no part of `sg`: a change of gradient_chunk and tnml_set_input_map leave it alone
@@ -381,6 +400,7 @@ struct tnml_ctx {
     // workspaces (io_release) and by tnml_destroy
     hipEvent_t io_ev = nullptr;                            // recorded on the caller's stream on entry; the context's stream waits for it (timing disabled)
     unsigned long long* io_blk = nullptr;                  // [3] the block of k_check_batch (kernels_iocheck.hip): 24 bytes, counted in `bytes`
+    struct SiteCopy* io_tab = nullptr;                     // [N] the table of k_sites_gather (tnml_set_sites_dev): 32 N bytes from its first call on, counted in `bytes`, released with the block
     // input map (tnml_set_input_map): geometry + host copy of the fp64 table; consulted by tnml_set_data_u8 and the *_u8 streamed calls only
     bool im_set = false;
     tnml_input_map im = {};          // geometry (table = nullptr)
@@ -675,6 +695,12 @@ typedef SiteGradArgsT<double> SiteGradArgs;
 // run_gemm false (tnml_backward_* without grad): k_site_backward alone
 template <typename E> int launch_site_gradient(tnml_ctx* c, SiteGradArgsT<E> a, int maxbond, int T, int rows, size_t tape_elems, int nblocks, bool run_gemm = true);
 
+// k_forward_taped (class fwd_taped): phase A of k_site_backward alone -- weights, pred and the inward tape; lab, coef, grad, goff, blk0 are not read
+template <typename E> int launch_forward_taped(tnml_ctx* c, SiteGradArgsT<E> a, int maxbond, int T, int rows, size_t tape_elems);
+// k_site_outward (class site_out): the seeds and outward walks of k_site_backward's coef mode from the inward tape a k_forward_taped launch
+// left, X and Y in two workgroups per tile; T is that launch's.  run_gemm: k_site_grad (class site_grad) behind it, as launch_site_gradient has it
+template <typename E> int launch_site_outward(tnml_ctx* c, SiteGradArgsT<E> a, int maxbond, int T, int rows, size_t tape_elems, int nblocks, bool run_gemm);
+
 // ---- kernels_inputgrad.hip: streamed input gradients, one bilinear form per site, feature component and image on the tapes of k_site_backward ----
 template <typename E> struct InputGradArgsT {
     const ChainSite<E>* sites;         // [N] device
@@ -696,6 +722,11 @@ template <typename E> int launch_input_grad(tnml_ctx* c, InputGradArgsT<E> a, in
 // ONE launch over labels [n], coef [n][nl] and which [n] (any may be null): blk[0..2], all ones before the launch, receive the smallest
 // offending flat index of each array (integer atomicMin); class io_check
 int launch_check_batch(tnml_ctx* c, const int* labels, const double* coef, const int* which, int64_t n, int nl, unsigned long long* blk);
+// one entry of the table of k_sites_gather: elems doubles from src to dst, by the workgroups from blk0 on (SITES_COPY_BLOCK doubles each)
+struct SiteCopy { const double* src; double* dst; long long elems; long long blk0; };
+#define SITES_COPY_BLOCK 2048
+// ONE launch that copies count site tensors (tab on the device, nblocks workgroups in all); class sites_copy
+int launch_sites_gather(tnml_ctx* c, const SiteCopy* tab, int count, long long nblocks);
 
 // ---- kernels_sitestep.hip: one optimiser step on W from the gradient tnml_site_gradient_*'s kernels left on the device ----
 #define STEP_NORM_BLOCK 65536      /* elements per block sum of the norm pass */

@@ -21,6 +21,7 @@ int tnml_mps_place(tnml_ctx* c, int j, int ML, int MR, int row0, int col0, int m
         return tnml_fail(c, "tnml_mps_place: block [%d,%d) x [%d,%d) leaves the %d x %d site %d", row0, row0 + ml, col0, col0 + mr, ML, MR, j);
     HIPCK(c, hipSetDevice(c->cfg.device));
     SiteT& s = c->W[j];
+    w_written(c, "tnml_mps_place");
     const int L = j == c->c0 ? TNML_NL : 1;
     if (!s.placed || s.ml != ML || s.mr != MR || s.L != L) {          // the first placement shapes and zeroes the site
         s.ml = ML; s.mr = MR; s.L = L; s.set = true; s.placed = true;
@@ -48,6 +49,7 @@ int tnml_mps_compress(tnml_ctx* c, double cutoff, int maxm, tnml_compress_report
     const long fb0 = c->svd_fallbacks;
     const int before = mps_maxbond(c);
     c->currb = -1; c->p_valid = false; c->sweep_start = false; c->plan = BondPlan();
+    w_written(c, "tnml_mps_compress");
     for (int j = 1; j <= N; ++j) c->W[j].placed = false;
     // pass 1, right to left: sites N..2 become right-orthonormal, nothing is discarded (cutoff 0, minm = maxm = the bond's dimension;
     // the split keeps min(that, rows, columns) columns, so a bond wider than its rank bound shrinks to it)
@@ -66,6 +68,7 @@ int tnml_mps_compress(tnml_ctx* c, double cutoff, int maxm, tnml_compress_report
         if (rep && rep->newm) rep->newm[b - 1] = m;
         if (rep && rep->truncerr) rep->truncerr[b - 1] = te;
     }
+    w_written(c, "tnml_mps_compress");                                 // (the splits above have said "a bond update")
     SYNCK(c, c->stream);
     if (rep) { rep->maxm_before = before; rep->maxm_after = mps_maxbond(c); rep->nbonds = N - 1; rep->truncerr_sum = tsum; rep->fallbacks = c->svd_fallbacks - fb0; }
     return 0;

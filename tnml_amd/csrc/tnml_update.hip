@@ -136,6 +136,7 @@ static void spec_rollback(tnml_ctx* c, PendingReport& pr) {
         SiteT& S = c->W[pr.undo[u].j];
         ((pr.undo[u].j == c->c0) ? c->spare_big : c->spare_small).push_back(S.a);
         S.a = pr.undo[u].old; S.ml = pr.undo[u].ml; S.mr = pr.undo[u].mr;
+        w_written(c, "a bond update");
     }
     pr.nundo = 0; pr.spec = false;
 }
@@ -314,6 +315,7 @@ static int heldout_step(tnml_ctx* c, const PendingReport& pr) {
         const SiteT& src = pr.ho_site[u];
         SiteT& dst = h->W[pr.b + u];
         dst.ml = src.ml; dst.mr = src.mr; dst.L = src.L; dst.set = true;
+        w_written(h, "a bond update of the training context");
         HIPCK(h, hipMemcpyAsync(dst.a, src.a, sizeof(double) * (size_t)src.ml * 2 * src.mr * src.L, hipMemcpyDeviceToDevice, h->stream));
     }
     HIPCK(h, hipEventRecord(s->ev_copied, h->stream));
@@ -357,6 +359,7 @@ int tnml_heldout_attach(tnml_ctx* c, tnml_ctx* h) {
         const SiteT& src = c->W[j];
         SiteT& dst = h->W[j];
         dst.ml = src.ml; dst.mr = src.mr; dst.L = src.L; dst.set = true;
+        w_written(h, "tnml_heldout_attach");
         if (hipMemcpyAsync(dst.a, src.a, sizeof(double) * (size_t)src.ml * 2 * src.mr * src.L, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
             rc = tnml_fail(h, "copy of site %d failed", j);
     }

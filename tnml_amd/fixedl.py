@@ -552,6 +552,69 @@ class TrainStates:
         self._note_chunk(n)
         return (grads, dphi, (w, pred)) if want_weights else (grads, dphi)
 
+    # -- backward from the forward's tape (tnml_forward_taped_* / tnml_backward_taped*)
+    def forward_taped(self, pixels=None, phi=None, dtype=None):
+        """predict() that keeps its tape (tnml_forward_taped_u8 / _phi / _dev): -> (weights[n, nl], pred[n], ticket).  Runs on the
+        gradient workspace under option gradient_dtype (dtype "f64" / "f32" sets it, as backward()'s), one chunk at most
+        (n <= gradient_chunk); weights and pred are bit for bit predict()'s under the matching predict_dtype.  ticket (> 0; 0 for
+        n = 0) is what backward_taped() takes, and lives until something else uses the gradient workspace or writes W."""
+        self._set_dtype("gradient_dtype", dtype)
+        t = C.c_int64(0)
+        if self._on_device(pixels, phi):
+            b, keep = self._dev_batch(pixels, phi)
+            w, pred, o = self._weights(b.n, True, dev=True)
+            self._ck(self._L.tnml_forward_taped_dev(self._h, C.byref(b), C.byref(o), C.byref(t)))
+            return w, pred, t.value
+        n, keep, (xp, _, _, _) = self._host_batch(pixels, phi)
+        w, pred, (wp, pp) = self._weights(n, True)
+        self._ck(self._entry("forward_taped", pixels)(self._h, n, xp, wp, pp, C.byref(t)))
+        return w, pred, t.value
+
+    def tape_ticket(self):
+        """tnml_tape_ticket: (the live ticket, its image count); (0, 0) when there is none"""
+        t, n = C.c_int64(0), C.c_int64(0)
+        self._ck(self._L.tnml_tape_ticket(self._h, C.byref(t), C.byref(n)))
+        return t.value, n.value
+
+    def backward_taped(self, ticket, coef, want_sites=True, want_inputs=True, inputs32=False):
+        """backward(coef=coef, ..) on the images of forward_taped()'s ticket, from its tape (tnml_backward_taped / _dev): ->
+        (grads | None, dphi | None), bit for bit backward()'s.  coef[n, nl]: a numpy array / CPU tensor (results as numpy arrays) or
+        a tensor on the context's device (results as device tensors; inputs32: dphi as float32, the fp64 result rounded once, what
+        backward() gives for a float32 phi) -- either serves a forward of either kind.  The ticket stays valid: another coef may follow."""
+        n = int(coef.shape[0])
+        if tuple(coef.shape) != (n, self.nl):
+            raise ValueError("coef must have shape [n, %d], got %s" % (self.nl, tuple(coef.shape)))
+        # the C call takes no n: it reads and writes the forward's image count.  A live ticket must therefore come with that many rows
+        # (a ticket that is not the live one is refused by the library before it touches any array)
+        live, n_live = self.tape_ticket()
+        if live == int(ticket) and n != n_live:
+            raise ValueError("coef has %d rows, the forward of ticket %d had %d images" % (n, live, n_live))
+        if self._on_device(coef):
+            where = torch.device("cuda", self.device)
+            cf = coef.to(torch.float64).contiguous()
+            o = _lib.DevOut()
+            grad = dphi = None
+            if want_sites:
+                grad = self._gradient_buffer(dev=True)
+                o.grad = grad.data_ptr()
+            if want_inputs:
+                f32 = bool(inputs32)
+                dphi = torch.empty((n, self.N, 2), dtype=torch.float32 if f32 else torch.float64, device=where)
+                if f32:
+                    o.dphi32 = dphi.data_ptr()
+                else:
+                    o.dphi = dphi.data_ptr()
+            self._ck(self._L.tnml_backward_taped_dev(self._h, int(ticket), cf.data_ptr(), C.byref(o), torch.cuda.current_stream(where).cuda_stream))
+            self._last_chunk = n or self._last_chunk
+            return (self._split_sites_dev(grad) if want_sites else None), dphi
+        cf = np.ascontiguousarray(coef, dtype=np.float64)
+        grad = self._gradient_buffer() if want_sites else None
+        dphi = np.zeros((n, self.N, 2)) if want_inputs else None
+        self._ck(self._L.tnml_backward_taped(self._h, int(ticket), _lib.dptr(cf), grad if grad is None else _lib.dptr(grad),
+                                             dphi if dphi is None else _lib.dptr(dphi)))
+        self._last_chunk = n or self._last_chunk
+        return (self._split_sites(grad) if want_sites else None), dphi
+
     def _note_chunk(self, n):
         """the size of the last chunk of a gradient or step call on n images (gradient_coef)"""
         if n > 0:
@@ -560,6 +623,10 @@ class TrainStates:
 
     def _gradient_chunk(self):
         return getattr(self, "_gchunk", _lib.GRADIENT_CHUNK_DEFAULT)
+
+    def gradient_chunk(self):
+        """option gradient_chunk as set_option() last set it on this object (the library's default before any)"""
+        return self._gradient_chunk()
 
     def gradient_coef(self, cnt=None):
         """test entry (tnml_site_gradient_coef): the coefficients [cnt, nl] of the last chunk of the last site_gradient() or
@@ -658,6 +725,32 @@ class TrainStates:
             return
         A = np.asarray(A, dtype=np.float64)
         self._ck(self._L.tnml_set_site(self._h, j, A.shape[0], A.shape[2], int(A.ndim == 4), _lib.dptr(_lib.flat(A))))
+
+    def set_sites(self, js, tensors):
+        """set_site() for many sites at once, in the shapes W has now.  Tensors on the context's device go up in ONE call
+        (tnml_set_sites_dev: one table upload, one copy launch, one synchronisation); a tensor that is not fp64 in
+        first-index-fastest strides is first brought into that layout on the device, as set_site() does.  Host arrays take
+        set_site() one by one."""
+        js, tensors = [int(j) for j in js], list(tensors)
+        if len(js) != len(tensors):
+            raise ValueError("set_sites: %d sites, %d tensors" % (len(js), len(tensors)))
+        if not js:
+            return
+        if not self._on_device(*tensors):
+            for j, A in zip(js, tensors):
+                self.set_site(j, A)
+            return
+        keep = []
+        for j, A in zip(js, tensors):
+            shape = tuple(A.shape)
+            if 1 <= j <= self.N and shape != self._site_shape(j):
+                raise ValueError("set_sites: site %d is %s in W, the tensor is %s (set_site() changes shapes)" % (j, self._site_shape(j), shape))
+            if A.dtype != torch.float64 or A.stride() != self._fstrides(shape):
+                A = torch.empty_strided(shape, self._fstrides(shape), dtype=torch.float64, device=A.device).copy_(A)
+            keep.append(A)
+        sites = (C.c_int32 * len(js))(*js)
+        ptrs = (C.c_void_p * len(js))(*[A.data_ptr() for A in keep])
+        self._ck(self._L.tnml_set_sites_dev(self._h, len(js), sites, ptrs, torch.cuda.current_stream(keep[0].device).cuda_stream))
 
     def get_site(self, j, device=False):
         """site j as a numpy array [ml, 2, mr(, 10)]; device=True: as a tensor on the context's device in first-index-fastest

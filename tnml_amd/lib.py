@@ -46,6 +46,8 @@ EXPORTS = [
     "tnml_backward_u8", "tnml_backward_phi",
     "tnml_predict_dev", "tnml_evaluate_dev", "tnml_response_dev", "tnml_backward_dev", "tnml_site_step_dev",
     "tnml_set_site_dev", "tnml_get_site_dev", "tnml_abi_layout",
+    "tnml_forward_taped_u8", "tnml_forward_taped_phi", "tnml_forward_taped_dev", "tnml_backward_taped", "tnml_backward_taped_dev",
+    "tnml_tape_ticket", "tnml_set_sites_dev",
 ]
 
 
@@ -200,6 +202,14 @@ def load():
     L.tnml_site_step_dev.argtypes = [vp, C.POINTER(DevBatch), C.POINTER(StepParams), C.POINTER(StepReport)]
     L.tnml_set_site_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.tnml_get_site_dev.argtypes = [vp, C.c_int, vp, vp]
+    i64p = C.POINTER(C.c_int64)
+    L.tnml_forward_taped_u8.argtypes = [vp, C.c_int64, C.POINTER(C.c_uint8), dp, C.POINTER(C.c_int32), i64p]
+    L.tnml_forward_taped_phi.argtypes = [vp, C.c_int64, dp, dp, C.POINTER(C.c_int32), i64p]
+    L.tnml_forward_taped_dev.argtypes = [vp, C.POINTER(DevBatch), C.POINTER(DevOut), i64p]
+    L.tnml_backward_taped.argtypes = [vp, C.c_int64, dp, dp, dp]
+    L.tnml_backward_taped_dev.argtypes = [vp, C.c_int64, vp, C.POINTER(DevOut), vp]
+    L.tnml_tape_ticket.argtypes = [vp, i64p, i64p]
+    L.tnml_set_sites_dev.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(vp), vp]
     L.tnml_abi_layout.argtypes = [C.c_char_p, C.POINTER(C.c_int64)]
     L.tnml_set_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
     L.tnml_get_input_map.argtypes = [vp, C.POINTER(InputMapStruct)]
